@@ -2,6 +2,7 @@
 """Headline benchmark: pipelined predict-and-recompute CG iterations/second on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s3|s2|s1|...] [--variant pipe_pr_cg|hs_cg|...]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
@@ -15,8 +16,10 @@ synthetic workload, inputs resident in HBM before the clock starts, no convergen
 The workload is fixed as N grows (strong scaling): S3 = the reference's ex2b banded
 model matrix at n = 1e7, 15 diagonals, ~150 M nonzeros, split into row blocks.
 
-Prints ONE JSON line on rank 0 (contract: see the task statement / DESIGN.md section 6).  At N = 1 the
-line also carries (all timed in this run, same K and W):
+Prints ONE JSON line on rank 0 (contract: DESIGN.md section 6).  A plain run sets up, warms up, times the K steps
+and prints the headline (`value`, `ms_per_step`, the schedule, the roofline of the timed launches); everything
+else below runs only with --full.  --dump-outputs DIR writes what the last timed step computed (dump_rows).
+With --full, at N = 1 the line also carries (all timed in this run, same K and W):
   value_general_csr            the same loop with the value dictionary off: the rate of an operator whose values
                                do not repeat (8 B per nonzero actually move) -- the transferable number
   roofline.plain_values        ... its launch time, bytes and fractions
@@ -24,6 +27,8 @@ line also carries (all timed in this run, same K and W):
                                1-rank communicator, and one rank's share of an 8-GPU run (S3/8 with a loopback halo)
   workloads                    BASELINE.json's other configurations: S1 (config 3), S2 at N=1 (config 4), the two
                                stand-ins for Queen_4147 (config 5), each with its plain-values twin where a dictionary applies
+  roofline.spmv, roofline.stream_ceiling, avg_launch_ms_sampled_after, cpu_baseline
+and at N > 1 the second, short leg on the RCCL schedule (roofline.rccl_schedule).
 """
 import argparse
 import json
@@ -112,6 +117,17 @@ PREWARM = 300      # untimed iterations before any clock starts: the chip's cloc
 SAMPLE_AFTER = 200  # launches AFTER the timed region with HIP events around every second one: a larger sample of the launch duration
 VARIANTS = ['pipe_pr_cg', 'hs_cg', 'pr_cg', 'pipe_pr_pcg', 'pipe_p_cg', 'cg_cg', 'gv_cg']
 FAMILY = {'pipe_pr_cg': 'pipe', 'hs_cg': 'hs', 'pr_cg': 'pr', 'pipe_pr_pcg': 'pipe', 'pipe_p_cg': 'pipe', 'cg_cg': 'cg_cg', 'gv_cg': 'gv'}
+DUMP_ROWS = 1 << 20  # --dump-outputs: rows of each vector written (8 MB in float64); all of them when n is smaller
+
+
+def dump_rows(n):
+    """Global row numbers whose entries --dump-outputs writes: every row up to DUMP_ROWS, else a fixed, seeded
+    sample of DUMP_ROWS rows in ascending order -- the same rows in every run of the same workload.  The files:
+    x.npy and r.npy (the iterate and the recursively updated residual after the last timed step, at these rows)
+    and scalars.npy (that step's five inner products: mu, delta, gamma, nu, rr of prcg.h)."""
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False)).astype(np.int64)
 
 
 def main():
@@ -123,6 +139,12 @@ def main():
                     help='s1 s2 s3 s4 s4b s3_8th s1_small s3_small; queen if QUEEN_4147_MTX names the MatrixMarket file')
     ap.add_argument('--variant', default='pipe_pr_cg', choices=VARIANTS,
                     help='pipe_pr_pcg = the pipelined variant with the Jacobi preconditioner (figure_gen.py:42-44)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps write what the last one computed as DIR/<name>.npy (float64; see dump_rows)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beyond the headline: CPU baseline, plain values, multi-rank schedule, other '
+                         'workloads, product rates, stream ceilings, sampled launches, the RCCL leg at N > 1 (the --no-* '
+                         'options below drop single legs of a --full run)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--force-comm', action='store_true',
                     help='N=1 only: the MAIN run uses a 1-rank RCCL communicator (multi-rank schedule)')
@@ -189,7 +211,7 @@ def main():
             partition.connect_peer_exchange(d, 0, lambda obj: [obj])
         return d
 
-    def timed_run(dev, variant, b, x0, inv_diag=None, K=None, sample_after=0):
+    def timed_run(dev, variant, b, x0, inv_diag=None, K=None, sample_after=0, after_timed=None):
         """(elapsed, host enqueue time, kernel timings, residual finite, error).  A library error (a one-launch
         iteration of a communicator session that waited longer than its bound for the reduction) is RETURNED, not
         raised: every rank must reach the barriers below, and the decision what to do next is taken collectively.
@@ -197,7 +219,9 @@ def main():
         warm-up and the K timed iterations run on the first W + K iterates of the solve -- a finite state whatever the
         operator's conditioning (round 3 timed one stand-in 500 iterations in, after CG had converged to an exact zero).
         sample_after > 0: that many further launches after the timed region with HIP events around every second one
-        (timings()['sampled_after_ms']): a larger sample of the launch duration than the timed region allows itself."""
+        (timings()['sampled_after_ms']): a larger sample of the launch duration than the timed region allows itself.
+        after_timed(dev, k): called once the timed region has ended without error, before any further launch, with the
+        iteration count k = W + K of the state it leaves."""
         K = K_MAIN if K is None else K
         err = None
         try:
@@ -235,6 +259,8 @@ def main():
             return elapsed, t_enq, None, False, err
         finite = bool(np.isfinite(dev.get_scalars(W + K)[L.S_NU]))
         tim = dev.timings()
+        if after_timed is not None:
+            after_timed(dev, W + K)
         if sample_after > 0:
             try:
                 dev.set_profiling(2)
@@ -328,6 +354,19 @@ def main():
     variant = VAR[args.variant]
     inv_diag = (1.0 / A_rows.tocsr()[:, lo:hi].diagonal()) if args.variant == 'pipe_pr_pcg' else None
 
+    outputs = {}
+
+    def capture(d, k):
+        """--dump-outputs: what a caller of the timed path receives after its last step, at the rows of dump_rows
+        (each rank contributes the rows of its block, in rank order = row order)"""
+        rows = dump_rows(n)
+        mine = rows[(rows >= lo) & (rows < hi)] - lo
+        parts = comm.allgather_obj({v: d.get_vector(v)[mine] for v in ('x', 'r')})
+        for v in ('x', 'r'):
+            outputs[v] = np.concatenate([p[v] for p in parts])
+        outputs['scalars'] = d.get_scalars(k)[:5]
+
+    keep = capture if args.dump_outputs else None
     fallback = None
     run_err = None
     if world > 1 and args.variant.startswith('pipe_'):
@@ -335,7 +374,9 @@ def main():
         # is timed (scaling.one_launch_self_check): on disagreement every rank runs the timed region on the RCCL schedule
         run_err = scaling.one_launch_self_check(op, variant, b, x0, inv_diag)
     if run_err is None:
-        elapsed, t_enq, tim, finite, run_err = timed_run(dev, variant, b, x0, inv_diag, sample_after=SAMPLE_AFTER if world == 1 else 0)
+        elapsed, t_enq, tim, finite, run_err = timed_run(dev, variant, b, x0, inv_diag,
+                                                         sample_after=SAMPLE_AFTER if world == 1 and args.full else 0,
+                                                         after_timed=keep)
     if run_err is not None:
         # the one-launch schedule of a multi-rank session could not be kept fed on this node (its waits are
         # bounded and reported): every rank rebuilds its operator with the RCCL two-kernel schedule and the run is repeated
@@ -346,11 +387,15 @@ def main():
         else:
             op = scaling.RowBlockOperator(comm, A_rows, device=local_rank, knobs={'PRCG_FUSED_COMM': '0', 'PRCG_PEER': '0'})
             dev = op.dev
-        elapsed, t_enq, tim, finite, run_err = timed_run(dev, variant, b, x0, inv_diag)
+        elapsed, t_enq, tim, finite, run_err = timed_run(dev, variant, b, x0, inv_diag, after_timed=keep)
         if run_err is not None:
             raise RuntimeError(run_err)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, f'{name}.npy'), np.ascontiguousarray(a, dtype=np.float64))
     sched = dev.schedule()
-    spmv = product_rates(dev, sched, n, nnz_total) if world == 1 else None
+    spmv = product_rates(dev, sched, n, nnz_total) if world == 1 and args.full else None
 
     rccl_leg = None
 
@@ -358,7 +403,7 @@ def main():
     # that path too, same matrix, value dictionary off.  This leg IS what SURVEY.md 8d's algorithmic bytes
     # (12 B per nonzero) describe up to the narrower column stream.
     plain = None
-    if world == 1 and not args.force_comm and sched['value_dict'] and not args.no_plain_values:
+    if args.full and world == 1 and not args.force_comm and sched['value_dict'] and not args.no_plain_values:
         dev2 = DeviceCSR(A_rows.tocsr(), device=local_rank, knobs={'PRCG_VALDICT': '0'})
         e2, _, tim2, fin2, _err2 = timed_run(dev2, variant, b, x0, inv_diag, sample_after=SAMPLE_AFTER)
         sched2 = dev2.schedule()
@@ -369,7 +414,7 @@ def main():
     # communicator; (b) one rank's share of an 8-GPU run: one eighth of S3 with a loopback halo (boundary tiles, ghost
     # rows, the whole exchange chain) beside the plain one-launch schedule on the same slice.
     multi = None
-    if world == 1 and not args.force_comm and not args.no_multi_rank_leg and args.variant.startswith('pipe_'):
+    if args.full and world == 1 and not args.force_comm and not args.no_multi_rank_leg and args.variant.startswith('pipe_'):
         def comm_leg(A, halo, bb, xx0, dd, knobs=None):
             d3 = one_rank_comm_device(A, halo, knobs)
             e3, q3, tim3, fin3, err3 = timed_run(d3, variant, bb, xx0, dd, K_LEG)
@@ -441,7 +486,7 @@ def main():
 
     # BASELINE.json's other configurations on this GPU (configs 3, 4 at N=1, 5 through its stand-ins)
     others = None
-    if world == 1 and not args.force_comm and not args.no_workloads and args.workload == 's3' and args.variant == 'pipe_pr_cg':
+    if args.full and world == 1 and not args.force_comm and not args.no_workloads and args.workload == 's3' and args.variant == 'pipe_pr_cg':
         others = {}
         for name, cfg in (('s1', 'BASELINE config 3'), ('s2', 'BASELINE config 4 at N=1'),
                           ('s4b', "BASELINE config 5, FEM-like stand-in at Queen_4147's size (uniform 3 dof x 27-point coupling)"),
@@ -539,7 +584,7 @@ def main():
         loop on the RCCL schedule (update kernel + two-vector SpMM, halo and the single all-reduce on side streams: the GPU form of
         scaling_experiments_petsc/cg_impls/pipeprcg.c:154-173), a short second leg.  Runs LAST, behind a watchdog on rank 0: if it has
         not finished after 120 s the line is written without it -- a second schedule must never cost the run its first number."""
-        if not (world > 1 and args.variant.startswith('pipe_') and fallback is None and sched.get('peer') and not args.no_rccl_leg):
+        if not (args.full and world > 1 and args.variant.startswith('pipe_') and fallback is None and sched.get('peer') and not args.no_rccl_leg):
             return None
         try:
             op2 = scaling.RowBlockOperator(comm, A_rows, device=local_rank, knobs={'PRCG_FUSED_COMM': '0', 'PRCG_PEER': '0'})
@@ -589,7 +634,7 @@ def main():
                                       'north_star\'s "effective" bandwidth; exceeds the peak when the stream is compressed',
                               'bytes_per_launch': kbytes, 'GBps': kbytes / ms * 1e-6 if ms > 0 else 0.0,
                               'frac_of_peak': kbytes / ms * 1e-6 / HBM_PEAK_GBS if ms > 0 else 0.0}}
-        if world == 1:
+        if world == 1 and args.full:
             # "also report a measured stream ceiling" -- in this run, on this GPU: the one-launch iteration's own vector mix
             # (per row 2 x 16 B read, 2 x 16 B written: all the dictionary kernel moves besides 15 MB of operator) over this workload's n
             # rows, with the stores the kernel uses; and a pure 16-byte read over 2 GB (what bounds the plain-value / sliced-row streams)
@@ -667,7 +712,7 @@ def main():
         }
         if others:
             out['workloads'] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(A_rows.tocsr(), b, x0, FAMILY[args.variant], args.cpu_seconds)
         else:
             out['cpu_baseline'] = None

@@ -761,14 +761,14 @@ def test_sweep_table_operator_in_a_communicator_session():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('world,workload', [(2, 's3_8th'), (3, 's2_8th'), (4, 's3')])
-def test_bench_launched_as_the_driver_does_with_processes_sharing_the_gpu(world, workload):
+def test_bench_launched_as_the_driver_does_with_processes_sharing_the_gpu(world, workload, tmp_path):
     """The driver's N > 1 launch, rehearsed on ONE GPU: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`,
     one PROCESS per rank, gloo control plane, every rank on device 0 (PRCG_BENCH_DEVICE) and the collectives of the set-up
     through tests/transport/libprocs_ccl.so (PRCG_RCCL_LIB; RCCL refuses ranks that share a device).  What runs is the
     product's N > 1 path end to end: row blocks, halo plan over gloo, exchange buffers mapped ACROSS PROCESSES with hipIpc,
     the self-check of the one-launch schedule against the two-kernel schedule, the timed loop in which every rank's
     launches wait in-kernel for the other processes' launches, max-over-ranks timing, the second leg on the RCCL side-stream
-    schedule, one JSON line from rank 0."""
+    schedule, one JSON line from rank 0, and the outputs of the last timed step gathered from every rank (--dump-outputs)."""
     import json
     env = dict(os.environ)
     env.update({'MASTER_ADDR': '127.0.0.1', 'OMP_NUM_THREADS': '1', 'HSA_ENABLE_IPC_MODE_LEGACY': '0', 'PRCG_BENCH_DEVICE': '0',
@@ -777,7 +777,7 @@ def test_bench_launched_as_the_driver_does_with_processes_sharing_the_gpu(world,
                 'PRCG_DEFER_GRID_PER_CU': '1'})
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={world}', '--master-addr', '127.0.0.1',
            '--master-port', str(free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', '60', '--warmup', '10',
-           '--workload', workload, '--no-cpu-baseline']
+           '--workload', workload, '--no-cpu-baseline', '--full', '--dump-outputs', str(tmp_path / 'out')]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -794,6 +794,13 @@ def test_bench_launched_as_the_driver_does_with_processes_sharing_the_gpu(world,
     assert leg and leg.get('rccl_ranks') == world and not leg.get('error') and leg['value'] > 1 and leg['residual_finite'], leg
     assert d['config']['rccl_ranks'] == world
     print(f"   RCCL side-stream schedule, same run: {leg['value']:.0f} it/s (merged exchange {leg['merged_exchange']})")
+    # the last timed step's outputs: every rank's rows of the sample, gathered on rank 0
+    sys.path.insert(0, ROOT)
+    import bench
+    rows = bench.dump_rows(d['config']['n'])
+    x, r, sc = (np.load(tmp_path / 'out' / f'{name}.npy') for name in ('x', 'r', 'scalars'))
+    assert x.shape == r.shape == rows.shape and sc.shape == (5,) and x.dtype == np.float64
+    assert np.all(np.isfinite(x)) and np.all(np.isfinite(r)) and np.all(np.isfinite(sc)) and np.linalg.norm(x) > 0
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/profile_round.sh <tag> [legs]     (on the GPU box, from the repo root; legs default: all)
 # The evidence behind bench.py's roofline object, written to gpurun_out/prof_<tag>/ :
-#   bench.json                   the default bench line (no profiler)
+#   bench.json                   the --full bench line (no profiler)
 #   <leg>_bench_under_rocprof.json / <leg>_kernel_stats.csv    the leg's bench command under rocprofv3 --kernel-trace --stats
 #   <leg>_pmc.json               per-kernel counter means (tools/pmc.sh: one pass per counter group, never combined with tracing)
 #   traffic.json                 HBM bytes per launch of the dominant kernel of every leg, stamped with the kernel-source hash
@@ -13,7 +13,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 cd $root
-timeout -k 10 900 python3 bench.py > $out/bench.json 2> $out/bench.err || exit 1
+timeout -k 10 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
 targs=""
 for leg in $legs; do
   wl=${leg%plain}; enc=dict; envs=""
