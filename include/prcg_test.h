@@ -136,7 +136,7 @@ int prcg_plan_gather(int rank, int doubles_per_table, const double* tables, int 
 /* Diagnostic (tests): how the resident operator is laid out for the one-launch iteration, i.e. everything the summation
  * order of its inner products depends on.  out[0..8) = {1 if window operator, window geometry id, rows per window tile,
  * number of tiles T, workgroups of the last one-launch iteration (0: none yet), waves per workgroup of that launch,
- * interior tiles, (1 if XCD-chunked tile order) | (waves a sweep table assumes) << 8}, then T pairs (first row, end row) in table order.  Returns the number of int64 written, -needed
+ * interior tiles, (waves a sweep table assumes) << 8 -- bit 0 is always 0 (it marked the retired XCD-chunked tile order)}, then T pairs (first row, end row) in table order.  Returns the number of int64 written, -needed
  * if capacity is too small, -1 on a bad argument.  tests/device_order.py rebuilds the launch's reduction tree from it. */
 int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity);
 /* Capacity rule of every vector a matrix-product launch reads (window pages are whole 64-column blocks, the narrow

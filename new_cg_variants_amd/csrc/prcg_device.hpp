@@ -93,71 +93,6 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NQ], double* pa
     }
 }
 
-// Same, plus: the block that finishes LAST sums all block partials in a fixed order and
-// writes the final values -- no separate reduction launch.  Which block is last varies
-// from run to run, the order of the summation does not, so the result is reproducible.
-// Hand-off protocol (cdna_hip_programming.md Guideline 16, counter form): every block
-// publishes its partials with plain stores -> s_waitcnt vmcnt(0) -> barrier -> one lane:
-// agent-scope release fence, wait, relaxed agent-scope ticket; the block that draws the
-// last ticket: agent-scope acquire fence, wait, barrier, plain loads.  Nobody spins.
-template <int NQ>
-__device__ __forceinline__ void block_reduce_store_final(double (&acc)[NQ], double* partials, unsigned* ticket,
-                                                         double* __restrict__ final_out) {
-    __shared__ double red[kWaves][NQ];
-    __shared__ int s_last;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const double v = wave_sum(acc[q]);
-        if (lane == 0) red[wv][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NQ) {
-        double v = red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v += red[w][threadIdx.x];
-        partials[(size_t)blockIdx.x * kPartialStride + threadIdx.x] = v;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (tk == gridDim.x - 1);
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // ---- last block: thread t sums partials t, t+256, ...; butterfly; waves in order ----
-    double tot[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) tot[q] = 0.0;
-    const int nparts = gridDim.x;
-    for (int j = threadIdx.x; j < nparts; j += kBlock) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) tot[q] += partials[(size_t)j * kPartialStride + q];
-    }
-    __syncthreads();   // red[] is reused
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const double v = wave_sum(tot[q]);
-        if (lane == 0) red[wv][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NQ) {
-        double v = red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v += red[w][threadIdx.x];
-        final_out[threadIdx.x] = v;
-    }
-    if (threadIdx.x == 0) *ticket = 0u;   // ready for the next launch (kernel boundary orders it)
-}
-
 // Every block of a launch sums the block partials the PREVIOUS launch left (slots slot0 .. slot0 + NQ) itself, in
 // the order of k_reduce_final (a 256-thread tree: thread v rows v, v + 256, ...; butterfly over each 64 lanes; the
 // four wave sums in order) whatever the block's own size: a block of NWAVES < 4 waves lets each thread play

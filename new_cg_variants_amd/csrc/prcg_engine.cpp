@@ -116,7 +116,7 @@ struct prcg_handle {
     bool want_vdict = true;              // PRCG_VALDICT=0 turns it off
     int nt_int = 0, nt_bnd = 0;          // interior tiles first, then boundary tiles
     int steps = kDefaultTileSteps;       // tile size the table was planned for
-    TileKnobs kn;                        // PRCG_GRID_PER_CU, PRCG_TILE_ORDER
+    TileKnobs kn;                        // PRCG_GRID_PER_CU
     int steps_override = 0;              // PRCG_TILE_STEPS
     // ---- window tiles (row-per-lane kernels, prcg_win.hip): all tiles of the operator or none ----
     bool want_win = true;                // PRCG_WIN=0 turns them off
@@ -152,25 +152,16 @@ struct prcg_handle {
     int sell_nt_opt = -1;                // PRCG_SELL_NT=0|1 overrides
     int place_k = 8;                     // PRCG_PLACE=k: the pipelined session's vectors are placed k times and the fastest placement is kept (place_session_vectors); 0 / 1: off
     void* placed_xp = nullptr;           // ... the (x,p) allocation that has been through it
-    int sell_gb = 0, sell_defer = 0;     // PRCG_SELL_GB=0|4|8, PRCG_SELL_DEFER=0|1: request orders inside the sliced-row kernels (prcg_sell.hip)
     int sell_sigma = 0, sell_planes = 0, sell_run = 1; // what the planner chose
     bool sell_runs_opt = true;           // PRCG_SELL_RUNS=0: a column code per nonzero even where the rows are runs of three
     int64_t sell_stride = 0;
     bool want_big = true;                // PRCG_WIN_BIG=0: short launches keep the small workgroups too
-    int win_order = 0;                   // 1: XCD-chunked tile order of the window launches (opt-in: PRCG_WIN_ORDER=1)
-    int win_order_override = -1;
     int win_period = 0;                  // tiles t and t + win_period read the same stream images (0: no such period found)
     bool want_share = true;              // PRCG_WIN_SHARE=0: every window tile keeps its own stream images
     int64_t win_stream_bytes = 0;        // bytes of the encoded operator a product must read at least once (window form)
-    bool side_stream = false;            // one GPU: reduce the partials beside the SpMM (PRCG_SIDE_STREAM=1);
-                                         // measured slower than in-order (cross-stream event waits ~15 us/iter)
     DevBuf tmp_ext;                      // 2*(n+g) doubles: SpMV input scratch with ghost room
     DevBuf t1;                           // 2*n doubles: SpMV output scratch
     DevBuf partA, partB;                 // block partials: update kernels / SpMV epilogues
-    DevBuf ticket;                       // arrival counter of the fused final reduction
-    bool fused_final = false;            // PRCG_FUSED_FINAL=1: last block of the update kernel reduces the
-                                         // partials (correct, but its per-block release fence writes back every
-                                         // XCD L2: update 140 -> 250 us at S3; kept as an experiment)
 
     // ---- halo plan ----
     int n_peers = 0;
@@ -209,13 +200,6 @@ struct prcg_handle {
     bool red_pending = false;    // the communication chain of the previous iteration is outstanding ...
     hipEvent_t red_event = nullptr;   // ... and this event marks its end
     bool want_fused = true;      // PRCG_FUSED=0 turns it off
-    bool medium = false;         // this session runs the few-workgroup solver (prcg_medium.hip): mid-size systems
-    bool want_medium = false;    // PRCG_MEDIUM=1 turns it on (opt-in: correct, but at ~5 us per grid-wide hand-off -- two per iteration -- it does not
-                                 // yet beat one launch per iteration, 8-12 us: profiles/r04_sweeps.md)
-    bool medium_ok = false;      // the operator has a medium plan (prcg_set_csr)
-    int med_groups = 0, med_window = 0;
-    unsigned long long med_seq = 0;
-    DevBuf m_val, m_col, m_slices, m_rows, m_wave_first, m_window, m_own, m_exch, m_slots, m_err;
     bool small = false;          // this session runs the one-workgroup solver (n <= 4096)
     int small_mode = 0;          // 0: matrix in LDS, 1: matrix in registers
     bool small_hs = false;       // Hestenes-Stiefel session of a small system: the whole solve in one launch of one workgroup
@@ -287,11 +271,11 @@ struct prcg_handle {
                       b16 ? static_cast<const unsigned short*>(wcw.p) : nullptr,
                       win_vd ? static_cast<const unsigned char*>(wvidx.p) : nullptr,
                       win_vd ? static_cast<const double*>(wvdict.p) : nullptr,
-                      static_cast<const unsigned short*>(wrel.p), static_cast<const PatRec*>(wpat.p), sweep_waves, sweep_tiles, want_big ? 1 : 0, win_order,
+                      static_cast<const unsigned short*>(wrel.p), static_cast<const PatRec*>(wpat.p), sweep_waves, sweep_tiles, want_big ? 1 : 0,
                       win_period};
     }
     const WTile* wtile_ptr(int first = 0) const { return static_cast<const WTile*>(wtiles.p) + first; }
-    SellDev sdev() const { return SellDev{indptr.i(), val_sell(), static_cast<const unsigned short*>(scol.p), static_cast<const int*>(srows.p), sell_nt, sell_run, sell_gb, sell_defer, sell_window > 0 ? static_cast<const int*>(sgran.p) : nullptr, sell_window}; }
+    SellDev sdev() const { return SellDev{indptr.i(), val_sell(), static_cast<const unsigned short*>(scol.p), static_cast<const int*>(srows.p), sell_nt, sell_run, sell_window > 0 ? static_cast<const int*>(sgran.p) : nullptr, sell_window}; }
     const double* val_sell() const { return static_cast<const double*>(sval.p); }
     const void* sslice_ptr(int first = 0) const { return static_cast<const char*>(sslices.p) + (size_t)first * 32; }
     // any communicator -- even a 1-rank one -- selects the two-stream schedule
@@ -497,7 +481,7 @@ int allreduce(prcg_t* h, double* buf, int count, hipStream_t st) {
 // the ranks all-gather their (peer, offset, count) send tables once.
 int plan_gather(prcg_t* h) {
     h->gather = false;
-    if (!h->multi() || !h->want_gather || h->fused_final) return PRCG_OK;
+    if (!h->multi() || !h->want_gather) return PRCG_OK;
     if (h->gather_planned) { h->gather = h->gather_ok; return PRCG_OK; }
     h->gather_planned = true;
     h->gather_ok = false;
@@ -637,9 +621,9 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
     const int mask = pipe_recompute(h->variant) ? 3 : 2;
     bool on = false;
     int rc;
-    if (!h->side_stream && !h->multi()) {
+    if (!h->multi()) {
         // everything in order on one stream
-        if (!h->fused_final) launch_reduce_final(h->sc, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5);
+        launch_reduce_final(h->sc, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5);
         if (profile) prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
         LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, in_ext, h->wu.d(), mask));
         if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
@@ -684,7 +668,7 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
         HIPCHK(h, hipEventRecord(h->e_halo, hs));
     }
     // block partials -> 5 doubles -> the one all-reduce
-    if (!h->fused_final) launch_reduce_final(h->sm, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5);
+    launch_reduce_final(h->sm, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5);
     if ((rc = allreduce(h, dots_at(h, k), 5, h->sm))) return rc;
     HIPCHK(h, hipEventRecord(h->e_red, h->sm));
 
@@ -740,8 +724,6 @@ PipeUpdateArgs pipe_args(prcg_t* h, int k) {
     a.dots_prev = k > 0 ? dots_at(h, k - 1) : dots_at(h, 0);
     a.coef_out = coef_at(h, k);
     a.partials = h->partA.d();
-    a.final_out = h->fused_final ? dots_at(h, k) : nullptr;
-    a.ticket = static_cast<unsigned*>(h->ticket.p);
     a.meurant = meurant(h->variant);
     a.recompute_w = pipe_recompute(h->variant);
     return a;
@@ -1294,26 +1276,21 @@ bool apply_option(prcg_t* h, const char* key, const char* val) {
     if (!key || !val) return false;
     const std::string k(key);
     const long v = atol(val);
-    if (k == "PRCG_SIDE_STREAM") h->side_stream = v != 0;
-    else if (k == "PRCG_FUSED_FINAL") h->fused_final = v != 0;
-    else if (k == "PRCG_FUSED") h->want_fused = v != 0;
+    if (k == "PRCG_FUSED") h->want_fused = v != 0;
     else if (k == "PRCG_WIN_SHARE") h->want_share = v != 0;
     else if (k == "PRCG_SMALL") h->want_small = v != 0;
-    else if (k == "PRCG_MEDIUM") h->want_medium = v != 0;
     else if (k == "PRCG_COL16") h->want_c16 = v != 0;
     else if (k == "PRCG_COL8") h->want_c8 = v != 0;
     else if (k == "PRCG_VALDICT") h->want_vdict = v != 0;
     else if (k == "PRCG_GATHER") h->want_gather = v != 0;
     else if (k == "PRCG_GATHER_MAX_BYTES") { if (v >= 64) h->gather_max_bytes = v; }
     else if (k == "PRCG_GRID_PER_CU") h->kn.per_cu = (v >= 1 && v <= 16) ? (int)v : 0;
-    else if (k == "PRCG_TILE_ORDER") h->kn.chunked = (val[0] == 'c') ? 1 : 0;
     else if (k == "PRCG_TILE_STEPS") h->steps_override = (v == 1 || v == 2 || v == 4) ? (int)v : 0;
     else if (k == "PRCG_WIN") h->want_win = v != 0;
     else if (k == "PRCG_FUSED_COMM") { h->want_fused_comm = v != 0; h->want_fused_comm_rccl = v != 0; }
     else if (k == "PRCG_PEER") h->want_peer = v != 0;
     else if (k == "PRCG_SELL") h->want_sell = v != 0;
     else if (k == "PRCG_CG_ONE") h->want_cg_one = v != 0;
-    else if (k == "PRCG_WIN_ORDER") h->win_order_override = v != 0;
     else if (k == "PRCG_WIN_BIG") h->want_big = v != 0;
     else if (k == "PRCG_WIN_PAT") h->want_pat = v != 0;
     else if (k == "PRCG_WIN_SWEEP") h->want_sweep = (v >= 0 && v <= 2) ? (int)v : 1;
@@ -1326,8 +1303,6 @@ bool apply_option(prcg_t* h, const char* key, const char* val) {
     else if (k == "PRCG_SELL_MAX_OVERHEAD_PCT") h->sell_overhead_opt = (v >= 100 && v <= 800) ? (double)v / 100.0 : 0.0;
     else if (k == "PRCG_PR_PACK") h->want_pr_pack = v != 0 ? 1 : 0;
     else if (k == "PRCG_PLACE") h->place_k = (v >= 0 && v <= 8) ? (int)v : 0;
-    else if (k == "PRCG_SELL_GB") h->sell_gb = (v == 4 || v == 8) ? (int)v : 0;
-    else if (k == "PRCG_SELL_DEFER") h->sell_defer = v != 0;
     else if (k == "PRCG_SELL_NT") { h->sell_nt_opt = v != 0; h->sell_nt = v != 0; }
     else if (k == "PRCG_STREAM_STORES") h->stream_override = v != 0;
     else if (k == "PRCG_EXT_SIGNAL") h->ext_signal = v != 0;
@@ -1339,10 +1314,10 @@ bool apply_option(prcg_t* h, const char* key, const char* val) {
     else return false;
     return true;
 }
-const char* const kOptionKeys[] = {"PRCG_SIDE_STREAM", "PRCG_FUSED_FINAL", "PRCG_FUSED", "PRCG_SMALL", "PRCG_MEDIUM", "PRCG_COL16", "PRCG_COL8",
-                                   "PRCG_VALDICT", "PRCG_GATHER", "PRCG_GATHER_MAX_BYTES", "PRCG_GRID_PER_CU", "PRCG_TILE_ORDER",
+const char* const kOptionKeys[] = {"PRCG_FUSED", "PRCG_SMALL", "PRCG_COL16", "PRCG_COL8",
+                                   "PRCG_VALDICT", "PRCG_GATHER", "PRCG_GATHER_MAX_BYTES", "PRCG_GRID_PER_CU",
                                    "PRCG_TILE_STEPS", "PRCG_WIN", "PRCG_WIN_GRID_PER_CU", "PRCG_WIN_MAX_MEAN", "PRCG_FUSED_COMM", "PRCG_WIN_ROWS", "PRCG_EXT_SIGNAL", "PRCG_DEFER_GRID_PER_CU",
-                                   "PRCG_WIN_SHARE", "PRCG_DEBUG_SHORT_SOURCES", "PRCG_PEER", "PRCG_STREAM_STORES", "PRCG_SELL", "PRCG_SELL_GRID_PER_CU", "PRCG_SELL_SIGMA", "PRCG_SELL_PLANES", "PRCG_PLACE", "PRCG_SELL_NT", "PRCG_SELL_GB", "PRCG_SELL_DEFER", "PRCG_SELL_RUNS", "PRCG_SELL_WINDOW", "PRCG_SELL_MAX_OVERHEAD_PCT", "PRCG_PR_PACK", "PRCG_CG_ONE", "PRCG_WIN_ORDER", "PRCG_WIN_BIG", "PRCG_WIN_PAT", "PRCG_WIN_SWEEP", "PRCG_SWEEP_WAVES"};
+                                   "PRCG_WIN_SHARE", "PRCG_DEBUG_SHORT_SOURCES", "PRCG_PEER", "PRCG_STREAM_STORES", "PRCG_SELL", "PRCG_SELL_GRID_PER_CU", "PRCG_SELL_SIGMA", "PRCG_SELL_PLANES", "PRCG_PLACE", "PRCG_SELL_NT", "PRCG_SELL_RUNS", "PRCG_SELL_WINDOW", "PRCG_SELL_MAX_OVERHEAD_PCT", "PRCG_PR_PACK", "PRCG_CG_ONE", "PRCG_WIN_BIG", "PRCG_WIN_PAT", "PRCG_WIN_SWEEP", "PRCG_SWEEP_WAVES"};
 
 int h2d(prcg_t* h, double* dst, const double* src, int64_t count) {
     HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyHostToDevice, h->sc));
@@ -1829,33 +1804,6 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const 
         h->sell_sigma = sp.sigma; h->sell_planes = sp.planes; h->sell_stride = sp.stride_rows; h->sell_run = sp.run;
         sp = SellPlan{};
     }
-    // mid-size systems (no ghosts, at most 131,072 rows): the plan of the few-workgroup solver, used by pipelined sessions
-    // that record nothing but the recurrence residual (prcg_solve_begin decides)
-    h->medium_ok = false;
-    if (h->want_medium && n_ghost == 0 && n_rows >= 256 && n_rows <= (int64_t)kMedMaxGroups * 16 * kMedSlices * 64 && nnz <= (int64_t)1 << 23) {
-        MediumPlan mp;
-        if (plan_medium(n_rows, ip.data(), indices, data, kMedMaxGroups, kMedSlices, kMedMaxWindow, mp)) {
-            HIPCHK(h, h->m_val.alloc(mp.sell.val.size() * sizeof(double), false));
-            HIPCHK(h, hipMemcpy(h->m_val.p, mp.sell.val.data(), mp.sell.val.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_col.alloc(mp.sell.col.size() * sizeof(uint16_t), false));
-            HIPCHK(h, hipMemcpy(h->m_col.p, mp.sell.col.data(), mp.sell.col.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_slices.alloc((mp.sell.s0.size() + 1) * sizeof(SellSlice)));
-            HIPCHK(h, hipMemcpy(h->m_slices.p, mp.sell.s0.data(), mp.sell.s0.size() * sizeof(SellSlice), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_rows.alloc((mp.sell.rows.size() + 128) * sizeof(int32_t)));
-            if (!mp.sell.rows.empty()) HIPCHK(h, hipMemcpy(h->m_rows.p, mp.sell.rows.data(), mp.sell.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_wave_first.alloc(mp.wave_first.size() * sizeof(int32_t)));
-            HIPCHK(h, hipMemcpy(h->m_wave_first.p, mp.wave_first.data(), mp.wave_first.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_window.alloc(mp.window.size() * sizeof(int32_t)));
-            HIPCHK(h, hipMemcpy(h->m_window.p, mp.window.data(), mp.window.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_own.alloc(mp.own.size() * sizeof(int32_t)));
-            HIPCHK(h, hipMemcpy(h->m_own.p, mp.own.data(), mp.own.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIPCHK(h, h->m_exch.alloc((size_t)4 * n_rows * sizeof(double) + 64));
-            HIPCHK(h, h->m_slots.alloc((size_t)3 * kMedMaxGroups * 8 * sizeof(double)));      // sums of even / odd iterations, flags
-            HIPCHK(h, h->m_err.alloc(64));
-            h->med_groups = mp.groups; h->med_window = mp.window_pairs;
-            h->medium_ok = true;
-        }
-    }
     h->peer_ok = false;
     h->wt_rb.clear(); h->wt_re.clear();
     if (h->win) {
@@ -1903,10 +1851,6 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const 
             }
             if (wall[t0 + 1].spare == wall[t0].spare && wall[t0 + 2].spare == wall[t0].spare) h->win_period = 0;   // (period 1: nothing to align)
         }
-        // tile order: PRCG_WIN_ORDER=1 lets every XCD sweep one contiguous eighth of the table (a 3-D stencil's plane neighbours
-        // then meet in one XCD's L2: S2 reads 0.39 instead of 0.67 GB per launch through the fabric) -- measured 2 % SLOWER at S2
-        // (profiles/r03_sweeps.md H: the 128-row stencil kernels are not bound by bytes), so the chip-wide front stays the default
-        h->win_order = h->win_order_override > 0 ? 1 : 0;
         HIPCHK(h, h->wrel.alloc(rstore.size() * sizeof(uint16_t)));
         HIPCHK(h, hipMemcpy(h->wrel.p, rstore.data(), rstore.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         HIPCHK(h, h->wtiles.alloc((wall.size() + 1) * sizeof(WTile)));
@@ -1930,7 +1874,6 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const 
     HIPCHK(h, h->t1.alloc((size_t)2 * n_rows * sizeof(double)));
     HIPCHK(h, h->partA.alloc((size_t)8192 * kPartialStride * sizeof(double)));
     HIPCHK(h, h->partB.alloc((size_t)8192 * kPartialStride * sizeof(double)));
-    HIPCHK(h, h->ticket.alloc(64));
     h->have_csr = true;
     h->have_halo = false;
     h->gather_planned = false;
@@ -2340,7 +2283,6 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     h->pr_packed = false;
     h->hs_pend_mu = 0;
     h->small = false; h->small_hs = false;
-    h->medium = false;
     h->gather = false;
     h->cb_session = h->cb != nullptr && inv_diag == nullptr;
     h->prec = inv_diag != nullptr || h->cb_session;
@@ -2379,7 +2321,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         h->red_pending = false;
         // direct peer exchange (every rank connected, window operator): the one-launch schedule without a collective.
         // Whether it is connected is the same on every rank (the host side connects all ranks or none).
-        h->peer = h->peer_ok && h->want_peer && h->want_fused && h->multi() && h->win && !h->fused_final && !h->cb_session;
+        h->peer = h->peer_ok && h->want_peer && h->want_fused && h->multi() && h->win && !h->cb_session;
         if (!h->peer && (rc = plan_gather(h))) return rc;
         // with a communicator: the same kernel in its deferred form -- window operators whose halo rides on the
         // one all-gather per iteration (bands; the merged exchange).  Larger halos (send/recv + all-reduce chain)
@@ -2387,7 +2329,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         // from the communication stream while a launch waited for it (profiles/r02_sweeps.md).
         // (the one-launch schedule over the RCCL all-gather chain is opt-in, PRCG_FUSED_COMM=1: its launches wait inside the
         //  kernel for kernels of ANOTHER stream to become resident, which has only ever been validated with one rank)
-        h->fused_comm = h->peer || (h->want_fused && h->want_fused_comm_rccl && h->multi() && h->win && !h->fused_final && h->gather);
+        h->fused_comm = h->peer || (h->want_fused && h->want_fused_comm_rccl && h->multi() && h->win && h->gather);
         if (h->fused_comm) h->fused = true;        // state layout, derived vectors: as the one-launch schedule
         HIPCHK(h, h->xp.ensure((size_t)2 * n * D, h->sc));
         HIPCHK(h, h->rs.ensure((size_t)2 * (h->prec ? n : ne) * D, h->sc));
@@ -2407,9 +2349,6 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         h->small = h->fused && !h->fused_comm && h->want_small && !h->prec && pipe_recompute(variant) &&
                    !(hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) &&
                    small_fits(h->n, h->nnz, h->max_row_len, &h->small_mode);
-        // few-workgroup solver for the systems the one-workgroup solver cannot hold: same conditions, up to 131,072 rows
-        h->medium = !h->small && h->medium_ok && h->want_medium && h->fused && !h->fused_comm && !h->prec && pipe_recompute(variant) &&
-                    !(hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) && !h->multi();
         HIPCHK(h, h->rst.ensure(h->prec ? (size_t)2 * ne * D : 16, h->sc));
         if (h->prec) h->rs_cur = h->rst.d();
         HIPCHK(h, h->wu.ensure((size_t)2 * n * D, h->sc));
@@ -2448,7 +2387,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         PipeUpdateArgs a = pipe_args(h, 0);
         const int grid = launch_pipe_dots(sc, a);                           // nu, mu, delta, gamma
         LAUNCHCHK(h, grid);
-        if (!h->fused_final) launch_reduce_final(sc, h->partA.d(), grid, dots_at(h, 0), 0, 0, 5);
+        launch_reduce_final(sc, h->partA.d(), grid, dots_at(h, 0), 0, 0, 5);
         if ((rc = allreduce(h, dots_at(h, 0), 5, sc))) return rc;
         if (h->gather) {
             // COLLECTIVE part, the same on every rank of a merged-exchange session whatever schedule the rank itself
@@ -2661,31 +2600,6 @@ int prcg_iterate(prcg_t* h, int iters) {
         h->k += iters;
         return PRCG_OK;
     }
-    if (h->medium && iters > 0) {
-        // all `iters` iterations inside one launch of a few co-operating workgroups (prcg_medium.hip)
-        for (int left = iters; left > 0;) {
-            const int now = left < (1 << 20) ? left : (1 << 20);
-            MediumArgs ma{};
-            ma.n = (int)h->n; ma.G = h->med_groups;
-            ma.slices = static_cast<const int4*>(h->m_slices.p);
-            ma.val = h->m_val.d(); ma.col16 = static_cast<const unsigned short*>(h->m_col.p);
-            ma.rows = static_cast<const int*>(h->m_rows.p); ma.indptr = h->indptr.i();
-            ma.wave_first = static_cast<const int*>(h->m_wave_first.p);
-            ma.wg_window = static_cast<const int2*>(h->m_window.p);
-            ma.wg_own = static_cast<const int2*>(h->m_own.p);
-            ma.xp = h->xp.d(); ma.rs = h->rs_cur; ma.exch = h->m_exch.d(); ma.slots = h->m_slots.d();
-            ma.dots = h->dots.d(); ma.coef = h->coef.d();
-            ma.k0 = h->k; ma.iters = now; ma.meurant = meurant(h->variant);
-            ma.seq = ++h->med_seq; ma.err = static_cast<unsigned*>(h->m_err.p);
-            bool on = false;
-            prof_begin(h, h->ev_spmv, h->n_ev_spmv, 0, on);
-            LAUNCHCHK(h, launch_medium_pipe_pr(h->sc, ma, h->med_window));
-            prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-            h->k += now;
-            left -= now;
-        }
-        return PRCG_OK;
-    }
     for (int i = 0; i < iters; ++i) {
         const int k = h->k + 1;
         int rc;
@@ -2731,12 +2645,6 @@ int prcg_sync(prcg_t* h) {
                                             "(communication stream starved or a peer stalled); results are invalid. "
                                             "PRCG_FUSED_COMM=0 selects the two-kernel schedule");
     }
-    if (h->in_session && h->medium && h->m_err.p) {
-        unsigned err = 0;
-        HIPCHK(h, hipMemcpy(&err, h->m_err.p, sizeof err, hipMemcpyDeviceToHost));
-        if (err) return fail(h, PRCG_EHIP, "the few-workgroup solver waited more than its bound for one of its workgroups (not all of them "
-                                           "resident?); results are invalid.  PRCG_MEDIUM=0 selects one launch per iteration");
-    }
     return PRCG_OK;
 }
 
@@ -2755,7 +2663,7 @@ int64_t prcg_operator_bytes(const prcg_t* h) {
 int prcg_schedule(const prcg_t* h) {
     if (!h) return -1;
     return ((h->fused || h->hs_fused || h->pr_fused || h->cg_fused) ? PRCG_SCHED_FUSED : 0) | (h->fused_comm ? PRCG_SCHED_FUSED_COMM : 0) |
-           (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->medium ? PRCG_SCHED_MEDIUM : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
+           (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
            (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
@@ -3088,7 +2996,7 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity) {
     out[4] = h->last_grid;                                                        // workgroups of the last one-launch iteration
     out[5] = h->win ? win_fused_waves_per_block(h->win_geom, h->win_vd, h->fused_comm, h->nwt_int + h->nwt_bnd, h->want_big, h->sweep_waves) : 4;
     out[6] = h->win ? h->nwt_int : h->nt_int;
-    out[7] = h->win ? (int64_t)h->win_order | ((int64_t)h->sweep_waves << 8) : 0;    // bit 0: XCD-chunked tile order; >> 8: waves of a sweep table
+    out[7] = h->win ? (int64_t)h->sweep_waves << 8 : 0;    // bit 0: always 0 (was the retired XCD-chunked tile order); >> 8: waves of a sweep table
     std::vector<int32_t> rows((size_t)nt * 2);
     if (h->win) {
         std::vector<WTile> t((size_t)nt);

@@ -168,7 +168,7 @@ constexpr int kDictMax = 64;   // one dictionary entry per lane
 constexpr int kGatherPad = 65536;
 
 // experiment knobs of the tile kernels, owned by the handle (read once in prcg_create / prcg_set_option)
-struct TileKnobs { int per_cu = 0; int chunked = 0; };
+struct TileKnobs { int per_cu = 0; };
 
 // y = A x over tiles[0..ntiles).  x has ghost room; y has n_rows entries.
 // partials: [grid][kPartialStride] doubles (slots 0..2 used by the epilogues) or null.
@@ -238,7 +238,6 @@ struct WinDev {
     const PatRec* pat;             // geometry 5: the pattern records (tile.src_c = pattern id)
     int sweep_waves, sweep_tiles;  // geometry 5, sweep table (prcg_plan.h: plan_sweep_tiles): the waves / tiles the carry bits assume (0: none)
     int big_ok;                    // short launches of the one-launch iteration may take big workgroups (PRCG_WIN_BIG=0: never)
-    int order;                     // 1: XCD-chunked tile order (each XCD sweeps one contiguous eighth of the table), 0: chip-wide front
     int period;                    // > 1: tiles t and t + period read the same stream images (host: the launch picks a wave
                                    // count that is a multiple of it, so that a wave meets the same image tile after tile)
 };
@@ -330,7 +329,6 @@ struct SellDev {
     const int* rows;          // slices with rows_off >= 0 (a sorting window wider than a slice): (row, length) of lane l at pair rows_off + l (row -1: none)
     int nt;                   // 1: value / code streams read with nontemporal loads (operators far larger than the Infinity Cache)
     int run;                  // 1: a column code per nonzero; 3: a code per aligned run of three consecutive columns (prcg_plan.h)
-    int gb, defer;            // order of a trip's gathers / the next trip's loads, and of a slice's row stores (prcg_sell.hip)
     const int* gran;          // non-null: WINDOW codes (prcg_plan.h) -- the first column of every granule, slice after slice
     int window;               // ... and the most granules a slice has (<= 64)
 };
@@ -355,27 +353,6 @@ bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode);
 int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode);
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode);      // Hestenes-Stiefel, same storage
 
-// ---- mid-size systems: the whole pipelined solve in one launch of a few co-operating workgroups (prcg_medium.hip) ----
-constexpr int kMedSlices = 4;                   // 64-row slices per wave at most
-constexpr int kMedMaxGroups = 32;               // workgroups (one per CU, 16 waves each)
-constexpr int kMedMaxWindow = 9728;             // (r,s) pairs of a workgroup's column window that fit its LDS (152 KB)
-struct MediumArgs {
-    int n, G;
-    const int4* slices;                          // the sliced layout of the operator (prcg_plan.h: plan_sell)
-    const double* val; const unsigned short* col16; const int* rows; const int* indptr;
-    const int* wave_first;                       // [16 G + 1]: first slice of every wave
-    const int2* wg_window;                       // [G]: {first column, columns} of the workgroup's window
-    const int2* wg_own;                          // [G]: the workgroup's own rows [first, end) -- every row of its slices, nobody else's
-    double* xp; double* rs;                      // pairs (x,p), (r,s): read at entry, written at exit
-    double* exch;                                // [2][n] pairs: the exchange buffer
-    double* slots;                               // [2][kMedMaxGroups][8] doubles: per workgroup four partial sums ... tag; "rows visible" tags
-    double* dots; double* coef;                  // [max_iter+1][kPartialStride], [max_iter+1][4]
-    int k0, iters, meurant;
-    unsigned long long seq;                      // launch number: the tags of this launch are (seq << 24) + iteration
-    unsigned* err;                               // set if a workgroup waited longer than its bound for the others
-};
-int launch_medium_pipe_pr(hipStream_t st, const MediumArgs& a, int window_pairs);
-
 // ---- fused vector updates + inner products -----------------------------------------
 struct PipeUpdateArgs {
     int64_t n;
@@ -389,8 +366,6 @@ struct PipeUpdateArgs {
     const double* dots_prev;   // kNumScalars doubles: mu, dl, gm, nu of iteration k-1
     double* coef_out;          // alpha, beta, nu_pred of this iteration
     double* partials;          // [grid][kPartialStride]
-    double* final_out;         // non-null: the last block reduces the partials into final_out[0..5)
-    unsigned* ticket;          // arrival counter of that hand-off (zero between launches)
     int meurant;      // nu prediction flavour
     int recompute_w;  // 'pr' flavours: w is overwritten by the following SpMM
 };

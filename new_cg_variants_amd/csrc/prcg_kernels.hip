@@ -226,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(
     CsrDev A, const Tile* __restrict__ tiles, const int* __restrict__ tbase, const int2* __restrict__ vdp, int ntiles,
     const void* __restrict__ xin_, void* __restrict__ yout_, int write_mask,
     const double* __restrict__ ep_r, const double* __restrict__ ep_d,
-    double* __restrict__ ep_st, double* __restrict__ partials, int chunked, double* __restrict__ aux,
+    double* __restrict__ ep_st, double* __restrict__ partials, double* __restrict__ aux,
     FusedPrev fz)
 {
     using V = typename VecT<NV>::type;
@@ -283,22 +283,14 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(
         if (blockIdx.x == 0 && threadIdx.x == 0) { aux[0] = cf.al; aux[1] = cf.bt; aux[2] = cf.nup; }
     }
 
-    // Tile order.  strided (default): wave `slot` takes tiles slot, slot+W, ... so the whole
-    // chip sweeps the matrix as one front (stencil neighbours are fetched while their
-    // lines are still in L2 / Infinity Cache).  chunked: wave `slot` owns the contiguous
-    // tile range [slot*T, (slot+1)*T) -- measured slower on S3 (profiles/r01_sweeps.md).
+    // Tile order: wave `slot` takes tiles slot, slot+W, ... so the whole chip sweeps the
+    // matrix as one front (stencil neighbours are fetched while their lines are still in
+    // L2 / Infinity Cache).
     const int nblk = gridDim.x;
     const int W = nblk * kWaves;
     const int slot = xcd_remap(blockIdx.x, nblk) * kWaves + wv;
-    int t, tend, step;
-    if (chunked) {
-        const int T = (ntiles + W - 1) / W;
-        t = slot * T;
-        tend = t + T < ntiles ? t + T : ntiles;
-        step = 1;
-    } else {
-        t = slot; tend = ntiles; step = W;
-    }
+    const int tend = ntiles, step = W;
+    int t = slot;
 
     MatRegs<STEPS, C16, VD> m0, m1;
     TileDesc d0 = {0, 0, 0, 0, 0, 0, 0}, d1 = {0, 0, 0, 0, 0, 0, 0};
@@ -443,8 +435,7 @@ __global__ __launch_bounds__(kBlock) void k_pipe_update(PipeUpdateArgs a, int tr
         }
     }
     if constexpr (!PREC) acc[4] = acc[3];
-    if (a.final_out) block_reduce_store_final<5>(acc, a.partials, a.ticket, a.final_out);
-    else block_reduce_store<5>(acc, a.partials, 0);
+    block_reduce_store<5>(acc, a.partials, 0);
 }
 
 // ---- Hestenes-Stiefel (hs_cg.py:54-61, hs_pcg :116-124) ------------------------------
@@ -1224,9 +1215,8 @@ int launch_tiles(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles,
     if (cw == 8) grid = vd ? tile_grid<NV * 1000 + EPI * 100 + STEPS * 10 + 5>(k, ntiles, kn.per_cu) : tile_grid<NV * 1000 + EPI * 100 + STEPS * 10 + 1>(k, ntiles, kn.per_cu);
     else if (cw == 16) grid = vd ? tile_grid<NV * 1000 + EPI * 100 + STEPS * 10 + 6>(k, ntiles, kn.per_cu) : tile_grid<NV * 1000 + EPI * 100 + STEPS * 10 + 2>(k, ntiles, kn.per_cu);
     else grid = vd ? tile_grid<NV * 1000 + EPI * 100 + STEPS * 10 + 4>(k, ntiles, kn.per_cu) : tile_grid<NV * 1000 + EPI * 100 + STEPS * 10>(k, ntiles, kn.per_cu);
-    const int chunked = kn.chunked;   // experiment knob PRCG_TILE_ORDER=chunk (measured slower: 4.2-4.7 vs 4.6-4.9 TB/s)
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, st, A, tiles, A.tile_base, A.vd, ntiles, x, y, write_mask, ep_r, ep_d, ep_st,
-                       partials, chunked, aux, fz);
+                       partials, aux, fz);
     return PRCG_LAUNCH_OK() ? grid : -1;
 }
 

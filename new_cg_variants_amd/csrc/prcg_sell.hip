@@ -78,14 +78,10 @@ __device__ __forceinline__ int2 slice_row(const SellDev& A, const SDesc& d, int 
 }
 
 // The wave's memory counter retires in issue order as far as a wait can tell: a wait for ANY load is a wait for everything
-// issued before it.  Two orders follow from that (GB, DEFER; both measured, r04_sweeps.md B):
-//   GB     0: the next trip's stream loads first, then this trip's gathers two codes at a time -- the first gather wait is a
-//             wait for the whole next trip, and nothing of the stream is in flight for the wave while the trip is summed;
-//             4 / 8: the gathers of the trip's first 4 / 8 codes, THEN the next trip's loads (they stay in flight);
-//   DEFER  the fused iteration's row results of slice k are stored right in front of the first gathers of slice k + 1 (their
-//             acknowledgement is covered by the gathers' round trip) instead of at the end of slice k, where the next
-//             slice's first address computation -- a wait for everything -- found them as the youngest requests
-template <int NV, int EPI, bool NT, int RUN, int GB, bool DEFER>
+// issued before it.  Order of a trip: the next trip's stream loads first, then this trip's gathers two codes at a time -- the
+// first gather wait is a wait for the whole next trip.  (Gathers first, or the fused iteration's row stores deferred into the
+// next slice, measured no faster: r04_sweeps.md B.)
+template <int NV, int EPI, bool NT, int RUN>
 __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     SellDev A, const int4* __restrict__ slices, int nslices,
     const void* __restrict__ xin_, void* __restrict__ yout_, int write_mask,
@@ -126,19 +122,6 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     for (int i = threadIdx.x; i < kWaves * 768; i += kBlock) vzero(diag_win[i]);
     __syncthreads();
 #endif
-    // DEFER: the previous slice's row, sums and operands until they are stored
-    int prow = -1;
-    V psum; vzero(psum);
-    FusedRowIn pq = {};
-    V pown; vzero(pown);
-    auto flush_row = [&]() {
-        if constexpr (DEFER && epi_fused(EPI)) {
-#if !defined(PRCG_SELL_DIAG_NOEPI)
-            if (prow >= 0) fused_row_update<epi_prec(EPI), epi_recompute(EPI)>(prow, psum, pq, pown, fr, cf, acc);
-#endif
-            prow = -1;
-        }
-    };
     SDesc d = {0, 0, 0, 0, 0, 0, -1, 0}, dn = {0, 0, 0, 0, 0, 0, -1, 0};
     int2 rl = make_int2(-1, 0);            // row and length of the lane's row in the CURRENT slice (requested a slice ahead)
     if (t < nslices) {
@@ -183,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
                 s.voff = other ? dn.voff : d.voff; s.coff = other ? dn.coff : d.coff; s.width = other ? dn.width : d.width;
                 load_trip<NT, RUN>(A, s, more ? u0 + TP : other ? 0 : u0, lane, nxt);
             };
-            if constexpr (GB == 0) request_next();
+            request_next();
             // the lane's running column: every code moves it by code - 16384 (to the first column of its run); codes 0 and
             // 65535 only move it (skips)
             int code[8], col[8];
@@ -191,8 +174,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
             code[4] = cur.c.z & 0xffffu; code[5] = cur.c.z >> 16; code[6] = cur.c.w & 0xffffu; code[7] = cur.c.w >> 16;
 #pragma unroll
             for (int k = 0; k < 8; ++k) { colacc += code[k] - 16384; col[k] = colacc; }
-            if (u0 == 0) flush_row();                                       // wave-uniform
-            constexpr int CB = GB == 0 ? 2 : GB;                            // codes per batch of gathers
+            constexpr int CB = 2;                                           // codes per batch of gathers
 #pragma unroll
             for (int k2 = 0; k2 < 8; k2 += CB) {
                 V g[CB * RUN];
@@ -210,13 +192,6 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
                                                                             //  two of the row's columns: valid entries, never used)
 #endif
                 }
-                if constexpr (GB != 0) {
-                    if (k2 == 0) {                                          // (the scheduler must not move the stream loads in front of the gathers)
-                        __builtin_amdgcn_sched_barrier(0);
-                        request_next();
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
 #pragma unroll
                 for (int k = 0; k < CB * RUN; ++k) {
                     const int pos = k2 * RUN + k;                           // position inside the trip
@@ -231,12 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
 #if defined(PRCG_SELL_DIAG_NOEPI)               // TIMING ONLY (wrong results): nothing is stored per row
             if constexpr (NV == 2) { if (active) acc[0] += sum.x + sum.y + q.xp.x + q.xp.y + own.x + own.y; }
 #else
-            if constexpr (DEFER) {
-                if (d.width == 0) flush_row();                              // (a slice without trips had no place for it)
-                prow = active ? row : -1; psum = sum; pq = q; pown = own;
-            } else {
-                if (active) fused_row_update<epi_prec(EPI), epi_recompute(EPI)>(row, sum, q, own, fr, cf, acc);
-            }
+            if (active) fused_row_update<epi_prec(EPI), epi_recompute(EPI)>(row, sum, q, own, fr, cf, acc);
 #endif
         } else {
             if (active) finish_row<NV, EPI>(row, sum, yout_, write_mask, X, ep_r, ep_d, ep_st, acc, cf, fr);
@@ -246,7 +216,6 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
         if (t + W < nslices) dn = read_sdesc(slices, t + W);
     }
 
-    flush_row();
     if constexpr (epi_fused(EPI)) { if constexpr (!epi_prec(EPI)) acc[4] = acc[3]; block_reduce_store<5>(acc, partials, 0); }
     else if constexpr (EPI == kEpiCG) block_reduce_store<5>(acc, partials, 0);
     else if constexpr (EPI != kEpiNone) {
@@ -472,27 +441,8 @@ int launch_sell(hipStream_t st, const SellDev& A, const void* slices, int nslice
                            ep_d, ep_st, partials, aux, fz);
         return hipGetLastError() == hipSuccess ? gridw : -1;
     }
-    auto pick = [&](auto gb, auto df) {
-        constexpr int G = decltype(gb)::value;
-        constexpr bool D = decltype(df)::value;
-        return A.run == 3 ? (A.nt ? k_sell_tiles<NV, EPI, true, 3, G, D> : k_sell_tiles<NV, EPI, false, 3, G, D>)
-                          : (A.nt ? k_sell_tiles<NV, EPI, true, 1, G, D> : k_sell_tiles<NV, EPI, false, 1, G, D>);
-    };
-    using I0 = std::integral_constant<int, 0>;
-    auto k = pick(I0{}, std::false_type{});
-    if constexpr (EPI == kEpiPipeFused) {                // (the experiment's orders: the unpreconditioned pipelined iteration only)
-        using I4 = std::integral_constant<int, 4>;
-        using I8 = std::integral_constant<int, 8>;
-        const int sel = (A.gb == 8 ? 2 : A.gb == 4 ? 1 : 0) * 2 + (A.defer ? 1 : 0);
-        switch (sel) {
-        case 1: k = pick(I0{}, std::true_type{}); break;
-        case 2: k = pick(I4{}, std::false_type{}); break;
-        case 3: k = pick(I4{}, std::true_type{}); break;
-        case 4: k = pick(I8{}, std::false_type{}); break;
-        case 5: k = pick(I8{}, std::true_type{}); break;
-        default: break;
-        }
-    }
+    auto k = A.run == 3 ? (A.nt ? k_sell_tiles<NV, EPI, true, 3> : k_sell_tiles<NV, EPI, false, 3>)
+                        : (A.nt ? k_sell_tiles<NV, EPI, true, 1> : k_sell_tiles<NV, EPI, false, 1>);
     const int grid = sell_grid(k, nslices, per_cu);
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, st, A, reinterpret_cast<const int4*>(slices), nslices, x, y, write_mask, ep_r, ep_d,
                        ep_st, partials, aux, fz);

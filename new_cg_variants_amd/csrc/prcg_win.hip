@@ -913,7 +913,7 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
                      FusedRowPtrs{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st),
                                   reinterpret_cast<double2*>(fz.rs), ep_d, fz.w, fz.wt, (write_mask & 8) != 0},
                      fz.pr, lane, nullptr, 0, nullptr, 0, &fz.lag, fz.nprev > 0,
-                     CW == 32 && DEF == 0 && A.sweep_waves > 0 && A.sweep_waves == (int)gridDim.x * WPB && A.order == 0};
+                     CW == 32 && DEF == 0 && A.sweep_waves > 0 && A.sweep_waves == (int)gridDim.x * WPB};
     WCtx<NV>& cm = c;
     if constexpr (DEF > 0) {
         if (fz.px) {
@@ -931,22 +931,6 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
     int W = nblk * WPB;
     int t = xcd_remap(blockIdx.x, nblk) * WPB + wv;
     int tend = ntiles;                       // the wave's tiles: t, t + W, ... below tend
-    if constexpr (DEF == 0) {
-        if (A.order == 1) {
-            // XCD-chunked order: the workgroups of one XCD (round-robin dispatch: workgroup b runs on XCD b % 8) sweep ONE
-            // contiguous eighth of the tile table, front by front, instead of every eighth tile-range of a chip-wide front.
-            // A 3-D stencil's plane neighbours (+-365 tiles at S2) are then rows the SAME XCD staged a round earlier or will
-            // own a round later -- they meet in its L2 instead of being read through the fabric by three XCDs (S2: 0.67 -> 0.39 GB read
-            // per launch, but 2 % slower: opt-in, PRCG_WIN_ORDER=1).
-            const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, q = nblk >> 3, r = nblk & 7;
-            const int nbx = q + (xcd < r ? 1 : 0);
-            const int before = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-            const int lo = (int)((long long)ntiles * before / nblk);
-            tend = (int)((long long)ntiles * (before + nbx) / nblk);
-            W = nbx * WPB;
-            t = lo + idx * WPB + wv;
-        }
-    }
     bool relay = false;
     if constexpr (DEF > 0) {
         if (fz.px) {
@@ -1402,7 +1386,7 @@ int launch_win_v(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles
         const int waves = grid * WPB, rounds = (ntiles + waves - 1) / waves;
         grid = ((ntiles + rounds - 1) / rounds + WPB - 1) / WPB;
     }
-    if (!DEFER && per_cu < 1 && CW == 32 && A.sweep_waves > 0 && A.sweep_waves % WPB == 0 && ntiles == A.sweep_tiles && A.order == 0) {
+    if (!DEFER && per_cu < 1 && CW == 32 && A.sweep_waves > 0 && A.sweep_waves % WPB == 0 && ntiles == A.sweep_tiles) {
         // a sweep table: the carry bits assume exactly these waves (slot s takes tiles s, s + waves, ...)
         grid = A.sweep_waves / WPB;
     }

@@ -229,8 +229,7 @@ class DeviceCSR:
                 'dual_comm': bool(s & 16), 'value_dict': bool(s & 32),
                 'col_bytes': 0 if s & 65536 else (1 if s & 64 else (2 if s & 128 else 4)), 'tile_steps': (s >> 8) & 15,
                 'pattern': bool(s & 65536), 'window': bool(s & 4096), 'fused_comm': bool(s & 8192), 'peer': bool(s & 16384), 'sliced_rows': bool(s & 32768),
-                'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152),
-                'medium': bool(s & 1048576)}
+                'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152)}
 
     def layout(self):
         """Diagnostic (prcg.h: prcg_debug_layout): what the summation order of the one-launch iteration's inner
@@ -241,7 +240,7 @@ class DeviceCSR:
         if got < 8:
             raise RuntimeError('prcg_debug_layout failed')
         return {'window': bool(out[0]), 'geometry': int(out[1]), 'rows_per_tile': int(out[2]), 'tiles': out[8:got].reshape(-1, 2).copy(),
-                'grid': int(out[4]), 'waves_per_block': int(out[5]), 'interior_tiles': int(out[6]), 'xcd_chunked': bool(int(out[7]) & 1), 'sweep_waves': int(out[7]) >> 8}
+                'grid': int(out[4]), 'waves_per_block': int(out[5]), 'interior_tiles': int(out[6]), 'sweep_waves': int(out[7]) >> 8}
 
     def operator_bytes(self):
         """Bytes of the operator as the device streams it (prcg.h: prcg_operator_bytes)."""
