@@ -216,6 +216,7 @@ int prcg_iteration(const prcg_t* h);
 #define PRCG_SCHED_SELL_SORTED 262144  /* sliced rows with a sorting window wider than a slice (SELL-C-sigma: row lengths vary) */
 #define PRCG_SCHED_NT_LOADS 524288     /* sliced rows: value / column-code streams read with nontemporal loads (operator far larger than the Infinity Cache) */
 #define PRCG_SCHED_SELL_WINDOW 2097152 /* sliced rows with WINDOW codes: a slice's input entries staged in LDS, per nonzero an LDS read instead of a gather */
+#define PRCG_SCHED_BLOCK_JACOBI 4194304 /* stored-tilde schedule with M^-1 applied by the block-Jacobi kernel (prcg_set_block_jacobi) */
 /* 1048576: retired (was PRCG_SCHED_MEDIUM, the few-workgroup solver of mid-size systems); never to be reused */
 #define PRCG_SCHED_WINDOW 4096  /* row-per-lane window kernels (bands, stencils): the column stream holds indices into the tile's
                                    LDS-staged window of the input vector */
@@ -229,6 +230,21 @@ int prcg_iteration(const prcg_t* h);
  * Single GPU.  fn == NULL removes it.  Jacobi stays on the device: pass inv_diag to prcg_solve_begin instead. */
 typedef int (*prcg_prec_fn)(void* ctx, int64_t n, const double* v, double* out);
 int prcg_set_preconditioner(prcg_t* h, prcg_prec_fn fn, void* ctx);
+/* Point-block Jacobi ON THE DEVICE: M^-1 = blockdiag(B_0 .. B_{nb-1}), one uniform block size bs in 1..8, the step after
+ * scalar Jacobi for assembled FEM matrices with bs unknowns per node.  No counterpart in the reference (its only
+ * preconditioner is the Jacobi lambda, figure_gen.py:43); the counterpart elsewhere is PETSc's `-pc_type pbjacobi`.
+ * Rows k*bs .. k*bs+bs-1 form block k, nb = ceil(n_rows / bs); inv_blocks: nb x bs x bs host doubles, row-major, the
+ * INVERSES of the diagonal blocks (the caller inverts them); a short last block (m = n_rows - bs*(nb-1) < bs rows) uses
+ * its leading m x m part, the rest is ignored.  Row i = k*bs + a of the result is
+ *     acc = B[k][a][0] * v[k*bs];   acc = acc + B[k][a][j] * v[k*bs + j]   for j = 1 .. columns-1, ascending,
+ * every product and every sum rounded (no FMA): the bits of the same loop on the host.
+ * Call after prcg_set_csr (which fixes n_rows; a later prcg_set_csr drops the blocks); the blocks are copied to the device.
+ * Sessions begun with inv_diag == NULL while blocks are set run the schedules of a host-callback session (every tilde
+ * vector a stored vector) with one kernel launch on the compute stream where that session calls fn: no copy, no
+ * synchronisation; the pipelined variants apply it to w and u in one launch.  inv_diag != NULL still selects Jacobi.
+ * This call and prcg_set_preconditioner replace each other: the last one set is in force.  Single GPU.
+ * inv_blocks == NULL removes it. */
+int prcg_set_block_jacobi(prcg_t* h, int bs, const double* inv_blocks);
 int prcg_schedule(const prcg_t* h);
 /* Bytes of the operator AS THE DEVICE STREAMS IT (the lossless re-encodings of the caller's CSR built at
  * prcg_set_csr: narrow column / window indices, value-dictionary indices, relative row pointers, tile

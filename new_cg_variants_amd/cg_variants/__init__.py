@@ -16,10 +16,13 @@ Differences, all at the edges:
   device->host copy of the state per iteration;
 * ``preconditioner``: a callable that acts as a *diagonal* scaling (the reference's Jacobi
   lambda ``(1/A.diagonal())*x``, figure_gen.py:43, or the identity default) is probed once
-  to recover the diagonal and then applied on the device; any other callable is the
-  caller's code, as it is in the reference, and is called on the host wherever the reference
-  calls ``preconditioner(...)`` (prcg.h: prcg_set_preconditioner) while products, updates
-  and inner products stay on the device;
+  to recover the diagonal and then applied on the device; an object that carries ``bs`` and
+  ``inv_blocks`` (``BlockJacobi(A, bs)``: the inverses of the bs x bs diagonal blocks, what
+  PETSc calls pbjacobi) is applied on the device too, by a kernel of its own, and is never
+  called (prcg.h: prcg_set_block_jacobi); any other callable is the caller's code, as it is
+  in the reference, and is called on the host wherever the reference calls
+  ``preconditioner(...)`` (prcg.h: prcg_set_preconditioner) while products, updates and
+  inner products stay on the device;
 * with an error recorder and no ``x_true`` the reference solves for it with a sparse direct
   solver on the fly (callbacks/error_A_norm.py:36-39); that is done here too up to n = 200,000
   -- beyond that it would never return, so the call asks for ``x_true`` instead.
@@ -77,13 +80,20 @@ def clear_operator_cache():
 def _diagonal_of(preconditioner, n):
     """(d, None) with M^-1 v = d * v for a diagonal scaling (d None: the identity), or (None, preconditioner)
     for anything else.  The probe is exact for a diagonal scaling: M^-1 applied to ones IS d, bit for bit.
-    A diagonal runs on the device; any other callable is called on the host wherever the reference calls
-    `preconditioner(...)` -- it is the caller's code there too (prcg.h: prcg_set_preconditioner)."""
+    A diagonal runs on the device; so does an object that carries `bs` and `inv_blocks` (BlockJacobi), which is
+    handed on without a probe (_blocks_of; with bs == 1 it IS a diagonal); any other callable is called on the host
+    wherever the reference calls `preconditioner(...)` -- it is the caller's code there too (prcg.h:
+    prcg_set_preconditioner)."""
     if preconditioner is None:
         return None, None
     d = getattr(preconditioner, 'inv_diag', None)
     if d is not None:
         return L.f64(d), None
+    blocks = _blocks_of(preconditioner)
+    if blocks is not None:
+        if blocks[0] == 1:
+            return np.ascontiguousarray(blocks[1].reshape(-1)[:n]), None
+        return None, preconditioner
     ones = np.ones(n)
     d = np.asarray(preconditioner(ones), dtype=np.float64)
     if d.shape != (n,):
@@ -96,6 +106,14 @@ def _diagonal_of(preconditioner, n):
     return np.ascontiguousarray(d), None
 
 
+def _blocks_of(preconditioner):
+    """(bs, inv_blocks) of an object that carries them (device block Jacobi), else None."""
+    bs, blocks = getattr(preconditioner, 'bs', None), getattr(preconditioner, 'inv_blocks', None)
+    if bs is None or blocks is None:
+        return None
+    return int(bs), L.f64(blocks)
+
+
 class Jacobi:
     """Jacobi preconditioner object: callable like the reference's lambda and carrying
     the reciprocal diagonal so no probing is needed."""
@@ -105,6 +123,103 @@ class Jacobi:
 
     def __call__(self, v):
         return self.inv_diag * v
+
+
+class BlockJacobi:
+    """Point-block Jacobi preconditioner object (PETSc's pbjacobi; the reference has only the Jacobi lambda): the
+    inverses of the bs x bs diagonal blocks of A, rows k*bs .. k*bs+bs-1 forming block k.  Passed as `preconditioner`
+    to a *_pcg function it is applied on the device (prcg.h: prcg_set_block_jacobi) and never called; called, it
+    evaluates the same arithmetic with NumPy multiplies and adds --
+
+        acc = B[k][a][0] * v[k*bs];   acc = acc + B[k][a][j] * v[k*bs + j]   for j = 1, 2, ...
+
+    -- so it serves any solver that takes a callable, with the same bits.  `inv_blocks`: (ceil(n/bs), bs, bs); a short
+    last block (n not a multiple of bs) is inverted on its leading m x m part and padded with the identity."""
+
+    _CHUNK = 1 << 22      # nonzeros gathered per step: bounds the temporaries on matrices with 10^8 nonzeros
+
+    def __init__(self, A, bs):
+        bs = int(bs)
+        if not 1 <= bs <= 8:
+            raise ValueError(f'BlockJacobi: block size {bs} outside 1..8')
+        if A.format != 'csr':
+            A = A.tocsr()
+        n = A.shape[0]
+        nb = -(-n // bs)
+        self.bs, self.n = bs, n
+        blocks = self._gather(A, n, nb, bs)
+        m = n - bs * (nb - 1)                     # rows of the last block
+        if m < bs and nb > 0:
+            blocks[-1, np.arange(m, bs), np.arange(m, bs)] = 1.0
+        bad = ~np.isfinite(blocks).all(axis=(1, 2))
+        if bad.any():
+            raise ValueError(f'BlockJacobi: diagonal block {int(np.argmax(bad))} (bs = {bs}) is not finite')
+        try:
+            inv = np.linalg.inv(blocks)
+        except np.linalg.LinAlgError:
+            raise ValueError(f'BlockJacobi: diagonal block {self._first_singular(blocks)} (bs = {bs}) is singular') from None
+        bad = ~np.isfinite(inv).all(axis=(1, 2))
+        if bad.any():
+            raise ValueError(f'BlockJacobi: diagonal block {int(np.argmax(bad))} (bs = {bs}) is singular')
+        if m < bs and nb > 0:                     # the short block: its own inverse, exact identity around it
+            last = np.eye(bs)
+            last[:m, :m] = np.linalg.inv(blocks[-1, :m, :m])
+            inv[-1] = last
+        self.inv_blocks = np.ascontiguousarray(inv)
+
+    @classmethod
+    def _gather(cls, A, n, nb, bs):
+        """The diagonal blocks of CSR A as (nb, bs, bs), duplicates summed; chunks of rows, no loop over rows."""
+        blocks = np.zeros((nb, bs, bs))
+        indptr, indices, data = A.indptr, A.indices, A.data
+        r0 = 0
+        while r0 < n:
+            r1 = int(np.searchsorted(indptr, indptr[r0] + cls._CHUNK, side='right')) - 1
+            r1 = min(max(r1, r0 + 1), n)
+            lo, hi = int(indptr[r0]), int(indptr[r1])
+            rows = np.repeat(np.arange(r0, r1), np.diff(indptr[r0:r1 + 1]))
+            cols = indices[lo:hi]
+            keep = (cols // bs) == (rows // bs)
+            rows, cols = rows[keep], cols[keep]
+            np.add.at(blocks, (rows // bs, rows % bs, cols % bs), data[lo:hi][keep])
+            r0 = r1
+        return blocks
+
+    @staticmethod
+    def _first_singular(blocks):
+        step = 4096
+        for c0 in range(0, blocks.shape[0], step):
+            try:
+                np.linalg.inv(blocks[c0:c0 + step])
+            except np.linalg.LinAlgError:
+                for k in range(c0, min(c0 + step, blocks.shape[0])):
+                    try:
+                        np.linalg.inv(blocks[k])
+                    except np.linalg.LinAlgError:
+                        return k
+        return -1
+
+    def __call__(self, v):
+        v = np.asarray(v, dtype=np.float64)
+        bs, n = self.bs, self.n
+        if v.shape != (n,):
+            raise ValueError(f'BlockJacobi: expected a vector of {n} entries, got shape {v.shape}')
+        nf = n // bs                               # full blocks
+        out = np.empty(n)
+        if nf:
+            B, V = self.inv_blocks[:nf], v[:nf * bs].reshape(nf, bs)
+            acc = B[:, :, 0] * V[:, 0:1]
+            for j in range(1, bs):
+                acc = acc + B[:, :, j] * V[:, j:j + 1]
+            out[:nf * bs] = acc.reshape(-1)
+        m = n - nf * bs
+        if m:                                      # short last block: its m columns only
+            B, V = self.inv_blocks[nf, :m, :m], v[nf * bs:]
+            acc = B[:, 0] * V[0]
+            for j in range(1, m):
+                acc = acc + B[:, j] * V[j]
+            out[nf * bs:] = acc
+        return out
 
 
 _STATE_NAMES = {   # device vector -> the reference's local name
@@ -171,7 +286,11 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         op.set_replace_hook(hook)
     else:
         op.set_replace_hook(None)
-    op.begin(variant, b, x0, max_iter, x_true=x_true, inv_diag=inv_diag, hist_mask=mask, preconditioner=prec_fn)
+    blocks = _blocks_of(prec_fn) if prec_fn is not None else None
+    if blocks is not None:
+        op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=blocks)
+    else:
+        op.begin(variant, b, x0, max_iter, x_true=x_true, inv_diag=inv_diag, hist_mask=mask, preconditioner=prec_fn)
 
     def call_host(k):
         env = {'output': output, 'k': k, 'max_iter': max_iter, 'A': A, 'b': b, 'x0': x0, 'n': n,
@@ -246,4 +365,5 @@ pipe_pr_m_pcg = _make(L.PIPE_PR_M, 'pipe_pr_m_pcg', True) # pipe_pr_cg.py:213
 
 __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr_pcg', 'm_cg', 'm_pcg',
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
-           'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'clear_operator_cache']
+           'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
+           'clear_operator_cache']

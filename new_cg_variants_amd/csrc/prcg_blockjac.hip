@@ -1,0 +1,159 @@
+// gfx950 (MI355X / CDNA4): point-block Jacobi, out = blockdiag(B_0 .. B_{nb-1}) v with one uniform block size bs in 1..8
+// (prcg_set_block_jacobi; PETSc's -pc_type pbjacobi -- the reference has only the Jacobi lambda, figure_gen.py:43).
+//
+// Arithmetic (prcg.h): row i = k*bs + a computes  acc = B[k][a][0] * v[k*bs];  acc = acc + B[k][a][j] * v[k*bs + j]
+// for ascending j -- every product and every sum rounded (-ffp-contract=off), so the result has the bits of the same
+// loop written with NumPy multiplies and adds on the host.  A short last block (n not a multiple of bs) uses its
+// leading m x m part only; nothing at or beyond row n is read or written.
+//
+// The kernel is bandwidth bound: per row it must read the row's bs block entries and one entry of v and write one
+// entry, (bs + 2) * 8 bytes.  Row per lane, wave64, 256 lanes per workgroup:
+//
+//   * a workgroup owns a TILE of TR = 256 - 256 % bs consecutive rows (255 at bs = 3), a whole number of blocks, so no
+//     block straddles two workgroups; lanes TR..255 idle (at most 6 of 256);
+//   * the caller's row-major nb x bs x bs array would make lane t read address (t * bs + j) * 8 for a fixed j: a
+//     stride of bs doubles, bs times the cache lines per instruction.  The blocks are therefore RE-LAID ONCE AT UPLOAD
+//     (block_jacobi_layout, below): entry j of the row of lane t of tile T sits at ((T * bs + j) * 256 + t), so that
+//     for a fixed j the 64 lanes of a wave read 64 consecutive doubles (512 B, aligned: the tile stride is 256
+//     entries, not TR, which costs 256 % bs / 256 of padding -- 0.4 % at bs = 3);
+//   * every lane loads ITS entry of v (coalesced; stride 2 when the vector is one column of a pair array) and parks it
+//     in LDS; after one barrier the lane reads its block's bs entries from there (lanes of one row-block read the
+//     same LDS address: a broadcast) -- one global load of v per row instead of bs;
+//   * the pair form does both columns of the pipelined loop's interleaved [w u] array in one launch: one 16-byte load
+//     per row brings (w_i, u_i), the block entries are read once and used for both: (bs + 4) * 8 bytes per row
+//     instead of 2 * (bs + 2) * 8.
+#include <hip/hip_runtime.h>
+
+#include "prcg_kernels.h"
+
+namespace prcg {
+namespace {
+
+constexpr int kBjBlock = 256;    // lanes per workgroup = entries per (tile, j) line of the device layout
+
+typedef double d2_t __attribute__((ext_vector_type(2)));
+
+template <int BS>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi(double* __restrict__ dst, int ds, const double* __restrict__ src, int ss,
+                                                           int64_t n, const double* __restrict__ blk) {
+    constexpr int TR = (kBjBlock / BS) * BS;
+    __shared__ double sv[kBjBlock];
+    const int t = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * TR;
+    const int64_t i = row0 + t;
+    const bool live = t < TR && i < n;
+    if (live) sv[t] = src[i * ss];
+    __syncthreads();
+    if (!live) return;
+    const int c0 = t - t % BS;                            // first lane of this row's block
+    const int64_t cols = n - (row0 + c0);                 // columns the block really has (>= BS except in a short last block)
+    const double* bp = blk + ((int64_t)blockIdx.x * BS) * kBjBlock + t;
+    double b[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) b[j] = bp[(int64_t)j * kBjBlock];
+    double acc = b[0] * sv[c0];
+#pragma unroll
+    for (int j = 1; j < BS; ++j)
+        if (j < cols) acc = acc + b[j] * sv[c0 + j];
+    dst[i * ds] = acc;
+}
+
+// both columns of the interleaved [w u] array: wt = M^-1 w (mask bit 0), ut = M^-1 u (mask bit 1)
+template <int BS>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_pair(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                                int64_t n, const double* __restrict__ blk, int mask) {
+    constexpr int TR = (kBjBlock / BS) * BS;
+    __shared__ d2_t sv[kBjBlock];
+    const int t = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * TR;
+    const int64_t i = row0 + t;
+    const bool live = t < TR && i < n;
+    if (live) sv[t] = wu[i];
+    __syncthreads();
+    if (!live) return;
+    const int c0 = t - t % BS;
+    const int64_t cols = n - (row0 + c0);
+    const double* bp = blk + ((int64_t)blockIdx.x * BS) * kBjBlock + t;
+    double b[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) b[j] = bp[(int64_t)j * kBjBlock];
+    d2_t v = sv[c0];
+    double aw = b[0] * v.x, au = b[0] * v.y;
+#pragma unroll
+    for (int j = 1; j < BS; ++j)
+        if (j < cols) {
+            v = sv[c0 + j];
+            aw = aw + b[j] * v.x;
+            au = au + b[j] * v.y;
+        }
+    if (mask & 1) wt[i] = aw;
+    if (mask & 2) ut[i] = au;
+}
+
+inline int bj_grid(int64_t n, int bs) {
+    const int64_t tr = (kBjBlock / bs) * bs;
+    return (int)((n + tr - 1) / tr);
+}
+
+template <int BS>
+void launch_one(hipStream_t st, double* dst, int ds, const double* src, int ss, int64_t n, const double* blk) {
+    hipLaunchKernelGGL(k_block_jacobi<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, dst, ds, src, ss, n, blk);
+}
+template <int BS>
+void launch_two(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, const double* blk, int mask) {
+    hipLaunchKernelGGL(k_block_jacobi_pair<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
+                       blk, mask);
+}
+
+}  // namespace
+
+int64_t block_jacobi_layout(int64_t n, int bs, const double* inv_blocks, double* out) {
+    if (n < 0 || bs < 1 || bs > 8) return -1;
+    const int64_t tr = (kBjBlock / bs) * bs;
+    const int64_t ntiles = (n + tr - 1) / tr;
+    const int64_t total = ntiles * bs * kBjBlock;
+    if (!out) return total;
+    for (int64_t T = 0; T < ntiles; ++T)
+        for (int j = 0; j < bs; ++j) {
+            double* line = out + (T * bs + j) * kBjBlock;
+            for (int t = 0; t < kBjBlock; ++t) {
+                const int64_t i = T * tr + t;             // row i = block i / bs, row i % bs of it
+                line[t] = (t < tr && i < n) ? inv_blocks[i * bs + j] : 0.0;
+            }
+        }
+    return total;
+}
+
+int launch_block_jacobi(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t n, int bs, const double* blocks) {
+    if (n <= 0) return 0;
+    switch (bs) {
+    case 1: launch_one<1>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 2: launch_one<2>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 3: launch_one<3>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 4: launch_one<4>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 5: launch_one<5>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 6: launch_one<6>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 7: launch_one<7>(st, dst, dstride, src, sstride, n, blocks); break;
+    case 8: launch_one<8>(st, dst, dstride, src, sstride, n, blocks); break;
+    default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask) {
+    if (n <= 0) return 0;
+    switch (bs) {
+    case 1: launch_two<1>(st, wt, ut, wu, n, blocks, mask); break;
+    case 2: launch_two<2>(st, wt, ut, wu, n, blocks, mask); break;
+    case 3: launch_two<3>(st, wt, ut, wu, n, blocks, mask); break;
+    case 4: launch_two<4>(st, wt, ut, wu, n, blocks, mask); break;
+    case 5: launch_two<5>(st, wt, ut, wu, n, blocks, mask); break;
+    case 6: launch_two<6>(st, wt, ut, wu, n, blocks, mask); break;
+    case 7: launch_two<7>(st, wt, ut, wu, n, blocks, mask); break;
+    case 8: launch_two<8>(st, wt, ut, wu, n, blocks, mask); break;
+    default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace prcg

@@ -207,9 +207,13 @@ struct prcg_handle {
     bool want_small = true;      // PRCG_SMALL=0 turns it off
     double* rs_cur = nullptr;    // fused: the current SpMM input pairs: rs / rs2 ((r,s)), with Jacobi rst / rst2 ((r~,s~))
     DevBuf partC;                // fused: second partials buffer (ping-pong with partB)
-    // host-callback preconditioner (prcg_set_preconditioner): M^-1 v is computed by the caller's function on host
-    // copies of v; sessions that use it run the schedules in which every tilde vector is a stored vector
-    prcg_prec_fn cb = nullptr; void* cb_ctx = nullptr; bool cb_session = false;
+    // preconditioners that are no diagonal scaling: sessions that use one run the schedules in which every tilde vector is
+    // a stored vector (stored_tilde).  Two kinds, the last one set is in force:
+    //  * host callback (prcg_set_preconditioner): M^-1 v is computed by the caller's function on host copies of v;
+    //  * point-block Jacobi (prcg_set_block_jacobi): M^-1 v is one launch of prcg_blockjac.hip on the compute stream
+    //    (bj_session says that THIS one applies M^-1 in the current session)
+    prcg_prec_fn cb = nullptr; void* cb_ctx = nullptr; bool stored_tilde = false;
+    int bj_bs = 0; DevBuf bj_blocks; bool bj_session = false;    // bj_bs > 0: blocks set, in the layout of block_jacobi_layout
     prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
     std::vector<double> cb_in, cb_out;
     DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
@@ -627,7 +631,10 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
         if (profile) prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
         LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, in_ext, h->wu.d(), mask));
         if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-        if (h->cb_session) {
+        if (h->bj_session) {
+            // block Jacobi: both columns of [w u] in one launch that reads every block once
+            LAUNCHCHK(h, launch_block_jacobi_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask));
+        } else if (h->stored_tilde) {
             // u~ = preconditioner(u); w~ = preconditioner(w) in the flavours that recompute w (pipe_pr_cg.py:178-182)
             if ((rc = apply_prec(h, h->wu.d() + 1, 2, h->ut.d(), 1))) return rc;
             if (pipe_recompute(h->variant) && (rc = apply_prec(h, h->wu.d(), 2, h->wt.d(), 1))) return rc;
@@ -719,8 +726,8 @@ PipeUpdateArgs pipe_args(prcg_t* h, int k) {
     a.xp = h->xp.d();
     a.rs = h->rs.d(); a.rst = h->prec ? h->rst.d() : nullptr;
     a.wu = h->wu.d(); a.wt = h->wt.d();
-    a.d = (h->prec && !h->cb_session) ? h->dinv.d() : nullptr;
-    a.ut = h->cb_session ? h->ut.d() : nullptr;
+    a.d = (h->prec && !h->stored_tilde) ? h->dinv.d() : nullptr;
+    a.ut = h->stored_tilde ? h->ut.d() : nullptr;
     a.dots_prev = k > 0 ? dots_at(h, k - 1) : dots_at(h, 0);
     a.coef_out = coef_at(h, k);
     a.partials = h->partA.d();
@@ -885,7 +892,7 @@ HsArgs hs_args(prcg_t* h, int k) {
     HsArgs a{};
     a.n = h->n;
     a.x = h->x.d(); a.r = h->r.d(); a.rt = h->prec ? h->rt.d() : nullptr;
-    a.p = h->p_cur; a.s = h->s.d(); a.d = (h->prec && !h->cb_session) ? h->dinv.d() : nullptr;
+    a.p = h->p_cur; a.s = h->s.d(); a.d = (h->prec && !h->stored_tilde) ? h->dinv.d() : nullptr;
     a.dots_prev = k > 0 ? dots_at(h, k - 1) : dots_at(h, 0);
     a.dots_cur = dots_at(h, k);
     a.coef_out = coef_at(h, k);
@@ -903,8 +910,8 @@ int iterate_hs(prcg_t* h, int k) {
     prof_end(h, h->ev_upd, h->n_ev_upd, on);
     launch_reduce_final(h->sc, h->partA.d(), g1, dots_at(h, k), PRCG_S_NU, PRCG_S_NU, 2);
     int rc;
-    if (h->cb_session) {
-        // r~ = preconditioner(r) on the host (hs_pcg :118), then nu = r~.r as an inner product of its own
+    if (h->stored_tilde) {
+        // r~ = preconditioner(r) -- host callback or block-Jacobi launch (hs_pcg :118) --, then nu = r~.r as an inner product of its own
         if ((rc = apply_prec(h, h->r.d(), 1, h->rt.d(), 1))) return rc;
         const int g2 = launch_dot(h->sc, h->rt.d(), h->r.d(), h->n, h->partB.d(), 0);
         LAUNCHCHK(h, g2);
@@ -1054,8 +1061,8 @@ int pr_spmv_and_reduce(prcg_t* h, int k, int grid_upd) {
     // s = A p; s~ = M^-1 s; mu, delta, gamma ride on the SpMV (pr_cg.py:152-157)
     int nparts = 0;
     int rc;
-    if (h->cb_session) {
-        // s = A p; s~ = preconditioner(s) on the host; mu, delta, gamma as inner products of their own
+    if (h->stored_tilde) {
+        // s = A p; s~ = preconditioner(s) (host callback or block-Jacobi launch); mu, delta, gamma as inner products of their own
         if ((rc = overlapped_spmv(h, k, h->p.d(), h->s.d(), kEpiNone, nullptr, nullptr, nullptr, &nparts))) return rc;
         if ((rc = apply_prec(h, h->s.d(), 1, h->st.d(), 1))) return rc;
         int g = launch_dot(h->sc, h->p.d(), h->s.d(), h->n, h->partB.d(), 0);
@@ -1094,7 +1101,7 @@ CgArgs cg_args(prcg_t* h, int k) {
     a.u = h->variant == PRCG_GV ? h->cur_u : nullptr;
     a.t = h->cur_t;
     a.z = h->prec ? h->rt.d() : h->cur_r;
-    a.d = (h->prec && !h->cb_session) ? h->dinv.d() : nullptr;
+    a.d = (h->prec && !h->stored_tilde) ? h->dinv.d() : nullptr;
     a.dots_prev = k > 0 ? dots_at(h, k - 1) : dots_at(h, 0);
     a.dots_cur = dots_at(h, k);
     a.dots_cur_w = dots_at(h, k);
@@ -1213,7 +1220,7 @@ int iterate_cgcg(prcg_t* h, int k) {
     double* z = h->prec ? h->rt.d() : h->r.d();
     int nparts = 0;
     int rc;
-    if (h->cb_session && (rc = apply_prec(h, h->r.d(), 1, h->rt.d(), 1))) return rc;   // r~ = preconditioner(r)  cg_cg.py:118
+    if (h->stored_tilde && (rc = apply_prec(h, h->r.d(), 1, h->rt.d(), 1))) return rc;   // r~ = preconditioner(r)  cg_cg.py:118
     rc = overlapped_spmv(h, k, z, h->w.d(), kEpiCG, h->r.d(), nullptr, nullptr, &nparts);   // w = A r~; nu, eta
     if (rc) return rc;
     launch_reduce_final(h->sc, h->partB.d(), nparts, dots_at(h, k), 0, 0, 5);
@@ -1241,11 +1248,11 @@ int iterate_gv(prcg_t* h, int k) {
         h->k = kk;
         if (fire) {
             if ((rc = dist_spmv(h, h->r.d(), h->cur_w, kEpiNone, nullptr, nullptr, nullptr, nullptr))) return rc;   // w = A r
-            if (h->prec && !h->cb_session) launch_mul(h->sc, h->wt.d(), 1, h->dinv.d(), 1, h->cur_w, 1, h->n);      // w~ = M^-1 w
+            if (h->prec && !h->stored_tilde) launch_mul(h->sc, h->wt.d(), 1, h->dinv.d(), 1, h->cur_w, 1, h->n);      // w~ = M^-1 w
             replaced = true;
         }
     }
-    if (h->cb_session && (rc = apply_prec(h, h->w.d(), 1, h->wt.d(), 1))) return rc;  // w~ = preconditioner(w)  gv_cg.py:161
+    if (h->stored_tilde && (rc = apply_prec(h, h->w.d(), 1, h->wt.d(), 1))) return rc;  // w~ = preconditioner(w)  gv_cg.py:161
     const bool side = h->multi() && !h->replace_fn;
     if (side) {
         HIPCHK(h, hipEventRecord(h->e_upd, h->sc));
@@ -1330,12 +1337,16 @@ int d2h(prcg_t* h, double* dst, const double* src, int64_t count) {
     return PRCG_OK;
 }
 
-// dst = M^-1 src: the inverse diagonal on the device, or the caller's function on the host (the reference's
-// `preconditioner(v)`, figure_gen.py:42-44 -- there, too, it is the caller's Python callable).
+// dst = M^-1 src: the inverse diagonal or the inverse diagonal blocks on the device, or the caller's function on the
+// host (the reference's `preconditioner(v)`, figure_gen.py:42-44 -- there, too, it is the caller's Python callable).
 int apply_prec(prcg_t* h, const double* src, int sstride, double* dst, int dstride) {
     const int64_t n = h->n;
-    if (!h->cb_session) {
+    if (!h->stored_tilde) {
         launch_mul(h->sc, dst, dstride, h->dinv.d(), 1, src, sstride, n);
+        return PRCG_OK;
+    }
+    if (h->bj_session) {        // one launch on the compute stream: no copy, no synchronisation
+        LAUNCHCHK(h, launch_block_jacobi(h->sc, dst, dstride, src, sstride, n, h->bj_bs, h->bj_blocks.d()));
         return PRCG_OK;
     }
     h->cb_in.resize((size_t)n); h->cb_out.resize((size_t)n);
@@ -1368,9 +1379,9 @@ bool locate(prcg_t* h, int which, double** base, int* stride) {
         case PRCG_VEC_U: if (h->fused) return false; *base = h->wu.d() + 1; *stride = 2; return true;
         case PRCG_VEC_RT: if (!h->prec) return false; *base = (h->fused ? h->rs_cur : h->rst.d()); *stride = 2; return true;
         case PRCG_VEC_ST: if (!h->prec) return false; *base = (h->fused ? h->rs_cur : h->rst.d()) + 1; *stride = 2; return true;
-        // host-callback preconditioner sessions: w~ and u~ are stored state (what the callback returned), in every flavour
-        case PRCG_VEC_WT: if (!h->prec || (pipe_recompute(v) && !h->cb_session)) return false; *base = h->wt.d(); return true;
-        case PRCG_VEC_UT: if (!h->cb_session) return false; *base = h->ut.d(); return true;
+        // stored-tilde sessions (host callback, block Jacobi): w~ and u~ are stored state (what M^-1 returned), in every flavour
+        case PRCG_VEC_WT: if (!h->prec || (pipe_recompute(v) && !h->stored_tilde)) return false; *base = h->wt.d(); return true;
+        case PRCG_VEC_UT: if (!h->stored_tilde) return false; *base = h->ut.d(); return true;
         default: return false;
         }
     }
@@ -1397,6 +1408,17 @@ bool locate(prcg_t* h, int which, double** base, int* stride) {
     case PRCG_VEC_ST: if (!h->prec || !is_pr(v)) return false; *base = h->cur_st; return true;
     default: return false;
     }
+}
+
+// forget the block-Jacobi blocks; a session that applies them ends here (its launches may still be reading them: wait)
+int drop_block_jacobi(prcg_t* h) {
+    if (h->bj_bs == 0 && !h->bj_blocks.p) return PRCG_OK;
+    HIPCHK(h, hipSetDevice(h->dev));
+    HIPCHK(h, hipStreamSynchronize(h->sc));
+    if (h->bj_session) { h->in_session = false; h->bj_session = false; }
+    h->bj_bs = 0;
+    h->bj_blocks.release();
+    return PRCG_OK;
 }
 
 void destroy_events(std::vector<EventPair>& evs) {
@@ -1477,6 +1499,25 @@ int prcg_set_preconditioner(prcg_t* h, prcg_prec_fn fn, void* ctx) {
     if (!h) return PRCG_EINVAL;
     h->cb = fn;
     h->cb_ctx = ctx;
+    if (fn) return drop_block_jacobi(h);         // the last preconditioner set is the one in force
+    return PRCG_OK;
+}
+
+int prcg_set_block_jacobi(prcg_t* h, int bs, const double* inv_blocks) {
+    if (!h) return PRCG_EINVAL;
+    if (!inv_blocks) return drop_block_jacobi(h);
+    CHECK(h, bs >= 1 && bs <= 8, "prcg_set_block_jacobi: block size %d outside 1..8", bs);
+    CHECK(h, h->have_csr, "prcg_set_block_jacobi: call prcg_set_csr first (the blocks are sized by its n_rows)");
+    CHECK(h, !h->multi(), "a block-Jacobi preconditioner runs on one GPU only");
+    if (int rc = drop_block_jacobi(h)) return rc;
+    const int64_t count = block_jacobi_layout(h->n, bs, inv_blocks, nullptr);
+    std::vector<double> laid;
+    try { laid.resize((size_t)count); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    block_jacobi_layout(h->n, bs, inv_blocks, laid.data());
+    HIPCHK(h, h->bj_blocks.alloc((size_t)count * sizeof(double), false));
+    HIPCHK(h, hipMemcpy(h->bj_blocks.p, laid.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
+    h->bj_bs = bs;
+    h->cb = nullptr; h->cb_ctx = nullptr;        // the last preconditioner set is the one in force
     return PRCG_OK;
 }
 
@@ -1539,6 +1580,7 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const 
     CHECK(h, indptr && (nnz == 0 || (indices && data)), "prcg_set_csr: null array");
     h->in_session = false;   // a new operator invalidates any open session
     HIPCHK(h, hipSetDevice(h->dev));
+    if (int rc = drop_block_jacobi(h)) return rc;     // ... and drops block-Jacobi blocks, sized for the old one
 
     // --- validate on the host before anything reaches a kernel ---
     std::vector<int32_t> ip((size_t)n_rows + 1);
@@ -2284,10 +2326,11 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     h->hs_pend_mu = 0;
     h->small = false; h->small_hs = false;
     h->gather = false;
-    h->cb_session = h->cb != nullptr && inv_diag == nullptr;
-    h->prec = inv_diag != nullptr || h->cb_session;
-    CHECK(h, !(h->cb_session && h->multi()), "a host-callback preconditioner runs on one GPU only");
-    if (h->cb_session) HIPCHK(h, h->cb_stage.ensure((size_t)h->n * sizeof(double), h->sc));
+    h->bj_session = h->bj_bs > 0 && inv_diag == nullptr;
+    h->stored_tilde = (h->cb != nullptr || h->bj_session) && inv_diag == nullptr;
+    h->prec = inv_diag != nullptr || h->stored_tilde;
+    CHECK(h, !(h->stored_tilde && h->multi()), "a host-callback or block-Jacobi preconditioner runs on one GPU only");
+    if (h->stored_tilde && !h->bj_session) HIPCHK(h, h->cb_stage.ensure((size_t)h->n * sizeof(double), h->sc));
     h->max_iter = max_iter;
     h->hist_mask = hist_mask;
     h->have_xtrue = x_true != nullptr;
@@ -2315,13 +2358,13 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     if ((rc = dist_spmv(h, tmp, t1, kEpiNone, nullptr, nullptr, nullptr, nullptr))) return rc;
 
     if (is_pipe(variant)) {
-        h->fused = h->want_fused && !h->multi() && h->g == 0 && !h->cb_session;
+        h->fused = h->want_fused && !h->multi() && h->g == 0 && !h->stored_tilde;
         // with a communicator: the same kernel in its deferred form (window operators only)
         h->fused_comm = false;
         h->red_pending = false;
         // direct peer exchange (every rank connected, window operator): the one-launch schedule without a collective.
         // Whether it is connected is the same on every rank (the host side connects all ranks or none).
-        h->peer = h->peer_ok && h->want_peer && h->want_fused && h->multi() && h->win && !h->cb_session;
+        h->peer = h->peer_ok && h->want_peer && h->want_fused && h->multi() && h->win && !h->stored_tilde;
         if (!h->peer && (rc = plan_gather(h))) return rc;
         // with a communicator: the same kernel in its deferred form -- window operators whose halo rides on the
         // one all-gather per iteration (bands; the merged exchange).  Larger halos (send/recv + all-reduce chain)
@@ -2353,7 +2396,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         if (h->prec) h->rs_cur = h->rst.d();
         HIPCHK(h, h->wu.ensure((size_t)2 * n * D, h->sc));
         HIPCHK(h, h->wt.ensure(h->prec ? (size_t)n * D : 16, h->sc));
-        HIPCHK(h, h->ut.ensure(h->cb_session ? (size_t)n * D : 16, h->sc));
+        HIPCHK(h, h->ut.ensure(h->stored_tilde ? (size_t)n * D : 16, h->sc));
         double* RS = h->rs.d();
         double* WU = h->wu.d();
         double* XP = h->xp.d();
@@ -2381,7 +2424,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
             launch_copy(sc, tmp, 1, RST + 1, 2, n);
             if ((rc = dist_spmv(h, tmp, t1, kEpiNone, nullptr, nullptr, nullptr, nullptr))) return rc;
             launch_copy(sc, WU + 1, 2, t1, 1, n);                           // u = A s~       :131
-            if (h->cb_session && (rc = apply_prec(h, WU + 1, 2, h->ut.d(), 1))) return rc;   // u~ = M^-1 u  :132
+            if (h->stored_tilde && (rc = apply_prec(h, WU + 1, 2, h->ut.d(), 1))) return rc;   // u~ = M^-1 u  :132
         }
         if (h->fused && !pipe_recompute(variant)) launch_copy(sc, h->wv.d(), 1, WU, 2, n);   // the stored w of the 'p' flavours
         PipeUpdateArgs a = pipe_args(h, 0);
@@ -2434,7 +2477,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         h->p_cur = h->p.d();
         HIPCHK(h, h->r.ensure((size_t)ne * D, h->sc));
         h->cur_r = h->r.d();
-        h->cg_fused = h->want_fused && !h->multi() && h->g == 0 && h->win && !h->cb_session &&
+        h->cg_fused = h->want_fused && !h->multi() && h->g == 0 && h->win && !h->stored_tilde &&
                       !(variant == PRCG_GV && h->replace_fn);      // (the predicate is called between the update and the product)
         // one launch per iteration: both variants unpreconditioned, Chronopoulos-Gear with Jacobi too
         h->cg_one = h->cg_fused && h->want_cg_one && (variant == PRCG_CG_CG || !h->prec);
@@ -2489,7 +2532,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         // HS and non-pipelined PR share the layout x, r, (r~), p(+ghosts), s, (s~)
         HIPCHK(h, h->p.ensure((size_t)ne * D, h->sc));
         h->p_cur = h->p.d();
-        h->hs_fused = variant == PRCG_HS && h->want_fused && !h->multi() && h->g == 0 && !h->cb_session;
+        h->hs_fused = variant == PRCG_HS && h->want_fused && !h->multi() && h->g == 0 && !h->stored_tilde;
         // one-workgroup solver (k_small_hs): only when nothing but the recurrence residual is recorded
         h->small_hs = h->hs_fused && h->want_small && !h->prec &&
                       !(hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) &&
@@ -2501,7 +2544,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         HIPCHK(h, h->rt.ensure(h->prec ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->st.ensure(h->prec ? (size_t)ne * D : 16, h->sc));
         // one launch per iteration for pr / m on a window operator: second copies of what the window is formed from
-        h->pr_fused = is_pr(variant) && h->want_fused && !h->multi() && h->g == 0 && h->win && !h->cb_session;
+        h->pr_fused = is_pr(variant) && h->want_fused && !h->multi() && h->g == 0 && h->win && !h->stored_tilde;
         HIPCHK(h, h->p2.ensure(((h->hs_fused && h->win) || h->pr_fused) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->r2.ensure((h->pr_fused && !h->prec) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->s2.ensure((h->pr_fused && !h->prec) ? (size_t)ne * D : 16, h->sc));
@@ -2527,7 +2570,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
             const int g1 = launch_hs_init_dots(sc, a);                      // nu = r.r~      hs_cg.py:25
             LAUNCHCHK(h, g1);
             launch_reduce_final(sc, h->partA.d(), g1, dots_at(h, 0), PRCG_S_NU, PRCG_S_NU, 2);
-            if (h->cb_session) {        // nu = r~.r with the r~ the callback returned
+            if (h->stored_tilde) {        // nu = r~.r with the r~ the callback returned
                 const int g2 = launch_dot(sc, h->rt.d(), h->r.d(), n, h->partB.d(), 0);
                 LAUNCHCHK(h, g2);
                 launch_reduce_final(sc, h->partB.d(), g2, dots_at(h, 0), 0, PRCG_S_NU, 1);
@@ -2542,7 +2585,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
             const int g1 = launch_pr_init_dots(sc, a);                      // nu = r~.r      pr_cg.py:109
             LAUNCHCHK(h, g1);
             int grid = 0;
-            if (h->cb_session) {
+            if (h->stored_tilde) {
                 if ((rc = pr_spmv_and_reduce(h, 0, g1))) return rc;                       // (s~ from the callback)
             } else {
                 if ((rc = dist_spmv(h, h->p.d(), h->s.d(), kEpiPR, h->r.d(), h->prec ? h->dinv.d() : nullptr,
@@ -2665,7 +2708,7 @@ int prcg_schedule(const prcg_t* h) {
     return ((h->fused || h->hs_fused || h->pr_fused || h->cg_fused) ? PRCG_SCHED_FUSED : 0) | (h->fused_comm ? PRCG_SCHED_FUSED_COMM : 0) |
            (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
-           (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
+           (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
            ((h->win ? h->win_vd : h->vd_int) ? PRCG_SCHED_VALDICT : 0) |
            (h->win ? (h->win_pat ? PRCG_SCHED_PATTERN : (h->win_geom < 2 ? PRCG_SCHED_COL8 : PRCG_SCHED_COL16)) | PRCG_SCHED_WINDOW

@@ -416,6 +416,14 @@ void launch_reduce_final(hipStream_t st, const double* partials, int nparts, dou
 void launch_copy(hipStream_t st, double* dst, int ds, const double* src, int ss, int64_t n);
 void launch_sub(hipStream_t st, double* dst, int ds, const double* a, int as, const double* b, int bs, int64_t n);
 void launch_mul(hipStream_t st, double* dst, int ds, const double* a, int as, const double* b, int bs, int64_t n);
+// ---- point-block Jacobi (prcg_blockjac.hip): dst = blockdiag(B_k) src, uniform block size bs in 1..8 ----
+// `blocks` is the DEVICE layout, not the caller's nb x bs x bs array: block_jacobi_layout re-lays it (entry j of the row
+// of lane t of 256-lane tile T at (T * bs + j) * 256 + t: coalesced for a fixed j) and returns the number of doubles
+// (out == nullptr: only that; -1 for bs outside 1..8).  Strides 1 or 2 (one column of a pair array).  0 / -1.
+int64_t block_jacobi_layout(int64_t n, int bs, const double* inv_blocks, double* out);
+int launch_block_jacobi(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t n, int bs, const double* blocks);
+// both columns of the interleaved [w u] array in one launch: wt = M^-1 w (mask bit 0), ut = M^-1 u (mask bit 1)
+int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask);
 // partial[slot] = sum (a[i*as] - b[i])^2
 int launch_diff_sq(hipStream_t st, const double* a, int as, const double* b, int64_t n, double* partials, int slot);
 // partial[slot] = sum a_i * b_i

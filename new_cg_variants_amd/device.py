@@ -163,12 +163,15 @@ class DeviceCSR:
         return WU, ms.value
 
     # -- solver session ------------------------------------------------------------------------
-    def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None):
-        """inv_diag: Jacobi on the device.  preconditioner: any callable v -> M^-1 v (what the reference's *_pcg
-        functions take); it runs on the host wherever the reference calls it (prcg.h: prcg_set_preconditioner)."""
+    def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None, block_jacobi=None):
+        """inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
+        the ceil(n/bs) x bs x bs inverses of the diagonal blocks (prcg.h: prcg_set_block_jacobi).  preconditioner: any
+        callable v -> M^-1 v (what the reference's *_pcg functions take); it runs on the host wherever the reference
+        calls it (prcg.h: prcg_set_preconditioner).  At most one of the three; a session without block_jacobi removes
+        the blocks an earlier session on this operator set."""
         b, x0 = L.f64(b), L.f64(x0)
         assert b.shape == (self.n,) and x0.shape == (self.n,)
-        assert inv_diag is None or preconditioner is None
+        assert sum(q is not None for q in (inv_diag, preconditioner, block_jacobi)) <= 1
         xt = None if x_true is None else L.f64(x_true)
         dv = None if inv_diag is None else L.f64(inv_diag)
         if preconditioner is not None:
@@ -190,6 +193,13 @@ class DeviceCSR:
         else:
             self._prec_fn = None
             self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
+        if block_jacobi is not None:
+            bs, blocks = int(block_jacobi[0]), L.f64(block_jacobi[1])
+            if not 1 <= bs <= 8 or blocks.shape != (-(-self.n // bs), bs, bs):
+                raise ValueError(f'block_jacobi: need 1 <= bs <= 8 and inv_blocks of shape (ceil(n/bs), bs, bs); got bs={bs}, {blocks.shape}')
+            self._check(self._lib.prcg_set_block_jacobi(self._h, bs, L.ptr(blocks)))
+        else:
+            self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
         self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
                                                L.ptr(xt), L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
@@ -229,7 +239,8 @@ class DeviceCSR:
                 'dual_comm': bool(s & 16), 'value_dict': bool(s & 32),
                 'col_bytes': 0 if s & 65536 else (1 if s & 64 else (2 if s & 128 else 4)), 'tile_steps': (s >> 8) & 15,
                 'pattern': bool(s & 65536), 'window': bool(s & 4096), 'fused_comm': bool(s & 8192), 'peer': bool(s & 16384), 'sliced_rows': bool(s & 32768),
-                'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152)}
+                'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152),
+                'block_jacobi': bool(s & 4194304)}
 
     def layout(self):
         """Diagnostic (prcg.h: prcg_debug_layout): what the summation order of the one-launch iteration's inner

@@ -6,7 +6,7 @@ callbacks (:37,:59), np.save the returned dict (:60) and write one row of the pa
 convergence table (:63-115).  This module does the same with the device solvers:
 
     python -m new_cg_variants_amd.experiments.figure_run --matrix ../matrices/bcsstk03.mtx \
-        --max-iter 1250 [--jacobi] [--methods hs_pcg,pr_pcg,pipe_pr_pcg] [--out ./data]
+        --max-iter 1250 [--jacobi | --block-jacobi BS] [--methods hs_pcg,pr_pcg,pipe_pr_pcg] [--out ./data]
 
 `--matrix` takes a MatrixMarket file or one of this repo's fixtures (tests/golden/matrix_*.npz).
 `--table tests/golden/paper_convergence_table.json --matrix-dir tests/golden` redoes every row of
@@ -41,7 +41,9 @@ def load_matrix(path):
 def run_matrix(A, max_iter, title, preconditioner=None, methods=DEVICE_METHODS, out='./data', progress=False,
                callbacks=None):
     """One (matrix, preconditioner) experiment: returns {method: trial dict} and saves each
-    (out=None: nothing is written).  callbacks=None: the reference's four histories."""
+    (out=None: nothing is written).  callbacks=None: the reference's four histories.
+    preconditioner: None, 'jacobi' or 'bjacobiBS' (point-block Jacobi on the device with BS x BS blocks, BS in 1..8;
+    no counterpart in the reference)."""
     N = A.shape[0]
     x_true = np.ones(N) / np.sqrt(N)                         # figure_gen.py:32
     b = A @ x_true                                           # :33
@@ -50,7 +52,14 @@ def run_matrix(A, max_iter, title, preconditioner=None, methods=DEVICE_METHODS, 
         [error_A_norm, residual_2_norm, error_2_norm, updated_residual_2_norm]
     if progress:
         callbacks.append(print_k(10))
-    prec = cgv.Jacobi(A) if preconditioner == 'jacobi' else (lambda v: v)
+    if preconditioner == 'jacobi':
+        prec = cgv.Jacobi(A)
+    elif preconditioner and preconditioner.startswith('bjacobi'):
+        prec = cgv.BlockJacobi(A, int(preconditioner[len('bjacobi'):]))
+    elif preconditioner is None:
+        prec = lambda v: v                                   # noqa: E731
+    else:
+        raise ValueError(f'unknown preconditioner {preconditioner!r}')
     if out is not None:
         folder = os.path.join(out, f'{title}_{preconditioner}')
         os.makedirs(folder, exist_ok=True)
@@ -125,7 +134,7 @@ def table_row(matrix_name, A, preconditioner, trials, methods=TABLE_METHODS):
         cells_it.append(('\\tableemph' if slow else '') + '{' + (str(its) if its else '-') + '}')
         cells_acc.append(('\\tableemph' if acc > 0.9 * acc0 else '') + '{' + f'{acc:1.2f}' + '}')
     name = '\\texttt{' + matrix_name.replace('_', '\\_') + '}'
-    prec = 'Jac.' if preconditioner == 'jacobi' else '-'
+    prec = 'Jac.' if preconditioner == 'jacobi' else ('BJac.' + preconditioner[len('bjacobi'):] if preconditioner else '-')
     return f'{name} & {prec} & {A.shape[0]} & {A.nnz}' + ''.join('& ' + c for c in cells_it) + \
         ''.join('&' + c for c in cells_acc) + '\\\\ \n'
 
@@ -138,6 +147,8 @@ def main():
     ap.add_argument('--matrix-dir', default='.', help='with --table: where tablemat_<name>.npz / <name>.mtx live')
     ap.add_argument('--cap', type=int, default=None, help='with --table: cap on max_iter per row')
     ap.add_argument('--jacobi', action='store_true')
+    ap.add_argument('--block-jacobi', type=int, default=None, metavar='BS',
+                    help='point-block Jacobi with BS x BS diagonal blocks (1..8), applied on the device')
     ap.add_argument('--methods', default=','.join(DEVICE_METHODS))
     ap.add_argument('--out', default='./data')
     args = ap.parse_args()
@@ -148,7 +159,9 @@ def main():
         ap.error('--matrix and --max-iter are required (or --table)')
     A = load_matrix(args.matrix)
     title = os.path.splitext(os.path.basename(args.matrix))[0].replace('matrix_', '')
-    prec = 'jacobi' if args.jacobi else None
+    if args.jacobi and args.block_jacobi is not None:
+        ap.error('--jacobi and --block-jacobi exclude each other')
+    prec = 'jacobi' if args.jacobi else (f'bjacobi{args.block_jacobi}' if args.block_jacobi is not None else None)
     methods = [m for m in args.methods.split(',') if m]
     trials = run_matrix(A, args.max_iter, title, prec, methods, args.out)
     for m in methods:
