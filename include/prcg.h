@@ -217,6 +217,8 @@ int prcg_iteration(const prcg_t* h);
 #define PRCG_SCHED_NT_LOADS 524288     /* sliced rows: value / column-code streams read with nontemporal loads (operator far larger than the Infinity Cache) */
 #define PRCG_SCHED_SELL_WINDOW 2097152 /* sliced rows with WINDOW codes: a slice's input entries staged in LDS, per nonzero an LDS read instead of a gather */
 #define PRCG_SCHED_BLOCK_JACOBI 4194304 /* stored-tilde schedule with M^-1 applied by the block-Jacobi kernel (prcg_set_block_jacobi) */
+#define PRCG_SCHED_XP_DEFERRED 8388608 /* single-GPU one-launch pipelined iteration: prcg_iterate runs its launches in pairs, the first of a
+                                          pair does not store (x,p) and the second rebuilds them bit for bit (PRCG_XP_DEFER=0: off) */
 /* 1048576: retired (was PRCG_SCHED_MEDIUM, the few-workgroup solver of mid-size systems); never to be reused */
 #define PRCG_SCHED_WINDOW 4096  /* row-per-lane window kernels (bands, stencils): the column stream holds indices into the tile's
                                    LDS-staged window of the input vector */

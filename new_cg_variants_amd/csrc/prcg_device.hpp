@@ -155,6 +155,9 @@ __device__ __forceinline__ Coefs predict(const double* __restrict__ dp, int meur
 struct FusedRowPtrs {
     double2* XP; double2* IN_NEW; double2* RS; const double* D; double* W; double* WT;
     bool stream;      // streaming stores for the row results (see store_pair)
+    // deferred (x,p) store (FusedPrev::xphase; wave-uniform, read once per wave): 1 = this launch does not store (x,p),
+    // 2 = the launch before did not: al_p, bt_p are ITS a, b and the row's (x,p) are rebuilt before they are used
+    int xphase = 0; double al_p = 0.0, bt_p = 0.0;
 };
 // the row's operands as loaded (ahead of time where the kernel can)
 struct FusedRowIn { double2 xp, rs; double d, w, wt; };
@@ -189,13 +192,20 @@ __device__ __forceinline__ double2 fused_row_update(int row, const double2& sum,
 {
     const double us = sum.y;                                   // u = A s  (A s~)
     const double wprev = RECOMP ? sum.x : q.w;                 // w = A r  (A r~), or the recurrence
-    const double xn = q.xp.x + cf.al * q.xp.y;                 // x += a p
+    double xo = q.xp.x, po = q.xp.y;
+    if (f.xphase == 2) {
+        // the update the previous launch computed and did not store: in_old.x is the r (r~) it wrote, q.xp its operands
+        const double pj = po;
+        po = in_old.x + f.bt_p * pj;                           // p = r + b p   (r~ with Jacobi)
+        xo = xo + f.al_p * pj;                                 // x += a p
+    }
+    const double xn = xo + cf.al * po;                         // x += a p
     if constexpr (!PREC) {
         const double rn = in_old.x - cf.al * in_old.y;         // r -= a s
         const double wn = wprev - cf.al * us;                  // w -= a u
-        const double pn = rn + cf.bt * q.xp.y;                 // p = r + b p
+        const double pn = rn + cf.bt * po;                     // p = r + b p
         const double sn = wn + cf.bt * in_old.y;               // s = w + b s
-        store_pair(f.XP + row, make_double2(xn, pn), f.stream);
+        if (f.xphase != 1) store_pair(f.XP + row, make_double2(xn, pn), f.stream);
         store_pair(f.IN_NEW + row, make_double2(rn, sn), f.stream);
         if constexpr (!RECOMP) f.W[row] = wn;
         acc[0] += pn * sn; acc[1] += rn * sn; acc[2] += sn * sn; acc[3] += rn * rn;
@@ -207,10 +217,10 @@ __device__ __forceinline__ double2 fused_row_update(int row, const double2& sum,
         const double rtn = in_old.x - cf.al * in_old.y;        // r~ -= a s~
         const double wn = wprev - cf.al * us;                  // w -= a u
         const double wtn = wtprev - cf.al * ut;                // w~ -= a u~
-        const double pn = rtn + cf.bt * q.xp.y;                // p = r~ + b p
+        const double pn = rtn + cf.bt * po;                    // p = r~ + b p
         const double sn = wn + cf.bt * q.rs.y;                 // s = w + b s
         const double stn = wtn + cf.bt * in_old.y;             // s~ = w~ + b s~
-        store_pair(f.XP + row, make_double2(xn, pn), f.stream);
+        if (f.xphase != 1) store_pair(f.XP + row, make_double2(xn, pn), f.stream);
         store_pair(f.RS + row, make_double2(rn, sn), f.stream);
         store_pair(f.IN_NEW + row, make_double2(rtn, stn), f.stream);
         if constexpr (!RECOMP) { f.W[row] = wn; f.WT[row] = wtn; }

@@ -289,6 +289,10 @@ struct prcg_handle {
     int stream_stores = 0;               // the one-launch iteration writes its row results with streaming stores: chosen per operator in
                                          // prcg_set_csr (vectors far larger than the 256 MB Infinity Cache), PRCG_STREAM_STORES=0|1 overrides
     int stream_override = -1;
+    // deferred (x,p) store (FusedPrev::xphase): a qualifying session runs prcg_iterate's launches as (SKIP, APPLY) pairs --
+    // one 16-byte store per row and pair of iterations less.  PRCG_XP_DEFER=0: every launch closes itself.
+    bool want_xp_defer = true;
+    int xphase = 0;                      // phase of the launch prcg_iterate issues next (0 outside its loop)
     int want_fused_comm_rccl = 0;        // PRCG_FUSED_COMM=1: one launch per iteration with the RCCL all-gather chain on the communication
                                          // stream (in-kernel wait for kernels of another stream: validated with one rank only -- opt-in)
     bool want_peer = true;               // PRCG_PEER=0: never use the peer exchange even when connected
@@ -600,8 +604,9 @@ int record(prcg_t* h, int k) {
     return allreduce(h, dots_at(h, k) + PRCG_S_RES2, 3, h->sc);
 }
 
-void prof_begin(prcg_t* h, std::vector<EventPair>& evs, int& count, int k, bool& on) {
-    on = h->prof_stride > 0 && (k % h->prof_stride) == 0 && count < kMaxProfSamples;
+// `shift`: sample iteration k when k - shift is a multiple of the stride (see iterate_pipe_fused)
+void prof_begin(prcg_t* h, std::vector<EventPair>& evs, int& count, int k, bool& on, int shift = 0) {
+    on = h->prof_stride > 0 && ((k - shift) % h->prof_stride) == 0 && count < kMaxProfSamples;
     if (!on) return;
     if ((int)evs.size() <= count) {
         EventPair ep;
@@ -749,6 +754,14 @@ void fused_flush(prcg_t* h) {
     }
 }
 
+// The session runs the deferred (x,p) store: single GPU, window operator, no recorder that reads x between two launches
+// of one prcg_iterate call.  Evaluated when asked (the option may change between calls; the arrays in memory are current
+// outside prcg_iterate's loop whatever the answer was).
+bool xp_deferred(const prcg_t* h) {
+    return h->want_xp_defer && h->in_session && is_pipe(h->variant) && h->fused && !h->fused_comm && !h->small && h->win && !h->multi() &&
+           !(h->hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM));
+}
+
 int iterate_pipe_fused(prcg_t* h, int k) {
     double* const bufA = h->prec ? h->rst.d() : h->rs.d();
     double* const bufB = h->prec ? h->rst2.d() : h->rs2.d();
@@ -763,7 +776,10 @@ int iterate_pipe_fused(prcg_t* h, int k) {
     }
     double* part_out = (h->pend_buf == h->partB.d()) ? h->partC.d() : h->partB.d();
     bool on = false;
-    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+    // SKIP and APPLY launches alternate: with an even sampling stride every sample would meet the same phase, so every
+    // second sample is taken one launch later -- the mean launch time is then the mean of both phases
+    const int ps = h->prof_stride;
+    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on, (h->xphase != 0 && ps > 0 && ps % 2 == 0) ? ((k / ps) & 1) : 0);
     const bool rec = pipe_recompute(h->variant);
     FusedState f{};
     f.in_old = rs_old; f.in_new = rs_new; f.xp = h->xp.d();
@@ -775,6 +791,8 @@ int iterate_pipe_fused(prcg_t* h, int k) {
     f.meurant = meurant(h->variant); f.recompute_w = rec;
     f.stream_stores = h->stream_stores;
     f.prev = prev;
+    f.prev.xphase = h->xphase;
+    f.prev.xcoef = h->xphase == 2 ? coef_at(h, k - 1) : nullptr;
     const int grid = eng_fused(h, h->sc, f);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
@@ -1312,6 +1330,7 @@ bool apply_option(prcg_t* h, const char* key, const char* val) {
     else if (k == "PRCG_PLACE") h->place_k = (v >= 0 && v <= 8) ? (int)v : 0;
     else if (k == "PRCG_SELL_NT") { h->sell_nt_opt = v != 0; h->sell_nt = v != 0; }
     else if (k == "PRCG_STREAM_STORES") h->stream_override = v != 0;
+    else if (k == "PRCG_XP_DEFER") h->want_xp_defer = v != 0;
     else if (k == "PRCG_EXT_SIGNAL") h->ext_signal = v != 0;
     else if (k == "PRCG_DEFER_GRID_PER_CU") h->defer_per_cu = (v >= 1 && v <= 4) ? (int)v : 0;
     else if (k == "PRCG_WIN_GRID_PER_CU") h->win_per_cu = (v >= 1 && v <= 32) ? (int)v : 0;
@@ -1324,7 +1343,7 @@ bool apply_option(prcg_t* h, const char* key, const char* val) {
 const char* const kOptionKeys[] = {"PRCG_FUSED", "PRCG_SMALL", "PRCG_COL16", "PRCG_COL8",
                                    "PRCG_VALDICT", "PRCG_GATHER", "PRCG_GATHER_MAX_BYTES", "PRCG_GRID_PER_CU",
                                    "PRCG_TILE_STEPS", "PRCG_WIN", "PRCG_WIN_GRID_PER_CU", "PRCG_WIN_MAX_MEAN", "PRCG_FUSED_COMM", "PRCG_WIN_ROWS", "PRCG_EXT_SIGNAL", "PRCG_DEFER_GRID_PER_CU",
-                                   "PRCG_WIN_SHARE", "PRCG_DEBUG_SHORT_SOURCES", "PRCG_PEER", "PRCG_STREAM_STORES", "PRCG_SELL", "PRCG_SELL_GRID_PER_CU", "PRCG_SELL_SIGMA", "PRCG_SELL_PLANES", "PRCG_PLACE", "PRCG_SELL_NT", "PRCG_SELL_RUNS", "PRCG_SELL_WINDOW", "PRCG_SELL_MAX_OVERHEAD_PCT", "PRCG_PR_PACK", "PRCG_CG_ONE", "PRCG_WIN_BIG", "PRCG_WIN_PAT", "PRCG_WIN_SWEEP", "PRCG_SWEEP_WAVES"};
+                                   "PRCG_WIN_SHARE", "PRCG_DEBUG_SHORT_SOURCES", "PRCG_PEER", "PRCG_STREAM_STORES", "PRCG_SELL", "PRCG_SELL_GRID_PER_CU", "PRCG_SELL_SIGMA", "PRCG_SELL_PLANES", "PRCG_PLACE", "PRCG_SELL_NT", "PRCG_SELL_RUNS", "PRCG_SELL_WINDOW", "PRCG_SELL_MAX_OVERHEAD_PCT", "PRCG_PR_PACK", "PRCG_CG_ONE", "PRCG_WIN_BIG", "PRCG_WIN_PAT", "PRCG_WIN_SWEEP", "PRCG_SWEEP_WAVES", "PRCG_XP_DEFER"};
 
 int h2d(prcg_t* h, double* dst, const double* src, int64_t count) {
     HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyHostToDevice, h->sc));
@@ -2643,9 +2662,13 @@ int prcg_iterate(prcg_t* h, int iters) {
         h->k += iters;
         return PRCG_OK;
     }
+    // deferred (x,p) store: (SKIP, APPLY) pairs counted from the start of the call, an odd last launch closes itself --
+    // when the loop ends the arrays in memory are current
+    const int n_paired = xp_deferred(h) ? (iters & ~1) : 0;
     for (int i = 0; i < iters; ++i) {
         const int k = h->k + 1;
         int rc;
+        h->xphase = i < n_paired ? 1 + (i & 1) : 0;
         if (is_pipe(h->variant)) rc = iterate_pipe(h, k);
         else if (h->variant == PRCG_HS) rc = h->hs_fused ? iterate_hs_fused(h, k) : iterate_hs(h, k);
         else if (is_cg_family(h->variant) && h->cg_one) rc = iterate_cg_one(h, k);
@@ -2656,6 +2679,7 @@ int prcg_iterate(prcg_t* h, int iters) {
         if ((rc = record(h, k))) return rc;
         h->k = k;
     }
+    h->xphase = 0;
     if (h->fused && !h->fused_comm) fused_flush(h);    // dots of the last iteration: one reduction per call, not per iteration
     if (h->hs_fused) hs_flush(h);
     if (h->pr_fused) { fused_flush(h); pr_unpack(h); }
@@ -2709,6 +2733,7 @@ int prcg_schedule(const prcg_t* h) {
            (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
            (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
+           (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
            ((h->win ? h->win_vd : h->vd_int) ? PRCG_SCHED_VALDICT : 0) |
            (h->win ? (h->win_pat ? PRCG_SCHED_PATTERN : (h->win_geom < 2 ? PRCG_SCHED_COL8 : PRCG_SCHED_COL16)) | PRCG_SCHED_WINDOW

@@ -91,6 +91,12 @@ struct FusedPrev {
         double* z0n; double* z1n; double* z2n;
         double* x; double* p; double* r; double* s; const double* d; double* coef_prev;
     } lag;
+    // deferred (x,p) store of the single-GPU one-launch iteration (window operators): x and p are row-local, so a launch
+    // may leave its (x,p) unwritten and the NEXT launch rebuilds them from the unchanged pair in memory, the row's own
+    // entry of the old input pairs (r or r~ of the skipped iteration) and that iteration's a, b -- same operands, same
+    // expressions, the same bits.  xphase 0: the launch closes itself; 1 (SKIP): no store to XP; 2 (APPLY): rebuild
+    // first, xcoef = the skipped iteration's stored coefficients {a, b} (coef[k-1]: the very doubles that launch used).
+    int xphase; const double* xcoef;
 };
 // State of the one-launch pipelined iteration (pipe_pr_cg.py:61-75 unpreconditioned, :169-187 Jacobi):
 // the two-vector product of the SpMM input pair array `in_old` with the NEXT vector update applied row

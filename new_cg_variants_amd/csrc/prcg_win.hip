@@ -915,6 +915,11 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
                      fz.pr, lane, nullptr, 0, nullptr, 0, &fz.lag, fz.nprev > 0,
                      CW == 32 && DEF == 0 && A.sweep_waves > 0 && A.sweep_waves == (int)gridDim.x * WPB};
     WCtx<NV>& cm = c;
+    if constexpr (FUSED && DEF == 0) {
+        // deferred (x,p) store: the phase and the skipped iteration's coefficients, scalar loads once per wave
+        cm.fr.xphase = fz.xphase;
+        if (fz.xphase == 2) { cm.fr.al_p = fz.xcoef[0]; cm.fr.bt_p = fz.xcoef[1]; }
+    }
     if constexpr (DEF > 0) {
         if (fz.px) {
             // direct peer exchange: this launch is iteration k = want + 1; it reads the ghost rows of iteration k - 1 from
