@@ -219,6 +219,7 @@ int prcg_iteration(const prcg_t* h);
 #define PRCG_SCHED_BLOCK_JACOBI 4194304 /* stored-tilde schedule with M^-1 applied by the block-Jacobi kernel (prcg_set_block_jacobi) */
 #define PRCG_SCHED_XP_DEFERRED 8388608 /* single-GPU one-launch pipelined iteration: prcg_iterate runs its launches in pairs, the first of a
                                           pair does not store (x,p) and the second rebuilds them bit for bit (PRCG_XP_DEFER=0: off) */
+#define PRCG_SCHED_RHS2 16777216 /* the session solves TWO right-hand sides (prcg_solve_begin_multi): one two-vector product per iteration */
 /* 1048576: retired (was PRCG_SCHED_MEDIUM, the few-workgroup solver of mid-size systems); never to be reused */
 #define PRCG_SCHED_WINDOW 4096  /* row-per-lane window kernels (bands, stencils): the column stream holds indices into the tile's
                                    LDS-staged window of the input vector */
@@ -272,6 +273,33 @@ int prcg_get_coefficients(prcg_t* h, int k, double* out);
 /* histories: for each bit set in hist_mask (ascending bit order) max_iter doubles;
  * entries beyond the current iteration are 0, as numpy.zeros(max_iter) leaves them. */
 int prcg_get_history(prcg_t* h, double* hist);
+/* ---- Hestenes-Stiefel with TWO right-hand sides in one session --------------------------------
+ * Replaces TWO calls of the reference's hs_cg (numerical_experiments/cg_variants/hs_cg.py:9) or hs_pcg (:70) on one
+ * matrix: load cases, time steps with a frozen operator, columns of a block solve.  The two recurrences stay what they are
+ * -- each column has its own a_k, b_k, inner products and history, nothing of one column enters the other (a breakdown of
+ * one leaves the other's bits untouched) -- but every iteration streams the operator ONCE: s = A p of both columns is one
+ * two-vector product (what prcg_spmm2 runs), on assembled FEM matrices most of an iteration's memory traffic.
+ *   variant: PRCG_HS only.  nrhs: 2 only.  b, x0: nrhs pointers to n_rows host doubles each.  inv_diag != NULL: hs_pcg with
+ *   Jacobi, the same diagonal for both columns.  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.
+ * Single GPU, whole operators: refused (PRCG_EINVAL, text names the reason) with a communicator on the handle, n_ghost > 0,
+ * a host-callback or block-Jacobi preconditioner or a replace hook set, another variant, nrhs, or history bit.
+ * prcg_iterate / prcg_sync / prcg_iteration / prcg_set_profiling / prcg_get_timings serve the session as they are.  State is
+ * read per column j = 0, 1 with the calls below; the single-column accessors (prcg_get_vector, prcg_set_vector,
+ * prcg_get_scalars, prcg_set_scalars, prcg_get_coefficients, prcg_get_history, prcg_set_iteration) are refused while it
+ * is open.  A later prcg_solve_begin on the handle opens an ordinary session again.
+ * Every inner product is summed in one fixed order: results are reproducible bit for bit, and
+ * exchanging the two right-hand sides exchanges the two results bit for bit. */
+int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
+                           int max_iter, const double* inv_diag, uint32_t hist_mask);
+/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi); out: n_rows host doubles */
+int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out);
+/* PRCG_NUM_SCALARS doubles: mu, nu, rr of column j at iteration k in their slots, every other slot 0 */
+int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out);
+/* out[0] = alpha, out[1] = beta used BY iteration k (k >= 1) of column j, out[2] = 0 */
+int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out);
+/* max_iter doubles: column j's updated_residual_2_norm history (nothing is written when hist_mask was 0) */
+int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
+
 /* HIP-event sampling of the SpMV/SpMM and update launches inside prcg_iterate:
  * every `stride`-th iteration is bracketed (0 = off).  Read back with prcg_get_timings. */
 int prcg_set_profiling(prcg_t* h, int stride);

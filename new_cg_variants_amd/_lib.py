@@ -77,6 +77,11 @@ _SIGNATURES = {
     'prcg_set_scalars': (C.c_int, [_P, C.c_int, _P]),
     'prcg_get_coefficients': (C.c_int, [_P, C.c_int, _P]),
     'prcg_get_history': (C.c_int, [_P, _P]),
+    'prcg_solve_begin_multi': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_uint32]),
+    'prcg_get_vector_rhs': (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    'prcg_get_scalars_rhs': (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    'prcg_get_coefficients_rhs': (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    'prcg_get_history_rhs': (C.c_int, [_P, C.c_int, _P]),
     'prcg_set_profiling': (C.c_int, [_P, C.c_int]),
     'prcg_get_timings': (C.c_int, [_P, C.POINTER(Timings)]),
     'prcg_solve': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_uint32, _P, _P, C.POINTER(Timings)]),

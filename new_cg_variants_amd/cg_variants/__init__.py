@@ -324,6 +324,76 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
     return output
 
 
+def _run_multi(name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
+    """Two right-hand sides of one matrix in ONE Hestenes-Stiefel session (prcg.h: prcg_solve_begin_multi): what two calls
+    of hs_cg / hs_pcg compute, with the operator streamed once per iteration for both.  Every argument is checked before
+    the device is touched; what the session does not serve raises ValueError -- nothing falls back to two sessions."""
+    if A.format != 'csr':
+        A = A.tocsr()
+    n = A.shape[0]
+    B, X0 = np.asarray(B, dtype=np.float64), np.asarray(X0, dtype=np.float64)
+    for nm, V in (('B', B), ('X0', X0)):
+        if V.shape != (2, n):
+            raise ValueError(f'{name}: {nm} must have shape (2, {n}) -- two right-hand sides of the operator\'s size -- got {V.shape}')
+    for key in ('x_true', 'w_replace'):
+        if kwargs.get(key) is not None:
+            raise ValueError(f'{name}: {key} is not served by the two-RHS session')
+    inv_diag, prec_fn = _diagonal_of(preconditioner, n)
+    if prec_fn is not None:
+        kind = 'a block-Jacobi preconditioner' if _blocks_of(prec_fn) is not None else 'a preconditioner that is no diagonal scaling'
+        raise ValueError(f'{name}: {kind} is not served by the two-RHS session (Jacobi(A), a callable that acts as a diagonal, or None)')
+    mask = 0
+    light = []
+    for cb in callbacks:
+        cname = getattr(cb, 'prcg_recorder', None) or getattr(cb, '__name__', '')
+        if cname == 'updated_residual_2_norm':
+            mask |= L.HIST_BITS[cname]
+        elif cname in RECORDER_NAMES:
+            raise ValueError(f'{name}: recorder {cname} is not served by the two-RHS session (updated_residual_2_norm only)')
+        elif getattr(cb, 'prcg_host_light', False) or cname == 'pk':
+            light.append(cb)
+        else:
+            raise ValueError(f'{name}: callback {cname or cb!r} needs the state vectors every iteration: not served by the two-RHS '
+                             'session (the updated_residual_2_norm recorder and light host callbacks are)')
+    op = _operator(A, int(kwargs.get('device', 0)))
+    op.set_replace_hook(None)
+    op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
+    op.begin_multi(L.HS, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(2)]
+
+    def call_host(k):
+        for j in range(2):
+            env = {'output': outputs[j], 'k': k, 'max_iter': max_iter, 'A': A, 'b': B[j], 'x0': X0[j], 'n': n,
+                   'kwargs': kwargs, 'callbacks': callbacks}
+            for cb in light:
+                cb(**env)
+
+    if light:
+        call_host(0)
+        for k in range(1, max_iter):
+            op.iterate(1)
+            call_host(k)
+    else:
+        op.iterate(max_iter - 1)
+    op.sync()
+    for j in range(2):
+        outputs[j].update(op.history(rhs=j))
+    return outputs
+
+
+def hs_cg_multi(A, B, X0, max_iter, callbacks=[], **kwargs):
+    """hs_cg (hs_cg.py:9) for TWO right-hand sides of one matrix: B, X0 of shape (2, n); returns a list of two trial dicts
+    shaped like hs_cg's.  One session, one pass over the operator per iteration."""
+    if kwargs.pop('preconditioner', None) is not None:
+        raise ValueError('hs_cg_multi takes no preconditioner: use hs_pcg_multi')
+    return _run_multi('hs_cg_multi', A, B, X0, max_iter, None, callbacks, kwargs)
+
+
+def hs_pcg_multi(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
+    """hs_pcg (hs_cg.py:70) for TWO right-hand sides of one matrix, with Jacobi(A) or a callable that probes as a diagonal."""
+    return _run_multi('hs_pcg_multi', A, B, X0, max_iter, preconditioner, callbacks, kwargs)
+
+
 def _make(variant, name, preconditioned):
     def take_w_replace(kwargs):
         # gv_cg.py:9 / :93 take a residual-replacement predicate (default: never); the other variants swallow the keyword
@@ -366,4 +436,4 @@ pipe_pr_m_pcg = _make(L.PIPE_PR_M, 'pipe_pr_m_pcg', True) # pipe_pr_cg.py:213
 __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr_pcg', 'm_cg', 'm_pcg',
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
-           'clear_operator_cache']
+           'hs_cg_multi', 'hs_pcg_multi', 'clear_operator_cache']

@@ -14,6 +14,18 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kElemsPerTrip = kBlock * 2;   // update kernels: 2 elements per thread per trip
 
+// Host side of the update kernels: block b owns `trips` consecutive trips of kElemsPerTrip elements (tests/device_order.py: chunking)
+struct Chunking { int grid; int trips; };
+inline Chunking chunking(int64_t n) {
+    const int64_t total = (n + kElemsPerTrip - 1) / kElemsPerTrip;
+    int64_t grid = total < kMaxGridBlocks ? total : kMaxGridBlocks;
+    if (grid < 1) grid = 1;
+    const int64_t trips = (total + grid - 1) / grid;
+    grid = trips > 0 ? (total + trips - 1) / trips : 1;
+    if (grid < 1) grid = 1;
+    return {(int)grid, (int)(trips > 0 ? trips : 1)};
+}
+
 // The butterfly v += v[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1: every lane ends with the same sum, added in the same tree.  The steps
 // inside a row of 16 lanes are data-parallel-primitive moves (VALU, no trip through the LDS crossbar as __shfl_xor makes): row_ror:8 IS
 // lane ^ 8; row_ror:4 hands a lane the value of lane ^ 4 or of (lane ^ 4) ^ 8 -- the same bits, since the ^ 8 step has been done;

@@ -190,6 +190,8 @@ struct prcg_handle {
     DevBuf r2, s2, rt2, st2;     // one-launch predict-and-recompute: the second copies of r, s (r~, s~ with Jacobi)
     DevBuf x, xp, p, p2, rs, rs2, rst, rst2, wu, wt, wv, r, s, rt, st, b, xt, dinv, e_ext;
     DevBuf w, u, tvec;           // cg_cg / gv: w (ghost room), u, t = A w~
+    bool rhs2 = false;           // session type "Hestenes-Stiefel, two right-hand sides" (prcg_solve_begin_multi): the state is the five
+    DevBuf mx, mr, mp, ms, mrt;  // ... interleaved n x 2 arrays X, R, P, S, RT (Hs2Args, prcg_kernels.h); dots / coef hold both columns per row
     bool fused = false;          // this session runs the one-launch-per-iteration pipelined kernel
     bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
     bool want_fused_comm = true; // PRCG_FUSED_COMM=0: communicator sessions keep the two-kernel schedule
@@ -315,7 +317,7 @@ struct prcg_handle {
     // every vector a window launch may stage (the pointer handed to the launch lies inside one of them)
     const DevBuf* owner(const void* ptr) const {
         const DevBuf* all[] = {&tmp_ext, &t1, &x, &xp, &p, &p2, &rs, &rs2, &rst, &rst2, &wu, &wt, &wv, &r, &r2, &s, &s2, &rt, &rt2,
-                               &st, &st2, &b, &xt, &dinv, &e_ext, &w, &w2, &u, &u2, &tvec, &t2, &ut, &cb_stage, &q, &q2};
+                               &st, &st2, &b, &xt, &dinv, &e_ext, &w, &w2, &u, &u2, &tvec, &t2, &ut, &cb_stage, &q, &q2, &mx, &mp};
         const char* c = static_cast<const char*>(ptr);
         for (const DevBuf* d : all)
             if (d->p && c >= static_cast<const char*>(d->p) && c < static_cast<const char*>(d->p) + d->bytes) return d;
@@ -357,6 +359,11 @@ int fail(prcg_t* h, int code, const char* fmt, ...) {
         if (g__ == -2) return PRCG_EINVAL;        /* refused by check_sources: message set */  \
         if (g__ < 0) return fail(h, PRCG_EHIP, "kernel launch failed (%s:%d)", __FILE__, __LINE__); \
     } while (0)
+
+// the single-column accessors do not answer for column 0 of a two-RHS session
+#define NOT_RHS2(h, name)                                                                     \
+    CHECK(h, !(h)->rhs2, name ": the open session has two right-hand sides: it is read per column with "               \
+                         "prcg_get_vector_rhs / _scalars_rhs / _coefficients_rhs / _history_rhs and has no setters")
 
 #define CHECK(h, cond, ...)                                                                   \
     do { if (!(cond)) return fail(h, PRCG_EINVAL, __VA_ARGS__); } while (0)
@@ -950,6 +957,43 @@ void hs_flush(prcg_t* h) {
         launch_reduce_final(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), 0, PRCG_S_MU, 1);
         h->hs_pend_mu = 0;
     }
+}
+
+// Two right-hand sides in one Hestenes-Stiefel session (hs_cg.py:54-62 / hs_pcg :116-125 for each column): the vector
+// kernels of prcg_rhs2.hip around ONE two-vector product of [p_0 p_1] -- the operator is streamed once for both systems.
+Hs2Args hs2_args(prcg_t* h, int k) {
+    Hs2Args a{};
+    a.n = h->n;
+    a.x = h->mx.d(); a.r = h->mr.d(); a.rt = h->prec ? h->mrt.d() : nullptr; a.p = h->mp.d(); a.s = h->ms.d();
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, k - 1) : nullptr;
+    a.dots_cur = dots_at(h, k);
+    a.coef_out = coef_at(h, k);
+    a.partials = h->partA.d();
+    return a;
+}
+// s = A p for both columns, then mu_c = p.s (a launch of its own: the two-vector products have no dot epilogue)
+int hs2_product_and_mu(prcg_t* h, int k, Hs2Args a) {
+    bool on = false;
+    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+    LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, h->mp.d(), h->ms.d(), 3));
+    prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+    a.partials = h->partB.d();
+    const int g = launch_hs2_dot_ps(h->sc, a);
+    LAUNCHCHK(h, g);
+    launch_reduce_final(h->sc, h->partB.d(), g, dots_at(h, k), kHs2Mu, kHs2Mu, 2);
+    return PRCG_OK;
+}
+int iterate_hs2(prcg_t* h, int k) {
+    Hs2Args a = hs2_args(h, k);
+    bool on = false;
+    prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
+    const int g1 = launch_hs2_update_xr(h->sc, a);
+    LAUNCHCHK(h, g1);
+    prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    launch_reduce_final(h->sc, h->partA.d(), g1, dots_at(h, k), kHs2Nu, kHs2Nu, 4);     // nu_0, rr_0, nu_1, rr_1
+    LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));
+    return hs2_product_and_mu(h, k, a);
 }
 
 // hs_cg.py:54-62 (hs_pcg :116-125) on one GPU without reduction launches.  The two inner products still separate
@@ -2336,6 +2380,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     const int64_t n = h->n, ne = h->n + h->g + kGatherPad;
     const size_t D = sizeof(double);
     h->in_session = false;
+    h->rhs2 = false;
     h->variant = variant;
     h->fused = false;
     h->hs_fused = false;
@@ -2631,6 +2676,14 @@ int prcg_iterate(prcg_t* h, int iters) {
     if (h->fused_comm && *h->err_host != 0u)
         return fail(h, PRCG_ERCCL, "a one-launch iteration waited more than its bound for the other ranks (a peer stalled or died); "
                                    "the session's results are invalid -- PRCG_PEER=0 / PRCG_FUSED_COMM=0 select the two-kernel schedule");
+    if (h->rhs2) {
+        for (int i = 0; i < iters; ++i) {
+            const int rc = iterate_hs2(h, h->k + 1);
+            if (rc) return rc;
+            ++h->k;
+        }
+        return PRCG_OK;
+    }
     if (h->small_hs && iters > 0) {
         // Hestenes-Stiefel: all `iters` iterations inside one launch of one workgroup
         hs_flush(h);
@@ -2733,7 +2786,7 @@ int prcg_schedule(const prcg_t* h) {
            (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
            (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
-           (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) |
+           (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) | (h->rhs2 ? PRCG_SCHED_RHS2 : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
            ((h->win ? h->win_vd : h->vd_int) ? PRCG_SCHED_VALDICT : 0) |
            (h->win ? (h->win_pat ? PRCG_SCHED_PATTERN : (h->win_geom < 2 ? PRCG_SCHED_COL8 : PRCG_SCHED_COL16)) | PRCG_SCHED_WINDOW
@@ -2743,6 +2796,7 @@ int prcg_schedule(const prcg_t* h) {
 int prcg_set_iteration(prcg_t* h, int k) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_set_iteration: no open session");
+    NOT_RHS2(h, "prcg_set_iteration");
     CHECK(h, k >= 0 && k < h->max_iter, "prcg_set_iteration: k out of range");
     h->k = k;
     if (h->peer && is_pipe(h->variant)) {
@@ -2772,6 +2826,7 @@ int prcg_set_iteration(prcg_t* h, int k) {
 int prcg_get_vector(prcg_t* h, int which, double* out) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && out, "prcg_get_vector: no session or null buffer");
+    NOT_RHS2(h, "prcg_get_vector");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int64_t n = h->n;
@@ -2801,6 +2856,7 @@ int prcg_get_vector(prcg_t* h, int which, double* out) {
 int prcg_set_vector(prcg_t* h, int which, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in, "prcg_set_vector: no session or null buffer");
+    NOT_RHS2(h, "prcg_set_vector");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int64_t n = h->n;
@@ -2820,6 +2876,7 @@ int prcg_set_vector(prcg_t* h, int which, const double* in) {
 int prcg_get_scalars(prcg_t* h, int k, double* out) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && out && k >= 0 && k <= h->max_iter, "prcg_get_scalars: bad argument");
+    NOT_RHS2(h, "prcg_get_scalars");
     int rc = prcg_sync(h);
     if (rc) return rc;
     return d2h(h, out, dots_at(h, k), kNS);
@@ -2828,6 +2885,7 @@ int prcg_get_scalars(prcg_t* h, int k, double* out) {
 int prcg_set_scalars(prcg_t* h, int k, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in && k >= 0 && k <= h->max_iter, "prcg_set_scalars: bad argument");
+    NOT_RHS2(h, "prcg_set_scalars");
     int rc = prcg_sync(h);
     if (rc) return rc;
     if ((rc = h2d(h, dots_at(h, k), in, kNS))) return rc;
@@ -2842,6 +2900,7 @@ int prcg_set_scalars(prcg_t* h, int k, const double* in) {
 int prcg_get_coefficients(prcg_t* h, int k, double* out) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && out && k >= 1 && k <= h->max_iter, "prcg_get_coefficients: bad argument");
+    NOT_RHS2(h, "prcg_get_coefficients");
     int rc = prcg_sync(h);
     if (rc) return rc;
     return d2h(h, out, coef_at(h, k), 3);
@@ -2850,6 +2909,7 @@ int prcg_get_coefficients(prcg_t* h, int k, double* out) {
 int prcg_get_history(prcg_t* h, double* hist) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && hist, "prcg_get_history: no session or null buffer");
+    NOT_RHS2(h, "prcg_get_history");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int m = h->max_iter;
@@ -2864,6 +2924,132 @@ int prcg_get_history(prcg_t* h, double* hist) {
             dst[k] = k <= h->k ? std::sqrt(all[(size_t)k * kNS + slot_of_bit[bit]]) : 0.0;
         ++row;
     }
+    return PRCG_OK;
+}
+
+// ---- Hestenes-Stiefel, two right-hand sides in one session ----
+int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
+                           const double* inv_diag, uint32_t hist_mask) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, h->have_csr, "prcg_solve_begin_multi: call prcg_set_csr first");
+    CHECK(h, nrhs == 2, "prcg_solve_begin_multi: nrhs = %d: the multi-RHS session serves exactly 2 right-hand sides", nrhs);
+    CHECK(h, variant == PRCG_HS, "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg) only", variant);
+    CHECK(h, !h->multi(), "prcg_solve_begin_multi: a communicator is set on the handle: the two-RHS session runs on one GPU");
+    CHECK(h, h->g == 0, "prcg_solve_begin_multi: n_ghost = %lld > 0: the two-RHS session serves whole operators only", (long long)h->g);
+    CHECK(h, h->cb == nullptr, "prcg_solve_begin_multi: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
+                               "session serves Jacobi (inv_diag) or none");
+    CHECK(h, h->bj_bs == 0, "prcg_solve_begin_multi: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
+                            "session serves Jacobi (inv_diag) or none");
+    CHECK(h, h->replace_fn == nullptr, "prcg_solve_begin_multi: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session");
+    CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+          "prcg_solve_begin_multi: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the two-RHS session");
+    CHECK(h, b && x0 && b[0] && b[1] && x0[0] && x0[1], "prcg_solve_begin_multi: null b or x0");
+    CHECK(h, max_iter >= 1, "prcg_solve_begin_multi: max_iter must be >= 1");
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int64_t n = h->n, ne = h->n + kGatherPad;
+    const size_t D = sizeof(double);
+    // what prcg_solve_begin resets, so that prcg_schedule / prcg_sync / a later ordinary session see no stale schedule
+    h->in_session = false;
+    h->variant = PRCG_HS;
+    h->fused = false; h->hs_fused = false; h->cg_fused = false; h->pr_fused = false; h->pr_packed = false;
+    h->hs_pend_mu = 0;
+    h->small = false; h->small_hs = false;
+    h->gather = false;
+    h->bj_session = false; h->stored_tilde = false;
+    h->prec = inv_diag != nullptr;
+    h->max_iter = max_iter;
+    h->hist_mask = hist_mask;
+    h->have_xtrue = false;
+    h->k = 0;
+    h->n_ev_spmv = h->n_ev_upd = 0;
+    h->rhs2 = true;
+    // X and P feed the two-vector product: like every product source they carry the spare entries behind row n
+    HIPCHK(h, h->mx.ensure((size_t)2 * ne * D, h->sc));
+    HIPCHK(h, h->mp.ensure((size_t)2 * ne * D, h->sc));
+    HIPCHK(h, h->mr.ensure((size_t)2 * n * D, h->sc));
+    HIPCHK(h, h->ms.ensure((size_t)2 * n * D, h->sc));
+    HIPCHK(h, h->mrt.ensure(h->prec ? (size_t)2 * n * D : 16, h->sc));
+    HIPCHK(h, h->dinv.ensure((size_t)ne * D, h->sc));
+    HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * kNS * D, h->sc));
+    HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * kCoefStride * D, h->sc));
+    std::vector<double> pairs;
+    try { pairs.resize((size_t)2 * n); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "prcg_solve_begin_multi: host staging"); }
+    int rc;
+    for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = x0[0][i]; pairs[2 * i + 1] = x0[1][i]; }
+    if ((rc = h2d(h, h->mx.d(), pairs.data(), 2 * n))) return rc;
+    for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = b[0][i]; pairs[2 * i + 1] = b[1][i]; }
+    if ((rc = h2d(h, h->mr.d(), pairs.data(), 2 * n))) return rc;
+    if (inv_diag && (rc = h2d(h, h->dinv.d(), inv_diag, n))) return rc;
+    hipStream_t sc = h->sc;
+    // r = b - A x0 for both columns (hs_cg.py:23): one two-vector product of [x0_0 x0_1], parked in S
+    LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->mx.d(), h->ms.d(), 3));
+    launch_sub(sc, h->mr.d(), 1, h->mr.d(), 1, h->ms.d(), 1, 2 * n);
+    Hs2Args a = hs2_args(h, 0);
+    const int g1 = launch_hs2_init_dots(sc, a);                              // (r~ = d r); nu = r.r~, r.r   :25 / :86-88
+    LAUNCHCHK(h, g1);
+    launch_reduce_final(sc, h->partA.d(), g1, dots_at(h, 0), kHs2Nu, kHs2Nu, 4);
+    launch_copy(sc, h->mp.d(), 1, h->prec ? h->mrt.d() : h->mr.d(), 1, 2 * n);   // p = r~ (r)   :24 / :87
+    if ((rc = hs2_product_and_mu(h, 0, a))) return rc;                       // s = A p, mu = p.s   :26-27
+    HIPCHK(h, hipStreamSynchronize(sc));
+    h->in_session = true;
+    return PRCG_OK;
+}
+
+#define NEED_RHS2(h, name, j)                                                                                        \
+    do {                                                                                                              \
+        CHECK(h, (h)->in_session && (h)->rhs2, name ": no open two-RHS session (prcg_solve_begin_multi)");             \
+        CHECK(h, (j) == 0 || (j) == 1, name ": right-hand side %d out of range (0, 1)", (int)(j));                      \
+    } while (0)
+
+int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_vector_rhs", j);
+    CHECK(h, out, "prcg_get_vector_rhs: null buffer");
+    const DevBuf* src = which == PRCG_VEC_X ? &h->mx : which == PRCG_VEC_R ? &h->mr : which == PRCG_VEC_P ? &h->mp :
+                        which == PRCG_VEC_S ? &h->ms : (which == PRCG_VEC_RT && h->prec) ? &h->mrt : nullptr;
+    CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the two-RHS session (x, r, p, s; rt with Jacobi)", which);
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    launch_copy(h->sc, h->t1.d(), 1, src->d() + j, 2, h->n);
+    return d2h(h, out, h->t1.d(), h->n);
+}
+
+int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_scalars_rhs", j);
+    CHECK(h, out && k >= 0 && k <= h->max_iter, "prcg_get_scalars_rhs: bad argument");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    double row[kNS];
+    if ((rc = d2h(h, row, dots_at(h, k), kNS))) return rc;
+    for (int q = 0; q < kNS; ++q) out[q] = 0.0;
+    out[PRCG_S_MU] = row[kHs2Mu + j]; out[PRCG_S_NU] = row[kHs2Nu + 2 * j]; out[PRCG_S_RR] = row[kHs2Rr + 2 * j];
+    return PRCG_OK;
+}
+
+int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_coefficients_rhs", j);
+    CHECK(h, out && k >= 1 && k <= h->max_iter, "prcg_get_coefficients_rhs: bad argument");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    double row[kCoefStride];
+    if ((rc = d2h(h, row, coef_at(h, k), kCoefStride))) return rc;
+    out[0] = row[2 * j]; out[1] = row[2 * j + 1]; out[2] = 0.0;      // Hestenes-Stiefel predicts no nu
+    return PRCG_OK;
+}
+
+int prcg_get_history_rhs(prcg_t* h, int j, double* hist) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_history_rhs", j);
+    CHECK(h, hist, "prcg_get_history_rhs: null buffer");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    if (!(h->hist_mask & PRCG_HIST_UPDATED_RESIDUAL_2_NORM)) return PRCG_OK;
+    const int m = h->max_iter;
+    std::vector<double> all((size_t)(m + 1) * kNS);
+    if ((rc = d2h(h, all.data(), h->dots.d(), (int64_t)(m + 1) * kNS))) return rc;
+    for (int k = 0; k < m; ++k) hist[k] = k <= h->k ? std::sqrt(all[(size_t)k * kNS + kHs2Rr + 2 * j]) : 0.0;
     return PRCG_OK;
 }
 

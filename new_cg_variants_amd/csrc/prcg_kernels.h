@@ -394,6 +394,25 @@ int launch_hs_update_p(hipStream_t st, const HsArgs& a, const double* prev_nu = 
                        double* dots_cur_w = nullptr);    // p = z + beta p
 int launch_hs_init_dots(hipStream_t st, const HsArgs& a);   // nu, rr of the initial state
 
+// ---- Hestenes-Stiefel, TWO right-hand sides in one session (prcg_rhs2.hip; prcg_solve_begin_multi) ----
+// x, r, rt, p, s: interleaved n x 2 arrays, row i = (column 0, column 1) -- p and s are directly the input and output of the
+// two-vector product.  d: the inverse diagonal (n doubles, shared by both columns) or null.  The scalars of one iteration
+// are ONE row of kPartialStride doubles holding both columns, the coefficients one row of four:
+//   scalars  [mu_0, mu_1, -, nu_0, rr_0, nu_1, rr_1, -]        coefficients  [a_0, b_0, a_1, b_1]
+// so that one launch_reduce_final serves both columns of a reduction (slots 0..1 of the product dot, 3..6 of the update).
+constexpr int kHs2Mu = 0, kHs2Nu = 3, kHs2Rr = 4;      // slot of column c: kHs2Mu + c, kHs2Nu + 2 c, kHs2Rr + 2 c
+struct Hs2Args {
+    int64_t n;
+    double* x; double* r; double* rt; double* p; const double* s; const double* d;
+    const double* dots_prev; const double* dots_cur; double* coef_out; double* partials;
+};
+// every inner product of this session type is summed in the order of tests/device_order.py: device_sum (thread t of
+// block b: elements (b * trips + j) * 512 + t, then + 256 + t, ascending j; butterfly; waves in order; launch_reduce_final)
+int launch_hs2_update_xr(hipStream_t st, const Hs2Args& a);   // x, r, (rt); partials nu_c (slots 3, 5), rr_c (4, 6)
+int launch_hs2_init_dots(hipStream_t st, const Hs2Args& a);   // ... of the initial state: no update, (rt = d r)
+int launch_hs2_update_p(hipStream_t st, const Hs2Args& a);    // p = z + b_c p
+int launch_hs2_dot_ps(hipStream_t st, const Hs2Args& a);      // partials mu_c = p.s (slots 0, 1)
+
 struct PrArgs {   // non-pipelined predict-and-recompute (pr_pcg / m_pcg)
     int64_t n;
     double* x; double* r; double* rt; double* p; const double* s; const double* st_;

@@ -1128,16 +1128,6 @@ __global__ void k_pack(double* buf, const double* v, const int* idx, int64_t cou
     }
 }
 
-struct Chunking { int grid; int trips; };
-Chunking chunking(int64_t n) {
-    const int64_t total = (n + kElemsPerTrip - 1) / kElemsPerTrip;
-    int64_t grid = total < kMaxGridBlocks ? total : kMaxGridBlocks;
-    if (grid < 1) grid = 1;
-    const int64_t trips = (total + grid - 1) / grid;
-    grid = trips > 0 ? (total + trips - 1) / trips : 1;
-    if (grid < 1) grid = 1;
-    return {(int)grid, (int)(trips > 0 ? trips : 1)};
-}
 
 int util_grid(int64_t n) {
     int64_t g = (n + 255) / 256;

@@ -1,0 +1,172 @@
+// gfx950 (MI355X / CDNA4): the vector kernels of the session type "Hestenes-Stiefel, two right-hand sides"
+// (prcg_solve_begin_multi; replaces two calls of the reference's hs_cg.py:9 / :70 on one matrix).
+//
+// One iteration of the session is  update_xr -> reduce -> update_p -> [p_0 p_1] -> A [p_0 p_1] (the two-vector product
+// every operator family already has) -> dot_ps -> reduce: the operator is streamed ONCE for both systems.
+//
+// State layout: X, R, P, S (and RT with Jacobi) are interleaved n x 2 arrays, row i = (column 0, column 1).  A lane touches
+// a row of an array with ONE 16-byte load or store, a wave instruction covers one contiguous kilobyte, and P / S are
+// directly the product's input and output.  All three kernels are bandwidth bound: per row update_xr moves 96 bytes
+// (x, r, p, s in; x, r out; + 8 of d in and 16 of rt out with Jacobi), update_p 48, dot_ps 32.
+//
+// Arithmetic: the expressions of k_hs_update_xr / k_hs_update_p (prcg_kernels.hip), multiply then add, every product
+// and every sum rounded (-ffp-contract=off).  Each column has its OWN scalars (a_c, b_c, its own accumulators): nothing
+// one column computes enters the other, there is no branch on a value and no 0 * x shortcut -- a NaN or inf of one
+// system stays in that system, and swapping the right-hand sides swaps the results bit for bit.
+//
+// Order of the sums (what tests/device_order.py: device_sum models, so the oracle can be asked for equal bits): grid and
+// trips as chunking(n); thread t of block b adds elements (b * trips + j) * 512 + t, then + 256 + t, for ascending j;
+// xor butterfly per wave; waves 0..3 in order (block_reduce_store); the block partials by launch_reduce_final.
+#include <hip/hip_runtime.h>
+
+#include "prcg_kernels.h"
+#include "prcg_device.hpp"
+
+namespace prcg {
+namespace {
+
+// a_c = nu_c / mu_c; x += a_c p; r -= a_c s; (z = d r); partials of nu_c = r.z and rr_c = r.r   (hs_cg.py:54-56, hs_pcg :116-119)
+template <bool PREC, bool DOTS_ONLY>
+__global__ __launch_bounds__(kBlock) void k_hs2_update_xr(Hs2Args a, int trips) {
+    double al0 = 0.0, al1 = 0.0;
+    if constexpr (!DOTS_ONLY) {
+        const double* __restrict__ dp = a.dots_prev;
+        al0 = dp[kHs2Nu] / dp[kHs2Mu];                          // a_k1 = nu / mu, column 0
+        al1 = dp[kHs2Nu + 2] / dp[kHs2Mu + 1];                  // ... column 1
+        if (blockIdx.x == 0 && threadIdx.x == 0) { a.coef_out[0] = al0; a.coef_out[2] = al1; }
+    }
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};                       // nu_0, rr_0, nu_1, rr_1
+    const int64_t n = a.n;
+    double2* __restrict__ X = reinterpret_cast<double2*>(a.x);
+    double2* __restrict__ R = reinterpret_cast<double2*>(a.r);
+    double2* __restrict__ RT = reinterpret_cast<double2*>(a.rt);
+    const double2* __restrict__ P = reinterpret_cast<const double2*>(a.p);
+    const double2* __restrict__ S = reinterpret_cast<const double2*>(a.s);
+    const double* __restrict__ D = a.d;
+
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        // ---- loads of both rows first (two independent rows in flight) ----
+        double2 x2[2], r2[2], p2[2], s2[2];
+        double dv[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;               // clamped: branch-free loads
+            r2[e] = R[il];
+            if constexpr (!DOTS_ONLY) { x2[e] = X[il]; p2[e] = P[il]; s2[e] = S[il]; }
+            if constexpr (PREC) dv[e] = D[il];
+        }
+        // ---- arithmetic + stores, row base then row base + 256 (this order is part of the reduction tree) ----
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!ok[e]) continue;
+            const int64_t ie = base + e * kBlock;
+            double2 rn = r2[e];
+            if constexpr (!DOTS_ONLY) {
+                X[ie] = make_double2(x2[e].x + al0 * p2[e].x, x2[e].y + al1 * p2[e].y);      // x += a p
+                rn = make_double2(rn.x - al0 * s2[e].x, rn.y - al1 * s2[e].y);               // r -= a s
+                R[ie] = rn;
+            }
+            if constexpr (PREC) {
+                const double2 z = make_double2(dv[e] * rn.x, dv[e] * rn.y);                  // r~ = M^-1 r
+                RT[ie] = z;
+                acc[0] += rn.x * z.x; acc[1] += rn.x * rn.x;
+                acc[2] += rn.y * z.y; acc[3] += rn.y * rn.y;
+            } else {
+                acc[0] += rn.x * rn.x;
+                acc[2] += rn.y * rn.y;
+            }
+        }
+    }
+    if constexpr (!PREC) { acc[1] = acc[0]; acc[3] = acc[2]; }
+    block_reduce_store<4>(acc, a.partials, kHs2Nu);
+}
+
+// b_c = nu_c / nu_prev_c; p = z + b_c p   (hs_cg.py:57-58, hs_pcg :120-121)
+__global__ __launch_bounds__(kBlock) void k_hs2_update_p(Hs2Args a, int trips) {
+    const double bt0 = a.dots_cur[kHs2Nu] / a.dots_prev[kHs2Nu];            // b_k = nu_k / nu_k1, column 0
+    const double bt1 = a.dots_cur[kHs2Nu + 2] / a.dots_prev[kHs2Nu + 2];    // ... column 1
+    if (blockIdx.x == 0 && threadIdx.x == 0) { a.coef_out[1] = bt0; a.coef_out[3] = bt1; }
+    const int64_t n = a.n;
+    const double2* __restrict__ Z = reinterpret_cast<const double2*>(a.rt ? a.rt : a.r);
+    double2* __restrict__ P = reinterpret_cast<double2*>(a.p);
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        double2 z2[2], p2[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;
+            z2[e] = Z[il]; p2[e] = P[il];
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!ok[e]) continue;
+            P[base + e * kBlock] = make_double2(z2[e].x + bt0 * p2[e].x, z2[e].y + bt1 * p2[e].y);
+        }
+    }
+}
+
+// partials of mu_c = p.s   (hs_cg.py:60): the two-vector products have no dot epilogue
+__global__ __launch_bounds__(kBlock) void k_hs2_dot_ps(Hs2Args a, int trips) {
+    double acc[2] = {0.0, 0.0};                                 // mu_0, mu_1
+    const int64_t n = a.n;
+    const double2* __restrict__ P = reinterpret_cast<const double2*>(a.p);
+    const double2* __restrict__ S = reinterpret_cast<const double2*>(a.s);
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        double2 p2[2], s2[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;
+            p2[e] = P[il]; s2[e] = S[il];
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!ok[e]) continue;
+            acc[0] += p2[e].x * s2[e].x;
+            acc[1] += p2[e].y * s2[e].y;
+        }
+    }
+    block_reduce_store<2>(acc, a.partials, kHs2Mu);
+}
+
+}  // namespace
+
+#define PRCG_LAUNCH_OK() (hipGetLastError() == hipSuccess)
+
+int launch_hs2_update_xr(hipStream_t st, const Hs2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_hs2_update_xr<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_hs2_update_xr<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_hs2_init_dots(hipStream_t st, const Hs2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_hs2_update_xr<true, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_hs2_update_xr<false, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_hs2_update_p(hipStream_t st, const Hs2Args& a) {
+    const Chunking c = chunking(a.n);
+    hipLaunchKernelGGL(k_hs2_update_p, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_hs2_dot_ps(hipStream_t st, const Hs2Args& a) {
+    const Chunking c = chunking(a.n);
+    hipLaunchKernelGGL(k_hs2_dot_ps, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+
+}  // namespace prcg

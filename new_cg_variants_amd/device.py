@@ -204,6 +204,27 @@ class DeviceCSR:
                                                L.ptr(xt), L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
+    def clear_preconditioners(self):
+        """Remove a host-callback or block-Jacobi preconditioner an earlier session set on this handle."""
+        self._prec_fn = None
+        self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
+        self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
+
+    def begin_multi(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
+        """Two right-hand sides in ONE Hestenes-Stiefel session (prcg.h: prcg_solve_begin_multi): B, X0 of shape (2, n),
+        row j = right-hand side / start vector of system j.  Every iteration streams the operator once for both systems.
+        variant: L.HS; inv_diag: Jacobi on the device (the same diagonal for both); hist_mask: 0 or updated_residual_2_norm.
+        iterate / sync / k serve the session as they are; state is read per column: get_vector(name, rhs=j), get_scalars(k, rhs=j),
+        get_coefficients(k, rhs=j), history(rhs=j)."""
+        B, X0 = _pair_of_vectors('B', B, self.n), _pair_of_vectors('X0', X0, self.n)
+        dv = None if inv_diag is None else L.f64(inv_diag)
+        if dv is not None and dv.shape != (self.n,):
+            raise ValueError(f'begin_multi: inv_diag must have shape ({self.n},), got {dv.shape}')
+        bp = (C.c_void_p * 2)(B[0].ctypes.data, B[1].ctypes.data)
+        xp = (C.c_void_p * 2)(X0[0].ctypes.data, X0[1].ctypes.data)
+        self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), 2, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
+        self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
+
     def set_replace_hook(self, fn):
         """Ghysels-Vanroose residual replacement (prcg.h: prcg_set_replace_hook): fn(k) -> truthy replaces w by A r in
         iteration k; None removes the hook.  Set before begin()."""
@@ -240,7 +261,7 @@ class DeviceCSR:
                 'col_bytes': 0 if s & 65536 else (1 if s & 64 else (2 if s & 128 else 4)), 'tile_steps': (s >> 8) & 15,
                 'pattern': bool(s & 65536), 'window': bool(s & 4096), 'fused_comm': bool(s & 8192), 'peer': bool(s & 16384), 'sliced_rows': bool(s & 32768),
                 'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152),
-                'block_jacobi': bool(s & 4194304), 'xp_deferred': bool(s & 8388608)}
+                'block_jacobi': bool(s & 4194304), 'xp_deferred': bool(s & 8388608), 'rhs2': bool(s & 16777216)}
 
     def layout(self):
         """Diagnostic (prcg.h: prcg_debug_layout): what the summation order of the one-launch iteration's inner
@@ -260,9 +281,13 @@ class DeviceCSR:
     def set_iteration(self, k):
         self._check(self._lib.prcg_set_iteration(self._h, int(k)))
 
-    def get_vector(self, name):
+    def get_vector(self, name, *, rhs=None):
+        """rhs=j: column j of a two-RHS session (begin_multi)."""
         out = np.empty(self.n)
-        self._check(self._lib.prcg_get_vector(self._h, L.VEC[name], L.ptr(out)))
+        if rhs is None:
+            self._check(self._lib.prcg_get_vector(self._h, L.VEC[name], L.ptr(out)))
+        else:
+            self._check(self._lib.prcg_get_vector_rhs(self._h, L.VEC[name], int(rhs), L.ptr(out)))
         return out
 
     def set_vector(self, name, v):
@@ -270,9 +295,12 @@ class DeviceCSR:
         assert v.shape == (self.n,)
         self._check(self._lib.prcg_set_vector(self._h, L.VEC[name], L.ptr(v)))
 
-    def get_scalars(self, k):
+    def get_scalars(self, k, *, rhs=None):
         out = np.empty(L.NUM_SCALARS)
-        self._check(self._lib.prcg_get_scalars(self._h, int(k), L.ptr(out)))
+        if rhs is None:
+            self._check(self._lib.prcg_get_scalars(self._h, int(k), L.ptr(out)))
+        else:
+            self._check(self._lib.prcg_get_scalars_rhs(self._h, int(k), int(rhs), L.ptr(out)))
         return out
 
     def set_scalars(self, k, values):
@@ -280,18 +308,24 @@ class DeviceCSR:
         assert v.shape == (L.NUM_SCALARS,)
         self._check(self._lib.prcg_set_scalars(self._h, int(k), L.ptr(v)))
 
-    def get_coefficients(self, k):
+    def get_coefficients(self, k, *, rhs=None):
         out = np.empty(3)
-        self._check(self._lib.prcg_get_coefficients(self._h, int(k), L.ptr(out)))
+        if rhs is None:
+            self._check(self._lib.prcg_get_coefficients(self._h, int(k), L.ptr(out)))
+        else:
+            self._check(self._lib.prcg_get_coefficients_rhs(self._h, int(k), int(rhs), L.ptr(out)))
         return out
 
-    def history(self):
-        """dict recorder-name -> array(max_iter) for the recorders of this session."""
+    def history(self, *, rhs=None):
+        """dict recorder-name -> array(max_iter) for the recorders of this session (rhs=j: of column j of a two-RHS session)."""
         names = [q for q, bit in sorted(L.HIST_BITS.items(), key=lambda kv: kv[1]) if self.hist_mask & bit]
         if not names:
             return {}
         buf = np.zeros((len(names), self.max_iter))
-        self._check(self._lib.prcg_get_history(self._h, L.ptr(buf)))
+        if rhs is None:
+            self._check(self._lib.prcg_get_history(self._h, L.ptr(buf)))
+        else:
+            self._check(self._lib.prcg_get_history_rhs(self._h, int(rhs), L.ptr(buf)))
         return {q: buf[i].copy() for i, q in enumerate(names)}
 
     def set_profiling(self, stride):
@@ -332,6 +366,14 @@ class DeviceCSR:
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
         names = [q for q, bit in sorted(L.HIST_BITS.items(), key=lambda kv: kv[1]) if hist_mask & bit]
         return x, {q: hist[i].copy() for i, q in enumerate(names)}, t.as_dict()
+
+
+def _pair_of_vectors(name, V, n):
+    """(2, n) C-contiguous float64, or ValueError: the two-RHS session takes exactly two systems of the operator's size."""
+    V = L.f64(V)
+    if V.shape != (2, n):
+        raise ValueError(f'{name} must have shape (2, {n}) -- two right-hand sides of the operator\'s size -- got {V.shape}')
+    return V
 
 
 def plan_tiles(indptr, row_class=None, cap_nnz=None, cap_rows=None):
