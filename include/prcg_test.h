@@ -123,6 +123,24 @@ int64_t prcg_plan_sell(int64_t n, const int32_t* indptr, const int32_t* indices,
                        double max_overhead, int sigma, int planes, int allow_runs, int window_granules, int32_t* slices_out, int64_t capacity,
                        double* val_out, uint16_t* col_out, int64_t array_capacity, int32_t* rows_out, int64_t rows_capacity,
                        int32_t* gran_out, int64_t gran_capacity, int64_t* stats);
+/* The operator decision of prcg_set_csr (csrc/prcg_plan.h: plan_operator) without a handle and without a GPU: which kernel
+ * family the row block gets, with which encodings, under the PRCG_* options keys[i] = values[i] (as prcg_set_option takes
+ * them; defaults otherwise -- the environment is not read).  indptr32: n_rows + 1 row pointers from 0 to nnz.
+ * out[0..18) = {family (0 CSR-adaptive tiles / 1 window tiles / 2 sliced rows), window geometry id (-1: none), rows per
+ * window tile, 1 if pattern tiles, waves of a sweep table, value dictionary for interior / for boundary tiles, bytes per
+ * column code of interior / of boundary tiles (0: pattern tiles have none), tile steps, interior / boundary tiles (slices)
+ * of the family in force, image period, operator bytes (prcg_operator_bytes), then four 64-bit FNV-1a hashes of what an
+ * upload would copy, array after array, an array that is not uploaded adding nothing:
+ *   index streams      16-bit codes, 8-bit codes, tile bases | window-index images, relative row pointers or slot masks |
+ *                      sliced rows: column codes, (row, length) pairs, granule starts
+ *   value-index        CSR-adaptive tiles' 1-byte indices | window tiles' value-index images
+ *   dictionaries       CSR-adaptive tiles' entries, {first, count} per tile | window tiles' entries | pattern records |
+ *                      sliced rows: the re-laid values
+ *   tile tables        CSR-adaptive tiles | window tiles | slices}.
+ * Returns 18, -18 if capacity is smaller, -1 on a bad argument, an unknown option or a column index out of range. */
+int64_t prcg_plan_operator(int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
+                           const double* data, const char* const* keys, const char* const* values, int n_options, int64_t* out,
+                           int64_t capacity);
 /* Merged exchange of the multi-GPU pipelined loop (small halos ride on the one all-gather per
  * iteration): where in the gathered buffer do this rank's ghost rows lie?  `tables`: every rank's
  * send table, doubles_per_table doubles each: [n_peers, (peer, first row of its list, rows)...];

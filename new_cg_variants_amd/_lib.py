@@ -90,6 +90,7 @@ _SIGNATURES = {
     'prcg_plan_gather': (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int64, _P]),
     'prcg_plan_sell': (C.c_int64, [C.c_int64, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P,
                                     C.c_int64, _P]),
+    'prcg_plan_operator': (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int64]),
     'prcg_plan_tiles': (C.c_int64, [C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     'prcg_plan_window': (C.c_int64, [C.c_int64, C.c_int64, _P, _P, _P, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int)]),

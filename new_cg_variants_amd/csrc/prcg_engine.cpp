@@ -1,4 +1,4 @@
-// libprcg.so engine: handle, operator upload, solver sessions, multi-GPU schedule.
+// libprcg.so engine: handle, operator upload (planned in prcg_plan.cpp), solver sessions, multi-GPU schedule.
 // Implements include/prcg.h.  Host code only; kernels live in prcg_kernels.hip.
 //
 // Per-iteration schedule of the pipelined variants (the GPU form of the PETSc plug-in's
@@ -84,177 +84,14 @@ struct DevBuf {
 
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; };
 
-}  // namespace
-
-struct prcg_handle {
-    int dev = 0;
-    std::string err;
-    hipStream_t sc = nullptr;   // compute
-    hipStream_t sm = nullptr;   // reductions + all-reduce
-    hipStream_t sh = nullptr;   // halo exchange (own stream + own communicator: runs beside the all-reduce)
-    hipEvent_t e_upd = nullptr, e_halo = nullptr, e_red = nullptr;
-    hipEvent_t e_kdone = nullptr;   // completion signal of a launch itself (hipExtLaunchKernel), see FusedState::done
-    hipEvent_t e_rdone = nullptr;   // ... of the unpack launch that ends the communication chain of an iteration
-
-    // ---- communicator ----
-    Rccl* rccl = nullptr;
-    ncclComm_t comm = nullptr;    // all-reduce (and, if comm_halo is null, the halo too)
-    ncclComm_t comm_halo = nullptr;
-    int rank = 0, nranks = 1;
-
-    // ---- operator ----
+// The resident operator: what plan_operator decided (OperatorShape) and the arrays prcg_set_csr uploaded.
+struct Operator : OperatorShape {
     bool have_csr = false;
-    int64_t n = 0, g = 0, nnz = 0;
     DevBuf indptr, col, val, tiles;
     DevBuf col16, col8, tile_base;       // 16- / 8-bit tile-relative column encodings (see CsrDev)
-    bool c16_int = false, c16_bnd = false;   // ... usable for all interior / all boundary tiles
-    bool c8_int = false, c8_bnd = false;
-    bool want_c16 = true;                // PRCG_COL16=0 turns it off
-    bool want_c8 = true;                 // PRCG_COL8=0: never narrower than 16 bit
     DevBuf vidx8, vdict, vdesc;          // value dictionary (see CsrDev): 1-byte indices, entries, {first,count} per tile
-    bool vd_int = false, vd_bnd = false;
-    bool want_vdict = true;              // PRCG_VALDICT=0 turns it off
-    int nt_int = 0, nt_bnd = 0;          // interior tiles first, then boundary tiles
-    int steps = kDefaultTileSteps;       // tile size the table was planned for
-    TileKnobs kn;                        // PRCG_GRID_PER_CU
-    int steps_override = 0;              // PRCG_TILE_STEPS
-    // ---- window tiles (row-per-lane kernels, prcg_win.hip): all tiles of the operator or none ----
-    bool want_win = true;                // PRCG_WIN=0 turns them off
-    int win_per_cu = 0;                  // PRCG_WIN_GRID_PER_CU
-    int win_max_mean = 24;               // PRCG_WIN_MAX_MEAN: longest mean row the window form is tried for
-    int win_rows_override = 0;           // PRCG_WIN_ROWS = 64 | 128: rows per window tile (default: by mean row length)
-    bool win = false;
-    int win_geom = 0, win_rows = 0;
-    bool win_vd = false;
-    bool win_pat = false;        // pattern tiles (geometry 5): no index streams, the rows' slot masks in wrel, records in wpat
-    bool want_pat = true;        // PRCG_WIN_PAT=0: constant-coefficient stencils keep the stream geometries
-    int want_sweep = 1;          // PRCG_WIN_SWEEP=0: pattern tiles in row order (no page carried from tile to tile); 2: sweep tables
-                                 // for operators of any size (default: 5e6 rows and more -- below, the row order with big workgroups wins)
-    int sweep_waves = 0, sweep_tiles = 0;
-    int sweep_max_waves = 6144;  // PRCG_SWEEP_WAVES: most waves a sweep table may ask for
-    DevBuf wpat;
-    int nwt_int = 0, nwt_bnd = 0;
-    DevBuf wtiles, wcw, wvidx, wvdict, wrel;
-    // ---- sliced rows (lane-per-row kernels for medium-length rows, prcg_sell.hip): all rows of the operator or none ----
-    bool want_sell = true;               // PRCG_SELL=0 turns them off
-    int sell_per_cu = 0;                 // PRCG_SELL_GRID_PER_CU
-    bool sell = false;
-    int nst_int = 0, nst_bnd = 0;        // interior slices first, then slices touching ghost columns
-    int64_t sell_bytes = 0;              // bytes of the re-laid operator a product reads
-    DevBuf sval, scol, sslices, srows, sgran;
-    int sell_window = 0;                 // > 0: WINDOW codes -- the kernels stage a slice's input entries in LDS (prcg_plan.h); the most granules of a slice
-    int sell_window_opt = 64;            // PRCG_SELL_WINDOW=0 turns them off (delta codes, gathers from memory); 1..64: granules a slice may use
-    double sell_overhead_opt = 0.0;      // PRCG_SELL_MAX_OVERHEAD_PCT: most padded nonzeros per nonzero, in percent (experiments)
-    int sell_sigma_opt = 0;              // PRCG_SELL_SIGMA: sorting window of the sliced layout in rows (0: chosen by the planner)
-    int sell_planes_opt = 0;             // PRCG_SELL_PLANES: grid planes interleaved in the slice table (<= 1: row order, the default:
-                                         // interleaving 8 planes cost s4b at 80^3 nodes 9 % -- profiles/r04_sweeps.md)
-    int sell_nt = 0;                     // the value / code streams are read with nontemporal loads: chosen per operator in prcg_set_csr
-    int sell_nt_opt = -1;                // PRCG_SELL_NT=0|1 overrides
-    int place_k = 8;                     // PRCG_PLACE=k: the pipelined session's vectors are placed k times and the fastest placement is kept (place_session_vectors); 0 / 1: off
-    void* placed_xp = nullptr;           // ... the (x,p) allocation that has been through it
-    int sell_sigma = 0, sell_planes = 0, sell_run = 1; // what the planner chose
-    bool sell_runs_opt = true;           // PRCG_SELL_RUNS=0: a column code per nonzero even where the rows are runs of three
-    int64_t sell_stride = 0;
-    bool want_big = true;                // PRCG_WIN_BIG=0: short launches keep the small workgroups too
-    int win_period = 0;                  // tiles t and t + win_period read the same stream images (0: no such period found)
-    bool want_share = true;              // PRCG_WIN_SHARE=0: every window tile keeps its own stream images
-    int64_t win_stream_bytes = 0;        // bytes of the encoded operator a product must read at least once (window form)
-    DevBuf tmp_ext;                      // 2*(n+g) doubles: SpMV input scratch with ghost room
-    DevBuf t1;                           // 2*n doubles: SpMV output scratch
-    DevBuf partA, partB;                 // block partials: update kernels / SpMV epilogues
-
-    // ---- halo plan ----
-    int n_peers = 0;
-    std::vector<int> peer_rank;
-    std::vector<int64_t> send_ptr, recv_ptr;
-    DevBuf send_idx, send_buf;
-    bool have_halo = false;
-
-    // ---- merged exchange: with a small halo, ONE all-gather per iteration carries the rank's five
-    // partial inner products and the rows its neighbours need (pipelined variants) ----
-    bool want_gather = true;             // PRCG_GATHER=0 turns it off (must agree on all ranks)
-    int64_t gather_max_bytes = 8192;     // PRCG_GATHER_MAX_BYTES: largest per-rank slot that still rides along
-    bool gather_planned = false, gather_ok = false;
-    bool gather = false;                 // this session uses it
-    int g_slot = 0;                      // doubles per rank slot: 8 + 2 * (largest send list of any rank)
-    DevBuf gbuf, ghost_src, gtab;
-
-    // ---- session ----
-    bool in_session = false;
-    int variant = -1;
-    bool prec = false;
-    int max_iter = 0;
-    int k = 0;
-    uint32_t hist_mask = 0;
-    bool have_xtrue = false;
-    DevBuf r2, s2, rt2, st2;     // one-launch predict-and-recompute: the second copies of r, s (r~, s~ with Jacobi)
-    DevBuf x, xp, p, p2, rs, rs2, rst, rst2, wu, wt, wv, r, s, rt, st, b, xt, dinv, e_ext;
-    DevBuf w, u, tvec;           // cg_cg / gv: w (ghost room), u, t = A w~
-    bool rhs2 = false;           // session type "Hestenes-Stiefel, two right-hand sides" (prcg_solve_begin_multi): the state is the five
-    DevBuf mx, mr, mp, ms, mrt;  // ... interleaved n x 2 arrays X, R, P, S, RT (Hs2Args, prcg_kernels.h); dots / coef hold both columns per row
-    bool fused = false;          // this session runs the one-launch-per-iteration pipelined kernel
-    bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
-    bool want_fused_comm = true; // PRCG_FUSED_COMM=0: communicator sessions keep the two-kernel schedule
-    bool ext_signal = true;      // PRCG_EXT_SIGNAL=0: separate hipEventRecord instead of the launch's own completion signal
-    int defer_per_cu = 0;        // PRCG_DEFER_GRID_PER_CU: workgroups per CU of the deferred launch (several ranks sharing one
-                                 // GPU in the tests must all be resident at once: 1)
-    DevBuf pub, pub_err;         // publication record of the reduced inner products / timeout flag
-    bool red_pending = false;    // the communication chain of the previous iteration is outstanding ...
-    hipEvent_t red_event = nullptr;   // ... and this event marks its end
-    bool want_fused = true;      // PRCG_FUSED=0 turns it off
-    bool small = false;          // this session runs the one-workgroup solver (n <= 4096)
-    int small_mode = 0;          // 0: matrix in LDS, 1: matrix in registers
-    bool small_hs = false;       // Hestenes-Stiefel session of a small system: the whole solve in one launch of one workgroup
-    int max_row_len = 0;
-    bool want_small = true;      // PRCG_SMALL=0 turns it off
-    double* rs_cur = nullptr;    // fused: the current SpMM input pairs: rs / rs2 ((r,s)), with Jacobi rst / rst2 ((r~,s~))
-    DevBuf partC;                // fused: second partials buffer (ping-pong with partB)
-    // preconditioners that are no diagonal scaling: sessions that use one run the schedules in which every tilde vector is
-    // a stored vector (stored_tilde).  Two kinds, the last one set is in force:
-    //  * host callback (prcg_set_preconditioner): M^-1 v is computed by the caller's function on host copies of v;
-    //  * point-block Jacobi (prcg_set_block_jacobi): M^-1 v is one launch of prcg_blockjac.hip on the compute stream
-    //    (bj_session says that THIS one applies M^-1 in the current session)
-    prcg_prec_fn cb = nullptr; void* cb_ctx = nullptr; bool stored_tilde = false;
-    int bj_bs = 0; DevBuf bj_blocks; bool bj_session = false;    // bj_bs > 0: blocks set, in the layout of block_jacobi_layout
-    prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
-    std::vector<double> cb_in, cb_out;
-    DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
-    bool pr_packed = false;      // ... unpreconditioned, no per-iteration vector recorder: inside a prcg_iterate call the state lives PACKED,
-                                 // one 32-byte entry (z, zs, p, x) per row in q / q2 (kEpiPROneQ: 16-byte accesses only); packed at the
-                                 // call's first iteration, unpacked into r, s, p, x at its end
-    bool pr_q_valid = false;     // ... the packed copy q_cur is the current state
-    int want_pr_pack = -1;       // PRCG_PR_PACK=0|1; default: pattern-tile operators only (S2: +7.6 %; S3 +-0; S2 with plain values -12 %)
-    double* q_cur = nullptr;
-    DevBuf q, q2;
-    bool pr_fused = false;       // non-pipelined predict-and-recompute (pr, m) on a window operator: ONE launch per iteration
-                                 // (window formed as (z - a zs) + b p_old); z, zs, p double-buffered:
-    double* cur_r = nullptr; double* cur_s = nullptr; double* cur_rt = nullptr; double* cur_st = nullptr;
-    double* cur_w = nullptr;     // ... Ghysels-Vanroose: w double-buffered the same way (w / w2)
-    DevBuf w2;
-    bool cg_fused = false;       // Chronopoulos-Gear / Ghysels-Vanroose on a window operator: two launches (product with the window formed as
-                                 // r - a s; p, s update that sums the product's partials itself); r double-buffered (cur_r)
-    bool cg_one = false;         // ... in ONE launch per iteration (launch_win_cg_one): the p, s (u) update of an iteration is deferred into the next
-                                 // launch's window formation; s (cg) / t, u (gv) double-buffered as well
-    bool cg_lag = false;         // ... and the update of iteration pend_k is pending (its partials: pend_buf / pend_parts)
-    bool want_cg_one = true;     // PRCG_CG_ONE=0: the two-launch schedule
-    double* cur_u = nullptr; double* cur_t = nullptr;      // (cur_s: above)
-    DevBuf u2, t2;
-    bool hs_fused = false;       // Hestenes-Stiefel without reduction launches: 2 launches per iteration on window
-                                 // operators (update; product with the direction formed in the staged window), else 3
-    double* p_cur = nullptr;     // ... the current direction: p / p2 (the product launch writes the other one)
-    int hs_pend_mu = 0;          // ... mu of iteration pend_k exists only as this many block partials in partB
-    int last_grid = 0;           // workgroups of the last one-launch iteration (prcg_debug_layout)
-    int pend_parts = 0;          // fused: dots[pend_k] exist only as this many block partials ...
-    int pend_k = -1;             // ... of iteration pend_k, in pend_buf
-    double* pend_buf = nullptr;
-    DevBuf dots, coef;
-
-    // ---- profiling ----
-    int prof_stride = 0;
-    std::vector<EventPair> ev_spmv, ev_upd;
-    int n_ev_spmv = 0, n_ev_upd = 0;
-    double last_tot_ms = 0.0;
-    int64_t last_iters = 0;
+    DevBuf wpat, wtiles, wcw, wvidx, wvdict, wrel;      // window tiles (prcg_win.hip)
+    DevBuf sval, scol, sslices, srows, sgran;            // sliced rows (prcg_sell.hip)
 
     // operator view for a launch over tiles [first, ...): interior launches pass first = 0,
     // boundary launches first = nt_int; a launch over ALL tiles needs both classes to qualify
@@ -271,33 +108,165 @@ struct prcg_handle {
                       okv ? static_cast<const int2*>(vdesc.p) + first : nullptr};
     }
     const Tile* tile_ptr(int first = 0) const { return static_cast<const Tile*>(tiles.p) + first; }
-    WinDev wdev() const {
+    WinDev wdev(bool big_ok) const {
         const bool b16 = win_geom >= 2;
         return WinDev{indptr.i(), val.d(), b16 ? nullptr : static_cast<const unsigned char*>(wcw.p),
                       b16 ? static_cast<const unsigned short*>(wcw.p) : nullptr,
                       win_vd ? static_cast<const unsigned char*>(wvidx.p) : nullptr,
                       win_vd ? static_cast<const double*>(wvdict.p) : nullptr,
-                      static_cast<const unsigned short*>(wrel.p), static_cast<const PatRec*>(wpat.p), sweep_waves, sweep_tiles, want_big ? 1 : 0,
+                      static_cast<const unsigned short*>(wrel.p), static_cast<const PatRec*>(wpat.p), sweep_waves, sweep_tiles, big_ok ? 1 : 0,
                       win_period};
     }
     const WTile* wtile_ptr(int first = 0) const { return static_cast<const WTile*>(wtiles.p) + first; }
     SellDev sdev() const { return SellDev{indptr.i(), val_sell(), static_cast<const unsigned short*>(scol.p), static_cast<const int*>(srows.p), sell_nt, sell_run, sell_window > 0 ? static_cast<const int*>(sgran.p) : nullptr, sell_window}; }
     const double* val_sell() const { return static_cast<const double*>(sval.p); }
     const void* sslice_ptr(int first = 0) const { return static_cast<const char*>(sslices.p) + (size_t)first * 32; }
+};
+
+// Everything that describes the OPEN session and nothing that outlives it.  open_session assigns Session{} -- the only
+// such assignment -- so a session inherits no flag, pointer or pending state from the one before.
+//
+// Resets that are NEW against the engine before Session existed (there each family of prcg_solve_begin cleared only what
+// it used), and who read the stale value:
+//   fused_comm, peer     after a communicator session with PRCG_FUSED_COMM=1 / peer exchange, in every later non-pipelined
+//                        or two-RHS session: prcg_schedule (reported FUSED_COMM / PEER), prcg_sync (blocking copy of pub_err
+//                        on every call), prcg_iterate (consulted err_host), record() (waited for red_event), prcg_set_scalars
+//                        (published / returned early), prcg_debug_layout (waves per workgroup)
+//   red_pending,         the same sessions: record() and the tail of prcg_iterate
+//   red_event
+//   cg_one, cg_lag       after a one-launch Chronopoulos-Gear / Ghysels-Vanroose session, in every later session of another
+//                        family: record() and the tail of prcg_iterate called cg_flush (a no-op only because cg_lag was false)
+//   cg_fused             two-RHS sessions only cleared it by hand copy; now by the one reset
+//   pr_q_valid           pipelined and Chronopoulos-Gear sessions: pr_unpack (guarded by pr_packed)
+//   pend_parts, pend_k,  two-RHS sessions: not read there; every other family cleared them itself
+//   pend_buf
+//   rs_cur, q_cur, p_cur, cur_r, cur_s, cur_rt, cur_st, cur_w, cur_u, cur_t
+//                        families that do not use a pointer kept the last session's; locate() and the *_args builders read
+//                        only the ones their family sets
+//   small_mode, xphase,  read only under flags their family sets; last_grid: prcg_debug_layout reported the last one-launch
+//   last_grid            grid of an EARLIER session until the new one launched
+struct Session {
+    bool in_session = false;
+    int variant = -1;
+    bool prec = false;
+    bool stored_tilde = false;   // M^-1 is a host callback or block Jacobi: every tilde vector is a stored vector
+    bool bj_session = false;     // ... block Jacobi applies M^-1 in this session
+    int max_iter = 0;
+    int k = 0;
+    uint32_t hist_mask = 0;
+    bool have_xtrue = false;
+    bool rhs2 = false;           // session type "Hestenes-Stiefel, two right-hand sides" (prcg_solve_begin_multi)
+    // ---- schedule ----
+    bool fused = false;          // pipelined: the one-launch-per-iteration kernel
+    bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
+    bool peer = false;           // ... over the direct peer exchange
+    bool gather = false;         // pipelined with a communicator: the merged exchange
+    bool small = false;          // the one-workgroup solver (n <= 4096)
+    int small_mode = 0;          // 0: matrix in LDS, 1: matrix in registers
+    bool small_hs = false;       // Hestenes-Stiefel session of a small system: the whole solve in one launch of one workgroup
+    bool hs_fused = false;       // Hestenes-Stiefel without reduction launches: 2 launches per iteration on window
+                                 // operators (update; product with the direction formed in the staged window), else 3
+    int hs_pend_mu = 0;          // ... mu of iteration pend_k exists only as this many block partials in partB
+    bool pr_fused = false;       // non-pipelined predict-and-recompute (pr, m) on a window operator: ONE launch per iteration
+                                 // (window formed as (z - a zs) + b p_old); z, zs, p double-buffered
+    bool pr_packed = false;      // ... unpreconditioned, no per-iteration vector recorder: inside a prcg_iterate call the state lives PACKED,
+                                 // one 32-byte entry (z, zs, p, x) per row in q / q2 (kEpiPROneQ: 16-byte accesses only); packed at the
+                                 // call's first iteration, unpacked into r, s, p, x at its end
+    bool pr_q_valid = false;     // ... the packed copy q_cur is the current state
+    bool cg_fused = false;       // Chronopoulos-Gear / Ghysels-Vanroose on a window operator: two launches (product with the window formed as
+                                 // r - a s; p, s update that sums the product's partials itself); r double-buffered (cur_r)
+    bool cg_one = false;         // ... in ONE launch per iteration (launch_win_cg_one): the p, s (u) update of an iteration is deferred into the next
+                                 // launch's window formation; s (cg) / t, u (gv) double-buffered as well
+    bool cg_lag = false;         // ... and the update of iteration pend_k is pending (its partials: pend_buf / pend_parts)
+    bool red_pending = false;    // fused_comm: the communication chain of the previous iteration is outstanding ...
+    hipEvent_t red_event = nullptr;   // ... and this event marks its end
+    int xphase = 0;              // deferred (x,p) store (FusedPrev::xphase): phase of the launch prcg_iterate issues next (0 outside its loop)
+    // ---- which copy of a double-buffered vector is current ----
+    double* rs_cur = nullptr;    // pipelined, one launch: the current SpMM input pairs: rs / rs2 ((r,s)), with Jacobi rst / rst2 ((r~,s~))
+    double* q_cur = nullptr;     // pr_packed: q / q2
+    double* p_cur = nullptr;     // the current direction: p / p2 (the product launch writes the other one)
+    double* cur_r = nullptr; double* cur_s = nullptr; double* cur_rt = nullptr; double* cur_st = nullptr;
+    double* cur_w = nullptr; double* cur_u = nullptr; double* cur_t = nullptr;
+    // ---- inner products that exist only as block partials ----
+    int pend_parts = 0;          // dots[pend_k] exist only as this many block partials ...
+    int pend_k = -1;             // ... of iteration pend_k, in pend_buf
+    double* pend_buf = nullptr;
+    int last_grid = 0;           // workgroups of the last one-launch iteration (prcg_debug_layout)
+};
+
+}  // namespace
+
+// The resident operator (Operator) and the state of the open session (Session) are base sub-objects, so that each is a
+// value of its own -- the operator's flags are assigned from the plan, the session is reset as a whole -- while the code
+// below addresses their fields as before.
+struct prcg_handle : Operator, Session {
+    int dev = 0;
+    std::string err;
+    hipStream_t sc = nullptr;   // compute
+    hipStream_t sm = nullptr;   // reductions + all-reduce
+    hipStream_t sh = nullptr;   // halo exchange (own stream + own communicator: runs beside the all-reduce)
+    hipEvent_t e_upd = nullptr, e_halo = nullptr, e_red = nullptr;
+    hipEvent_t e_kdone = nullptr;   // completion signal of a launch itself (hipExtLaunchKernel), see FusedState::done
+    hipEvent_t e_rdone = nullptr;   // ... of the unpack launch that ends the communication chain of an iteration
+
+    Options opt;                // every PRCG_* switch (prcg_plan.h)
+
+    // ---- communicator ----
+    Rccl* rccl = nullptr;
+    ncclComm_t comm = nullptr;    // all-reduce (and, if comm_halo is null, the halo too)
+    ncclComm_t comm_halo = nullptr;
+    int rank = 0, nranks = 1;
+
+    // ---- halo plan ----
+    int n_peers = 0;
+    std::vector<int> peer_rank;
+    std::vector<int64_t> send_ptr, recv_ptr;
+    DevBuf send_idx, send_buf;
+    bool have_halo = false;
+
+    // ---- merged exchange: with a small halo, ONE all-gather per iteration carries the rank's five
+    // partial inner products and the rows its neighbours need (pipelined variants; Session::gather) ----
+    bool gather_planned = false, gather_ok = false;
+    int g_slot = 0;                      // doubles per rank slot: 8 + 2 * (largest send list of any rank)
+    DevBuf gbuf, ghost_src, gtab;
+
+    // ---- allocations, reused from session to session by design (DevBuf::ensure) ----
+    DevBuf tmp_ext;                      // 2*(n+g) doubles: SpMV input scratch with ghost room
+    DevBuf t1;                           // 2*n doubles: SpMV output scratch
+    DevBuf partA, partB;                 // block partials: update kernels / SpMV epilogues
+    DevBuf partC;                        // one-launch schedules: second partials buffer (ping-pong with partB)
+    DevBuf r2, s2, rt2, st2;     // one-launch predict-and-recompute: the second copies of r, s (r~, s~ with Jacobi)
+    DevBuf x, xp, p, p2, rs, rs2, rst, rst2, wu, wt, wv, r, s, rt, st, b, xt, dinv, e_ext;
+    DevBuf w, u, tvec;           // cg_cg / gv: w (ghost room), u, t = A w~
+    DevBuf w2, u2, t2;           // ... their second copies (one- / two-launch schedules on window operators)
+    DevBuf mx, mr, mp, ms, mrt;  // two right-hand sides: the interleaved n x 2 arrays X, R, P, S, RT (Hs2Args, prcg_kernels.h); dots / coef hold both columns per row
+    DevBuf pub, pub_err;         // publication record of the reduced inner products / timeout flag
+    DevBuf q, q2;                // packed predict-and-recompute state (Session::pr_packed)
+    DevBuf dots, coef;
+    void* placed_xp = nullptr;   // the (x,p) allocation that has been through place_session_vectors
+
+    // preconditioners that are no diagonal scaling: sessions that use one run the schedules in which every tilde vector is
+    // a stored vector (Session::stored_tilde).  Two kinds, the last one set is in force:
+    //  * host callback (prcg_set_preconditioner): M^-1 v is computed by the caller's function on host copies of v;
+    //  * point-block Jacobi (prcg_set_block_jacobi): M^-1 v is one launch of prcg_blockjac.hip on the compute stream
+    prcg_prec_fn cb = nullptr; void* cb_ctx = nullptr;
+    int bj_bs = 0; DevBuf bj_blocks;     // bj_bs > 0: blocks set, in the layout of block_jacobi_layout
+    prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
+    std::vector<double> cb_in, cb_out;
+    DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
+
+    // ---- profiling ----
+    int prof_stride = 0;
+    std::vector<EventPair> ev_spmv, ev_upd;
+    int n_ev_spmv = 0, n_ev_upd = 0;
+    double last_tot_ms = 0.0;
+    int64_t last_iters = 0;
+
+    WinDev wdev() const { return Operator::wdev(opt.want_big); }
     // any communicator -- even a 1-rank one -- selects the two-stream schedule
     bool multi() const { return comm != nullptr; }
 
     // ---- direct peer exchange over xGMI (PeerDev, prcg_kernels.h): the multi-rank one-launch schedule without a collective ----
-    int stream_stores = 0;               // the one-launch iteration writes its row results with streaming stores: chosen per operator in
-                                         // prcg_set_csr (vectors far larger than the 256 MB Infinity Cache), PRCG_STREAM_STORES=0|1 overrides
-    int stream_override = -1;
-    // deferred (x,p) store (FusedPrev::xphase): a qualifying session runs prcg_iterate's launches as (SKIP, APPLY) pairs --
-    // one 16-byte store per row and pair of iterations less.  PRCG_XP_DEFER=0: every launch closes itself.
-    bool want_xp_defer = true;
-    int xphase = 0;                      // phase of the launch prcg_iterate issues next (0 outside its loop)
-    int want_fused_comm_rccl = 0;        // PRCG_FUSED_COMM=1: one launch per iteration with the RCCL all-gather chain on the communication
-                                         // stream (in-kernel wait for kernels of another stream: validated with one rank only -- opt-in)
-    bool want_peer = true;               // PRCG_PEER=0: never use the peer exchange even when connected
     void* xbuf = nullptr;                // this rank's exchange buffer
     size_t xbuf_bytes = 0;
     bool xbuf_fine = false;              // allocated fine-grained (what other GPUs' stores need); else plain device memory (one GPU)
@@ -306,14 +275,11 @@ struct prcg_handle {
     PeerDev peer_host{};
     DevBuf peer_dev, peer_ents, peer_tile_send;
     bool peer_ok = false;                // connected: every rank's buffer is mapped, send entries planned
-    bool peer = false;                   // this session uses it
     uint64_t peer_epoch = 0;
     unsigned* err_host = nullptr;        // pinned host word a timed-out wave also writes: prcg_iterate sees it without a sync
     std::vector<int32_t> send_idx_host;  // prcg_set_halo's send lists (host copy: the peer plan is built from them)
     std::vector<int32_t> wt_rb, wt_re;   // rows of the window tiles in table order
 
-    bool debug_short_sources = false;    // PRCG_DEBUG_SHORT_SOURCES=1 (TESTS ONLY): Hestenes-Stiefel sessions allocate r without
-                                         // the spare entries a window source needs -- the launch must be refused, not fault
     // every vector a window launch may stage (the pointer handed to the launch lies inside one of them)
     const DevBuf* owner(const void* ptr) const {
         const DevBuf* all[] = {&tmp_ext, &t1, &x, &xp, &p, &p2, &rs, &rs2, &rst, &rst2, &wu, &wt, &wv, &r, &r2, &s, &s2, &rt, &rt2,
@@ -368,19 +334,6 @@ int fail(prcg_t* h, int code, const char* fmt, ...) {
 #define CHECK(h, cond, ...)                                                                   \
     do { if (!(cond)) return fail(h, PRCG_EINVAL, __VA_ARGS__); } while (0)
 
-// Tile size (256-nnz steps per wave tile).  Short rows (stencils: 5-7 nonzeros) do better
-// with 256-slot tiles -- more rows per lane would otherwise serialise the reduce phase
-// (measured: S1 34.3 k vs 31.3 k it/s, S2 3236 vs 3013) -- longer rows with 512-slot tiles
-// (S3, 15 per row: 2115 vs 1885 it/s).  PRCG_TILE_STEPS = 1 | 2 | 4 overrides.
-int pick_tile_steps(int override_, int64_t n = 0, int64_t nnz = 0) {
-    if (override_ == 1 || override_ == 2 || override_ == 4) return override_;
-    if (n > 0 && nnz < 10 * n) return 1;
-    // medium rows (FEM-like, ~50+ nonzeros): the lane-per-row sums are a serial chain per row, so
-    // bigger tiles (more rows summed side by side per wave) win (s4b: 2983 vs 2740 it/s)
-    if (n > 0 && nnz >= 48 * n) return 4;
-    return kDefaultTileSteps;
-}
-
 // A window launch stages whole 64-column pages of its source vectors and the narrow column encodings of the
 // CSR-adaptive kernels decode a few out-of-tile bytes per tile: every such source must hold its n + g entries AND
 // kGatherPad spare ones behind them (prcg_window_source_ok).  Checked at every launch from the size of the
@@ -401,54 +354,46 @@ int check_sources(prcg_t* h, std::initializer_list<std::pair<const void*, int>> 
 #define SRCCHK(h, ...) do { if (check_sources(h, {__VA_ARGS__})) return -2; } while (0)              // inside a launch helper (returns a grid)
 #define SRCCHK2(h, ...) do { if (check_sources(h, {__VA_ARGS__})) return PRCG_EINVAL; } while (0)   // inside an iterate_* function
 
-// The matrix products of the engine: window kernels when the operator qualified, else the
+// The matrix products of the engine: window kernels when the operator qualified, else sliced rows, else the
 // CSR-adaptive tile kernels.  which: 0 = every tile, 1 = interior tiles, 2 = tiles touching ghosts.
+struct TileRange { int first, count; };
+TileRange tile_range(const prcg_t* h, int which) {
+    const Operator& op = *h;
+    const int n_int = op.win ? op.nwt_int : (op.sell ? op.nst_int : op.nt_int);
+    const int n_bnd = op.win ? op.nwt_bnd : (op.sell ? op.nst_bnd : op.nt_bnd);
+    return TileRange{which == 2 ? n_int : 0, which == 0 ? n_int + n_bnd : (which == 1 ? n_int : n_bnd)};
+}
+// (the narrow encodings of the CSR-adaptive tiles are per class: a launch over one class asks for that class's)
+CsrDev csr_view(const prcg_t* h, int which) {
+    return which == 0 ? h->csr() : (which == 1 ? h->csr(0, h->nt_bnd == 0) : h->csr(h->nt_int, false));
+}
 int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, SpmvEpilogue epi, const double* ep_r,
              const double* ep_d, double* ep_st, double* partials) {
     SRCCHK(h, {x, 1});
-    if (h->win) {
-        const int first = which == 2 ? h->nwt_int : 0;
-        const int nt = which == 0 ? h->nwt_int + h->nwt_bnd : (which == 1 ? h->nwt_int : h->nwt_bnd);
-        return launch_win_spmv(st, h->wdev(), h->wtile_ptr(first), nt, h->win_geom, x, y, epi, ep_r, ep_d, ep_st, partials,
-                               h->win_per_cu);
-    }
-    if (h->sell) {
-        const int first = which == 2 ? h->nst_int : 0;
-        const int nt = which == 0 ? h->nst_int + h->nst_bnd : (which == 1 ? h->nst_int : h->nst_bnd);
-        return launch_sell_spmv(st, h->sdev(), h->sslice_ptr(first), nt, x, y, epi, ep_r, ep_d, ep_st, partials, h->sell_per_cu);
-    }
-    const int first = which == 2 ? h->nt_int : 0;
-    const int nt = which == 0 ? h->nt_int + h->nt_bnd : (which == 1 ? h->nt_int : h->nt_bnd);
-    const CsrDev A = which == 0 ? h->csr() : (which == 1 ? h->csr(0, h->nt_bnd == 0) : h->csr(h->nt_int, false));
-    return launch_spmv(st, A, h->tile_ptr(first), nt, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->kn);
+    const TileRange t = tile_range(h, which);
+    if (h->win)
+        return launch_win_spmv(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, x, y, epi, ep_r, ep_d, ep_st, partials,
+                               h->opt.win_per_cu);
+    if (h->sell)
+        return launch_sell_spmv(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.sell_per_cu);
+    return launch_spmv(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.kn);
 }
 int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask) {
     SRCCHK(h, {rs, 2});
-    if (h->win) {
-        const int first = which == 2 ? h->nwt_int : 0;
-        const int nt = which == 0 ? h->nwt_int + h->nwt_bnd : (which == 1 ? h->nwt_int : h->nwt_bnd);
-        return launch_win_spmm2(st, h->wdev(), h->wtile_ptr(first), nt, h->win_geom, rs, wu, mask, h->win_per_cu);
-    }
-    if (h->sell) {
-        const int first = which == 2 ? h->nst_int : 0;
-        const int nt = which == 0 ? h->nst_int + h->nst_bnd : (which == 1 ? h->nst_int : h->nst_bnd);
-        return launch_sell_spmm2(st, h->sdev(), h->sslice_ptr(first), nt, rs, wu, mask, h->sell_per_cu);
-    }
-    const int first = which == 2 ? h->nt_int : 0;
-    const int nt = which == 0 ? h->nt_int + h->nt_bnd : (which == 1 ? h->nt_int : h->nt_bnd);
-    const CsrDev A = which == 0 ? h->csr() : (which == 1 ? h->csr(0, h->nt_bnd == 0) : h->csr(h->nt_int, false));
-    return launch_spmm2(st, A, h->tile_ptr(first), nt, h->steps, rs, wu, mask, h->kn);
+    const TileRange t = tile_range(h, which);
+    if (h->win) return launch_win_spmm2(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, mask, h->opt.win_per_cu);
+    if (h->sell) return launch_sell_spmm2(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, h->opt.sell_per_cu);
+    return launch_spmm2(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, h->opt.kn);
 }
+// (only the window kernels have the deferred form that runs one class of tiles; the others always take every tile)
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which = 0) {
     SRCCHK(h, {f.in_old, 2});
-    if (h->win) {
-        const int first = which == 2 ? h->nwt_int : 0;
-        const int nt = which == 0 ? h->nwt_int + h->nwt_bnd : (which == 1 ? h->nwt_int : h->nwt_bnd);
-        return launch_win_pipe_fused(st, h->wdev(), h->wtile_ptr(first), nt, h->win_geom, f,
-                                     f.deferred ? h->defer_per_cu : h->win_per_cu);
-    }
-    if (h->sell) return launch_sell_pipe_fused(st, h->sdev(), h->sslice_ptr(0), h->nst_int + h->nst_bnd, f, h->sell_per_cu);
-    return launch_pipe_fused(st, h->csr(), h->tile_ptr(), h->nt_int + h->nt_bnd, h->steps, f, h->kn);
+    const TileRange t = tile_range(h, h->win ? which : 0);
+    if (h->win)
+        return launch_win_pipe_fused(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, f,
+                                     f.deferred ? h->opt.defer_per_cu : h->opt.win_per_cu);
+    if (h->sell) return launch_sell_pipe_fused(st, h->sdev(), h->sslice_ptr(t.first), t.count, f, h->opt.sell_per_cu);
+    return launch_pipe_fused(st, h->csr(), h->tile_ptr(t.first), t.count, h->steps, f, h->opt.kn);
 }
 
 bool is_pipe(int v) { return v == PRCG_PIPE_PR || v == PRCG_PIPE_P || v == PRCG_PIPE_PR_M || v == PRCG_PIPE_P_M; }
@@ -456,6 +401,10 @@ bool is_pr(int v) { return v == PRCG_PR || v == PRCG_M; }
 bool is_cg_family(int v) { return v == PRCG_CG_CG || v == PRCG_GV; }
 bool pipe_recompute(int v) { return v == PRCG_PIPE_PR || v == PRCG_PIPE_PR_M; }
 bool meurant(int v) { return v == PRCG_PIPE_PR_M || v == PRCG_PIPE_P_M || v == PRCG_M; }
+// a recorder reads the state vectors after every iteration (so no schedule may leave them stale between two launches)
+bool records_state(uint32_t hist_mask) {
+    return (hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) != 0;
+}
 
 // ---- halo exchange of an nc-component extended vector, all on `st` ----------------------
 int exchange(prcg_t* h, double* vec_ext, int nc, hipStream_t st) {
@@ -495,8 +444,7 @@ int allreduce(prcg_t* h, double* buf, int count, hipStream_t st) {
 // on the reduction?  If so, learn where in each neighbour's slot this rank's ghost rows lie:
 // the ranks all-gather their (peer, offset, count) send tables once.
 int plan_gather(prcg_t* h) {
-    h->gather = false;
-    if (!h->multi() || !h->want_gather) return PRCG_OK;
+    if (!h->multi() || !h->opt.want_gather) return PRCG_OK;
     if (h->gather_planned) { h->gather = h->gather_ok; return PRCG_OK; }
     h->gather_planned = true;
     h->gather_ok = false;
@@ -513,7 +461,7 @@ int plan_gather(prcg_t* h) {
     const int64_t max_send = (int64_t)mx[0];
     const int max_peers = (int)mx[1];
     const int64_t slot = 8 + 2 * max_send;
-    if (slot * (int64_t)sizeof(double) > h->gather_max_bytes) return PRCG_OK;      // same verdict on every rank
+    if (slot * (int64_t)sizeof(double) > h->opt.gather_max_bytes) return PRCG_OK;      // same verdict on every rank
     // (b) everybody's send table: [n_peers, (peer, first row of the list, rows) ...]
     const int T = 1 + 3 * max_peers;
     std::vector<double> tab((size_t)R * T, 0.0);
@@ -567,26 +515,16 @@ void fused_flush(prcg_t* h);
 void pr_unpack(prcg_t* h);
 void hs_flush(prcg_t* h);
 void cg_flush(prcg_t* h);
+int flush_pending(prcg_t* h);
 int apply_prec(prcg_t* h, const double* src, int sstride, double* dst, int dstride);
 
 // ---- history recorders for the state of iteration k (compute stream) -------------------
 int record(prcg_t* h, int k) {
     const uint32_t m = h->hist_mask;
-    if (!(m & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM))) return PRCG_OK;
-    if (h->fused && !h->fused_comm) fused_flush(h);    // the recorders reuse the partials buffers
-    if (h->hs_fused) hs_flush(h);
-    if (h->pr_fused) { fused_flush(h); pr_unpack(h); }
-    if (h->cg_one) cg_flush(h);
-    if (h->fused_comm && h->red_pending) HIPCHK(h, hipStreamWaitEvent(h->sc, h->red_event, 0));
-    if (h->peer && h->pend_parts > 0) {
-        // (peer exchange: the last launch's partials are still to be sent by the next launch's communication wave -- the
-        //  recorders reuse the buffer, so the slot goes out now)
-        launch_peer_collect(h->sc, static_cast<const PeerDev*>(h->peer_dev.p), h->pend_k, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k),
-                            h->pub.d(), static_cast<unsigned*>(h->pub_err.p));
-        h->pend_parts = 0;
-    }
+    if (!records_state(m)) return PRCG_OK;
+    int rc = flush_pending(h);      // the recorders reuse the partials buffers and read the state vectors
+    if (rc) return rc;
     const int64_t n = h->n;
-    int rc;
     if (m & PRCG_HIST_RESIDUAL_2_NORM) {
         // |b - A x|   callbacks/residual_2_norm.py:41
         launch_copy(h->sc, h->tmp_ext.d(), 1, x_ptr(h), x_stride(h), n);
@@ -762,11 +700,26 @@ void fused_flush(prcg_t* h) {
 }
 
 // The session runs the deferred (x,p) store: single GPU, window operator, no recorder that reads x between two launches
-// of one prcg_iterate call.  Evaluated when asked (the option may change between calls; the arrays in memory are current
-// outside prcg_iterate's loop whatever the answer was).
+// of one prcg_iterate call.  A property of the open session: PRCG_XP_DEFER is fixed once the operator is set
+// (prcg_set_option refuses it after prcg_set_csr), and the arrays in memory are current outside prcg_iterate's loop.
 bool xp_deferred(const prcg_t* h) {
-    return h->want_xp_defer && h->in_session && is_pipe(h->variant) && h->fused && !h->fused_comm && !h->small && h->win && !h->multi() &&
-           !(h->hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM));
+    const Session& s = *h;
+    return h->opt.want_xp_defer && s.in_session && is_pipe(s.variant) && s.fused && !s.fused_comm && !s.small && h->win && !h->multi() &&
+           !records_state(s.hist_mask);
+}
+
+// what both one-launch pipelined schedules hand their kernel: the state of iteration k-1 and where iteration k goes
+FusedState fused_state(prcg_t* h, int k, double* in_old, double* in_new, double* part_out) {
+    const bool rec = pipe_recompute(h->variant), prec = h->prec;
+    FusedState f{};
+    f.in_old = in_old; f.in_new = in_new; f.xp = h->xp.d();
+    f.rs = prec ? h->rs.d() : nullptr;
+    f.dinv = prec ? h->dinv.d() : nullptr;
+    f.w = rec ? nullptr : h->wv.d();
+    f.wt = (!rec && prec) ? h->wt.d() : nullptr;
+    f.dots_prev = dots_at(h, k - 1); f.coef_out = coef_at(h, k); f.partials = part_out;
+    f.meurant = meurant(h->variant); f.recompute_w = rec;
+    return f;
 }
 
 int iterate_pipe_fused(prcg_t* h, int k) {
@@ -787,15 +740,7 @@ int iterate_pipe_fused(prcg_t* h, int k) {
     // second sample is taken one launch later -- the mean launch time is then the mean of both phases
     const int ps = h->prof_stride;
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on, (h->xphase != 0 && ps > 0 && ps % 2 == 0) ? ((k / ps) & 1) : 0);
-    const bool rec = pipe_recompute(h->variant);
-    FusedState f{};
-    f.in_old = rs_old; f.in_new = rs_new; f.xp = h->xp.d();
-    f.rs = h->prec ? h->rs.d() : nullptr;
-    f.dinv = h->prec ? h->dinv.d() : nullptr;
-    f.w = rec ? nullptr : h->wv.d();
-    f.wt = (!rec && h->prec) ? h->wt.d() : nullptr;
-    f.dots_prev = dots_at(h, k - 1); f.coef_out = coef_at(h, k); f.partials = part_out;
-    f.meurant = meurant(h->variant); f.recompute_w = rec;
+    FusedState f = fused_state(h, k, rs_old, rs_new, part_out);
     f.stream_stores = h->stream_stores;
     f.prev = prev;
     f.prev.xphase = h->xphase;
@@ -826,19 +771,11 @@ int iterate_pipe_fused_comm(prcg_t* h, int k) {
     double* in_old = h->rs_cur;
     double* in_new = (h->rs_cur == bufA) ? bufB : bufA;
     double* part_out = (k & 1) ? h->partB.d() : h->partC.d();
-    const bool rec = pipe_recompute(h->variant);
-    FusedState f{};
-    f.in_old = in_old; f.in_new = in_new; f.xp = h->xp.d();
-    f.rs = h->prec ? h->rs.d() : nullptr;
-    f.dinv = h->prec ? h->dinv.d() : nullptr;
-    f.w = rec ? nullptr : h->wv.d();
-    f.wt = (!rec && h->prec) ? h->wt.d() : nullptr;
-    f.dots_prev = dots_at(h, k - 1); f.coef_out = coef_at(h, k); f.partials = part_out;
-    f.meurant = meurant(h->variant); f.recompute_w = rec;
+    FusedState f = fused_state(h, k, in_old, in_new, part_out);
     // (the deferred form gains nothing from streaming stores where the plain schedule gains 20 % -- S3 on one rank 143.7 against
     //  142.7 us -- and loses 13 % where the vectors just exceed the Infinity Cache -- one half of S3: 78.1 against 68.0 us;
     //  profiles/r04_sweeps.md: plain stores unless PRCG_STREAM_STORES=1 asks)
-    f.stream_stores = h->stream_override > 0 ? 1 : 0;
+    f.stream_stores = h->opt.stream_override > 0 ? 1 : 0;
     f.prev = FusedPrev{};
     f.prev.pub = h->pub.d(); f.prev.want = (unsigned)(k - 1); f.prev.err = static_cast<unsigned*>(h->pub_err.p);
     f.deferred = 1;
@@ -846,7 +783,7 @@ int iterate_pipe_fused_comm(prcg_t* h, int k) {
     // ONE launch over all tiles: the boundary tiles come last in the table and are touched only after the wave has
     // seen the publication (which the ghost rows precede).  The launch signals the communication stream with its own
     // completion (no marker packet on the compute stream: the next iteration's launch follows directly).
-    const bool ext_signal = h->ext_signal && !h->peer;
+    const bool ext_signal = h->opt.ext_signal && !h->peer;
     f.done = ext_signal ? h->e_kdone : nullptr;
     if (h->peer) {
         // direct peer exchange: this launch is the whole iteration -- its tiles send the neighbours' rows, its last workgroup
@@ -1024,7 +961,7 @@ int iterate_hs_fused(prcg_t* h, int k) {
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
         grid = launch_win_hs(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom,
                              h->prec ? h->rt.d() : h->r.d(), h->p_cur, p_new, h->s.d(), h->partB.d(), coef_at(h, k), hs,
-                             h->win_per_cu);
+                             h->opt.win_per_cu);
         LAUNCHCHK(h, grid);
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->p_cur = p_new;
@@ -1086,7 +1023,7 @@ int iterate_pr_fused(prcg_t* h, int k) {
     else SRCCHK2(h, {f.pr.z_old, 1}, {f.pr.zs_old, 1}, {f.pr.p_old, 1});
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
     const int grid = launch_win_pr_one(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f,
-                                       (meurant(h->variant) ? 1 : 0) | (h->stream_stores ? 2 : 0), part_out, coef_at(h, k), h->win_per_cu);
+                                       (meurant(h->variant) ? 1 : 0) | (h->stream_stores ? 2 : 0), part_out, coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     h->pend_parts = grid; h->pend_k = k; h->pend_buf = part_out; h->last_grid = grid;
@@ -1186,7 +1123,7 @@ int iterate_cgcg_fused(prcg_t* h, int k) {
     SRCCHK2(h, {f.pr.z_old, 1}, {f.pr.zs_old, 1}, {f.pr.d, 1});
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
     const int grid = launch_win_cg_w(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f, h->w.d(),
-                                     h->partB.d(), coef_at(h, k), h->win_per_cu);
+                                     h->partB.d(), coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     h->cur_r = r_new;
@@ -1211,7 +1148,7 @@ int iterate_gv_fused(prcg_t* h, int k) {
     SRCCHK2(h, {f.pr.z_old, 1}, {f.pr.zs_old, 1}, {f.pr.d, 1});
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
     const int grid = launch_win_gv_w(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f, h->tvec.d(),
-                                     h->partB.d(), coef_at(h, k), h->win_per_cu);
+                                     h->partB.d(), coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     h->cur_w = w_new;
@@ -1230,6 +1167,27 @@ void cg_flush(prcg_t* h) {
     (void)launch_cg_update_ps(h->sc, cg_args(h, h->pend_k), h->pend_buf, h->pend_parts);
     h->cg_lag = false;
     h->pend_parts = 0;
+}
+
+// Finish what the last launch of the session left pending, each schedule its own: inner products that exist only as block
+// partials, the packed state, the deferred p, s update, the communication chain of the last iteration.  Called before a
+// recorder runs (it reuses the partials buffers and reads the state vectors) and at the end of prcg_iterate (the caller
+// may read or rewrite state next: recorders, teacher forcing).
+int flush_pending(prcg_t* h) {
+    Session& s = *h;
+    if (s.fused && !s.fused_comm) fused_flush(h);
+    if (s.hs_fused) hs_flush(h);
+    if (s.pr_fused) { fused_flush(h); pr_unpack(h); }
+    if (s.cg_one) cg_flush(h);
+    if (s.fused_comm && s.red_pending) HIPCHK(h, hipStreamWaitEvent(h->sc, s.red_event, 0));
+    if (s.peer && s.pend_parts > 0) {
+        // peer exchange: the last launch's partials are sent by the NEXT launch's communication wave -- there may be none, or
+        // a recorder is about to reuse the buffer: this rank's slot goes out now, then every rank's slot is added in rank order
+        launch_peer_collect(h->sc, static_cast<const PeerDev*>(h->peer_dev.p), s.pend_k, s.pend_buf, s.pend_parts, dots_at(h, s.pend_k),
+                            h->pub.d(), static_cast<unsigned*>(h->pub_err.p));
+        s.pend_parts = 0;
+    }
+    return PRCG_OK;
 }
 
 // ONE launch per iteration of Chronopoulos-Gear / Ghysels-Vanroose on a window operator (launch_win_cg_one): the launch of
@@ -1263,7 +1221,7 @@ int iterate_cg_one(prcg_t* h, int k) {
     bool on = false;
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
     const int grid = launch_win_cg_one(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f, gv ? 1 : 0, part_out,
-                                       coef_at(h, k), h->win_per_cu);
+                                       coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     if (gv) { h->cur_w = z0n; h->cur_t = z1n; h->cur_u = z2n; }
@@ -1338,56 +1296,6 @@ int iterate_gv(prcg_t* h, int k) {
     LAUNCHCHK(h, launch_cg_update_ps(h->sc, a));                              // p, s, s~, u; mu by recurrence
     return PRCG_OK;
 }
-
-// One place for every PRCG_* switch: prcg_create reads the environment through it, prcg_set_option
-// sets them per handle.  Returns false for an unknown key.
-bool apply_option(prcg_t* h, const char* key, const char* val) {
-    if (!key || !val) return false;
-    const std::string k(key);
-    const long v = atol(val);
-    if (k == "PRCG_FUSED") h->want_fused = v != 0;
-    else if (k == "PRCG_WIN_SHARE") h->want_share = v != 0;
-    else if (k == "PRCG_SMALL") h->want_small = v != 0;
-    else if (k == "PRCG_COL16") h->want_c16 = v != 0;
-    else if (k == "PRCG_COL8") h->want_c8 = v != 0;
-    else if (k == "PRCG_VALDICT") h->want_vdict = v != 0;
-    else if (k == "PRCG_GATHER") h->want_gather = v != 0;
-    else if (k == "PRCG_GATHER_MAX_BYTES") { if (v >= 64) h->gather_max_bytes = v; }
-    else if (k == "PRCG_GRID_PER_CU") h->kn.per_cu = (v >= 1 && v <= 16) ? (int)v : 0;
-    else if (k == "PRCG_TILE_STEPS") h->steps_override = (v == 1 || v == 2 || v == 4) ? (int)v : 0;
-    else if (k == "PRCG_WIN") h->want_win = v != 0;
-    else if (k == "PRCG_FUSED_COMM") { h->want_fused_comm = v != 0; h->want_fused_comm_rccl = v != 0; }
-    else if (k == "PRCG_PEER") h->want_peer = v != 0;
-    else if (k == "PRCG_SELL") h->want_sell = v != 0;
-    else if (k == "PRCG_CG_ONE") h->want_cg_one = v != 0;
-    else if (k == "PRCG_WIN_BIG") h->want_big = v != 0;
-    else if (k == "PRCG_WIN_PAT") h->want_pat = v != 0;
-    else if (k == "PRCG_WIN_SWEEP") h->want_sweep = (v >= 0 && v <= 2) ? (int)v : 1;
-    else if (k == "PRCG_SWEEP_WAVES") h->sweep_max_waves = (v >= 64 && v <= 16384) ? (int)v : 6144;
-    else if (k == "PRCG_SELL_GRID_PER_CU") h->sell_per_cu = (v >= 1 && v <= 8) ? (int)v : 0;
-    else if (k == "PRCG_SELL_SIGMA") h->sell_sigma_opt = (v >= 64 && v <= (1 << 20)) ? (int)v : 0;
-    else if (k == "PRCG_SELL_PLANES") h->sell_planes_opt = (v >= 0 && v <= 64) ? (int)v : 0;
-    else if (k == "PRCG_SELL_RUNS") h->sell_runs_opt = v != 0;
-    else if (k == "PRCG_SELL_WINDOW") h->sell_window_opt = v == 1 ? 64 : (v >= 0 && v <= 64) ? (int)v : 64;
-    else if (k == "PRCG_SELL_MAX_OVERHEAD_PCT") h->sell_overhead_opt = (v >= 100 && v <= 800) ? (double)v / 100.0 : 0.0;
-    else if (k == "PRCG_PR_PACK") h->want_pr_pack = v != 0 ? 1 : 0;
-    else if (k == "PRCG_PLACE") h->place_k = (v >= 0 && v <= 8) ? (int)v : 0;
-    else if (k == "PRCG_SELL_NT") { h->sell_nt_opt = v != 0; h->sell_nt = v != 0; }
-    else if (k == "PRCG_STREAM_STORES") h->stream_override = v != 0;
-    else if (k == "PRCG_XP_DEFER") h->want_xp_defer = v != 0;
-    else if (k == "PRCG_EXT_SIGNAL") h->ext_signal = v != 0;
-    else if (k == "PRCG_DEFER_GRID_PER_CU") h->defer_per_cu = (v >= 1 && v <= 4) ? (int)v : 0;
-    else if (k == "PRCG_WIN_GRID_PER_CU") h->win_per_cu = (v >= 1 && v <= 32) ? (int)v : 0;
-    else if (k == "PRCG_WIN_MAX_MEAN") { if (v >= 1) h->win_max_mean = (int)v; }
-    else if (k == "PRCG_WIN_ROWS") h->win_rows_override = (v == 64 || v == 128) ? (int)v : 0;
-    else if (k == "PRCG_DEBUG_SHORT_SOURCES") h->debug_short_sources = v != 0;
-    else return false;
-    return true;
-}
-const char* const kOptionKeys[] = {"PRCG_FUSED", "PRCG_SMALL", "PRCG_COL16", "PRCG_COL8",
-                                   "PRCG_VALDICT", "PRCG_GATHER", "PRCG_GATHER_MAX_BYTES", "PRCG_GRID_PER_CU",
-                                   "PRCG_TILE_STEPS", "PRCG_WIN", "PRCG_WIN_GRID_PER_CU", "PRCG_WIN_MAX_MEAN", "PRCG_FUSED_COMM", "PRCG_WIN_ROWS", "PRCG_EXT_SIGNAL", "PRCG_DEFER_GRID_PER_CU",
-                                   "PRCG_WIN_SHARE", "PRCG_DEBUG_SHORT_SOURCES", "PRCG_PEER", "PRCG_STREAM_STORES", "PRCG_SELL", "PRCG_SELL_GRID_PER_CU", "PRCG_SELL_SIGMA", "PRCG_SELL_PLANES", "PRCG_PLACE", "PRCG_SELL_NT", "PRCG_SELL_RUNS", "PRCG_SELL_WINDOW", "PRCG_SELL_MAX_OVERHEAD_PCT", "PRCG_PR_PACK", "PRCG_CG_ONE", "PRCG_WIN_BIG", "PRCG_WIN_PAT", "PRCG_WIN_SWEEP", "PRCG_SWEEP_WAVES", "PRCG_XP_DEFER"};
 
 int h2d(prcg_t* h, double* dst, const double* src, int64_t count) {
     HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyHostToDevice, h->sc));
@@ -1484,6 +1392,108 @@ int drop_block_jacobi(prcg_t* h) {
     return PRCG_OK;
 }
 
+template <typename T>
+int upload(prcg_t* h, DevBuf& dst, const std::vector<T>& src) {
+    if (!src.empty()) HIPCHK(h, hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PRCG_OK;
+}
+
+// the arrays of a plan into the handle's device buffers (padded so the 16-byte stream loads never leave the allocation)
+int upload_operator(prcg_t* h, const OperatorPlan& pl, const int32_t* ip, const int32_t* indices, const double* data) {
+    Operator& op = *h;
+    const int64_t n_rows = pl.n, nnz = pl.nnz;
+    const size_t pad = 32;
+    int rc;
+    HIPCHK(h, op.indptr.alloc(((size_t)n_rows + 1 + pad) * sizeof(int32_t)));
+    HIPCHK(h, op.col.alloc(((size_t)nnz + pad) * sizeof(int32_t)));
+    HIPCHK(h, op.val.alloc(((size_t)nnz + pad) * sizeof(double)));
+    HIPCHK(h, op.tiles.alloc((pl.tiles.size() + 1) * sizeof(Tile)));
+    HIPCHK(h, hipMemcpy(op.indptr.p, ip, ((size_t)n_rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (nnz > 0) {
+        HIPCHK(h, hipMemcpy(op.col.p, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(op.val.p, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = upload(h, op.tiles, pl.tiles))) return rc;
+    HIPCHK(h, op.tile_base.alloc(pl.tbase.size() * sizeof(int32_t)));
+    if ((rc = upload(h, op.tile_base, pl.tbase))) return rc;
+    HIPCHK(h, op.col16.alloc(pl.c16.empty() ? 16 : pl.c16.size() * sizeof(uint16_t)));
+    if ((rc = upload(h, op.col16, pl.c16))) return rc;
+    HIPCHK(h, op.col8.alloc(pl.c8.empty() ? 16 : pl.c8.size()));
+    if ((rc = upload(h, op.col8, pl.c8))) return rc;
+    const bool any_vd = pl.vd_int || pl.vd_bnd;
+    HIPCHK(h, op.vidx8.alloc(any_vd ? pl.vidx.size() : 16));
+    HIPCHK(h, op.vdict.alloc(any_vd ? (pl.vdict.size() + kDictMax) * sizeof(double) : 16));
+    HIPCHK(h, op.vdesc.alloc(any_vd ? pl.vdesc.size() * sizeof(int32_t) : 16));
+    if (any_vd) {
+        if ((rc = upload(h, op.vidx8, pl.vidx))) return rc;
+        if ((rc = upload(h, op.vdict, pl.vdict))) return rc;
+        if ((rc = upload(h, op.vdesc, pl.vdesc))) return rc;
+    }
+    if (pl.sell) {
+        const SellPlan& sp = pl.sp;
+        HIPCHK(h, op.sval.alloc(sp.val.size() * sizeof(double), false));
+        if ((rc = upload(h, op.sval, sp.val))) return rc;
+        HIPCHK(h, op.scol.alloc(sp.col.size() * sizeof(uint16_t), false));
+        if ((rc = upload(h, op.scol, sp.col))) return rc;
+        HIPCHK(h, op.sslices.alloc((pl.sslices.size() + 1) * sizeof(SellSlice)));
+        if ((rc = upload(h, op.sslices, pl.sslices))) return rc;
+        HIPCHK(h, op.srows.alloc((sp.rows.size() + 64) * sizeof(int32_t)));
+        if ((rc = upload(h, op.srows, sp.rows))) return rc;
+        HIPCHK(h, op.sgran.alloc((sp.gran.size() + 64) * sizeof(int32_t)));
+        if ((rc = upload(h, op.sgran, sp.gran))) return rc;
+    }
+    if (pl.win) {
+        if (pl.win_pat) {
+            // pattern tiles: the rows' slot masks (wrel) take the place of the row pointers; no window-index images
+            HIPCHK(h, op.wcw.alloc(64));
+            HIPCHK(h, op.wpat.alloc((pl.pats.size() + 1) * sizeof(PatRec)));
+            if ((rc = upload(h, op.wpat, pl.pats))) return rc;
+        } else if (pl.win_geom >= 2) {
+            HIPCHK(h, op.wcw.alloc(pl.wcw16.size() * sizeof(uint16_t)));
+            if ((rc = upload(h, op.wcw, pl.wcw16))) return rc;
+        } else {
+            HIPCHK(h, op.wcw.alloc(pl.wcw8.size()));
+            if ((rc = upload(h, op.wcw, pl.wcw8))) return rc;
+        }
+        HIPCHK(h, op.wrel.alloc(pl.wrel.size() * sizeof(uint16_t)));
+        if ((rc = upload(h, op.wrel, pl.wrel))) return rc;
+        HIPCHK(h, op.wtiles.alloc((pl.wtiles.size() + 1) * sizeof(WTile)));
+        if ((rc = upload(h, op.wtiles, pl.wtiles))) return rc;
+        if (pl.win_vd) {
+            HIPCHK(h, op.wvidx.alloc(pl.wvidx.size()));
+            if ((rc = upload(h, op.wvidx, pl.wvidx))) return rc;
+            HIPCHK(h, op.wvdict.alloc((pl.wvdict.size() + kWinDictMax) * sizeof(double)));
+            if ((rc = upload(h, op.wvdict, pl.wvdict))) return rc;
+        }
+    }
+    HIPCHK(h, h->tmp_ext.alloc((size_t)2 * (n_rows + pl.g + kGatherPad) * sizeof(double)));
+    HIPCHK(h, h->t1.alloc((size_t)2 * n_rows * sizeof(double)));
+    HIPCHK(h, h->partA.alloc((size_t)8192 * kPartialStride * sizeof(double)));
+    HIPCHK(h, h->partB.alloc((size_t)8192 * kPartialStride * sizeof(double)));
+    return PRCG_OK;
+}
+
+// 32-bit row pointers, checked: inside [0, nnz], monotone, from 0 to nnz
+int checked_indptr(prcg_t* h, int64_t n_rows, int64_t nnz, const void* indptr, int indptr_is64, std::vector<int32_t>& ip) {
+    ip.resize((size_t)n_rows + 1);
+    for (int64_t i = 0; i <= n_rows; ++i) {
+        const int64_t v = indptr_is64 ? static_cast<const int64_t*>(indptr)[i] : static_cast<const int32_t*>(indptr)[i];
+        CHECK(h, v >= 0 && v <= nnz, "prcg_set_csr: indptr[%lld]=%lld out of [0,nnz]", (long long)i, (long long)v);
+        CHECK(h, i == 0 || v >= ip[i - 1], "prcg_set_csr: indptr not monotone at row %lld", (long long)i);
+        ip[i] = (int32_t)v;
+    }
+    CHECK(h, ip[0] == 0 && ip[n_rows] == nnz, "prcg_set_csr: indptr must run from 0 to nnz");
+    return PRCG_OK;
+}
+
+uint64_t fnv1a(uint64_t hash, const void* data, size_t bytes) {
+    const unsigned char* c = static_cast<const unsigned char*>(data);
+    for (size_t i = 0; i < bytes; ++i) { hash ^= c[i]; hash *= 0x100000001b3ull; }
+    return hash;
+}
+template <typename T>
+uint64_t fnv1a(uint64_t hash, const std::vector<T>& v) { return fnv1a(hash, v.data(), v.size() * sizeof(T)); }
+
 void destroy_events(std::vector<EventPair>& evs) {
     for (auto& e : evs) { if (e.a) (void)hipEventDestroy(e.a); if (e.b) (void)hipEventDestroy(e.b); }
     evs.clear();
@@ -1514,8 +1524,8 @@ int prcg_create(prcg_t** out, int device_id) {
     if (!h) return fail(nullptr, PRCG_ENOMEM, "out of host memory");
     h->dev = device_id;
     // every switch lives in the handle from here on (no lazily read environment anywhere else)
-    for (const char* key : kOptionKeys)
-        if (const char* e = getenv(key)) (void)apply_option(h, key, e);
+    for (int i = 0; i < kNumOptions; ++i)
+        if (const char* e = getenv(kOptions[i].key)) kOptions[i].set(h->opt, atol(e));
     // the communication stream outranks the compute stream: its small kernels (halo pack,
     // partial reduction, RCCL) must get CU slots while the matrix product floods the chip
     int prio_lo = 0, prio_hi = 0;
@@ -1595,7 +1605,7 @@ int prcg_set_option(prcg_t* h, const char* key, const char* value) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, key && value, "prcg_set_option: null key or value");
     CHECK(h, !h->have_csr, "prcg_set_option: options are fixed once the operator is set (call it before prcg_set_csr)");
-    CHECK(h, apply_option(h, key, value), "prcg_set_option: unknown option '%s'", key);
+    CHECK(h, apply_option(h->opt, key, value), "prcg_set_option: unknown option '%s'", key);
     return PRCG_OK;
 }
 
@@ -1634,6 +1644,7 @@ int prcg_comm_init(prcg_t* h, const char* rccl_path, int rank, int nranks, const
     return PRCG_OK;
 }
 
+// check arguments -> plan_operator (host only, prcg_plan.cpp) -> upload the plan's arrays -> keep its flags
 int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const void* indptr, int indptr_is64,
                  const int32_t* indices, const double* data) {
     if (!h) return PRCG_EINVAL;
@@ -1645,352 +1656,22 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const 
     HIPCHK(h, hipSetDevice(h->dev));
     if (int rc = drop_block_jacobi(h)) return rc;     // ... and drops block-Jacobi blocks, sized for the old one
 
-    // --- validate on the host before anything reaches a kernel ---
-    std::vector<int32_t> ip((size_t)n_rows + 1);
-    for (int64_t i = 0; i <= n_rows; ++i) {
-        const int64_t v = indptr_is64 ? static_cast<const int64_t*>(indptr)[i] : static_cast<const int32_t*>(indptr)[i];
-        CHECK(h, v >= 0 && v <= nnz, "prcg_set_csr: indptr[%lld]=%lld out of [0,nnz]", (long long)i, (long long)v);
-        CHECK(h, i == 0 || v >= ip[i - 1], "prcg_set_csr: indptr not monotone at row %lld", (long long)i);
-        ip[i] = (int32_t)v;
-    }
-    CHECK(h, ip[0] == 0 && ip[n_rows] == nnz, "prcg_set_csr: indptr must run from 0 to nnz");
-    const int64_t ncols = n_rows + n_ghost;
-    std::vector<uint8_t> cls((size_t)n_rows, 0);
-    int max_len = 0;
-    for (int64_t i = 0; i < n_rows; ++i) {
-        uint8_t c = 0;
-        for (int32_t q = ip[i]; q < ip[i + 1]; ++q) {
-            const int32_t j = indices[q];
-            CHECK(h, j >= 0 && j < ncols, "prcg_set_csr: column index %d out of [0,%lld) in row %lld", j,
-                  (long long)ncols, (long long)i);
-            if (j >= n_rows) c = 1;
-        }
-        cls[i] = c;
-        if (ip[i + 1] - ip[i] > max_len) max_len = ip[i + 1] - ip[i];
-    }
-    h->max_row_len = max_len;
-    std::vector<Tile> t0, t1;
-    h->steps = pick_tile_steps(h->steps_override, n_rows, nnz);
-    plan_tiles(n_rows, ip.data(), n_ghost > 0 ? cls.data() : nullptr, tile_cap_nnz(h->steps), kTileCapRows, t0, t1);
-    std::vector<Tile> all(t0);
-    all.insert(all.end(), t1.begin(), t1.end());
-
-    // --- window tiles (row-per-lane kernels): tried first; when every tile of the operator qualifies the
-    // narrow encodings of the CSR-adaptive kernels below are not built at all ---
-    h->win = false; h->win_vd = false; h->nwt_int = h->nwt_bnd = 0;
-    WinPlan wp;
-    std::vector<WTile> wall;
-    std::vector<uint8_t> wvidx;
-    std::vector<double> wvdict;
-    // pattern tiles first (constant-coefficient stencils: 64-row tiles, at most kWinPatPages pages, every tile one pattern --
-    // prcg_plan.h: plan_window_patterns): no per-nonzero stream at all
-    h->win_pat = false;
-    std::vector<PatRec> pats;
-    std::vector<uint16_t> pmasks;
-    h->sweep_waves = h->sweep_tiles = 0;
-    if (h->want_win && h->want_pat && (h->want_sweep == 2 || (h->want_sweep == 1 && n_rows >= 5000000)) && h->want_vdict &&
-        !h->win_rows_override && n_ghost == 0 && nnz > 0 && nnz <= (int64_t)kPatSlots * n_rows) {
-        // a stencil on a regular grid, long launches: sweep order (a wave's consecutive tiles = the same rows of consecutive grid
-        // planes; the pages they share stay in LDS -- prcg_plan.h: plan_sweep_tiles), then the pattern check as for any tiling
-        SweepPlan sw;
-        if (plan_sweep_tiles(n_rows, ncols, ip.data(), indices, kWinPatPages, h->sweep_max_waves, sw) &&
-            plan_window_patterns(sw.tiles, ip.data(), sw.cw.data(), data, pats, pmasks)) {
-            h->win = true; h->win_pat = true; h->win_vd = true; h->win_geom = kWinPatGeom; h->win_rows = 64;
-            h->sweep_waves = sw.waves; h->sweep_tiles = (int)sw.tiles.size();
-            wall.swap(sw.tiles);
-            wp.t0 = wall; wp.t1.clear();
-        }
-    }
-    if (!h->win_pat && h->want_win && h->want_pat && h->want_vdict && !h->win_rows_override && n_rows >= 64 && nnz > 0 && nnz <= (int64_t)kPatSlots * n_rows) {
-        WinPlan wq;
-        plan_window_tiles(n_rows, ncols, ip.data(), indices, n_ghost > 0 ? cls.data() : nullptr, 64, kWinCapNnz, kWinPatPages, wq);
-        if (wq.ok0 && wq.ok1 && wq.t0.size() + wq.t1.size() < (size_t)(1 << 26)) {
-            std::vector<WTile> wa(wq.t0);
-            wa.insert(wa.end(), wq.t1.begin(), wq.t1.end());
-            if (plan_window_patterns(wa, ip.data(), wq.cw.data(), data, pats, pmasks)) {
-                h->win = true; h->win_pat = true; h->win_vd = true; h->win_geom = kWinPatGeom; h->win_rows = 64;
-                wall.swap(wa);
-                wp.t0.swap(wq.t0); wp.t1.swap(wq.t1);
-            }
-        }
-    }
-    if (!h->win_pat && h->want_win && n_rows >= 64 && nnz > 0 && nnz <= (int64_t)h->win_max_mean * n_rows) {
-        int rows = h->win_rows_override ? h->win_rows_override : (nnz < 10 * n_rows ? 128 : 64);
-        plan_window_tiles(n_rows, ncols, ip.data(), indices, n_ghost > 0 ? cls.data() : nullptr, rows, kWinCapNnz,
-                          win_max_pages(rows), wp);
-        int most = wp.pages0 > wp.pages1 ? wp.pages0 : wp.pages1;
-        if (!h->win_rows_override && rows == 128 && wp.ok0 && wp.ok1 && most > 8) {
-            // short rows whose 128-row tiles need more than eight pages (a 3-D stencil: its plane neighbours): 64-row tiles of
-            // at most eight pages stream better (S2: +6 % with the dictionary, +4.5 % plain; r03_sweeps.md J), where they qualify
-            WinPlan w64;
-            plan_window_tiles(n_rows, ncols, ip.data(), indices, n_ghost > 0 ? cls.data() : nullptr, 64, kWinCapNnz, win_max_pages(64), w64);
-            const int m64 = w64.pages0 > w64.pages1 ? w64.pages0 : w64.pages1;
-            if (w64.ok0 && w64.ok1 && win_geometry(64, m64) >= 0) {
-                wp.t0.swap(w64.t0); wp.t1.swap(w64.t1); wp.cw.swap(w64.cw);
-                wp.pages0 = w64.pages0; wp.pages1 = w64.pages1;
-                rows = 64; most = m64;
-            }
-        }
-        const int geom = win_geometry(rows, most);
-        if (wp.ok0 && wp.ok1 && geom >= 0 && wp.t0.size() + wp.t1.size() < (size_t)(1 << 26)) {
-            h->win = true; h->win_geom = geom; h->win_rows = rows;
-            wall = wp.t0;
-            wall.insert(wall.end(), wp.t1.begin(), wp.t1.end());
-            if (h->want_vdict) {
-                wvidx.assign((size_t)nnz + 32, 0);
-                h->win_vd = plan_window_dict(wall, data, kWinDictMax, wvidx, wvdict);
-                if (!h->win_vd) { for (auto& t : wall) t.vd_first = t.vd_count = 0; }
-            }
-        }
-    }
-    // --- sliced rows (lane-per-row kernels): operators that are no window operators but whose rows are long enough for
-    // a lane each -- assembled FEM matrices -- when the padding to the slices' longest rows stays below 25 % ---
-    h->sell = false; h->nst_int = h->nst_bnd = 0;
-    SellPlan sp;
-    // (rows of 24 nonzeros and more: shorter rows that are no window operator keep the CSR-adaptive kernels with their
-    //  narrow column / value encodings -- a lane per row pays once a row is a sizeable share of a tile)
-    if (!h->win && h->want_sell && n_rows >= 64 && nnz >= 24 * n_rows) {
-        SellOptions so;
-        so.sigma = h->sell_sigma_opt;
-        so.planes = h->sell_planes_opt;
-        so.allow_runs = h->sell_runs_opt;
-        so.window_granules = h->sell_window_opt;
-        if (h->sell_overhead_opt > 0.0) so.max_overhead = h->sell_overhead_opt;
-        h->sell = plan_sell(n_rows, ip.data(), indices, data, n_ghost > 0 ? cls.data() : nullptr, so, sp);
-    }
-    const bool classic_enc = !h->win && !h->sell;      // column / value re-encodings of the CSR-adaptive kernels
-
-    // --- 16-bit tile-relative column encoding (host, once) ---
-    std::vector<int32_t> tbase(all.size() + 1, 0);
-    std::vector<uint16_t> c16;
-    std::vector<uint8_t> c8;
-    bool fit_int = classic_enc && h->want_c16 && !all.empty(), fit_bnd = classic_enc && h->want_c16;
-    bool fit8_int = fit_int && h->want_c8, fit8_bnd = fit_bnd && h->want_c8;
-    if (classic_enc && h->want_c16) {
-        const int cap = tile_cap_nnz(h->steps);
-        for (size_t ti = 0; ti < all.size(); ++ti) {
-            const Tile& tl = all[ti];
-            if (tl.nnz_end - tl.nnz_begin > cap || tl.nnz_end == tl.nnz_begin) continue;   // long row / empty: not streamed
-            int32_t lo_c = indices[tl.nnz_begin], hi_c = lo_c;
-            for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) {
-                lo_c = indices[q] < lo_c ? indices[q] : lo_c;
-                hi_c = indices[q] > hi_c ? indices[q] : hi_c;
-            }
-            tbase[ti] = lo_c;
-            if (hi_c - lo_c >= 65536) { if (ti < t0.size()) fit_int = false; else fit_bnd = false; }
-            if (hi_c - lo_c >= 256) { if (ti < t0.size()) fit8_int = false; else fit8_bnd = false; }
-        }
-        if (fit_int || (fit_bnd && !t1.empty())) {
-            c16.assign((size_t)nnz + 8, 0);
-            for (size_t ti = 0; ti < all.size(); ++ti) {
-                const bool ok = ti < t0.size() ? fit_int : fit_bnd;
-                const Tile& tl = all[ti];
-                if (!ok || tl.nnz_end - tl.nnz_begin > cap) continue;
-                for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) c16[q] = (uint16_t)(indices[q] - tbase[ti]);
-            }
-        }
-    }
-    h->c16_int = fit_int && !c16.empty();
-    h->c16_bnd = fit_bnd && !c16.empty() && !t1.empty();
-    fit8_int = fit8_int && h->c16_int;
-    fit8_bnd = fit8_bnd && h->c16_bnd;
-    if (fit8_int || fit8_bnd) {
-        c8.assign((size_t)nnz + 8, 0);
-        for (size_t ti = 0; ti < all.size(); ++ti) {
-            const bool ok = ti < t0.size() ? fit8_int : fit8_bnd;
-            const Tile& tl = all[ti];
-            if (!ok || tl.nnz_end - tl.nnz_begin > tile_cap_nnz(h->steps)) continue;
-            for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) c8[q] = (uint8_t)(indices[q] - tbase[ti]);
-        }
-    }
-    h->c8_int = fit8_int;
-    h->c8_bnd = fit8_bnd;
-
-    // --- value dictionary (host, once): per streamed tile the distinct bit patterns of its values;
-    // a class of tiles qualifies if none of its tiles needs more than kDictMax entries.
-    std::vector<uint8_t> vidx;
-    std::vector<double> vdict;
-    std::vector<int32_t> vdesc;     // {first entry, count} per tile
-    bool vd_int = classic_enc && h->want_vdict && !t0.empty(), vd_bnd = classic_enc && h->want_vdict && !t1.empty();
-    if (vd_int || vd_bnd) {
-        const int cap = tile_cap_nnz(h->steps);
-        vidx.assign((size_t)nnz + 8, 0);
-        vdesc.assign(2 * (all.size() + 1), 0);
-        vdict.reserve(all.size() * 4);
-        constexpr int kHash = 256;          // open addressing, <= kDictMax live keys
-        uint64_t keys[kHash];
-        int16_t slot_of[kHash];
-        for (size_t ti = 0; ti < all.size(); ++ti) {
-            const bool interior = ti < t0.size();
-            if (!(interior ? vd_int : vd_bnd)) continue;
-            const Tile& tl = all[ti];
-            if (tl.nnz_end - tl.nnz_begin > cap || tl.nnz_end == tl.nnz_begin) continue;   // long row / empty: not streamed
-            for (int i = 0; i < kHash; ++i) slot_of[i] = -1;
-            const size_t first = vdict.size();
-            int count = 0;
-            bool ok = true;
-            for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) {
-                uint64_t bits;
-                memcpy(&bits, &data[q], sizeof bits);
-                uint32_t hsh = (uint32_t)((bits * 0x9E3779B97F4A7C15ull) >> 56);   // 8 bits
-                while (slot_of[hsh] >= 0 && keys[hsh] != bits) hsh = (hsh + 1) & (kHash - 1);
-                if (slot_of[hsh] < 0) {
-                    if (count == kDictMax) { ok = false; break; }
-                    keys[hsh] = bits;
-                    slot_of[hsh] = (int16_t)count++;
-                    vdict.push_back(data[q]);
-                }
-                vidx[q] = (uint8_t)slot_of[hsh];
-            }
-            if (!ok) {
-                vdict.resize(first);
-                if (interior) vd_int = false; else vd_bnd = false;
-                continue;
-            }
-            vdesc[2 * ti] = (int32_t)first;
-            vdesc[2 * ti + 1] = count;
-        }
-        if (vdict.size() >= (size_t)INT32_MAX) vd_int = vd_bnd = false;
-    }
-    h->vd_int = vd_int;
-    h->vd_bnd = vd_bnd && !t1.empty();
-
-    // --- upload (arrays padded so the 16-byte stream loads never leave the allocation) ---
-    const size_t pad = 32;
-    HIPCHK(h, h->indptr.alloc(((size_t)n_rows + 1 + pad) * sizeof(int32_t)));
-    HIPCHK(h, h->col.alloc(((size_t)nnz + pad) * sizeof(int32_t)));
-    HIPCHK(h, h->val.alloc(((size_t)nnz + pad) * sizeof(double)));
-    HIPCHK(h, h->tiles.alloc((all.size() + 1) * sizeof(Tile)));
-    HIPCHK(h, hipMemcpy(h->indptr.p, ip.data(), ((size_t)n_rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (nnz > 0) {
-        HIPCHK(h, hipMemcpy(h->col.p, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->val.p, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (!all.empty())
-        HIPCHK(h, hipMemcpy(h->tiles.p, all.data(), all.size() * sizeof(Tile), hipMemcpyHostToDevice));
-    HIPCHK(h, h->tile_base.alloc(tbase.size() * sizeof(int32_t)));
-    HIPCHK(h, hipMemcpy(h->tile_base.p, tbase.data(), tbase.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(h, h->col16.alloc(c16.empty() ? 16 : c16.size() * sizeof(uint16_t)));
-    if (!c16.empty())
-        HIPCHK(h, hipMemcpy(h->col16.p, c16.data(), c16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIPCHK(h, h->col8.alloc(c8.empty() ? 16 : c8.size()));
-    if (!c8.empty()) HIPCHK(h, hipMemcpy(h->col8.p, c8.data(), c8.size(), hipMemcpyHostToDevice));
-    const bool any_vd = h->vd_int || h->vd_bnd;
-    HIPCHK(h, h->vidx8.alloc(any_vd ? vidx.size() : 16));
-    HIPCHK(h, h->vdict.alloc(any_vd ? (vdict.size() + kDictMax) * sizeof(double) : 16));
-    HIPCHK(h, h->vdesc.alloc(any_vd ? vdesc.size() * sizeof(int32_t) : 16));
-    if (any_vd) {
-        HIPCHK(h, hipMemcpy(h->vidx8.p, vidx.data(), vidx.size(), hipMemcpyHostToDevice));
-        if (!vdict.empty())
-            HIPCHK(h, hipMemcpy(h->vdict.p, vdict.data(), vdict.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->vdesc.p, vdesc.data(), vdesc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    if (h->sell) {
-        h->nst_int = (int)sp.s0.size(); h->nst_bnd = (int)sp.s1.size();
-        std::vector<SellSlice> sall(sp.s0);
-        sall.insert(sall.end(), sp.s1.begin(), sp.s1.end());
-        HIPCHK(h, h->sval.alloc(sp.val.size() * sizeof(double), false));
-        HIPCHK(h, hipMemcpy(h->sval.p, sp.val.data(), sp.val.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(h, h->scol.alloc(sp.col.size() * sizeof(uint16_t), false));
-        HIPCHK(h, hipMemcpy(h->scol.p, sp.col.data(), sp.col.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(h, h->sslices.alloc((sall.size() + 1) * sizeof(SellSlice)));
-        if (!sall.empty()) HIPCHK(h, hipMemcpy(h->sslices.p, sall.data(), sall.size() * sizeof(SellSlice), hipMemcpyHostToDevice));
-        HIPCHK(h, h->srows.alloc((sp.rows.size() + 64) * sizeof(int32_t)));
-        if (!sp.rows.empty()) HIPCHK(h, hipMemcpy(h->srows.p, sp.rows.data(), sp.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        // what a product reads of the operator: 8 B per (padded) value, 2 B per (padded) column code, the slice descriptors, and
-        // the row pointers (slices of consecutive rows) or the slices' (row, stored length) pairs
-        HIPCHK(h, h->sgran.alloc((sp.gran.size() + 64) * sizeof(int32_t)));
-        if (!sp.gran.empty()) HIPCHK(h, hipMemcpy(h->sgran.p, sp.gran.data(), sp.gran.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        h->sell_window = sp.window;
-        // ... and with WINDOW codes the granule starts (the window pages themselves are vector traffic: every entry a slice touches,
-        // read once per slice instead of once per nonzero)
-        h->sell_bytes = sp.padded_nnz * 8 + sp.col_entries * 2 + (int64_t)sall.size() * 32 + 4 * (n_rows + 1) + (int64_t)sp.rows.size() * 4 +
-                        (int64_t)sp.gran.size() * 4;
-        h->sell_sigma = sp.sigma; h->sell_planes = sp.planes; h->sell_stride = sp.stride_rows; h->sell_run = sp.run;
-        sp = SellPlan{};
-    }
+    // --- validate on the host before anything reaches a kernel, then decide family and encodings ---
+    std::vector<int32_t> ip;
+    if (int rc = checked_indptr(h, n_rows, nnz, indptr, indptr_is64, ip)) return rc;
+    OperatorPlan pl;
+    std::string why;
+    if (!plan_operator(h->opt, n_rows, n_ghost, nnz, ip.data(), indices, data, pl, why)) return fail(h, PRCG_EINVAL, "%s", why.c_str());
+    // (the flags describe the upload in progress, as they always have: a failed upload leaves have_csr as it was)
+    static_cast<OperatorShape&>(*h) = pl;
+    if (int rc = upload_operator(h, pl, ip.data(), indices, data)) return rc;
     h->peer_ok = false;
     h->wt_rb.clear(); h->wt_re.clear();
-    if (h->win) {
-        h->nwt_int = (int)wp.t0.size(); h->nwt_bnd = (int)wp.t1.size();
-        for (const auto& t : wall) { h->wt_rb.push_back(t.rb); h->wt_re.push_back(t.re); }
-        // the tiles' stream images: byte-identical ones are stored once (prcg_plan.h: share_window_streams)
-        std::vector<uint8_t> vstore;
-        std::vector<uint16_t> rstore;
-        size_t cw_bytes = 0;
-        if (h->win_pat) {
-            // pattern tiles: the rows' slot masks take the place of the row pointers; no window-index / value-index images
-            rstore.swap(pmasks);
-            rstore.resize(rstore.size() + 64, 0);
-            HIPCHK(h, h->wcw.alloc(64));
-            HIPCHK(h, h->wpat.alloc((pats.size() + 1) * sizeof(PatRec)));
-            HIPCHK(h, hipMemcpy(h->wpat.p, pats.data(), pats.size() * sizeof(PatRec), hipMemcpyHostToDevice));
-            cw_bytes = pats.size() * sizeof(PatRec);
-            vstore.assign(64, 0);
-        } else if (h->win_geom >= 2) {
-            std::vector<uint16_t> cstore;
-            share_window_streams<uint16_t>(wall, ip.data(), wp.cw.data(), h->win_vd ? wvidx.data() : nullptr, h->want_share,
-                                           cstore, vstore, rstore);
-            cw_bytes = cstore.size() * sizeof(uint16_t);
-            HIPCHK(h, h->wcw.alloc(cw_bytes));
-            HIPCHK(h, hipMemcpy(h->wcw.p, cstore.data(), cw_bytes, hipMemcpyHostToDevice));
-        } else {
-            std::vector<uint8_t> c8w(wp.cw.size()), cstore;
-            for (size_t q = 0; q < wp.cw.size(); ++q) c8w[q] = (uint8_t)wp.cw[q];
-            share_window_streams<uint8_t>(wall, ip.data(), c8w.data(), h->win_vd ? wvidx.data() : nullptr, h->want_share,
-                                          cstore, vstore, rstore);
-            cw_bytes = cstore.size();
-            HIPCHK(h, h->wcw.alloc(cw_bytes));
-            HIPCHK(h, hipMemcpy(h->wcw.p, cstore.data(), cw_bytes, hipMemcpyHostToDevice));
-        }
-        // period of the images over the interior tiles (a stencil on a regular grid: a grid line, a grid plane): the
-        // smallest P with image(t + P) == image(t) for every t of a long stretch in the middle of the table
-        h->win_period = 0;
-        if (h->want_share && h->win_vd && !h->win_pat && wp.t0.size() > 4096) {
-            const size_t nt0 = wp.t0.size(), t0 = nt0 / 3;
-            for (size_t P = 2; P <= 4096 && t0 + 3 * P < nt0; ++P) {
-                if (wall[t0 + P].spare != wall[t0].spare || wall[t0].spare == 0) continue;
-                bool ok = true;
-                for (size_t j = 0; j < 2 * P && ok; ++j) ok = wall[t0 + j + P].spare == wall[t0 + j].spare;
-                if (ok) { h->win_period = (int)P; break; }
-            }
-            if (wall[t0 + 1].spare == wall[t0].spare && wall[t0 + 2].spare == wall[t0].spare) h->win_period = 0;   // (period 1: nothing to align)
-        }
-        HIPCHK(h, h->wrel.alloc(rstore.size() * sizeof(uint16_t)));
-        HIPCHK(h, hipMemcpy(h->wrel.p, rstore.data(), rstore.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(h, h->wtiles.alloc((wall.size() + 1) * sizeof(WTile)));
-        HIPCHK(h, hipMemcpy(h->wtiles.p, wall.data(), wall.size() * sizeof(WTile), hipMemcpyHostToDevice));
-        h->win_stream_bytes = (int64_t)(wall.size() * sizeof(WTile) + cw_bytes + rstore.size() * sizeof(uint16_t)) +
-                              (h->win_pat ? 0 : (h->win_vd ? (int64_t)(vstore.size() + wvdict.size() * sizeof(double)) : (int64_t)nnz * 8));
-        if (h->win_vd) {
-            HIPCHK(h, h->wvidx.alloc(vstore.size()));
-            HIPCHK(h, hipMemcpy(h->wvidx.p, vstore.data(), vstore.size(), hipMemcpyHostToDevice));
-            HIPCHK(h, h->wvdict.alloc((wvdict.size() + kWinDictMax) * sizeof(double)));
-            if (!wvdict.empty())
-                HIPCHK(h, hipMemcpy(h->wvdict.p, wvdict.data(), wvdict.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
-    h->n = n_rows; h->g = n_ghost; h->nnz = nnz;
-    h->nt_int = (int)t0.size(); h->nt_bnd = (int)t1.size();
-    // what one launch moves -- the operator as streamed plus 64 bytes of vectors per row: beyond the Infinity Cache
-    // (256 MB) the next launch finds none of its row results cached anyway (S3 +23 %, s4b +4 %, S2 +2 %; S1 and one
-    // eighth of S3 fit and lose 4-8 % with streaming stores)
-    HIPCHK(h, h->tmp_ext.alloc((size_t)2 * (n_rows + n_ghost + kGatherPad) * sizeof(double)));
-    HIPCHK(h, h->t1.alloc((size_t)2 * n_rows * sizeof(double)));
-    HIPCHK(h, h->partA.alloc((size_t)8192 * kPartialStride * sizeof(double)));
-    HIPCHK(h, h->partB.alloc((size_t)8192 * kPartialStride * sizeof(double)));
+    if (pl.win)
+        for (const WTile& t : pl.wtiles) { h->wt_rb.push_back(t.rb); h->wt_re.push_back(t.re); }
     h->have_csr = true;
     h->have_halo = false;
     h->gather_planned = false;
-    h->stream_stores = h->stream_override >= 0 ? h->stream_override
-                                               : ((int64_t)64 * n_rows + prcg_operator_bytes(h) > (int64_t)256 << 20);
-    // sliced rows with a sorting window: a slice's rows lie anywhere in the window, its 16-byte row results are PARTS of cache
-    // lines that the other slices of the window complete -- plain stores let the L2 merge them (nontemporal ones wrote 1.54 x the
-    // bytes: s4c 706 -> 675 us, profiles/r04_sweeps.md)
-    if (h->sell && h->sell_sigma > 64 && h->stream_override < 0) h->stream_stores = 0;
-    // ... and the value / code streams of an operator far larger than the Infinity Cache are read with nontemporal loads
-    // (s4b at 3.4 GB: 638 -> 610 us, s4c +4.6 %; at 1.3 GB -1 %)
-    if (h->sell && h->sell_nt_opt < 0) h->sell_nt = h->sell_bytes >= (int64_t)2000 << 20;
     return PRCG_OK;
 }
 
@@ -2331,9 +2012,9 @@ int place_session_vectors(prcg_t* h, size_t xp_bytes, size_t rs_bytes) {
     if (rc) return rc;
     if (getenv("PRCG_PLAN_DEBUG")) fprintf(stderr, "place_session_vectors: placement 0: %.1f us (stream %d KB per 64 rows)\n", best / 3 * 1e3, kb);
     // (every placement stays allocated until the choice is made: a freed one would be handed out again for the next)
-    std::vector<std::array<DevBuf, 3>> cand((size_t)h->place_k - 1);
+    std::vector<std::array<DevBuf, 3>> cand((size_t)h->opt.place_k - 1);
     int best_c = -1;
-    for (int c = 0; c + 1 < h->place_k; ++c) {
+    for (int c = 0; c + 1 < h->opt.place_k; ++c) {
         DevBuf& cx = cand[(size_t)c][0]; DevBuf& cr = cand[(size_t)c][1]; DevBuf& cr2 = cand[(size_t)c][2];
         if (cx.alloc(xp_bytes, false) != hipSuccess || cr.alloc(rs_bytes, false) != hipSuccess || cr2.alloc(rs_bytes, false) != hipSuccess) {
             (void)hipGetLastError();                 // (no room for another placement: the ones so far compete; the error is not the session's)
@@ -2362,57 +2043,69 @@ int place_session_vectors(prcg_t* h, size_t xp_bytes, size_t rs_bytes) {
     return PRCG_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// ---- session start --------------------------------------------------------------------------------------------
+// Every session is opened here, whichever family it belongs to: the shared argument checks, THE reset of the session state
+// (the only assignment of Session{}), the fields every family fills the same way, the caller's leading vectors (`lead`:
+// allocated before the scalar arrays, as they always were -- the order of hipMalloc decides where a vector lies), then
+// dinv, dots and coef, and the profiling sample counts.  The session stays closed (in_session false) until its family
+// has computed the initial state.
+struct Lead { DevBuf* buf; size_t bytes; };
+int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
+                 std::initializer_list<Lead> lead) {
+    CHECK(h, h->have_csr, "%s: call prcg_set_csr first", who);
+    CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
+    HIPCHK(h, hipSetDevice(h->dev));
+    static_cast<Session&>(*h) = Session{};
+    Session& s = *h;
+    s.variant = variant;
+    s.bj_session = h->bj_bs > 0 && inv_diag == nullptr;
+    s.stored_tilde = (h->cb != nullptr || s.bj_session) && inv_diag == nullptr;
+    s.prec = inv_diag != nullptr || s.stored_tilde;
+    CHECK(h, !(s.stored_tilde && h->multi()), "a host-callback or block-Jacobi preconditioner runs on one GPU only");
+    if (s.stored_tilde && !s.bj_session) HIPCHK(h, h->cb_stage.ensure((size_t)h->n * sizeof(double), h->sc));
+    s.max_iter = max_iter;
+    s.hist_mask = hist_mask;
+    s.have_xtrue = have_xtrue;
+    h->n_ev_spmv = h->n_ev_upd = 0;
+    const size_t D = sizeof(double);
+    for (const Lead& l : lead) HIPCHK(h, l.buf->ensure(l.bytes, h->sc));
+    // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries (dinv is a window source of
+    // the Chronopoulos-Gear product launch)
+    HIPCHK(h, h->dinv.ensure((size_t)(h->n + h->g + kGatherPad) * D, h->sc));
+    HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * kNS * D, h->sc));
+    HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * kCoefStride * D, h->sc));
+    if (inv_diag) return h2d(h, h->dinv.d(), inv_diag, h->n);
+    return PRCG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, int max_iter, const double* x_true,
                      const double* inv_diag, uint32_t hist_mask) {
     if (!h) return PRCG_EINVAL;
-    CHECK(h, h->have_csr, "prcg_solve_begin: call prcg_set_csr first");
     CHECK(h, variant >= 0 && variant < PRCG_NUM_VARIANTS, "prcg_solve_begin: unknown variant %d", variant);
     CHECK(h, b && x0, "prcg_solve_begin: null b or x0");
-    CHECK(h, max_iter >= 1, "prcg_solve_begin: max_iter must be >= 1");
     CHECK(h, (hist_mask & ~PRCG_HIST_ALL) == 0, "prcg_solve_begin: unknown history bits");
     CHECK(h, !(hist_mask & (PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) || x_true,
           "prcg_solve_begin: error histories need x_true");
     CHECK(h, h->g == 0 || (h->multi() && h->have_halo), "ghost columns need a communicator and a halo plan");
-    HIPCHK(h, hipSetDevice(h->dev));
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries: the
     // narrow column encodings decode a few out-of-tile bytes per tile against the tile's own base
     // (products nobody reads); the pad keeps those gathers inside the allocation without a test
     const int64_t n = h->n, ne = h->n + h->g + kGatherPad;
     const size_t D = sizeof(double);
-    h->in_session = false;
-    h->rhs2 = false;
-    h->variant = variant;
-    h->fused = false;
-    h->hs_fused = false;
-    h->cg_fused = false;
-    h->pr_fused = false;
-    h->pr_packed = false;
-    h->hs_pend_mu = 0;
-    h->small = false; h->small_hs = false;
-    h->gather = false;
-    h->bj_session = h->bj_bs > 0 && inv_diag == nullptr;
-    h->stored_tilde = (h->cb != nullptr || h->bj_session) && inv_diag == nullptr;
-    h->prec = inv_diag != nullptr || h->stored_tilde;
-    CHECK(h, !(h->stored_tilde && h->multi()), "a host-callback or block-Jacobi preconditioner runs on one GPU only");
-    if (h->stored_tilde && !h->bj_session) HIPCHK(h, h->cb_stage.ensure((size_t)h->n * sizeof(double), h->sc));
-    h->max_iter = max_iter;
-    h->hist_mask = hist_mask;
-    h->have_xtrue = x_true != nullptr;
-    h->k = 0;
-    h->n_ev_spmv = h->n_ev_upd = 0;
-
-    HIPCHK(h, h->x.ensure((size_t)n * D, h->sc));
-    HIPCHK(h, h->b.ensure((size_t)n * D, h->sc));
-    HIPCHK(h, h->xt.ensure((size_t)n * D, h->sc));
-    HIPCHK(h, h->e_ext.ensure((size_t)ne * D, h->sc));
-    HIPCHK(h, h->dinv.ensure((size_t)ne * D, h->sc));     // (a window source of the Chronopoulos-Gear product launch)
-    HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * kNS * D, h->sc));
-    HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * kCoefStride * D, h->sc));
-    int rc;
+    int rc = open_session(h, "prcg_solve_begin", variant, max_iter, hist_mask, inv_diag, x_true != nullptr,
+                          {{&h->x, (size_t)n * D}, {&h->b, (size_t)n * D}, {&h->xt, (size_t)n * D}, {&h->e_ext, (size_t)ne * D}});
+    if (rc) return rc;
     if ((rc = h2d(h, h->x.d(), x0, n))) return rc;
     if ((rc = h2d(h, h->b.d(), b, n))) return rc;
     if (x_true && (rc = h2d(h, h->xt.d(), x_true, n))) return rc;
-    if (inv_diag && (rc = h2d(h, h->dinv.d(), inv_diag, n))) return rc;
     hipStream_t sc = h->sc;
     double* tmp = h->tmp_ext.d();
     double* t1 = h->t1.d();
@@ -2422,13 +2115,10 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     if ((rc = dist_spmv(h, tmp, t1, kEpiNone, nullptr, nullptr, nullptr, nullptr))) return rc;
 
     if (is_pipe(variant)) {
-        h->fused = h->want_fused && !h->multi() && h->g == 0 && !h->stored_tilde;
-        // with a communicator: the same kernel in its deferred form (window operators only)
-        h->fused_comm = false;
-        h->red_pending = false;
+        h->fused = h->opt.want_fused && !h->multi() && h->g == 0 && !h->stored_tilde;
         // direct peer exchange (every rank connected, window operator): the one-launch schedule without a collective.
         // Whether it is connected is the same on every rank (the host side connects all ranks or none).
-        h->peer = h->peer_ok && h->want_peer && h->want_fused && h->multi() && h->win && !h->stored_tilde;
+        h->peer = h->peer_ok && h->opt.want_peer && h->opt.want_fused && h->multi() && h->win && !h->stored_tilde;
         if (!h->peer && (rc = plan_gather(h))) return rc;
         // with a communicator: the same kernel in its deferred form -- window operators whose halo rides on the
         // one all-gather per iteration (bands; the merged exchange).  Larger halos (send/recv + all-reduce chain)
@@ -2436,12 +2126,12 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         // from the communication stream while a launch waited for it (profiles/r02_sweeps.md).
         // (the one-launch schedule over the RCCL all-gather chain is opt-in, PRCG_FUSED_COMM=1: its launches wait inside the
         //  kernel for kernels of ANOTHER stream to become resident, which has only ever been validated with one rank)
-        h->fused_comm = h->peer || (h->want_fused && h->want_fused_comm_rccl && h->multi() && h->win && h->gather);
+        h->fused_comm = h->peer || (h->opt.want_fused && h->opt.want_fused_comm_rccl && h->multi() && h->win && h->gather);
         if (h->fused_comm) h->fused = true;        // state layout, derived vectors: as the one-launch schedule
         HIPCHK(h, h->xp.ensure((size_t)2 * n * D, h->sc));
         HIPCHK(h, h->rs.ensure((size_t)2 * (h->prec ? n : ne) * D, h->sc));
         HIPCHK(h, h->rs2.ensure((h->fused && !h->prec) ? (size_t)2 * ne * D : 16, h->sc));
-        if (h->place_k > 1 && h->fused && !h->prec && h->placed_xp != h->xp.p && h->rs.bytes == h->rs2.bytes) {       // (every rank for itself: its vectors are its own)
+        if (h->opt.place_k > 1 && h->fused && !h->prec && h->placed_xp != h->xp.p && h->rs.bytes == h->rs2.bytes) {       // (every rank for itself: its vectors are its own)
             int prc = place_session_vectors(h, h->xp.bytes, h->rs.bytes);
             if (prc) return prc;
         }
@@ -2450,11 +2140,10 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         HIPCHK(h, h->partC.ensure(h->fused ? (size_t)8192 * kPartialStride * sizeof(double) : 16, h->sc));
         HIPCHK(h, h->pub.ensure(h->fused_comm ? kPubDoubles * sizeof(double) : 16, h->sc));
         HIPCHK(h, h->pub_err.ensure(64, h->sc));
-        h->pend_parts = 0; h->pend_k = -1; h->pend_buf = nullptr;
         h->rs_cur = h->rs.d();
         // one-workgroup solver: only when nothing but the recurrence residual is recorded
-        h->small = h->fused && !h->fused_comm && h->want_small && !h->prec && pipe_recompute(variant) &&
-                   !(hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) &&
+        h->small = h->fused && !h->fused_comm && h->opt.want_small && !h->prec && pipe_recompute(variant) &&
+                   !records_state(hist_mask) &&
                    small_fits(h->n, h->nnz, h->max_row_len, &h->small_mode);
         HIPCHK(h, h->rst.ensure(h->prec ? (size_t)2 * ne * D : 16, h->sc));
         if (h->prec) h->rs_cur = h->rst.d();
@@ -2541,18 +2230,16 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         h->p_cur = h->p.d();
         HIPCHK(h, h->r.ensure((size_t)ne * D, h->sc));
         h->cur_r = h->r.d();
-        h->cg_fused = h->want_fused && !h->multi() && h->g == 0 && h->win && !h->stored_tilde &&
+        h->cg_fused = h->opt.want_fused && !h->multi() && h->g == 0 && h->win && !h->stored_tilde &&
                       !(variant == PRCG_GV && h->replace_fn);      // (the predicate is called between the update and the product)
         // one launch per iteration: both variants unpreconditioned, Chronopoulos-Gear with Jacobi too
-        h->cg_one = h->cg_fused && h->want_cg_one && (variant == PRCG_CG_CG || !h->prec);
-        h->cg_lag = false;
+        h->cg_one = h->cg_fused && h->opt.want_cg_one && (variant == PRCG_CG_CG || !h->prec);
         HIPCHK(h, h->r2.ensure((h->cg_fused && variant == PRCG_CG_CG) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->w2.ensure((h->cg_fused && (variant == PRCG_GV || h->cg_one)) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->s2.ensure((h->cg_one && variant == PRCG_CG_CG) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->u2.ensure((h->cg_one && variant == PRCG_GV) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->t2.ensure((h->cg_one && variant == PRCG_GV) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->partC.ensure(h->cg_one ? (size_t)8192 * kPartialStride * sizeof(double) : 16, h->sc));
-        h->pend_parts = 0; h->pend_k = -1; h->pend_buf = nullptr;
         HIPCHK(h, h->rt.ensure(h->prec ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->w.ensure((size_t)ne * D, h->sc));
         h->cur_w = h->w.d();
@@ -2596,32 +2283,30 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         // HS and non-pipelined PR share the layout x, r, (r~), p(+ghosts), s, (s~)
         HIPCHK(h, h->p.ensure((size_t)ne * D, h->sc));
         h->p_cur = h->p.d();
-        h->hs_fused = variant == PRCG_HS && h->want_fused && !h->multi() && h->g == 0 && !h->stored_tilde;
+        h->hs_fused = variant == PRCG_HS && h->opt.want_fused && !h->multi() && h->g == 0 && !h->stored_tilde;
         // one-workgroup solver (k_small_hs): only when nothing but the recurrence residual is recorded
-        h->small_hs = h->hs_fused && h->want_small && !h->prec &&
-                      !(hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) &&
+        h->small_hs = h->hs_fused && h->opt.want_small && !h->prec &&
+                      !records_state(hist_mask) &&
                       small_fits(h->n, h->nnz, h->max_row_len, &h->small_mode);
         // r (r~) is the staged-window source of the Hestenes-Stiefel product launch: like every vector that feeds a
         // product it has the spare entries behind its end (a window page of the last tile may reach past row n)
-        HIPCHK(h, h->r.ensure((size_t)(h->debug_short_sources ? n : ne) * D, h->sc));
+        HIPCHK(h, h->r.ensure((size_t)(h->opt.debug_short_sources ? n : ne) * D, h->sc));
         HIPCHK(h, h->s.ensure((size_t)ne * D, h->sc));
         HIPCHK(h, h->rt.ensure(h->prec ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->st.ensure(h->prec ? (size_t)ne * D : 16, h->sc));
         // one launch per iteration for pr / m on a window operator: second copies of what the window is formed from
-        h->pr_fused = is_pr(variant) && h->want_fused && !h->multi() && h->g == 0 && h->win && !h->stored_tilde;
+        h->pr_fused = is_pr(variant) && h->opt.want_fused && !h->multi() && h->g == 0 && h->win && !h->stored_tilde;
         HIPCHK(h, h->p2.ensure(((h->hs_fused && h->win) || h->pr_fused) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->r2.ensure((h->pr_fused && !h->prec) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->s2.ensure((h->pr_fused && !h->prec) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->rt2.ensure((h->pr_fused && h->prec) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->st2.ensure((h->pr_fused && h->prec) ? (size_t)ne * D : 16, h->sc));
         HIPCHK(h, h->partC.ensure(h->pr_fused ? (size_t)8192 * kPartialStride * sizeof(double) : 16, h->sc));
-        h->pr_packed = h->pr_fused && (h->want_pr_pack < 0 ? h->win_pat : h->want_pr_pack != 0) && !h->prec &&
-                       !(hist_mask & (PRCG_HIST_RESIDUAL_2_NORM | PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM));
-        h->pr_q_valid = false;
+        h->pr_packed = h->pr_fused && (h->opt.want_pr_pack < 0 ? h->win_pat : h->opt.want_pr_pack != 0) && !h->prec &&
+                       !records_state(hist_mask);
         HIPCHK(h, h->q.ensure(h->pr_packed ? (size_t)4 * ne * D : 16, h->sc));
         HIPCHK(h, h->q2.ensure(h->pr_packed ? (size_t)4 * ne * D : 16, h->sc));
         h->cur_r = h->r.d(); h->cur_s = h->s.d(); h->cur_rt = h->rt.d(); h->cur_st = h->st.d();
-        h->pend_parts = 0; h->pend_k = -1; h->pend_buf = nullptr;
         launch_sub(sc, h->r.d(), 1, h->b.d(), 1, t1, 1, n);                 // r = b - A x
         if (h->prec) {
             if ((rc = apply_prec(h, h->r.d(), 1, h->rt.d(), 1))) return rc;   // r~ = M^-1 r
@@ -2733,21 +2418,8 @@ int prcg_iterate(prcg_t* h, int iters) {
         h->k = k;
     }
     h->xphase = 0;
-    if (h->fused && !h->fused_comm) fused_flush(h);    // dots of the last iteration: one reduction per call, not per iteration
-    if (h->hs_fused) hs_flush(h);
-    if (h->pr_fused) { fused_flush(h); pr_unpack(h); }
-    if (h->cg_one) cg_flush(h);
-    if (h->fused_comm && h->red_pending) {
-        // the caller may read or rewrite state next (recorders, teacher forcing): finish the exchange of the last iteration
-        HIPCHK(h, hipStreamWaitEvent(h->sc, h->red_event, 0));
-    }
-    if (h->peer && h->pend_parts > 0 && h->pend_k == h->k) {
-        // the inner products of the last iteration: this rank's slot goes out now (no next launch to send it), then every
-        // rank's slot is added in rank order
-        launch_peer_collect(h->sc, static_cast<const PeerDev*>(h->peer_dev.p), h->k, h->pend_buf, h->pend_parts, dots_at(h, h->k),
-                            h->pub.d(), static_cast<unsigned*>(h->pub_err.p));
-        h->pend_parts = 0;
-    }
+    // dots of the last iteration: one reduction per call, not per iteration; the caller may read or rewrite state next
+    if (int rc = flush_pending(h)) return rc;
     return PRCG_OK;
 }
 
@@ -2770,15 +2442,7 @@ int prcg_sync(prcg_t* h) {
 
 int prcg_iteration(const prcg_t* h) { return h ? h->k : -1; }
 
-int64_t prcg_operator_bytes(const prcg_t* h) {
-    if (!h || !h->have_csr) return -1;
-    if (h->win) return h->win_stream_bytes;
-    if (h->sell) return h->sell_bytes;
-    // CSR-adaptive tiles: row pointers, tile table, column stream as encoded, values or dictionary indices
-    const int64_t colb = h->c8_int ? 1 : (h->c16_int ? 2 : 4);
-    const int64_t nt = (int64_t)h->nt_int + h->nt_bnd;
-    return 4 * (h->n + 1) + nt * (int64_t)sizeof(Tile) + h->nnz * colb + (h->vd_int ? h->nnz + nt * 16 : h->nnz * 8);
-}
+int64_t prcg_operator_bytes(const prcg_t* h) { return (h && h->have_csr) ? h->bytes() : -1; }
 
 int prcg_schedule(const prcg_t* h) {
     if (!h) return -1;
@@ -2931,7 +2595,6 @@ int prcg_get_history(prcg_t* h, double* hist) {
 int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
                            const double* inv_diag, uint32_t hist_mask) {
     if (!h) return PRCG_EINVAL;
-    CHECK(h, h->have_csr, "prcg_solve_begin_multi: call prcg_set_csr first");
     CHECK(h, nrhs == 2, "prcg_solve_begin_multi: nrhs = %d: the multi-RHS session serves exactly 2 right-hand sides", nrhs);
     CHECK(h, variant == PRCG_HS, "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg) only", variant);
     CHECK(h, !h->multi(), "prcg_solve_begin_multi: a communicator is set on the handle: the two-RHS session runs on one GPU");
@@ -2944,42 +2607,20 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
           "prcg_solve_begin_multi: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the two-RHS session");
     CHECK(h, b && x0 && b[0] && b[1] && x0[0] && x0[1], "prcg_solve_begin_multi: null b or x0");
-    CHECK(h, max_iter >= 1, "prcg_solve_begin_multi: max_iter must be >= 1");
-    HIPCHK(h, hipSetDevice(h->dev));
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
-    // what prcg_solve_begin resets, so that prcg_schedule / prcg_sync / a later ordinary session see no stale schedule
-    h->in_session = false;
-    h->variant = PRCG_HS;
-    h->fused = false; h->hs_fused = false; h->cg_fused = false; h->pr_fused = false; h->pr_packed = false;
-    h->hs_pend_mu = 0;
-    h->small = false; h->small_hs = false;
-    h->gather = false;
-    h->bj_session = false; h->stored_tilde = false;
-    h->prec = inv_diag != nullptr;
-    h->max_iter = max_iter;
-    h->hist_mask = hist_mask;
-    h->have_xtrue = false;
-    h->k = 0;
-    h->n_ev_spmv = h->n_ev_upd = 0;
-    h->rhs2 = true;
     // X and P feed the two-vector product: like every product source they carry the spare entries behind row n
-    HIPCHK(h, h->mx.ensure((size_t)2 * ne * D, h->sc));
-    HIPCHK(h, h->mp.ensure((size_t)2 * ne * D, h->sc));
-    HIPCHK(h, h->mr.ensure((size_t)2 * n * D, h->sc));
-    HIPCHK(h, h->ms.ensure((size_t)2 * n * D, h->sc));
-    HIPCHK(h, h->mrt.ensure(h->prec ? (size_t)2 * n * D : 16, h->sc));
-    HIPCHK(h, h->dinv.ensure((size_t)ne * D, h->sc));
-    HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * kNS * D, h->sc));
-    HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * kCoefStride * D, h->sc));
+    int rc = open_session(h, "prcg_solve_begin_multi", PRCG_HS, max_iter, hist_mask, inv_diag, false,
+                          {{&h->mx, (size_t)2 * ne * D}, {&h->mp, (size_t)2 * ne * D}, {&h->mr, (size_t)2 * n * D}, {&h->ms, (size_t)2 * n * D},
+                           {&h->mrt, inv_diag ? (size_t)2 * n * D : 16}});
+    if (rc) return rc;
+    h->rhs2 = true;
     std::vector<double> pairs;
     try { pairs.resize((size_t)2 * n); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "prcg_solve_begin_multi: host staging"); }
-    int rc;
     for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = x0[0][i]; pairs[2 * i + 1] = x0[1][i]; }
     if ((rc = h2d(h, h->mx.d(), pairs.data(), 2 * n))) return rc;
     for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = b[0][i]; pairs[2 * i + 1] = b[1][i]; }
     if ((rc = h2d(h, h->mr.d(), pairs.data(), 2 * n))) return rc;
-    if (inv_diag && (rc = h2d(h, h->dinv.d(), inv_diag, n))) return rc;
     hipStream_t sc = h->sc;
     // r = b - A x0 for both columns (hs_cg.py:23): one two-vector product of [x0_0 x0_1], parked in S
     LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->mx.d(), h->ms.d(), 3));
@@ -3099,6 +2740,58 @@ int prcg_solve(prcg_t* h, int variant, const double* b, const double* x0, int ma
     if (x_out && (rc = prcg_get_vector(h, PRCG_VEC_X, x_out))) return rc;
     if (t) rc = prcg_get_timings(h, t);
     return rc;
+}
+
+int64_t prcg_plan_operator(int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
+                           const double* data, const char* const* keys, const char* const* values, int n_options, int64_t* out,
+                           int64_t capacity) {
+    constexpr int64_t kFields = 18;
+    if (n_rows < 0 || n_ghost < 0 || nnz < 0 || !indptr32 || (nnz > 0 && (!indices || !data)) || n_options < 0 ||
+        (n_options > 0 && (!keys || !values)) || !out)
+        return -1;
+    if (capacity < kFields) return -kFields;
+    if (indptr32[0] != 0 || indptr32[n_rows] != nnz) return -1;
+    for (int64_t i = 0; i < n_rows; ++i)
+        if (indptr32[i + 1] < indptr32[i]) return -1;
+    Options opt;
+    for (int i = 0; i < n_options; ++i)
+        if (!apply_option(opt, keys[i], values[i])) return -1;
+    OperatorPlan pl;
+    std::string why;
+    if (!plan_operator(opt, n_rows, n_ghost, nnz, indptr32, indices, data, pl, why)) return -1;
+    const int cw = pl.win_pat ? 0 : (pl.win_geom < 2 ? 1 : 2);
+    out[0] = pl.win ? 1 : (pl.sell ? 2 : 0);
+    out[1] = pl.win ? pl.win_geom : -1;
+    out[2] = pl.win ? pl.win_rows : 0;
+    out[3] = pl.win_pat ? 1 : 0;
+    out[4] = pl.sweep_waves;
+    out[5] = pl.win ? pl.win_vd : pl.vd_int;
+    out[6] = pl.win ? pl.win_vd : pl.vd_bnd;
+    out[7] = pl.win ? cw : (pl.sell ? 2 : (pl.c8_int ? 1 : (pl.c16_int ? 2 : 4)));
+    out[8] = pl.win ? cw : (pl.sell ? 2 : (pl.c8_bnd ? 1 : (pl.c16_bnd ? 2 : 4)));
+    out[9] = pl.steps;
+    out[10] = pl.win ? pl.nwt_int : (pl.sell ? pl.nst_int : pl.nt_int);
+    out[11] = pl.win ? pl.nwt_bnd : (pl.sell ? pl.nst_bnd : pl.nt_bnd);
+    out[12] = pl.win_period;
+    out[13] = pl.bytes();
+    // what upload_operator copies, array after array (an array that is not uploaded adds nothing)
+    const uint64_t seed = 0xcbf29ce484222325ull;
+    const bool any_vd = pl.vd_int || pl.vd_bnd, win_vd = pl.win && pl.win_vd;
+    uint64_t hi = seed, hv = seed, hd = seed, ht = seed;
+    hi = fnv1a(hi, pl.c16); hi = fnv1a(hi, pl.c8); hi = fnv1a(hi, pl.tbase);
+    if (pl.win) { hi = fnv1a(hi, pl.wcw16); hi = fnv1a(hi, pl.wcw8); hi = fnv1a(hi, pl.wrel); }
+    if (pl.sell) { hi = fnv1a(hi, pl.sp.col); hi = fnv1a(hi, pl.sp.rows); hi = fnv1a(hi, pl.sp.gran); }
+    if (any_vd) hv = fnv1a(hv, pl.vidx);
+    if (win_vd) hv = fnv1a(hv, pl.wvidx);
+    if (any_vd) { hd = fnv1a(hd, pl.vdict); hd = fnv1a(hd, pl.vdesc); }
+    if (win_vd) hd = fnv1a(hd, pl.wvdict);
+    if (pl.win && pl.win_pat) hd = fnv1a(hd, pl.pats);
+    if (pl.sell) hd = fnv1a(hd, pl.sp.val);
+    ht = fnv1a(ht, pl.tiles);
+    if (pl.win) ht = fnv1a(ht, pl.wtiles);
+    if (pl.sell) ht = fnv1a(ht, pl.sslices);
+    out[14] = (int64_t)hi; out[15] = (int64_t)hv; out[16] = (int64_t)hd; out[17] = (int64_t)ht;
+    return kFields;
 }
 
 int64_t prcg_plan_tiles(int64_t n, const int32_t* indptr, const uint8_t* row_class, int cap_nnz, int cap_rows,
@@ -3248,7 +2941,7 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity) {
     out[2] = h->win ? h->win_rows : 0;
     out[3] = nt;
     out[4] = h->last_grid;                                                        // workgroups of the last one-launch iteration
-    out[5] = h->win ? win_fused_waves_per_block(h->win_geom, h->win_vd, h->fused_comm, h->nwt_int + h->nwt_bnd, h->want_big, h->sweep_waves) : 4;
+    out[5] = h->win ? win_fused_waves_per_block(h->win_geom, h->win_vd, h->fused_comm, h->nwt_int + h->nwt_bnd, h->opt.want_big, h->sweep_waves) : 4;
     out[6] = h->win ? h->nwt_int : h->nt_int;
     out[7] = h->win ? (int64_t)h->sweep_waves << 8 : 0;    // bit 0: always 0 (was the retired XCD-chunked tile order); >> 8: waves of a sweep table
     std::vector<int32_t> rows((size_t)nt * 2);

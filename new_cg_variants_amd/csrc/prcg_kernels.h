@@ -4,22 +4,13 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "prcg_geometry.h"
+
 namespace prcg {
 
-// ---- tile geometry (must agree with the host planner) -----------------------------
-// A tile is a run of consecutive rows handled by ONE wavefront: its nonzeros are
-// streamed with 16-byte loads, the products staged in that wave's LDS slice, and each
-// row reduced sequentially (left to right, as scipy's csr_matvec does) by one lane.
-constexpr int kDefaultTileSteps = 2;                // 256-nnz steps per tile (1, 2 or 4)
-inline int tile_cap_nnz(int steps) { return 256 * steps - 3; }   // -3: the stream starts 16-B aligned
-constexpr int kTileCapRows = 256;
+// ---- launch geometry (tile geometry shared with the host planner: prcg_geometry.h) ----
 constexpr int kMaxGridBlocks = 2048;                // 8 blocks x 256 CUs
 constexpr int kPartialStride = 8;                   // doubles per block in a partials array
-
-#ifndef PRCG_TILE_DEFINED
-#define PRCG_TILE_DEFINED
-struct alignas(16) Tile { int row_begin, row_end, nnz_begin, nnz_end; };
-#endif
 
 // ---- direct peer exchange over xGMI (multi-rank one-launch schedule) ------------------------
 // Every rank owns one EXCHANGE BUFFER (fine-grained device memory, mapped into every other rank's process with
@@ -168,13 +159,6 @@ struct CsrDev {
     const double* vdict;
     const int2* vd;            // per tile (same indexing as the tile table): {first entry, count}
 };
-constexpr int kDictMax = 64;   // one dictionary entry per lane
-// spare entries behind every gather-source vector: the largest tile-relative column offset (16 bit)
-// added to a valid column of the tile never leaves the allocation
-constexpr int kGatherPad = 65536;
-
-// experiment knobs of the tile kernels, owned by the handle (read once in prcg_create / prcg_set_option)
-struct TileKnobs { int per_cu = 0; };
 
 // y = A x over tiles[0..ntiles).  x has ghost room; y has n_rows entries.
 // partials: [grid][kPartialStride] doubles (slots 0..2 used by the epilogues) or null.
@@ -206,33 +190,6 @@ int launch_pipe_fused(hipStream_t st, const CsrDev& A, const Tile* tiles, int nt
 // device-internal, lossless re-encodings: cw8 / cw16[q] = index of col[q] in the tile's staged
 // window of the input vector (page * 64 + offset); vidx8 / vdict = per-tile value dictionary
 // (<= kWinDictMax distinct bit patterns per tile; entries ARE the caller's doubles).
-constexpr int kWinSlots = 1024;                 // nonzeros of one window tile that fit the wave's LDS slice
-constexpr int kWinCapNnz = kWinSlots - 15;      // the stream starts at a multiple of 16 nonzeros
-constexpr int kWinDictMax = 256;
-#ifndef PRCG_WTILE_DEFINED
-#define PRCG_WTILE_DEFINED
-constexpr int kWinMaxPages = 12;
-struct alignas(16) WTile {
-    int rb, re, lo, hi;
-    int geo, maxlen, vd_first, vd_count;
-    int page_col[kWinMaxPages];
-    int src_c, src_v, src_r, spare;
-};
-#endif
-static_assert(sizeof(WTile) == 96, "the kernels read a window tile descriptor as six int4");
-#ifndef PRCG_PATREC_DEFINED
-#define PRCG_PATREC_DEFINED
-// pattern tiles (prcg_plan.h: plan_window_patterns): constant-coefficient stencils without index streams
-constexpr int kPatSlots = 16;
-constexpr int kPatValues = 4;
-struct alignas(8) PatRec {
-    int nslots;
-    unsigned vsel;
-    short cb[kPatSlots];
-    double val[kPatValues];
-};
-static_assert(sizeof(PatRec) == 72, "the kernels read a pattern record with scalar loads");
-#endif
 struct WinDev {
     const int* indptr;
     const double* val;
@@ -247,18 +204,6 @@ struct WinDev {
     int period;                    // > 1: tiles t and t + period read the same stream images (host: the launch picks a wave
                                    // count that is a multiple of it, so that a wave meets the same image tile after tile)
 };
-// geometry id of a class planned with rows_per_tile (64 | 128) whose tiles need at most most_pages
-// pages: 0 = 64 rows / 2 pages / 8-bit indices, 1 = 64 / 4 / 8-bit, 2 = 128 / 8 / 16-bit, 3 = 128 / 12 / 16-bit,
-// 4 = 64 / 8 / 16-bit (3-D stencils in 64-row tiles: images repeat with the period of a grid plane)
-// 5 = 64 rows / 6 pages / PATTERN tiles (constant-coefficient stencils, no index streams; chosen by prcg_set_csr when every
-//     tile qualifies, prcg_plan.h: plan_window_patterns)
-constexpr int kWinPatGeom = 5, kWinPatPages = 6;
-inline int win_geometry(int rows_per_tile, int most_pages) {
-    if (rows_per_tile == 64) return most_pages <= 2 ? 0 : (most_pages <= 4 ? 1 : (most_pages <= 8 ? 4 : -1));
-    if (rows_per_tile == 128) return most_pages <= 8 ? 2 : (most_pages <= 12 ? 3 : -1);
-    return -1;
-}
-inline int win_max_pages(int rows_per_tile) { return rows_per_tile == 64 ? 8 : 12; }
 // same contracts as launch_spmv / launch_spmm2 / launch_pipe_fused below; per_cu > 0 overrides the
 // number of workgroups launched per CU (experiments)
 int launch_win_spmv(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* x, double* y,

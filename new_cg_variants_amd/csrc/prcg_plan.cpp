@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <unordered_map>
 
@@ -92,7 +93,7 @@ int window_pages(std::vector<WTile>& tiles, size_t first, size_t last, int64_t n
             if (np == max_pages || np == kWinMaxPages) { fail = true; break; }
             // keep the page inside the vector where possible (its 64 entries are loaded unconditionally); a page
             // pushed behind the previous one may still end up to 63 entries past n_cols -- every vector that feeds
-            // a product is allocated with spare entries behind its end (kGatherPad, prcg_engine.cpp)
+            // a product is allocated with spare entries behind its end (kGatherPad, prcg_geometry.h)
             // (a page of ghost columns is not pulled back below n_own; it may end past n_cols like a pushed one)
             if ((int64_t)c + 64 > n_cols) c = (int32_t)std::max<int64_t>(n_cols - 64, (int64_t)c >= n_own ? n_own : 0);
             if (np > 0 && c < page_end(page[np - 1])) c = (int32_t)page_end(page[np - 1]);   // the columns a page SERVES never overlap
@@ -969,6 +970,358 @@ int plan_gather_sources(int rank, int T, const double* tab, int n_peers, const i
         for (int64_t i = 0; i < want; ++i) src[(size_t)(recv_ptr[q] + i)] = (int32_t)(first + i);
     }
     return 0;
+}
+
+// ---- options ---------------------------------------------------------------------------------------------
+#define OPT(key, expr) {key, [](Options& o, long v) { expr; }}
+const OptionDef kOptions[] = {
+    OPT("PRCG_FUSED", o.want_fused = v != 0),
+    OPT("PRCG_SMALL", o.want_small = v != 0),
+    OPT("PRCG_COL16", o.want_c16 = v != 0),
+    OPT("PRCG_COL8", o.want_c8 = v != 0),
+    OPT("PRCG_VALDICT", o.want_vdict = v != 0),
+    OPT("PRCG_GATHER", o.want_gather = v != 0),
+    OPT("PRCG_GATHER_MAX_BYTES", if (v >= 64) o.gather_max_bytes = v),
+    OPT("PRCG_GRID_PER_CU", o.kn.per_cu = (v >= 1 && v <= 16) ? (int)v : 0),
+    OPT("PRCG_TILE_STEPS", o.steps_override = (v == 1 || v == 2 || v == 4) ? (int)v : 0),
+    OPT("PRCG_WIN", o.want_win = v != 0),
+    OPT("PRCG_WIN_GRID_PER_CU", o.win_per_cu = (v >= 1 && v <= 32) ? (int)v : 0),
+    OPT("PRCG_WIN_MAX_MEAN", if (v >= 1) o.win_max_mean = (int)v),
+    OPT("PRCG_FUSED_COMM", o.want_fused_comm_rccl = v != 0),
+    OPT("PRCG_WIN_ROWS", o.win_rows_override = (v == 64 || v == 128) ? (int)v : 0),
+    OPT("PRCG_EXT_SIGNAL", o.ext_signal = v != 0),
+    OPT("PRCG_DEFER_GRID_PER_CU", o.defer_per_cu = (v >= 1 && v <= 4) ? (int)v : 0),
+    OPT("PRCG_WIN_SHARE", o.want_share = v != 0),
+    OPT("PRCG_DEBUG_SHORT_SOURCES", o.debug_short_sources = v != 0),
+    OPT("PRCG_PEER", o.want_peer = v != 0),
+    OPT("PRCG_STREAM_STORES", o.stream_override = v != 0),
+    OPT("PRCG_SELL", o.want_sell = v != 0),
+    OPT("PRCG_SELL_GRID_PER_CU", o.sell_per_cu = (v >= 1 && v <= 8) ? (int)v : 0),
+    OPT("PRCG_SELL_SIGMA", o.sell_sigma_opt = (v >= 64 && v <= (1 << 20)) ? (int)v : 0),
+    OPT("PRCG_SELL_PLANES", o.sell_planes_opt = (v >= 0 && v <= 64) ? (int)v : 0),
+    OPT("PRCG_PLACE", o.place_k = (v >= 0 && v <= 8) ? (int)v : 0),
+    OPT("PRCG_SELL_NT", o.sell_nt_opt = v != 0),
+    OPT("PRCG_SELL_RUNS", o.sell_runs_opt = v != 0),
+    OPT("PRCG_SELL_WINDOW", o.sell_window_opt = v == 1 ? 64 : (v >= 0 && v <= 64) ? (int)v : 64),
+    OPT("PRCG_SELL_MAX_OVERHEAD_PCT", o.sell_overhead_opt = (v >= 100 && v <= 800) ? (double)v / 100.0 : 0.0),
+    OPT("PRCG_PR_PACK", o.want_pr_pack = v != 0 ? 1 : 0),
+    OPT("PRCG_CG_ONE", o.want_cg_one = v != 0),
+    OPT("PRCG_WIN_BIG", o.want_big = v != 0),
+    OPT("PRCG_WIN_PAT", o.want_pat = v != 0),
+    OPT("PRCG_WIN_SWEEP", o.want_sweep = (v >= 0 && v <= 2) ? (int)v : 1),
+    OPT("PRCG_SWEEP_WAVES", o.sweep_max_waves = (v >= 64 && v <= 16384) ? (int)v : 6144),
+    OPT("PRCG_XP_DEFER", o.want_xp_defer = v != 0),
+};
+#undef OPT
+const int kNumOptions = (int)(sizeof kOptions / sizeof kOptions[0]);
+
+bool apply_option(Options& o, const char* key, const char* value) {
+    if (!key || !value) return false;
+    for (const OptionDef& d : kOptions)
+        if (strcmp(d.key, key) == 0) { d.set(o, atol(value)); return true; }
+    return false;
+}
+
+// ---- the operator decision ---------------------------------------------------------------------------------
+// Tile size (256-nnz steps per wave tile).  Short rows (stencils: 5-7 nonzeros) do better
+// with 256-slot tiles -- more rows per lane would otherwise serialise the reduce phase
+// (measured: S1 34.3 k vs 31.3 k it/s, S2 3236 vs 3013) -- longer rows with 512-slot tiles
+// (S3, 15 per row: 2115 vs 1885 it/s).  PRCG_TILE_STEPS = 1 | 2 | 4 overrides.
+int pick_tile_steps(int override_, int64_t n, int64_t nnz) {
+    if (override_ == 1 || override_ == 2 || override_ == 4) return override_;
+    if (n > 0 && nnz < 10 * n) return 1;
+    // medium rows (FEM-like, ~50+ nonzeros): the lane-per-row sums are a serial chain per row, so
+    // bigger tiles (more rows summed side by side per wave) win (s4b: 2983 vs 2740 it/s)
+    if (n > 0 && nnz >= 48 * n) return 4;
+    return kDefaultTileSteps;
+}
+
+int64_t OperatorShape::bytes() const {
+    if (win) return win_stream_bytes;
+    if (sell) return sell_bytes;
+    // CSR-adaptive tiles: row pointers, tile table, column stream as encoded, values or dictionary indices
+    const int64_t colb = c8_int ? 1 : (c16_int ? 2 : 4);
+    const int64_t nt = (int64_t)nt_int + nt_bnd;
+    return 4 * (n + 1) + nt * (int64_t)sizeof(Tile) + nnz * colb + (vd_int ? nnz + nt * 16 : nnz * 8);
+}
+
+bool plan_operator(const Options& o, int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
+                   const double* data, OperatorPlan& out, std::string& err) {
+    out = OperatorPlan{};
+    // --- row classes (0: interior, 1: touches a ghost column), longest row; column indices checked on the way ---
+    const int32_t* ip = indptr32;
+    const int64_t ncols = n_rows + n_ghost;
+    std::vector<uint8_t> cls((size_t)n_rows, 0);
+    int max_len = 0;
+    for (int64_t i = 0; i < n_rows; ++i) {
+        uint8_t c = 0;
+        for (int32_t q = ip[i]; q < ip[i + 1]; ++q) {
+            const int32_t j = indices[q];
+            if (j < 0 || j >= ncols) {
+                err = "prcg_set_csr: column index " + std::to_string(j) + " out of [0," + std::to_string(ncols) + ") in row " + std::to_string(i);
+                return false;
+            }
+            if (j >= n_rows) c = 1;
+        }
+        cls[i] = c;
+        if (ip[i + 1] - ip[i] > max_len) max_len = ip[i + 1] - ip[i];
+    }
+    out.max_row_len = max_len;
+    std::vector<Tile> t0, t1;
+    out.steps = pick_tile_steps(o.steps_override, n_rows, nnz);
+    plan_tiles(n_rows, ip, n_ghost > 0 ? cls.data() : nullptr, tile_cap_nnz(out.steps), kTileCapRows, t0, t1);
+    std::vector<Tile>& all = out.tiles;
+    all = t0;
+    all.insert(all.end(), t1.begin(), t1.end());
+
+    // --- window tiles (row-per-lane kernels): tried first; when every tile of the operator qualifies the
+    // narrow encodings of the CSR-adaptive kernels below are not built at all ---
+    WinPlan wp;
+    std::vector<WTile>& wall = out.wtiles;
+    std::vector<uint8_t> wvidx;          // per nonzero; the images the kernels read: out.wvidx
+    std::vector<double>& wvdict = out.wvdict;
+    // pattern tiles first (constant-coefficient stencils: 64-row tiles, at most kWinPatPages pages, every tile one pattern --
+    // prcg_plan.h: plan_window_patterns): no per-nonzero stream at all
+    std::vector<PatRec>& pats = out.pats;
+    std::vector<uint16_t> pmasks;
+    if (o.want_win && o.want_pat && (o.want_sweep == 2 || (o.want_sweep == 1 && n_rows >= 5000000)) && o.want_vdict &&
+        !o.win_rows_override && n_ghost == 0 && nnz > 0 && nnz <= (int64_t)kPatSlots * n_rows) {
+        // a stencil on a regular grid, long launches: sweep order (a wave's consecutive tiles = the same rows of consecutive grid
+        // planes; the pages they share stay in LDS -- prcg_plan.h: plan_sweep_tiles), then the pattern check as for any tiling
+        SweepPlan sw;
+        if (plan_sweep_tiles(n_rows, ncols, ip, indices, kWinPatPages, o.sweep_max_waves, sw) &&
+            plan_window_patterns(sw.tiles, ip, sw.cw.data(), data, pats, pmasks)) {
+            out.win = true; out.win_pat = true; out.win_vd = true; out.win_geom = kWinPatGeom; out.win_rows = 64;
+            out.sweep_waves = sw.waves; out.sweep_tiles = (int)sw.tiles.size();
+            wall.swap(sw.tiles);
+            wp.t0 = wall; wp.t1.clear();
+        }
+    }
+    if (!out.win_pat && o.want_win && o.want_pat && o.want_vdict && !o.win_rows_override && n_rows >= 64 && nnz > 0 && nnz <= (int64_t)kPatSlots * n_rows) {
+        WinPlan wq;
+        plan_window_tiles(n_rows, ncols, ip, indices, n_ghost > 0 ? cls.data() : nullptr, 64, kWinCapNnz, kWinPatPages, wq);
+        if (wq.ok0 && wq.ok1 && wq.t0.size() + wq.t1.size() < (size_t)(1 << 26)) {
+            std::vector<WTile> wa(wq.t0);
+            wa.insert(wa.end(), wq.t1.begin(), wq.t1.end());
+            if (plan_window_patterns(wa, ip, wq.cw.data(), data, pats, pmasks)) {
+                out.win = true; out.win_pat = true; out.win_vd = true; out.win_geom = kWinPatGeom; out.win_rows = 64;
+                wall.swap(wa);
+                wp.t0.swap(wq.t0); wp.t1.swap(wq.t1);
+            }
+        }
+    }
+    if (!out.win_pat && o.want_win && n_rows >= 64 && nnz > 0 && nnz <= (int64_t)o.win_max_mean * n_rows) {
+        int rows = o.win_rows_override ? o.win_rows_override : (nnz < 10 * n_rows ? 128 : 64);
+        plan_window_tiles(n_rows, ncols, ip, indices, n_ghost > 0 ? cls.data() : nullptr, rows, kWinCapNnz,
+                          win_max_pages(rows), wp);
+        int most = wp.pages0 > wp.pages1 ? wp.pages0 : wp.pages1;
+        if (!o.win_rows_override && rows == 128 && wp.ok0 && wp.ok1 && most > 8) {
+            // short rows whose 128-row tiles need more than eight pages (a 3-D stencil: its plane neighbours): 64-row tiles of
+            // at most eight pages stream better (S2: +6 % with the dictionary, +4.5 % plain; r03_sweeps.md J), where they qualify
+            WinPlan w64;
+            plan_window_tiles(n_rows, ncols, ip, indices, n_ghost > 0 ? cls.data() : nullptr, 64, kWinCapNnz, win_max_pages(64), w64);
+            const int m64 = w64.pages0 > w64.pages1 ? w64.pages0 : w64.pages1;
+            if (w64.ok0 && w64.ok1 && win_geometry(64, m64) >= 0) {
+                wp.t0.swap(w64.t0); wp.t1.swap(w64.t1); wp.cw.swap(w64.cw);
+                wp.pages0 = w64.pages0; wp.pages1 = w64.pages1;
+                rows = 64; most = m64;
+            }
+        }
+        const int geom = win_geometry(rows, most);
+        if (wp.ok0 && wp.ok1 && geom >= 0 && wp.t0.size() + wp.t1.size() < (size_t)(1 << 26)) {
+            out.win = true; out.win_geom = geom; out.win_rows = rows;
+            wall = wp.t0;
+            wall.insert(wall.end(), wp.t1.begin(), wp.t1.end());
+            if (o.want_vdict) {
+                wvidx.assign((size_t)nnz + 32, 0);
+                out.win_vd = plan_window_dict(wall, data, kWinDictMax, wvidx, wvdict);
+                if (!out.win_vd) { for (auto& t : wall) t.vd_first = t.vd_count = 0; }
+            }
+        }
+    }
+    // --- sliced rows (lane-per-row kernels): operators that are no window operators but whose rows are long enough for
+    // a lane each -- assembled FEM matrices -- when the padding to the slices' longest rows stays below 25 % ---
+    SellPlan& sp = out.sp;
+    // (rows of 24 nonzeros and more: shorter rows that are no window operator keep the CSR-adaptive kernels with their
+    //  narrow column / value encodings -- a lane per row pays once a row is a sizeable share of a tile)
+    if (!out.win && o.want_sell && n_rows >= 64 && nnz >= 24 * n_rows) {
+        SellOptions so;
+        so.sigma = o.sell_sigma_opt;
+        so.planes = o.sell_planes_opt;
+        so.allow_runs = o.sell_runs_opt;
+        so.window_granules = o.sell_window_opt;
+        if (o.sell_overhead_opt > 0.0) so.max_overhead = o.sell_overhead_opt;
+        out.sell = plan_sell(n_rows, ip, indices, data, n_ghost > 0 ? cls.data() : nullptr, so, sp);
+    }
+    const bool classic_enc = !out.win && !out.sell;      // column / value re-encodings of the CSR-adaptive kernels
+
+    // --- 16-bit tile-relative column encoding (host, once) ---
+    std::vector<int32_t>& tbase = out.tbase;
+    tbase.assign(all.size() + 1, 0);
+    std::vector<uint16_t>& c16 = out.c16;
+    std::vector<uint8_t>& c8 = out.c8;
+    bool fit_int = classic_enc && o.want_c16 && !all.empty(), fit_bnd = classic_enc && o.want_c16;
+    bool fit8_int = fit_int && o.want_c8, fit8_bnd = fit_bnd && o.want_c8;
+    if (classic_enc && o.want_c16) {
+        const int cap = tile_cap_nnz(out.steps);
+        for (size_t ti = 0; ti < all.size(); ++ti) {
+            const Tile& tl = all[ti];
+            if (tl.nnz_end - tl.nnz_begin > cap || tl.nnz_end == tl.nnz_begin) continue;   // long row / empty: not streamed
+            int32_t lo_c = indices[tl.nnz_begin], hi_c = lo_c;
+            for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) {
+                lo_c = indices[q] < lo_c ? indices[q] : lo_c;
+                hi_c = indices[q] > hi_c ? indices[q] : hi_c;
+            }
+            tbase[ti] = lo_c;
+            if (hi_c - lo_c >= 65536) { if (ti < t0.size()) fit_int = false; else fit_bnd = false; }
+            if (hi_c - lo_c >= 256) { if (ti < t0.size()) fit8_int = false; else fit8_bnd = false; }
+        }
+        if (fit_int || (fit_bnd && !t1.empty())) {
+            c16.assign((size_t)nnz + 8, 0);
+            for (size_t ti = 0; ti < all.size(); ++ti) {
+                const bool ok = ti < t0.size() ? fit_int : fit_bnd;
+                const Tile& tl = all[ti];
+                if (!ok || tl.nnz_end - tl.nnz_begin > cap) continue;
+                for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) c16[q] = (uint16_t)(indices[q] - tbase[ti]);
+            }
+        }
+    }
+    out.c16_int = fit_int && !c16.empty();
+    out.c16_bnd = fit_bnd && !c16.empty() && !t1.empty();
+    fit8_int = fit8_int && out.c16_int;
+    fit8_bnd = fit8_bnd && out.c16_bnd;
+    if (fit8_int || fit8_bnd) {
+        c8.assign((size_t)nnz + 8, 0);
+        for (size_t ti = 0; ti < all.size(); ++ti) {
+            const bool ok = ti < t0.size() ? fit8_int : fit8_bnd;
+            const Tile& tl = all[ti];
+            if (!ok || tl.nnz_end - tl.nnz_begin > tile_cap_nnz(out.steps)) continue;
+            for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) c8[q] = (uint8_t)(indices[q] - tbase[ti]);
+        }
+    }
+    out.c8_int = fit8_int;
+    out.c8_bnd = fit8_bnd;
+
+    // --- value dictionary (host, once): per streamed tile the distinct bit patterns of its values;
+    // a class of tiles qualifies if none of its tiles needs more than kDictMax entries.
+    std::vector<uint8_t>& vidx = out.vidx;
+    std::vector<double>& vdict = out.vdict;
+    std::vector<int32_t>& vdesc = out.vdesc;     // {first entry, count} per tile
+    bool vd_int = classic_enc && o.want_vdict && !t0.empty(), vd_bnd = classic_enc && o.want_vdict && !t1.empty();
+    if (vd_int || vd_bnd) {
+        const int cap = tile_cap_nnz(out.steps);
+        vidx.assign((size_t)nnz + 8, 0);
+        vdesc.assign(2 * (all.size() + 1), 0);
+        vdict.reserve(all.size() * 4);
+        constexpr int kHash = 256;          // open addressing, <= kDictMax live keys
+        uint64_t keys[kHash];
+        int16_t slot_of[kHash];
+        for (size_t ti = 0; ti < all.size(); ++ti) {
+            const bool interior = ti < t0.size();
+            if (!(interior ? vd_int : vd_bnd)) continue;
+            const Tile& tl = all[ti];
+            if (tl.nnz_end - tl.nnz_begin > cap || tl.nnz_end == tl.nnz_begin) continue;   // long row / empty: not streamed
+            for (int i = 0; i < kHash; ++i) slot_of[i] = -1;
+            const size_t first = vdict.size();
+            int count = 0;
+            bool ok = true;
+            for (int32_t q = tl.nnz_begin; q < tl.nnz_end; ++q) {
+                uint64_t bits;
+                memcpy(&bits, &data[q], sizeof bits);
+                uint32_t hsh = (uint32_t)((bits * 0x9E3779B97F4A7C15ull) >> 56);   // 8 bits
+                while (slot_of[hsh] >= 0 && keys[hsh] != bits) hsh = (hsh + 1) & (kHash - 1);
+                if (slot_of[hsh] < 0) {
+                    if (count == kDictMax) { ok = false; break; }
+                    keys[hsh] = bits;
+                    slot_of[hsh] = (int16_t)count++;
+                    vdict.push_back(data[q]);
+                }
+                vidx[q] = (uint8_t)slot_of[hsh];
+            }
+            if (!ok) {
+                vdict.resize(first);
+                if (interior) vd_int = false; else vd_bnd = false;
+                continue;
+            }
+            vdesc[2 * ti] = (int32_t)first;
+            vdesc[2 * ti + 1] = count;
+        }
+        if (vdict.size() >= (size_t)INT32_MAX) vd_int = vd_bnd = false;
+    }
+    out.vd_int = vd_int;
+    out.vd_bnd = vd_bnd && !t1.empty();
+
+    // --- sliced rows: the table and what a product reads ---
+    if (out.sell) {
+        out.nst_int = (int)sp.s0.size(); out.nst_bnd = (int)sp.s1.size();
+        std::vector<SellSlice>& sall = out.sslices;
+        sall = sp.s0;
+        sall.insert(sall.end(), sp.s1.begin(), sp.s1.end());
+        // what a product reads of the operator: 8 B per (padded) value, 2 B per (padded) column code, the slice descriptors, and
+        // the row pointers (slices of consecutive rows) or the slices' (row, stored length) pairs
+        out.sell_window = sp.window;
+        // ... and with WINDOW codes the granule starts (the window pages themselves are vector traffic: every entry a slice touches,
+        // read once per slice instead of once per nonzero)
+        out.sell_bytes = sp.padded_nnz * 8 + sp.col_entries * 2 + (int64_t)sall.size() * 32 + 4 * (n_rows + 1) + (int64_t)sp.rows.size() * 4 +
+                        (int64_t)sp.gran.size() * 4;
+        out.sell_sigma = sp.sigma; out.sell_planes = sp.planes; out.sell_stride = sp.stride_rows; out.sell_run = sp.run;
+    }
+    // --- window tiles: the stream images the kernels read ---
+    if (out.win) {
+        out.nwt_int = (int)wp.t0.size(); out.nwt_bnd = (int)wp.t1.size();
+        // the tiles' stream images: byte-identical ones are stored once (prcg_plan.h: share_window_streams)
+        std::vector<uint8_t>& vstore = out.wvidx;
+        std::vector<uint16_t>& rstore = out.wrel;
+        size_t cw_bytes = 0;
+        if (out.win_pat) {
+            // pattern tiles: the rows' slot masks take the place of the row pointers; no window-index / value-index images
+            rstore.swap(pmasks);
+            rstore.resize(rstore.size() + 64, 0);
+            cw_bytes = pats.size() * sizeof(PatRec);
+            vstore.assign(64, 0);
+        } else if (out.win_geom >= 2) {
+            std::vector<uint16_t>& cstore = out.wcw16;
+            share_window_streams<uint16_t>(wall, ip, wp.cw.data(), out.win_vd ? wvidx.data() : nullptr, o.want_share,
+                                           cstore, vstore, rstore);
+            cw_bytes = cstore.size() * sizeof(uint16_t);
+        } else {
+            std::vector<uint8_t> c8w(wp.cw.size());
+            std::vector<uint8_t>& cstore = out.wcw8;
+            for (size_t q = 0; q < wp.cw.size(); ++q) c8w[q] = (uint8_t)wp.cw[q];
+            share_window_streams<uint8_t>(wall, ip, c8w.data(), out.win_vd ? wvidx.data() : nullptr, o.want_share,
+                                          cstore, vstore, rstore);
+            cw_bytes = cstore.size();
+        }
+        // period of the images over the interior tiles (a stencil on a regular grid: a grid line, a grid plane): the
+        // smallest P with image(t + P) == image(t) for every t of a long stretch in the middle of the table
+        if (o.want_share && out.win_vd && !out.win_pat && wp.t0.size() > 4096) {
+            const size_t nt0 = wp.t0.size(), t0 = nt0 / 3;
+            for (size_t P = 2; P <= 4096 && t0 + 3 * P < nt0; ++P) {
+                if (wall[t0 + P].spare != wall[t0].spare || wall[t0].spare == 0) continue;
+                bool ok = true;
+                for (size_t j = 0; j < 2 * P && ok; ++j) ok = wall[t0 + j + P].spare == wall[t0 + j].spare;
+                if (ok) { out.win_period = (int)P; break; }
+            }
+            if (wall[t0 + 1].spare == wall[t0].spare && wall[t0 + 2].spare == wall[t0].spare) out.win_period = 0;   // (period 1: nothing to align)
+        }
+        out.win_stream_bytes = (int64_t)(wall.size() * sizeof(WTile) + cw_bytes + rstore.size() * sizeof(uint16_t)) +
+                              (out.win_pat ? 0 : (out.win_vd ? (int64_t)(vstore.size() + wvdict.size() * sizeof(double)) : (int64_t)nnz * 8));
+    }
+    out.n = n_rows; out.g = n_ghost; out.nnz = nnz;
+    out.nt_int = (int)t0.size(); out.nt_bnd = (int)t1.size();
+    // what one launch moves -- the operator as streamed plus 64 bytes of vectors per row: beyond the Infinity Cache
+    // (256 MB) the next launch finds none of its row results cached anyway (S3 +23 %, s4b +4 %, S2 +2 %; S1 and one
+    // eighth of S3 fit and lose 4-8 % with streaming stores)
+    out.stream_stores = o.stream_override >= 0 ? o.stream_override
+                                               : ((int64_t)64 * n_rows + out.bytes() > (int64_t)256 << 20);
+    // sliced rows with a sorting window: a slice's rows lie anywhere in the window, its 16-byte row results are PARTS of cache
+    // lines that the other slices of the window complete -- plain stores let the L2 merge them (nontemporal ones wrote 1.54 x the
+    // bytes: s4c 706 -> 675 us, profiles/r04_sweeps.md)
+    if (out.sell && out.sell_sigma > 64 && o.stream_override < 0) out.stream_stores = 0;
+    // ... and the value / code streams of an operator far larger than the Infinity Cache are read with nontemporal loads
+    // (s4b at 3.4 GB: 638 -> 610 us, s4c +4.6 %; at 1.3 GB -1 %)
+    out.sell_nt = o.sell_nt_opt >= 0 ? o.sell_nt_opt : (out.sell && out.sell_bytes >= (int64_t)2000 << 20);
+    return true;
 }
 
 }  // namespace prcg

@@ -1,14 +1,12 @@
 #pragma once
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
-namespace prcg {
+#include "prcg_geometry.h"
 
-#ifndef PRCG_TILE_DEFINED
-#define PRCG_TILE_DEFINED
-struct alignas(16) Tile { int row_begin, row_end, nnz_begin, nnz_end; };
-#endif
+namespace prcg {
 
 void plan_tiles(int64_t n, const int32_t* indptr, const uint8_t* row_class,
                 int cap_nnz, int cap_rows,
@@ -20,19 +18,6 @@ void plan_tiles(int64_t n, const int32_t* indptr, const uint8_t* row_class,
 // PAGES of 64 consecutive columns.  The kernel stages the pages of the input vector in LDS once
 // per tile and each lane walks its own row; the column of a nonzero is streamed as its index into
 // that staged window (page * 64 + offset) -- 1 byte when max_pages <= 4, else 2.
-#ifndef PRCG_WTILE_DEFINED
-#define PRCG_WTILE_DEFINED
-constexpr int kWinMaxPages = 12;
-struct alignas(16) WTile {
-    int rb, re, lo, hi;                  // rows [rb,re), nonzeros [lo,hi)
-    int geo, maxlen, vd_first, vd_count;      // geo = pages in use | (window index of row rb) << 8; longest row;
-                                         // value dictionary {first entry, count}
-    int page_col[kWinMaxPages];          // first column of each page
-    // where the kernel reads the tile's encoded streams (share_window_streams): 16-aligned start of the
-    // window-index image / of the value-index image (elements), start of the relative row pointers
-    int src_c, src_v, src_r, spare;      // spare: image id (share_window_streams), equal for tiles that read identical streams
-};
-#endif
 struct WinPlan {
     std::vector<WTile> t0, t1;           // interior tiles, tiles touching ghost columns
     std::vector<uint16_t> cw;            // per nonzero: index into its tile's staged window
@@ -79,18 +64,6 @@ StreamStats share_window_streams(std::vector<WTile>& tiles, const int32_t* indpt
 // taken as a whole or not at all.  The kernels then read NO per-nonzero stream: per tile the pattern (scalar loads, a few
 // records for the whole operator) and, for tiles with incomplete rows, 128 bytes of masks (shared between identical
 // tiles like the other stream images).
-#ifndef PRCG_PATREC_DEFINED
-#define PRCG_PATREC_DEFINED
-constexpr int kPatSlots = 16;
-constexpr int kPatValues = 4;
-struct alignas(8) PatRec {
-    int nslots;                 // U
-    unsigned vsel;              // 2 bits per slot: which of val[] the slot's value is
-    short cb[kPatSlots];        // slot u sits at window index lane + cb[u]  (may be negative for lanes without the slot)
-    double val[kPatValues];     // the caller's doubles, bit for bit
-};
-static_assert(sizeof(PatRec) == 72, "the kernels read a pattern record with scalar loads");
-#endif
 // tiles: window tiles planned with 64 rows per tile (geo, page_col set), cw: their window indices.  On success every
 // tile's src_c = pattern id, src_r = start of its 64 masks in `masks`, spare = 1 if all 64 rows have every slot (no
 // mask needed) else 0, maxlen = number of slots.  Returns false if some tile does not qualify (tiles unchanged then).
@@ -189,6 +162,119 @@ struct SellPlan {
 };
 bool plan_sell(int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, const uint8_t* row_class,
                const SellOptions& opt, SellPlan& out);
+
+// ---- options ------------------------------------------------------------------------------------------------
+// Every PRCG_* switch as a value: prcg_create reads the environment into the handle's copy, prcg_set_option sets single
+// ones until the operator is set, the planner reads them (plan_operator).  kOptions is the ONE list of keys and setters.
+struct Options {
+    bool want_fused = true;              // PRCG_FUSED=0: no one-launch / reduction-free schedules
+    bool want_small = true;              // PRCG_SMALL=0: no one-workgroup solver
+    bool want_c16 = true;                // PRCG_COL16=0: CSR-adaptive tiles keep 32-bit columns
+    bool want_c8 = true;                 // PRCG_COL8=0: never narrower than 16 bit
+    bool want_vdict = true;              // PRCG_VALDICT=0: plain values
+    bool want_gather = true;             // PRCG_GATHER=0: no merged exchange (must agree on all ranks)
+    int64_t gather_max_bytes = 8192;     // PRCG_GATHER_MAX_BYTES: largest per-rank slot that still rides along
+    TileKnobs kn;                        // PRCG_GRID_PER_CU
+    int steps_override = 0;              // PRCG_TILE_STEPS
+    // window tiles (row-per-lane kernels, prcg_win.hip): all tiles of the operator or none
+    bool want_win = true;                // PRCG_WIN=0 turns them off
+    int win_per_cu = 0;                  // PRCG_WIN_GRID_PER_CU
+    int win_max_mean = 24;               // PRCG_WIN_MAX_MEAN: longest mean row the window form is tried for
+    int win_rows_override = 0;           // PRCG_WIN_ROWS = 64 | 128: rows per window tile (default: by mean row length)
+    bool want_pat = true;                // PRCG_WIN_PAT=0: constant-coefficient stencils keep the stream geometries
+    int want_sweep = 1;                  // PRCG_WIN_SWEEP=0: pattern tiles in row order (no page carried from tile to tile); 2: sweep tables
+                                         // for operators of any size (default: 5e6 rows and more -- below, the row order with big workgroups wins)
+    int sweep_max_waves = 6144;          // PRCG_SWEEP_WAVES: most waves a sweep table may ask for
+    bool want_big = true;                // PRCG_WIN_BIG=0: short launches keep the small workgroups too
+    bool want_share = true;              // PRCG_WIN_SHARE=0: every window tile keeps its own stream images
+    // sliced rows (lane-per-row kernels for medium-length rows, prcg_sell.hip): all rows of the operator or none
+    bool want_sell = true;               // PRCG_SELL=0 turns them off
+    int sell_per_cu = 0;                 // PRCG_SELL_GRID_PER_CU
+    int sell_window_opt = 64;            // PRCG_SELL_WINDOW=0: delta codes, gathers from memory; 1..64: granules a slice may use
+    double sell_overhead_opt = 0.0;      // PRCG_SELL_MAX_OVERHEAD_PCT: most padded nonzeros per nonzero, in percent (experiments)
+    int sell_sigma_opt = 0;              // PRCG_SELL_SIGMA: sorting window of the sliced layout in rows (0: chosen by the planner)
+    int sell_planes_opt = 0;             // PRCG_SELL_PLANES: grid planes interleaved in the slice table (<= 1: row order, the default:
+                                         // interleaving 8 planes cost s4b at 80^3 nodes 9 % -- profiles/r04_sweeps.md)
+    int sell_nt_opt = -1;                // PRCG_SELL_NT=0|1: nontemporal loads of the value / code streams (default: by operator size)
+    bool sell_runs_opt = true;           // PRCG_SELL_RUNS=0: a column code per nonzero even where the rows are runs of three
+    // sessions
+    int place_k = 8;                     // PRCG_PLACE=k: the pipelined session's vectors are placed k times and the fastest placement
+                                         // is kept (place_session_vectors); 0 / 1: off
+    int want_pr_pack = -1;               // PRCG_PR_PACK=0|1; default: pattern-tile operators only (S2: +7.6 %; S3 +-0; S2 with plain values -12 %)
+    bool want_cg_one = true;             // PRCG_CG_ONE=0: Chronopoulos-Gear / Ghysels-Vanroose keep the two-launch schedule
+    int stream_override = -1;            // PRCG_STREAM_STORES=0|1 (default: by operator size, plan_operator)
+    bool want_xp_defer = true;           // PRCG_XP_DEFER=0: every one-launch pipelined iteration stores (x,p) itself
+    int want_fused_comm_rccl = 0;        // PRCG_FUSED_COMM=1: one launch per iteration with the RCCL all-gather chain on the communication
+                                         // stream (in-kernel wait for kernels of another stream: validated with one rank only -- opt-in)
+    bool want_peer = true;               // PRCG_PEER=0: never use the peer exchange even when connected
+    bool ext_signal = true;              // PRCG_EXT_SIGNAL=0: separate hipEventRecord instead of the launch's own completion signal
+    int defer_per_cu = 0;                // PRCG_DEFER_GRID_PER_CU: workgroups per CU of the deferred launch (several ranks sharing one
+                                         // GPU in the tests must all be resident at once: 1)
+    bool debug_short_sources = false;    // PRCG_DEBUG_SHORT_SOURCES=1 (TESTS ONLY): Hestenes-Stiefel sessions allocate r without
+                                         // the spare entries a window source needs -- the launch must be refused, not fault
+};
+struct OptionDef { const char* key; void (*set)(Options&, long); };
+extern const OptionDef kOptions[];
+extern const int kNumOptions;
+// value: a decimal integer as in the environment.  Returns false for an unknown key.
+bool apply_option(Options& o, const char* key, const char* value);
+
+// ---- the operator decision -----------------------------------------------------------------------------------
+// Which kernel family an operator gets and with which encodings: everything prcg_set_csr decides between validating its
+// arguments and uploading.  Host only.  OperatorShape is what stays with the handle, OperatorPlan adds the arrays to upload.
+int pick_tile_steps(int override_, int64_t n = 0, int64_t nnz = 0);
+struct OperatorShape {
+    int64_t n = 0, g = 0, nnz = 0;
+    int max_row_len = 0;
+    // CSR-adaptive tiles (always planned: the one-workgroup solver and the diagnostics read the plain CSR arrays)
+    int steps = kDefaultTileSteps;           // tile size the table was planned for
+    int nt_int = 0, nt_bnd = 0;              // interior tiles first, then boundary tiles
+    bool c16_int = false, c16_bnd = false;   // 16-bit tile-relative columns usable for all interior / all boundary tiles
+    bool c8_int = false, c8_bnd = false;     // ... 8-bit
+    bool vd_int = false, vd_bnd = false;     // value dictionary
+    // window tiles: all tiles of the operator or none
+    bool win = false;
+    int win_geom = 0, win_rows = 0;
+    bool win_vd = false;
+    bool win_pat = false;                    // pattern tiles (geometry 5): no index streams, the rows' slot masks in wrel, records in wpat
+    int sweep_waves = 0, sweep_tiles = 0;
+    int nwt_int = 0, nwt_bnd = 0;
+    int win_period = 0;                      // tiles t and t + win_period read the same stream images (0: no such period found)
+    int64_t win_stream_bytes = 0;            // bytes of the encoded operator a product must read at least once (window form)
+    // sliced rows: all rows of the operator or none
+    bool sell = false;
+    int nst_int = 0, nst_bnd = 0;            // interior slices first, then slices touching ghost columns
+    int64_t sell_bytes = 0;                  // bytes of the re-laid operator a product reads
+    int sell_window = 0;                     // > 0: WINDOW codes; the most granules of a slice
+    int sell_sigma = 0, sell_planes = 0, sell_run = 1;     // what plan_sell chose
+    int64_t sell_stride = 0;
+    int sell_nt = 0;                         // the value / code streams are read with nontemporal loads
+    int stream_stores = 0;                   // the one-launch iterations write their row results with streaming stores
+    // bytes of the operator as encoded that one product reads (prcg_operator_bytes)
+    int64_t bytes() const;
+};
+struct OperatorPlan : OperatorShape {
+    std::vector<Tile> tiles;                 // interior, then boundary
+    std::vector<int32_t> tbase;              // per tile (+1): smallest column
+    std::vector<uint16_t> c16;               // per nonzero (+8), empty: not built
+    std::vector<uint8_t> c8;
+    std::vector<uint8_t> vidx;               // per nonzero (+8); with vdict / vdesc only if vd_int || vd_bnd
+    std::vector<double> vdict;
+    std::vector<int32_t> vdesc;              // {first entry, count} per tile
+    std::vector<WTile> wtiles;               // window tiles, interior first
+    std::vector<PatRec> pats;                // pattern tiles: the records
+    std::vector<uint8_t> wcw8;               // window-index images as stored: 1 byte per index (geometry 0, 1) ...
+    std::vector<uint16_t> wcw16;             // ... or 2
+    std::vector<uint16_t> wrel;              // relative row pointers; pattern tiles: slot masks
+    std::vector<uint8_t> wvidx;              // value-index images (win_vd)
+    std::vector<double> wvdict;
+    SellPlan sp;                             // sliced rows: val, col, rows, gran
+    std::vector<SellSlice> sslices;          // interior, then boundary
+};
+// indptr32: n_rows + 1 validated row pointers (0 .. nnz, monotone).  Returns false and a message in `err` for a column
+// index outside [0, n_rows + n_ghost).
+bool plan_operator(const Options& o, int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
+                   const double* data, OperatorPlan& out, std::string& err);
 
 // Merged exchange (small halos ride on the one all-gather per iteration):
 // every rank contributes a slot of `slot` doubles = 8 (partial sums) + 2 x its packed send rows;

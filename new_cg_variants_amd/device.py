@@ -396,3 +396,32 @@ def plan_tiles(indptr, row_class=None, cap_nnz=None, cap_rows=None):
     if got < 0:
         raise RuntimeError('prcg_plan_tiles failed')
     return out[:got].copy(), int(n0.value)
+
+
+PLAN_OPERATOR_FIELDS = ('family', 'win_geom', 'rows_per_tile', 'pattern', 'sweep_waves', 'value_dict', 'value_dict_boundary',
+                        'col_bytes', 'col_bytes_boundary', 'tile_steps', 'tiles_interior', 'tiles_boundary', 'image_period',
+                        'operator_bytes', 'hash_index', 'hash_value_index', 'hash_dictionary', 'hash_tiles')
+
+
+def plan_operator(A, knobs=None):
+    """Host-only view of what prcg_set_csr decides for the row block ``A`` under the PRCG_* ``knobs`` (no handle, no GPU):
+    a dict of PLAN_OPERATOR_FIELDS -- family 0 = CSR-adaptive tiles, 1 = window tiles, 2 = sliced rows; the four hashes
+    are 64-bit FNV-1a sums (as unsigned integers) of the arrays an upload would copy (include/prcg_test.h)."""
+    lib = L.lib()
+    A = A.tocsr()
+    n_rows, n_cols = A.shape
+    indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+    indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+    data = np.ascontiguousarray(A.data, dtype=np.float64)
+    items = [(str(k).encode(), str(v).encode()) for k, v in (knobs or {}).items()]
+    keys = (C.c_char_p * max(len(items), 1))(*[k for k, _ in items])
+    values = (C.c_char_p * max(len(items), 1))(*[v for _, v in items])
+    out = np.zeros(len(PLAN_OPERATOR_FIELDS), dtype=np.int64)
+    got = lib.prcg_plan_operator(int(n_rows), int(n_cols - n_rows), int(A.nnz), L.ptr(indptr), L.ptr(indices), L.ptr(data),
+                                 keys, values, len(items), L.ptr(out), out.size)
+    if got != out.size:
+        raise RuntimeError(f'prcg_plan_operator failed ({got})')
+    res = {f: int(v) for f, v in zip(PLAN_OPERATOR_FIELDS, out)}
+    for f in PLAN_OPERATOR_FIELDS[-4:]:
+        res[f] &= (1 << 64) - 1
+    return res
