@@ -273,14 +273,18 @@ int prcg_get_coefficients(prcg_t* h, int k, double* out);
 /* histories: for each bit set in hist_mask (ascending bit order) max_iter doubles;
  * entries beyond the current iteration are 0, as numpy.zeros(max_iter) leaves them. */
 int prcg_get_history(prcg_t* h, double* hist);
-/* ---- Hestenes-Stiefel with TWO right-hand sides in one session --------------------------------
- * Replaces TWO calls of the reference's hs_cg (numerical_experiments/cg_variants/hs_cg.py:9) or hs_pcg (:70) on one
- * matrix: load cases, time steps with a frozen operator, columns of a block solve.  The two recurrences stay what they are
+/* ---- Hestenes-Stiefel or predict-and-recompute with TWO right-hand sides in one session --------
+ * Replaces TWO calls of the reference's hs_cg (numerical_experiments/cg_variants/hs_cg.py:9) or hs_pcg (:70), of pr_pcg
+ * (pr_cg.py:166) or of m_pcg (pr_cg.py:172) on one matrix: load cases, time steps with a frozen operator, columns of a
+ * block solve.  The two recurrences stay what they are
  * -- each column has its own a_k, b_k, inner products and history, nothing of one column enters the other (a breakdown of
  * one leaves the other's bits untouched) -- but every iteration streams the operator ONCE: s = A p of both columns is one
  * two-vector product (what prcg_spmm2 runs), on assembled FEM matrices most of an iteration's memory traffic.
- *   variant: PRCG_HS only.  nrhs: 2 only.  b, x0: nrhs pointers to n_rows host doubles each.  inv_diag != NULL: hs_pcg with
- *   Jacobi, the same diagonal for both columns.  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.
+ *   variant: PRCG_HS, PRCG_PR or PRCG_M.  nrhs: 2 only.  b, x0: nrhs pointers to n_rows host doubles each.  inv_diag != NULL:
+ *   hs_pcg / pr_pcg / m_pcg with Jacobi, the same diagonal for both columns; inv_diag == NULL: hs_cg, or for PRCG_PR / PRCG_M
+ *   the identity-preconditioned recurrences (this library's pr_cg / m_cg).  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.
+ *   A Hestenes-Stiefel iteration is six launches around its two dependent inner products; a predict-and-recompute
+ *   iteration has ONE reduction point: update, two-vector product, the inner products that need s, one reduction per column.
  * Single GPU, whole operators: refused (PRCG_EINVAL, text names the reason) with a communicator on the handle, n_ghost > 0,
  * a host-callback or block-Jacobi preconditioner or a replace hook set, another variant, nrhs, or history bit.
  * prcg_iterate / prcg_sync / prcg_iteration / prcg_set_profiling / prcg_get_timings serve the session as they are.  State is
@@ -291,11 +295,13 @@ int prcg_get_history(prcg_t* h, double* hist);
  * exchanging the two right-hand sides exchanges the two results bit for bit. */
 int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
                            int max_iter, const double* inv_diag, uint32_t hist_mask);
-/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi); out: n_rows host doubles */
+/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi; PRCG_PR / PRCG_M sessions with Jacobi also _ST); out: n_rows host doubles */
 int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out);
-/* PRCG_NUM_SCALARS doubles: mu, nu, rr of column j at iteration k in their slots, every other slot 0 */
+/* PRCG_NUM_SCALARS doubles: mu, nu, rr of column j at iteration k in their slots (PRCG_PR / PRCG_M sessions: mu, delta,
+ * gamma, nu, rr), every other slot 0 */
 int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out);
-/* out[0] = alpha, out[1] = beta used BY iteration k (k >= 1) of column j, out[2] = 0 */
+/* out[0] = alpha, out[1] = beta used BY iteration k (k >= 1) of column j; out[2] = the predicted nu of iteration k in a
+ * PRCG_PR / PRCG_M session, 0 in a Hestenes-Stiefel session (which predicts none) */
 int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out);
 /* max_iter doubles: column j's updated_residual_2_norm history (nothing is written when hist_mask was 0) */
 int prcg_get_history_rhs(prcg_t* h, int j, double* hist);

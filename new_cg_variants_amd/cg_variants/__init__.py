@@ -324,9 +324,9 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
     return output
 
 
-def _run_multi(name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
-    """Two right-hand sides of one matrix in ONE Hestenes-Stiefel session (prcg.h: prcg_solve_begin_multi): what two calls
-    of hs_cg / hs_pcg compute, with the operator streamed once per iteration for both.  Every argument is checked before
+def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
+    """Two right-hand sides of one matrix in ONE session of `variant` (L.HS, L.PR, L.M; prcg.h: prcg_solve_begin_multi): what
+    two calls of hs_cg / hs_pcg (pr_cg / pr_pcg, m_cg / m_pcg) compute, with the operator streamed once per iteration for both.  Every argument is checked before
     the device is touched; what the session does not serve raises ValueError -- nothing falls back to two sessions."""
     if A.format != 'csr':
         A = A.tocsr()
@@ -358,7 +358,7 @@ def _run_multi(name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
     op = _operator(A, int(kwargs.get('device', 0)))
     op.set_replace_hook(None)
     op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
-    op.begin_multi(L.HS, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
     outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(2)]
 
     def call_host(k):
@@ -386,12 +386,37 @@ def hs_cg_multi(A, B, X0, max_iter, callbacks=[], **kwargs):
     shaped like hs_cg's.  One session, one pass over the operator per iteration."""
     if kwargs.pop('preconditioner', None) is not None:
         raise ValueError('hs_cg_multi takes no preconditioner: use hs_pcg_multi')
-    return _run_multi('hs_cg_multi', A, B, X0, max_iter, None, callbacks, kwargs)
+    return _run_multi(L.HS, 'hs_cg_multi', A, B, X0, max_iter, None, callbacks, kwargs)
 
 
 def hs_pcg_multi(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
     """hs_pcg (hs_cg.py:70) for TWO right-hand sides of one matrix, with Jacobi(A) or a callable that probes as a diagonal."""
-    return _run_multi('hs_pcg_multi', A, B, X0, max_iter, preconditioner, callbacks, kwargs)
+    return _run_multi(L.HS, 'hs_pcg_multi', A, B, X0, max_iter, preconditioner, callbacks, kwargs)
+
+
+def _make_multi(variant, name, preconditioned):
+    single = name[:-len('_multi')]
+    if preconditioned:
+        def f(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
+            return _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs)
+        f.__doc__ = (f'{single} (pr_cg.py:{166 if variant == L.PR else 172}) for TWO right-hand sides of one matrix, with Jacobi(A) or a '
+                     'callable that probes as a diagonal: B, X0 of shape (2, n); returns a list of two trial dicts.  One session, one '
+                     'pass over the operator and one reduction point per iteration.')
+    else:
+        def f(A, B, X0, max_iter, callbacks=[], **kwargs):
+            if kwargs.pop('preconditioner', None) is not None:
+                raise ValueError(f'{name} takes no preconditioner: use {single[:-2]}pcg_multi')
+            return _run_multi(variant, name, A, B, X0, max_iter, None, callbacks, kwargs)
+        f.__doc__ = (f'{single} (the identity-preconditioned recurrence of {single[:-2]}pcg) for TWO right-hand sides of one matrix: B, X0 '
+                     'of shape (2, n); returns a list of two trial dicts.  One session, one pass over the operator per iteration.')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+pr_cg_multi = _make_multi(L.PR, 'pr_cg_multi', False)
+pr_pcg_multi = _make_multi(L.PR, 'pr_pcg_multi', True)       # pr_cg.py:166
+m_cg_multi = _make_multi(L.M, 'm_cg_multi', False)
+m_pcg_multi = _make_multi(L.M, 'm_pcg_multi', True)          # pr_cg.py:172
 
 
 def _make(variant, name, preconditioned):
@@ -436,4 +461,4 @@ pipe_pr_m_pcg = _make(L.PIPE_PR_M, 'pipe_pr_m_pcg', True) # pipe_pr_cg.py:213
 __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr_pcg', 'm_cg', 'm_pcg',
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
-           'hs_cg_multi', 'hs_pcg_multi', 'clear_operator_cache']
+           'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi', 'clear_operator_cache']

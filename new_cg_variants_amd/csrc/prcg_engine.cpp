@@ -43,6 +43,7 @@ std::string g_last_error;   // errors with no handle to hang them on
 constexpr int kNS = PRCG_NUM_SCALARS;
 static_assert(kPartialStride == PRCG_NUM_SCALARS, "the small-system kernel indexes the scalar history with kPartialStride");
 constexpr int kCoefStride = 4;
+static_assert(kCoefStride == kPr2CoefStride, "k_pr2_update steps from column 0's coefficient row to column 1's");
 constexpr int kMaxProfSamples = 512;
 
 struct DevBuf {
@@ -155,7 +156,8 @@ struct Session {
     int k = 0;
     uint32_t hist_mask = 0;
     bool have_xtrue = false;
-    bool rhs2 = false;           // session type "Hestenes-Stiefel, two right-hand sides" (prcg_solve_begin_multi)
+    bool rhs2 = false;           // session type "two right-hand sides" (prcg_solve_begin_multi): Hestenes-Stiefel, or with
+                                 // variant PRCG_PR / PRCG_M predict-and-recompute (two scalar / coefficient rows per iteration)
     // ---- schedule ----
     bool fused = false;          // pipelined: the one-launch-per-iteration kernel
     bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
@@ -240,6 +242,7 @@ struct prcg_handle : Operator, Session {
     DevBuf w, u, tvec;           // cg_cg / gv: w (ghost room), u, t = A w~
     DevBuf w2, u2, t2;           // ... their second copies (one- / two-launch schedules on window operators)
     DevBuf mx, mr, mp, ms, mrt;  // two right-hand sides: the interleaved n x 2 arrays X, R, P, S, RT (Hs2Args, prcg_kernels.h); dots / coef hold both columns per row
+    DevBuf mst;                  // ... predict-and-recompute with Jacobi: ST (Pr2Args); dots / coef hold one row per column and iteration
     DevBuf pub, pub_err;         // publication record of the reduced inner products / timeout flag
     DevBuf q, q2;                // packed predict-and-recompute state (Session::pr_packed)
     DevBuf dots, coef;
@@ -931,6 +934,44 @@ int iterate_hs2(prcg_t* h, int k) {
     launch_reduce_final(h->sc, h->partA.d(), g1, dots_at(h, k), kHs2Nu, kHs2Nu, 4);     // nu_0, rr_0, nu_1, rr_1
     LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));
     return hs2_product_and_mu(h, k, a);
+}
+
+// Two right-hand sides in one predict-and-recompute session (pr_cg.py:146-158 for each column; PRCG_M: Meurant's prediction):
+// update, ONE two-vector product of [p_0 p_1], the three inner products that need s, one reduction launch per column.
+bool pr2(const prcg_t* h) { return h->rhs2 && is_pr(h->variant); }
+Pr2Args pr2_args(prcg_t* h, int k) {
+    Pr2Args a{};
+    a.n = h->n;
+    a.x = h->mx.d(); a.r = h->mr.d(); a.p = h->mp.d(); a.s = h->ms.d();
+    a.rt = h->prec ? h->mrt.d() : nullptr; a.st = h->prec ? h->mst.d() : nullptr;
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, 2 * (k - 1)) : nullptr;       // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
+    a.coef_out = coef_at(h, 2 * k);
+    a.part0 = h->partA.d(); a.part1 = h->partB.d();
+    a.meurant = meurant(h->variant);
+    return a;
+}
+// s = A p for both columns, (s~ = d s), mu, dl, gm; then the five sums of each column: rows 2 k and 2 k + 1
+int pr2_product_and_sums(prcg_t* h, int k, const Pr2Args& a, int g_upd) {
+    bool on = false;
+    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+    LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, h->mp.d(), h->ms.d(), 3));
+    prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+    const int g = launch_pr2_dots(h->sc, a);
+    LAUNCHCHK(h, g);
+    CHECK(h, g == g_upd, "two-RHS session: the update and the dots launch disagree on the grid (%d, %d)", g_upd, g);
+    launch_reduce_final(h->sc, h->partA.d(), g, dots_at(h, 2 * k), 0, 0, 5);
+    launch_reduce_final(h->sc, h->partB.d(), g, dots_at(h, 2 * k + 1), 0, 0, 5);
+    return PRCG_OK;
+}
+int iterate_pr2(prcg_t* h, int k) {
+    const Pr2Args a = pr2_args(h, k);
+    bool on = false;
+    prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
+    const int g1 = launch_pr2_update(h->sc, a);
+    LAUNCHCHK(h, g1);
+    prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    return pr2_product_and_sums(h, k, a, g1);
 }
 
 // hs_cg.py:54-62 (hs_pcg :116-125) on one GPU without reduction launches.  The two inner products still separate
@@ -2055,7 +2096,7 @@ namespace {
 // has computed the initial state.
 struct Lead { DevBuf* buf; size_t bytes; };
 int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
-                 std::initializer_list<Lead> lead) {
+                 std::initializer_list<Lead> lead, int rows_per_iteration = 1) {
     CHECK(h, h->have_csr, "%s: call prcg_set_csr first", who);
     CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
     HIPCHK(h, hipSetDevice(h->dev));
@@ -2076,8 +2117,9 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries (dinv is a window source of
     // the Chronopoulos-Gear product launch)
     HIPCHK(h, h->dinv.ensure((size_t)(h->n + h->g + kGatherPad) * D, h->sc));
-    HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * kNS * D, h->sc));
-    HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * kCoefStride * D, h->sc));
+    // (rows_per_iteration = 2: the predict-and-recompute two-RHS session keeps one scalar and one coefficient row per column)
+    HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * rows_per_iteration * kNS * D, h->sc));
+    HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * rows_per_iteration * kCoefStride * D, h->sc));
     if (inv_diag) return h2d(h, h->dinv.d(), inv_diag, h->n);
     return PRCG_OK;
 }
@@ -2363,7 +2405,7 @@ int prcg_iterate(prcg_t* h, int iters) {
                                    "the session's results are invalid -- PRCG_PEER=0 / PRCG_FUSED_COMM=0 select the two-kernel schedule");
     if (h->rhs2) {
         for (int i = 0; i < iters; ++i) {
-            const int rc = iterate_hs2(h, h->k + 1);
+            const int rc = pr2(h) ? iterate_pr2(h, h->k + 1) : iterate_hs2(h, h->k + 1);
             if (rc) return rc;
             ++h->k;
         }
@@ -2591,12 +2633,13 @@ int prcg_get_history(prcg_t* h, double* hist) {
     return PRCG_OK;
 }
 
-// ---- Hestenes-Stiefel, two right-hand sides in one session ----
+// ---- two right-hand sides in one session: Hestenes-Stiefel, predict-and-recompute (PRCG_PR, PRCG_M) ----
 int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
                            const double* inv_diag, uint32_t hist_mask) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, nrhs == 2, "prcg_solve_begin_multi: nrhs = %d: the multi-RHS session serves exactly 2 right-hand sides", nrhs);
-    CHECK(h, variant == PRCG_HS, "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg) only", variant);
+    CHECK(h, variant == PRCG_HS || is_pr(variant), "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg), "
+                                                   "PRCG_PR (pr_cg / pr_pcg) and PRCG_M (m_cg / m_pcg) only", variant);
     CHECK(h, !h->multi(), "prcg_solve_begin_multi: a communicator is set on the handle: the two-RHS session runs on one GPU");
     CHECK(h, h->g == 0, "prcg_solve_begin_multi: n_ghost = %lld > 0: the two-RHS session serves whole operators only", (long long)h->g);
     CHECK(h, h->cb == nullptr, "prcg_solve_begin_multi: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
@@ -2610,9 +2653,15 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
     // X and P feed the two-vector product: like every product source they carry the spare entries behind row n
-    int rc = open_session(h, "prcg_solve_begin_multi", PRCG_HS, max_iter, hist_mask, inv_diag, false,
+    int rc;
+    if (variant == PRCG_HS)
+        rc = open_session(h, "prcg_solve_begin_multi", PRCG_HS, max_iter, hist_mask, inv_diag, false,
                           {{&h->mx, (size_t)2 * ne * D}, {&h->mp, (size_t)2 * ne * D}, {&h->mr, (size_t)2 * n * D}, {&h->ms, (size_t)2 * n * D},
                            {&h->mrt, inv_diag ? (size_t)2 * n * D : 16}});
+    else
+        rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
+                          {{&h->mx, (size_t)2 * ne * D}, {&h->mp, (size_t)2 * ne * D}, {&h->mr, (size_t)2 * n * D}, {&h->ms, (size_t)2 * n * D},
+                           {&h->mrt, inv_diag ? (size_t)2 * n * D : 16}, {&h->mst, inv_diag ? (size_t)2 * n * D : 16}}, 2);
     if (rc) return rc;
     h->rhs2 = true;
     std::vector<double> pairs;
@@ -2625,6 +2674,16 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     // r = b - A x0 for both columns (hs_cg.py:23): one two-vector product of [x0_0 x0_1], parked in S
     LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->mx.d(), h->ms.d(), 3));
     launch_sub(sc, h->mr.d(), 1, h->mr.d(), 1, h->ms.d(), 1, 2 * n);
+    if (pr2(h)) {
+        const Pr2Args pa = pr2_args(h, 0);
+        const int g0 = launch_pr2_init_dots(sc, pa);                         // (r~ = d r); nu = r~.r, r.r   pr_cg.py:108-109
+        LAUNCHCHK(h, g0);
+        launch_copy(sc, h->mp.d(), 1, h->prec ? h->mrt.d() : h->mr.d(), 1, 2 * n);   // p = r~ (r)   :110
+        if ((rc = pr2_product_and_sums(h, 0, pa, g0))) return rc;            // s = A p, (s~ = d s), mu, dl, gm   :111-116
+        HIPCHK(h, hipStreamSynchronize(sc));
+        h->in_session = true;
+        return PRCG_OK;
+    }
     Hs2Args a = hs2_args(h, 0);
     const int g1 = launch_hs2_init_dots(sc, a);                              // (r~ = d r); nu = r.r~, r.r   :25 / :86-88
     LAUNCHCHK(h, g1);
@@ -2647,8 +2706,10 @@ int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out) {
     NEED_RHS2(h, "prcg_get_vector_rhs", j);
     CHECK(h, out, "prcg_get_vector_rhs: null buffer");
     const DevBuf* src = which == PRCG_VEC_X ? &h->mx : which == PRCG_VEC_R ? &h->mr : which == PRCG_VEC_P ? &h->mp :
-                        which == PRCG_VEC_S ? &h->ms : (which == PRCG_VEC_RT && h->prec) ? &h->mrt : nullptr;
-    CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the two-RHS session (x, r, p, s; rt with Jacobi)", which);
+                        which == PRCG_VEC_S ? &h->ms : (which == PRCG_VEC_RT && h->prec) ? &h->mrt :
+                        (which == PRCG_VEC_ST && h->prec && pr2(h)) ? &h->mst : nullptr;
+    CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the two-RHS session (x, r, p, s; rt with Jacobi; st with Jacobi "
+                  "in a PRCG_PR / PRCG_M session)", which);
     int rc = prcg_sync(h);
     if (rc) return rc;
     launch_copy(h->sc, h->t1.d(), 1, src->d() + j, 2, h->n);
@@ -2662,8 +2723,12 @@ int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out) {
     int rc = prcg_sync(h);
     if (rc) return rc;
     double row[kNS];
-    if ((rc = d2h(h, row, dots_at(h, k), kNS))) return rc;
+    if ((rc = d2h(h, row, dots_at(h, pr2(h) ? 2 * k + j : k), kNS))) return rc;
     for (int q = 0; q < kNS; ++q) out[q] = 0.0;
+    if (pr2(h)) {
+        for (int q = 0; q <= PRCG_S_RR; ++q) out[q] = row[q];         // mu, dl, gm, nu, rr: the column's own row
+        return PRCG_OK;
+    }
     out[PRCG_S_MU] = row[kHs2Mu + j]; out[PRCG_S_NU] = row[kHs2Nu + 2 * j]; out[PRCG_S_RR] = row[kHs2Rr + 2 * j];
     return PRCG_OK;
 }
@@ -2675,7 +2740,8 @@ int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out) {
     int rc = prcg_sync(h);
     if (rc) return rc;
     double row[kCoefStride];
-    if ((rc = d2h(h, row, coef_at(h, k), kCoefStride))) return rc;
+    if ((rc = d2h(h, row, coef_at(h, pr2(h) ? 2 * k + j : k), kCoefStride))) return rc;
+    if (pr2(h)) { out[0] = row[0]; out[1] = row[1]; out[2] = row[2]; return PRCG_OK; }     // a, b, the predicted nu
     out[0] = row[2 * j]; out[1] = row[2 * j + 1]; out[2] = 0.0;      // Hestenes-Stiefel predicts no nu
     return PRCG_OK;
 }
@@ -2688,9 +2754,13 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist) {
     if (rc) return rc;
     if (!(h->hist_mask & PRCG_HIST_UPDATED_RESIDUAL_2_NORM)) return PRCG_OK;
     const int m = h->max_iter;
-    std::vector<double> all((size_t)(m + 1) * kNS);
-    if ((rc = d2h(h, all.data(), h->dots.d(), (int64_t)(m + 1) * kNS))) return rc;
-    for (int k = 0; k < m; ++k) hist[k] = k <= h->k ? std::sqrt(all[(size_t)k * kNS + kHs2Rr + 2 * j]) : 0.0;
+    const int rows = pr2(h) ? 2 : 1;
+    std::vector<double> all((size_t)(m + 1) * rows * kNS);
+    if ((rc = d2h(h, all.data(), h->dots.d(), (int64_t)(m + 1) * rows * kNS))) return rc;
+    for (int k = 0; k < m; ++k) {
+        const double rr = pr2(h) ? all[(size_t)(2 * k + j) * kNS + PRCG_S_RR] : all[(size_t)k * kNS + kHs2Rr + 2 * j];
+        hist[k] = k <= h->k ? std::sqrt(rr) : 0.0;
+    }
     return PRCG_OK;
 }
 

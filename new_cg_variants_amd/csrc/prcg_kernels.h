@@ -358,6 +358,23 @@ int launch_hs2_init_dots(hipStream_t st, const Hs2Args& a);   // ... of the init
 int launch_hs2_update_p(hipStream_t st, const Hs2Args& a);    // p = z + b_c p
 int launch_hs2_dot_ps(hipStream_t st, const Hs2Args& a);      // partials mu_c = p.s (slots 0, 1)
 
+// ---- predict-and-recompute (pr_pcg / m_pcg), TWO right-hand sides in one session (prcg_rhs2.hip) ----
+// The interleaved n x 2 arrays of Hs2Args plus st (s~, with Jacobi).  Scalars and coefficients: TWO rows per iteration, row
+// 2 k + c = column c's iteration k in the single-session order [mu dl gm nu rr - - -] / [a b nu_pred -], so that predict()
+// reads a column's row as it reads a single session's.  dots_prev, coef_out: column 0's row (column 1's follows it).
+// part0, part1: the block partials of column 0 / 1 in the same slots -- one launch_reduce_final per column sums all five.
+constexpr int kPr2Mu = 0, kPr2Nu = 3;                  // slots: mu, dl, gm from the dots kernel; nu, rr from the update
+constexpr int kPr2CoefStride = 4;                      // doubles per coefficient row (the engine's kCoefStride)
+struct Pr2Args {
+    int64_t n;
+    double* x; double* r; double* rt; double* p; const double* s; double* st; const double* d;
+    const double* dots_prev; double* coef_out; double* part0; double* part1;
+    int meurant;
+};
+int launch_pr2_update(hipStream_t st, const Pr2Args& a);      // x, r, (rt), p; partials nu_c (slot 3), rr_c (4) of part[c]
+int launch_pr2_init_dots(hipStream_t st, const Pr2Args& a);   // ... of the initial state: no update, (rt = d r)
+int launch_pr2_dots(hipStream_t st, const Pr2Args& a);        // (st = d s); partials mu_c, dl_c, gm_c (slots 0..2) of part[c]
+
 struct PrArgs {   // non-pipelined predict-and-recompute (pr_pcg / m_pcg)
     int64_t n;
     double* x; double* r; double* rt; double* p; const double* s; const double* st_;

@@ -1,5 +1,6 @@
 // gfx950 (MI355X / CDNA4): the vector kernels of the session type "Hestenes-Stiefel, two right-hand sides"
-// (prcg_solve_begin_multi; replaces two calls of the reference's hs_cg.py:9 / :70 on one matrix).
+// (prcg_solve_begin_multi; replaces two calls of the reference's hs_cg.py:9 / :70 on one matrix), and below them those of
+// "predict-and-recompute, two right-hand sides" (pr_cg.py:166 / :172; k_pr2_*).
 //
 // One iteration of the session is  update_xr -> reduce -> update_p -> [p_0 p_1] -> A [p_0 p_1] (the two-vector product
 // every operator family already has) -> dot_ps -> reduce: the operator is streamed ONCE for both systems.
@@ -142,6 +143,146 @@ __global__ __launch_bounds__(kBlock) void k_hs2_dot_ps(Hs2Args a, int trips) {
     block_reduce_store<2>(acc, a.partials, kHs2Mu);
 }
 
+// ---- predict-and-recompute (pr_cg.py:166 pr_pcg, :172 m_pcg; identity-preconditioned: pr_cg / m_cg), two right-hand sides ----
+// One iteration is  update -> [p_0 p_1] -> A [p_0 p_1] -> dots -> two reductions (one per column): ONE reduction point.
+// Column c's five sums of iteration k are row 2 k + c of the scalar array in the single-session order [mu dl gm nu rr],
+// so predict() serves each column as it serves a single session; the block partials of column c go to part[c] in the
+// same slots (the update fills 3..4, the dots kernel 0..2) and one launch_reduce_final per column sums all five.
+
+// block_reduce_store for two columns: acc = (column 0's NQ sums, column 1's NQ sums) -> part[c][block][slot0 + q]
+template <int NQ>
+__device__ __forceinline__ void block_reduce_store2(double (&acc)[2 * NQ], double* part0, double* part1, int slot0) {
+    __shared__ double red[kWaves][2 * NQ];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 2 * NQ; ++q) {
+        const double v = wave_sum(acc[q]);
+        if (lane == 0) red[wv][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * NQ) {
+        double v = red[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) v += red[w][threadIdx.x];
+        double* part = threadIdx.x < NQ ? part0 : part1;
+        const int q = threadIdx.x < NQ ? threadIdx.x : threadIdx.x - NQ;
+        part[(size_t)blockIdx.x * kPartialStride + slot0 + q] = v;
+    }
+}
+
+// (a_c, b_c) = predict(column c's sums of k - 1); x += a p; r -= a s; r~ -= a s~ (without Jacobi r~ IS the new r);
+// p = r~ + b p; partials of nu_c = r~.r and rr_c = r.r   (pr_cg.py:146-151, :157)
+// DOTS_ONLY, the initial state: (r~ = d r); nu_c, rr_c   (:107-109)
+template <bool PREC, bool DOTS_ONLY>
+__global__ __launch_bounds__(kBlock) void k_pr2_update(Pr2Args a, int trips) {
+    Coefs c0 = {0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0};
+    if constexpr (!DOTS_ONLY) {
+        c0 = predict(a.dots_prev, a.meurant);
+        c1 = predict(a.dots_prev + kPartialStride, a.meurant);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            a.coef_out[0] = c0.al; a.coef_out[1] = c0.bt; a.coef_out[2] = c0.nup;
+            a.coef_out[kPr2CoefStride] = c1.al; a.coef_out[kPr2CoefStride + 1] = c1.bt; a.coef_out[kPr2CoefStride + 2] = c1.nup;
+        }
+    }
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};                       // nu_0, rr_0, nu_1, rr_1
+    const int64_t n = a.n;
+    double2* __restrict__ X = reinterpret_cast<double2*>(a.x);
+    double2* __restrict__ R = reinterpret_cast<double2*>(a.r);
+    double2* __restrict__ RT = reinterpret_cast<double2*>(a.rt);
+    double2* __restrict__ P = reinterpret_cast<double2*>(a.p);
+    const double2* __restrict__ S = reinterpret_cast<const double2*>(a.s);
+    const double2* __restrict__ ST = reinterpret_cast<const double2*>(a.st);
+    const double* __restrict__ D = a.d;
+
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        // ---- loads of both rows first (two independent rows in flight) ----
+        double2 x2[2], r2[2], rt2[2], p2[2], s2[2], st2[2];
+        double dv[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;               // clamped: branch-free loads
+            r2[e] = R[il];
+            if constexpr (!DOTS_ONLY) {
+                x2[e] = X[il]; p2[e] = P[il]; s2[e] = S[il];
+                if constexpr (PREC) { rt2[e] = RT[il]; st2[e] = ST[il]; }
+            } else if constexpr (PREC) {
+                dv[e] = D[il];
+            }
+        }
+        // ---- arithmetic + stores, row base then row base + 256 (this order is part of the reduction tree) ----
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!ok[e]) continue;
+            const int64_t ie = base + e * kBlock;
+            double2 rn = r2[e], zn;
+            if constexpr (!DOTS_ONLY) {
+                X[ie] = make_double2(x2[e].x + c0.al * p2[e].x, x2[e].y + c1.al * p2[e].y);  // x += a p
+                rn = make_double2(rn.x - c0.al * s2[e].x, rn.y - c1.al * s2[e].y);           // r -= a s
+                R[ie] = rn;
+                if constexpr (PREC) {
+                    zn = make_double2(rt2[e].x - c0.al * st2[e].x, rt2[e].y - c1.al * st2[e].y);   // r~ -= a s~
+                    RT[ie] = zn;
+                } else {
+                    zn = rn;
+                }
+                P[ie] = make_double2(zn.x + c0.bt * p2[e].x, zn.y + c1.bt * p2[e].y);        // p = r~ + b p
+            } else if constexpr (PREC) {
+                zn = make_double2(dv[e] * rn.x, dv[e] * rn.y);                               // r~ = M^-1 r
+                RT[ie] = zn;
+            } else {
+                zn = rn;
+            }
+            acc[0] += zn.x * rn.x; acc[1] += rn.x * rn.x;
+            acc[2] += zn.y * rn.y; acc[3] += rn.y * rn.y;
+        }
+    }
+    block_reduce_store2<2>(acc, a.part0, a.part1, kPr2Nu);
+}
+
+// after s = A p of both columns: (s~ = d s); partials of mu_c = p.s, dl_c = r.s~, gm_c = s~.s   (pr_cg.py:153-156)
+template <bool PREC>
+__global__ __launch_bounds__(kBlock) void k_pr2_dots(Pr2Args a, int trips) {
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};             // mu_0, dl_0, gm_0, mu_1, dl_1, gm_1
+    const int64_t n = a.n;
+    const double2* __restrict__ R = reinterpret_cast<const double2*>(a.r);
+    const double2* __restrict__ P = reinterpret_cast<const double2*>(a.p);
+    const double2* __restrict__ S = reinterpret_cast<const double2*>(a.s);
+    double2* __restrict__ ST = reinterpret_cast<double2*>(a.st);
+    const double* __restrict__ D = a.d;
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        double2 r2[2], p2[2], s2[2];
+        double dv[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;
+            r2[e] = R[il]; p2[e] = P[il]; s2[e] = S[il];
+            if constexpr (PREC) dv[e] = D[il];
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!ok[e]) continue;
+            double2 zs = s2[e];
+            if constexpr (PREC) {
+                zs = make_double2(dv[e] * s2[e].x, dv[e] * s2[e].y);                         // s~ = M^-1 s
+                ST[base + e * kBlock] = zs;
+            }
+            acc[0] += p2[e].x * s2[e].x; acc[1] += r2[e].x * zs.x; acc[2] += zs.x * s2[e].x;
+            acc[3] += p2[e].y * s2[e].y; acc[4] += r2[e].y * zs.y; acc[5] += zs.y * s2[e].y;
+        }
+    }
+    block_reduce_store2<3>(acc, a.part0, a.part1, kPr2Mu);
+}
+
 }  // namespace
 
 #define PRCG_LAUNCH_OK() (hipGetLastError() == hipSuccess)
@@ -166,6 +307,25 @@ int launch_hs2_update_p(hipStream_t st, const Hs2Args& a) {
 int launch_hs2_dot_ps(hipStream_t st, const Hs2Args& a) {
     const Chunking c = chunking(a.n);
     hipLaunchKernelGGL(k_hs2_dot_ps, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+
+int launch_pr2_update(hipStream_t st, const Pr2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_pr2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_pr2_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_pr2_init_dots(hipStream_t st, const Pr2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_pr2_update<true, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_pr2_update<false, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_pr2_dots(hipStream_t st, const Pr2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_pr2_dots<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_pr2_dots<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 

@@ -211,9 +211,10 @@ class DeviceCSR:
         self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
 
     def begin_multi(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
-        """Two right-hand sides in ONE Hestenes-Stiefel session (prcg.h: prcg_solve_begin_multi): B, X0 of shape (2, n),
+        """Two right-hand sides in ONE session (prcg.h: prcg_solve_begin_multi): B, X0 of shape (2, n),
         row j = right-hand side / start vector of system j.  Every iteration streams the operator once for both systems.
-        variant: L.HS; inv_diag: Jacobi on the device (the same diagonal for both); hist_mask: 0 or updated_residual_2_norm.
+        variant: L.HS (hs_cg / hs_pcg), L.PR (pr_cg / pr_pcg) or L.M (m_cg / m_pcg); inv_diag: Jacobi on the device (the same
+        diagonal for both); hist_mask: 0 or updated_residual_2_norm.
         iterate / sync / k serve the session as they are; state is read per column: get_vector(name, rhs=j), get_scalars(k, rhs=j),
         get_coefficients(k, rhs=j), history(rhs=j)."""
         B, X0 = _pair_of_vectors('B', B, self.n), _pair_of_vectors('X0', X0, self.n)
@@ -282,7 +283,7 @@ class DeviceCSR:
         self._check(self._lib.prcg_set_iteration(self._h, int(k)))
 
     def get_vector(self, name, *, rhs=None):
-        """rhs=j: column j of a two-RHS session (begin_multi)."""
+        """rhs=j: column j of a two-RHS session (begin_multi): x, r, p, s; with Jacobi rt, and in an L.PR / L.M session st."""
         out = np.empty(self.n)
         if rhs is None:
             self._check(self._lib.prcg_get_vector(self._h, L.VEC[name], L.ptr(out)))

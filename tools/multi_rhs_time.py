@@ -1,7 +1,9 @@
-"""Time of one Hestenes-Stiefel iteration of TWO right-hand sides, two ways, on one operator in one process:
-   multi_rhs_time.py [workload=s4b_80] [prec=none] [legs=ab] [repeats=3] [window=0.5] [ceiling=1]
+"""Time of one Hestenes-Stiefel (variant=pr, m: predict-and-recompute) iteration of TWO right-hand sides, two ways, on one
+operator in one process:
+   multi_rhs_time.py [workload=s4b_80] [variant=hs] [prec=none] [legs=ab] [repeats=3] [window=0.5] [ceiling=1]
      a  the two-RHS session (prcg_solve_begin_multi: one two-vector product per iteration serves both systems)
-     b  two single hs_cg (prec=jacobi: hs_pcg) sessions on the same handle, one after the other -- what there was before
+     b  two single hs_cg (prec=jacobi: hs_pcg) sessions on the same handle, one after the other -- what there was before;
+        variant=pr: pr_cg / pr_pcg, variant=m: m_cg / m_pcg
    prec: none | jacobi | none,jacobi (both, one after the other, in this process).
 The legs are alternated, `repeats` times each.  A window is `iterate(K)` + `sync` under the host clock after a warm-up, K
 chosen so that it lasts at least `window` seconds; leg b's window is the sum of its two sessions' windows of K iterations
@@ -10,7 +12,7 @@ One record per window on stderr; ONE JSON line on stdout: per prec and leg the m
 b / a of the medians, and whether a exceeds b by more than the spread of the repeats of both legs.
 ceiling=1 adds what prcg_stream_ceiling (mode 1) reaches in this process, the yardstick for the vector kernels: under
 `rocprofv3 --kernel-trace --stats -- python tools/multi_rhs_time.py legs=a repeats=1` k_hs2_update_xr moves 96 n bytes per
-launch (120 n with Jacobi), k_hs2_update_p 48 n, k_hs2_dot_ps 32 n.
+launch (120 n with Jacobi), k_hs2_update_p 48 n, k_hs2_dot_ps 32 n; variant=pr: k_pr2_update 112 n (160 n), k_pr2_dots 48 n (72 n).
 legs=b uses nothing the two-RHS session added, so this file also runs against an older build of the package."""
 import json, os, sys, time
 import numpy as np
@@ -19,16 +21,17 @@ import torch  # noqa: F401
 from new_cg_variants_amd import problems as P, _lib as L
 from new_cg_variants_amd.device import DeviceCSR
 
-opt = dict(workload='s4b_80', prec='none', legs='ab', repeats='3', window='0.5', ceiling='1')
+opt = dict(workload='s4b_80', variant='hs', prec='none', legs='ab', repeats='3', window='0.5', ceiling='1')
 for a in sys.argv[1:]:
     k, _, v = a.partition('=')
     if k not in opt or not v:
         sys.exit(f'unknown argument {a!r}\n{__doc__}')
     opt[k] = v
 repeats, window = int(opt['repeats']), float(opt['window'])
-if set(opt['legs']) - set('ab') or set(opt['prec'].split(',')) - {'none', 'jacobi'}:
+if set(opt['legs']) - set('ab') or set(opt['prec'].split(',')) - {'none', 'jacobi'} or opt['variant'] not in ('hs', 'pr', 'm'):
     sys.exit(__doc__)
 MAX_ITER, WARM, CALIB = 6000, 5, 5
+VARIANT = {'hs': L.HS, 'pr': L.PR, 'm': L.M}[opt['variant']]
 
 t0 = time.perf_counter()
 wl = P.WORKLOADS[opt['workload']]
@@ -56,20 +59,20 @@ def window_of(begin, target, k_fixed=None):
     return k, timed(k)
 
 
-result = {'workload': opt['workload'], 'n': n, 'nnz': nnz, 'operator_bytes': op.operator_bytes(), 'window_s': window, 'repeats': repeats}
+result = {'workload': opt['workload'], **({} if opt['variant'] == 'hs' else {'variant': opt['variant']}), 'n': n, 'nnz': nnz, 'operator_bytes': op.operator_bytes(), 'window_s': window, 'repeats': repeats}
 for prec in opt['prec'].split(','):
     d = 1 / A.diagonal() if prec == 'jacobi' else None
     us = {leg: [] for leg in opt['legs']}
     for rep in range(repeats):
         for leg in opt['legs']:
             if leg == 'a':
-                k, dt = window_of(lambda: op.begin_multi(L.HS, B, X0, MAX_ITER, inv_diag=d), window)
+                k, dt = window_of(lambda: op.begin_multi(VARIANT, B, X0, MAX_ITER, inv_diag=d), window)
                 finite = bool(np.isfinite(op.get_scalars(op.k, rhs=0)[L.S_NU]) and np.isfinite(op.get_scalars(op.k, rhs=1)[L.S_NU]))
             else:
                 # each session half a window: the pair of sessions is one window of K iterations of both systems
-                k, dt0 = window_of(lambda: op.begin(L.HS, B[0], X0[0], MAX_ITER, inv_diag=d), window / 2)
+                k, dt0 = window_of(lambda: op.begin(VARIANT, B[0], X0[0], MAX_ITER, inv_diag=d), window / 2)
                 finite = bool(np.isfinite(op.get_scalars(op.k)[L.S_NU]))
-                _, dt1 = window_of(lambda: op.begin(L.HS, B[1], X0[1], MAX_ITER, inv_diag=d), window / 2, k)
+                _, dt1 = window_of(lambda: op.begin(VARIANT, B[1], X0[1], MAX_ITER, inv_diag=d), window / 2, k)
                 finite = finite and bool(np.isfinite(op.get_scalars(op.k)[L.S_NU]))
                 dt = dt0 + dt1
             s = op.schedule()
