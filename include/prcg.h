@@ -175,6 +175,12 @@ int prcg_spmv_ext(prcg_t* h, const double* x_ext, double* y);
 /* [w u] = A [r s], the fused two-vector product of the pipelined loop
  * (pipe_pr_cg.py:69-70; mpi4py pipe_pr_cg.py:65).  rs, wu: n_rows x 2 row-major. */
 int prcg_spmm2(prcg_t* h, const double* rs, double* wu, int reps, double* ms_avg);
+/* [y_0 y_1 y_2 y_3] = A [x_0 x_1 x_2 x_3], the product of a four-RHS session (prcg_solve_begin_multi with nrhs = 4), on the
+ * route that session takes: ONE launch that reads the operator once on sliced-row operators (PRCG_SPMM4=0: never), two
+ * two-vector launches (columns 0, 1 and 2, 3) on every other operator -- per column the bits of prcg_spmm2 either way.
+ * Replaces four `A @ v` (hs_cg.py:23,26,59 for each of four right-hand sides).  x4, y4: n_rows x 4 row-major host doubles.
+ * Single GPU, n_ghost == 0. */
+int prcg_spmm4(prcg_t* h, const double* x4, double* y4, int reps, double* ms_avg);
 
 /* ---- solver session ----------------------------------------------------------------
  * begin: upload b, x0 (+ optional x_true, inv_diag), run the variant's initialisation
@@ -220,6 +226,8 @@ int prcg_iteration(const prcg_t* h);
 #define PRCG_SCHED_XP_DEFERRED 8388608 /* single-GPU one-launch pipelined iteration: prcg_iterate runs its launches in pairs, the first of a
                                           pair does not store (x,p) and the second rebuilds them bit for bit (PRCG_XP_DEFER=0: off) */
 #define PRCG_SCHED_RHS2 16777216 /* the session solves TWO right-hand sides (prcg_solve_begin_multi): one two-vector product per iteration */
+#define PRCG_SCHED_RHS4 33554432 /* the session solves FOUR right-hand sides as two pair groups (PRCG_SCHED_RHS2 means exactly two: clear here) */
+#define PRCG_SCHED_SPMM4 67108864 /* ... and its product is ONE four-vector launch (sliced rows; else two two-vector launches) */
 /* 1048576: retired (was PRCG_SCHED_MEDIUM, the few-workgroup solver of mid-size systems); never to be reused */
 #define PRCG_SCHED_WINDOW 4096  /* row-per-lane window kernels (bands, stencils): the column stream holds indices into the tile's
                                    LDS-staged window of the input vector */
@@ -273,14 +281,14 @@ int prcg_get_coefficients(prcg_t* h, int k, double* out);
 /* histories: for each bit set in hist_mask (ascending bit order) max_iter doubles;
  * entries beyond the current iteration are 0, as numpy.zeros(max_iter) leaves them. */
 int prcg_get_history(prcg_t* h, double* hist);
-/* ---- Hestenes-Stiefel or predict-and-recompute with TWO right-hand sides in one session --------
+/* ---- Hestenes-Stiefel or predict-and-recompute with TWO right-hand sides in one session (or FOUR) --------
  * Replaces TWO calls of the reference's hs_cg (numerical_experiments/cg_variants/hs_cg.py:9) or hs_pcg (:70), of pr_pcg
  * (pr_cg.py:166) or of m_pcg (pr_cg.py:172) on one matrix: load cases, time steps with a frozen operator, columns of a
  * block solve.  The two recurrences stay what they are
  * -- each column has its own a_k, b_k, inner products and history, nothing of one column enters the other (a breakdown of
  * one leaves the other's bits untouched) -- but every iteration streams the operator ONCE: s = A p of both columns is one
  * two-vector product (what prcg_spmm2 runs), on assembled FEM matrices most of an iteration's memory traffic.
- *   variant: PRCG_HS, PRCG_PR or PRCG_M.  nrhs: 2 only.  b, x0: nrhs pointers to n_rows host doubles each.  inv_diag != NULL:
+ *   variant: PRCG_HS, PRCG_PR or PRCG_M.  nrhs: 2 or 4.  b, x0: nrhs pointers to n_rows host doubles each.  inv_diag != NULL:
  *   hs_pcg / pr_pcg / m_pcg with Jacobi, the same diagonal for both columns; inv_diag == NULL: hs_cg, or for PRCG_PR / PRCG_M
  *   the identity-preconditioned recurrences (this library's pr_cg / m_cg).  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.
  *   A Hestenes-Stiefel iteration is six launches around its two dependent inner products; a predict-and-recompute
@@ -292,7 +300,12 @@ int prcg_get_history(prcg_t* h, double* hist);
  * prcg_get_scalars, prcg_set_scalars, prcg_get_coefficients, prcg_get_history, prcg_set_iteration) are refused while it
  * is open.  A later prcg_solve_begin on the handle opens an ordinary session again.
  * Every inner product is summed in one fixed order: results are reproducible bit for bit, and
- * exchanging the two right-hand sides exchanges the two results bit for bit. */
+ * exchanging the two right-hand sides exchanges the two results bit for bit.
+ * nrhs = 4 (replaces FOUR calls of the reference's function): two PAIR GROUPS, columns (0, 1) and (2, 3), each a complete
+ * two-RHS state with its own vectors, inner products and coefficients, iterated by the same vector kernels around ONE product
+ * [S_0 S_1 | S_2 S_3] = A [P_0 P_1 | P_2 P_3] (what prcg_spmm4 runs; PRCG_SCHED_SPMM4 says whether it is one launch).  Columns
+ * (0, 1) and (2, 3) carry the bits of two two-RHS sessions begun with those pairs; the accessors below take j = 0 .. 3 and
+ * return per column what they return in a two-RHS session; the refusals are those of the two-RHS session, word for word. */
 int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
                            int max_iter, const double* inv_diag, uint32_t hist_mask);
 /* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi; PRCG_PR / PRCG_M sessions with Jacobi also _ST); out: n_rows host doubles */

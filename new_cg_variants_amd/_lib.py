@@ -61,6 +61,7 @@ _SIGNATURES = {
     'prcg_spmv': (C.c_int, [_P, _P, _P, C.c_int, _dp]),
     'prcg_spmv_ext': (C.c_int, [_P, _P, _P]),
     'prcg_spmm2': (C.c_int, [_P, _P, _P, C.c_int, _dp]),
+    'prcg_spmm4': (C.c_int, [_P, _P, _P, C.c_int, _dp]),
     'prcg_solve_begin': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_uint32]),
     'prcg_iterate': (C.c_int, [_P, C.c_int]),
     'prcg_sync': (C.c_int, [_P]),

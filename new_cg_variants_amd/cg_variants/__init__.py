@@ -33,7 +33,7 @@ import numpy as np
 
 from .. import _lib as L
 from ..callbacks import RECORDER_NAMES
-from ..device import DeviceCSR
+from ..device import DeviceCSR, multi_rhs_shape_error
 
 _OPERATORS = OrderedDict()   # small cache: figure_gen runs nine variants on one matrix
 _MAX_CACHED = 2
@@ -325,16 +325,18 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
 
 
 def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
-    """Two right-hand sides of one matrix in ONE session of `variant` (L.HS, L.PR, L.M; prcg.h: prcg_solve_begin_multi): what
-    two calls of hs_cg / hs_pcg (pr_cg / pr_pcg, m_cg / m_pcg) compute, with the operator streamed once per iteration for both.  Every argument is checked before
+    """Two or four right-hand sides of one matrix in ONE session of `variant` (L.HS, L.PR, L.M; prcg.h: prcg_solve_begin_multi): what
+    two (four) calls of hs_cg / hs_pcg (pr_cg / pr_pcg, m_cg / m_pcg) compute, with the operator streamed once per iteration for all of them.  Every argument is checked before
     the device is touched; what the session does not serve raises ValueError -- nothing falls back to two sessions."""
     if A.format != 'csr':
         A = A.tocsr()
     n = A.shape[0]
     B, X0 = np.asarray(B, dtype=np.float64), np.asarray(X0, dtype=np.float64)
-    for nm, V in (('B', B), ('X0', X0)):
-        if V.shape != (2, n):
-            raise ValueError(f'{name}: {nm} must have shape (2, {n}) -- two right-hand sides of the operator\'s size -- got {V.shape}')
+    for nm, V, want in (('B', B, None), ('X0', X0, B.shape[0] if B.ndim == 2 else None)):
+        err = multi_rhs_shape_error(nm, V.shape, n, want)
+        if err:
+            raise ValueError(f'{name}: {err}')
+    nrhs = B.shape[0]
     for key in ('x_true', 'w_replace'):
         if kwargs.get(key) is not None:
             raise ValueError(f'{name}: {key} is not served by the two-RHS session')
@@ -359,10 +361,10 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
     op.set_replace_hook(None)
     op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
     op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
-    outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(2)]
+    outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(nrhs)]
 
     def call_host(k):
-        for j in range(2):
+        for j in range(nrhs):
             env = {'output': outputs[j], 'k': k, 'max_iter': max_iter, 'A': A, 'b': B[j], 'x0': X0[j], 'n': n,
                    'kwargs': kwargs, 'callbacks': callbacks}
             for cb in light:
@@ -376,21 +378,21 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
     else:
         op.iterate(max_iter - 1)
     op.sync()
-    for j in range(2):
+    for j in range(nrhs):
         outputs[j].update(op.history(rhs=j))
     return outputs
 
 
 def hs_cg_multi(A, B, X0, max_iter, callbacks=[], **kwargs):
-    """hs_cg (hs_cg.py:9) for TWO right-hand sides of one matrix: B, X0 of shape (2, n); returns a list of two trial dicts
-    shaped like hs_cg's.  One session, one pass over the operator per iteration."""
+    """hs_cg (hs_cg.py:9) for TWO or FOUR right-hand sides of one matrix: B, X0 of shape (2, n) or (4, n); returns a list of
+    two or four trial dicts shaped like hs_cg's.  One session, one pass over the operator per iteration."""
     if kwargs.pop('preconditioner', None) is not None:
         raise ValueError('hs_cg_multi takes no preconditioner: use hs_pcg_multi')
     return _run_multi(L.HS, 'hs_cg_multi', A, B, X0, max_iter, None, callbacks, kwargs)
 
 
 def hs_pcg_multi(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
-    """hs_pcg (hs_cg.py:70) for TWO right-hand sides of one matrix, with Jacobi(A) or a callable that probes as a diagonal."""
+    """hs_pcg (hs_cg.py:70) for TWO or FOUR right-hand sides of one matrix, with Jacobi(A) or a callable that probes as a diagonal."""
     return _run_multi(L.HS, 'hs_pcg_multi', A, B, X0, max_iter, preconditioner, callbacks, kwargs)
 
 
@@ -399,16 +401,16 @@ def _make_multi(variant, name, preconditioned):
     if preconditioned:
         def f(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
             return _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs)
-        f.__doc__ = (f'{single} (pr_cg.py:{166 if variant == L.PR else 172}) for TWO right-hand sides of one matrix, with Jacobi(A) or a '
-                     'callable that probes as a diagonal: B, X0 of shape (2, n); returns a list of two trial dicts.  One session, one '
+        f.__doc__ = (f'{single} (pr_cg.py:{166 if variant == L.PR else 172}) for TWO or FOUR right-hand sides of one matrix, with Jacobi(A) or a '
+                     'callable that probes as a diagonal: B, X0 of shape (2, n) or (4, n); returns a list of two or four trial dicts.  One session, one '
                      'pass over the operator and one reduction point per iteration.')
     else:
         def f(A, B, X0, max_iter, callbacks=[], **kwargs):
             if kwargs.pop('preconditioner', None) is not None:
                 raise ValueError(f'{name} takes no preconditioner: use {single[:-2]}pcg_multi')
             return _run_multi(variant, name, A, B, X0, max_iter, None, callbacks, kwargs)
-        f.__doc__ = (f'{single} (the identity-preconditioned recurrence of {single[:-2]}pcg) for TWO right-hand sides of one matrix: B, X0 '
-                     'of shape (2, n); returns a list of two trial dicts.  One session, one pass over the operator per iteration.')
+        f.__doc__ = (f'{single} (the identity-preconditioned recurrence of {single[:-2]}pcg) for TWO or FOUR right-hand sides of one matrix: B, X0 '
+                     'of shape (2, n) or (4, n); returns a list of two or four trial dicts.  One session, one pass over the operator per iteration.')
     f.__name__ = f.__qualname__ = name
     return f
 

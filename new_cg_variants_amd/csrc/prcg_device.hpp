@@ -76,13 +76,18 @@ __device__ __forceinline__ void wave_lds_sync() {
 template <int NV> struct VecT;
 template <> struct VecT<1> { using type = double; };
 template <> struct VecT<2> { using type = double2; };
+template <> struct VecT<4> { using type = double4; };      // two pairs: (x, y) from the first pair array, (z, w) from the second
 
 __device__ __forceinline__ double vmul(double a, double g) { return a * g; }
 __device__ __forceinline__ double2 vmul(double a, double2 g) { return make_double2(a * g.x, a * g.y); }
+__device__ __forceinline__ double4 vmul(double a, double4 g) { return make_double4(a * g.x, a * g.y, a * g.z, a * g.w); }
 __device__ __forceinline__ void vacc(double& s, double p) { s += p; }
 __device__ __forceinline__ void vacc(double2& s, double2 p) { s.x += p.x; s.y += p.y; }
+__device__ __forceinline__ void vacc(double4& s, double4 p) { s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w; }
 __device__ __forceinline__ void vzero(double& s) { s = 0.0; }
 __device__ __forceinline__ void vzero(double2& s) { s.x = 0.0; s.y = 0.0; }
+__device__ __forceinline__ void vzero(double4& s) { s.x = 0.0; s.y = 0.0; s.z = 0.0; s.w = 0.0; }
+__device__ __forceinline__ double4 two_pairs(double2 a, double2 b) { return make_double4(a.x, a.y, b.x, b.y); }
 __device__ __forceinline__ double vwave_sum(double v) { return wave_sum(v); }
 __device__ __forceinline__ double2 vwave_sum(double2 v) { return make_double2(wave_sum(v.x), wave_sum(v.y)); }
 

@@ -158,6 +158,9 @@ struct Session {
     bool have_xtrue = false;
     bool rhs2 = false;           // session type "two right-hand sides" (prcg_solve_begin_multi): Hestenes-Stiefel, or with
                                  // variant PRCG_PR / PRCG_M predict-and-recompute (two scalar / coefficient rows per iteration)
+    int groups = 0;              // ... its PAIR GROUPS: 1 with two right-hand sides, 2 with four (group g: columns 2 g, 2 g + 1, a
+                                 // complete two-RHS state of its own -- pair_group)
+    bool spmm4 = false;          // ... two groups: the product of an iteration is ONE four-vector launch (sliced rows, PRCG_SPMM4)
     // ---- schedule ----
     bool fused = false;          // pipelined: the one-launch-per-iteration kernel
     bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
@@ -243,6 +246,9 @@ struct prcg_handle : Operator, Session {
     DevBuf w2, u2, t2;           // ... their second copies (one- / two-launch schedules on window operators)
     DevBuf mx, mr, mp, ms, mrt;  // two right-hand sides: the interleaved n x 2 arrays X, R, P, S, RT (Hs2Args, prcg_kernels.h); dots / coef hold both columns per row
     DevBuf mst;                  // ... predict-and-recompute with Jacobi: ST (Pr2Args); dots / coef hold one row per column and iteration
+    DevBuf mx1, mr1, mp1, ms1, mrt1, mst1;   // four right-hand sides: the same arrays of the SECOND pair group (columns 2, 3) ...
+    DevBuf partA1, partB1;                   // ... and its block partials
+    DevBuf x4b, y4b;             // prcg_spmm4: the second source / destination pair array (the first: tmp_ext / t1)
     DevBuf pub, pub_err;         // publication record of the reduced inner products / timeout flag
     DevBuf q, q2;                // packed predict-and-recompute state (Session::pr_packed)
     DevBuf dots, coef;
@@ -286,7 +292,7 @@ struct prcg_handle : Operator, Session {
     // every vector a window launch may stage (the pointer handed to the launch lies inside one of them)
     const DevBuf* owner(const void* ptr) const {
         const DevBuf* all[] = {&tmp_ext, &t1, &x, &xp, &p, &p2, &rs, &rs2, &rst, &rst2, &wu, &wt, &wv, &r, &r2, &s, &s2, &rt, &rt2,
-                               &st, &st2, &b, &xt, &dinv, &e_ext, &w, &w2, &u, &u2, &tvec, &t2, &ut, &cb_stage, &q, &q2, &mx, &mp};
+                               &st, &st2, &b, &xt, &dinv, &e_ext, &w, &w2, &u, &u2, &tvec, &t2, &ut, &cb_stage, &q, &q2, &mx, &mp, &mx1, &mp1, &x4b};
         const char* c = static_cast<const char*>(ptr);
         for (const DevBuf* d : all)
             if (d->p && c >= static_cast<const char*>(d->p) && c < static_cast<const char*>(d->p) + d->bytes) return d;
@@ -387,6 +393,19 @@ int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu
     if (h->win) return launch_win_spmm2(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, mask, h->opt.win_per_cu);
     if (h->sell) return launch_sell_spmm2(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, h->opt.sell_per_cu);
     return launch_spmm2(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, h->opt.kn);
+}
+// [dst0 | dst1] = A [src0 | src1], two pair arrays: one launch on sliced rows (PRCG_SPMM4=0: never), else a two-vector
+// product per pair -- the same bits per column either way
+bool spmm4_one_launch(const prcg_t* h) { return h->sell && h->opt.want_spmm4; }
+int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1) {
+    SRCCHK(h, {src0, 2}, {src1, 2});
+    if (spmm4_one_launch(h)) {
+        const TileRange t = tile_range(h, which);
+        return launch_sell_spmm4(st, h->sdev(), h->sslice_ptr(t.first), t.count, src0, src1, dst0, dst1, h->opt.sell_per_cu);
+    }
+    const int g0 = eng_spmm2(h, st, which, src0, dst0, 3);
+    if (g0 < 0) return g0;
+    return eng_spmm2(h, st, which, src1, dst1, 3);
 }
 // (only the window kernels have the deferred form that runs one class of tiles; the others always take every tile)
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which = 0) {
@@ -901,77 +920,106 @@ void hs_flush(prcg_t* h) {
 
 // Two right-hand sides in one Hestenes-Stiefel session (hs_cg.py:54-62 / hs_pcg :116-125 for each column): the vector
 // kernels of prcg_rhs2.hip around ONE two-vector product of [p_0 p_1] -- the operator is streamed once for both systems.
-Hs2Args hs2_args(prcg_t* h, int k) {
-    Hs2Args a{};
-    a.n = h->n;
-    a.x = h->mx.d(); a.r = h->mr.d(); a.rt = h->prec ? h->mrt.d() : nullptr; a.p = h->mp.d(); a.s = h->ms.d();
-    a.d = h->prec ? h->dinv.d() : nullptr;
-    a.dots_prev = k > 0 ? dots_at(h, k - 1) : nullptr;
-    a.dots_cur = dots_at(h, k);
-    a.coef_out = coef_at(h, k);
-    a.partials = h->partA.d();
-    return a;
+// Four right-hand sides are two PAIR GROUPS, each a complete state of this kind (its own arrays, block partials and rows of
+// dots / coef: group g's rows follow group g - 1's max_iter + 1 iterations), around ONE product of both groups' directions.
+bool pr2(const prcg_t* h) { return h->rhs2 && is_pr(h->variant); }
+struct PairGroup { DevBuf *x, *r, *p, *s, *rt, *st, *partA, *partB; int row0; };
+PairGroup pair_group(prcg_t* h, int g) {
+    const int row0 = g * (h->max_iter + 1) * (pr2(h) ? 2 : 1);
+    if (g == 0) return PairGroup{&h->mx, &h->mr, &h->mp, &h->ms, &h->mrt, &h->mst, &h->partA, &h->partB, row0};
+    return PairGroup{&h->mx1, &h->mr1, &h->mp1, &h->ms1, &h->mrt1, &h->mst1, &h->partA1, &h->partB1, row0};
 }
-// s = A p for both columns, then mu_c = p.s (a launch of its own: the two-vector products have no dot epilogue)
-int hs2_product_and_mu(prcg_t* h, int k, Hs2Args a) {
+// s = A p of every column: one two-vector product, or with two pair groups one product of [P_0 P_1 | P_2 P_3]
+int multi_product(prcg_t* h, int k) {
     bool on = false;
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
-    LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, h->mp.d(), h->ms.d(), 3));
+    if (h->groups == 2) LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, h->mp.d(), h->mp1.d(), h->ms.d(), h->ms1.d()));
+    else LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, h->mp.d(), h->ms.d(), 3));
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-    a.partials = h->partB.d();
-    const int g = launch_hs2_dot_ps(h->sc, a);
-    LAUNCHCHK(h, g);
-    launch_reduce_final(h->sc, h->partB.d(), g, dots_at(h, k), kHs2Mu, kHs2Mu, 2);
+    return PRCG_OK;
+}
+Hs2Args hs2_args(prcg_t* h, int k, int g) {
+    const PairGroup G = pair_group(h, g);
+    Hs2Args a{};
+    a.n = h->n;
+    a.x = G.x->d(); a.r = G.r->d(); a.rt = h->prec ? G.rt->d() : nullptr; a.p = G.p->d(); a.s = G.s->d();
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, G.row0 + k - 1) : nullptr;
+    a.dots_cur = dots_at(h, G.row0 + k);
+    a.coef_out = coef_at(h, G.row0 + k);
+    a.partials = G.partA->d();
+    return a;
+}
+// s = A p for every column, then per group mu_c = p.s (a launch of its own: the multi-vector products have no dot epilogue)
+int hs2_product_and_mu(prcg_t* h, int k) {
+    int rc = multi_product(h, k);
+    if (rc) return rc;
+    for (int g = 0; g < h->groups; ++g) {
+        const PairGroup G = pair_group(h, g);
+        Hs2Args a = hs2_args(h, k, g);
+        a.partials = G.partB->d();
+        const int grid = launch_hs2_dot_ps(h->sc, a);
+        LAUNCHCHK(h, grid);
+        launch_reduce_final(h->sc, G.partB->d(), grid, dots_at(h, G.row0 + k), kHs2Mu, kHs2Mu, 2);
+    }
     return PRCG_OK;
 }
 int iterate_hs2(prcg_t* h, int k) {
-    Hs2Args a = hs2_args(h, k);
-    bool on = false;
-    prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-    const int g1 = launch_hs2_update_xr(h->sc, a);
-    LAUNCHCHK(h, g1);
-    prof_end(h, h->ev_upd, h->n_ev_upd, on);
-    launch_reduce_final(h->sc, h->partA.d(), g1, dots_at(h, k), kHs2Nu, kHs2Nu, 4);     // nu_0, rr_0, nu_1, rr_1
-    LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));
-    return hs2_product_and_mu(h, k, a);
+    for (int g = 0; g < h->groups; ++g) {
+        const Hs2Args a = hs2_args(h, k, g);
+        bool on = false;
+        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);             // (the sample: the first group's update launch)
+        const int g1 = launch_hs2_update_xr(h->sc, a);
+        LAUNCHCHK(h, g1);
+        prof_end(h, h->ev_upd, h->n_ev_upd, on);
+        launch_reduce_final(h->sc, a.partials, g1, dots_at(h, pair_group(h, g).row0 + k), kHs2Nu, kHs2Nu, 4);     // nu_0, rr_0, nu_1, rr_1
+        LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));
+    }
+    return hs2_product_and_mu(h, k);
 }
 
 // Two right-hand sides in one predict-and-recompute session (pr_cg.py:146-158 for each column; PRCG_M: Meurant's prediction):
 // update, ONE two-vector product of [p_0 p_1], the three inner products that need s, one reduction launch per column.
-bool pr2(const prcg_t* h) { return h->rhs2 && is_pr(h->variant); }
-Pr2Args pr2_args(prcg_t* h, int k) {
+Pr2Args pr2_args(prcg_t* h, int k, int g) {
+    const PairGroup G = pair_group(h, g);
     Pr2Args a{};
     a.n = h->n;
-    a.x = h->mx.d(); a.r = h->mr.d(); a.p = h->mp.d(); a.s = h->ms.d();
-    a.rt = h->prec ? h->mrt.d() : nullptr; a.st = h->prec ? h->mst.d() : nullptr;
+    a.x = G.x->d(); a.r = G.r->d(); a.p = G.p->d(); a.s = G.s->d();
+    a.rt = h->prec ? G.rt->d() : nullptr; a.st = h->prec ? G.st->d() : nullptr;
     a.d = h->prec ? h->dinv.d() : nullptr;
-    a.dots_prev = k > 0 ? dots_at(h, 2 * (k - 1)) : nullptr;       // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
-    a.coef_out = coef_at(h, 2 * k);
-    a.part0 = h->partA.d(); a.part1 = h->partB.d();
+    a.dots_prev = k > 0 ? dots_at(h, G.row0 + 2 * (k - 1)) : nullptr;       // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
+    a.coef_out = coef_at(h, G.row0 + 2 * k);
+    a.part0 = G.partA->d(); a.part1 = G.partB->d();
     a.meurant = meurant(h->variant);
     return a;
 }
-// s = A p for both columns, (s~ = d s), mu, dl, gm; then the five sums of each column: rows 2 k and 2 k + 1
-int pr2_product_and_sums(prcg_t* h, int k, const Pr2Args& a, int g_upd) {
-    bool on = false;
-    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
-    LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, h->mp.d(), h->ms.d(), 3));
-    prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-    const int g = launch_pr2_dots(h->sc, a);
-    LAUNCHCHK(h, g);
-    CHECK(h, g == g_upd, "two-RHS session: the update and the dots launch disagree on the grid (%d, %d)", g_upd, g);
-    launch_reduce_final(h->sc, h->partA.d(), g, dots_at(h, 2 * k), 0, 0, 5);
-    launch_reduce_final(h->sc, h->partB.d(), g, dots_at(h, 2 * k + 1), 0, 0, 5);
+// s = A p for every column, (s~ = d s), mu, dl, gm; then the five sums of each column: rows 2 k and 2 k + 1 of its group
+// (g_upd[g]: the grid of group g's update launch, whose partials the sums include)
+int pr2_product_and_sums(prcg_t* h, int k, const int* g_upd) {
+    int rc = multi_product(h, k);
+    if (rc) return rc;
+    for (int g = 0; g < h->groups; ++g) {
+        const Pr2Args a = pr2_args(h, k, g);
+        const int grid = launch_pr2_dots(h->sc, a);
+        LAUNCHCHK(h, grid);
+        CHECK(h, grid == g_upd[g], "two-RHS session: the update and the dots launch disagree on the grid (%d, %d)", g_upd[g], grid);
+        const int row = pair_group(h, g).row0 + 2 * k;
+        launch_reduce_final(h->sc, a.part0, grid, dots_at(h, row), 0, 0, 5);
+        launch_reduce_final(h->sc, a.part1, grid, dots_at(h, row + 1), 0, 0, 5);
+    }
     return PRCG_OK;
 }
 int iterate_pr2(prcg_t* h, int k) {
-    const Pr2Args a = pr2_args(h, k);
-    bool on = false;
-    prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-    const int g1 = launch_pr2_update(h->sc, a);
-    LAUNCHCHK(h, g1);
-    prof_end(h, h->ev_upd, h->n_ev_upd, on);
-    return pr2_product_and_sums(h, k, a, g1);
+    int g_upd[2] = {0, 0};
+    for (int g = 0; g < h->groups; ++g) {
+        const Pr2Args a = pr2_args(h, k, g);
+        bool on = false;
+        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);             // (the sample: the first group's update launch)
+        g_upd[g] = launch_pr2_update(h->sc, a);
+        LAUNCHCHK(h, g_upd[g]);
+        prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    }
+    return pr2_product_and_sums(h, k, g_upd);
 }
 
 // hs_cg.py:54-62 (hs_pcg :116-125) on one GPU without reduction launches.  The two inner products still separate
@@ -2015,6 +2063,46 @@ int prcg_spmm2(prcg_t* h, const double* rs, double* wu, int reps, double* ms_avg
     return timed_product(h, 2, rs, wu, reps, ms_avg);
 }
 
+int prcg_spmm4(prcg_t* h, const double* x4, double* y4, int reps, double* ms_avg) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, h->have_csr, "no matrix: call prcg_set_csr first");
+    CHECK(h, x4 && y4 && reps >= 1, "bad argument");
+    CHECK(h, !h->multi() && h->g == 0, "prcg_spmm4: one GPU, whole operators only (no communicator, n_ghost = 0)");
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int64_t n = h->n;
+    const size_t D = sizeof(double);
+    HIPCHK(h, h->x4b.ensure((size_t)2 * (n + kGatherPad) * D, h->sc));
+    HIPCHK(h, h->y4b.ensure((size_t)2 * n * D, h->sc));
+    std::vector<double> pairs;
+    try { pairs.resize((size_t)2 * n); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "prcg_spmm4: host staging"); }
+    int rc;
+    for (int g = 0; g < 2; ++g) {
+        for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = x4[4 * i + 2 * g]; pairs[2 * i + 1] = x4[4 * i + 2 * g + 1]; }
+        if ((rc = h2d(h, g == 0 ? h->tmp_ext.d() : h->x4b.d(), pairs.data(), 2 * n))) return rc;
+    }
+    hipEvent_t a, b;
+    HIPCHK(h, hipEventCreate(&a));
+    HIPCHK(h, hipEventCreate(&b));
+    double total = 0.0;
+    for (int i = 0; i < reps; ++i) {
+        HIPCHK(h, hipEventRecord(a, h->sc));
+        LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, h->tmp_ext.d(), h->x4b.d(), h->t1.d(), h->y4b.d()));
+        HIPCHK(h, hipEventRecord(b, h->sc));
+        HIPCHK(h, hipEventSynchronize(b));
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, a, b));
+        total += ms;
+    }
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    if (ms_avg) *ms_avg = total / reps;
+    for (int g = 0; g < 2; ++g) {
+        if ((rc = d2h(h, pairs.data(), g == 0 ? h->t1.d() : h->y4b.d(), 2 * n))) return rc;
+        for (int64_t i = 0; i < n; ++i) { y4[4 * i + 2 * g] = pairs[2 * i]; y4[4 * i + 2 * g + 1] = pairs[2 * i + 1]; }
+    }
+    return PRCG_OK;
+}
+
 // What the row results of a one-launch iteration cost beside the operator's read stream depends on WHERE the written arrays lie:
 // the same byte mix runs at two speeds from process to process (tools/mixbench.hip: s4b's mix 467-477 or 530-560 us, the read
 // stream alone 443 either way; r04_sweeps.md D, K) and from allocation to allocation inside a process.  The session's three
@@ -2117,7 +2205,8 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries (dinv is a window source of
     // the Chronopoulos-Gear product launch)
     HIPCHK(h, h->dinv.ensure((size_t)(h->n + h->g + kGatherPad) * D, h->sc));
-    // (rows_per_iteration = 2: the predict-and-recompute two-RHS session keeps one scalar and one coefficient row per column)
+    // (rows_per_iteration = 2: the predict-and-recompute two-RHS session keeps one scalar and one coefficient row per column;
+    //  four right-hand sides: twice the rows again, one set per pair group)
     HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * rows_per_iteration * kNS * D, h->sc));
     HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * rows_per_iteration * kCoefStride * D, h->sc));
     if (inv_diag) return h2d(h, h->dinv.d(), inv_diag, h->n);
@@ -2492,7 +2581,8 @@ int prcg_schedule(const prcg_t* h) {
            (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
            (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
-           (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) | (h->rhs2 ? PRCG_SCHED_RHS2 : 0) |
+           (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) | ((h->rhs2 && h->groups == 1) ? PRCG_SCHED_RHS2 : 0) |
+           (h->groups == 2 ? PRCG_SCHED_RHS4 : 0) | (h->spmm4 ? PRCG_SCHED_SPMM4 : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
            ((h->win ? h->win_vd : h->vd_int) ? PRCG_SCHED_VALDICT : 0) |
            (h->win ? (h->win_pat ? PRCG_SCHED_PATTERN : (h->win_geom < 2 ? PRCG_SCHED_COL8 : PRCG_SCHED_COL16)) | PRCG_SCHED_WINDOW
@@ -2633,11 +2723,12 @@ int prcg_get_history(prcg_t* h, double* hist) {
     return PRCG_OK;
 }
 
-// ---- two right-hand sides in one session: Hestenes-Stiefel, predict-and-recompute (PRCG_PR, PRCG_M) ----
+// ---- two or four right-hand sides in one session: Hestenes-Stiefel, predict-and-recompute (PRCG_PR, PRCG_M) ----
 int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
                            const double* inv_diag, uint32_t hist_mask) {
     if (!h) return PRCG_EINVAL;
-    CHECK(h, nrhs == 2, "prcg_solve_begin_multi: nrhs = %d: the multi-RHS session serves exactly 2 right-hand sides", nrhs);
+    CHECK(h, nrhs == 2 || nrhs == 4, "prcg_solve_begin_multi: nrhs = %d: the multi-RHS session serves exactly 2 right-hand sides "
+                                     "(or 4, as two pairs)", nrhs);
     CHECK(h, variant == PRCG_HS || is_pr(variant), "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg), "
                                                    "PRCG_PR (pr_cg / pr_pcg) and PRCG_M (m_cg / m_pcg) only", variant);
     CHECK(h, !h->multi(), "prcg_solve_begin_multi: a communicator is set on the handle: the two-RHS session runs on one GPU");
@@ -2649,70 +2740,97 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     CHECK(h, h->replace_fn == nullptr, "prcg_solve_begin_multi: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session");
     CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
           "prcg_solve_begin_multi: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the two-RHS session");
-    CHECK(h, b && x0 && b[0] && b[1] && x0[0] && x0[1], "prcg_solve_begin_multi: null b or x0");
+    bool have_all = b && x0;
+    for (int j = 0; have_all && j < nrhs; ++j) have_all = b[j] && x0[j];
+    CHECK(h, have_all, "prcg_solve_begin_multi: null b or x0");
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
-    // X and P feed the two-vector product: like every product source they carry the spare entries behind row n
+    const int groups = nrhs / 2;
+    const bool pr = is_pr(variant);
+    // X and P feed the product: like every product source they carry the spare entries behind row n.  The second pair
+    // group's arrays (and its block partials) follow the first's, and only a four-RHS session asks for them.
+    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D, tilde = inv_diag ? vec : 16, part = (size_t)8192 * kPartialStride * D;
     int rc;
-    if (variant == PRCG_HS)
+    if (groups == 1 && !pr)
         rc = open_session(h, "prcg_solve_begin_multi", PRCG_HS, max_iter, hist_mask, inv_diag, false,
-                          {{&h->mx, (size_t)2 * ne * D}, {&h->mp, (size_t)2 * ne * D}, {&h->mr, (size_t)2 * n * D}, {&h->ms, (size_t)2 * n * D},
-                           {&h->mrt, inv_diag ? (size_t)2 * n * D : 16}});
+                          {{&h->mx, src}, {&h->mp, src}, {&h->mr, vec}, {&h->ms, vec}, {&h->mrt, tilde}});
+    else if (groups == 1)
+        rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
+                          {{&h->mx, src}, {&h->mp, src}, {&h->mr, vec}, {&h->ms, vec}, {&h->mrt, tilde}, {&h->mst, tilde}}, 2);
     else
         rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
-                          {{&h->mx, (size_t)2 * ne * D}, {&h->mp, (size_t)2 * ne * D}, {&h->mr, (size_t)2 * n * D}, {&h->ms, (size_t)2 * n * D},
-                           {&h->mrt, inv_diag ? (size_t)2 * n * D : 16}, {&h->mst, inv_diag ? (size_t)2 * n * D : 16}}, 2);
+                          {{&h->mx, src}, {&h->mp, src}, {&h->mr, vec}, {&h->ms, vec}, {&h->mrt, tilde}, {&h->mst, pr ? tilde : 16},
+                           {&h->mx1, src}, {&h->mp1, src}, {&h->mr1, vec}, {&h->ms1, vec}, {&h->mrt1, tilde}, {&h->mst1, pr ? tilde : 16},
+                           {&h->partA1, part}, {&h->partB1, part}}, (pr ? 2 : 1) * 2);
     if (rc) return rc;
     h->rhs2 = true;
+    h->groups = groups;
+    h->spmm4 = groups == 2 && spmm4_one_launch(h);
     std::vector<double> pairs;
     try { pairs.resize((size_t)2 * n); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "prcg_solve_begin_multi: host staging"); }
-    for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = x0[0][i]; pairs[2 * i + 1] = x0[1][i]; }
-    if ((rc = h2d(h, h->mx.d(), pairs.data(), 2 * n))) return rc;
-    for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = b[0][i]; pairs[2 * i + 1] = b[1][i]; }
-    if ((rc = h2d(h, h->mr.d(), pairs.data(), 2 * n))) return rc;
+    for (int g = 0; g < groups; ++g) {
+        const PairGroup G = pair_group(h, g);
+        for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = x0[2 * g][i]; pairs[2 * i + 1] = x0[2 * g + 1][i]; }
+        if ((rc = h2d(h, G.x->d(), pairs.data(), 2 * n))) return rc;
+        for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = b[2 * g][i]; pairs[2 * i + 1] = b[2 * g + 1][i]; }
+        if ((rc = h2d(h, G.r->d(), pairs.data(), 2 * n))) return rc;
+    }
     hipStream_t sc = h->sc;
-    // r = b - A x0 for both columns (hs_cg.py:23): one two-vector product of [x0_0 x0_1], parked in S
-    LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->mx.d(), h->ms.d(), 3));
-    launch_sub(sc, h->mr.d(), 1, h->mr.d(), 1, h->ms.d(), 1, 2 * n);
+    // r = b - A x0 for every column (hs_cg.py:23): one product of [x0_0 x0_1] (| [x0_2 x0_3]), parked in S
+    if (groups == 2) LAUNCHCHK(h, eng_spmm4(h, sc, 0, h->mx.d(), h->mx1.d(), h->ms.d(), h->ms1.d()));
+    else LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->mx.d(), h->ms.d(), 3));
+    for (int g = 0; g < groups; ++g) {
+        const PairGroup G = pair_group(h, g);
+        launch_sub(sc, G.r->d(), 1, G.r->d(), 1, G.s->d(), 1, 2 * n);
+    }
     if (pr2(h)) {
-        const Pr2Args pa = pr2_args(h, 0);
-        const int g0 = launch_pr2_init_dots(sc, pa);                         // (r~ = d r); nu = r~.r, r.r   pr_cg.py:108-109
-        LAUNCHCHK(h, g0);
-        launch_copy(sc, h->mp.d(), 1, h->prec ? h->mrt.d() : h->mr.d(), 1, 2 * n);   // p = r~ (r)   :110
-        if ((rc = pr2_product_and_sums(h, 0, pa, g0))) return rc;            // s = A p, (s~ = d s), mu, dl, gm   :111-116
+        int g0[2] = {0, 0};
+        for (int g = 0; g < groups; ++g) {
+            const PairGroup G = pair_group(h, g);
+            g0[g] = launch_pr2_init_dots(sc, pr2_args(h, 0, g));             // (r~ = d r); nu = r~.r, r.r   pr_cg.py:108-109
+            LAUNCHCHK(h, g0[g]);
+            launch_copy(sc, G.p->d(), 1, h->prec ? G.rt->d() : G.r->d(), 1, 2 * n);   // p = r~ (r)   :110
+        }
+        if ((rc = pr2_product_and_sums(h, 0, g0))) return rc;                // s = A p, (s~ = d s), mu, dl, gm   :111-116
         HIPCHK(h, hipStreamSynchronize(sc));
         h->in_session = true;
         return PRCG_OK;
     }
-    Hs2Args a = hs2_args(h, 0);
-    const int g1 = launch_hs2_init_dots(sc, a);                              // (r~ = d r); nu = r.r~, r.r   :25 / :86-88
-    LAUNCHCHK(h, g1);
-    launch_reduce_final(sc, h->partA.d(), g1, dots_at(h, 0), kHs2Nu, kHs2Nu, 4);
-    launch_copy(sc, h->mp.d(), 1, h->prec ? h->mrt.d() : h->mr.d(), 1, 2 * n);   // p = r~ (r)   :24 / :87
-    if ((rc = hs2_product_and_mu(h, 0, a))) return rc;                       // s = A p, mu = p.s   :26-27
+    for (int g = 0; g < groups; ++g) {
+        const PairGroup G = pair_group(h, g);
+        const Hs2Args a = hs2_args(h, 0, g);
+        const int g1 = launch_hs2_init_dots(sc, a);                          // (r~ = d r); nu = r.r~, r.r   :25 / :86-88
+        LAUNCHCHK(h, g1);
+        launch_reduce_final(sc, a.partials, g1, dots_at(h, G.row0), kHs2Nu, kHs2Nu, 4);
+        launch_copy(sc, G.p->d(), 1, h->prec ? G.rt->d() : G.r->d(), 1, 2 * n);   // p = r~ (r)   :24 / :87
+    }
+    if ((rc = hs2_product_and_mu(h, 0))) return rc;                          // s = A p, mu = p.s   :26-27
     HIPCHK(h, hipStreamSynchronize(sc));
     h->in_session = true;
     return PRCG_OK;
 }
 
+// (column j of a four-RHS session: column j % 2 of pair group j / 2 -- per column what a two-RHS session returns)
 #define NEED_RHS2(h, name, j)                                                                                        \
     do {                                                                                                              \
         CHECK(h, (h)->in_session && (h)->rhs2, name ": no open two-RHS session (prcg_solve_begin_multi)");             \
-        CHECK(h, (j) == 0 || (j) == 1, name ": right-hand side %d out of range (0, 1)", (int)(j));                      \
+        CHECK(h, (j) >= 0 && (j) < 2 * (h)->groups, (h)->groups == 2 ? name ": right-hand side %d out of range (0 .. 3)"  \
+                                                                    : name ": right-hand side %d out of range (0, 1)", (int)(j)); \
     } while (0)
 
 int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out) {
     if (!h) return PRCG_EINVAL;
     NEED_RHS2(h, "prcg_get_vector_rhs", j);
     CHECK(h, out, "prcg_get_vector_rhs: null buffer");
-    const DevBuf* src = which == PRCG_VEC_X ? &h->mx : which == PRCG_VEC_R ? &h->mr : which == PRCG_VEC_P ? &h->mp :
-                        which == PRCG_VEC_S ? &h->ms : (which == PRCG_VEC_RT && h->prec) ? &h->mrt :
-                        (which == PRCG_VEC_ST && h->prec && pr2(h)) ? &h->mst : nullptr;
+    const PairGroup G = pair_group(h, j / 2);
+    const DevBuf* src = which == PRCG_VEC_X ? G.x : which == PRCG_VEC_R ? G.r : which == PRCG_VEC_P ? G.p :
+                        which == PRCG_VEC_S ? G.s : (which == PRCG_VEC_RT && h->prec) ? G.rt :
+                        (which == PRCG_VEC_ST && h->prec && pr2(h)) ? G.st : nullptr;
     CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the two-RHS session (x, r, p, s; rt with Jacobi; st with Jacobi "
                   "in a PRCG_PR / PRCG_M session)", which);
     int rc = prcg_sync(h);
     if (rc) return rc;
-    launch_copy(h->sc, h->t1.d(), 1, src->d() + j, 2, h->n);
+    launch_copy(h->sc, h->t1.d(), 1, src->d() + j % 2, 2, h->n);
     return d2h(h, out, h->t1.d(), h->n);
 }
 
@@ -2723,7 +2841,9 @@ int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out) {
     int rc = prcg_sync(h);
     if (rc) return rc;
     double row[kNS];
-    if ((rc = d2h(h, row, dots_at(h, pr2(h) ? 2 * k + j : k), kNS))) return rc;
+    const int row0 = pair_group(h, j / 2).row0;
+    j %= 2;
+    if ((rc = d2h(h, row, dots_at(h, row0 + (pr2(h) ? 2 * k + j : k)), kNS))) return rc;
     for (int q = 0; q < kNS; ++q) out[q] = 0.0;
     if (pr2(h)) {
         for (int q = 0; q <= PRCG_S_RR; ++q) out[q] = row[q];         // mu, dl, gm, nu, rr: the column's own row
@@ -2740,7 +2860,9 @@ int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out) {
     int rc = prcg_sync(h);
     if (rc) return rc;
     double row[kCoefStride];
-    if ((rc = d2h(h, row, coef_at(h, pr2(h) ? 2 * k + j : k), kCoefStride))) return rc;
+    const int row0 = pair_group(h, j / 2).row0;
+    j %= 2;
+    if ((rc = d2h(h, row, coef_at(h, row0 + (pr2(h) ? 2 * k + j : k)), kCoefStride))) return rc;
     if (pr2(h)) { out[0] = row[0]; out[1] = row[1]; out[2] = row[2]; return PRCG_OK; }     // a, b, the predicted nu
     out[0] = row[2 * j]; out[1] = row[2 * j + 1]; out[2] = 0.0;      // Hestenes-Stiefel predicts no nu
     return PRCG_OK;
@@ -2756,7 +2878,8 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist) {
     const int m = h->max_iter;
     const int rows = pr2(h) ? 2 : 1;
     std::vector<double> all((size_t)(m + 1) * rows * kNS);
-    if ((rc = d2h(h, all.data(), h->dots.d(), (int64_t)(m + 1) * rows * kNS))) return rc;
+    if ((rc = d2h(h, all.data(), dots_at(h, pair_group(h, j / 2).row0), (int64_t)(m + 1) * rows * kNS))) return rc;
+    j %= 2;
     for (int k = 0; k < m; ++k) {
         const double rr = pr2(h) ? all[(size_t)(2 * k + j) * kNS + PRCG_S_RR] : all[(size_t)k * kNS + kHs2Rr + 2 * j];
         hist[k] = k <= h->k ? std::sqrt(rr) : 0.0;

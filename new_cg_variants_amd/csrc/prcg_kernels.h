@@ -287,6 +287,10 @@ int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int n
                      const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu);
 int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
                       int per_cu);
+// [dst0 | dst1] = A [src0 | src1] for two pair arrays in ONE walk of the operator (four right-hand sides in one session): sources
+// (n + g) x 2 with the spare entries of every product source, destinations n x 2; per column the bits of launch_sell_spmm2
+int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
+                      double* dst0, double* dst1, int per_cu);
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu);
 
 // ---- small systems: the whole pipelined solve in one launch of one workgroup -------------

@@ -1011,6 +1011,7 @@ const OptionDef kOptions[] = {
     OPT("PRCG_WIN_SWEEP", o.want_sweep = (v >= 0 && v <= 2) ? (int)v : 1),
     OPT("PRCG_SWEEP_WAVES", o.sweep_max_waves = (v >= 64 && v <= 16384) ? (int)v : 6144),
     OPT("PRCG_XP_DEFER", o.want_xp_defer = v != 0),
+    OPT("PRCG_SPMM4", o.want_spmm4 = v != 0),
 };
 #undef OPT
 const int kNumOptions = (int)(sizeof kOptions / sizeof kOptions[0]);

@@ -203,6 +203,7 @@ struct Options {
     int want_pr_pack = -1;               // PRCG_PR_PACK=0|1; default: pattern-tile operators only (S2: +7.6 %; S3 +-0; S2 with plain values -12 %)
     bool want_cg_one = true;             // PRCG_CG_ONE=0: Chronopoulos-Gear / Ghysels-Vanroose keep the two-launch schedule
     int stream_override = -1;            // PRCG_STREAM_STORES=0|1 (default: by operator size, plan_operator)
+    bool want_spmm4 = true;              // PRCG_SPMM4=0: the product of a four-RHS session (prcg_spmm4) is always two two-vector launches
     bool want_xp_defer = true;           // PRCG_XP_DEFER=0: every one-launch pipelined iteration stores (x,p) itself
     int want_fused_comm_rccl = 0;        // PRCG_FUSED_COMM=1: one launch per iteration with the RCCL all-gather chain on the communication
                                          // stream (in-kernel wait for kernels of another stream: validated with one rank only -- opt-in)

@@ -77,10 +77,20 @@ __device__ __forceinline__ int2 slice_row(const SellDev& A, const SDesc& d, int 
     return reinterpret_cast<const int2*>(A.rows)[d.rows_off + lane];
 }
 
+// row result of the four-vector product: one 16-byte store into each destination pair array
+__device__ __forceinline__ void store_two_pairs(int row, const double4& sum, void* __restrict__ y0, double* __restrict__ y1) {
+    reinterpret_cast<double2*>(y0)[row] = make_double2(sum.x, sum.y);
+    reinterpret_cast<double2*>(y1)[row] = make_double2(sum.z, sum.w);
+}
+
 // The wave's memory counter retires in issue order as far as a wait can tell: a wait for ANY load is a wait for everything
 // issued before it.  Order of a trip: the next trip's stream loads first, then this trip's gathers two codes at a time -- the
 // first gather wait is a wait for the whole next trip.  (Gathers first, or the fused iteration's row stores deferred into the
 // next slice, measured no faster: r04_sweeps.md B.)
+//
+// NV = 4 (plain epilogue only): [S0 S1 | S2 S3] = A [P0 P1 | P2 P3] for TWO pair arrays in one walk of the operator -- the
+// second pair's source arrives in ep_r and its destination in ep_st (the plain epilogue uses neither); the lane multiplies
+// every stored value by the four operands and adds left to right, so each column carries the bits of the NV = 2 product.
 template <int NV, int EPI, bool NT, int RUN>
 __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     SellDev A, const int4* __restrict__ slices, int nslices,
@@ -88,8 +98,11 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     const double* __restrict__ ep_r, const double* __restrict__ ep_d, double* __restrict__ ep_st,
     double* __restrict__ partials, double* __restrict__ aux, FusedPrev fz)
 {
+    static_assert(NV != 4 || EPI == kEpiNone, "the four-vector product has the plain epilogue only");
     using V = typename VecT<NV>::type;
     const V* __restrict__ X = reinterpret_cast<const V*>(xin_);
+    const double2* __restrict__ XA = reinterpret_cast<const double2*>(xin_);      // NV = 4: the two source pair arrays
+    const double2* __restrict__ XB = reinterpret_cast<const double2*>(ep_r);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
@@ -188,7 +201,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
 #elif defined(PRCG_SELL_DIAG_NOGATHER)      // TIMING ONLY (wrong products): every gather hits the same 64 entries -- what the kernel costs without gather misses
                     g[k] = X[d.cbase + (c0 & 63)];
 #else
-                    g[k] = X[c0];                                           // (padding positions stay at the row's last column, a skip lands between
+                    if constexpr (NV == 4) g[k] = two_pairs(XA[c0], XB[c0]);
+                    else g[k] = X[c0];                                      // (padding positions stay at the row's last column, a skip lands between
                                                                             //  two of the row's columns: valid entries, never used)
 #endif
                 }
@@ -208,6 +222,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
 #else
             if (active) fused_row_update<epi_prec(EPI), epi_recompute(EPI)>(row, sum, q, own, fr, cf, acc);
 #endif
+        } else if constexpr (NV == 4) {
+            if (active) store_two_pairs(row, sum, yout_, ep_st);
         } else {
             if (active) finish_row<NV, EPI>(row, sum, yout_, write_mask, X, ep_r, ep_d, ep_st, acc, cf, fr);
         }
@@ -237,11 +253,19 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
 // wait counts at a join assume the path without it).
 // PAGES = 12 or 16 wave-wide page loads per slice (48 or 64 granules: SellPlan::window decides; the window lives in dynamic LDS,
 // 4 waves x PAGES x 1 KB for pairs).
+//
+// NV = 4 (plain epilogue only; operands as in k_sell_tiles): the wave keeps TWO windows of pairs, one per source array, under the
+// same codes -- 4 waves x PAGES x 2 KB, 96 KB (12 pages) or 128 KB (16 pages) of the CU's 160 KiB: one workgroup per CU.  Both
+// arrays' pages of the next slice are requested together, a slice ahead, and sit in 2 PAGES page registers (above 256 VGPRs with
+// RUN = 3: one wave per SIMD either way).  PRCG_SELL_WIN4_PARKED (a build for the comparison in profiles/multi_rhs4.md) keeps
+// PAGES page registers instead: the second array's pages of THIS slice are requested at its head, after the first array's are in
+// LDS, and parked in turn -- their latency is not covered by the previous slice's walk.
 
 // (pages and window entries as native vectors: arrays of the HIP double2 class that live across the slice loop stay in scratch memory)
 template <int NV> struct PageT;
 template <> struct PageT<1> { using type = double; };
 template <> struct PageT<2> { using type = d2_t; };
+template <> struct PageT<4> { using type = d2_t; };      // two windows of pairs, one per source pair array
 __device__ __forceinline__ double from_page(double w) { return w; }
 __device__ __forceinline__ double2 from_page(d2_t w) { return make_double2(w.x, w.y); }
 
@@ -267,10 +291,18 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     const V* __restrict__ X = reinterpret_cast<const V*>(xin_);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    static_assert(NV != 4 || EPI == kEpiNone, "the four-vector product has the plain epilogue only");
     using PV = typename PageT<NV>::type;
     const PV* __restrict__ XPG = reinterpret_cast<const PV*>(xin_);
+    const PV* __restrict__ XPG1 = reinterpret_cast<const PV*>(ep_r);       // NV = 4: the second source pair array
     extern __shared__ __align__(16) unsigned char sell_smem[];
-    PV* const win = reinterpret_cast<PV*>(sell_smem) + wv * (PAGES * 64);
+    PV* const win = reinterpret_cast<PV*>(sell_smem) + wv * (PAGES * 64 * (NV == 4 ? 2 : 1));
+    PV* const win1 = win + PAGES * 64;                                     // NV = 4: its window
+#if defined(PRCG_SELL_WIN4_PARKED)
+    constexpr bool kBoth = false;
+#else
+    constexpr bool kBoth = NV == 4;
+#endif
 
     double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     Coefs cf = {0.0, 0.0, 0.0};
@@ -301,11 +333,14 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     constexpr int TP = 8 * RUN;
     Trip<RUN> cur, nxt;
     PV pg[PAGES];
+    PV pg1[kBoth ? PAGES : 1];
     // granule starts of a slice, lane g <- granule g (clamped); a page load: lane l reads entry l % 16 of granule 4 j + l / 16
     auto granule_starts = [&](const SDesc& s) { const int ng = s.flags >> 8; return A.gran[s.cbase + (lane < ng ? lane : ng > 0 ? ng - 1 : 0)]; };   // (a slice of empty rows has none)
     SDesc d = read_sdesc(slices, t);
     SDesc dn = t + W < nslices ? read_sdesc(slices, t + W) : d;
-    request_pages<PV, PAGES>(XPG, d.flags >> 8, granule_starts(d), lane, pg);
+    int gbc = granule_starts(d);                          // the granule starts of the CURRENT slice (NV = 4, parked: used again at its head)
+    request_pages<PV, PAGES>(XPG, d.flags >> 8, gbc, lane, pg);
+    if constexpr (kBoth) request_pages<PV, PAGES>(XPG1, d.flags >> 8, gbc, lane, pg1);
     int gbn = granule_starts(dn);
     load_trip<NT, RUN>(A, d, 0, lane, cur);
     int2 rl = slice_row(A, d, lane);
@@ -317,8 +352,15 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
         // this slice's window; then everything the next slices need
 #pragma unroll
         for (int j = 0; j < PAGES; ++j) win[64 * j + lane] = pg[j];
+        if constexpr (NV == 4) {
+            if constexpr (!kBoth) request_pages<PV, PAGES>(XPG1, d.flags >> 8, gbc, lane, pg);
+#pragma unroll
+            for (int j = 0; j < PAGES; ++j) win1[64 * j + lane] = kBoth ? pg1[j] : pg[j];
+            gbc = gbn;
+        }
         wave_lds_sync();
         request_pages<PV, PAGES>(XPG, dn.flags >> 8, gbn, lane, pg);
+        if constexpr (kBoth) request_pages<PV, PAGES>(XPG1, dn.flags >> 8, gbn, lane, pg1);
         const SDesc dnn = t + 2 * W < nslices ? read_sdesc(slices, t + 2 * W) : dn;
         gbn = granule_starts(dnn);
         rl = slice_row(A, dn, lane);
@@ -345,7 +387,11 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
             for (int k2 = 0; k2 < 8; k2 += 2) {
                 V g[2 * RUN];
 #pragma unroll
-                for (int k = 0; k < 2 * RUN; ++k) g[k] = from_page(win[code[k2 + k / RUN] + k % RUN]);
+                for (int k = 0; k < 2 * RUN; ++k) {
+                    const int e = code[k2 + k / RUN] + k % RUN;
+                    if constexpr (NV == 4) g[k] = two_pairs(from_page(win[e]), from_page(win1[e]));
+                    else g[k] = from_page(win[e]);
+                }
 #pragma unroll
                 for (int k = 0; k < 2 * RUN; ++k) {
                     const int pos = k2 * RUN + k;
@@ -359,6 +405,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
         wave_lds_sync();                                                     // (the window is rewritten at the head of the next slice)
         if constexpr (epi_fused(EPI)) {
             if (active) fused_row_update<epi_prec(EPI), epi_recompute(EPI)>(row, sum, q, own, fr, cf, acc);
+        } else if constexpr (NV == 4) {
+            if (active) store_two_pairs(row, sum, yout_, ep_st);
         } else {
             if (active) finish_row<NV, EPI>(row, sum, yout_, write_mask, X, ep_r, ep_d, ep_st, acc, cf, fr);
         }
@@ -432,7 +480,9 @@ int launch_sell(hipStream_t st, const SellDev& A, const void* slices, int nslice
             static std::mutex mu;
             std::lock_guard<std::mutex> lk(mu);
             if (!raised[reinterpret_cast<const void*>(kw)]) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+                // (the four-vector windows of 16 pages need 128 KB)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kw), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(NV == 4 ? lds : 96 * 1024));
                 raised[reinterpret_cast<const void*>(kw)] = true;
             }
         }
@@ -471,6 +521,13 @@ int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int 
 {
     if (nslices <= 0) return 0;
     return launch_sell<2, kEpiNone>(st, A, slices, nslices, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, FusedPrev{}, per_cu);
+}
+
+int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
+                      double* dst0, double* dst1, int per_cu)
+{
+    if (nslices <= 0) return 0;
+    return launch_sell<4, kEpiNone>(st, A, slices, nslices, src0, dst0, 3, src1, nullptr, dst1, nullptr, nullptr, FusedPrev{}, per_cu);
 }
 
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu)

@@ -162,6 +162,16 @@ class DeviceCSR:
         self._check(self._lib.prcg_spmm2(self._h, L.ptr(RS), L.ptr(WU), int(reps), C.byref(ms)))
         return WU, ms.value
 
+    def matmat4(self, X, reps=1):
+        """[y0 y1 y2 y3] = A [x0 x1 x2 x3] for an (n,4) array, on the route a four-RHS session takes (prcg.h: prcg_spmm4): one
+        launch on sliced-row operators, else two two-vector launches; returns ((n,4) array, mean ms per product)."""
+        X = L.f64(X)
+        assert X.shape == (self.n, 4)
+        Y = np.empty((self.n, 4))
+        ms = C.c_double(0.0)
+        self._check(self._lib.prcg_spmm4(self._h, L.ptr(X), L.ptr(Y), int(reps), C.byref(ms)))
+        return Y, ms.value
+
     # -- solver session ------------------------------------------------------------------------
     def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None, block_jacobi=None):
         """inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
@@ -211,19 +221,22 @@ class DeviceCSR:
         self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
 
     def begin_multi(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
-        """Two right-hand sides in ONE session (prcg.h: prcg_solve_begin_multi): B, X0 of shape (2, n),
-        row j = right-hand side / start vector of system j.  Every iteration streams the operator once for both systems.
+        """Two or four right-hand sides in ONE session (prcg.h: prcg_solve_begin_multi): B, X0 of shape (2, n) or (4, n), both
+        the same, row j = right-hand side / start vector of system j.  Every iteration streams the operator once for all systems
+        (four systems: in one launch on sliced-row operators, see schedule()['spmm4']).
         variant: L.HS (hs_cg / hs_pcg), L.PR (pr_cg / pr_pcg) or L.M (m_cg / m_pcg); inv_diag: Jacobi on the device (the same
         diagonal for both); hist_mask: 0 or updated_residual_2_norm.
         iterate / sync / k serve the session as they are; state is read per column: get_vector(name, rhs=j), get_scalars(k, rhs=j),
         get_coefficients(k, rhs=j), history(rhs=j)."""
-        B, X0 = _pair_of_vectors('B', B, self.n), _pair_of_vectors('X0', X0, self.n)
+        B = _pair_of_vectors('B', B, self.n)
+        X0 = _pair_of_vectors('X0', X0, self.n, nrhs=B.shape[0])
+        nrhs = B.shape[0]
         dv = None if inv_diag is None else L.f64(inv_diag)
         if dv is not None and dv.shape != (self.n,):
             raise ValueError(f'begin_multi: inv_diag must have shape ({self.n},), got {dv.shape}')
-        bp = (C.c_void_p * 2)(B[0].ctypes.data, B[1].ctypes.data)
-        xp = (C.c_void_p * 2)(X0[0].ctypes.data, X0[1].ctypes.data)
-        self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), 2, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
+        bp = (C.c_void_p * nrhs)(*[B[j].ctypes.data for j in range(nrhs)])
+        xp = (C.c_void_p * nrhs)(*[X0[j].ctypes.data for j in range(nrhs)])
+        self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), nrhs, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def set_replace_hook(self, fn):
@@ -262,7 +275,8 @@ class DeviceCSR:
                 'col_bytes': 0 if s & 65536 else (1 if s & 64 else (2 if s & 128 else 4)), 'tile_steps': (s >> 8) & 15,
                 'pattern': bool(s & 65536), 'window': bool(s & 4096), 'fused_comm': bool(s & 8192), 'peer': bool(s & 16384), 'sliced_rows': bool(s & 32768),
                 'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152),
-                'block_jacobi': bool(s & 4194304), 'xp_deferred': bool(s & 8388608), 'rhs2': bool(s & 16777216)}
+                'block_jacobi': bool(s & 4194304), 'xp_deferred': bool(s & 8388608), 'rhs2': bool(s & 16777216),
+                'rhs4': bool(s & 33554432), 'spmm4': bool(s & 67108864)}
 
     def layout(self):
         """Diagnostic (prcg.h: prcg_debug_layout): what the summation order of the one-launch iteration's inner
@@ -283,7 +297,7 @@ class DeviceCSR:
         self._check(self._lib.prcg_set_iteration(self._h, int(k)))
 
     def get_vector(self, name, *, rhs=None):
-        """rhs=j: column j of a two-RHS session (begin_multi): x, r, p, s; with Jacobi rt, and in an L.PR / L.M session st."""
+        """rhs=j: column j of a two- or four-RHS session (begin_multi): x, r, p, s; with Jacobi rt, and in an L.PR / L.M session st."""
         out = np.empty(self.n)
         if rhs is None:
             self._check(self._lib.prcg_get_vector(self._h, L.VEC[name], L.ptr(out)))
@@ -369,11 +383,23 @@ class DeviceCSR:
         return x, {q: hist[i].copy() for i, q in enumerate(names)}, t.as_dict()
 
 
-def _pair_of_vectors(name, V, n):
-    """(2, n) C-contiguous float64, or ValueError: the two-RHS session takes exactly two systems of the operator's size."""
+def multi_rhs_shape_error(name, shape, n, nrhs=None):
+    """None if `shape` is (2, n) or (4, n) -- (nrhs, n) when nrhs is given -- else the text of the ValueError."""
+    if len(shape) == 2 and shape[1] == n and shape[0] in ((2, 4) if nrhs is None else (nrhs,)):
+        return None
+    if nrhs in (2, 4):
+        return (f'{name} must have shape (2, {n}) or (4, {n}), the same as B -- here ({nrhs}, {n}) -- got {tuple(shape)}')
+    return (f'{name} must have shape (2, {n}) or (4, {n}) -- two or four right-hand sides of the operator\'s size -- '
+            f'got {tuple(shape)}')
+
+
+def _pair_of_vectors(name, V, n, nrhs=None):
+    """(2, n) or (4, n) C-contiguous float64 ((nrhs, n) when nrhs is given), or ValueError: the multi-RHS session takes two
+    or four systems of the operator's size."""
     V = L.f64(V)
-    if V.shape != (2, n):
-        raise ValueError(f'{name} must have shape (2, {n}) -- two right-hand sides of the operator\'s size -- got {V.shape}')
+    err = multi_rhs_shape_error(name, V.shape, n, nrhs)
+    if err:
+        raise ValueError(err)
     return V
 
 
