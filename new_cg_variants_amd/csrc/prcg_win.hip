@@ -403,6 +403,59 @@ __device__ __forceinline__ double uniform_double(double v) {       // the same v
     return __hiloint2double(hi, lo);
 }
 
+// ---- the cached row walks: window reads in BATCHES ----
+// A slot of a cached walk is one LDS read and a multiply-add on it.  Issued slot by slot behind a wave-uniform test per
+// slot (`if (u < maxlen)`), every read was a round trip of its own with nothing of the wave in flight beside it: 15 LDS
+// latencies in a row for a 15-diagonal band.  The walks therefore take ONE wave-uniform branch per tile on the slot count
+// (1 ... 16) into straight-line code: the reads of a batch are issued back to back into distinct registers and consumed in
+// slot order behind counted waits (LDS returns in order); the scalar value selects sit between issue and use.  Same
+// products, same left-to-right order, no FMA; a slot the row lacks is never multiplied into the sum.
+// window reads in flight per wave in a uniform walk: four single operands, two operand pairs (16 VGPRs of operands less than the
+// budget of the dictionary kernels leaves; reading all of a row's entries first measured no faster: profiles/row_walk.md A)
+constexpr int walk_batch(int nv) { return nv == 1 ? 4 : 2; }
+// adds p to s in the lanes where `on` holds, branch-free (a lane-predicated `if` costs an execz branch per slot)
+__device__ __forceinline__ void vacc_if(bool on, double& s, double p) { const double t = s + p; s = on ? t : s; }
+__device__ __forceinline__ void vacc_if(bool on, double2& s, double2 p) {
+    const double tx = s.x + p.x, ty = s.y + p.y;
+    s.x = on ? tx : s.x; s.y = on ? ty : s.y;
+}
+// N slots with wave-uniform value and wave-uniform window offset each: sel(u) -> the slot's value (scalar), off(u) -> its
+// window offset (scalar)
+template <int NV, int N, typename Sel, typename Off>
+__device__ __forceinline__ void walk_uniform_slots(typename VecT<NV>::type& sum, const typename VecT<NV>::type* sw, int lane, Sel sel, Off off) {
+    using V = typename VecT<NV>::type;
+    constexpr int B = walk_batch(NV);
+#pragma unroll
+    for (int b0 = 0; b0 < N; b0 += B) {
+        V g[B];
+        double a[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i)
+            if (b0 + i < N) g[i] = sw[off(b0 + i) + lane];
+#pragma unroll
+        for (int i = 0; i < B; ++i)
+            if (b0 + i < N) a[i] = sel(b0 + i);
+#pragma unroll
+        for (int i = 0; i < B; ++i)
+            if (b0 + i < N) vacc(sum, vmul(a[i], g[i]));
+    }
+}
+template <int NV, typename Sel, typename Off>
+__device__ __forceinline__ void walk_uniform(int n, typename VecT<NV>::type& sum, const typename VecT<NV>::type* sw, int lane, Sel sel, Off off) {
+#ifdef PRCG_DEBUG_WALK_SLOTS          // TIMING EXPERIMENT ONLY (wrong products wherever a tile has another slot count): no dispatch at all
+    walk_uniform_slots<NV, PRCG_DEBUG_WALK_SLOTS>(sum, sw, lane, sel, off);
+#else
+#define PRCG_WALK_CASE(N) case N: walk_uniform_slots<NV, N>(sum, sw, lane, sel, off); break;
+    switch (n) {                                                            // wave-uniform: the tile's one branch
+        PRCG_WALK_CASE(1) PRCG_WALK_CASE(2) PRCG_WALK_CASE(3) PRCG_WALK_CASE(4) PRCG_WALK_CASE(5) PRCG_WALK_CASE(6)
+        PRCG_WALK_CASE(7) PRCG_WALK_CASE(8) PRCG_WALK_CASE(9) PRCG_WALK_CASE(10) PRCG_WALK_CASE(11) PRCG_WALK_CASE(12)
+        PRCG_WALK_CASE(13) PRCG_WALK_CASE(14) PRCG_WALK_CASE(15) PRCG_WALK_CASE(16)
+        default: break;     // (0 slots: nothing to add; never more than 16 -- a cached image has maxlen <= RL <= 16, a pattern kPatSlots)
+    }
+#undef PRCG_WALK_CASE
+#endif
+}
+
 // `same_cur`: the tile's index streams, row pointers and dictionary were neither requested nor need parking -- its image
 // is the one the row cache `rc` holds (see RowCache).  Returns whether the tile requested here (dnext) is in that case.
 template <int NV, int EPI, int M, int PG, int CW, bool VD, int RL, bool STASH = false>
@@ -599,45 +652,54 @@ __device__ __forceinline__ bool win_step(const WinDev& A, const WCtx<NV>& c, WRe
             if (cached) {
                 // indices from registers; the value is a select between the table's two entries, or one LDS read
                 const int clen = rc.len[j];
-                if (rc.uni) {
-                    // every lane: a full row, scalar value, window entry lane + scalar offset
-#pragma unroll
-                    for (int u = 0; u < RL; ++u) {
-                        if (u < dcur.maxlen) {                             // wave-uniform
-                            const int cb = (rc.cbase[u >> 2] >> (8 * (u & 3))) & 255;
-                            const double a = ((rc.vmask >> u) & 1u) ? rc.d1 : rc.d0;
-                            const V g = c.sw[cb + lane];
-                            vacc(sum, vmul(a, g));
-                        }
+                bool uniform = false;                                      // (rows can be uniform in the 64-row, 1-byte-index geometry only)
+                if constexpr (M == 1 && CW == 8) {
+                    if (rc.uni) {
+                        // every lane: a full row, scalar value, window entry lane + scalar offset
+                        uniform = true;
+                        walk_uniform<NV>(dcur.maxlen, sum, c.sw, lane,
+                                         [&](int u) { return ((rc.vmask >> u) & 1u) ? rc.d1 : rc.d0; },
+                                         [&](int u) { return (int)((rc.cbase[u >> 2] >> (8 * (u & 3))) & 255u); });
                     }
-                } else if (dcur.vdc <= 2) {
+                }
+                if (!uniform && dcur.vdc <= 2) {
+                    // (four slots under one wave-uniform test: their window reads first, then the lane-predicated adds)
 #pragma unroll
                     for (int q4 = 0; q4 < RL; q4 += 4) {
                         if (q4 < dcur.maxlen) {                            // wave-uniform
+                            V g[4];
+                            double a[4];
 #pragma unroll
                             for (int u = q4; u < q4 + 4; ++u) {
                                 int ci;
                                 if constexpr (CW == 8) ci = (rc.c[j][u >> 2] >> (8 * (u & 3))) & 255; else ci = (rc.c[j][u >> 1] >> (16 * (u & 1))) & 65535;
-                                const int vi = (rc.v[j][u >> 2] >> (8 * (u & 3))) & 255;
-                                const double a = vi ? rc.d1 : rc.d0;
-                                const V g = c.sw[ci];
-                                if (u < clen) vacc(sum, vmul(a, g));
+                                g[u - q4] = c.sw[ci];
                             }
+#pragma unroll
+                            for (int u = q4; u < q4 + 4; ++u) {
+                                const int vi = (rc.v[j][u >> 2] >> (8 * (u & 3))) & 255;
+                                a[u - q4] = vi ? rc.d1 : rc.d0;
+                            }
+#pragma unroll
+                            for (int u = q4; u < q4 + 4; ++u) vacc_if(u < clen, sum, vmul(a[u - q4], g[u - q4]));
                         }
                     }
-                } else {
+                } else if (!uniform) {
 #pragma unroll
                     for (int q4 = 0; q4 < RL; q4 += 4) {
                         if (q4 < dcur.maxlen) {
+                            V g[4];
+                            double a[4];
 #pragma unroll
                             for (int u = q4; u < q4 + 4; ++u) {
                                 int ci;
                                 if constexpr (CW == 8) ci = (rc.c[j][u >> 2] >> (8 * (u & 3))) & 255; else ci = (rc.c[j][u >> 1] >> (16 * (u & 1))) & 65535;
                                 const int vi = (rc.v[j][u >> 2] >> (8 * (u & 3))) & 255;
-                                const double a = c.sd[vi];
-                                const V g = c.sw[ci];
-                                if (u < clen) vacc(sum, vmul(a, g));
+                                a[u - q4] = c.sd[vi];
+                                g[u - q4] = c.sw[ci];
                             }
+#pragma unroll
+                            for (int u = q4; u < q4 + 4; ++u) vacc_if(u < clen, sum, vmul(a[u - q4], g[u - q4]));
                         }
                     }
                 }
@@ -668,25 +730,29 @@ __device__ __forceinline__ bool win_step(const WinDev& A, const WCtx<NV>& c, WRe
             const bool two = (ps.vsel & 0xaaaaaaaau) == 0u;                 // selectors 0 / 1 only
             auto offset_of = [&](int u) { const unsigned w = pcb[u >> 1]; return (u & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu); };
             if (full && two) {
-#pragma unroll
-                for (int u = 0; u < kPatSlots; ++u) {
-                    if (u < ps.nslots) {                                    // wave-uniform
-                        const double a = ((ps.vsel >> (2 * u)) & 1u) ? ps.val[1] : ps.val[0];
-                        const V g = c.sw[offset_of(u) + lane];
-                        vacc(sum, vmul(a, g));
-                    }
-                }
+                walk_uniform<NV>(ps.nslots, sum, c.sw, lane,
+                                 [&](int u) { return ((ps.vsel >> (2 * u)) & 1u) ? ps.val[1] : ps.val[0]; }, offset_of);
             } else {
+                // (four slots under one wave-uniform test: their window reads first, then the lane-predicated adds)
 #pragma unroll
-                for (int u = 0; u < kPatSlots; ++u) {
-                    if (u < ps.nslots) {                                    // wave-uniform
-                        const unsigned sel = (ps.vsel >> (2 * u)) & 3u;
-                        const double a01 = (sel & 1u) ? ps.val[1] : ps.val[0], a23 = (sel & 1u) ? ps.val[3] : ps.val[2];
-                        const double a = (sel & 2u) ? a23 : a01;
-                        int idx = offset_of(u) + lane;
-                        idx = idx < 0 ? 0 : (idx > PG * 64 - 1 ? PG * 64 - 1 : idx);     // lanes without the slot: any valid entry
-                        const V g = c.sw[idx];
-                        if ((mk >> u) & 1u) vacc(sum, vmul(a, g));
+                for (int q4 = 0; q4 < kPatSlots; q4 += 4) {
+                    if (q4 < ps.nslots) {                                   // wave-uniform
+                        V g[4];
+                        double a[4];
+#pragma unroll
+                        for (int u = q4; u < q4 + 4; ++u) {
+                            int idx = offset_of(u) + lane;
+                            idx = idx < 0 ? 0 : (idx > PG * 64 - 1 ? PG * 64 - 1 : idx);     // lanes without the slot: any valid entry
+                            g[u - q4] = c.sw[idx];
+                        }
+#pragma unroll
+                        for (int u = q4; u < q4 + 4; ++u) {
+                            const unsigned sel = (ps.vsel >> (2 * u)) & 3u;
+                            const double a01 = (sel & 1u) ? ps.val[1] : ps.val[0], a23 = (sel & 1u) ? ps.val[3] : ps.val[2];
+                            a[u - q4] = (sel & 2u) ? a23 : a01;
+                        }
+#pragma unroll
+                        for (int u = q4; u < q4 + 4; ++u) vacc_if(u < ps.nslots && ((mk >> u) & 1u), sum, vmul(a[u - q4], g[u - q4]));
                     }
                 }
             }
