@@ -228,6 +228,8 @@ int prcg_iteration(const prcg_t* h);
 #define PRCG_SCHED_RHS2 16777216 /* the session solves TWO right-hand sides (prcg_solve_begin_multi): one two-vector product per iteration */
 #define PRCG_SCHED_RHS4 33554432 /* the session solves FOUR right-hand sides as two pair groups (PRCG_SCHED_RHS2 means exactly two: clear here) */
 #define PRCG_SCHED_SPMM4 67108864 /* ... and its product is ONE four-vector launch (sliced rows; else two two-vector launches) */
+#define PRCG_SCHED_RHS2_PIPE 134217728 /* the two-RHS session is the PIPELINED one (prcg_solve_begin_multi_pipe): PRCG_SCHED_RHS2 is set too, and
+                                       * PRCG_SCHED_SPMM4 says whether its product of four vectors is one launch */
 /* 1048576: retired (was PRCG_SCHED_MEDIUM, the few-workgroup solver of mid-size systems); never to be reused */
 #define PRCG_SCHED_WINDOW 4096  /* row-per-lane window kernels (bands, stencils): the column stream holds indices into the tile's
                                    LDS-staged window of the input vector */
@@ -308,10 +310,35 @@ int prcg_get_history(prcg_t* h, double* hist);
  * return per column what they return in a two-RHS session; the refusals are those of the two-RHS session, word for word. */
 int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
                            int max_iter, const double* inv_diag, uint32_t hist_mask);
-/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi; PRCG_PR / PRCG_M sessions with Jacobi also _ST); out: n_rows host doubles */
+/* ---- pipelined predict-and-recompute with TWO right-hand sides in one session --------------------------------------------
+ * Replaces TWO calls of the reference's pipe_pr_cg (numerical_experiments/cg_variants/pipe_pr_cg.py:89) or pipe_pr_pcg (:201),
+ * of pipe_pr_m_cg (:101) or of pipe_pr_m_pcg (:213) on one matrix.  The pipelined iteration needs [w u] = A [r s] per system;
+ * for two systems that is ONE product of four vectors, [w_0 u_0 | w_1 u_1] = A [r_0 s_0 | r_1 s_1] (what prcg_spmm4 runs: one
+ * launch on sliced-row operators, PRCG_SCHED_SPMM4; else two two-vector launches, the same bits), so every iteration streams
+ * the operator ONCE for both systems.  Each column keeps the single session's state -- the pairs (x,p), (r,s), (w,u) and with
+ * Jacobi (r~,s~); w~ = d w and u~ = d u are formed in registers -- its own a_k, b_k, predicted nu, inner products and history;
+ * nothing of one column enters the other.  An iteration is three steps: one update launch for both columns, one reduction
+ * launch per column, the product.
+ *   variant: PRCG_PIPE_PR or PRCG_PIPE_PR_M (the flavours that recompute w).  nrhs: 2.  b, x0: two pointers to n_rows host
+ *   doubles each.  inv_diag != NULL: pipe_pr_pcg / pipe_pr_m_pcg with Jacobi, the same diagonal for both columns.  hist_mask: 0
+ *   or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.
+ * A new entry, not a case of prcg_solve_begin_multi (which keeps refusing the pipelined variants).  Refused (PRCG_EINVAL, the
+ * text names the reason; an open session stays as it was): PRCG_PIPE_P / PRCG_PIPE_P_M (the stored-w flavours) and every other
+ * variant, nrhs != 2 (an eight-vector product does not exist), a communicator on the handle, n_ghost > 0, a host-callback or
+ * block-Jacobi preconditioner or a replace hook set, another history bit, null b or x0.
+ * prcg_iterate / prcg_sync / prcg_iteration / prcg_set_profiling / prcg_get_timings serve the session as they are; prcg_schedule
+ * reports PRCG_SCHED_RHS2 | PRCG_SCHED_RHS2_PIPE.  State is read per column j = 0, 1 with the calls below -- vectors PRCG_VEC_X,
+ * _R, _P, _S, _W, _U, with Jacobi _RT and _ST; _WT and _UT are refused (never stored); scalars mu, delta, gamma, nu, rr;
+ * coefficients alpha, beta, the predicted nu -- and the single-column accessors are refused while it is open.  A later
+ * prcg_solve_begin or prcg_solve_begin_multi opens an ordinary session again.  Every inner product is summed in one fixed
+ * order: exchanging the two right-hand sides exchanges the two results bit for bit. */
+int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
+                                int max_iter, const double* inv_diag, uint32_t hist_mask);
+/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi; PRCG_PR / PRCG_M sessions with Jacobi also _ST; pipelined sessions: see
+ * prcg_solve_begin_multi_pipe); out: n_rows host doubles */
 int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out);
 /* PRCG_NUM_SCALARS doubles: mu, nu, rr of column j at iteration k in their slots (PRCG_PR / PRCG_M sessions: mu, delta,
- * gamma, nu, rr), every other slot 0 */
+ * gamma, nu, rr; pipelined sessions the same), every other slot 0 */
 int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out);
 /* out[0] = alpha, out[1] = beta used BY iteration k (k >= 1) of column j; out[2] = the predicted nu of iteration k in a
  * PRCG_PR / PRCG_M session, 0 in a Hestenes-Stiefel session (which predicts none) */

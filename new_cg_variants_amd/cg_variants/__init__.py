@@ -325,7 +325,8 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
 
 
 def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
-    """Two or four right-hand sides of one matrix in ONE session of `variant` (L.HS, L.PR, L.M; prcg.h: prcg_solve_begin_multi): what
+    """Two or four right-hand sides of one matrix in ONE session of `variant` (L.HS, L.PR, L.M; prcg.h: prcg_solve_begin_multi; two
+    of L.PIPE_PR, L.PIPE_PR_M: prcg_solve_begin_multi_pipe): what
     two (four) calls of hs_cg / hs_pcg (pr_cg / pr_pcg, m_cg / m_pcg) compute, with the operator streamed once per iteration for all of them.  Every argument is checked before
     the device is touched; what the session does not serve raises ValueError -- nothing falls back to two sessions."""
     if A.format != 'csr':
@@ -337,6 +338,10 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
         if err:
             raise ValueError(f'{name}: {err}')
     nrhs = B.shape[0]
+    pipelined = variant in (L.PIPE_PR, L.PIPE_PR_M)
+    if pipelined and nrhs != 2:
+        raise ValueError(f'{name}: B has shape {tuple(B.shape)}: the pipelined session serves exactly two right-hand sides, shape (2, {n}) '
+                         '(its product is the four-vector one); solve four as two calls')
     for key in ('x_true', 'w_replace'):
         if kwargs.get(key) is not None:
             raise ValueError(f'{name}: {key} is not served by the two-RHS session')
@@ -360,7 +365,10 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
     op = _operator(A, int(kwargs.get('device', 0)))
     op.set_replace_hook(None)
     op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
-    op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    if pipelined:
+        op.begin_multi_pipe(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    else:
+        op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
     outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(nrhs)]
 
     def call_host(k):
@@ -421,6 +429,33 @@ m_cg_multi = _make_multi(L.M, 'm_cg_multi', False)
 m_pcg_multi = _make_multi(L.M, 'm_pcg_multi', True)          # pr_cg.py:172
 
 
+def _make_multi_pipe(variant, name, preconditioned, line):
+    single = name[:-len('_multi')]
+    doc = (f'{single} (pipe_pr_cg.py:{line}) for TWO right-hand sides of one matrix: B, X0 of shape (2, n); returns a list of two trial dicts '
+           f'shaped like {single}\'s.  One pipelined session (prcg.h: prcg_solve_begin_multi_pipe): per iteration one update launch for both '
+           'systems and ONE product of four vectors, so the operator is streamed once for both.  Prefer it where the operator dominates an '
+           'iteration\'s traffic (assembled FEM matrices); on band and stencil operators two calls of the single function, one launch per '
+           'iteration each, may be faster (profiles/multi_rhs_pipe.md).  (4, n) is refused: nothing falls back to two sessions.')
+    if preconditioned:
+        def f(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
+            return _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs)
+        f.__doc__ = doc + '  preconditioner: Jacobi(A), a callable that probes as a diagonal, or None.'
+    else:
+        def f(A, B, X0, max_iter, callbacks=[], **kwargs):
+            if kwargs.pop('preconditioner', None) is not None:
+                raise ValueError(f'{name} takes no preconditioner: use {single[:-2]}pcg_multi')
+            return _run_multi(variant, name, A, B, X0, max_iter, None, callbacks, kwargs)
+        f.__doc__ = doc
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+pipe_pr_cg_multi = _make_multi_pipe(L.PIPE_PR, 'pipe_pr_cg_multi', False, 89)
+pipe_pr_pcg_multi = _make_multi_pipe(L.PIPE_PR, 'pipe_pr_pcg_multi', True, 201)
+pipe_pr_m_cg_multi = _make_multi_pipe(L.PIPE_PR_M, 'pipe_pr_m_cg_multi', False, 101)
+pipe_pr_m_pcg_multi = _make_multi_pipe(L.PIPE_PR_M, 'pipe_pr_m_pcg_multi', True, 213)
+
+
 def _make(variant, name, preconditioned):
     def take_w_replace(kwargs):
         # gv_cg.py:9 / :93 take a residual-replacement predicate (default: never); the other variants swallow the keyword
@@ -463,4 +498,5 @@ pipe_pr_m_pcg = _make(L.PIPE_PR_M, 'pipe_pr_m_pcg', True) # pipe_pr_cg.py:213
 __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr_pcg', 'm_cg', 'm_pcg',
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
-           'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi', 'clear_operator_cache']
+           'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
+           'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache']

@@ -161,6 +161,9 @@ struct Session {
     int groups = 0;              // ... its PAIR GROUPS: 1 with two right-hand sides, 2 with four (group g: columns 2 g, 2 g + 1, a
                                  // complete two-RHS state of its own -- pair_group)
     bool spmm4 = false;          // ... two groups: the product of an iteration is ONE four-vector launch (sliced rows, PRCG_SPMM4)
+    bool pipe2 = false;          // session type "pipelined predict-and-recompute, two right-hand sides" (prcg_solve_begin_multi_pipe):
+                                 // rhs2 with one group, variant PRCG_PIPE_PR / PRCG_PIPE_PR_M, per column the pair arrays cxp, crs, cwu
+                                 // (crst) around ONE product of four vectors (spmm4: in one launch); two scalar / coefficient rows per iteration
     // ---- schedule ----
     bool fused = false;          // pipelined: the one-launch-per-iteration kernel
     bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
@@ -249,6 +252,7 @@ struct prcg_handle : Operator, Session {
     DevBuf mx1, mr1, mp1, ms1, mrt1, mst1;   // four right-hand sides: the same arrays of the SECOND pair group (columns 2, 3) ...
     DevBuf partA1, partB1;                   // ... and its block partials
     DevBuf x4b, y4b;             // prcg_spmm4: the second source / destination pair array (the first: tmp_ext / t1)
+    DevBuf cxp[2], crs[2], cwu[2], crst[2];   // pipelined, two right-hand sides: column c's pairs (x,p), (r,s), (w,u) and with Jacobi (r~,s~) (Pipe2Args)
     DevBuf pub, pub_err;         // publication record of the reduced inner products / timeout flag
     DevBuf q, q2;                // packed predict-and-recompute state (Session::pr_packed)
     DevBuf dots, coef;
@@ -292,7 +296,8 @@ struct prcg_handle : Operator, Session {
     // every vector a window launch may stage (the pointer handed to the launch lies inside one of them)
     const DevBuf* owner(const void* ptr) const {
         const DevBuf* all[] = {&tmp_ext, &t1, &x, &xp, &p, &p2, &rs, &rs2, &rst, &rst2, &wu, &wt, &wv, &r, &r2, &s, &s2, &rt, &rt2,
-                               &st, &st2, &b, &xt, &dinv, &e_ext, &w, &w2, &u, &u2, &tvec, &t2, &ut, &cb_stage, &q, &q2, &mx, &mp, &mx1, &mp1, &x4b};
+                               &st, &st2, &b, &xt, &dinv, &e_ext, &w, &w2, &u, &u2, &tvec, &t2, &ut, &cb_stage, &q, &q2, &mx, &mp, &mx1, &mp1, &x4b,
+                               &crs[0], &crs[1], &crst[0], &crst[1]};
         const char* c = static_cast<const char*>(ptr);
         for (const DevBuf* d : all)
             if (d->p && c >= static_cast<const char*>(d->p) && c < static_cast<const char*>(d->p) + d->bytes) return d;
@@ -923,6 +928,8 @@ void hs_flush(prcg_t* h) {
 // Four right-hand sides are two PAIR GROUPS, each a complete state of this kind (its own arrays, block partials and rows of
 // dots / coef: group g's rows follow group g - 1's max_iter + 1 iterations), around ONE product of both groups' directions.
 bool pr2(const prcg_t* h) { return h->rhs2 && is_pr(h->variant); }
+// the session keeps one scalar and one coefficient row per column and iteration, each in the single-session order
+bool two_rows(const prcg_t* h) { return pr2(h) || h->pipe2; }
 struct PairGroup { DevBuf *x, *r, *p, *s, *rt, *st, *partA, *partB; int row0; };
 PairGroup pair_group(prcg_t* h, int g) {
     const int row0 = g * (h->max_iter + 1) * (pr2(h) ? 2 : 1);
@@ -1020,6 +1027,49 @@ int iterate_pr2(prcg_t* h, int k) {
         prof_end(h, h->ev_upd, h->n_ev_upd, on);
     }
     return pr2_product_and_sums(h, k, g_upd);
+}
+
+// Two right-hand sides in one pipelined predict-and-recompute session (pipe_pr_cg.py:61-75 / :169-187 for each column; the
+// flavours that recompute w): ONE update launch for both columns, one reduction launch per column, ONE product of four vectors
+// [w_0 u_0 | w_1 u_1] = A [r_0 s_0 | r_1 s_1] (with Jacobi of the (r~,s~) pairs) -- the operator is streamed once for both systems.
+Pipe2Args pipe2_args(prcg_t* h, int k) {
+    Pipe2Args a{};
+    a.n = h->n;
+    for (int c = 0; c < 2; ++c) {
+        a.xp[c] = h->cxp[c].d(); a.rs[c] = h->crs[c].d(); a.wu[c] = h->cwu[c].d();
+        a.rst[c] = h->prec ? h->crst[c].d() : nullptr;
+    }
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, 2 * (k - 1)) : nullptr;                // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
+    a.coef_out = coef_at(h, 2 * k);
+    a.part0 = h->partA.d(); a.part1 = h->partB.d();
+    a.meurant = meurant(h->variant);
+    return a;
+}
+// the five sums of each column from the block partials an update (or dots) launch of `grid` blocks left: rows 2 k, 2 k + 1
+void pipe2_reduce(prcg_t* h, int k, int grid) {
+    launch_reduce_final(h->sc, h->partA.d(), grid, dots_at(h, 2 * k), 0, 0, 5);
+    launch_reduce_final(h->sc, h->partB.d(), grid, dots_at(h, 2 * k + 1), 0, 0, 5);
+}
+// (w_c, u_c) = A (r_c, s_c) of both columns (Jacobi: A (r~_c, s~_c)): one launch on sliced rows, else two two-vector launches
+int pipe2_product(prcg_t* h) {
+    DevBuf* src = h->prec ? h->crst : h->crs;
+    LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, src[0].d(), src[1].d(), h->cwu[0].d(), h->cwu[1].d()));
+    return PRCG_OK;
+}
+int iterate_pipe2(prcg_t* h, int k) {
+    const Pipe2Args a = pipe2_args(h, k);
+    bool on = false;
+    prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
+    const int grid = launch_pipe2_update(h->sc, a);
+    LAUNCHCHK(h, grid);
+    prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    pipe2_reduce(h, k, grid);
+    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+    const int rc = pipe2_product(h);
+    if (rc) return rc;
+    prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+    return PRCG_OK;
 }
 
 // hs_cg.py:54-62 (hs_pcg :116-125) on one GPU without reduction launches.  The two inner products still separate
@@ -2494,7 +2544,7 @@ int prcg_iterate(prcg_t* h, int iters) {
                                    "the session's results are invalid -- PRCG_PEER=0 / PRCG_FUSED_COMM=0 select the two-kernel schedule");
     if (h->rhs2) {
         for (int i = 0; i < iters; ++i) {
-            const int rc = pr2(h) ? iterate_pr2(h, h->k + 1) : iterate_hs2(h, h->k + 1);
+            const int rc = h->pipe2 ? iterate_pipe2(h, h->k + 1) : pr2(h) ? iterate_pr2(h, h->k + 1) : iterate_hs2(h, h->k + 1);
             if (rc) return rc;
             ++h->k;
         }
@@ -2582,7 +2632,7 @@ int prcg_schedule(const prcg_t* h) {
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
            (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
            (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) | ((h->rhs2 && h->groups == 1) ? PRCG_SCHED_RHS2 : 0) |
-           (h->groups == 2 ? PRCG_SCHED_RHS4 : 0) | (h->spmm4 ? PRCG_SCHED_SPMM4 : 0) |
+           (h->groups == 2 ? PRCG_SCHED_RHS4 : 0) | (h->spmm4 ? PRCG_SCHED_SPMM4 : 0) | (h->pipe2 ? PRCG_SCHED_RHS2_PIPE : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
            ((h->win ? h->win_vd : h->vd_int) ? PRCG_SCHED_VALDICT : 0) |
            (h->win ? (h->win_pat ? PRCG_SCHED_PATTERN : (h->win_geom < 2 ? PRCG_SCHED_COL8 : PRCG_SCHED_COL16)) | PRCG_SCHED_WINDOW
@@ -2810,6 +2860,71 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     return PRCG_OK;
 }
 
+// ---- two right-hand sides in one pipelined predict-and-recompute session (PRCG_PIPE_PR, PRCG_PIPE_PR_M) ----
+int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
+                                const double* inv_diag, uint32_t hist_mask) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, variant != PRCG_PIPE_P && variant != PRCG_PIPE_P_M, "prcg_solve_begin_multi_pipe: variant %d: the stored-w flavours (PRCG_PIPE_P, "
+          "PRCG_PIPE_P_M) are not served: the pipelined two-RHS session recomputes w = A r in its four-vector product", variant);
+    CHECK(h, pipe_recompute(variant), "prcg_solve_begin_multi_pipe: variant %d: the pipelined two-RHS session serves PRCG_PIPE_PR (pipe_pr_cg / "
+                                      "pipe_pr_pcg) and PRCG_PIPE_PR_M (pipe_pr_m_cg / pipe_pr_m_pcg) only", variant);
+    CHECK(h, nrhs == 2, "prcg_solve_begin_multi_pipe: nrhs = %d: the pipelined session serves exactly 2 right-hand sides (its product is the "
+                        "four-vector one; an eight-vector product does not exist)", nrhs);
+    CHECK(h, !h->multi(), "prcg_solve_begin_multi_pipe: a communicator is set on the handle: the two-RHS session runs on one GPU");
+    CHECK(h, h->g == 0, "prcg_solve_begin_multi_pipe: n_ghost = %lld > 0: the two-RHS session serves whole operators only", (long long)h->g);
+    CHECK(h, h->cb == nullptr, "prcg_solve_begin_multi_pipe: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
+                               "session serves Jacobi (inv_diag) or none");
+    CHECK(h, h->bj_bs == 0, "prcg_solve_begin_multi_pipe: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
+                            "session serves Jacobi (inv_diag) or none");
+    CHECK(h, h->replace_fn == nullptr, "prcg_solve_begin_multi_pipe: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session");
+    CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+          "prcg_solve_begin_multi_pipe: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the two-RHS session");
+    CHECK(h, b && x0 && b[0] && b[1] && x0[0] && x0[1], "prcg_solve_begin_multi_pipe: null b or x0");
+    const int64_t n = h->n, ne = h->n + kGatherPad;
+    const size_t D = sizeof(double);
+    // the pair array that feeds the product -- (r,s), with Jacobi (r~,s~) -- carries the spare entries of every product source
+    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D;
+    int rc = open_session(h, "prcg_solve_begin_multi_pipe", variant, max_iter, hist_mask, inv_diag, false,
+                          {{&h->cxp[0], vec}, {&h->cxp[1], vec}, {&h->crs[0], inv_diag ? vec : src}, {&h->crs[1], inv_diag ? vec : src},
+                           {&h->cwu[0], vec}, {&h->cwu[1], vec}, {&h->crst[0], inv_diag ? src : 16}, {&h->crst[1], inv_diag ? src : 16},
+                           {&h->b, vec}}, 2);
+    if (rc) return rc;
+    h->rhs2 = true;
+    h->groups = 1;
+    h->pipe2 = true;
+    h->spmm4 = spmm4_one_launch(h);
+    std::vector<double> pairs;
+    try { pairs.resize((size_t)2 * n); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "prcg_solve_begin_multi_pipe: host staging"); }
+    for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = x0[0][i]; pairs[2 * i + 1] = x0[1][i]; }
+    if ((rc = h2d(h, h->tmp_ext.d(), pairs.data(), 2 * n))) return rc;
+    for (int64_t i = 0; i < n; ++i) { pairs[2 * i] = b[0][i]; pairs[2 * i + 1] = b[1][i]; }
+    if ((rc = h2d(h, h->b.d(), pairs.data(), 2 * n))) return rc;
+    hipStream_t sc = h->sc;
+    DevBuf* in = h->prec ? h->crst : h->crs;                                  // the product's source pairs
+    // r = b - A x0 of both columns: one two-vector product of [x0_0 x0_1]   (pipe_pr_cg.py:22-23)
+    LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->tmp_ext.d(), h->t1.d(), 3));
+    for (int c = 0; c < 2; ++c) {
+        launch_copy(sc, h->cxp[c].d(), 2, h->tmp_ext.d() + c, 2, n);                       // x = x0
+        launch_sub(sc, h->crs[c].d(), 2, h->b.d() + c, 2, h->t1.d() + c, 2, n);             // r = b - A x
+        if (h->prec) launch_mul(sc, h->crst[c].d(), 2, h->dinv.d(), 1, h->crs[c].d(), 2, n);   // r~ = M^-1 r    :124
+        launch_copy(sc, h->cxp[c].d() + 1, 2, in[c].d(), 2, n);                             // p = r (r~)     :24 / :125
+    }
+    // s = A p: p is r (r~), so the product of the source pairs -- their second halves still zero -- leaves it in w's place
+    if ((rc = pipe2_product(h))) return rc;
+    for (int c = 0; c < 2; ++c) {
+        launch_copy(sc, h->crs[c].d() + 1, 2, h->cwu[c].d(), 2, n);                         // s = A p        :26 / :127
+        if (h->prec) launch_mul(sc, h->crst[c].d() + 1, 2, h->dinv.d(), 1, h->crs[c].d() + 1, 2, n);   // s~ = M^-1 s   :128
+    }
+    // (w, u) = A (r, s) (A (r~, s~)): w = A p again, the bits of `w = s.copy()` (:27 / :129), and u = A w = A s (A s~)   :28 / :131
+    if ((rc = pipe2_product(h))) return rc;
+    const int grid = launch_pipe2_dots(sc, pipe2_args(h, 0));                               // mu, delta, gamma, nu, r.r   :25-36 / :126-140
+    LAUNCHCHK(h, grid);
+    pipe2_reduce(h, 0, grid);
+    HIPCHK(h, hipStreamSynchronize(sc));
+    h->in_session = true;
+    return PRCG_OK;
+}
+
 // (column j of a four-RHS session: column j % 2 of pair group j / 2 -- per column what a two-RHS session returns)
 #define NEED_RHS2(h, name, j)                                                                                        \
     do {                                                                                                              \
@@ -2822,6 +2937,19 @@ int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out) {
     if (!h) return PRCG_EINVAL;
     NEED_RHS2(h, "prcg_get_vector_rhs", j);
     CHECK(h, out, "prcg_get_vector_rhs: null buffer");
+    if (h->pipe2) {
+        // column j's pairs: (x,p), (r,s), (w,u) -- w = A r, u = A s as the iteration's product left them -- and with Jacobi (r~,s~)
+        const double* src = which == PRCG_VEC_X ? h->cxp[j].d() : which == PRCG_VEC_P ? h->cxp[j].d() + 1 :
+                            which == PRCG_VEC_R ? h->crs[j].d() : which == PRCG_VEC_S ? h->crs[j].d() + 1 :
+                            which == PRCG_VEC_W ? h->cwu[j].d() : which == PRCG_VEC_U ? h->cwu[j].d() + 1 :
+                            (which == PRCG_VEC_RT && h->prec) ? h->crst[j].d() : (which == PRCG_VEC_ST && h->prec) ? h->crst[j].d() + 1 : nullptr;
+        CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the pipelined two-RHS session (x, r, p, s, w, u; rt, st with Jacobi; "
+                      "w~ and u~ are formed in registers and never stored)", which);
+        int rc = prcg_sync(h);
+        if (rc) return rc;
+        launch_copy(h->sc, h->t1.d(), 1, src, 2, h->n);
+        return d2h(h, out, h->t1.d(), h->n);
+    }
     const PairGroup G = pair_group(h, j / 2);
     const DevBuf* src = which == PRCG_VEC_X ? G.x : which == PRCG_VEC_R ? G.r : which == PRCG_VEC_P ? G.p :
                         which == PRCG_VEC_S ? G.s : (which == PRCG_VEC_RT && h->prec) ? G.rt :
@@ -2843,9 +2971,9 @@ int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out) {
     double row[kNS];
     const int row0 = pair_group(h, j / 2).row0;
     j %= 2;
-    if ((rc = d2h(h, row, dots_at(h, row0 + (pr2(h) ? 2 * k + j : k)), kNS))) return rc;
+    if ((rc = d2h(h, row, dots_at(h, row0 + (two_rows(h) ? 2 * k + j : k)), kNS))) return rc;
     for (int q = 0; q < kNS; ++q) out[q] = 0.0;
-    if (pr2(h)) {
+    if (two_rows(h)) {
         for (int q = 0; q <= PRCG_S_RR; ++q) out[q] = row[q];         // mu, dl, gm, nu, rr: the column's own row
         return PRCG_OK;
     }
@@ -2862,8 +2990,8 @@ int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out) {
     double row[kCoefStride];
     const int row0 = pair_group(h, j / 2).row0;
     j %= 2;
-    if ((rc = d2h(h, row, coef_at(h, row0 + (pr2(h) ? 2 * k + j : k)), kCoefStride))) return rc;
-    if (pr2(h)) { out[0] = row[0]; out[1] = row[1]; out[2] = row[2]; return PRCG_OK; }     // a, b, the predicted nu
+    if ((rc = d2h(h, row, coef_at(h, row0 + (two_rows(h) ? 2 * k + j : k)), kCoefStride))) return rc;
+    if (two_rows(h)) { out[0] = row[0]; out[1] = row[1]; out[2] = row[2]; return PRCG_OK; }     // a, b, the predicted nu
     out[0] = row[2 * j]; out[1] = row[2 * j + 1]; out[2] = 0.0;      // Hestenes-Stiefel predicts no nu
     return PRCG_OK;
 }
@@ -2876,12 +3004,12 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist) {
     if (rc) return rc;
     if (!(h->hist_mask & PRCG_HIST_UPDATED_RESIDUAL_2_NORM)) return PRCG_OK;
     const int m = h->max_iter;
-    const int rows = pr2(h) ? 2 : 1;
+    const int rows = two_rows(h) ? 2 : 1;
     std::vector<double> all((size_t)(m + 1) * rows * kNS);
     if ((rc = d2h(h, all.data(), dots_at(h, pair_group(h, j / 2).row0), (int64_t)(m + 1) * rows * kNS))) return rc;
     j %= 2;
     for (int k = 0; k < m; ++k) {
-        const double rr = pr2(h) ? all[(size_t)(2 * k + j) * kNS + PRCG_S_RR] : all[(size_t)k * kNS + kHs2Rr + 2 * j];
+        const double rr = two_rows(h) ? all[(size_t)(2 * k + j) * kNS + PRCG_S_RR] : all[(size_t)k * kNS + kHs2Rr + 2 * j];
         hist[k] = k <= h->k ? std::sqrt(rr) : 0.0;
     }
     return PRCG_OK;

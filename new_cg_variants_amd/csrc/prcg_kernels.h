@@ -379,6 +379,22 @@ int launch_pr2_update(hipStream_t st, const Pr2Args& a);      // x, r, (rt), p; 
 int launch_pr2_init_dots(hipStream_t st, const Pr2Args& a);   // ... of the initial state: no update, (rt = d r)
 int launch_pr2_dots(hipStream_t st, const Pr2Args& a);        // (st = d s); partials mu_c, dl_c, gm_c (slots 0..2) of part[c]
 
+// ---- pipelined predict-and-recompute (pipe_pr_cg / pipe_pr_m_cg, with Jacobi pipe_pr_pcg / pipe_pr_m_pcg), TWO right-hand
+// sides in one session (prcg_rhs2.hip; prcg_solve_begin_multi_pipe) ----
+// Column c keeps the single session's 16-byte pairs: xp[c] = (x,p), rs[c] = (r,s), wu[c] = (w,u) and with Jacobi rst[c] =
+// (r~,s~), n pairs each (rs[c] / rst[c], whichever feeds the product, with the spare entries of a product source).  d: the
+// inverse diagonal shared by both columns, or null.  Scalars, coefficients and block partials: the layout of Pr2Args -- row
+// 2 k + c = column c's iteration k, [mu dl gm nu rr - - -] / [a b nu_pred -]; dots_prev, coef_out: column 0's row; part0 /
+// part1: five slots per block.  ONE launch updates both columns; wu is read only (the four-vector product rewrites it).
+struct Pipe2Args {
+    int64_t n;
+    double* xp[2]; double* rs[2]; double* rst[2]; const double* wu[2]; const double* d;
+    const double* dots_prev; double* coef_out; double* part0; double* part1;
+    int meurant;
+};
+int launch_pipe2_update(hipStream_t st, const Pipe2Args& a);   // x, p, r, s, (r~, s~) of both columns; partials mu .. rr (slots 0..4) of part[c]
+int launch_pipe2_dots(hipStream_t st, const Pipe2Args& a);     // the five sums of the state as it stands: no update (initialisation)
+
 struct PrArgs {   // non-pipelined predict-and-recompute (pr_pcg / m_pcg)
     int64_t n;
     double* x; double* r; double* rt; double* p; const double* s; const double* st_;

@@ -1,6 +1,7 @@
 // gfx950 (MI355X / CDNA4): the vector kernels of the session type "Hestenes-Stiefel, two right-hand sides"
 // (prcg_solve_begin_multi; replaces two calls of the reference's hs_cg.py:9 / :70 on one matrix), and below them those of
-// "predict-and-recompute, two right-hand sides" (pr_cg.py:166 / :172; k_pr2_*).
+// "predict-and-recompute, two right-hand sides" (pr_cg.py:166 / :172; k_pr2_*) and of "pipelined predict-and-recompute, two
+// right-hand sides" (prcg_solve_begin_multi_pipe; pipe_pr_cg.py:89 / :201 / :101 / :213; k_pipe2_update).
 //
 // One iteration of the session is  update_xr -> reduce -> update_p -> [p_0 p_1] -> A [p_0 p_1] (the two-vector product
 // every operator family already has) -> dot_ps -> reduce: the operator is streamed ONCE for both systems.
@@ -283,6 +284,112 @@ __global__ __launch_bounds__(kBlock) void k_pr2_dots(Pr2Args a, int trips) {
     block_reduce_store2<3>(acc, a.part0, a.part1, kPr2Mu);
 }
 
+// ---- pipelined predict-and-recompute (pipe_pr_cg.py:89 pipe_pr_cg, :101 pipe_pr_m_cg, :201 / :213 with Jacobi), two right-hand sides ----
+// One iteration is  update (this kernel, BOTH columns) -> one reduction per column -> [w_0 u_0 | w_1 u_1] = A [r_0 s_0 | r_1 s_1],
+// the four-vector product.  The state is NOT interleaved across columns: each column keeps the 16-byte pairs of the single
+// session, XP_c = (x,p), RS_c = (r,s), WU_c = (w,u), with Jacobi RSt_c = (r~,s~) -- RS_c (RSt_c) and WU_c are, as they stand, a
+// source and a destination pair array of the four-vector product.  Only the flavours that recompute w exist here: WU is
+// read and never written, w~ = d w and u~ = d u are formed in registers.
+//
+// Per row and column the expressions of k_pipe_update (prcg_kernels.hip) in its order, multiply then add; column c has its own
+// Coefs and its own five accumulators [mu dl gm nu rr]; a thread's twelve 16-byte loads (two rows x two columns x three arrays;
+// sixteen with Jacobi, and two of d) are issued before any arithmetic.  Sums: the tree described at the head of this file.
+template <bool PREC, bool DOTS_ONLY>
+__global__ __launch_bounds__(kBlock) void k_pipe2_update(Pipe2Args a, int trips) {
+    Coefs cf[2] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    if constexpr (!DOTS_ONLY) {
+        cf[0] = predict(a.dots_prev, a.meurant);
+        cf[1] = predict(a.dots_prev + kPartialStride, a.meurant);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                double* co = a.coef_out + c * kPr2CoefStride;
+                co[0] = cf[c].al; co[1] = cf[c].bt; co[2] = cf[c].nup;
+            }
+        }
+    }
+    double acc[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // column 0's mu, dl, gm, nu, rr; column 1's
+    const int64_t n = a.n;
+    double2* __restrict__ XP[2] = {reinterpret_cast<double2*>(a.xp[0]), reinterpret_cast<double2*>(a.xp[1])};
+    double2* __restrict__ RS[2] = {reinterpret_cast<double2*>(a.rs[0]), reinterpret_cast<double2*>(a.rs[1])};
+    double2* __restrict__ RST[2] = {reinterpret_cast<double2*>(a.rst[0]), reinterpret_cast<double2*>(a.rst[1])};
+    const double2* __restrict__ WU[2] = {reinterpret_cast<const double2*>(a.wu[0]), reinterpret_cast<const double2*>(a.wu[1])};
+    const double* __restrict__ D = a.d;
+
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        // ---- loads of both rows of both columns first ----
+        double2 xp[2][2], rs[2][2], wu[2][2], rst[2][2];
+        double dv[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;               // clamped: branch-free loads
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                xp[c][e] = XP[c][il];
+                rs[c][e] = RS[c][il];
+                if constexpr (!DOTS_ONLY) wu[c][e] = WU[c][il];
+                if constexpr (PREC) rst[c][e] = RST[c][il];
+            }
+            if constexpr (PREC && !DOTS_ONLY) dv[e] = D[il];
+        }
+        // ---- arithmetic + stores, row base then row base + 256 (this order is part of the reduction tree) ----
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (!ok[e]) continue;
+            const int64_t ie = base + e * kBlock;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                double* ac = acc + 5 * c;
+                const double2 xpv = xp[c][e], rsv = rs[c][e];
+                if constexpr (DOTS_ONLY) {
+                    if constexpr (PREC) {
+                        const double2 rstv = rst[c][e];
+                        ac[0] += xpv.y * rsv.y; ac[1] += rsv.x * rstv.y; ac[2] += rstv.y * rsv.y;
+                        ac[3] += rstv.x * rsv.x; ac[4] += rsv.x * rsv.x;
+                    } else {
+                        ac[0] += xpv.y * rsv.y; ac[1] += rsv.x * rsv.y; ac[2] += rsv.y * rsv.y;
+                        ac[3] += rsv.x * rsv.x;
+                    }
+                } else {
+                    const double al = cf[c].al, bt = cf[c].bt;
+                    const double2 wuv = wu[c][e];
+                    const double xn = xpv.x + al * xpv.y;               // x += a p
+                    const double rn = rsv.x - al * rsv.y;               // r -= a s
+                    const double wn = wuv.x - al * wuv.y;               // w -= a u
+                    if constexpr (PREC) {
+                        const double2 rstv = rst[c][e];
+                        const double ut = dv[e] * wuv.y;                // u~ = M^-1 u
+                        const double wtv = dv[e] * wuv.x;               // w~ = M^-1 w
+                        const double rtn = rstv.x - al * rstv.y;        // r~ -= a s~
+                        const double wtn = wtv - al * ut;               // w~ -= a u~
+                        const double pn = rtn + bt * xpv.y;             // p = r~ + b p
+                        const double sn = wn + bt * rsv.y;              // s = w + b s
+                        const double stn = wtn + bt * rstv.y;           // s~ = w~ + b s~
+                        XP[c][ie] = make_double2(xn, pn);
+                        RS[c][ie] = make_double2(rn, sn);
+                        RST[c][ie] = make_double2(rtn, stn);
+                        ac[0] += pn * sn; ac[1] += rn * stn; ac[2] += stn * sn;
+                        ac[3] += rtn * rn; ac[4] += rn * rn;
+                    } else {
+                        const double pn = rn + bt * xpv.y;              // p = r + b p
+                        const double sn = wn + bt * rsv.y;              // s = w + b s
+                        XP[c][ie] = make_double2(xn, pn);
+                        RS[c][ie] = make_double2(rn, sn);
+                        ac[0] += pn * sn; ac[1] += rn * sn; ac[2] += sn * sn; ac[3] += rn * rn;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!PREC) { acc[4] = acc[3]; acc[9] = acc[8]; }      // unpreconditioned: rr IS nu
+    block_reduce_store2<5>(acc, a.part0, a.part1, 0);
+}
+
 }  // namespace
 
 #define PRCG_LAUNCH_OK() (hipGetLastError() == hipSuccess)
@@ -326,6 +433,19 @@ int launch_pr2_dots(hipStream_t st, const Pr2Args& a) {
     const Chunking c = chunking(a.n);
     if (a.d) hipLaunchKernelGGL((k_pr2_dots<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     else     hipLaunchKernelGGL((k_pr2_dots<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+
+int launch_pipe2_update(hipStream_t st, const Pipe2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_pipe2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_pipe2_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_pipe2_dots(hipStream_t st, const Pipe2Args& a) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_pipe2_update<true, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else     hipLaunchKernelGGL((k_pipe2_update<false, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 

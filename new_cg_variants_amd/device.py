@@ -239,6 +239,33 @@ class DeviceCSR:
         self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), nrhs, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
+    def begin_multi_pipe(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
+        """Two right-hand sides in ONE pipelined session (prcg.h: prcg_solve_begin_multi_pipe): B, X0 of shape (2, n), row j =
+        right-hand side / start vector of system j.  Every iteration streams the operator once for both systems: the pipelined
+        iteration's [w u] = A [r s] of both columns is one product of four vectors (one launch on sliced-row operators, see
+        schedule()['spmm4']).
+        variant: L.PIPE_PR (pipe_pr_cg / pipe_pr_pcg) or L.PIPE_PR_M (pipe_pr_m_cg / pipe_pr_m_pcg); inv_diag: Jacobi on the device
+        (the same diagonal for both); hist_mask: 0 or updated_residual_2_norm.  begin_multi keeps refusing the pipelined variants.
+        Which to prefer: this session where the operator dominates an iteration's traffic (assembled FEM matrices, sliced rows);
+        on band and stencil operators two single sessions, each ONE launch per iteration, may well be faster -- see
+        profiles/multi_rhs_pipe.md for what was measured.
+        iterate / sync / k serve the session as they are; state is read per column: get_vector(name, rhs=j) (x, r, p, s, w, u; with
+        Jacobi rt, st), get_scalars(k, rhs=j), get_coefficients(k, rhs=j), history(rhs=j)."""
+        B = L.f64(B)
+        if B.shape != (2, self.n):
+            raise ValueError(f'begin_multi_pipe: B must have shape (2, {self.n}) -- the pipelined session serves exactly two right-hand '
+                             f'sides of the operator\'s size -- got {tuple(B.shape)}')
+        X0 = L.f64(X0)
+        if X0.shape != (2, self.n):
+            raise ValueError(f'begin_multi_pipe: X0 must have shape (2, {self.n}), the same as B, got {tuple(X0.shape)}')
+        dv = None if inv_diag is None else L.f64(inv_diag)
+        if dv is not None and dv.shape != (self.n,):
+            raise ValueError(f'begin_multi_pipe: inv_diag must have shape ({self.n},), got {dv.shape}')
+        bp = (C.c_void_p * 2)(B[0].ctypes.data, B[1].ctypes.data)
+        xp = (C.c_void_p * 2)(X0[0].ctypes.data, X0[1].ctypes.data)
+        self._check(self._lib.prcg_solve_begin_multi_pipe(self._h, int(variant), 2, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
+        self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
+
     def set_replace_hook(self, fn):
         """Ghysels-Vanroose residual replacement (prcg.h: prcg_set_replace_hook): fn(k) -> truthy replaces w by A r in
         iteration k; None removes the hook.  Set before begin()."""
@@ -276,7 +303,7 @@ class DeviceCSR:
                 'pattern': bool(s & 65536), 'window': bool(s & 4096), 'fused_comm': bool(s & 8192), 'peer': bool(s & 16384), 'sliced_rows': bool(s & 32768),
                 'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152),
                 'block_jacobi': bool(s & 4194304), 'xp_deferred': bool(s & 8388608), 'rhs2': bool(s & 16777216),
-                'rhs4': bool(s & 33554432), 'spmm4': bool(s & 67108864)}
+                'rhs4': bool(s & 33554432), 'spmm4': bool(s & 67108864), 'rhs2_pipe': bool(s & 134217728)}
 
     def layout(self):
         """Diagnostic (prcg.h: prcg_debug_layout): what the summation order of the one-launch iteration's inner
@@ -297,7 +324,8 @@ class DeviceCSR:
         self._check(self._lib.prcg_set_iteration(self._h, int(k)))
 
     def get_vector(self, name, *, rhs=None):
-        """rhs=j: column j of a two- or four-RHS session (begin_multi): x, r, p, s; with Jacobi rt, and in an L.PR / L.M session st."""
+        """rhs=j: column j of a two- or four-RHS session (begin_multi): x, r, p, s; with Jacobi rt, and in an L.PR / L.M session st.
+        In a pipelined two-RHS session (begin_multi_pipe) also w and u, and with Jacobi rt and st."""
         out = np.empty(self.n)
         if rhs is None:
             self._check(self._lib.prcg_get_vector(self._h, L.VEC[name], L.ptr(out)))

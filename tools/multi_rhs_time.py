@@ -20,7 +20,14 @@ nrhs=4: FOUR right-hand sides, three legs, the figure is microseconds per iterat
      b  two two-RHS sessions of K iterations each on the same handle, one after the other -- what there was before
      c  the four-RHS session on a second handle with PRCG_SPMM4=0 (two two-vector launches): c against a isolates the kernel
    `knobs=PRCG_SELL_WINDOW:0,...` sets switches on every handle (delta codes instead of window codes, for instance).
-   With nrhs=4, legs=b uses nothing the four-RHS session added and runs against a build without it."""
+   With nrhs=4, legs=b uses nothing the four-RHS session added and runs against a build without it.
+
+variant=pipe_pr | pipe_pr_m (nrhs=2): the PIPELINED predict-and-recompute iteration, three legs, microseconds per iteration OF BOTH SYSTEMS:
+     a  the pipelined two-RHS session (prcg_solve_begin_multi_pipe: one update launch and ONE product of four vectors per iteration)
+     b  two single default sessions of pipe_pr_cg (prec=jacobi: pipe_pr_pcg; pipe_pr_m: pipe_pr_m_cg / pipe_pr_m_pcg) on the same
+        handle, one after the other, each ONE launch per iteration -- what there was before; runs against a build without the session
+     c  the pipelined two-RHS session on a second handle with PRCG_SPMM4=0 (two two-vector launches): c against a isolates the
+        four-vector kernel (profiles/multi_rhs_pipe.md)"""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,10 +42,13 @@ for a in sys.argv[1:]:
         sys.exit(f'unknown argument {a!r}\n{__doc__}')
     opt[k] = v
 repeats, window = int(opt['repeats']), float(opt['window'])
-if opt['nrhs'] not in ('2', '4') or set(opt['legs']) - set('ab' if opt['nrhs'] == '2' else 'abc') or set(opt['prec'].split(',')) - {'none', 'jacobi'} or opt['variant'] not in ('hs', 'pr', 'm'):
+if opt['nrhs'] not in ('2', '4') or set(opt['legs']) - set('ab' if opt['nrhs'] == '2' and not opt['variant'].startswith('pipe') else 'abc') or set(opt['prec'].split(',')) - {'none', 'jacobi'} or opt['variant'] not in ('hs', 'pr', 'm', 'pipe_pr', 'pipe_pr_m'):
     sys.exit(__doc__)
+PIPE = opt['variant'].startswith('pipe')
+if PIPE and opt['nrhs'] != '2':
+    sys.exit('variant=pipe_pr / pipe_pr_m: nrhs=2 only\n' + __doc__)
 MAX_ITER, WARM, CALIB = 6000, 5, 5
-VARIANT = {'hs': L.HS, 'pr': L.PR, 'm': L.M}[opt['variant']]
+VARIANT = {'hs': L.HS, 'pr': L.PR, 'm': L.M, 'pipe_pr': L.PIPE_PR, 'pipe_pr_m': L.PIPE_PR_M}[opt['variant']]
 NRHS = int(opt['nrhs'])
 KNOBS = dict(kv.split(':', 1) for kv in opt['knobs'].split(',') if kv)
 
@@ -82,7 +92,7 @@ for prec in opt['prec'].split(','):
         for leg in opt['legs']:
             o = op_c if leg == 'c' else op
             if leg in 'ac':
-                k, dt = window_of(lambda: o.begin_multi(VARIANT, B, X0, MAX_ITER, inv_diag=d), window, o=o)
+                k, dt = window_of(lambda: (o.begin_multi_pipe if PIPE else o.begin_multi)(VARIANT, B, X0, MAX_ITER, inv_diag=d), window, o=o)
                 finite = finite_nu(o, NRHS)
             elif NRHS == 4:
                 # each two-RHS session half a window: the two sessions are one window of K iterations of all four systems
@@ -100,7 +110,7 @@ for prec in opt['prec'].split(','):
                 dt = dt0 + dt1
             s = o.schedule()
             rec = {'workload': opt['workload'], 'prec': prec, 'leg': leg, 'repeat': rep, 'iterations': k, 'seconds': dt,
-                   'us_per_iteration_of_both': dt / k * 1e6, 'rhs2': s.get('rhs2', False), 'rhs4': s.get('rhs4', False), 'spmm4': s.get('spmm4', False),
+                   'us_per_iteration_of_both': dt / k * 1e6, 'rhs2': s.get('rhs2', False), 'rhs4': s.get('rhs4', False), 'spmm4': s.get('spmm4', False), 'rhs2_pipe': s.get('rhs2_pipe', False),
                    'window_codes': s.get('window_codes', False), 'fused': s['fused'], 'sliced_rows': s['sliced_rows'],
                    'window': s['window'], 'stream_stores': s['stream_stores'], 'finite': finite}
             print('# ' + json.dumps(rec), file=sys.stderr, flush=True)
