@@ -156,6 +156,35 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz,
                  const void* indptr, int indptr_is64,
                  const int32_t* indices, const double* data);
 
+/* New values for the nonzeros of the operator set by prcg_set_csr: same n_rows, nnz, indptr, indices (the caller's
+ * promise -- nothing of the pattern is passed again), data[q] replaces the value of nonzero q in that CSR order.
+ * data_on_device = 0: nnz host doubles.  data_on_device = 1: nnz doubles in device memory of the handle's GPU
+ * (e.g. a torch tensor's data_ptr(); the caller has synchronised whatever wrote them).
+ * Replaces a second prcg_set_csr (a second DeviceCSR(A)) with the same pattern -- the same mesh with new coefficients: Newton
+ * steps, a time-dependent material, a re-assembled stiffness matrix -- and with it the reference's re-assignment of `A`
+ * between calls of `method(A, b, x0, max_iter, ...)` (figure_gen.py:59), which there costs nothing because scipy streams the
+ * CSR arrays as they are.  Which of two routes serves the call depends on the encodings prcg_set_csr chose (prcg_values_route):
+ *   0, in place: no encoding of the operator holds values (no value dictionary, no pattern tiles).  The handle keeps its plan --
+ *      family, tiles, slices, column codes, grids, hence the summation tree of every inner product; the values are copied into
+ *      the caller-order value array on the compute stream once the handle's pending work has finished, and for sliced rows
+ *      one kernel re-lays them (k_sell_set_values).  No host planning; nothing else is touched.  The handle does NOT decide
+ *      again: an operator whose new values would qualify for a value dictionary keeps plain values until the next prcg_set_csr.
+ *   1, re-planned: result and state are those of prcg_set_csr with the new values under the handle's options (the row pointers
+ *      and column indices are read back from the device, no host copy of them is kept) -- a dictionary may fall to plain values,
+ *      pattern tiles to index streams, and back.
+ * On both routes an open session ends (as after prcg_set_csr) while the session buffers stay allocated; options, a
+ * host-callback preconditioner and block-Jacobi blocks stay in force (a frozen preconditioner is legitimate; call
+ * prcg_set_block_jacobi for new blocks).  The call returns after `data` has been read -- the caller may overwrite it -- though
+ * the re-lay kernel may still be enqueued.  nnz == 0: nothing to do.
+ * Refused (PRCG_EINVAL, the text names the reason, the handle is untouched): no operator; null data with nnz > 0; n_ghost > 0,
+ * a communicator or a world size > 1 on the handle (rank-local blocks: set them again with prcg_set_csr); data_on_device
+ * outside 0 / 1; a device pointer the runtime does not report as device memory of the handle's GPU, or with
+ * [data, data + nnz) leaving its allocation -- the library reads no pointer it has not checked. */
+int prcg_update_values(prcg_t* h, const double* data, int data_on_device);
+/* how prcg_update_values serves the operator now on the handle: 0 = in place (no host planning), 1 = re-planned;
+ * -1 without an operator */
+int prcg_values_route(const prcg_t* h);
+
 /* Halo plan (needed iff n_ghost > 0).  Peer q = peer_rank[q]:
  *   send_idx[send_ptr[q] .. send_ptr[q+1])  local rows whose entries peer q needs
  *   ghost slots [recv_ptr[q], recv_ptr[q+1]) receive from peer q, in the peer's send order. */

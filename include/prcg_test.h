@@ -141,6 +141,12 @@ int64_t prcg_plan_sell(int64_t n, const int32_t* indptr, const int32_t* indices,
 int64_t prcg_plan_operator(int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
                            const double* data, const char* const* keys, const char* const* values, int n_options, int64_t* out,
                            int64_t capacity);
+/* The route prcg_update_values would take on a handle holding this operator under these options (the arguments of
+ * prcg_plan_operator without the output array), by the predicate the handle itself evaluates (csrc/prcg_plan.h: values_route):
+ * 0 = in place -- no encoding holds values --, 1 = re-planned (value dictionary or pattern tiles).  -1 on a bad argument, an
+ * unknown option or a column index out of range. */
+int prcg_plan_values_route(int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
+                           const double* data, const char* const* keys, const char* const* values, int n_options);
 /* Merged exchange of the multi-GPU pipelined loop (small halos ride on the one all-gather per
  * iteration): where in the gathered buffer do this rank's ghost rows lie?  `tables`: every rank's
  * send table, doubles_per_table doubles each: [n_peers, (peer, first row of its list, rows)...];

@@ -53,6 +53,8 @@ _SIGNATURES = {
     'prcg_comm_unique_id': (C.c_int, [C.c_char_p, _P]),
     'prcg_comm_init': (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, _P, C.c_int]),
     'prcg_set_csr': (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, _P, _P]),
+    'prcg_update_values': (C.c_int, [_P, _P, C.c_int]),
+    'prcg_values_route': (C.c_int, [_P]),
     'prcg_set_halo': (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     'prcg_peer_setup': (C.c_int, [_P, C.c_int64, _P, C.POINTER(_P)]),
     'prcg_peer_connect': (C.c_int, [_P, _P, _P, _P]),
@@ -93,6 +95,7 @@ _SIGNATURES = {
     'prcg_plan_sell': (C.c_int64, [C.c_int64, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P,
                                     C.c_int64, _P]),
     'prcg_plan_operator': (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int64]),
+    'prcg_plan_values_route': (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int]),
     'prcg_plan_tiles': (C.c_int64, [C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     'prcg_plan_window': (C.c_int64, [C.c_int64, C.c_int64, _P, _P, _P, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int)]),

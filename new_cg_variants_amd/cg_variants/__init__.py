@@ -36,6 +36,7 @@ from ..callbacks import RECORDER_NAMES
 from ..device import DeviceCSR, multi_rhs_shape_error
 
 _OPERATORS = OrderedDict()   # small cache: figure_gen runs nine variants on one matrix
+_PATTERNS = {}               # cache key -> fingerprint of indptr / indices alone (update_values finds an operator by its pattern)
 _MAX_CACHED = 2
 _MAX_DIRECT_SOLVE = 200_000   # largest system solved on the host for a missing x_true (the reference's on-the-fly spsolve)
 
@@ -57,14 +58,25 @@ def _fingerprint(A):
         return c
 
 
+def _pattern_fingerprint(A):
+    """_fingerprint's hash over indptr and indices alone: what stays when only the values of a matrix change."""
+    import zlib
+    c = 0
+    for a in (A.indptr, A.indices):
+        c = zlib.crc32(np.ascontiguousarray(a).data, c)
+    return c
+
+
 def _operator(A, device):
     key = (id(A), A.shape, A.nnz, A.data.__array_interface__['data'][0], device, _fingerprint(A))
     op = _OPERATORS.get(key)
     if op is None:
         op = DeviceCSR(A, device=device)
         _OPERATORS[key] = op
+        _PATTERNS[key] = _pattern_fingerprint(A)
         while len(_OPERATORS) > _MAX_CACHED:
-            _, old = _OPERATORS.popitem(last=False)
+            old_key, old = _OPERATORS.popitem(last=False)
+            _PATTERNS.pop(old_key, None)
             old.close()
     else:
         _OPERATORS.move_to_end(key)
@@ -72,9 +84,43 @@ def _operator(A, device):
 
 
 def clear_operator_cache():
+    _PATTERNS.clear()
     while _OPERATORS:
         _, op = _OPERATORS.popitem()
         op.close()
+
+
+def update_values(A, device=0):
+    """After ``A.data`` has been modified IN PLACE (same indptr, indices: the same mesh with new coefficients), bring the
+    cached device operator of ``A`` up to date instead of letting the next solve upload ``A`` as a second operator
+    (DeviceCSR.update_values; prcg.h: prcg_update_values).  The operator is found by identity, shape, nnz and the
+    fingerprint of indptr / indices kept beside the cache entry, and is re-keyed to the new content.  Returns the route
+    taken, 'in_place' or 'replanned', or None if ``A`` has no cached operator on ``device`` -- the next solve then uploads
+    it as it always has.  The reference has no counterpart: its functions read ``A`` anew at every call."""
+    head = (id(A), A.shape, A.nnz, A.data.__array_interface__['data'][0], int(device))
+    pattern = None
+    for key in list(_OPERATORS):
+        if key[:5] != head:
+            continue
+        if pattern is None:
+            pattern = _pattern_fingerprint(A)
+        if _PATTERNS.get(key) != pattern:
+            continue
+        op = _OPERATORS.pop(key)
+        _PATTERNS.pop(key, None)
+        try:
+            route = op.update_values(np.ascontiguousarray(A.data, dtype=np.float64))
+        except Exception:
+            op.close()
+            raise
+        new_key = head + (_fingerprint(A),)
+        stale = _OPERATORS.pop(new_key, None)
+        if stale is not None:
+            stale.close()
+        _OPERATORS[new_key] = op
+        _PATTERNS[new_key] = pattern
+        return route
+    return None
 
 
 def _diagonal_of(preconditioner, n):
@@ -499,4 +545,4 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
-           'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache']
+           'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values']

@@ -1625,6 +1625,46 @@ int checked_indptr(prcg_t* h, int64_t n_rows, int64_t nnz, const void* indptr, i
     return PRCG_OK;
 }
 
+// plan_operator (host only, prcg_plan.cpp) -> upload the plan's arrays -> keep its flags: what prcg_set_csr does with validated
+// arrays, and what the re-planning route of prcg_update_values does with the arrays it read back
+int install_operator(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* ip, const int32_t* indices, const double* data) {
+    OperatorPlan pl;
+    std::string why;
+    if (!plan_operator(h->opt, n_rows, n_ghost, nnz, ip, indices, data, pl, why)) return fail(h, PRCG_EINVAL, "%s", why.c_str());
+    // (the flags describe the upload in progress, as they always have: a failed upload leaves have_csr as it was)
+    static_cast<OperatorShape&>(*h) = pl;
+    if (int rc = upload_operator(h, pl, ip, indices, data)) return rc;
+    h->peer_ok = false;
+    h->wt_rb.clear(); h->wt_re.clear();
+    if (pl.win)
+        for (const WTile& t : pl.wtiles) { h->wt_rb.push_back(t.rb); h->wt_re.push_back(t.re); }
+    h->have_csr = true;
+    return PRCG_OK;
+}
+
+// A caller's device pointer is read only after the runtime has vouched for it: device memory of the handle's GPU, and
+// [p, p + bytes) inside the allocation it belongs to
+int checked_device_range(prcg_t* h, const char* who, const void* p, size_t bytes) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, PRCG_EINVAL, "%s: data_on_device = 1, but the runtime knows no allocation at %p", who, p);
+    }
+    CHECK(h, at.type == hipMemoryTypeDevice, "%s: data_on_device = 1, but %p is not device memory (memory type %d)", who, p, (int)at.type);
+    CHECK(h, at.device == h->dev, "%s: the values lie on GPU %d, the handle's GPU is %d", who, at.device, h->dev);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, PRCG_EINVAL, "%s: no address range for the device pointer %p", who, p);
+    }
+    const char* lo = static_cast<const char*>(base);
+    const char* c = static_cast<const char*>(p);
+    CHECK(h, c >= lo && bytes <= size && (size_t)(c - lo) <= size - bytes,
+          "%s: %zu bytes from %p leave the allocation they begin in (%zu bytes from %p)", who, bytes, p, size, (void*)base);
+    return PRCG_OK;
+}
+
 uint64_t fnv1a(uint64_t hash, const void* data, size_t bytes) {
     const unsigned char* c = static_cast<const unsigned char*>(data);
     for (size_t i = 0; i < bytes; ++i) { hash ^= c[i]; hash *= 0x100000001b3ull; }
@@ -1798,21 +1838,64 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz, const 
     // --- validate on the host before anything reaches a kernel, then decide family and encodings ---
     std::vector<int32_t> ip;
     if (int rc = checked_indptr(h, n_rows, nnz, indptr, indptr_is64, ip)) return rc;
-    OperatorPlan pl;
-    std::string why;
-    if (!plan_operator(h->opt, n_rows, n_ghost, nnz, ip.data(), indices, data, pl, why)) return fail(h, PRCG_EINVAL, "%s", why.c_str());
-    // (the flags describe the upload in progress, as they always have: a failed upload leaves have_csr as it was)
-    static_cast<OperatorShape&>(*h) = pl;
-    if (int rc = upload_operator(h, pl, ip.data(), indices, data)) return rc;
-    h->peer_ok = false;
-    h->wt_rb.clear(); h->wt_re.clear();
-    if (pl.win)
-        for (const WTile& t : pl.wtiles) { h->wt_rb.push_back(t.rb); h->wt_re.push_back(t.re); }
-    h->have_csr = true;
+    if (int rc = install_operator(h, n_rows, n_ghost, nnz, ip.data(), indices, data)) return rc;
     h->have_halo = false;
     h->gather_planned = false;
     return PRCG_OK;
 }
+
+// New values on the pattern prcg_set_csr fixed: in place where no encoding holds values (values_route, prcg_plan.cpp), else the
+// operator is planned and uploaded again from the pattern read back and the new values
+int prcg_update_values(prcg_t* h, const double* data, int data_on_device) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, h->have_csr, "prcg_update_values: no operator: call prcg_set_csr first");
+    CHECK(h, data_on_device == 0 || data_on_device == 1, "prcg_update_values: data_on_device = %d is neither 0 (host) nor 1 (device)", data_on_device);
+    CHECK(h, h->g == 0, "prcg_update_values: the operator is a row block with %lld ghost columns; only whole operators on one GPU are updated "
+                        "(set the block again with prcg_set_csr)", (long long)h->g);
+    CHECK(h, !h->multi() && h->nranks == 1, "prcg_update_values: the handle has a communicator or a world size > 1; only whole operators on one GPU "
+                                            "are updated (set the block again with prcg_set_csr)");
+    CHECK(h, data || h->nnz == 0, "prcg_update_values: null data");
+    if (h->nnz == 0) return PRCG_OK;
+    const int64_t n = h->n, nnz = h->nnz;
+    const size_t bytes = (size_t)nnz * sizeof(double);
+    HIPCHK(h, hipSetDevice(h->dev));
+    if (data_on_device) {
+        CHECK(h, reinterpret_cast<uintptr_t>(data) % sizeof(double) == 0, "prcg_update_values: device pointer %p is not aligned to 8 bytes", (const void*)data);
+        if (int rc = checked_device_range(h, "prcg_update_values", data, bytes)) return rc;
+    }
+    // the handle's pending work reads the old values
+    HIPCHK(h, hipStreamSynchronize(h->sh));
+    HIPCHK(h, hipStreamSynchronize(h->sm));
+    HIPCHK(h, hipStreamSynchronize(h->sc));
+    if (values_route(*h) == 0) {
+        // the plan stays: values in the caller's order (window tiles with plain values and CSR-adaptive tiles read them), and
+        // for sliced rows the re-laid copy rewritten from them
+        HIPCHK(h, hipMemcpyAsync(h->val.p, data, bytes, data_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->sc));
+        HIPCHK(h, hipStreamSynchronize(h->sc));             // `data` has been read: the caller may overwrite it
+        h->in_session = false;                              // new values invalidate any open session
+        if (h->sell) {
+            const int grid = launch_sell_set_values(h->sc, h->sdev(), h->sslice_ptr(0), h->nst_int + h->nst_bnd, h->val.d(),
+                                                    static_cast<double*>(h->sval.p));
+            if (grid < 0) return fail(h, PRCG_EHIP, "kernel launch failed (%s:%d)", __FILE__, __LINE__);
+        }
+        return PRCG_OK;
+    }
+    // a dictionary or pattern tiles hold values: prcg_set_csr's plan and upload under the handle's options, with the pattern
+    // read back from the device (no host copy is kept) -- preconditioners and session buffers stay
+    std::vector<int32_t> ip, idx;
+    std::vector<double> host;
+    try {
+        ip.resize((size_t)n + 1); idx.resize((size_t)nnz);
+        if (data_on_device) host.resize((size_t)nnz);
+    } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    HIPCHK(h, hipMemcpy(ip.data(), h->indptr.p, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(idx.data(), h->col.p, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (data_on_device) HIPCHK(h, hipMemcpy(host.data(), data, bytes, hipMemcpyDeviceToHost));
+    h->in_session = false;
+    return install_operator(h, n, 0, nnz, ip.data(), idx.data(), data_on_device ? host.data() : data);
+}
+
+int prcg_values_route(const prcg_t* h) { return (h && h->have_csr) ? values_route(*h) : -1; }
 
 int prcg_set_halo(prcg_t* h, int n_peers, const int32_t* peer_rank, const int64_t* send_ptr, const int32_t* send_idx,
                   const int64_t* recv_ptr) {
@@ -3113,6 +3196,23 @@ int64_t prcg_plan_operator(int64_t n_rows, int64_t n_ghost, int64_t nnz, const i
     if (pl.sell) ht = fnv1a(ht, pl.sslices);
     out[14] = (int64_t)hi; out[15] = (int64_t)hv; out[16] = (int64_t)hd; out[17] = (int64_t)ht;
     return kFields;
+}
+
+int prcg_plan_values_route(int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
+                           const double* data, const char* const* keys, const char* const* values, int n_options) {
+    if (n_rows < 0 || n_ghost < 0 || nnz < 0 || !indptr32 || (nnz > 0 && (!indices || !data)) || n_options < 0 ||
+        (n_options > 0 && (!keys || !values)))
+        return -1;
+    if (indptr32[0] != 0 || indptr32[n_rows] != nnz) return -1;
+    for (int64_t i = 0; i < n_rows; ++i)
+        if (indptr32[i + 1] < indptr32[i]) return -1;
+    Options opt;
+    for (int i = 0; i < n_options; ++i)
+        if (!apply_option(opt, keys[i], values[i])) return -1;
+    OperatorPlan pl;
+    std::string why;
+    if (!plan_operator(opt, n_rows, n_ghost, nnz, indptr32, indices, data, pl, why)) return -1;
+    return values_route(pl);
 }
 
 int64_t prcg_plan_tiles(int64_t n, const int32_t* indptr, const uint8_t* row_class, int cap_nnz, int cap_rows,

@@ -292,6 +292,10 @@ int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int 
 int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
                       double* dst0, double* dst1, int per_cu);
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu);
+// New values on an unchanged pattern (prcg_update_values): sval, the re-laid value array A.val points to, rewritten from val_csr, the
+// nnz values in the caller's CSR order -- one wave per slice, every position of a slice written (no nonzero: 0), so that sval holds
+// the bytes plan_sell's fill pass would have produced from these values.  Reads A.indptr, A.rows and, for rows with skips, A.col16.
+int launch_sell_set_values(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* val_csr, double* sval);
 
 // ---- small systems: the whole pipelined solve in one launch of one workgroup -------------
 struct SmallArgs {

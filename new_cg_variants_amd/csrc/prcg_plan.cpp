@@ -1325,4 +1325,6 @@ bool plan_operator(const Options& o, int64_t n_rows, int64_t n_ghost, int64_t nn
     return true;
 }
 
+int values_route(const OperatorShape& s) { return (s.win_vd || s.win_pat || s.vd_int || s.vd_bnd) ? 1 : 0; }
+
 }  // namespace prcg

@@ -276,6 +276,13 @@ struct OperatorPlan : OperatorShape {
 // index outside [0, n_rows + n_ghost).
 bool plan_operator(const Options& o, int64_t n_rows, int64_t n_ghost, int64_t nnz, const int32_t* indptr32, const int32_t* indices,
                    const double* data, OperatorPlan& out, std::string& err);
+// How new values on an unchanged pattern are served (prcg_update_values): 0 = in place, 1 = re-planned.  The encodings that
+// HOLD values are a closed list -- the window value dictionary (win_vd: value-index images, entries), pattern tiles (win_pat:
+// the records carry the values) and the CSR-adaptive value dictionary (vd_int / vd_bnd); an operator with one of them is
+// planned again.  Every other encoding is a function of indptr / indices alone: window tiles with plain values and
+// CSR-adaptive tiles without a dictionary read the caller-order values, sliced rows a re-laid copy of them that
+// k_sell_set_values rewrites (plan_sell touches `data` only in its fill pass).
+int values_route(const OperatorShape& s);
 
 // Merged exchange (small halos ride on the one all-gather per iteration):
 // every rank contributes a slot of `slot` doubles = 8 (partial sums) + 2 x its packed send rows;

@@ -499,7 +499,73 @@ int launch_sell(hipStream_t st, const SellDev& A, const void* slices, int nslice
     return hipGetLastError() == hipSuccess ? grid : -1;
 }
 
+// ---- new values on an unchanged pattern (prcg_update_values): the re-laid value array rewritten from the CSR-order values ----
+// One wave per slice, lane l the slice's lane-l row -- the mapping of plan_sell's fill pass.  Stored position u of the row goes
+// to sval[voff + ((u/2)*64 + l)*2 + u%2]; every position of the slice's even-rounded width that holds no nonzero -- the row's
+// tail, the idle lanes of a short or cut slice, skip positions -- is written 0, so that sval has the bytes of a fresh upload.
+// Slices of consecutive rows (all WINDOW-code slices among them) have no skips: position u takes val_csr[indptr[row] + u].
+// Slices that name their rows take (row, stored length) from the pairs; a row whose stored length exceeds its nonzeros has skip
+// codes, and the lane walks its delta codes as the product kernels do: a skip code (0 / 65535) consumes RUN positions and no
+// value.  The values move as 64-bit patterns (-0, inf, NaN payloads survive); a lane stores whole 16-byte pairs, the wave's store
+// for one pair index is one contiguous 1 KB.  The lane's reads walk its row's contiguous CSR range (8 bytes per lane and load,
+// the wave's 64 rows one contiguous block that its loads share line by line).
+typedef unsigned long long ull2_t __attribute__((ext_vector_type(2)));
+
+template <int RUN>
+__global__ __launch_bounds__(kBlock) void k_sell_set_values(SellDev A, const int4* __restrict__ slices, int nslices,
+                                                            const unsigned long long* __restrict__ val_csr,
+                                                            unsigned long long* __restrict__ sval)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + (threadIdx.x >> 6)));
+    if (t >= nslices) return;
+    const SDesc d = read_sdesc(slices, t);
+    int row = -1, stored = 0;
+    if (d.rows_off < 0) {                                                   // wave-uniform
+        if (d.rb + lane < d.re) row = d.rb + lane;
+    } else {
+        const int2 p = reinterpret_cast<const int2*>(A.rows)[d.rows_off + lane];
+        row = p.x; stored = p.y;
+    }
+    int lo = 0, len = 0;
+    if (row >= 0) { lo = A.indptr[row]; len = A.indptr[row + 1] - lo; }
+    if (d.rows_off < 0) stored = len;
+    if (stored > d.width) stored = d.width;                                 // (the planner's invariant; never past the slice)
+    const bool skips = stored != len;
+    const int pairs = (d.width + 1) >> 1;                                   // wave-uniform
+    ull2_t* __restrict__ dst = reinterpret_cast<ull2_t*>(sval + (int64_t)d.voff) + lane;
+    int q = 0;                                                              // nonzeros of the row consumed so far
+    unsigned code = 1u;
+#pragma unroll 4
+    for (int j = 0; j < pairs; ++j) {
+        unsigned long long v[2] = {0ull, 0ull};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int u = 2 * j + e;
+            if (u < stored) {
+                if (skips && u % RUN == 0) {
+                    const int c = u / RUN;
+                    code = A.col16[(int64_t)d.coff + ((int64_t)(c >> 3) * 64 + lane) * 8 + (c & 7)];
+                }
+                if ((!skips || code - 1u < 65534u) && q < len) v[e] = val_csr[lo + q++];
+            }
+        }
+        ull2_t w; w.x = v[0]; w.y = v[1];
+        dst[(int64_t)j * 64] = w;
+    }
+}
+
 }  // namespace
+
+int launch_sell_set_values(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* val_csr, double* sval)
+{
+    if (nslices <= 0) return 0;
+    const int grid = (nslices + kWaves - 1) / kWaves;
+    auto k = A.run == 3 ? k_sell_set_values<3> : k_sell_set_values<1>;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, st, A, reinterpret_cast<const int4*>(slices), nslices,
+                       reinterpret_cast<const unsigned long long*>(val_csr), reinterpret_cast<unsigned long long*>(sval));
+    return hipGetLastError() == hipSuccess ? grid : -1;
+}
 
 int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, SpmvEpilogue epi,
                      const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu)

@@ -43,6 +43,7 @@ class DeviceCSR:
         is not touched."""
         self._h = C.c_void_p()
         self._lib = L.lib()
+        self.device = int(device)
         rc = self._lib.prcg_create(C.byref(self._h), int(device))
         if rc != L.OK:
             msg = self._lib.prcg_last_error(None)
@@ -107,6 +108,50 @@ class DeviceCSR:
             recv_ptr = np.ascontiguousarray(halo['recv_ptr'], dtype=np.int64)
             self._check(self._lib.prcg_set_halo(self._h, len(peers), L.ptr(peers), L.ptr(send_ptr),
                                                 L.ptr(send_idx), L.ptr(recv_ptr)))
+
+    # -- new values on the same pattern (prcg.h: prcg_update_values) -----------------------------------
+    def values_route(self):
+        """How update_values serves the operator now on the handle: 'in_place' (no encoding holds values: no host planning)
+        or 'replanned' (value dictionary or pattern tiles)."""
+        route = int(self._lib.prcg_values_route(self._h))
+        if route not in (0, 1):
+            raise RuntimeError('prcg_values_route: the handle has no operator')
+        return ('in_place', 'replanned')[route]
+
+    def update_values(self, data):
+        """New values for the nonzeros of the matrix this handle was built from -- same shape, indptr and indices, the
+        caller's promise -- instead of a second DeviceCSR(A).  ``data``: nnz float64 values in the order of that matrix's CSR
+        arrays, as an array (or CPU tensor), or as a CUDA torch tensor, which is read where it lies: it must be float64,
+        contiguous, of nnz elements and on the handle's device (ValueError otherwise), and its memory must belong to the HIP
+        runtime libprcg.so is bound to, i.e. torch was imported before the library was loaded (the library refuses a pointer
+        its runtime does not know).  torch's current stream on that device is synchronised first.
+        Returns the route taken, 'in_place' or 'replanned' (values_route).  An open session ends; options, a host-callback
+        preconditioner and block-Jacobi blocks stay in force."""
+        if type(data).__module__.split('.')[0] == 'torch' and hasattr(data, 'is_cuda'):
+            if data.is_cuda:
+                import torch
+                if data.dtype != torch.float64:
+                    raise ValueError(f'update_values: fp64 only (got a {data.dtype} tensor)')
+                if data.numel() != self.nnz:
+                    raise ValueError(f'update_values: the operator has {self.nnz} nonzeros, the tensor {data.numel()} elements')
+                if not data.is_contiguous():
+                    raise ValueError('update_values: the tensor must be contiguous (the values are read where they lie)')
+                if data.device.index != self.device:
+                    raise ValueError(f'update_values: the tensor lies on {data.device}, the handle on GPU {self.device}')
+                torch.cuda.current_stream(data.device).synchronize()
+                route = self.values_route()
+                self._check(self._lib.prcg_update_values(self._h, C.c_void_p(data.data_ptr()), 1))
+                return route
+            data = data.detach().numpy()
+        data = np.asarray(data)
+        if data.dtype != np.float64:
+            raise ValueError(f'update_values: fp64 only (got {data.dtype})')
+        if data.size != self.nnz or data.ndim != 1:
+            raise ValueError(f'update_values: the operator has {self.nnz} nonzeros, the array has shape {data.shape}')
+        data = np.ascontiguousarray(data)
+        route = self.values_route()
+        self._check(self._lib.prcg_update_values(self._h, L.ptr(data), 0))
+        return route
 
     # -- direct peer exchange (prcg.h: prcg_peer_setup / prcg_peer_connect) ------------------------------
     def peer_setup(self, max_ghost_any_rank):
@@ -456,6 +501,25 @@ def plan_tiles(indptr, row_class=None, cap_nnz=None, cap_rows=None):
 PLAN_OPERATOR_FIELDS = ('family', 'win_geom', 'rows_per_tile', 'pattern', 'sweep_waves', 'value_dict', 'value_dict_boundary',
                         'col_bytes', 'col_bytes_boundary', 'tile_steps', 'tiles_interior', 'tiles_boundary', 'image_period',
                         'operator_bytes', 'hash_index', 'hash_value_index', 'hash_dictionary', 'hash_tiles')
+
+
+def plan_values_route(A, knobs=None):
+    """Host-only: the route DeviceCSR(A, knobs=knobs).update_values would take (prcg_test.h: prcg_plan_values_route),
+    'in_place' or 'replanned'."""
+    lib = L.lib()
+    A = A.tocsr()
+    n_rows, n_cols = A.shape
+    indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+    indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+    data = np.ascontiguousarray(A.data, dtype=np.float64)
+    items = [(str(k).encode(), str(v).encode()) for k, v in (knobs or {}).items()]
+    keys = (C.c_char_p * max(len(items), 1))(*[k for k, _ in items])
+    values = (C.c_char_p * max(len(items), 1))(*[v for _, v in items])
+    route = int(lib.prcg_plan_values_route(int(n_rows), int(n_cols - n_rows), int(A.nnz), L.ptr(indptr), L.ptr(indices), L.ptr(data),
+                                           keys, values, len(items)))
+    if route not in (0, 1):
+        raise RuntimeError(f'prcg_plan_values_route failed ({route})')
+    return ('in_place', 'replanned')[route]
 
 
 def plan_operator(A, knobs=None):
