@@ -174,7 +174,7 @@ int prcg_set_csr(prcg_t* h, int64_t n_rows, int64_t n_ghost, int64_t nnz,
  *      pattern tiles to index streams, and back.
  * On both routes an open session ends (as after prcg_set_csr) while the session buffers stay allocated; options, a
  * host-callback preconditioner and block-Jacobi blocks stay in force (a frozen preconditioner is legitimate; call
- * prcg_set_block_jacobi for new blocks).  The call returns after `data` has been read -- the caller may overwrite it -- though
+ * prcg_build_block_jacobi or prcg_set_block_jacobi for new blocks).  The call returns after `data` has been read -- the caller may overwrite it -- though
  * the re-lay kernel may still be enqueued.  nnz == 0: nothing to do.
  * Refused (PRCG_EINVAL, the text names the reason, the handle is untouched): no operator; null data with nnz > 0; n_ghost > 0,
  * a communicator or a world size > 1 on the handle (rank-local blocks: set them again with prcg_set_csr); data_on_device
@@ -287,6 +287,35 @@ int prcg_set_preconditioner(prcg_t* h, prcg_prec_fn fn, void* ctx);
  * This call and prcg_set_preconditioner replace each other: the last one set is in force.  Single GPU.
  * inv_blocks == NULL removes it. */
 int prcg_set_block_jacobi(prcg_t* h, int bs, const double* inv_blocks);
+/* The same blocks BUILT ON THE DEVICE from the operator now on the handle: one kernel pass over the caller-order CSR arrays the
+ * handle keeps (current after prcg_update_values on both routes) gathers the bs x bs diagonal blocks, inverts them and stores
+ * them where the apply kernel reads them -- no host pass over the matrix, no upload.  No counterpart in the reference; it
+ * replaces the caller's own gather-and-invert in front of prcg_set_block_jacobi (cg_variants.BlockJacobi: a NumPy pass over
+ * every nonzero plus LAPACK), which a Newton loop would otherwise pay beside every prcg_update_values.
+ * The arithmetic is fixed, so that a host restatement (cg_variants.invert_blocks) has the same bits:
+ *   gather   rows k*bs .. k*bs+bs-1 form block k, nb = ceil(n_rows / bs).  Row i = k*bs + a starts with g[c] = +0.0, c < bs; for
+ *            q = indptr[i] .. indptr[i+1]-1 ascending: if indices[q] / bs == k then g[indices[q] % bs] = g[indices[q] % bs] +
+ *            data[q].  Unsorted rows and duplicates are legal; duplicates add in CSR order.  A short last block (m = n_rows -
+ *            bs*(nb-1) < bs rows) is its leading m x m part inside an identity.
+ *   invert   Gauss-Jordan on [M | E], E = I, NO pivoting (CG needs an SPD operator, whose diagonal blocks are SPD).  For c = 0 ..
+ *            bs-1:  p = M[c][c];  row c becomes M[c][j] / p and E[c][j] / p for every j (a division, not a multiplication by a
+ *            reciprocal);  for every r != c:  f = M[r][c];  M[r][j] = M[r][j] - f * M[c][j],  E[r][j] = E[r][j] - f * E[c][j] for
+ *            every j.  Every quotient, product and difference rounded (no FMA).  E is the inverse.
+ *   bad      a block is bad iff one of its pivots is zero or not finite at its step, or an entry of its E is not finite.  A block
+ *            that is not bad carries exactly the bits of this loop, signed zeros included.  (A block such as [[0,1],[1,0]] is bad
+ *            here although it has an inverse.)
+ * Call after prcg_set_csr; valid again after every prcg_update_values.  The call waits for the handle's pending work, drops
+ * blocks set before, runs the kernel on the compute stream and reads the flag back.  On success the state is that of
+ * prcg_set_block_jacobi with these inverses (sessions, PRCG_SCHED_BLOCK_JACOBI, the mutual replacement with
+ * prcg_set_preconditioner; a later prcg_set_csr drops them, a later prcg_update_values leaves them frozen) and *first_bad_block
+ * (nullable) = -1.  With a bad block: PRCG_EINVAL, text "diagonal block K (bs = B) is singular or not finite", K the smallest
+ * index of a bad block, *first_bad_block = K, and the handle is left WITHOUT blocks.
+ * Refused (PRCG_EINVAL, the text names the reason, the handle is untouched): no operator; bs outside 1..8; n_ghost > 0; a
+ * communicator or a world size > 1 on the handle. */
+int prcg_build_block_jacobi(prcg_t* h, int bs, int64_t* first_bad_block);
+/* The blocks now on the handle, whichever call set them: inv_blocks receives nb x bs x bs host doubles, row-major (bs: the one
+ * they were set with); a short last block comes back as its leading m x m part inside an identity.  PRCG_EINVAL without blocks. */
+int prcg_get_block_jacobi(prcg_t* h, double* inv_blocks);
 int prcg_schedule(const prcg_t* h);
 /* Bytes of the operator AS THE DEVICE STREAMS IT (the lossless re-encodings of the caller's CSR built at
  * prcg_set_csr: narrow column / window indices, value-dictionary indices, relative row pointers, tile

@@ -19,7 +19,9 @@ Differences, all at the edges:
   to recover the diagonal and then applied on the device; an object that carries ``bs`` and
   ``inv_blocks`` (``BlockJacobi(A, bs)``: the inverses of the bs x bs diagonal blocks, what
   PETSc calls pbjacobi) is applied on the device too, by a kernel of its own, and is never
-  called (prcg.h: prcg_set_block_jacobi); any other callable is the caller's code, as it is
+  called (prcg.h: prcg_set_block_jacobi); ``DeviceBlockJacobi(A, bs)`` has the same blocks built on
+  the device from the resident operator, without a host pass over the matrix (prcg.h:
+  prcg_build_block_jacobi); any other callable is the caller's code, as it is
   in the reference, and is called on the host wherever the reference calls
   ``preconditioner(...)`` (prcg.h: prcg_set_preconditioner) while products, updates and
   inner products stay on the device;
@@ -268,6 +270,77 @@ class BlockJacobi:
         return out
 
 
+def invert_blocks(blocks):
+    """The inversion loop of prcg_build_block_jacobi (prcg.h), restated with NumPy: Gauss-Jordan on [M | E], E = I, no pivoting,
+    vectorised over the blocks, one ufunc per rounded operation -- for c = 0 .. bs-1: p = M[c][c]; row c of M and of E divided by
+    p; every other row r: f = M[r][c], M[r] = M[r] - f * M[c], E[r] = E[r] - f * E[c].  ``blocks``: (nb, bs, bs), a short last
+    block already inside its identity (what BlockJacobi._gather plus the padding gives).  Returns (inv, bad): E, which carries the
+    bits of the device build for every block that is not bad, and the boolean mask of bad blocks -- a pivot zero or not finite at
+    its step, or an entry of E not finite."""
+    M = np.array(blocks, dtype=np.float64)
+    if M.ndim != 3 or M.shape[1] != M.shape[2]:
+        raise ValueError(f'invert_blocks: expected an array of shape (nb, bs, bs), got {M.shape}')
+    nb, bs = M.shape[:2]
+    E = np.broadcast_to(np.eye(bs), M.shape).copy()
+    bad = np.zeros(nb, dtype=bool)
+    with np.errstate(all='ignore'):
+        for c in range(bs):
+            p = M[:, c, c].copy()
+            bad |= (p == 0.0) | ~np.isfinite(p)
+            Mc, Ec = M[:, c, :] / p[:, None], E[:, c, :] / p[:, None]
+            f = M[:, :, c].copy()
+            M = M - f[:, :, None] * Mc[:, None, :]
+            E = E - f[:, :, None] * Ec[:, None, :]
+            M[:, c, :], E[:, c, :] = Mc, Ec             # the pivot row itself is scaled, not eliminated
+        bad |= ~np.isfinite(E).all(axis=(1, 2))
+    return E, bad
+
+
+class DeviceBlockJacobi:
+    """Point-block Jacobi whose inverses are BUILT ON THE DEVICE from the operator (prcg.h: prcg_build_block_jacobi): passed as
+    `preconditioner` to a *_pcg function, the matrix is never touched on the host -- one kernel pass over the operator already
+    resident gathers the bs x bs diagonal blocks, inverts them and leaves them where the apply kernel reads them; a later solve
+    on the same operator reuses them, and a solve after update_values(A) builds them again.  The step after BlockJacobi for a
+    Newton loop on an assembled matrix::
+
+        A.data[:] = ...; update_values(A); pipe_pr_pcg(A, b, x0, max_iter, preconditioner=DeviceBlockJacobi(A, 3))
+
+    The inversion is the fixed loop of prcg.h (Gauss-Jordan without pivoting: CG needs an SPD operator, whose diagonal blocks are
+    SPD), not LAPACK's: the inverses differ from BlockJacobi's in the last bits, and a block such as [[0, 1], [1, 0]], which
+    BlockJacobi inverts, is refused here (its first pivot is zero).  bs == 1 goes through the block kernel too.
+    Called, the object builds `inv_blocks` on the host on first use -- BlockJacobi._gather plus invert_blocks, the restatement
+    of the device loop, hence the bits the device uses -- from the values ``A`` holds at that moment, and applies them with
+    BlockJacobi.__call__'s arithmetic: it serves the oracle and any solver that takes a callable.  A bad block raises
+    ValueError('DeviceBlockJacobi: diagonal block K (bs = B) is singular or not finite') there as on the device path."""
+
+    def __init__(self, A, bs):
+        bs = int(bs)
+        if not 1 <= bs <= 8:
+            raise ValueError(f'DeviceBlockJacobi: block size {bs} outside 1..8')
+        if A.format != 'csr':
+            A = A.tocsr()
+        self.A, self.bs, self.n = A, bs, A.shape[0]
+        self._inv_blocks = None
+
+    @property
+    def inv_blocks(self):
+        if self._inv_blocks is None:
+            n, bs = self.n, self.bs
+            nb = -(-n // bs)
+            blocks = BlockJacobi._gather(self.A, n, nb, bs)
+            m = n - bs * (nb - 1)
+            if m < bs and nb > 0:
+                blocks[-1, np.arange(m, bs), np.arange(m, bs)] = 1.0
+            inv, bad = invert_blocks(blocks)
+            if bad.any():
+                raise ValueError(f'DeviceBlockJacobi: diagonal block {int(np.argmax(bad))} (bs = {bs}) is singular or not finite')
+            self._inv_blocks = np.ascontiguousarray(inv)
+        return self._inv_blocks
+
+    def __call__(self, v):
+        return BlockJacobi.__call__(self, v)
+
+
 _STATE_NAMES = {   # device vector -> the reference's local name
     'x': 'x_k', 'r': 'r_k', 'p': 'p_k', 's': 's_k', 'w': 'w_k', 'u': 'u_k',
     'rt': 'rt_k', 'st': 'st_k', 'wt': 'wt_k', 'ut': 'ut_k',
@@ -291,7 +364,13 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
     if A.format != 'csr':
         A = A.tocsr()
     n = A.shape[0]
-    inv_diag, prec_fn = _diagonal_of(preconditioner, n)
+    built = isinstance(preconditioner, DeviceBlockJacobi)      # blocks built on the device: the object is neither probed nor read
+    if built:
+        if preconditioner.n != n:
+            raise ValueError(f'DeviceBlockJacobi: made for a matrix of {preconditioner.n} rows, the system has {n}')
+        inv_diag, prec_fn = None, preconditioner
+    else:
+        inv_diag, prec_fn = _diagonal_of(preconditioner, n)
 
     mask = 0
     foreign = []          # callables we must call ourselves, every iteration
@@ -332,8 +411,15 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         op.set_replace_hook(hook)
     else:
         op.set_replace_hook(None)
-    blocks = _blocks_of(prec_fn) if prec_fn is not None else None
-    if blocks is not None:
+    blocks = _blocks_of(prec_fn) if prec_fn is not None and not built else None
+    if built:
+        try:
+            op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=(preconditioner.bs, None))
+        except ValueError as e:
+            if 'diagonal block' not in str(e):
+                raise
+            raise ValueError('DeviceBlockJacobi: ' + str(e).split(': ', 1)[-1]) from None      # the library's text, this object's name
+    elif blocks is not None:
         op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=blocks)
     else:
         op.begin(variant, b, x0, max_iter, x_true=x_true, inv_diag=inv_diag, hist_mask=mask, preconditioner=prec_fn)
@@ -391,9 +477,12 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
     for key in ('x_true', 'w_replace'):
         if kwargs.get(key) is not None:
             raise ValueError(f'{name}: {key} is not served by the two-RHS session')
-    inv_diag, prec_fn = _diagonal_of(preconditioner, n)
+    if isinstance(preconditioner, DeviceBlockJacobi):
+        inv_diag, prec_fn = None, preconditioner
+    else:
+        inv_diag, prec_fn = _diagonal_of(preconditioner, n)
     if prec_fn is not None:
-        kind = 'a block-Jacobi preconditioner' if _blocks_of(prec_fn) is not None else 'a preconditioner that is no diagonal scaling'
+        kind = 'a block-Jacobi preconditioner' if isinstance(prec_fn, DeviceBlockJacobi) or _blocks_of(prec_fn) is not None else 'a preconditioner that is no diagonal scaling'
         raise ValueError(f'{name}: {kind} is not served by the two-RHS session (Jacobi(A), a callable that acts as a diagonal, or None)')
     mask = 0
     light = []
@@ -545,4 +634,5 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
-           'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values']
+           'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
+           'invert_blocks', 'DeviceBlockJacobi']

@@ -105,6 +105,79 @@ void launch_two(hipStream_t st, double* wt, double* ut, const double* wu, int64_
                        blk, mask);
 }
 
+// ---- the device build (prcg_build_block_jacobi): gather the diagonal blocks from the caller-order CSR arrays, invert them, store
+// them in the layout above -- one pass over the operator, no host re-lay, no upload.  The arithmetic is the contract of prcg.h
+// (cg_variants.invert_blocks restates it): per row g[c] = g[c] + val[q] over the row's nonzeros in CSR order, then Gauss-Jordan on
+// [M | E] without pivoting, a division per entry of the pivot row, a product and a difference per entry of every other row.
+//   * lane per row, the tiling of k_block_jacobi: lane t of tile T owns row T * TR + t and keeps its row of [M | E], 2 * BS doubles;
+//   * the row walk reads the column first and loads the value only on a match (about BS of a row's entries match);
+//   * at step c the lane with a == c scales its row and parks it in LDS for its block; after ONE barrier the other lanes of the
+//     block eliminate (the parking area is double buffered by the step's parity, so the next pivot row is written while slow lanes
+//     still read this one).  Blocks straddle waves (TR = 255 at bs = 3): hence LDS and the workgroup barrier, not shuffles;
+//   * the rows a short last block lacks are played by their lanes as identity rows, so the block runs the whole loop as the host
+//     restatement does; they store 0 like every lane without a row, as block_jacobi_layout does;
+//   * a bad block (a pivot zero or not finite at its step, an entry of E not finite) takes the minimum of its index into *first_bad.
+template <int BS>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_build(double* __restrict__ blk, int64_t n, const int* __restrict__ indptr,
+                                                                 const int* __restrict__ col, const double* __restrict__ val,
+                                                                 long long* __restrict__ first_bad) {
+    constexpr int TR = (kBjBlock / BS) * BS;
+    __shared__ double park[2][kBjBlock / BS][2 * BS];
+    const int t = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * TR;
+    const int64_t i = row0 + t;
+    const int a = t % BS, lb = t / BS;
+    const int64_t kb = i - a;                             // first row of this row's block (row0 is a multiple of BS)
+    const bool live = t < TR && i < n;                    // the lane has a row
+    const bool member = t < TR && kb < n;                 // ... or plays an identity row of a short last block
+    double M[BS], E[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) { M[j] = (!live && j == a) ? 1.0 : 0.0; E[j] = j == a ? 1.0 : 0.0; }
+    if (live) {
+        const int q1 = indptr[i + 1];
+        const int c0 = (int)kb;
+        for (int q = indptr[i]; q < q1; ++q) {
+            const int c = col[q] - c0;
+            if (c >= 0 && c < BS) {
+                const double v = val[q];
+#pragma unroll
+                for (int j = 0; j < BS; ++j)
+                    if (c == j) M[j] = M[j] + v;
+            }
+        }
+    }
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < BS; ++c) {
+        double* pr = park[c & 1][lb];
+        if (member && a == c) {
+            const double p = M[c];
+            bad = bad || p == 0.0 || !(p - p == 0.0);     // zero, infinite or NaN
+#pragma unroll
+            for (int j = 0; j < BS; ++j) { M[j] = M[j] / p; E[j] = E[j] / p; pr[j] = M[j]; pr[BS + j] = E[j]; }
+        }
+        __syncthreads();
+        if (member && a != c) {
+            const double f = M[c];
+#pragma unroll
+            for (int j = 0; j < BS; ++j) { M[j] = M[j] - f * pr[j]; E[j] = E[j] - f * pr[BS + j]; }
+        }
+    }
+    if (member) {
+#pragma unroll
+        for (int j = 0; j < BS; ++j) bad = bad || !(E[j] - E[j] == 0.0);
+        if (bad) atomicMin(first_bad, (long long)(kb / BS));
+    }
+    double* out = blk + ((int64_t)blockIdx.x * BS) * kBjBlock + t;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) out[(int64_t)j * kBjBlock] = live ? E[j] : 0.0;
+}
+
+template <int BS>
+void launch_build(hipStream_t st, double* blk, int64_t n, const int* indptr, const int* col, const double* val, long long* first_bad) {
+    hipLaunchKernelGGL(k_block_jacobi_build<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, blk, n, indptr, col, val, first_bad);
+}
+
 }  // namespace
 
 int64_t block_jacobi_layout(int64_t n, int bs, const double* inv_blocks, double* out) {
@@ -122,6 +195,39 @@ int64_t block_jacobi_layout(int64_t n, int bs, const double* inv_blocks, double*
             }
         }
     return total;
+}
+
+int64_t block_jacobi_unlay(int64_t n, int bs, const double* laid, double* inv_blocks) {
+    if (n < 0 || bs < 1 || bs > 8) return -1;
+    const int64_t tr = (kBjBlock / bs) * bs;
+    const int64_t nb = (n + bs - 1) / bs;
+    for (int64_t i = 0; i < nb * bs; ++i) {               // row i = block i / bs, row i % bs of it
+        const int64_t T = i / tr, t = i % tr;
+        for (int j = 0; j < bs; ++j) {
+            const int64_t cols = n - (i - i % bs);        // columns the block really has
+            double v = (i % bs == j) ? 1.0 : 0.0;         // the identity around a short last block
+            if (i < n && j < cols) v = laid[(T * bs + j) * kBjBlock + t];
+            inv_blocks[i * bs + j] = v;
+        }
+    }
+    return nb * bs * bs;
+}
+
+int launch_block_jacobi_build(hipStream_t st, double* blocks, int64_t n, int bs, const int* indptr, const int* col, const double* val,
+                              long long* first_bad) {
+    if (n <= 0) return 0;
+    switch (bs) {
+    case 1: launch_build<1>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 2: launch_build<2>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 3: launch_build<3>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 4: launch_build<4>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 5: launch_build<5>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 6: launch_build<6>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 7: launch_build<7>(st, blocks, n, indptr, col, val, first_bad); break;
+    case 8: launch_build<8>(st, blocks, n, indptr, col, val, first_bad); break;
+    default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_block_jacobi(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t n, int bs, const double* blocks) {

@@ -264,6 +264,7 @@ struct prcg_handle : Operator, Session {
     //  * point-block Jacobi (prcg_set_block_jacobi): M^-1 v is one launch of prcg_blockjac.hip on the compute stream
     prcg_prec_fn cb = nullptr; void* cb_ctx = nullptr;
     int bj_bs = 0; DevBuf bj_blocks;     // bj_bs > 0: blocks set, in the layout of block_jacobi_layout
+    DevBuf bj_flag;                      // one int64: smallest index of a bad block of the last device build (prcg_build_block_jacobi)
     prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
     std::vector<double> cb_in, cb_out;
     DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
@@ -1770,6 +1771,64 @@ int prcg_set_block_jacobi(prcg_t* h, int bs, const double* inv_blocks) {
     HIPCHK(h, hipMemcpy(h->bj_blocks.p, laid.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
     h->bj_bs = bs;
     h->cb = nullptr; h->cb_ctx = nullptr;        // the last preconditioner set is the one in force
+    return PRCG_OK;
+}
+
+// The blocks from the operator itself: one launch over the caller-order CSR arrays upload_operator keeps for every family
+// (both routes of prcg_update_values keep val current) gathers the diagonal blocks, inverts them and stores the device layout
+int prcg_build_block_jacobi(prcg_t* h, int bs, int64_t* first_bad_block) {
+    if (!h) return PRCG_EINVAL;
+    if (first_bad_block) *first_bad_block = -1;
+    CHECK(h, h->have_csr, "prcg_build_block_jacobi: no operator: call prcg_set_csr first");
+    CHECK(h, bs >= 1 && bs <= 8, "prcg_build_block_jacobi: block size %d outside 1..8", bs);
+    CHECK(h, h->g == 0, "prcg_build_block_jacobi: the operator is a row block with %lld ghost columns; the blocks are built for whole "
+                        "operators on one GPU only (invert them on the host: prcg_set_block_jacobi)", (long long)h->g);
+    CHECK(h, !h->multi() && h->nranks == 1, "prcg_build_block_jacobi: the handle has a communicator or a world size > 1; the blocks are "
+                                            "built for whole operators on one GPU only");
+    HIPCHK(h, hipSetDevice(h->dev));
+    // the handle's pending work may still apply the old blocks
+    HIPCHK(h, hipStreamSynchronize(h->sh));
+    HIPCHK(h, hipStreamSynchronize(h->sm));
+    HIPCHK(h, hipStreamSynchronize(h->sc));
+    if (int rc = drop_block_jacobi(h)) return rc;
+    const int64_t count = block_jacobi_layout(h->n, bs, nullptr, nullptr);
+    HIPCHK(h, h->bj_blocks.alloc((size_t)count * sizeof(double), false));     // the kernel writes every entry
+    if (!h->bj_flag.p) HIPCHK(h, h->bj_flag.alloc(sizeof(long long)));
+    long long bad = INT64_MAX;
+    HIPCHK(h, hipMemcpyAsync(h->bj_flag.p, &bad, sizeof bad, hipMemcpyHostToDevice, h->sc));
+    HIPCHK(h, hipStreamSynchronize(h->sc));                                   // (`bad` is a pageable stack variable)
+    if (launch_block_jacobi_build(h->sc, h->bj_blocks.d(), h->n, bs, h->indptr.i(), h->col.i(), h->val.d(),
+                                  static_cast<long long*>(h->bj_flag.p)) != 0) {
+        h->bj_blocks.release();
+        return fail(h, PRCG_EHIP, "kernel launch failed (%s:%d)", __FILE__, __LINE__);
+    }
+    hipError_t e = hipMemcpyAsync(&bad, h->bj_flag.p, sizeof bad, hipMemcpyDeviceToHost, h->sc);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->sc);
+    if (e != hipSuccess) {
+        h->bj_blocks.release();
+        return fail(h, PRCG_EHIP, "%s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    }
+    if (bad != INT64_MAX) {
+        h->bj_blocks.release();                    // the handle is left without blocks
+        if (first_bad_block) *first_bad_block = (int64_t)bad;
+        return fail(h, PRCG_EINVAL, "prcg_build_block_jacobi: diagonal block %lld (bs = %d) is singular or not finite", bad, bs);
+    }
+    h->bj_bs = bs;
+    h->cb = nullptr; h->cb_ctx = nullptr;          // the last preconditioner set is the one in force
+    return PRCG_OK;
+}
+
+int prcg_get_block_jacobi(prcg_t* h, double* inv_blocks) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, h->bj_bs > 0, "prcg_get_block_jacobi: no block-Jacobi blocks on the handle (prcg_set_block_jacobi / prcg_build_block_jacobi)");
+    CHECK(h, inv_blocks, "prcg_get_block_jacobi: null output");
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int64_t count = block_jacobi_layout(h->n, h->bj_bs, nullptr, nullptr);
+    std::vector<double> laid;
+    try { laid.resize((size_t)count); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    HIPCHK(h, hipStreamSynchronize(h->sc));
+    if (count > 0) HIPCHK(h, hipMemcpy(laid.data(), h->bj_blocks.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    block_jacobi_unlay(h->n, h->bj_bs, laid.data(), inv_blocks);
     return PRCG_OK;
 }
 

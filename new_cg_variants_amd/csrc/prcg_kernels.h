@@ -433,6 +433,14 @@ void launch_mul(hipStream_t st, double* dst, int ds, const double* a, int as, co
 // (out == nullptr: only that; -1 for bs outside 1..8).  Strides 1 or 2 (one column of a pair array).  0 / -1.
 int64_t block_jacobi_layout(int64_t n, int bs, const double* inv_blocks, double* out);
 int launch_block_jacobi(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t n, int bs, const double* blocks);
+// the inverse of block_jacobi_layout on the host (prcg_get_block_jacobi): nb x bs x bs row-major from the device layout, a short
+// last block as its leading m x m part inside an identity; returns the number of doubles written (-1 for bs outside 1..8)
+int64_t block_jacobi_unlay(int64_t n, int bs, const double* laid, double* inv_blocks);
+// the blocks built ON THE DEVICE from the caller-order CSR arrays (prcg_build_block_jacobi; contract in prcg.h): `blocks` receives
+// the device layout (block_jacobi_layout's count of doubles, every one written), *first_bad (device, preset to INT64_MAX) the
+// smallest index of a bad block.  0 / -1.
+int launch_block_jacobi_build(hipStream_t st, double* blocks, int64_t n, int bs, const int* indptr, const int* col, const double* val,
+                              long long* first_bad);
 // both columns of the interleaved [w u] array in one launch: wt = M^-1 w (mask bit 0), ut = M^-1 u (mask bit 1)
 int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask);
 // partial[slot] = sum (a[i*as] - b[i])^2

@@ -98,6 +98,7 @@ class DeviceCSR:
         indices = np.ascontiguousarray(A.indices, dtype=np.int32)
         data = np.ascontiguousarray(A.data, dtype=np.float64)
         self.n, self.n_ghost, self.nnz = int(n_rows), int(n_ghost), int(A.nnz)
+        self._bj_bs = self._bj_built = None          # prcg_set_csr drops block-Jacobi blocks
         self._check(self._lib.prcg_set_csr(self._h, self.n, self.n_ghost, self.nnz, L.ptr(indptr), int(is64),
                                            L.ptr(indices), L.ptr(data)))
         self.halo = halo
@@ -141,6 +142,7 @@ class DeviceCSR:
                 torch.cuda.current_stream(data.device).synchronize()
                 route = self.values_route()
                 self._check(self._lib.prcg_update_values(self._h, C.c_void_p(data.data_ptr()), 1))
+                self._bj_built = None                # the blocks stay, frozen: no longer those of the current values
                 return route
             data = data.detach().numpy()
         data = np.asarray(data)
@@ -151,7 +153,51 @@ class DeviceCSR:
         data = np.ascontiguousarray(data)
         route = self.values_route()
         self._check(self._lib.prcg_update_values(self._h, L.ptr(data), 0))
+        self._bj_built = None                        # the blocks stay, frozen: no longer those of the current values
         return route
+
+    # -- point-block Jacobi: the blocks on the handle (prcg.h: prcg_set_block_jacobi / prcg_build_block_jacobi) ----------
+    _bj_bs = None        # block size of the blocks this wrapper put on the handle (None: none)
+    _bj_built = None     # ... and, when they were BUILT from the operator's current values, that block size again
+
+    def set_block_jacobi(self, bs, inv_blocks):
+        """Put the caller's inverses on the handle (prcg.h: prcg_set_block_jacobi): inv_blocks of shape (ceil(n/bs), bs, bs);
+        inv_blocks None removes whatever blocks are set."""
+        if inv_blocks is None:
+            self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
+            self._bj_bs = self._bj_built = None
+            return
+        bs, blocks = int(bs), L.f64(inv_blocks)
+        if not 1 <= bs <= 8 or blocks.shape != (-(-self.n // bs), bs, bs):
+            raise ValueError(f'block_jacobi: need 1 <= bs <= 8 and inv_blocks of shape (ceil(n/bs), bs, bs); got bs={bs}, {blocks.shape}')
+        self._bj_bs = self._bj_built = None
+        self._check(self._lib.prcg_set_block_jacobi(self._h, bs, L.ptr(blocks)))
+        self._bj_bs = bs
+
+    def build_block_jacobi(self, bs):
+        """Build the inverses of the bs x bs diagonal blocks ON THE DEVICE from the operator's current values (prcg.h:
+        prcg_build_block_jacobi: one kernel pass, no host pass over the matrix, no upload) and put them in force, as
+        set_block_jacobi would.  Valid again after every update_values.  ValueError with the library's text if a block is
+        singular or not finite (the handle is then left without blocks); any other refusal is a PrcgError."""
+        bad = C.c_int64(-1)
+        rc = self._lib.prcg_build_block_jacobi(self._h, int(bs), C.byref(bad))
+        if rc == L.EINVAL and bad.value >= 0:
+            self._bj_bs = self._bj_built = None
+            raise ValueError(self._lib.prcg_last_error(self._h).decode())
+        self._check(rc)
+        self._bj_bs = self._bj_built = int(bs)
+
+    def get_block_jacobi(self, bs=None):
+        """The blocks now on the handle as (ceil(n/bs), bs, bs) (prcg.h: prcg_get_block_jacobi), a short last block as its leading
+        m x m part inside an identity.  bs: the block size they were set with -- known to this object when it set them itself
+        (begin, set_block_jacobi, build_block_jacobi), to be passed when the C-ABI was called around it."""
+        bs = self._bj_bs if bs is None else int(bs)
+        if bs is None:
+            raise ValueError('get_block_jacobi: this object has set no blocks; pass bs= if the C-ABI was called directly')
+        out = np.zeros((self.n + 8) * 8)             # room for any bs in 1..8
+        self._check(self._lib.prcg_get_block_jacobi(self._h, L.ptr(out)))
+        nb = -(-self.n // bs)
+        return out[:nb * bs * bs].reshape(nb, bs, bs).copy()
 
     # -- direct peer exchange (prcg.h: prcg_peer_setup / prcg_peer_connect) ------------------------------
     def peer_setup(self, max_ghost_any_rank):
@@ -220,7 +266,10 @@ class DeviceCSR:
     # -- solver session ------------------------------------------------------------------------
     def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None, block_jacobi=None):
         """inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
-        the ceil(n/bs) x bs x bs inverses of the diagonal blocks (prcg.h: prcg_set_block_jacobi).  preconditioner: any
+        the ceil(n/bs) x bs x bs inverses of the diagonal blocks (prcg.h: prcg_set_block_jacobi); inv_blocks None: the blocks
+        BUILT ON THE DEVICE from the operator (build_block_jacobi) -- rebuilt only when blocks of that bs built from the
+        current values are not in force already (after update_values, after a session that removed or replaced them).
+        preconditioner: any
         callable v -> M^-1 v (what the reference's *_pcg functions take); it runs on the host wherever the reference
         calls it (prcg.h: prcg_set_preconditioner).  At most one of the three; a session without block_jacobi removes
         the blocks an earlier session on this operator set."""
@@ -245,16 +294,17 @@ class DeviceCSR:
                     return 1
             self._prec_fn = L.PREC_FN(call)            # keep the trampoline alive for the whole session
             self._check(self._lib.prcg_set_preconditioner(self._h, C.cast(self._prec_fn, C.c_void_p), None))
+            self._bj_bs = self._bj_built = None         # (it replaces the blocks)
         else:
             self._prec_fn = None
             self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
-        if block_jacobi is not None:
-            bs, blocks = int(block_jacobi[0]), L.f64(block_jacobi[1])
-            if not 1 <= bs <= 8 or blocks.shape != (-(-self.n // bs), bs, bs):
-                raise ValueError(f'block_jacobi: need 1 <= bs <= 8 and inv_blocks of shape (ceil(n/bs), bs, bs); got bs={bs}, {blocks.shape}')
-            self._check(self._lib.prcg_set_block_jacobi(self._h, bs, L.ptr(blocks)))
+        if block_jacobi is not None and block_jacobi[1] is None:
+            if self._bj_built is None or self._bj_built != int(block_jacobi[0]):
+                self.build_block_jacobi(int(block_jacobi[0]))
+        elif block_jacobi is not None:
+            self.set_block_jacobi(block_jacobi[0], block_jacobi[1])
         else:
-            self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
+            self.set_block_jacobi(0, None)
         self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
                                                L.ptr(xt), L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
@@ -263,7 +313,7 @@ class DeviceCSR:
         """Remove a host-callback or block-Jacobi preconditioner an earlier session set on this handle."""
         self._prec_fn = None
         self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
-        self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
+        self.set_block_jacobi(0, None)
 
     def begin_multi(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
         """Two or four right-hand sides in ONE session (prcg.h: prcg_solve_begin_multi): B, X0 of shape (2, n) or (4, n), both
