@@ -157,11 +157,18 @@ int prcg_plan_values_route(int64_t n_rows, int64_t n_ghost, int64_t nnz, const i
 int prcg_plan_gather(int rank, int doubles_per_table, const double* tables, int n_peers,
                      const int32_t* peer_rank, const int64_t* recv_ptr, int64_t slot_doubles,
                      int32_t* ghost_src);
-/* Diagnostic (tests): how the resident operator is laid out for the one-launch iteration, i.e. everything the summation
- * order of its inner products depends on.  out[0..8) = {1 if window operator, window geometry id, rows per window tile,
- * number of tiles T, workgroups of the last one-launch iteration (0: none yet), waves per workgroup of that launch,
- * interior tiles, (waves a sweep table assumes) << 8 -- bit 0 is always 0 (it marked the retired XCD-chunked tile order)}, then T pairs (first row, end row) in table order.  Returns the number of int64 written, -needed
- * if capacity is too small, -1 on a bad argument.  tests/device_order.py rebuilds the launch's reduction tree from it. */
+/* Diagnostic (tests): how the resident operator is laid out for the window-tile launches, i.e. everything the summation
+ * order of their inner products depends on.  out[0..8) = {1 if window operator, window geometry id, rows per window tile,
+ * number of tiles T, out[4], out[5], interior tiles, (waves a sweep table assumes) << 8 -- bit 0 is always 0 (it marked the
+ * retired XCD-chunked tile order)}, then T pairs (first row, end row) in table order.
+ * out[4], out[5]: workgroups and waves per workgroup of the open session's LAST launch that left inner-product partials,
+ * as that launch ran: the one-launch pipelined, predict-and-recompute, Chronopoulos-Gear and Ghysels-Vanroose iterations,
+ * the product launches of their two-launch forms and of Hestenes-Stiefel, and a product with a dot epilogue (the start-up
+ * inner products of prcg_solve_begin; not a recorder's).  On a window operator out[5] is the workgroup size the launcher
+ * instantiated, whatever the epilogue; other operators report 4.  out[4] = 0: no such launch yet in this session (out[5]
+ * is then what a one-launch pipelined iteration would take).  Both are cleared when a session opens.
+ * Returns the number of int64 written, -needed if capacity is too small, -1 on a bad argument.  tests/device_order.py
+ * rebuilds the launch's reduction tree from it. */
 int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity);
 /* Capacity rule of every vector a matrix-product launch reads (window pages are whole 64-column blocks, the narrow
  * column encodings decode a few out-of-tile bytes per tile): n_rows + n_ghost entries of `components` doubles plus

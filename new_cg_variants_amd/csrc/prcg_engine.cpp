@@ -144,8 +144,8 @@ struct Operator : OperatorShape {
 //   rs_cur, q_cur, p_cur, cur_r, cur_s, cur_rt, cur_st, cur_w, cur_u, cur_t
 //                        families that do not use a pointer kept the last session's; locate() and the *_args builders read
 //                        only the ones their family sets
-//   small_mode, xphase,  read only under flags their family sets; last_grid: prcg_debug_layout reported the last one-launch
-//   last_grid            grid of an EARLIER session until the new one launched
+//   small_mode, xphase,  read only under flags their family sets; last_grid, last_wpb: prcg_debug_layout reported the last
+//   last_grid, last_wpb  launch of an EARLIER session until the new one launched
 struct Session {
     bool in_session = false;
     int variant = -1;
@@ -199,7 +199,8 @@ struct Session {
     int pend_parts = 0;          // dots[pend_k] exist only as this many block partials ...
     int pend_k = -1;             // ... of iteration pend_k, in pend_buf
     double* pend_buf = nullptr;
-    int last_grid = 0;           // workgroups of the last one-launch iteration (prcg_debug_layout)
+    int last_grid = 0;           // workgroups of the session's last launch that left inner-product partials (prcg_debug_layout) ...
+    int last_wpb = 0;            // ... and its waves per workgroup (window operators: what launch_win_v instantiated; else 0)
 };
 
 }  // namespace
@@ -382,13 +383,23 @@ TileRange tile_range(const prcg_t* h, int which) {
 CsrDev csr_view(const prcg_t* h, int which) {
     return which == 0 ? h->csr() : (which == 1 ? h->csr(0, h->nt_bnd == 0) : h->csr(h->nt_int, false));
 }
+// The launch that left inner-product partials last -- what prcg_debug_layout reports: on a window operator the workgroups and
+// waves per workgroup launch_win_v used (win_last_launch: call this right behind the launch), else the grid alone.
+void note_partials_launch(prcg_t* h, int grid) {
+    if (grid <= 0) return;
+    const WinLaunchShape s = h->win ? win_last_launch() : WinLaunchShape{grid, 0};
+    h->last_grid = s.grid; h->last_wpb = s.wpb;
+}
 int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, SpmvEpilogue epi, const double* ep_r,
              const double* ep_d, double* ep_st, double* partials) {
     SRCCHK(h, {x, 1});
     const TileRange t = tile_range(h, which);
-    if (h->win)
-        return launch_win_spmv(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, x, y, epi, ep_r, ep_d, ep_st, partials,
-                               h->opt.win_per_cu);
+    if (h->win) {
+        const int grid = launch_win_spmv(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, x, y, epi, ep_r, ep_d, ep_st, partials,
+                                         h->opt.win_per_cu);
+        if (epi != kEpiNone) note_partials_launch(h, grid);
+        return grid;
+    }
     if (h->sell)
         return launch_sell_spmv(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.sell_per_cu);
     return launch_spmv(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.kn);
@@ -571,7 +582,10 @@ int record(prcg_t* h, int k) {
         // e = x - x_true; e'(A e)   callbacks/error_A_norm.py:47-48
         launch_sub(h->sc, h->e_ext.d(), 1, x_ptr(h), x_stride(h), h->xt.d(), 1, n);
         int grid = 0;
+        // (a recorder's product, no inner product of the method: prcg_debug_layout keeps the iteration's launch)
+        const int it_grid = h->last_grid, it_wpb = h->last_wpb;
         if ((rc = dist_spmv(h, h->e_ext.d(), h->t1.d(), kEpiDotXY, nullptr, nullptr, nullptr, &grid))) return rc;
+        h->last_grid = it_grid; h->last_wpb = it_wpb;
         launch_reduce_final(h->sc, h->partB.d(), grid, dots_at(h, k), 0, PRCG_S_ERRA2, 1);
     }
     return allreduce(h, dots_at(h, k) + PRCG_S_RES2, 3, h->sc);
@@ -776,7 +790,8 @@ int iterate_pipe_fused(prcg_t* h, int k) {
     const int grid = eng_fused(h, h->sc, f);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-    h->pend_parts = grid; h->pend_k = k; h->pend_buf = part_out; h->last_grid = grid;
+    h->pend_parts = grid; h->pend_k = k; h->pend_buf = part_out;
+    note_partials_launch(h, grid);
     h->rs_cur = rs_new;
     return PRCG_OK;
 }
@@ -827,7 +842,7 @@ int iterate_pipe_fused_comm(prcg_t* h, int k) {
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
     const int g1 = eng_fused(h, h->sc, f, 0);
     LAUNCHCHK(h, g1);
-    h->last_grid = g1;
+    note_partials_launch(h, g1);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     if (h->peer) {
         h->pend_parts = g1; h->pend_k = k; h->pend_buf = part_out;
@@ -1103,6 +1118,7 @@ int iterate_hs_fused(prcg_t* h, int k) {
                              h->prec ? h->rt.d() : h->r.d(), h->p_cur, p_new, h->s.d(), h->partB.d(), coef_at(h, k), hs,
                              h->opt.win_per_cu);
         LAUNCHCHK(h, grid);
+        note_partials_launch(h, grid);
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->p_cur = p_new;
     } else {
@@ -1166,7 +1182,8 @@ int iterate_pr_fused(prcg_t* h, int k) {
                                        (meurant(h->variant) ? 1 : 0) | (h->stream_stores ? 2 : 0), part_out, coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-    h->pend_parts = grid; h->pend_k = k; h->pend_buf = part_out; h->last_grid = grid;
+    h->pend_parts = grid; h->pend_k = k; h->pend_buf = part_out;
+    note_partials_launch(h, grid);
     if (h->pr_packed) h->q_cur = f.pr.q_new;
     else { z_cur = z_new; zs_cur = zs_new; h->p_cur = p_new; }
     return PRCG_OK;
@@ -1265,6 +1282,7 @@ int iterate_cgcg_fused(prcg_t* h, int k) {
     const int grid = launch_win_cg_w(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f, h->w.d(),
                                      h->partB.d(), coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
+    note_partials_launch(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     h->cur_r = r_new;
     on = false;
@@ -1290,6 +1308,7 @@ int iterate_gv_fused(prcg_t* h, int k) {
     const int grid = launch_win_gv_w(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f, h->tvec.d(),
                                      h->partB.d(), coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
+    note_partials_launch(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     h->cur_w = w_new;
     on = false;
@@ -1363,6 +1382,7 @@ int iterate_cg_one(prcg_t* h, int k) {
     const int grid = launch_win_cg_one(h->sc, h->wdev(), h->wtile_ptr(0), h->nwt_int + h->nwt_bnd, h->win_geom, f, gv ? 1 : 0, part_out,
                                        coef_at(h, k), h->opt.win_per_cu);
     LAUNCHCHK(h, grid);
+    note_partials_launch(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     if (gv) { h->cur_w = z0n; h->cur_t = z1n; h->cur_u = z2n; }
     else { h->cur_r = z0n; h->cur_w = z1n; h->cur_s = z2n; }
@@ -3420,8 +3440,11 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity) {
     out[1] = h->win ? h->win_geom : -1;
     out[2] = h->win ? h->win_rows : 0;
     out[3] = nt;
-    out[4] = h->last_grid;                                                        // workgroups of the last one-launch iteration
-    out[5] = h->win ? win_fused_waves_per_block(h->win_geom, h->win_vd, h->fused_comm, h->nwt_int + h->nwt_bnd, h->opt.want_big, h->sweep_waves) : 4;
+    // the session's last launch that left inner-product partials: its workgroups and, on a window operator, the waves per
+    // workgroup it ran with (before any such launch: what the one-launch pipelined iteration would take)
+    out[4] = h->last_grid;
+    out[5] = !h->win ? 4 : (h->last_grid > 0 ? h->last_wpb
+                            : win_fused_waves_per_block(h->win_geom, h->win_vd, h->fused_comm, h->nwt_int + h->nwt_bnd, h->opt.want_big, h->sweep_waves));
     out[6] = h->win ? h->nwt_int : h->nt_int;
     out[7] = h->win ? (int64_t)h->sweep_waves << 8 : 0;    // bit 0: always 0 (was the retired XCD-chunked tile order); >> 8: waves of a sweep table
     std::vector<int32_t> rows((size_t)nt * 2);

@@ -1402,6 +1402,8 @@ template <int NV, int EPI, int M, int PG, int CW, bool vd, bool DEFER, bool BIG 
 int launch_win_v(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, const void* x, void* y, int write_mask,
                  const double* ep_r, const double* ep_d, double* ep_st, double* partials, double* aux, FusedPrev fz,
                  int per_cu, hipEvent_t done);
+// what launch_win_v launched last on this thread (win_last_launch)
+thread_local WinLaunchShape t_last_launch{0, 0};
 
 template <int NV, int EPI, int M, int PG, int CW, bool DEFER = false>
 int launch_win_g(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, const void* x, void* y, int write_mask,
@@ -1475,6 +1477,7 @@ int launch_win_v(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles
     else
         hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WPB), 0, st, A, reinterpret_cast<const int4*>(tiles), ntiles, x, y,
                            write_mask, ep_r, ep_d, ep_st, partials, aux, fz);
+    t_last_launch = WinLaunchShape{grid, WPB};
     return hipGetLastError() == hipSuccess ? grid : -1;
 }
 
@@ -1495,6 +1498,8 @@ int launch_win(int geom, hipStream_t st, const WinDev& A, const WTile* tiles, in
 }
 
 }  // namespace
+
+WinLaunchShape win_last_launch() { return t_last_launch; }
 
 int win_fused_waves_per_block(int geom, bool value_dict, bool deferred, int ntiles, bool big_ok, int sweep_waves) {
     if (deferred) {

@@ -401,8 +401,10 @@ class DeviceCSR:
                 'rhs4': bool(s & 33554432), 'spmm4': bool(s & 67108864), 'rhs2_pipe': bool(s & 134217728)}
 
     def layout(self):
-        """Diagnostic (prcg.h: prcg_debug_layout): what the summation order of the one-launch iteration's inner
-        products depends on -- tile rows in table order, workgroups and waves per workgroup of the last launch."""
+        """Diagnostic (prcg_test.h: prcg_debug_layout): what the summation order of a tile launch's inner products depends
+        on -- tile rows in table order, and 'grid' / 'waves_per_block' of the session's LAST launch that left inner-product
+        partials (any schedule's iteration launch, or the start-up products right after begin(); never a recorder's;
+        grid 0: none yet).  Every session leaves the partials of an iteration from ONE tile launch, so one pair suffices."""
         need = -int(self._lib.prcg_debug_layout(self._h, L.ptr(np.zeros(1, dtype=np.int64)), 0))
         out = np.zeros(max(need, 8), dtype=np.int64)
         got = int(self._lib.prcg_debug_layout(self._h, L.ptr(out), out.size))

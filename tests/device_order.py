@@ -22,6 +22,19 @@ bench.py times and every solve uses by default): its inner products are summed
           by k_reduce_final when a prcg_iterate call ends: the same tree either way
 
 built from DeviceCSR.layout() (prcg.h: prcg_debug_layout: tile rows, grid, waves per workgroup).
+
+EVERY launch of k_win_tiles that leaves inner-product partials sums them this way, whatever its epilogue (one per-lane
+acc[5] over the wave's tiles, win_block_reduce_store, the 256-thread final tree): the one-launch predict-and-recompute,
+Chronopoulos-Gear and Ghysels-Vanroose iterations, their two-launch forms, the Hestenes-Stiefel product launch and the
+products with a dot epilogue at a session's start.  Only the workgroup count and the waves per workgroup differ from launch
+to launch; layout() reports those of the session's last such launch.
+
+The update kernels other than k_pipe_update (k_hs_update_xr, k_pr_update, k_gv_update1, k_dot: prcg_kernels.hip) give each
+thread two NEIGHBOURING elements per trip -- thread (block b, lane t): elements (b*trips + j)*512 + 2t, then + 1 -- and the
+same wave / block / final tree: ``pair_sum``.
+
+``Routed`` lets a schedule whose inner products come from different launches (Hestenes-Stiefel: nu from the update
+kernel, mu from the tile launch) plug into the oracle: the oracle calls ``dot`` in a fixed order per advance.
 """
 import numpy as np
 
@@ -79,6 +92,30 @@ def device_sum(prod):
     return float(out)
 
 
+def pair_sum(prod):
+    """k_hs_update_xr / k_pr_update / k_gv_update1 / k_dot: thread t of block b sums elements (b*trips + j)*512 + 2t and + 1,
+    j = 0..trips-1, in that order; then as device_sum.  Returns np.float64."""
+    prod = np.asarray(prod, dtype=np.float64)
+    n = prod.shape[0]
+    grid, trips = chunking(n)
+    padded = np.zeros(grid * trips * ELEMS_PER_TRIP)
+    padded[:n] = prod
+    a = padded.reshape(grid, trips, 256, 2)
+    acc = np.zeros((grid, 256))
+    for j in range(trips):
+        for e in range(2):
+            acc = acc + a[:, j, :, e]
+    waves = _butterfly(acc.reshape(grid, 4, 64))
+    partial = waves[:, 0]
+    for w in range(1, 4):
+        partial = partial + waves[:, w]
+    return _final_tree(partial)
+
+
+def pair_dot(a, b):
+    return pair_sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
 def device_dot(a, b):
     return device_sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
 
@@ -105,11 +142,36 @@ def _final_tree(partial):
     out = wf[0]
     for w in range(1, FINAL_THREADS // 64):
         out = out + wf[w]
-    return float(out)
+    return np.float64(out)        # (not a Python float: the oracle's nu / mu must give inf / nan at a breakdown, not raise)
+
+
+class Routed:
+    """dot(a, b) for the oracle that sends its i-th call to sums[i % len(sums)] (each a callable on the array of products):
+    the order in which a ``*_start`` / ``*_advance`` of oracle/ne_oracle.py asks for its inner products is fixed --
+    hs: nu, mu;  cg_cg and gv: nu, eta (start: then mu);  pr: mu, delta, gamma, nu (start: nu first)."""
+
+    def __init__(self, *sums):
+        self.sums, self.calls = sums, 0
+
+    def __call__(self, a, b):
+        s = self.sums[self.calls % len(self.sums)]
+        self.calls += 1
+        return np.float64(s(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64)))
+
+
+def first_mismatch(got, want):
+    """first row at which two (iterations, slots) arrays differ in any bit, -1 if none.  NaN never equals NaN here: a
+    trajectory comparison holds only where both sides are numbers."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = ~(got == want)
+    bad = bad.reshape(bad.shape[0], -1).any(axis=1)
+    return int(np.argmax(bad)) if bad.any() else -1
 
 
 class OneLaunchTree:
-    """The summation order of the inner products of the one-launch pipelined iteration on a window operator."""
+    """The summation order of the inner products a launch of k_win_tiles leaves (the one-launch pipelined iteration and every
+    other epilogue with partials): built from layout()'s tile rows, workgroups and waves per workgroup of that launch."""
 
     def __init__(self, layout):
         assert layout['window'] and layout['grid'] > 0, layout
