@@ -30,7 +30,7 @@ $(CSRC)/prcg_blockjac.o: $(CSRC)/prcg_blockjac.hip $(CSRC)/prcg_kernels.h $(CSRC
 $(CSRC)/prcg_rhs2.o: $(CSRC)/prcg_rhs2.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
-$(CSRC)/prcg_engine.o: $(CSRC)/prcg_engine.cpp $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_plan.h $(CSRC)/prcg_rccl.h include/prcg.h include/prcg_test.h
+$(CSRC)/prcg_engine.o: $(CSRC)/prcg_engine.cpp $(CSRC)/prcg_kernels.h $(CSRC)/prcg_bjvar.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_plan.h $(CSRC)/prcg_rccl.h include/prcg.h include/prcg_test.h
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
 $(CSRC)/prcg_plan.o: $(CSRC)/prcg_plan.cpp $(CSRC)/prcg_plan.h $(CSRC)/prcg_geometry.h

@@ -316,6 +316,41 @@ int prcg_build_block_jacobi(prcg_t* h, int bs, int64_t* first_bad_block);
 /* The blocks now on the handle, whichever call set them: inv_blocks receives nb x bs x bs host doubles, row-major (bs: the one
  * they were set with); a short last block comes back as its leading m x m part inside an identity.  PRCG_EINVAL without blocks. */
 int prcg_get_block_jacobi(prcg_t* h, double* inv_blocks);
+/* Point-block Jacobi with VARIABLE block sizes, applied and built on the device: the blocks follow the nodes of a mesh whose nodes
+ * carry different numbers of unknowns (shells next to solids, constrained nodes, mixed elements), where no uniform bs lines up.
+ * No counterpart in the reference; the counterpart elsewhere is PETSc's `-pc_type vpbjacobi`, next to pbjacobi above.
+ *   partition  block_ptr: nb + 1 int64 host entries, block_ptr[0] == 0, block_ptr[nb] == n_rows, every size
+ *              m_k = block_ptr[k+1] - block_ptr[k] in 1..8.  Block k owns rows -- and the same columns -- block_ptr[k] .. block_ptr[k+1]-1.
+ *   packed     inv_blocks holds block k as m_k x m_k doubles, row-major, at offset sum of m_q^2 over q < k: no padding, no identity fill.
+ *   apply      row i = block_ptr[k] + a of the result is
+ *                  acc = B_k[a][0] * v[block_ptr[k]];   acc = acc + B_k[a][j] * v[block_ptr[k] + j]   for j = 1 .. m_k-1, ascending,
+ *              every product and every sum rounded (no FMA) -- word for word the loop of prcg_set_block_jacobi, so that on a uniform
+ *              partition (a short last block included) the result has the bits of prcg_set_block_jacobi with the same inverses.
+ *   build      gather: row i of block k starts with g[c] = +0.0, c < m_k; for q = indptr[i] .. indptr[i+1]-1 ascending: if
+ *              block_ptr[k] <= indices[q] < block_ptr[k+1] then g[indices[q] - block_ptr[k]] = g[...] + data[q].  Unsorted rows and
+ *              duplicates are legal; duplicates add in CSR order.  invert: the Gauss-Jordan loop of prcg_build_block_jacobi on the
+ *              m_k x m_k block for exactly m_k steps -- no pivoting, the pivot row divided (not multiplied by a reciprocal), every
+ *              other row one product and one difference per entry.  (The uniform build of a short last block, padded with an identity
+ *              and run for bs steps, leaves exactly these bits in its leading m x m part: a uniform partition gives the uniform
+ *              build's bits.)  bad: as there -- a pivot zero or not finite at its step, or an entry of E not finite.
+ * State and life cycle are those of the uniform calls: call after prcg_set_csr; a later prcg_set_csr drops the blocks, a later
+ * prcg_update_values leaves them frozen; prcg_set_block_jacobi, prcg_build_block_jacobi, these two setters and
+ * prcg_set_preconditioner replace each other, the last one is in force; inv_blocks == NULL in the setter removes the blocks.
+ * Sessions begun with inv_diag == NULL while variable blocks are set run the stored-tilde schedule exactly as a uniform block-Jacobi
+ * session does, with the variable kernels where M^-1 is applied (one vector, or the pair [w u] of the pipelined variants in one
+ * launch); prcg_schedule reports PRCG_SCHED_BLOCK_JACOBI | PRCG_SCHED_BLOCK_JACOBI_VAR.  The multi-RHS sessions refuse them as
+ * they refuse uniform blocks.  The partition is cut into tiles on the host in O(nb); the matrix is never touched there.
+ * Refused (PRCG_EINVAL, the text names the reason, the handle is untouched -- blocks set before stay in force): no operator; null
+ * block_ptr; block_ptr[0] != 0 or block_ptr[nb] != n_rows; a size outside 1..8 (the text names the first such block and its size);
+ * for the build also n_ghost > 0, a communicator or a world size > 1.
+ * prcg_build_block_jacobi_var with a bad block: PRCG_EINVAL, text "diagonal block K (size M) is singular or not finite", K the
+ * smallest such index, *first_bad_block = K (nullable; -1 otherwise), and the handle is left WITHOUT blocks.
+ * prcg_get_block_jacobi_var returns the blocks now on the handle in the packed format; it refuses while the blocks on the handle
+ * are uniform (use prcg_get_block_jacobi), as prcg_get_block_jacobi refuses while they are variable. */
+int prcg_set_block_jacobi_var(prcg_t* h, int64_t nb, const int64_t* block_ptr, const double* inv_blocks);
+int prcg_build_block_jacobi_var(prcg_t* h, int64_t nb, const int64_t* block_ptr, int64_t* first_bad_block);
+int prcg_get_block_jacobi_var(prcg_t* h, double* inv_blocks);   /* packed, as above */
+#define PRCG_SCHED_BLOCK_JACOBI_VAR 268435456   /* set together with PRCG_SCHED_BLOCK_JACOBI: the blocks have variable sizes */
 int prcg_schedule(const prcg_t* h);
 /* Bytes of the operator AS THE DEVICE STREAMS IT (the lossless re-encodings of the caller's CSR built at
  * prcg_set_csr: narrow column / window indices, value-dictionary indices, relative row pointers, tile

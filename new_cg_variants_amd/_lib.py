@@ -72,6 +72,9 @@ _SIGNATURES = {
     'prcg_set_block_jacobi': (C.c_int, [_P, C.c_int, _P]),
     'prcg_build_block_jacobi': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'prcg_get_block_jacobi': (C.c_int, [_P, _P]),
+    'prcg_set_block_jacobi_var': (C.c_int, [_P, C.c_int64, _P, _P]),
+    'prcg_build_block_jacobi_var': (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    'prcg_get_block_jacobi_var': (C.c_int, [_P, _P]),
     'prcg_set_replace_hook': (C.c_int, [_P, _P, _P]),
     'prcg_schedule': (C.c_int, [_P]),
     'prcg_operator_bytes': (C.c_int64, [_P]),

@@ -21,7 +21,9 @@ Differences, all at the edges:
   PETSc calls pbjacobi) is applied on the device too, by a kernel of its own, and is never
   called (prcg.h: prcg_set_block_jacobi); ``DeviceBlockJacobi(A, bs)`` has the same blocks built on
   the device from the resident operator, without a host pass over the matrix (prcg.h:
-  prcg_build_block_jacobi); any other callable is the caller's code, as it is
+  prcg_build_block_jacobi); ``VarBlockJacobi(A, block_ptr)`` and ``DeviceVarBlockJacobi(A, block_ptr)`` are the two
+  for blocks of VARIABLE size that follow a partition (PETSc's vpbjacobi; prcg.h: prcg_set_block_jacobi_var,
+  prcg_build_block_jacobi_var); any other callable is the caller's code, as it is
   in the reference, and is called on the host wherever the reference calls
   ``preconditioner(...)`` (prcg.h: prcg_set_preconditioner) while products, updates and
   inner products stay on the device;
@@ -341,6 +343,151 @@ class DeviceBlockJacobi:
         return BlockJacobi.__call__(self, v)
 
 
+def _checked_partition(who, block_ptr, n):
+    """block_ptr as int64, refused with the reasons of prcg_set_block_jacobi_var (prcg.h)"""
+    ptr = np.ascontiguousarray(block_ptr, dtype=np.int64)
+    if ptr.ndim != 1 or ptr.size < 1:
+        raise ValueError(f'{who}: block_ptr must be a one-dimensional array of nb + 1 entries, got shape {ptr.shape}')
+    if ptr[0] != 0:
+        raise ValueError(f'{who}: block_ptr[0] is {int(ptr[0])}, not 0')
+    if ptr[-1] != n:
+        raise ValueError(f'{who}: block_ptr[nb] is {int(ptr[-1])}, not n_rows = {n}')
+    sizes = np.diff(ptr)
+    off = (sizes < 1) | (sizes > 8)
+    if off.any():
+        k = int(np.argmax(off))
+        raise ValueError(f'{who}: block {k} has size {int(sizes[k])}, outside 1..8')
+    return ptr
+
+
+class VarBlockJacobi:
+    """Point-block Jacobi with VARIABLE block sizes (PETSc's vpbjacobi): the inverses of the diagonal blocks of A that follow a
+    partition -- block k owns rows and columns block_ptr[k] .. block_ptr[k+1]-1, every size in 1..8 -- for matrices whose nodes
+    carry different numbers of unknowns (problems.fem_irregular_blocks gives the nodal partition of fem_irregular_3d).  As
+    BlockJacobi: gathered on the host, inverted by LAPACK; passed as `preconditioner` to a *_pcg function it is applied on the
+    device (prcg.h: prcg_set_block_jacobi_var) and never called; called, it evaluates the same arithmetic with NumPy --
+
+        acc = B_k[a][0] * v[block_ptr[k]];   acc = acc + B_k[a][j] * v[block_ptr[k] + j]   for j = 1 .. m_k-1
+
+    `inv_blocks`: PACKED, block k as m_k x m_k row-major at offset sum of m_q^2 over q < k; `block_ptr`; `n`."""
+
+    _NAME = 'VarBlockJacobi'
+
+    def __init__(self, A, block_ptr):
+        if A.format != 'csr':
+            A = A.tocsr()
+        self.n = A.shape[0]
+        self.block_ptr = _checked_partition(self._NAME, block_ptr, self.n)
+        self._layout()
+        packed = self._gather(A)
+        inv = np.empty_like(packed)
+        bad = np.zeros(self.block_ptr.size - 1, dtype=bool)
+        with np.errstate(all='ignore'):
+            for m, ks, at in self._groups:
+                G = packed[at]
+                fin = np.isfinite(G).all(axis=(1, 2))
+                G = np.where(fin[:, None, None], G, np.eye(m))
+                try:
+                    E = np.linalg.inv(G)
+                except np.linalg.LinAlgError:
+                    E = np.full(G.shape, np.nan)
+                    for q in range(G.shape[0]):
+                        try:
+                            E[q] = np.linalg.inv(G[q])
+                        except np.linalg.LinAlgError:
+                            pass
+                bad[ks] = ~fin | ~np.isfinite(E).all(axis=(1, 2))
+                inv[at] = E
+        if bad.any():
+            k = int(np.argmax(bad))
+            raise ValueError(f'{self._NAME}: diagonal block {k} (size {int(self._sizes[k])}) is singular or not finite')
+        self.inv_blocks = inv
+
+    def _layout(self):
+        """per block size m: the blocks of that size, and the index array (count, m, m) of their entries in the packed array"""
+        ptr = self.block_ptr
+        self._sizes = np.diff(ptr)
+        self._offsets = np.concatenate([[0], np.cumsum(self._sizes ** 2)]).astype(np.int64)
+        self._groups = []
+        for m in range(1, 9):
+            ks = np.flatnonzero(self._sizes == m)
+            if ks.size:
+                at = self._offsets[ks][:, None, None] + (np.arange(m)[:, None] * m + np.arange(m)[None, :])[None]
+                self._groups.append((m, ks, at))
+
+    def _gather(self, A):
+        """The diagonal blocks of CSR A, packed: per row g = +0.0, then the row's entries whose column lies in the row's block
+        added in CSR order (np.add.at adds one by one, in the order given) -- the gather of prcg_build_block_jacobi_var."""
+        ptr, n = self.block_ptr, self.n
+        packed = np.zeros(int(self._offsets[-1]))
+        if n == 0:
+            return packed
+        block_of = np.repeat(np.arange(ptr.size - 1), self._sizes)
+        indptr, indices, data = A.indptr, A.indices, A.data
+        chunk, r0 = BlockJacobi._CHUNK, 0
+        while r0 < n:
+            r1 = int(np.searchsorted(indptr, indptr[r0] + chunk, side='right')) - 1
+            r1 = min(max(r1, r0 + 1), n)
+            lo, hi = int(indptr[r0]), int(indptr[r1])
+            rows = np.repeat(np.arange(r0, r1), np.diff(indptr[r0:r1 + 1]))
+            cols = indices[lo:hi].astype(np.int64)
+            k = block_of[rows]
+            keep = (cols >= ptr[k]) & (cols < ptr[k + 1])
+            rows, cols, k = rows[keep], cols[keep], k[keep]
+            np.add.at(packed, self._offsets[k] + (rows - ptr[k]) * self._sizes[k] + (cols - ptr[k]), data[lo:hi][keep])
+            r0 = r1
+        return packed
+
+    def __call__(self, v):
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape != (self.n,):
+            raise ValueError(f'{self._NAME}: expected a vector of {self.n} entries, got shape {v.shape}')
+        inv, out = self.inv_blocks, np.empty(self.n)
+        for m, ks, at in self._groups:
+            rows = self.block_ptr[ks][:, None] + np.arange(m)[None, :]
+            B, V = inv[at], v[rows]
+            acc = B[:, :, 0] * V[:, 0:1]
+            for j in range(1, m):
+                acc = acc + B[:, :, j] * V[:, j:j + 1]
+            out[rows] = acc
+        return out
+
+
+class DeviceVarBlockJacobi(VarBlockJacobi):
+    """VarBlockJacobi whose inverses are BUILT ON THE DEVICE from the operator (prcg.h: prcg_build_block_jacobi_var): passed as
+    `preconditioner` to a *_pcg function, the matrix is never touched on the host; a later solve on the same operator with the
+    same partition reuses the blocks, and a solve after update_values(A) builds them again -- DeviceBlockJacobi for a partition.
+    The inversion is the fixed loop of prcg.h (Gauss-Jordan without pivoting, m_k steps on block k), not LAPACK's.
+    Called, the object builds `inv_blocks` on the host on first use with the restatement of the device arithmetic -- the
+    per-block gather in CSR order, then invert_blocks per group of equal size -- hence with the device's bits, from the values
+    ``A`` holds at that moment.  A bad block raises ValueError('DeviceVarBlockJacobi: diagonal block K (size M) is singular or
+    not finite') there as on the device path."""
+
+    _NAME = 'DeviceVarBlockJacobi'
+
+    def __init__(self, A, block_ptr):
+        if A.format != 'csr':
+            A = A.tocsr()
+        self.A, self.n = A, A.shape[0]
+        self.block_ptr = _checked_partition(self._NAME, block_ptr, self.n)
+        self._inv_blocks = None
+
+    @property
+    def inv_blocks(self):
+        if self._inv_blocks is None:
+            self._layout()
+            packed = self._gather(self.A)
+            inv = np.empty_like(packed)
+            bad = np.zeros(self.block_ptr.size - 1, dtype=bool)
+            for m, ks, at in self._groups:
+                inv[at], bad[ks] = invert_blocks(packed[at])
+            if bad.any():
+                k = int(np.argmax(bad))
+                raise ValueError(f'{self._NAME}: diagonal block {k} (size {int(self._sizes[k])}) is singular or not finite')
+            self._inv_blocks = inv
+        return self._inv_blocks
+
+
 _STATE_NAMES = {   # device vector -> the reference's local name
     'x': 'x_k', 'r': 'r_k', 'p': 'p_k', 's': 's_k', 'w': 'w_k', 'u': 'u_k',
     'rt': 'rt_k', 'st': 'st_k', 'wt': 'wt_k', 'ut': 'ut_k',
@@ -365,9 +512,10 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         A = A.tocsr()
     n = A.shape[0]
     built = isinstance(preconditioner, DeviceBlockJacobi)      # blocks built on the device: the object is neither probed nor read
-    if built:
+    var = isinstance(preconditioner, VarBlockJacobi)           # variable block sizes (either class): recognised before any probing
+    if built or var:
         if preconditioner.n != n:
-            raise ValueError(f'DeviceBlockJacobi: made for a matrix of {preconditioner.n} rows, the system has {n}')
+            raise ValueError(f'{type(preconditioner).__name__}: made for a matrix of {preconditioner.n} rows, the system has {n}')
         inv_diag, prec_fn = None, preconditioner
     else:
         inv_diag, prec_fn = _diagonal_of(preconditioner, n)
@@ -411,8 +559,17 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         op.set_replace_hook(hook)
     else:
         op.set_replace_hook(None)
-    blocks = _blocks_of(prec_fn) if prec_fn is not None and not built else None
-    if built:
+    blocks = _blocks_of(prec_fn) if prec_fn is not None and not built and not var else None
+    if var:
+        on_device = isinstance(preconditioner, DeviceVarBlockJacobi)       # built there: the object's blocks are never read
+        try:
+            op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask,
+                     block_jacobi_var=(preconditioner.block_ptr, None if on_device else preconditioner.inv_blocks))
+        except ValueError as e:
+            if 'diagonal block' not in str(e):
+                raise
+            raise ValueError('DeviceVarBlockJacobi: ' + str(e).split(': ', 1)[-1]) from None
+    elif built:
         try:
             op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=(preconditioner.bs, None))
         except ValueError as e:
@@ -477,12 +634,12 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
     for key in ('x_true', 'w_replace'):
         if kwargs.get(key) is not None:
             raise ValueError(f'{name}: {key} is not served by the two-RHS session')
-    if isinstance(preconditioner, DeviceBlockJacobi):
+    if isinstance(preconditioner, (DeviceBlockJacobi, VarBlockJacobi)):
         inv_diag, prec_fn = None, preconditioner
     else:
         inv_diag, prec_fn = _diagonal_of(preconditioner, n)
     if prec_fn is not None:
-        kind = 'a block-Jacobi preconditioner' if isinstance(prec_fn, DeviceBlockJacobi) or _blocks_of(prec_fn) is not None else 'a preconditioner that is no diagonal scaling'
+        kind = 'a block-Jacobi preconditioner' if isinstance(prec_fn, (DeviceBlockJacobi, VarBlockJacobi)) or _blocks_of(prec_fn) is not None else 'a preconditioner that is no diagonal scaling'
         raise ValueError(f'{name}: {kind} is not served by the two-RHS session (Jacobi(A), a callable that acts as a diagonal, or None)')
     mask = 0
     light = []
@@ -635,4 +792,4 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
            'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
-           'invert_blocks', 'DeviceBlockJacobi']
+           'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi']

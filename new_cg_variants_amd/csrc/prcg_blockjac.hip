@@ -178,7 +178,169 @@ void launch_build(hipStream_t st, double* blk, int64_t n, const int* indptr, con
     hipLaunchKernelGGL(k_block_jacobi_build<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, blk, n, indptr, col, val, first_bad);
 }
 
+// ---- variable block sizes (prcg_set_block_jacobi_var / prcg_build_block_jacobi_var; PETSc's -pc_type vpbjacobi): block k owns
+// rows block_ptr[k] .. block_ptr[k+1]-1, every size in 1..8.  The arithmetic is word for word that of the kernels above, the loop
+// over j bounded by the row's own size m instead of a template parameter.  The device layout is prcg_bjvar.h's: a TILE is a run of
+// consecutive whole blocks with at most 256 rows (no block straddles a workgroup); the tile table gives a workgroup its first
+// row and its first LINE, a code byte gives a lane its index a in its block and the block's size m (one coalesced byte load).
+// Coalescing: entry j of the row of lane t of tile T sits at (line0[T] + j) * 256 + t, so for a fixed j the lanes of a wave read
+// consecutive doubles, as above; a lane loads only j < m, so in a mix of sizes the lines j >= 3, say, are touched by the runs of
+// lanes whose blocks are that wide (a run of six lanes is 48 of a 64-byte sector).  A row moves (m + 2) * 8 + 1 useful bytes.
+// The eight loads are unrolled and predicated (j < m), not a loop with a data-dependent trip count: all are in flight together.
+// LDS: a lane reads sv[c0 + j] for j < m only, i.e. inside its own block's lanes; the arrays carry 8 spare entries so that even
+// a load hoisted above its predicate stays inside them.
+constexpr int kBjvPad = 8;
+constexpr int kBjvDeadBit = 0x80;     // prcg_bjvar.h: kBjvDead
+
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var(double* __restrict__ dst, int ds, const double* __restrict__ src, int ss,
+                                                               const long long* __restrict__ tiles, const unsigned char* __restrict__ code,
+                                                               const double* __restrict__ blk) {
+    __shared__ double sv[kBjBlock + kBjvPad];
+    const int t = threadIdx.x;
+    const long long* tw = tiles + (int64_t)blockIdx.x * 4;
+    const int64_t i = tw[0] + t;
+    const int cd = code[(int64_t)blockIdx.x * kBjBlock + t];
+    const bool live = !(cd & kBjvDeadBit);
+    if (live) sv[t] = src[i * ss];
+    __syncthreads();
+    if (!live) return;
+    const int a = cd & 7, m = ((cd >> 3) & 7) + 1;
+    const int c0 = t - a;                                 // first lane of this row's block
+    const double* bp = blk + tw[1] * kBjBlock + t;
+    double b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = j < m ? bp[(int64_t)j * kBjBlock] : 0.0;
+    double acc = b[0] * sv[c0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j)
+        if (j < m) acc = acc + b[j] * sv[c0 + j];
+    dst[i * ds] = acc;
+}
+
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_pair(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                                    const long long* __restrict__ tiles, const unsigned char* __restrict__ code,
+                                                                    const double* __restrict__ blk, int mask) {
+    __shared__ d2_t sv[kBjBlock + kBjvPad];
+    const int t = threadIdx.x;
+    const long long* tw = tiles + (int64_t)blockIdx.x * 4;
+    const int64_t i = tw[0] + t;
+    const int cd = code[(int64_t)blockIdx.x * kBjBlock + t];
+    const bool live = !(cd & kBjvDeadBit);
+    if (live) sv[t] = wu[i];
+    __syncthreads();
+    if (!live) return;
+    const int a = cd & 7, m = ((cd >> 3) & 7) + 1;
+    const int c0 = t - a;
+    const double* bp = blk + tw[1] * kBjBlock + t;
+    double b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = j < m ? bp[(int64_t)j * kBjBlock] : 0.0;
+    d2_t v = sv[c0];
+    double aw = b[0] * v.x, au = b[0] * v.y;
+#pragma unroll
+    for (int j = 1; j < 8; ++j)
+        if (j < m) {
+            v = sv[c0 + j];
+            aw = aw + b[j] * v.x;
+            au = au + b[j] * v.y;
+        }
+    if (mask & 1) wt[i] = aw;
+    if (mask & 2) ut[i] = au;
+}
+
+// the device build for a partition: k_block_jacobi_build's scheme, lane per row, with the row's own m.
+//   * the row walk needs no block_ptr: the row's block owns columns [row0 + c0, row0 + c0 + m);
+//   * the steps are bounded by L, the tile's largest size (uniform over the workgroup, so every lane meets every barrier); a
+//     lane takes part in step c only if c < m, and touches only entries j < m of its rows of M and E;
+//   * the pivot row is parked in the slots of the block's own lanes: pm / pe[parity][c0 + j], j < m (8 KB whatever the sizes);
+//   * every slot of the tile's L lines is written: E[j] for j < m, 0.0 elsewhere (the layout's "slots never loaded hold 0.0").
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_build(double* __restrict__ blk, const long long* __restrict__ tiles,
+                                                                     const unsigned char* __restrict__ code, const unsigned char* __restrict__ bidx,
+                                                                     const int* __restrict__ indptr, const int* __restrict__ col,
+                                                                     const double* __restrict__ val, long long* __restrict__ first_bad) {
+    __shared__ double pm[2][kBjBlock + kBjvPad], pe[2][kBjBlock + kBjvPad];
+    const int t = threadIdx.x;
+    const long long* tw = tiles + (int64_t)blockIdx.x * 4;
+    const int64_t row0 = tw[0], i = row0 + t;
+    const int L = (int)tw[3];
+    const int cd = code[(int64_t)blockIdx.x * kBjBlock + t];
+    const bool live = !(cd & kBjvDeadBit);
+    const int a = cd & 7, m = live ? ((cd >> 3) & 7) + 1 : 0;
+    const int c0 = t - a;
+    double M[8], E[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { M[j] = 0.0; E[j] = j == a ? 1.0 : 0.0; }
+    if (live) {
+        const int q1 = indptr[i + 1];
+        const int64_t cb = row0 + c0;                     // first column of the row's block
+        for (int q = indptr[i]; q < q1; ++q) {
+            const int64_t c = (int64_t)col[q] - cb;
+            if (c >= 0 && c < m) {
+                const double v = val[q];
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (c == j) M[j] = M[j] + v;
+            }
+        }
+    }
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        if (c < L) {                                      // uniform over the workgroup
+            double* qm = pm[c & 1] + c0;
+            double* qe = pe[c & 1] + c0;
+            if (c < m && a == c) {
+                const double p = M[c];
+                bad = bad || p == 0.0 || !(p - p == 0.0);     // zero, infinite or NaN
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j < m) { M[j] = M[j] / p; E[j] = E[j] / p; qm[j] = M[j]; qe[j] = E[j]; }
+            }
+            __syncthreads();
+            if (c < m && a != c) {
+                const double f = M[c];
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j < m) { M[j] = M[j] - f * qm[j]; E[j] = E[j] - f * qe[j]; }
+            }
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < m) bad = bad || !(E[j] - E[j] == 0.0);
+        if (bad) atomicMin(first_bad, tw[2] + (long long)bidx[(int64_t)blockIdx.x * kBjBlock + t]);
+    }
+    double* out = blk + tw[1] * kBjBlock + t;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (j < L) out[(int64_t)j * kBjBlock] = j < m ? E[j] : 0.0;
+}
+
 }  // namespace
+
+int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t ntiles, const long long* tiles,
+                            const unsigned char* code, const double* blocks) {
+    if (ntiles <= 0) return 0;
+    hipLaunchKernelGGL(k_block_jacobi_var, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, dst, dstride, src, sstride, tiles, code, blocks);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
+                                 const unsigned char* code, const double* blocks, int mask) {
+    if (ntiles <= 0) return 0;
+    hipLaunchKernelGGL(k_block_jacobi_var_pair, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), tiles,
+                       code, blocks, mask);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_block_jacobi_var_build(hipStream_t st, double* blocks, int64_t ntiles, const long long* tiles, const unsigned char* code,
+                                  const unsigned char* bidx, const int* indptr, const int* col, const double* val, long long* first_bad) {
+    if (ntiles <= 0) return 0;
+    hipLaunchKernelGGL(k_block_jacobi_var_build, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, blocks, tiles, code, bidx, indptr, col, val,
+                       first_bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int64_t block_jacobi_layout(int64_t n, int bs, const double* inv_blocks, double* out) {
     if (n < 0 || bs < 1 || bs > 8) return -1;

@@ -31,6 +31,7 @@
 #include "../../include/prcg.h"
 #include "../../include/prcg_test.h"
 #include "prcg_kernels.h"
+#include "prcg_bjvar.h"
 #include "prcg_plan.h"
 #include "prcg_rccl.h"
 
@@ -266,6 +267,15 @@ struct prcg_handle : Operator, Session {
     prcg_prec_fn cb = nullptr; void* cb_ctx = nullptr;
     int bj_bs = 0; DevBuf bj_blocks;     // bj_bs > 0: blocks set, in the layout of block_jacobi_layout
     DevBuf bj_flag;                      // one int64: smallest index of a bad block of the last device build (prcg_build_block_jacobi)
+    // ... or blocks of VARIABLE size (prcg_set_block_jacobi_var / prcg_build_block_jacobi_var): bj_var, then bj_bs == 0 and bj_blocks
+    // holds prcg_bjvar.h's layout; the partition's tile table and lane bytes on the device, the partition itself on the host (getter)
+    bool bj_var = false;
+    BjVarPlan bjv_plan; std::vector<int64_t> bjv_ptr;
+    DevBuf bjv_tiles, bjv_bytes;         // ntiles x 4 int64; code bytes (ntiles x 256) followed by block-in-tile bytes (ntiles x 256)
+    bool have_block_jacobi() const { return bj_bs > 0 || bj_var; }
+    const long long* bjv_tiles_d() const { return static_cast<const long long*>(bjv_tiles.p); }
+    const unsigned char* bjv_code_d() const { return static_cast<const unsigned char*>(bjv_bytes.p); }
+    const unsigned char* bjv_bidx_d() const { return bjv_code_d() + bjv_plan.ntiles * kBjvLanes; }
     prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
     std::vector<double> cb_in, cb_out;
     DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
@@ -625,7 +635,11 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
         if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         if (h->bj_session) {
             // block Jacobi: both columns of [w u] in one launch that reads every block once
-            LAUNCHCHK(h, launch_block_jacobi_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask));
+            if (h->bj_var)
+                LAUNCHCHK(h, launch_block_jacobi_var_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->bjv_plan.ntiles, h->bjv_tiles_d(), h->bjv_code_d(),
+                                                          h->bj_blocks.d(), mask));
+            else
+                LAUNCHCHK(h, launch_block_jacobi_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask));
         } else if (h->stored_tilde) {
             // u~ = preconditioner(u); w~ = preconditioner(w) in the flavours that recompute w (pipe_pr_cg.py:178-182)
             if ((rc = apply_prec(h, h->wu.d() + 1, 2, h->ut.d(), 1))) return rc;
@@ -1477,7 +1491,10 @@ int apply_prec(prcg_t* h, const double* src, int sstride, double* dst, int dstri
         return PRCG_OK;
     }
     if (h->bj_session) {        // one launch on the compute stream: no copy, no synchronisation
-        LAUNCHCHK(h, launch_block_jacobi(h->sc, dst, dstride, src, sstride, n, h->bj_bs, h->bj_blocks.d()));
+        if (h->bj_var)
+            LAUNCHCHK(h, launch_block_jacobi_var(h->sc, dst, dstride, src, sstride, h->bjv_plan.ntiles, h->bjv_tiles_d(), h->bjv_code_d(), h->bj_blocks.d()));
+        else
+            LAUNCHCHK(h, launch_block_jacobi(h->sc, dst, dstride, src, sstride, n, h->bj_bs, h->bj_blocks.d()));
         return PRCG_OK;
     }
     h->cb_in.resize((size_t)n); h->cb_out.resize((size_t)n);
@@ -1543,12 +1560,15 @@ bool locate(prcg_t* h, int which, double** base, int* stride) {
 
 // forget the block-Jacobi blocks; a session that applies them ends here (its launches may still be reading them: wait)
 int drop_block_jacobi(prcg_t* h) {
-    if (h->bj_bs == 0 && !h->bj_blocks.p) return PRCG_OK;
+    if (!h->have_block_jacobi() && !h->bj_blocks.p) return PRCG_OK;
     HIPCHK(h, hipSetDevice(h->dev));
     HIPCHK(h, hipStreamSynchronize(h->sc));
     if (h->bj_session) { h->in_session = false; h->bj_session = false; }
     h->bj_bs = 0;
     h->bj_blocks.release();
+    h->bj_var = false;                   // the variable kind: its tables go with its blocks
+    h->bjv_tiles.release(); h->bjv_bytes.release();
+    h->bjv_plan = BjVarPlan{}; h->bjv_ptr.clear();
     return PRCG_OK;
 }
 
@@ -1840,6 +1860,7 @@ int prcg_build_block_jacobi(prcg_t* h, int bs, int64_t* first_bad_block) {
 
 int prcg_get_block_jacobi(prcg_t* h, double* inv_blocks) {
     if (!h) return PRCG_EINVAL;
+    CHECK(h, !h->bj_var, "prcg_get_block_jacobi: the blocks on the handle have variable sizes: call prcg_get_block_jacobi_var");
     CHECK(h, h->bj_bs > 0, "prcg_get_block_jacobi: no block-Jacobi blocks on the handle (prcg_set_block_jacobi / prcg_build_block_jacobi)");
     CHECK(h, inv_blocks, "prcg_get_block_jacobi: null output");
     HIPCHK(h, hipSetDevice(h->dev));
@@ -1849,6 +1870,136 @@ int prcg_get_block_jacobi(prcg_t* h, double* inv_blocks) {
     HIPCHK(h, hipStreamSynchronize(h->sc));
     if (count > 0) HIPCHK(h, hipMemcpy(laid.data(), h->bj_blocks.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
     block_jacobi_unlay(h->n, h->bj_bs, laid.data(), inv_blocks);
+    return PRCG_OK;
+}
+
+// ---- blocks of variable size: the partition is checked and cut into tiles on the host (prcg_bjvar.h) BEFORE the handle is
+// touched, so that a refusal leaves the blocks set before in force
+static int bjvar_accept(prcg_t* h, const char* who, int64_t nb, const int64_t* block_ptr, BjVarPlan& P) {
+    CHECK(h, block_ptr, "%s: null block_ptr", who);
+    CHECK(h, nb >= 0, "%s: nb = %lld is negative", who, (long long)nb);
+    int64_t k = 0, m = 0;
+    switch (bjvar_check(h->n, nb, block_ptr, &k, &m)) {
+    case 1: return fail(h, PRCG_EINVAL, "%s: block_ptr[0] is %lld, not 0", who, (long long)block_ptr[0]);
+    case 2: return fail(h, PRCG_EINVAL, "%s: block_ptr[nb] is %lld, not n_rows = %lld", who, (long long)block_ptr[nb], (long long)h->n);
+    case 3: return fail(h, PRCG_EINVAL, "%s: block %lld has size %lld, outside 1..8", who, (long long)k, (long long)m);
+    default: break;
+    }
+    try {
+        bjvar_plan(h->n, nb, block_ptr, P);
+    } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    return PRCG_OK;
+}
+
+// the tables of an accepted partition onto the device, room for its blocks (not written here); the handle has no blocks before
+static int bjvar_install(prcg_t* h, BjVarPlan& P, int64_t nb, const int64_t* block_ptr) {
+    try { h->bjv_ptr.assign(block_ptr, block_ptr + nb + 1); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    const size_t lanes = (size_t)P.ntiles * kBjvLanes;
+    hipError_t e = h->bj_blocks.alloc((size_t)P.doubles() * sizeof(double), false);
+    if (e == hipSuccess) e = h->bjv_tiles.alloc(P.tiles.size() * sizeof(int64_t), false);
+    if (e == hipSuccess) e = h->bjv_bytes.alloc(2 * lanes, false);
+    if (e == hipSuccess && lanes) e = hipMemcpy(h->bjv_tiles.p, P.tiles.data(), P.tiles.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && lanes) e = hipMemcpy(h->bjv_bytes.p, P.code.data(), lanes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && lanes) e = hipMemcpy(static_cast<unsigned char*>(h->bjv_bytes.p) + lanes, P.bidx.data(), lanes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        h->bj_blocks.release(); h->bjv_tiles.release(); h->bjv_bytes.release(); h->bjv_ptr.clear();
+        return fail(h, PRCG_EHIP, "%s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    }
+    h->bjv_plan = std::move(P);
+    return PRCG_OK;
+}
+
+// the handle without blocks again after a failure behind bjvar_install
+static void bjvar_abandon(prcg_t* h) {
+    h->bj_blocks.release(); h->bjv_tiles.release(); h->bjv_bytes.release();
+    h->bjv_plan = BjVarPlan{}; h->bjv_ptr.clear();
+}
+
+int prcg_set_block_jacobi_var(prcg_t* h, int64_t nb, const int64_t* block_ptr, const double* inv_blocks) {
+    if (!h) return PRCG_EINVAL;
+    if (!inv_blocks) return drop_block_jacobi(h);
+    CHECK(h, h->have_csr, "prcg_set_block_jacobi_var: no operator: call prcg_set_csr first (the partition is checked against its n_rows)");
+    CHECK(h, !h->multi(), "a block-Jacobi preconditioner runs on one GPU only");
+    BjVarPlan P;
+    if (int rc = bjvar_accept(h, "prcg_set_block_jacobi_var", nb, block_ptr, P)) return rc;
+    std::vector<double> laid;
+    try { laid.resize((size_t)P.doubles()); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    bjvar_lay(P, block_ptr, inv_blocks, laid.data());
+    if (int rc = drop_block_jacobi(h)) return rc;
+    HIPCHK(h, hipSetDevice(h->dev));
+    if (int rc = bjvar_install(h, P, nb, block_ptr)) return rc;
+    if (!laid.empty()) {
+        const hipError_t e = hipMemcpy(h->bj_blocks.p, laid.data(), laid.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            bjvar_abandon(h);
+            return fail(h, PRCG_EHIP, "%s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        }
+    }
+    h->bj_var = true;
+    h->cb = nullptr; h->cb_ctx = nullptr;        // the last preconditioner set is the one in force
+    return PRCG_OK;
+}
+
+// prcg_build_block_jacobi for a partition: the same one pass over the caller-order CSR arrays, lane per row
+int prcg_build_block_jacobi_var(prcg_t* h, int64_t nb, const int64_t* block_ptr, int64_t* first_bad_block) {
+    if (!h) return PRCG_EINVAL;
+    if (first_bad_block) *first_bad_block = -1;
+    CHECK(h, h->have_csr, "prcg_build_block_jacobi_var: no operator: call prcg_set_csr first");
+    BjVarPlan P;
+    if (int rc = bjvar_accept(h, "prcg_build_block_jacobi_var", nb, block_ptr, P)) return rc;
+    CHECK(h, h->g == 0, "prcg_build_block_jacobi_var: the operator is a row block with %lld ghost columns; the blocks are built for whole "
+                        "operators on one GPU only (invert them on the host: prcg_set_block_jacobi_var)", (long long)h->g);
+    CHECK(h, !h->multi() && h->nranks == 1, "prcg_build_block_jacobi_var: the handle has a communicator or a world size > 1; the blocks are "
+                                            "built for whole operators on one GPU only");
+    HIPCHK(h, hipSetDevice(h->dev));
+    // the handle's pending work may still apply the old blocks
+    HIPCHK(h, hipStreamSynchronize(h->sh));
+    HIPCHK(h, hipStreamSynchronize(h->sm));
+    HIPCHK(h, hipStreamSynchronize(h->sc));
+    if (int rc = drop_block_jacobi(h)) return rc;
+    if (!h->bj_flag.p) HIPCHK(h, h->bj_flag.alloc(sizeof(long long)));
+    if (int rc = bjvar_install(h, P, nb, block_ptr)) return rc;         // the kernel writes every entry of the blocks
+    long long bad = INT64_MAX;
+    hipError_t e = hipMemcpyAsync(h->bj_flag.p, &bad, sizeof bad, hipMemcpyHostToDevice, h->sc);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->sc);                 // (`bad` is a pageable stack variable)
+    if (e != hipSuccess) {
+        bjvar_abandon(h);
+        return fail(h, PRCG_EHIP, "%s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    }
+    if (launch_block_jacobi_var_build(h->sc, h->bj_blocks.d(), h->bjv_plan.ntiles, h->bjv_tiles_d(), h->bjv_code_d(), h->bjv_bidx_d(),
+                                      h->indptr.i(), h->col.i(), h->val.d(), static_cast<long long*>(h->bj_flag.p)) != 0) {
+        bjvar_abandon(h);
+        return fail(h, PRCG_EHIP, "kernel launch failed (%s:%d)", __FILE__, __LINE__);
+    }
+    e = hipMemcpyAsync(&bad, h->bj_flag.p, sizeof bad, hipMemcpyDeviceToHost, h->sc);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->sc);
+    if (e != hipSuccess) {
+        bjvar_abandon(h);
+        return fail(h, PRCG_EHIP, "%s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    }
+    if (bad != INT64_MAX) {
+        bjvar_abandon(h);                          // the handle is left without blocks
+        if (first_bad_block) *first_bad_block = (int64_t)bad;
+        return fail(h, PRCG_EINVAL, "prcg_build_block_jacobi_var: diagonal block %lld (size %lld) is singular or not finite", bad,
+                    (long long)(block_ptr[bad + 1] - block_ptr[bad]));
+    }
+    h->bj_var = true;
+    h->cb = nullptr; h->cb_ctx = nullptr;          // the last preconditioner set is the one in force
+    return PRCG_OK;
+}
+
+int prcg_get_block_jacobi_var(prcg_t* h, double* inv_blocks) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, h->bj_bs == 0, "prcg_get_block_jacobi_var: the blocks on the handle have one uniform size: call prcg_get_block_jacobi");
+    CHECK(h, h->bj_var, "prcg_get_block_jacobi_var: no block-Jacobi blocks on the handle (prcg_set_block_jacobi_var / prcg_build_block_jacobi_var)");
+    CHECK(h, inv_blocks, "prcg_get_block_jacobi_var: null output");
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int64_t count = h->bjv_plan.doubles();
+    std::vector<double> laid;
+    try { laid.resize((size_t)count); } catch (const std::bad_alloc&) { return fail(h, PRCG_ENOMEM, "out of host memory"); }
+    HIPCHK(h, hipStreamSynchronize(h->sc));
+    if (count > 0) HIPCHK(h, hipMemcpy(laid.data(), h->bj_blocks.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    bjvar_unlay(h->bjv_plan, h->bjv_ptr.data(), laid.data(), inv_blocks);
     return PRCG_OK;
 }
 
@@ -2403,7 +2554,7 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     static_cast<Session&>(*h) = Session{};
     Session& s = *h;
     s.variant = variant;
-    s.bj_session = h->bj_bs > 0 && inv_diag == nullptr;
+    s.bj_session = h->have_block_jacobi() && inv_diag == nullptr;
     s.stored_tilde = (h->cb != nullptr || s.bj_session) && inv_diag == nullptr;
     s.prec = inv_diag != nullptr || s.stored_tilde;
     CHECK(h, !(s.stored_tilde && h->multi()), "a host-callback or block-Jacobi preconditioner runs on one GPU only");
@@ -2792,7 +2943,7 @@ int prcg_schedule(const prcg_t* h) {
     return ((h->fused || h->hs_fused || h->pr_fused || h->cg_fused) ? PRCG_SCHED_FUSED : 0) | (h->fused_comm ? PRCG_SCHED_FUSED_COMM : 0) |
            (h->peer ? PRCG_SCHED_PEER : 0) | (h->sell ? PRCG_SCHED_SELL | PRCG_SCHED_COL16 : 0) | ((h->small || h->small_hs) ? PRCG_SCHED_SMALL : 0) | (h->comm ? PRCG_SCHED_COMM : 0) |
            (h->gather ? PRCG_SCHED_GATHER : 0) | (h->comm_halo ? PRCG_SCHED_DUAL_COMM : 0) | ((h->steps & 15) << 8) |
-           (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
+           (h->stream_stores ? PRCG_SCHED_STREAM_STORES : 0) | (h->bj_session ? PRCG_SCHED_BLOCK_JACOBI : 0) | ((h->bj_session && h->bj_var) ? PRCG_SCHED_BLOCK_JACOBI_VAR : 0) | ((h->sell && h->sell_sigma > 64) ? PRCG_SCHED_SELL_SORTED : 0) |
            (xp_deferred(h) ? PRCG_SCHED_XP_DEFERRED : 0) | ((h->rhs2 && h->groups == 1) ? PRCG_SCHED_RHS2 : 0) |
            (h->groups == 2 ? PRCG_SCHED_RHS4 : 0) | (h->spmm4 ? PRCG_SCHED_SPMM4 : 0) | (h->pipe2 ? PRCG_SCHED_RHS2_PIPE : 0) |
            ((h->sell && h->sell_nt) ? PRCG_SCHED_NT_LOADS : 0) | ((h->sell && h->sell_window > 0) ? PRCG_SCHED_SELL_WINDOW : 0) |
@@ -2947,7 +3098,7 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     CHECK(h, h->g == 0, "prcg_solve_begin_multi: n_ghost = %lld > 0: the two-RHS session serves whole operators only", (long long)h->g);
     CHECK(h, h->cb == nullptr, "prcg_solve_begin_multi: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
                                "session serves Jacobi (inv_diag) or none");
-    CHECK(h, h->bj_bs == 0, "prcg_solve_begin_multi: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
+    CHECK(h, !h->have_block_jacobi(), "prcg_solve_begin_multi: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
                             "session serves Jacobi (inv_diag) or none");
     CHECK(h, h->replace_fn == nullptr, "prcg_solve_begin_multi: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session");
     CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
@@ -3036,7 +3187,7 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     CHECK(h, h->g == 0, "prcg_solve_begin_multi_pipe: n_ghost = %lld > 0: the two-RHS session serves whole operators only", (long long)h->g);
     CHECK(h, h->cb == nullptr, "prcg_solve_begin_multi_pipe: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
                                "session serves Jacobi (inv_diag) or none");
-    CHECK(h, h->bj_bs == 0, "prcg_solve_begin_multi_pipe: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
+    CHECK(h, !h->have_block_jacobi(), "prcg_solve_begin_multi_pipe: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
                             "session serves Jacobi (inv_diag) or none");
     CHECK(h, h->replace_fn == nullptr, "prcg_solve_begin_multi_pipe: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session");
     CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,

@@ -449,6 +449,16 @@ int launch_block_jacobi_build(hipStream_t st, double* blocks, int64_t n, int bs,
                               long long* first_bad);
 // both columns of the interleaved [w u] array in one launch: wt = M^-1 w (mask bit 0), ut = M^-1 u (mask bit 1)
 int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask);
+// ---- the same with VARIABLE block sizes (prcg_set_block_jacobi_var / prcg_build_block_jacobi_var): the partition reaches the
+// kernels as prcg_bjvar.h's tables -- `tiles` ntiles x 4 int64 (first row, first line, first block, largest size), `code` and
+// `bidx` one byte per lane, 256 per tile -- and `blocks` is that header's layout (BjVarPlan::doubles()).  0 / -1.
+int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t ntiles, const long long* tiles,
+                            const unsigned char* code, const double* blocks);
+int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
+                                 const unsigned char* code, const double* blocks, int mask);
+// gather, invert, store: every double of the layout is written; *first_bad as in launch_block_jacobi_build
+int launch_block_jacobi_var_build(hipStream_t st, double* blocks, int64_t ntiles, const long long* tiles, const unsigned char* code,
+                                  const unsigned char* bidx, const int* indptr, const int* col, const double* val, long long* first_bad);
 // partial[slot] = sum (a[i*as] - b[i])^2
 int launch_diff_sq(hipStream_t st, const double* a, int as, const double* b, int64_t n, double* partials, int slot);
 // partial[slot] = sum a_i * b_i

@@ -98,7 +98,7 @@ class DeviceCSR:
         indices = np.ascontiguousarray(A.indices, dtype=np.int32)
         data = np.ascontiguousarray(A.data, dtype=np.float64)
         self.n, self.n_ghost, self.nnz = int(n_rows), int(n_ghost), int(A.nnz)
-        self._bj_bs = self._bj_built = None          # prcg_set_csr drops block-Jacobi blocks
+        self._no_blocks()                            # prcg_set_csr drops block-Jacobi blocks
         self._check(self._lib.prcg_set_csr(self._h, self.n, self.n_ghost, self.nnz, L.ptr(indptr), int(is64),
                                            L.ptr(indices), L.ptr(data)))
         self.halo = halo
@@ -142,7 +142,7 @@ class DeviceCSR:
                 torch.cuda.current_stream(data.device).synchronize()
                 route = self.values_route()
                 self._check(self._lib.prcg_update_values(self._h, C.c_void_p(data.data_ptr()), 1))
-                self._bj_built = None                # the blocks stay, frozen: no longer those of the current values
+                self._bj_built = self._bjv_built = None      # the blocks stay, frozen: no longer those of the current values
                 return route
             data = data.detach().numpy()
         data = np.asarray(data)
@@ -153,24 +153,81 @@ class DeviceCSR:
         data = np.ascontiguousarray(data)
         route = self.values_route()
         self._check(self._lib.prcg_update_values(self._h, L.ptr(data), 0))
-        self._bj_built = None                        # the blocks stay, frozen: no longer those of the current values
+        self._bj_built = self._bjv_built = None      # the blocks stay, frozen: no longer those of the current values
         return route
 
     # -- point-block Jacobi: the blocks on the handle (prcg.h: prcg_set_block_jacobi / prcg_build_block_jacobi) ----------
     _bj_bs = None        # block size of the blocks this wrapper put on the handle (None: none)
     _bj_built = None     # ... and, when they were BUILT from the operator's current values, that block size again
 
+    _bjv_ptr = None      # partition of the VARIABLE-size blocks this wrapper put on the handle (None: none; then _bj_bs is None)
+    _bjv_built = None    # ... and, when they were BUILT from the operator's current values, that partition again
+
+    def _no_blocks(self):
+        self._bj_bs = self._bj_built = self._bjv_ptr = self._bjv_built = None
+
+    # -- ... with variable block sizes (prcg.h: prcg_set_block_jacobi_var / prcg_build_block_jacobi_var) ------------------
+    def _partition(self, block_ptr, who):
+        """block_ptr as a contiguous int64 array; the library checks what it says (and names the reason of a refusal)"""
+        ptr = np.ascontiguousarray(block_ptr, dtype=np.int64)
+        if ptr.ndim != 1 or ptr.size < 1:
+            raise ValueError(f'{who}: block_ptr must be a one-dimensional array of nb + 1 entries, got shape {ptr.shape}')
+        return ptr
+
+    def set_block_jacobi_var(self, block_ptr, inv_blocks):
+        """Put the caller's inverses of variable-size diagonal blocks on the handle (prcg.h: prcg_set_block_jacobi_var): block k
+        owns rows block_ptr[k] .. block_ptr[k+1]-1, every size in 1..8; inv_blocks packed, block k as m_k x m_k row-major at
+        offset sum of m_q^2, q < k.  inv_blocks None removes whatever blocks are set.  A partition the library refuses leaves
+        the blocks set before in force (PrcgError with the reason)."""
+        if inv_blocks is None:
+            self._check(self._lib.prcg_set_block_jacobi_var(self._h, 0, None, None))
+            self._no_blocks()
+            return
+        ptr = self._partition(block_ptr, 'set_block_jacobi_var')
+        blocks = L.f64(inv_blocks).reshape(-1)
+        want = int((np.diff(ptr) ** 2).sum())
+        if blocks.size != want:
+            raise ValueError(f'set_block_jacobi_var: the partition needs {want} packed doubles (sum of m_k^2), inv_blocks has {blocks.size}')
+        self._check(self._lib.prcg_set_block_jacobi_var(self._h, ptr.size - 1, L.ptr(ptr), L.ptr(blocks)))
+        self._no_blocks()
+        self._bjv_ptr = ptr.copy()
+
+    def build_block_jacobi_var(self, block_ptr):
+        """Build the inverses of the diagonal blocks of the partition ON THE DEVICE from the operator's current values (prcg.h:
+        prcg_build_block_jacobi_var) and put them in force.  Valid again after every update_values.  ValueError with the
+        library's text if a block is singular or not finite (the handle is then left without blocks); any other refusal is
+        a PrcgError and leaves the handle as it was."""
+        ptr = self._partition(block_ptr, 'build_block_jacobi_var')
+        bad = C.c_int64(-1)
+        rc = self._lib.prcg_build_block_jacobi_var(self._h, ptr.size - 1, L.ptr(ptr), C.byref(bad))
+        if rc == L.EINVAL and bad.value >= 0:
+            self._no_blocks()
+            raise ValueError(self._lib.prcg_last_error(self._h).decode())
+        self._check(rc)
+        self._no_blocks()
+        self._bjv_ptr = self._bjv_built = ptr.copy()
+
+    def get_block_jacobi_var(self, block_ptr=None):
+        """The variable-size blocks now on the handle, packed (prcg.h: prcg_get_block_jacobi_var).  block_ptr: the partition
+        they were set with -- known to this object when it set them itself, to be passed when the C-ABI was called around it."""
+        ptr = self._bjv_ptr if block_ptr is None else self._partition(block_ptr, 'get_block_jacobi_var')
+        out = np.zeros(self.n * 8 + 8)               # room for any partition: a row has at most 8 entries
+        self._check(self._lib.prcg_get_block_jacobi_var(self._h, L.ptr(out)))       # (refuses without variable blocks)
+        if ptr is None:
+            raise ValueError('get_block_jacobi_var: this object has set no variable blocks; pass block_ptr= if the C-ABI was called directly')
+        return out[:int((np.diff(ptr) ** 2).sum())].copy()
+
     def set_block_jacobi(self, bs, inv_blocks):
         """Put the caller's inverses on the handle (prcg.h: prcg_set_block_jacobi): inv_blocks of shape (ceil(n/bs), bs, bs);
         inv_blocks None removes whatever blocks are set."""
         if inv_blocks is None:
             self._check(self._lib.prcg_set_block_jacobi(self._h, 0, None))
-            self._bj_bs = self._bj_built = None
+            self._no_blocks()
             return
         bs, blocks = int(bs), L.f64(inv_blocks)
         if not 1 <= bs <= 8 or blocks.shape != (-(-self.n // bs), bs, bs):
             raise ValueError(f'block_jacobi: need 1 <= bs <= 8 and inv_blocks of shape (ceil(n/bs), bs, bs); got bs={bs}, {blocks.shape}')
-        self._bj_bs = self._bj_built = None
+        self._no_blocks()
         self._check(self._lib.prcg_set_block_jacobi(self._h, bs, L.ptr(blocks)))
         self._bj_bs = bs
 
@@ -182,9 +239,10 @@ class DeviceCSR:
         bad = C.c_int64(-1)
         rc = self._lib.prcg_build_block_jacobi(self._h, int(bs), C.byref(bad))
         if rc == L.EINVAL and bad.value >= 0:
-            self._bj_bs = self._bj_built = None
+            self._no_blocks()
             raise ValueError(self._lib.prcg_last_error(self._h).decode())
         self._check(rc)
+        self._no_blocks()                            # (they replace variable-size blocks too)
         self._bj_bs = self._bj_built = int(bs)
 
     def get_block_jacobi(self, bs=None):
@@ -264,18 +322,22 @@ class DeviceCSR:
         return Y, ms.value
 
     # -- solver session ------------------------------------------------------------------------
-    def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None, block_jacobi=None):
+    def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None, block_jacobi=None,
+              block_jacobi_var=None):
         """inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
         the ceil(n/bs) x bs x bs inverses of the diagonal blocks (prcg.h: prcg_set_block_jacobi); inv_blocks None: the blocks
         BUILT ON THE DEVICE from the operator (build_block_jacobi) -- rebuilt only when blocks of that bs built from the
         current values are not in force already (after update_values, after a session that removed or replaced them).
         preconditioner: any
         callable v -> M^-1 v (what the reference's *_pcg functions take); it runs on the host wherever the reference
-        calls it (prcg.h: prcg_set_preconditioner).  At most one of the three; a session without block_jacobi removes
-        the blocks an earlier session on this operator set."""
+        calls it (prcg.h: prcg_set_preconditioner).  block_jacobi_var=(block_ptr, inv_blocks): point-block Jacobi with VARIABLE
+        block sizes on the device (prcg.h: prcg_set_block_jacobi_var; inv_blocks packed); inv_blocks None: built on the device
+        (build_block_jacobi_var), rebuilt only when blocks of that same partition built from the current values are not in
+        force already.  At most one of the four; a session without block_jacobi / block_jacobi_var removes the blocks an earlier
+        session on this operator set."""
         b, x0 = L.f64(b), L.f64(x0)
         assert b.shape == (self.n,) and x0.shape == (self.n,)
-        assert sum(q is not None for q in (inv_diag, preconditioner, block_jacobi)) <= 1
+        assert sum(q is not None for q in (inv_diag, preconditioner, block_jacobi, block_jacobi_var)) <= 1
         xt = None if x_true is None else L.f64(x_true)
         dv = None if inv_diag is None else L.f64(inv_diag)
         if preconditioner is not None:
@@ -294,7 +356,7 @@ class DeviceCSR:
                     return 1
             self._prec_fn = L.PREC_FN(call)            # keep the trampoline alive for the whole session
             self._check(self._lib.prcg_set_preconditioner(self._h, C.cast(self._prec_fn, C.c_void_p), None))
-            self._bj_bs = self._bj_built = None         # (it replaces the blocks)
+            self._no_blocks()                           # (it replaces the blocks)
         else:
             self._prec_fn = None
             self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
@@ -303,6 +365,12 @@ class DeviceCSR:
                 self.build_block_jacobi(int(block_jacobi[0]))
         elif block_jacobi is not None:
             self.set_block_jacobi(block_jacobi[0], block_jacobi[1])
+        elif block_jacobi_var is not None and block_jacobi_var[1] is None:
+            ptr = self._partition(block_jacobi_var[0], 'block_jacobi_var')
+            if self._bjv_built is None or not np.array_equal(self._bjv_built, ptr):
+                self.build_block_jacobi_var(ptr)
+        elif block_jacobi_var is not None:
+            self.set_block_jacobi_var(block_jacobi_var[0], block_jacobi_var[1])
         else:
             self.set_block_jacobi(0, None)
         self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
@@ -398,7 +466,8 @@ class DeviceCSR:
                 'pattern': bool(s & 65536), 'window': bool(s & 4096), 'fused_comm': bool(s & 8192), 'peer': bool(s & 16384), 'sliced_rows': bool(s & 32768),
                 'stream_stores': bool(s & 131072), 'sorted_windows': bool(s & 262144), 'nt_loads': bool(s & 524288), 'window_codes': bool(s & 2097152),
                 'block_jacobi': bool(s & 4194304), 'xp_deferred': bool(s & 8388608), 'rhs2': bool(s & 16777216),
-                'rhs4': bool(s & 33554432), 'spmm4': bool(s & 67108864), 'rhs2_pipe': bool(s & 134217728)}
+                'rhs4': bool(s & 33554432), 'spmm4': bool(s & 67108864), 'rhs2_pipe': bool(s & 134217728),
+                'block_jacobi_var': bool(s & 268435456)}
 
     def layout(self):
         """Diagnostic (prcg_test.h: prcg_debug_layout): what the summation order of a tile launch's inner products depends

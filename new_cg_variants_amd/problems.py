@@ -217,6 +217,15 @@ def fem_irregular_3d(m, seed=0, keep=0.8, rows=None, shift=1e-4, dof_choices=(1,
     return _fem_assemble(m, dofs, keep_bits, shift, rows)
 
 
+def fem_irregular_blocks(m, seed=0, dof_choices=(1, 3, 6), dof_probs=(0.3, 0.5, 0.2)):
+    """The NODAL partition of fem_irregular_3d(m, seed, ...): block_ptr, m^3 + 1 int64 entries, node k owning rows block_ptr[k] ..
+    block_ptr[k+1]-1 (what prcg_set_block_jacobi_var / cg_variants.VarBlockJacobi take).  The same generator and the same first
+    draw as fem_irregular_3d, so the two always agree."""
+    rng = np.random.default_rng(seed)
+    dofs = rng.choice(np.array(dof_choices, dtype=np.int8), size=m ** 3, p=dof_probs)
+    return np.concatenate([[0], np.cumsum(dofs, dtype=np.int64)]).astype(np.int64)
+
+
 def _row_slice(A, rows):
     return A if rows is None else A[rows[0]:rows[1]]
 
