@@ -439,6 +439,55 @@ int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out);
 /* max_iter doubles: column j's updated_residual_2_norm history (nothing is written when hist_mask was 0) */
 int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
 
+/* ---- a BATCH of small independent systems, solved in one launch, one workgroup per system --------------------------------
+ * Replaces the reference's loop over matrices and methods around `method(A, b, x0, max_iter, ...)` (numerical_experiments/
+ * figure_gen.py:59, :245-339: the convergence table is small matrices times nine methods), and the loop a time stepper or a
+ * parameter sweep runs over hundreds of right-hand sides of one small matrix.  n_sys systems A_s x_s = b_s; every one is solved
+ * by the one-workgroup solver of a small single session (PRCG_SCHED_SMALL: the whole solve inside one launch of one 1024-thread
+ * workgroup, matrix in registers or LDS), all of them in the SAME launch, the workgroup index selecting the system.  Systems
+ * may differ in size and matrix; systems that share a matrix name the same one, which is uploaded once.
+ *   prcg_batch_create  n_mat matrices concatenated: rows_off / nnz_off (n_mat + 1 int64 each, from 0); indptr int32, zero-based
+ *                      PER MATRIX, n_m + 1 entries each (matrix m's start at rows_off[m] + m); indices int32 local columns
+ *                      (matrix m's at nnz_off[m]); data likewise.  mat_of[s] in [0, n_mat): the matrix of system s.  A separate
+ *                      object: it borrows the handle's device and compute stream, needs no operator on the handle and leaves one
+ *                      there (and an open session) alone.  Destroy it before the handle.
+ *   prcg_batch_begin   rhs, x0: the systems' vectors concatenated in system order.  variant: PRCG_PIPE_PR, PRCG_PIPE_PR_M or
+ *                      PRCG_HS, unpreconditioned.  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.  One launch per launch
+ *                      group computes x = x0, r = b - A x0, p = r, s = A p and the initial inner products of every system.
+ *                      May be called again: a new session on the same matrices.
+ *   prcg_batch_iterate enqueues; every system advances by iters (k + iters <= max_iter).  prcg_batch_sync waits.
+ * Launch groups: the systems whose matrix lives in registers (n <= 1024, rows of at most 8) form one launch, those whose matrix
+ * lives in LDS another; a call is one launch per group.
+ * Bits: from the same state and scalars a system's iterations are those of a single small session on its matrix, bit for bit
+ * -- vectors, inner products, coefficients, history -- whatever its position in the batch and whatever the other systems are; a
+ * breakdown (inf / nan) of one system stays in that system.  The initial VECTORS carry the single session's bits too.  The
+ * initial inner products (row 0 of the scalars) are summed in the workgroup's own order -- thread-sequential over rows tid,
+ * tid + 1024, ..., wave butterfly, 16 waves: the order of the loop -- where the single session sums them in the order of its
+ * start-up launches: row 0 may differ from a single session's in the last bit.
+ * Refused (PRCG_EINVAL, the text names the reason and, for a reason that lies in one system, the first such system; nothing is
+ * created or changed): create -- a null pointer, n_sys < 1, n_mat < 1, a communicator on the handle, inconsistent offsets
+ * (rows_off / nnz_off not from 0 or a matrix without rows; an indptr that does not run from 0 to its matrix's nonzero count or
+ * decreases), a column index outside its matrix, a mat_of entry out of range, a system that does not fit the one-workgroup
+ * solver (a batch has no other schedule); begin -- another variant, another history bit, null rhs or x0, max_iter < 1.
+ * Errors are reported through prcg_last_error of the handle the batch was created on.
+ * Accessors (they synchronise): s = the system.  prcg_batch_get_vector: PRCG_VEC_X, _R, _P, _S, the system's n doubles;
+ * prcg_batch_get_solutions: every x concatenated in system order, ONE copy; scalars / coefficients / history as
+ * prcg_get_scalars / prcg_get_coefficients / prcg_get_history return them (history: max_iter doubles, nothing is written when
+ * hist_mask was 0).  No setters, no preconditioner, no recorder of state. */
+typedef struct prcg_batch prcg_batch_t;
+int  prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
+                       const int32_t* indices, const double* data, int n_sys, const int32_t* mat_of, prcg_batch_t** out);
+void prcg_batch_destroy(prcg_batch_t* b);
+int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask);
+int prcg_batch_iterate(prcg_batch_t* b, int iters);
+int prcg_batch_sync(prcg_batch_t* b);
+int prcg_batch_iteration(const prcg_batch_t* b);
+int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out);
+int prcg_batch_get_solutions(prcg_batch_t* b, double* x_cat);
+int prcg_batch_get_scalars(prcg_batch_t* b, int k, int s, double* out);
+int prcg_batch_get_coefficients(prcg_batch_t* b, int k, int s, double* out);
+int prcg_batch_get_history(prcg_batch_t* b, int s, double* hist);
+
 /* HIP-event sampling of the SpMV/SpMM and update launches inside prcg_iterate:
  * every `stride`-th iteration is bracketed (0 = off).  Read back with prcg_get_timings. */
 int prcg_set_profiling(prcg_t* h, int stride);

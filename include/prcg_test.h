@@ -175,6 +175,13 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity);
  * 65,536 spare entries must lie between the pointer and the end of its allocation.  The engine evaluates this at
  * every launch and returns PRCG_EINVAL instead of launching (a short source used to be a memory fault).  1 = ok. */
 int prcg_window_source_ok(int64_t n_rows, int64_t n_ghost, int components, int64_t bytes_available);
+/* How prcg_batch_create classifies the systems of a batch (host only): per system its rows n[s], nonzeros nnz[s] and longest
+ * row max_row_len[s]; mode_out[s] = 1 (matrix in registers: n <= 1024, rows of at most 8) or 0 (matrix in LDS), group_out[s] =
+ * the launch group of system s, counted in launch order (the register group first when both exist).  Returns the number of
+ * launch groups (1 or 2), -(s + 1) for the first system s that does not fit the one-workgroup solver (mode_out / group_out are
+ * then unspecified), 0 on a bad argument. */
+int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
+                          int32_t* group_out);
 /* the tile caps the device kernels were compiled for */
 void prcg_tile_caps(int* cap_nnz, int* cap_rows);
 

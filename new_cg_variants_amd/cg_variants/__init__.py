@@ -37,7 +37,7 @@ import numpy as np
 
 from .. import _lib as L
 from ..callbacks import RECORDER_NAMES
-from ..device import DeviceCSR, multi_rhs_shape_error
+from ..device import DeviceBatch, DeviceCSR, batch_matrices, batch_vectors, multi_rhs_shape_error
 
 _OPERATORS = OrderedDict()   # small cache: figure_gen runs nine variants on one matrix
 _PATTERNS = {}               # cache key -> fingerprint of indptr / indices alone (update_values finds an operator by its pattern)
@@ -748,6 +748,66 @@ pipe_pr_m_cg_multi = _make_multi_pipe(L.PIPE_PR_M, 'pipe_pr_m_cg_multi', False, 
 pipe_pr_m_pcg_multi = _make_multi_pipe(L.PIPE_PR_M, 'pipe_pr_m_pcg_multi', True, 213)
 
 
+def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs):
+    """A batch of small independent systems in ONE launch, one workgroup per system (prcg.h: prcg_batch_create): what a loop
+    of `name`'s single function over the systems computes.  Every argument is checked before the device is touched; what the
+    batch does not serve raises ValueError -- nothing falls back to a loop of sessions."""
+    if kwargs.pop('preconditioner', None) is not None:
+        raise ValueError(f'{name} takes no preconditioner: a batch runs the unpreconditioned one-workgroup solver')
+    for key in ('x_true', 'w_replace'):
+        if kwargs.get(key) is not None:
+            raise ValueError(f'{name}: {key} is not served by a batch')
+    n_sys = bs.shape[0] if isinstance(bs, np.ndarray) and bs.ndim == 2 else len(bs)
+    try:
+        matrices, mat_of = batch_matrices(As, n_sys)
+    except ValueError as e:
+        raise ValueError(f'{name}: {e}') from None
+    matrices = [A if A.format == 'csr' else A.tocsr() for A in matrices]
+    sizes = [matrices[m].shape[0] for m in mat_of]
+    try:
+        B, X0 = batch_vectors('bs', bs, sizes), batch_vectors('x0s', x0s, sizes)
+    except ValueError as e:
+        raise ValueError(f'{name}: {e}') from None
+    mask = 0
+    for cb in callbacks:
+        cname = getattr(cb, 'prcg_recorder', None) or getattr(cb, '__name__', '')
+        if cname == 'updated_residual_2_norm':
+            mask |= L.HIST_BITS[cname]
+        else:
+            raise ValueError(f'{name}: callback {cname or repr(cb)} is not served by a batch (the updated_residual_2_norm recorder or none)')
+    batch = DeviceBatch(matrices, mat_of, device=int(kwargs.get('device', 0)))
+    try:
+        at = np.concatenate([[0], np.cumsum(sizes)])
+        batch.begin(variant, [B[at[s]:at[s + 1]] for s in range(n_sys)], [X0[at[s]:at[s + 1]] for s in range(n_sys)], max_iter, hist_mask=mask)
+        batch.iterate(max_iter - 1)
+        batch.sync()
+        outputs = [{'name': name, 'max_iter': max_iter, 'system': s} for s in range(n_sys)]
+        for s in range(n_sys):
+            outputs[s].update(batch.history(s))
+    finally:
+        batch.close()
+    return outputs
+
+
+def _make_batch(variant, name, where):
+    single = name[:-len('_batch')]
+
+    def f(As, bs, x0s, max_iter, callbacks=[], **kwargs):
+        return _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs)
+    f.__doc__ = (f'{single} ({where}) for a BATCH of small independent systems, all solved in one launch, one workgroup per system: As is one '
+                 'matrix (every system uses it) or a sequence as long as bs (entries that are the same object share one upload); bs, x0s are '
+                 f'lists of vectors or, when all sizes agree, 2-D arrays.  Returns a list of trial dicts, one per system, shaped like {single}\'s.  '
+                 'callbacks: updated_residual_2_norm or none.  Every system must fit the one-workgroup solver (n <= 4096, matrix in registers '
+                 'or LDS): anything else is refused.')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+pipe_pr_cg_batch = _make_batch(L.PIPE_PR, 'pipe_pr_cg_batch', 'pipe_pr_cg.py:89')
+pipe_pr_m_cg_batch = _make_batch(L.PIPE_PR_M, 'pipe_pr_m_cg_batch', 'pipe_pr_cg.py:101')
+hs_cg_batch = _make_batch(L.HS, 'hs_cg_batch', 'hs_cg.py:9')
+
+
 def _make(variant, name, preconditioned):
     def take_w_replace(kwargs):
         # gv_cg.py:9 / :93 take a residual-replacement predicate (default: never); the other variants swallow the keyword
@@ -792,4 +852,5 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
            'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
+           'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch',
            'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi']

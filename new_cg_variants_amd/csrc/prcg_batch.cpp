@@ -1,0 +1,336 @@
+// A batch of small independent systems A_s x_s = b_s, every one solved by the one-workgroup solver (k_small_pipe_pr /
+// k_small_hs, prcg_kernels.hip), all of them in the same launch: blockIdx.x selects the system.  Implements the prcg_batch_*
+// entries of include/prcg.h and the planner hook prcg_plan_small_batch of include/prcg_test.h.  Host code only.
+//
+// Layout on the device: the matrices concatenated (every matrix uploaded once, however many systems use it); per session the
+// systems' state concatenated in system order -- pipelined: the pairs (x,p) and (r,s); Hestenes-Stiefel: x, r, p, s --, one
+// scalar history [max_iter+1][PRCG_NUM_SCALARS] and one coefficient history [max_iter+1][4] per system, and one descriptor
+// (SmallArgs) per system, sorted by LAUNCH GROUP: the systems whose matrix lives in registers (mode 1) first, then those
+// whose matrix lives in LDS (mode 0); inside a group in system order.  An iteration call is one launch per group on the
+// handle's compute stream, begin one initialisation launch per group.  Nothing a system computes depends on its group's other
+// members: the launch's dynamic LDS is the group's largest need, each workgroup carves it by its own n and nnz.
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "../../include/prcg.h"
+#include "../../include/prcg_test.h"
+#include "prcg_batch.h"
+#include "prcg_kernels.h"
+
+using namespace prcg;
+
+namespace {
+
+constexpr int kNS = PRCG_NUM_SCALARS;
+constexpr int kCoefStride = 4;
+static_assert(kPartialStride == PRCG_NUM_SCALARS, "the small-system kernels index the scalar history with kPartialStride");
+
+struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { if (p) (void)hipFree(p); }
+    hipError_t ensure(size_t bytes) {      // (contents undefined)
+        if (bytes == 0) bytes = 16;
+        if (p && cap >= bytes) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = bytes;
+        return hipSuccess;
+    }
+    double* d() const { return static_cast<double*>(p); }
+};
+
+// launch groups of a batch: mode 1 first, then mode 0; group ids count the groups that exist
+int plan_groups(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out, int32_t* group_out) {
+    bool have[2] = {false, false};
+    for (int s = 0; s < n_sys; ++s) {
+        int mode = 0;
+        if (nnz[s] < 0 || !small_fits(n[s], nnz[s], max_row_len[s], &mode)) return -s - 1;
+        mode_out[s] = mode;
+        have[mode] = true;
+    }
+    for (int s = 0; s < n_sys; ++s) group_out[s] = mode_out[s] == 1 ? 0 : (have[1] ? 1 : 0);
+    return (have[0] ? 1 : 0) + (have[1] ? 1 : 0);
+}
+
+}  // namespace
+
+struct prcg_batch {
+    prcg_t* h = nullptr;
+    int dev = 0;
+    hipStream_t sc = nullptr;
+    int n_sys = 0;
+    std::vector<int> n, nnz, mode, slot;           // per system: rows, nonzeros, mode, position of its descriptor
+    std::vector<int64_t> voff;                     // per system (+1): first row in the concatenated vectors
+    std::vector<const int*> indptr, col;           // per system: its matrix on the device
+    std::vector<const double*> val;
+    int count[2] = {0, 0};                         // systems of mode 0 / mode 1
+    size_t lds[2] = {0, 0};                        // largest small_lds_bytes of each mode's members
+    Buf m_indptr, m_col, m_val;                    // the matrices, concatenated
+    Buf state, rhs, x0, dots, coef, desc, init, tmp;
+    // ---- session ----
+    bool in_session = false, hs = false;
+    int variant = 0, max_iter = 0, k = 0;
+    uint32_t hist_mask = 0;
+
+    int64_t N() const { return voff[(size_t)n_sys]; }
+    double* dots_of(int s) const { return dots.d() + (size_t)s * (max_iter + 1) * kNS; }
+    double* coef_of(int s) const { return coef.d() + (size_t)s * (max_iter + 1) * kCoefStride; }
+    // first descriptor of a mode's launch: mode 1 leads
+    const SmallArgs* desc_of(int m) const { return static_cast<const SmallArgs*>(desc.p) + (m == 1 ? 0 : count[1]); }
+    const SmallInit* init_of(int m) const { return static_cast<const SmallInit*>(init.p) + (m == 1 ? 0 : count[1]); }
+};
+
+#define BCHECK(h, cond, ...)                                                                  \
+    do { if (!(cond)) return batch_fail(h, PRCG_EINVAL, __VA_ARGS__); } while (0)
+#define BHIP(h, expr)                                                                         \
+    do {                                                                                      \
+        hipError_t e__ = (expr);                                                              \
+        if (e__ != hipSuccess)                                                                \
+            return batch_fail(h, PRCG_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+    } while (0)
+
+extern "C" {
+
+int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
+                          int32_t* group_out) {
+    if (n_sys < 1 || !n || !nnz || !max_row_len || !mode_out || !group_out) return 0;
+    return plan_groups(n_sys, n, nnz, max_row_len, mode_out, group_out);
+}
+
+int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
+                      const int32_t* indices, const double* data, int n_sys, const int32_t* mat_of, prcg_batch_t** out) {
+    if (!h) return PRCG_EINVAL;
+    BCHECK(h, out, "prcg_batch_create: null output pointer");
+    *out = nullptr;
+    BCHECK(h, rows_off && nnz_off && indptr && indices && data && mat_of, "prcg_batch_create: null pointer argument");
+    BCHECK(h, n_sys >= 1, "prcg_batch_create: n_sys = %d: a batch holds at least one system", n_sys);
+    BCHECK(h, n_mat >= 1, "prcg_batch_create: n_mat = %d: a batch holds at least one matrix", n_mat);
+    const BatchHost host = batch_host(h);
+    BCHECK(h, !host.comm, "prcg_batch_create: the handle carries a communicator: a batch runs on one GPU, on a handle without one");
+    BCHECK(h, rows_off[0] == 0 && nnz_off[0] == 0, "prcg_batch_create: inconsistent offsets: rows_off[0] and nnz_off[0] must be 0");
+    std::vector<int> mrl((size_t)n_mat, 0);
+    for (int m = 0; m < n_mat; ++m) {
+        const int64_t nm = rows_off[m + 1] - rows_off[m], zm = nnz_off[m + 1] - nnz_off[m];
+        BCHECK(h, nm >= 1 && zm >= 0 && nm < (1 << 30) && zm < (1ll << 31),
+               "prcg_batch_create: inconsistent offsets: matrix %d has %lld rows and %lld nonzeros", m, (long long)nm, (long long)zm);
+        const int32_t* ip = indptr + rows_off[m] + m;            // n_m + 1 entries per matrix
+        BCHECK(h, ip[0] == 0 && ip[nm] == zm, "prcg_batch_create: inconsistent offsets: indptr of matrix %d runs from %d to %d, its "
+               "nonzeros number %lld (indptr is zero-based per matrix)", m, ip[0], ip[nm], (long long)zm);
+        for (int64_t i = 0; i < nm; ++i) {
+            BCHECK(h, ip[i + 1] >= ip[i], "prcg_batch_create: inconsistent offsets: indptr of matrix %d decreases at row %lld", m, (long long)i);
+            if (ip[i + 1] - ip[i] > mrl[(size_t)m]) mrl[(size_t)m] = ip[i + 1] - ip[i];
+        }
+        const int32_t* ci = indices + nnz_off[m];
+        for (int64_t q = 0; q < zm; ++q)
+            BCHECK(h, ci[q] >= 0 && ci[q] < nm, "prcg_batch_create: column index %d of matrix %d (nonzero %lld) lies outside its %lld columns",
+                   ci[q], m, (long long)q, (long long)nm);
+    }
+    std::vector<int64_t> sn((size_t)n_sys), sz((size_t)n_sys);
+    std::vector<int32_t> sl((size_t)n_sys), mode((size_t)n_sys), group((size_t)n_sys);
+    for (int s = 0; s < n_sys; ++s) {
+        const int m = mat_of[s];
+        BCHECK(h, m >= 0 && m < n_mat, "prcg_batch_create: mat_of[%d] = %d lies outside [0, %d): system %d names no matrix", s, m, n_mat, s);
+        sn[(size_t)s] = rows_off[m + 1] - rows_off[m]; sz[(size_t)s] = nnz_off[m + 1] - nnz_off[m]; sl[(size_t)s] = mrl[(size_t)m];
+    }
+    const int ng = plan_groups(n_sys, sn.data(), sz.data(), sl.data(), mode.data(), group.data());
+    if (ng < 0) {
+        const int s = -ng - 1;
+        return batch_fail(h, PRCG_EINVAL, "prcg_batch_create: system %d (n = %lld, nnz = %lld, longest row %d) does not fit the one-workgroup "
+                          "solver (at most 4096 rows, and the matrix in registers or in LDS beside the vectors); a batch has no other "
+                          "schedule: solve it in a session of its own", s, (long long)sn[(size_t)s], (long long)sz[(size_t)s], sl[(size_t)s]);
+    }
+    prcg_batch* b = new (std::nothrow) prcg_batch();
+    if (!b) return batch_fail(h, PRCG_ENOMEM, "out of host memory");
+    struct Guard { prcg_batch* b; ~Guard() { delete b; } } guard{b};      // (released on success)
+    b->h = h; b->dev = host.dev; b->sc = host.sc; b->n_sys = n_sys;
+    BHIP(h, hipSetDevice(b->dev));
+    const int64_t rows_all = rows_off[n_mat], nnz_all = nnz_off[n_mat];
+    BHIP(h, b->m_indptr.ensure((size_t)(rows_all + n_mat) * sizeof(int32_t)));
+    BHIP(h, b->m_col.ensure((size_t)nnz_all * sizeof(int32_t)));
+    BHIP(h, b->m_val.ensure((size_t)nnz_all * sizeof(double)));
+    BHIP(h, hipMemcpyAsync(b->m_indptr.p, indptr, (size_t)(rows_all + n_mat) * sizeof(int32_t), hipMemcpyHostToDevice, b->sc));
+    if (nnz_all) {
+        BHIP(h, hipMemcpyAsync(b->m_col.p, indices, (size_t)nnz_all * sizeof(int32_t), hipMemcpyHostToDevice, b->sc));
+        BHIP(h, hipMemcpyAsync(b->m_val.p, data, (size_t)nnz_all * sizeof(double), hipMemcpyHostToDevice, b->sc));
+    }
+    BHIP(h, hipStreamSynchronize(b->sc));
+    b->n.resize((size_t)n_sys); b->nnz.resize((size_t)n_sys); b->mode.resize((size_t)n_sys); b->slot.resize((size_t)n_sys);
+    b->voff.assign((size_t)n_sys + 1, 0);
+    b->indptr.resize((size_t)n_sys); b->col.resize((size_t)n_sys); b->val.resize((size_t)n_sys);
+    for (int s = 0; s < n_sys; ++s) {
+        const int m = mat_of[s], md = mode[(size_t)s];
+        b->n[(size_t)s] = (int)sn[(size_t)s]; b->nnz[(size_t)s] = (int)sz[(size_t)s]; b->mode[(size_t)s] = md;
+        b->voff[(size_t)s + 1] = b->voff[(size_t)s] + sn[(size_t)s];
+        b->indptr[(size_t)s] = static_cast<const int*>(b->m_indptr.p) + rows_off[m] + m;
+        b->col[(size_t)s] = static_cast<const int*>(b->m_col.p) + nnz_off[m];
+        b->val[(size_t)s] = b->m_val.d() + nnz_off[m];
+        ++b->count[md];
+        const size_t need = small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], md);
+        if (need > b->lds[md]) b->lds[md] = need;
+    }
+    int at[2] = {b->count[1], 0};                  // descriptors: mode 1 first, then mode 0, each in system order
+    for (int s = 0; s < n_sys; ++s) b->slot[(size_t)s] = at[b->mode[(size_t)s]]++;
+    guard.b = nullptr;
+    *out = b;
+    return PRCG_OK;
+}
+
+void prcg_batch_destroy(prcg_batch_t* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->dev);
+    (void)hipStreamSynchronize(b->sc);
+    delete b;
+}
+
+int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
+           "prcg_batch_begin: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", variant);
+    BCHECK(h, rhs && x0, "prcg_batch_begin: null rhs or x0");
+    BCHECK(h, max_iter >= 1, "prcg_batch_begin: max_iter = %d, must be at least 1", max_iter);
+    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+           "prcg_batch_begin: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", hist_mask);
+    BHIP(h, hipSetDevice(b->dev));
+    b->in_session = false;
+    const int n_sys = b->n_sys;
+    const int64_t N = b->N();
+    const size_t D = sizeof(double);
+    const bool hs = variant == PRCG_HS;
+    BHIP(h, b->state.ensure((size_t)4 * N * D));
+    BHIP(h, b->rhs.ensure((size_t)N * D));
+    BHIP(h, b->x0.ensure((size_t)N * D));
+    BHIP(h, b->tmp.ensure((size_t)N * D));
+    BHIP(h, b->dots.ensure((size_t)n_sys * (max_iter + 1) * kNS * D));
+    BHIP(h, b->coef.ensure((size_t)n_sys * (max_iter + 1) * kCoefStride * D));
+    BHIP(h, b->desc.ensure((size_t)n_sys * sizeof(SmallArgs)));
+    BHIP(h, b->init.ensure((size_t)n_sys * sizeof(SmallInit)));
+    b->variant = variant; b->hs = hs; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
+    std::vector<SmallArgs> desc((size_t)n_sys);
+    std::vector<SmallInit> init((size_t)n_sys);
+    double* st = b->state.d();
+    for (int s = 0; s < n_sys; ++s) {
+        const int64_t v = b->voff[(size_t)s];
+        SmallArgs a{};
+        a.n = b->n[(size_t)s]; a.nnz = b->nnz[(size_t)s];
+        a.indptr = b->indptr[(size_t)s]; a.col = b->col[(size_t)s]; a.val = b->val[(size_t)s];
+        if (hs) { a.xp = st + v; a.rs = st + N + v; a.hs_p = st + 2 * N + v; a.hs_s = st + 3 * N + v; }
+        else { a.xp = st + 2 * v; a.rs = st + 2 * N + 2 * v; }
+        a.dots = b->dots_of(s); a.coef = b->coef_of(s);
+        desc[(size_t)b->slot[(size_t)s]] = a;
+        init[(size_t)b->slot[(size_t)s]] = SmallInit{b->rhs.d() + v, b->x0.d() + v};
+    }
+    hipStream_t sc = b->sc;
+    BHIP(h, hipMemsetAsync(b->dots.p, 0, (size_t)n_sys * (max_iter + 1) * kNS * D, sc));
+    BHIP(h, hipMemsetAsync(b->coef.p, 0, (size_t)n_sys * (max_iter + 1) * kCoefStride * D, sc));
+    BHIP(h, hipMemcpyAsync(b->rhs.p, rhs, (size_t)N * D, hipMemcpyHostToDevice, sc));
+    BHIP(h, hipMemcpyAsync(b->x0.p, x0, (size_t)N * D, hipMemcpyHostToDevice, sc));
+    BHIP(h, hipMemcpyAsync(b->desc.p, desc.data(), (size_t)n_sys * sizeof(SmallArgs), hipMemcpyHostToDevice, sc));
+    BHIP(h, hipMemcpyAsync(b->init.p, init.data(), (size_t)n_sys * sizeof(SmallInit), hipMemcpyHostToDevice, sc));
+    BHIP(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
+    for (int m = 1; m >= 0; --m)                   // one initialisation launch per group
+        if (b->count[m] && launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), b->count[m], hs) < 0)
+            return batch_fail(h, PRCG_EHIP, "prcg_batch_begin: kernel launch failed");
+    BHIP(h, hipStreamSynchronize(sc));
+    b->in_session = true;
+    return PRCG_OK;
+}
+
+int prcg_batch_iterate(prcg_batch_t* b, int iters) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session, "prcg_batch_iterate: no open session");
+    BCHECK(h, iters >= 0, "prcg_batch_iterate: negative count");
+    BCHECK(h, b->k + iters <= b->max_iter, "prcg_batch_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters, b->max_iter, b->k);
+    if (iters == 0) return PRCG_OK;
+    BHIP(h, hipSetDevice(b->dev));
+    for (int m = 1; m >= 0; --m)                   // one launch per group: every system advances by iters
+        if (b->count[m] && launch_small_batch(b->sc, b->desc_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters,
+                                              b->variant == PRCG_PIPE_PR_M ? 1 : 0) < 0)
+            return batch_fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
+    b->k += iters;
+    return PRCG_OK;
+}
+
+int prcg_batch_sync(prcg_batch_t* b) {
+    if (!b) return PRCG_EINVAL;
+    BHIP(b->h, hipSetDevice(b->dev));
+    BHIP(b->h, hipStreamSynchronize(b->sc));
+    return PRCG_OK;
+}
+
+int prcg_batch_iteration(const prcg_batch_t* b) { return b ? b->k : -1; }
+
+static int batch_d2h(prcg_batch_t* b, double* dst, const double* src, int64_t count) {
+    BHIP(b->h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->sc));
+    BHIP(b->h, hipStreamSynchronize(b->sc));
+    return PRCG_OK;
+}
+
+int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session && out, "prcg_batch_get_vector: no session or null buffer");
+    BCHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_vector: system %d outside [0, %d)", s, b->n_sys);
+    BCHECK(h, which == PRCG_VEC_X || which == PRCG_VEC_R || which == PRCG_VEC_P || which == PRCG_VEC_S,
+           "prcg_batch_get_vector: vector %d is not part of a batch session (PRCG_VEC_X, _R, _P, _S)", which);
+    BHIP(h, hipSetDevice(b->dev));
+    const int64_t N = b->N(), v = b->voff[(size_t)s], n = b->n[(size_t)s];
+    const int idx = which == PRCG_VEC_X ? 0 : which == PRCG_VEC_R ? 1 : which == PRCG_VEC_P ? 2 : 3;
+    if (b->hs) return batch_d2h(b, out, b->state.d() + idx * N + v, n);
+    // pairs (x,p) and (r,s): component (idx >> 1) of pair array (idx & 1)
+    launch_copy(b->sc, b->tmp.d(), 1, b->state.d() + (idx & 1) * 2 * N + 2 * v + (idx >> 1), 2, n);
+    return batch_d2h(b, out, b->tmp.d(), n);
+}
+
+int prcg_batch_get_solutions(prcg_batch_t* b, double* x_cat) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session && x_cat, "prcg_batch_get_solutions: no session or null buffer");
+    BHIP(h, hipSetDevice(b->dev));
+    const int64_t N = b->N();
+    if (b->hs) return batch_d2h(b, x_cat, b->state.d(), N);
+    launch_copy(b->sc, b->tmp.d(), 1, b->state.d(), 2, N);       // the x of every (x,p) pair, all systems at once
+    return batch_d2h(b, x_cat, b->tmp.d(), N);
+}
+
+int prcg_batch_get_scalars(prcg_batch_t* b, int k, int s, double* out) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session && out && k >= 0 && k <= b->max_iter && s >= 0 && s < b->n_sys, "prcg_batch_get_scalars: bad argument");
+    BHIP(h, hipSetDevice(b->dev));
+    return batch_d2h(b, out, b->dots_of(s) + (size_t)k * kNS, kNS);
+}
+
+int prcg_batch_get_coefficients(prcg_batch_t* b, int k, int s, double* out) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session && out && k >= 1 && k <= b->max_iter && s >= 0 && s < b->n_sys, "prcg_batch_get_coefficients: bad argument");
+    BHIP(h, hipSetDevice(b->dev));
+    return batch_d2h(b, out, b->coef_of(s) + (size_t)k * kCoefStride, 3);
+}
+
+int prcg_batch_get_history(prcg_batch_t* b, int s, double* hist) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session && hist, "prcg_batch_get_history: no session or null buffer");
+    BCHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_history: system %d outside [0, %d)", s, b->n_sys);
+    if (!(b->hist_mask & PRCG_HIST_UPDATED_RESIDUAL_2_NORM)) return PRCG_OK;
+    BHIP(h, hipSetDevice(b->dev));
+    const int m = b->max_iter;
+    std::vector<double> all((size_t)(m + 1) * kNS);
+    if (int rc = batch_d2h(b, all.data(), b->dots_of(s), (int64_t)(m + 1) * kNS)) return rc;
+    for (int k = 0; k < m; ++k) hist[k] = k <= b->k ? std::sqrt(all[(size_t)k * kNS + PRCG_S_RR]) : 0.0;
+    return PRCG_OK;
+}
+
+}  // extern "C"

@@ -31,6 +31,7 @@
 #include "../../include/prcg.h"
 #include "../../include/prcg_test.h"
 #include "prcg_kernels.h"
+#include "prcg_batch.h"
 #include "prcg_bjvar.h"
 #include "prcg_plan.h"
 #include "prcg_rccl.h"
@@ -3623,3 +3624,19 @@ void prcg_tile_caps(int* cap_nnz, int* cap_rows) {
 }
 
 }  // extern "C"
+
+// ---- what a batch of small systems borrows from its handle (prcg_batch.h; the batch itself: prcg_batch.cpp) ----
+namespace prcg {
+
+BatchHost batch_host(const prcg_handle* h) { return BatchHost{h->dev, h->sc, h->multi()}; }
+
+int batch_fail(prcg_handle* h, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return fail(h, code, "%s", buf);
+}
+
+}  // namespace prcg

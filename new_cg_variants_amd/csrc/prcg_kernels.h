@@ -317,6 +317,18 @@ struct SmallArgs {
 bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode);
 int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode);
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode);      // Hestenes-Stiefel, same storage
+// ---- a batch of small systems: the same solver, one workgroup per system, blockIdx.x selects the system (prcg_batch.cpp) ----
+// desc: `count` SmallArgs in DEVICE memory, all of one mode (k0, iters, meurant in them are ignored: the launch carries them);
+// lds: the largest small_lds_bytes(n, nnz, mode) among them -- each workgroup carves it by its own n and nnz.
+// Results of a system are those of launch_small_pipe_pr / launch_small_hs with its descriptor, bit for bit, whatever its
+// position or company in the launch.  The dynamic-LDS attribute is set, and its result checked, on first use on each device.
+struct SmallInit { const double* b; const double* x0; };       // right-hand side and initial guess of one system
+size_t small_lds_bytes(int n, int nnz, int mode);
+int launch_small_batch(hipStream_t st, const SmallArgs* desc, int count, int mode, size_t lds, bool hs, int k0, int iters, int meurant);
+// x = x0, r = b - A x0, p = r, s = A p and row 0 of every system's scalars in ONE launch; init[i] belongs to desc[i].  The
+// vectors carry the bits of the single session's start-up launches; the inner products are summed in the order of the loop
+// (thread-sequential rows, wave butterfly, 16 waves), not of those launches.
+int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, int count, bool hs);
 
 // ---- fused vector updates + inner products -----------------------------------------
 struct PipeUpdateArgs {

@@ -687,8 +687,10 @@ constexpr int kSmallMaxN = kSmallThreads * kSmallRows;
 //         nonzeros -- the paper's small test matrices (nos7: rows of 4-7, bcsstk03: 4-6).
 constexpr int kSmallRegLen = 8;
 
+// The body is a device function of its argument: k_small_pipe_pr hands it the launch's SmallArgs, k_small_pipe_pr_batch the
+// descriptor of workgroup blockIdx.x -- one body, so that a system of a batch carries the single solver's bits.
 template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) {
+__device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
     const int n = a.n, nnz = a.nnz;
@@ -804,6 +806,8 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) {
         if (row < n) { XPo[row] = make_double2(xr[j], pr[j]); RSo[row] = cur[row]; }
     }
 }
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { small_pipe_pr_body<MODE>(a); }
 
 // ---- Hestenes-Stiefel, the whole solve of a SMALL system in one launch of one workgroup (hs_cg.py:54-62) ----
 // BASELINE config 1 is bcsstk03 (n = 112) under hs_cg: two launches and two kernel boundaries per iteration cost it 9-10 us each.
@@ -813,7 +817,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) {
 // s = A p;  mu = p.s  -- two workgroup-wide sums (the two reductions that make Hestenes-Stiefel what it is), three barriers.
 // Scalars as the launches leave them: dots[k] = {mu_k, -, -, nu_k, rr_k}, coef[k] = {a_k, b_k}.
 template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) {
+__device__ __forceinline__ void small_hs_body(const SmallArgs& a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
     const int n = a.n, nnz = a.nnz;
@@ -914,6 +918,85 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) {
     for (int j = 0; j < ROWS; ++j) {
         const int row = tid + j * kSmallThreads;
         if (row < n) { a.xp[row] = xr[j]; a.rs[row] = rr_[j]; a.hs_p[row] = pr[j]; a.hs_s[row] = sr[j]; }
+    }
+}
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small_hs_body<MODE>(a); }
+
+// ---- a BATCH of small systems: one launch, workgroup blockIdx.x solves system desc[blockIdx.x] (prcg_batch.cpp) ----
+// The descriptors live in device memory, one SmallArgs per system with pointers into the batch's concatenated matrix, state,
+// scalar and coefficient buffers; blockIdx.x is uniform, so a workgroup reads its descriptor with uniform loads.  Where the
+// session stands (k0, iters, meurant) is the same for every system and comes with the launch.  Each workgroup carves the
+// launch's dynamic LDS by its OWN n and nnz (the bodies do), so a system's bits do not depend on its neighbours in the launch.
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_batch(const SmallArgs* __restrict__ desc, int k0, int iters, int meurant) {
+    SmallArgs a = desc[blockIdx.x];
+    a.k0 = k0; a.iters = iters; a.meurant = meurant;
+    small_pipe_pr_body<MODE>(a);
+}
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs_batch(const SmallArgs* __restrict__ desc, int k0, int iters) {
+    SmallArgs a = desc[blockIdx.x];
+    a.k0 = k0; a.iters = iters; a.meurant = 0;
+    small_hs_body<MODE>(a);
+}
+
+// Initial state of every system of a batch in ONE launch (pipe_pr_cg.py:22-28, hs_cg.py:22-27), workgroup blockIdx.x for system
+// desc[blockIdx.x]:  x = x0;  r = b - A x0;  p = r;  s = A p  -- row sums left to right from +0.0 and the expressions of the
+// single session's start-up launches, so the four vectors carry its bits -- and the inner products of row 0 of the scalars
+// (pipelined: mu = p.s, delta = r.s, gamma = s.s, nu = rr = r.r; Hestenes-Stiefel: mu, nu = rr), summed in the order of the LOOP:
+// thread-sequential over rows tid, tid + 1024, ..., wave butterfly, 16 waves.  (The single session sums its initial products in
+// the order of its start-up launches: row 0 may differ from it in the last bit.)  The matrix is read from memory: once.
+template <bool HS>
+__global__ __launch_bounds__(kSmallThreads) void k_small_batch_init(const SmallArgs* __restrict__ desc, const SmallInit* __restrict__ init) {
+    __shared__ double rl[kSmallMaxN];                            // r (= p): the source of s = A p
+    __shared__ double red[64];                                   // [16 waves][4]
+    const SmallArgs a = desc[blockIdx.x];
+    const SmallInit in = init[blockIdx.x];
+    const int n = a.n;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double xr[kSmallRows], rr_[kSmallRows];
+#pragma unroll
+    for (int j = 0; j < kSmallRows; ++j) {
+        const int row = tid + j * kSmallThreads;
+        xr[j] = 0.0; rr_[j] = 0.0;
+        if (row < n) {
+            double t = 0.0;                                      // (A x0)_i, left to right
+            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) t += a.val[q] * in.x0[a.col[q]];
+            xr[j] = in.x0[row];                                  // x = x0
+            rr_[j] = in.b[row] - t;                              // r = b - A x
+            rl[row] = rr_[j];
+        }
+    }
+    __syncthreads();
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+#pragma unroll
+    for (int j = 0; j < kSmallRows; ++j) {
+        const int row = tid + j * kSmallThreads;
+        if (row < n) {
+            double sp = 0.0;                                     // (A p)_i, p = r, left to right
+            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) sp += a.val[q] * rl[a.col[q]];
+            const double rn = rr_[j];
+            if constexpr (HS) {
+                a.xp[row] = xr[j]; a.rs[row] = rn; a.hs_p[row] = rn; a.hs_s[row] = sp;
+            } else {
+                reinterpret_cast<double2*>(a.xp)[row] = make_double2(xr[j], rn);
+                reinterpret_cast<double2*>(a.rs)[row] = make_double2(rn, sp);
+            }
+            acc0 += rn * sp; acc1 += rn * sp; acc2 += sp * sp; acc3 += rn * rn;      // p.s, r.s (p = r), s.s, r.r
+        }
+    }
+    acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2); acc3 = wave_sum(acc3);
+    if (lane == 0) { red[wv * 4 + 0] = acc0; red[wv * 4 + 1] = acc1; red[wv * 4 + 2] = acc2; red[wv * 4 + 3] = acc3; }
+    __syncthreads();
+    const double mu = wave_sum16(red[(lane & 15) * 4 + 0]);
+    const double dl = wave_sum16(red[(lane & 15) * 4 + 1]);
+    const double gm = wave_sum16(red[(lane & 15) * 4 + 2]);
+    const double nu = wave_sum16(red[(lane & 15) * 4 + 3]);
+    if (tid == 0) {
+        double* d = a.dots;                                      // row 0
+        d[0] = mu; d[3] = nu; d[4] = nu;
+        if constexpr (!HS) { d[1] = dl; d[2] = gm; }
     }
 }
 
@@ -1303,6 +1386,36 @@ int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode) {
     if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr<1>, dim3(1), dim3(kSmallThreads), lds, st, a);
     else hipLaunchKernelGGL(k_small_pipe_pr<0>, dim3(1), dim3(kSmallThreads), lds, st, a);
     return PRCG_LAUNCH_OK() ? 1 : -1;
+}
+
+// ---- batch of small systems: `count` workgroups, one per descriptor (all of one mode; lds: the largest small_lds_bytes among them)
+int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, int count, bool hs) {
+    if (hs) hipLaunchKernelGGL(k_small_batch_init<true>, dim3(count), dim3(kSmallThreads), 0, st, desc, init);
+    else hipLaunchKernelGGL(k_small_batch_init<false>, dim3(count), dim3(kSmallThreads), 0, st, desc, init);
+    return PRCG_LAUNCH_OK() ? count : -1;
+}
+int launch_small_batch(hipStream_t st, const SmallArgs* desc, int count, int mode, size_t lds, bool hs, int k0, int iters, int meurant) {
+    // the kernels may ask for more dynamic LDS than the default 64 KB.  The attribute belongs to the CURRENT device: set once per
+    // device, and only a SUCCESSFUL call counts as done
+    constexpr int kMaxDev = 64;
+    static bool attr_done[kMaxDev] = {};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
+    if (dev >= kMaxDev || !attr_done[dev]) {
+        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_batch<0>), reinterpret_cast<const void*>(k_small_pipe_pr_batch<1>),
+                              reinterpret_cast<const void*>(k_small_hs_batch<0>), reinterpret_cast<const void*>(k_small_hs_batch<1>)};
+        for (const void* f : fns)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
+        if (dev < kMaxDev) attr_done[dev] = true;
+    }
+    if (hs) {
+        if (mode == 1) hipLaunchKernelGGL(k_small_hs_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters);
+        else hipLaunchKernelGGL(k_small_hs_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters);
+    } else {
+        if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters, meurant);
+        else hipLaunchKernelGGL(k_small_pipe_pr_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters, meurant);
+    }
+    return PRCG_LAUNCH_OK() ? count : -1;
 }
 
 int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a) {

@@ -577,6 +577,169 @@ class DeviceCSR:
         return x, {q: hist[i].copy() for i, q in enumerate(names)}, t.as_dict()
 
 
+def batch_matrices(As, n_sys=None):
+    """(matrices, mat_of) of a batch from what the caller passes as `As`: ONE matrix (every one of the n_sys systems uses it) or a
+    sequence of matrices, one per system -- entries that are the same object become one matrix of the batch (one upload).
+    Pure host work; ValueError names what is wrong."""
+    if hasattr(As, 'indptr'):
+        if n_sys is None:
+            raise ValueError('one matrix for every system needs the number of systems')
+        return [As], [0] * int(n_sys)
+    As = list(As)
+    if n_sys is not None and len(As) != n_sys:
+        raise ValueError(f'As must be one matrix or a sequence of {n_sys} matrices, one per right-hand side -- got {len(As)}')
+    matrices, mat_of, seen = [], [], {}
+    for A in As:
+        if not hasattr(A, 'indptr'):
+            raise TypeError('every entry of As must be a scipy.sparse CSR matrix/array')
+        if id(A) not in seen:
+            seen[id(A)] = len(matrices)
+            matrices.append(A)
+        mat_of.append(seen[id(A)])
+    return matrices, mat_of
+
+
+def batch_vectors(name, V, sizes):
+    """The systems' vectors concatenated in system order (1-D float64) from a list of vectors or, when all sizes agree, one 2-D
+    array (n_sys, n); ValueError names the expected shape."""
+    n_sys = len(sizes)
+    if isinstance(V, np.ndarray) and V.ndim == 2:
+        if len(set(sizes)) != 1:
+            raise ValueError(f'{name} is one 2-D array of shape {tuple(V.shape)} but the systems have different sizes: pass a list of '
+                             f'{n_sys} vectors, {name}[s] of shape (n_s,)')
+        if V.shape != (n_sys, sizes[0]):
+            raise ValueError(f'{name} must have shape ({n_sys}, {sizes[0]}) -- one row per system -- got {tuple(V.shape)}')
+        return L.f64(V).reshape(-1)
+    V = list(V)
+    if len(V) != n_sys:
+        raise ValueError(f'{name} must hold {n_sys} vectors, one per system -- got {len(V)}')
+    out = np.empty(int(sum(sizes)))
+    at = 0
+    for s, (v, n) in enumerate(zip(V, sizes)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape != (n,):
+            raise ValueError(f'{name}[{s}] must have shape ({n},), the size of system {s} -- got {tuple(v.shape)}')
+        out[at:at + n] = v
+        at += n
+    return out
+
+
+class DeviceBatch:
+    """A batch of small independent systems A_s x_s = b_s solved in ONE launch, one workgroup per system (prcg.h:
+    prcg_batch_create): what a Python loop over ``DeviceCSR(A).begin(...); iterate(...)`` computes for matrices that fit the
+    one-workgroup solver, without a handle, a planning pass and a launch per system.
+
+    ``matrices``: a sequence of scipy.sparse CSR matrices; ``mat_of[s]``: the matrix of system s (default: system s uses
+    matrix s).  Systems that share a matrix share its upload.  Every system must fit the one-workgroup solver (n <= 4096, the
+    matrix in registers or LDS): anything else is refused, a batch has no other schedule.
+    """
+
+    def __init__(self, matrices, mat_of=None, device=0):
+        if hasattr(matrices, 'indptr'):
+            matrices = [matrices]
+        mats = []
+        for A in matrices:
+            if not hasattr(A, 'indptr'):
+                raise TypeError('every matrix must be a scipy.sparse CSR matrix/array')
+            if A.format != 'csr':
+                A = A.tocsr()
+            if A.dtype != np.float64:
+                raise TypeError(f'fp64 only (got {A.dtype}); the reference works in double precision')
+            if A.shape[0] != A.shape[1]:
+                raise ValueError(f'a system of a batch is square, got a matrix of shape {A.shape}')
+            mats.append(A)
+        if not mats:
+            raise ValueError('a batch holds at least one matrix')
+        mat_of = np.arange(len(mats), dtype=np.int32) if mat_of is None else np.ascontiguousarray(mat_of, dtype=np.int32)
+        if mat_of.ndim != 1:
+            raise ValueError(f'mat_of must be one-dimensional, got shape {mat_of.shape}')
+        rows_off = np.concatenate([[0], np.cumsum([A.shape[0] for A in mats])]).astype(np.int64)
+        nnz_off = np.concatenate([[0], np.cumsum([A.nnz for A in mats])]).astype(np.int64)
+        indptr = np.concatenate([np.asarray(A.indptr, dtype=np.int32) for A in mats])
+        indices = np.ascontiguousarray(np.concatenate([A.indices for A in mats]), dtype=np.int32)
+        data = np.ascontiguousarray(np.concatenate([A.data for A in mats]), dtype=np.float64)
+        self._lib = L.lib()
+        self._h, self._b = C.c_void_p(), C.c_void_p()
+        self.device = int(device)
+        rc = self._lib.prcg_create(C.byref(self._h), int(device))
+        if rc != L.OK:
+            msg = self._lib.prcg_last_error(None)
+            self._h = C.c_void_p()
+            raise L.PrcgError(rc, msg.decode() if msg else '?')
+        try:
+            self._check(self._lib.prcg_batch_create(self._h, len(mats), L.ptr(rows_off), L.ptr(nnz_off), L.ptr(indptr), L.ptr(indices),
+                                                    L.ptr(data), int(mat_of.size), L.ptr(mat_of), C.byref(self._b)))
+        except Exception:
+            self.close()
+            raise
+        self.n_sys = int(mat_of.size)
+        self.sizes = [int(mats[m].shape[0]) for m in mat_of]
+        self.max_iter, self.hist_mask = 0, 0
+
+    def _check(self, rc):
+        L.check(self._h, rc)
+
+    def close(self):
+        if getattr(self, '_b', None) is not None and self._b.value:
+            self._lib.prcg_batch_destroy(self._b)
+            self._b = C.c_void_p()
+        if getattr(self, '_h', None) is not None and self._h.value:
+            self._lib.prcg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def begin(self, variant, B, X0, max_iter, hist_mask=0):
+        """variant: L.PIPE_PR, L.PIPE_PR_M or L.HS.  B, X0: a list of vectors, one per system, or one 2-D array (n_sys, n) when
+        all sizes agree.  hist_mask: 0 or L.HIST_UPDATED_RESIDUAL_2_NORM."""
+        b, x0 = batch_vectors('B', B, self.sizes), batch_vectors('X0', X0, self.sizes)
+        self._check(self._lib.prcg_batch_begin(self._b, int(variant), L.ptr(b), L.ptr(x0), int(max_iter), int(hist_mask)))
+        self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
+
+    def iterate(self, iters):
+        self._check(self._lib.prcg_batch_iterate(self._b, int(iters)))
+
+    def sync(self):
+        self._check(self._lib.prcg_batch_sync(self._b))
+
+    @property
+    def k(self):
+        return self._lib.prcg_batch_iteration(self._b)
+
+    def get_vector(self, name, s):
+        out = np.empty(self.sizes[s])
+        self._check(self._lib.prcg_batch_get_vector(self._b, L.VEC[name], int(s), L.ptr(out)))
+        return out
+
+    def solutions(self):
+        """every system's x, concatenated in system order (one copy from the device)"""
+        out = np.empty(int(sum(self.sizes)))
+        self._check(self._lib.prcg_batch_get_solutions(self._b, L.ptr(out)))
+        return out
+
+    def get_scalars(self, k, s):
+        out = np.empty(L.NUM_SCALARS)
+        self._check(self._lib.prcg_batch_get_scalars(self._b, int(k), int(s), L.ptr(out)))
+        return out
+
+    def get_coefficients(self, k, s):
+        out = np.empty(3)
+        self._check(self._lib.prcg_batch_get_coefficients(self._b, int(k), int(s), L.ptr(out)))
+        return out
+
+    def history(self, s):
+        """dict recorder-name -> array(max_iter) of system s ({} when hist_mask was 0)"""
+        if not self.hist_mask & L.HIST_UPDATED_RESIDUAL_2_NORM:
+            return {}
+        buf = np.zeros(self.max_iter)
+        self._check(self._lib.prcg_batch_get_history(self._b, int(s), L.ptr(buf)))
+        return {'updated_residual_2_norm': buf}
+
+
 def multi_rhs_shape_error(name, shape, n, nrhs=None):
     """None if `shape` is (2, n) or (4, n) -- (nrhs, n) when nrhs is given -- else the text of the ValueError."""
     if len(shape) == 2 and shape[1] == n and shape[0] in ((2, 4) if nrhs is None else (nrhs,)):
