@@ -455,6 +455,21 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
  *                      PRCG_HS, unpreconditioned.  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.  One launch per launch
  *                      group computes x = x0, r = b - A x0, p = r, s = A p and the initial inner products of every system.
  *                      May be called again: a new session on the same matrices.
+ *   prcg_batch_begin_jacobi  the same three variants preconditioned by a diagonal scaling that is applied INSIDE the one-workgroup
+ *                      solver: replaces the reference's `*_pcg` calls with the Jacobi lambda `(1/A.diagonal())*x` (figure_gen.py:43 and
+ *                      the `*_pcg` half of the convergence table; pipe_pr_cg.py:109-193 for PRCG_PIPE_PR / PRCG_PIPE_PR_M, hs_cg.py:70-131
+ *                      for PRCG_HS).  inv_diag: the systems' reciprocal diagonals concatenated in system order like rhs -- they belong
+ *                      to the SYSTEM, not the matrix: two systems on one matrix may differ.  Its values are not inspected: a zero, inf
+ *                      or nan poisons its own system only, as a bad right-hand side does.  One launch per group computes x = x0,
+ *                      r = b - A x0, r~ = d r, p = r~, s = A p (pipelined: s~ = d s) and row 0 of the scalars.  The pipelined state is
+ *                      the six vectors x, p, r, s, r~, s~ (w = A r~ and u = A s~ are formed anew in every iteration); scalars per
+ *                      iteration {mu = p.s, delta = r.s~, gamma = s~.s, nu = r~.r, rr = r.r}, Hestenes-Stiefel {mu, -, -, nu, rr}; the
+ *                      history is sqrt(rr).  The per-row expressions are those of a single Jacobi session: from the same state and
+ *                      coefficients one iteration yields the same vectors, bit for bit.  The session then runs through
+ *                      prcg_batch_iterate / _sync / the accessors below, unchanged.  With inv_diag = ones a system carries the bits of
+ *                      prcg_batch_begin's.  Refused beside what prcg_batch_begin refuses: null inv_diag; a system whose matrix lives in
+ *                      LDS and lies within 128 bytes of the cap -- the fifth inner product needs 128 bytes more (the text names the
+ *                      first such system).
  *   prcg_batch_iterate enqueues; every system advances by iters (k + iters <= max_iter).  prcg_batch_sync waits.
  * Launch groups: the systems whose matrix lives in registers (n <= 1024, rows of at most 8) form one launch, those whose matrix
  * lives in LDS another; a call is one launch per group.
@@ -470,15 +485,19 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
  * decreases), a column index outside its matrix, a mat_of entry out of range, a system that does not fit the one-workgroup
  * solver (a batch has no other schedule); begin -- another variant, another history bit, null rhs or x0, max_iter < 1.
  * Errors are reported through prcg_last_error of the handle the batch was created on.
- * Accessors (they synchronise): s = the system.  prcg_batch_get_vector: PRCG_VEC_X, _R, _P, _S, the system's n doubles;
+ * Accessors (they synchronise): s = the system.  prcg_batch_get_vector: PRCG_VEC_X, _R, _P, _S, the system's n doubles, and in a
+ * pipelined session begun with prcg_batch_begin_jacobi also PRCG_VEC_RT, _ST (refused in any other batch session);
  * prcg_batch_get_solutions: every x concatenated in system order, ONE copy; scalars / coefficients / history as
  * prcg_get_scalars / prcg_get_coefficients / prcg_get_history return them (history: max_iter doubles, nothing is written when
- * hist_mask was 0).  No setters, no preconditioner, no recorder of state. */
+ * hist_mask was 0).  No setters, no recorder of state, no preconditioner but the diagonal scaling of prcg_batch_begin_jacobi (no
+ * block Jacobi, no callback). */
 typedef struct prcg_batch prcg_batch_t;
 int  prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
                        const int32_t* indices, const double* data, int n_sys, const int32_t* mat_of, prcg_batch_t** out);
 void prcg_batch_destroy(prcg_batch_t* b);
 int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask);
+int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
+                            uint32_t hist_mask);
 int prcg_batch_iterate(prcg_batch_t* b, int iters);
 int prcg_batch_sync(prcg_batch_t* b);
 int prcg_batch_iteration(const prcg_batch_t* b);

@@ -182,6 +182,11 @@ int prcg_window_source_ok(int64_t n_rows, int64_t n_ghost, int components, int64
  * then unspecified), 0 on a bad argument. */
 int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
                           int32_t* group_out);
+/* The same classification under the fit rule of prcg_batch_begin_jacobi (prcg.h): the preconditioned one-workgroup solver sums
+ * five inner products and needs 128 bytes more LDS, so a system whose matrix lives in LDS and lies within 128 bytes of the cap
+ * fits prcg_plan_small_batch and not this one.  Arguments and return value as prcg_plan_small_batch. */
+int prcg_plan_small_batch_jacobi(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
+                                 int32_t* group_out);
 /* the tile caps the device kernels were compiled for */
 void prcg_tile_caps(int* cap_nnz, int* cap_rows);
 

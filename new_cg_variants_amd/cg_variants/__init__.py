@@ -748,11 +748,46 @@ pipe_pr_m_cg_multi = _make_multi_pipe(L.PIPE_PR_M, 'pipe_pr_m_cg_multi', False, 
 pipe_pr_m_pcg_multi = _make_multi_pipe(L.PIPE_PR_M, 'pipe_pr_m_pcg_multi', True, 213)
 
 
-def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs):
+def _batch_diagonals(name, preconditioner, sizes):
+    """The systems' reciprocal diagonals, one vector per system, from the `preconditioner` of a *_pcg_batch function: one
+    object (every system uses it: the sizes must agree) or a sequence with one per system, each resolved with the rule of
+    _diagonal_of; None -- the whole argument or an entry -- is the identity (ones), as the reference's *_pcg without a
+    preconditioner.  Host work only; ValueError for anything that is not a diagonal scaling."""
+    n_sys = len(sizes)
+
+    def resolve(prec, n, where):
+        if prec is None:
+            return np.ones(n)
+        if not callable(prec) and getattr(prec, 'inv_diag', None) is None and _blocks_of(prec) is None:
+            raise ValueError(f'{name}: {where} is neither callable nor carries inv_diag: a batch applies diagonal preconditioners only')
+        d, fn = _diagonal_of(prec, n)
+        if fn is not None:
+            raise ValueError(f'{name}: {where} is not a diagonal scaling: a batch applies diagonal preconditioners only '
+                             '(Jacobi, a callable v -> d * v, or block Jacobi with bs == 1)')
+        if d is None:
+            return np.ones(n)
+        d = np.asarray(d, dtype=np.float64)
+        if d.shape != (n,):
+            raise ValueError(f'{name}: {where} carries a diagonal of shape {tuple(d.shape)}, the system has size {n}')
+        return d
+    if isinstance(preconditioner, (list, tuple)):
+        if len(preconditioner) != n_sys:
+            raise ValueError(f'{name}: preconditioner must be one object or a sequence of {n_sys}, one per system -- got {len(preconditioner)}')
+        return [resolve(prec, n, f'preconditioner[{s}]') for s, (prec, n) in enumerate(zip(preconditioner, sizes))]
+    if preconditioner is not None and len(set(sizes)) != 1:
+        raise ValueError(f'{name}: one preconditioner object for {n_sys} systems of different sizes {sorted(set(sizes))}: pass a sequence '
+                         'with one per system')
+    d = resolve(preconditioner, sizes[0], 'preconditioner') if preconditioner is not None else None
+    return [np.ones(n) if d is None else d for n in sizes]
+
+
+def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=False):
     """A batch of small independent systems in ONE launch, one workgroup per system (prcg.h: prcg_batch_create): what a loop
     of `name`'s single function over the systems computes.  Every argument is checked before the device is touched; what the
-    batch does not serve raises ValueError -- nothing falls back to a loop of sessions."""
-    if kwargs.pop('preconditioner', None) is not None:
+    batch does not serve raises ValueError -- nothing falls back to a loop of sessions.  jacobi: a *_pcg_batch function,
+    kwargs['preconditioner'] resolved to one reciprocal diagonal per system (prcg.h: prcg_batch_begin_jacobi)."""
+    preconditioner = kwargs.pop('preconditioner', None)
+    if not jacobi and preconditioner is not None:
         raise ValueError(f'{name} takes no preconditioner: a batch runs the unpreconditioned one-workgroup solver')
     for key in ('x_true', 'w_replace'):
         if kwargs.get(key) is not None:
@@ -775,10 +810,12 @@ def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs):
             mask |= L.HIST_BITS[cname]
         else:
             raise ValueError(f'{name}: callback {cname or repr(cb)} is not served by a batch (the updated_residual_2_norm recorder or none)')
+    inv_diag = _batch_diagonals(name, preconditioner, sizes) if jacobi else None
     batch = DeviceBatch(matrices, mat_of, device=int(kwargs.get('device', 0)))
     try:
         at = np.concatenate([[0], np.cumsum(sizes)])
-        batch.begin(variant, [B[at[s]:at[s + 1]] for s in range(n_sys)], [X0[at[s]:at[s + 1]] for s in range(n_sys)], max_iter, hist_mask=mask)
+        batch.begin(variant, [B[at[s]:at[s + 1]] for s in range(n_sys)], [X0[at[s]:at[s + 1]] for s in range(n_sys)], max_iter, hist_mask=mask,
+                    inv_diag=inv_diag)
         batch.iterate(max_iter - 1)
         batch.sync()
         outputs = [{'name': name, 'max_iter': max_iter, 'system': s} for s in range(n_sys)]
@@ -806,6 +843,26 @@ def _make_batch(variant, name, where):
 pipe_pr_cg_batch = _make_batch(L.PIPE_PR, 'pipe_pr_cg_batch', 'pipe_pr_cg.py:89')
 pipe_pr_m_cg_batch = _make_batch(L.PIPE_PR_M, 'pipe_pr_m_cg_batch', 'pipe_pr_cg.py:101')
 hs_cg_batch = _make_batch(L.HS, 'hs_cg_batch', 'hs_cg.py:9')
+
+
+def _make_pcg_batch(variant, name, where):
+    single = name[:-len('_batch')]
+
+    def f(As, bs, x0s, max_iter, preconditioner=None, callbacks=[], **kwargs):
+        kwargs['preconditioner'] = preconditioner
+        return _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=True)
+    f.__doc__ = (f'{single} ({where}) for a BATCH of small independent systems, all solved in one launch, one workgroup per system, the '
+                 f'preconditioner applied inside it.  As, bs, x0s, callbacks and the result as {single[:-3]}cg_batch.  preconditioner: one object '
+                 '(every system uses it: the sizes must agree) or a sequence with one per system; each must be a DIAGONAL scaling -- an object '
+                 'carrying inv_diag (Jacobi), block Jacobi with bs == 1, or a callable that the exact probe shows to be v -> d * v --, anything '
+                 'else is a ValueError; None is the identity, as the reference\'s function without a preconditioner.')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+pipe_pr_pcg_batch = _make_pcg_batch(L.PIPE_PR, 'pipe_pr_pcg_batch', 'pipe_pr_cg.py:201')
+pipe_pr_m_pcg_batch = _make_pcg_batch(L.PIPE_PR_M, 'pipe_pr_m_pcg_batch', 'pipe_pr_cg.py:213')
+hs_pcg_batch = _make_pcg_batch(L.HS, 'hs_pcg_batch', 'hs_cg.py:70')
 
 
 def _make(variant, name, preconditioned):
@@ -852,5 +909,5 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_p_pcg', 'pipe_pr_pcg', 'pipe_p_m_pcg', 'pipe_pr_m_pcg', 'Jacobi', 'BlockJacobi',
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
            'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
-           'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch',
+           'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch', 'pipe_pr_pcg_batch', 'pipe_pr_m_pcg_batch', 'hs_pcg_batch',
            'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi']

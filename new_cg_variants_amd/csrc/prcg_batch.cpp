@@ -3,7 +3,8 @@
 // entries of include/prcg.h and the planner hook prcg_plan_small_batch of include/prcg_test.h.  Host code only.
 //
 // Layout on the device: the matrices concatenated (every matrix uploaded once, however many systems use it); per session the
-// systems' state concatenated in system order -- pipelined: the pairs (x,p) and (r,s); Hestenes-Stiefel: x, r, p, s --, one
+// systems' state concatenated in system order -- pipelined: the pairs (x,p) and (r,s); Hestenes-Stiefel: x, r, p, s; a session
+// begun with prcg_batch_begin_jacobi adds the pairs (r~,s~) (pipelined) and the systems' inverse diagonals d --, one
 // scalar history [max_iter+1][PRCG_NUM_SCALARS] and one coefficient history [max_iter+1][4] per system, and one descriptor
 // (SmallArgs) per system, sorted by LAUNCH GROUP: the systems whose matrix lives in registers (mode 1) first, then those
 // whose matrix lives in LDS (mode 0); inside a group in system order.  An iteration call is one launch per group on the
@@ -48,12 +49,15 @@ struct Buf {
     double* d() const { return static_cast<double*>(p); }
 };
 
-// launch groups of a batch: mode 1 first, then mode 0; group ids count the groups that exist
-int plan_groups(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out, int32_t* group_out) {
+// launch groups of a batch: mode 1 first, then mode 0; group ids count the groups that exist.  jacobi: the fit rule of the
+// preconditioned bodies (128 B more LDS)
+int plan_groups(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out, int32_t* group_out,
+                bool jacobi = false) {
     bool have[2] = {false, false};
     for (int s = 0; s < n_sys; ++s) {
         int mode = 0;
-        if (nnz[s] < 0 || !small_fits(n[s], nnz[s], max_row_len[s], &mode)) return -s - 1;
+        if (nnz[s] < 0 || !(jacobi ? small_fits_jacobi(n[s], nnz[s], max_row_len[s], &mode) : small_fits(n[s], nnz[s], max_row_len[s], &mode)))
+            return -s - 1;
         mode_out[s] = mode;
         have[mode] = true;
     }
@@ -68,16 +72,17 @@ struct prcg_batch {
     int dev = 0;
     hipStream_t sc = nullptr;
     int n_sys = 0;
-    std::vector<int> n, nnz, mode, slot;           // per system: rows, nonzeros, mode, position of its descriptor
+    std::vector<int> n, nnz, mode, slot, mrl;      // per system: rows, nonzeros, mode, position of its descriptor, longest row
     std::vector<int64_t> voff;                     // per system (+1): first row in the concatenated vectors
     std::vector<const int*> indptr, col;           // per system: its matrix on the device
     std::vector<const double*> val;
     int count[2] = {0, 0};                         // systems of mode 0 / mode 1
     size_t lds[2] = {0, 0};                        // largest small_lds_bytes of each mode's members
+    size_t lds_jac[2] = {0, 0};                    // ... and small_lds_bytes_jacobi
     Buf m_indptr, m_col, m_val;                    // the matrices, concatenated
-    Buf state, rhs, x0, dots, coef, desc, init, tmp;
+    Buf state, rhs, x0, dinv, dots, coef, desc, init, jac, tmp;
     // ---- session ----
-    bool in_session = false, hs = false;
+    bool in_session = false, hs = false, jacobi = false;
     int variant = 0, max_iter = 0, k = 0;
     uint32_t hist_mask = 0;
 
@@ -87,6 +92,7 @@ struct prcg_batch {
     // first descriptor of a mode's launch: mode 1 leads
     const SmallArgs* desc_of(int m) const { return static_cast<const SmallArgs*>(desc.p) + (m == 1 ? 0 : count[1]); }
     const SmallInit* init_of(int m) const { return static_cast<const SmallInit*>(init.p) + (m == 1 ? 0 : count[1]); }
+    const SmallJacobi* jac_of(int m) const { return static_cast<const SmallJacobi*>(jac.p) + (m == 1 ? 0 : count[1]); }
 };
 
 #define BCHECK(h, cond, ...)                                                                  \
@@ -104,6 +110,12 @@ int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const
                           int32_t* group_out) {
     if (n_sys < 1 || !n || !nnz || !max_row_len || !mode_out || !group_out) return 0;
     return plan_groups(n_sys, n, nnz, max_row_len, mode_out, group_out);
+}
+
+int prcg_plan_small_batch_jacobi(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
+                                 int32_t* group_out) {
+    if (n_sys < 1 || !n || !nnz || !max_row_len || !mode_out || !group_out) return 0;
+    return plan_groups(n_sys, n, nnz, max_row_len, mode_out, group_out, true);
 }
 
 int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
@@ -164,11 +176,13 @@ int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64
     }
     BHIP(h, hipStreamSynchronize(b->sc));
     b->n.resize((size_t)n_sys); b->nnz.resize((size_t)n_sys); b->mode.resize((size_t)n_sys); b->slot.resize((size_t)n_sys);
+    b->mrl.resize((size_t)n_sys);
     b->voff.assign((size_t)n_sys + 1, 0);
     b->indptr.resize((size_t)n_sys); b->col.resize((size_t)n_sys); b->val.resize((size_t)n_sys);
     for (int s = 0; s < n_sys; ++s) {
         const int m = mat_of[s], md = mode[(size_t)s];
         b->n[(size_t)s] = (int)sn[(size_t)s]; b->nnz[(size_t)s] = (int)sz[(size_t)s]; b->mode[(size_t)s] = md;
+        b->mrl[(size_t)s] = sl[(size_t)s];
         b->voff[(size_t)s + 1] = b->voff[(size_t)s] + sn[(size_t)s];
         b->indptr[(size_t)s] = static_cast<const int*>(b->m_indptr.p) + rows_off[m] + m;
         b->col[(size_t)s] = static_cast<const int*>(b->m_col.p) + nnz_off[m];
@@ -176,6 +190,8 @@ int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64
         ++b->count[md];
         const size_t need = small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], md);
         if (need > b->lds[md]) b->lds[md] = need;
+        const size_t need_jac = small_lds_bytes_jacobi(b->n[(size_t)s], b->nnz[(size_t)s], md);
+        if (need_jac > b->lds_jac[md]) b->lds_jac[md] = need_jac;
     }
     int at[2] = {b->count[1], 0};                  // descriptors: mode 1 first, then mode 0, each in system order
     for (int s = 0; s < n_sys; ++s) b->slot[(size_t)s] = at[b->mode[(size_t)s]]++;
@@ -191,22 +207,24 @@ void prcg_batch_destroy(prcg_batch_t* b) {
     delete b;
 }
 
-int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask) {
-    if (!b) return PRCG_EINVAL;
+}  // extern "C"
+
+// what prcg_batch_begin and prcg_batch_begin_jacobi (inv_diag non-null) share: every argument has been checked
+static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
+                       uint32_t hist_mask) {
     prcg_t* h = b->h;
-    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
-           "prcg_batch_begin: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", variant);
-    BCHECK(h, rhs && x0, "prcg_batch_begin: null rhs or x0");
-    BCHECK(h, max_iter >= 1, "prcg_batch_begin: max_iter = %d, must be at least 1", max_iter);
-    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
-           "prcg_batch_begin: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", hist_mask);
+    const bool jacobi = inv_diag != nullptr;
     BHIP(h, hipSetDevice(b->dev));
     b->in_session = false;
     const int n_sys = b->n_sys;
     const int64_t N = b->N();
     const size_t D = sizeof(double);
     const bool hs = variant == PRCG_HS;
-    BHIP(h, b->state.ensure((size_t)4 * N * D));
+    BHIP(h, b->state.ensure((size_t)(jacobi && !hs ? 6 : 4) * N * D));
+    if (jacobi) {
+        BHIP(h, b->dinv.ensure((size_t)N * D));
+        BHIP(h, b->jac.ensure((size_t)n_sys * sizeof(SmallJacobi)));
+    }
     BHIP(h, b->rhs.ensure((size_t)N * D));
     BHIP(h, b->x0.ensure((size_t)N * D));
     BHIP(h, b->tmp.ensure((size_t)N * D));
@@ -214,9 +232,10 @@ int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const doub
     BHIP(h, b->coef.ensure((size_t)n_sys * (max_iter + 1) * kCoefStride * D));
     BHIP(h, b->desc.ensure((size_t)n_sys * sizeof(SmallArgs)));
     BHIP(h, b->init.ensure((size_t)n_sys * sizeof(SmallInit)));
-    b->variant = variant; b->hs = hs; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
+    b->variant = variant; b->hs = hs; b->jacobi = jacobi; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
     std::vector<SmallArgs> desc((size_t)n_sys);
     std::vector<SmallInit> init((size_t)n_sys);
+    std::vector<SmallJacobi> jac(jacobi ? (size_t)n_sys : 0);
     double* st = b->state.d();
     for (int s = 0; s < n_sys; ++s) {
         const int64_t v = b->voff[(size_t)s];
@@ -228,6 +247,8 @@ int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const doub
         a.dots = b->dots_of(s); a.coef = b->coef_of(s);
         desc[(size_t)b->slot[(size_t)s]] = a;
         init[(size_t)b->slot[(size_t)s]] = SmallInit{b->rhs.d() + v, b->x0.d() + v};
+        // the pairs (r~,s~) follow (x,p) and (r,s); Hestenes-Stiefel holds no r~
+        if (jacobi) jac[(size_t)b->slot[(size_t)s]] = SmallJacobi{hs ? nullptr : st + 4 * N + 2 * v, b->dinv.d() + v};
     }
     hipStream_t sc = b->sc;
     BHIP(h, hipMemsetAsync(b->dots.p, 0, (size_t)n_sys * (max_iter + 1) * kNS * D, sc));
@@ -236,13 +257,56 @@ int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const doub
     BHIP(h, hipMemcpyAsync(b->x0.p, x0, (size_t)N * D, hipMemcpyHostToDevice, sc));
     BHIP(h, hipMemcpyAsync(b->desc.p, desc.data(), (size_t)n_sys * sizeof(SmallArgs), hipMemcpyHostToDevice, sc));
     BHIP(h, hipMemcpyAsync(b->init.p, init.data(), (size_t)n_sys * sizeof(SmallInit), hipMemcpyHostToDevice, sc));
+    if (jacobi) {
+        BHIP(h, hipMemcpyAsync(b->dinv.p, inv_diag, (size_t)N * D, hipMemcpyHostToDevice, sc));
+        BHIP(h, hipMemcpyAsync(b->jac.p, jac.data(), (size_t)n_sys * sizeof(SmallJacobi), hipMemcpyHostToDevice, sc));
+    }
     BHIP(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
-    for (int m = 1; m >= 0; --m)                   // one initialisation launch per group
-        if (b->count[m] && launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), b->count[m], hs) < 0)
-            return batch_fail(h, PRCG_EHIP, "prcg_batch_begin: kernel launch failed");
+    for (int m = 1; m >= 0; --m) {                 // one initialisation launch per group
+        if (!b->count[m]) continue;
+        const int rc = jacobi ? launch_small_batch_init_jacobi(sc, b->desc_of(m), b->init_of(m), b->jac_of(m), b->count[m], hs)
+                              : launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), b->count[m], hs);
+        if (rc < 0) return batch_fail(h, PRCG_EHIP, "%s: kernel launch failed", jacobi ? "prcg_batch_begin_jacobi" : "prcg_batch_begin");
+    }
     BHIP(h, hipStreamSynchronize(sc));
     b->in_session = true;
     return PRCG_OK;
+}
+
+extern "C" {
+
+int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
+           "prcg_batch_begin: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", variant);
+    BCHECK(h, rhs && x0, "prcg_batch_begin: null rhs or x0");
+    BCHECK(h, max_iter >= 1, "prcg_batch_begin: max_iter = %d, must be at least 1", max_iter);
+    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+           "prcg_batch_begin: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", hist_mask);
+    return batch_begin(b, variant, rhs, x0, nullptr, max_iter, hist_mask);
+}
+
+int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
+                            uint32_t hist_mask) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
+           "prcg_batch_begin_jacobi: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)",
+           variant);
+    BCHECK(h, rhs && x0 && inv_diag, "prcg_batch_begin_jacobi: null rhs, x0 or inv_diag");
+    BCHECK(h, max_iter >= 1, "prcg_batch_begin_jacobi: max_iter = %d, must be at least 1", max_iter);
+    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+           "prcg_batch_begin_jacobi: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)",
+           hist_mask);
+    for (int s = 0; s < b->n_sys; ++s) {
+        int mode = 0;
+        BCHECK(h, small_fits_jacobi(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode),
+               "prcg_batch_begin_jacobi: system %d (n = %d, nnz = %d) fits the one-workgroup solver without a preconditioner but not with one: "
+               "the preconditioned solver needs %zu bytes of LDS, 128 more, and the cap is 159744", s, b->n[(size_t)s], b->nnz[(size_t)s],
+               small_lds_bytes_jacobi(b->n[(size_t)s], b->nnz[(size_t)s], 0));
+    }
+    return batch_begin(b, variant, rhs, x0, inv_diag, max_iter, hist_mask);
 }
 
 int prcg_batch_iterate(prcg_batch_t* b, int iters) {
@@ -253,10 +317,14 @@ int prcg_batch_iterate(prcg_batch_t* b, int iters) {
     BCHECK(h, b->k + iters <= b->max_iter, "prcg_batch_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters, b->max_iter, b->k);
     if (iters == 0) return PRCG_OK;
     BHIP(h, hipSetDevice(b->dev));
-    for (int m = 1; m >= 0; --m)                   // one launch per group: every system advances by iters
-        if (b->count[m] && launch_small_batch(b->sc, b->desc_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters,
-                                              b->variant == PRCG_PIPE_PR_M ? 1 : 0) < 0)
-            return batch_fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
+    const int meurant = b->variant == PRCG_PIPE_PR_M ? 1 : 0;
+    for (int m = 1; m >= 0; --m) {                 // one launch per group: every system advances by iters
+        if (!b->count[m]) continue;
+        const int rc = b->jacobi ? launch_small_batch_jacobi(b->sc, b->desc_of(m), b->jac_of(m), b->count[m], m, b->lds_jac[m], b->hs, b->k,
+                                                             iters, meurant)
+                                 : launch_small_batch(b->sc, b->desc_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters, meurant);
+        if (rc < 0) return batch_fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
+    }
     b->k += iters;
     return PRCG_OK;
 }
@@ -281,10 +349,18 @@ int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out) {
     prcg_t* h = b->h;
     BCHECK(h, b->in_session && out, "prcg_batch_get_vector: no session or null buffer");
     BCHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_vector: system %d outside [0, %d)", s, b->n_sys);
-    BCHECK(h, which == PRCG_VEC_X || which == PRCG_VEC_R || which == PRCG_VEC_P || which == PRCG_VEC_S,
+    const bool tilde = which == PRCG_VEC_RT || which == PRCG_VEC_ST;
+    BCHECK(h, !tilde || (b->jacobi && !b->hs), "prcg_batch_get_vector: vector %d (PRCG_VEC_RT / _ST) is held by a pipelined session begun "
+           "with prcg_batch_begin_jacobi only: this session is %s", which, b->jacobi ? "Hestenes-Stiefel, which forms r~ anew in every iteration"
+                                                                                     : "unpreconditioned");
+    BCHECK(h, tilde || which == PRCG_VEC_X || which == PRCG_VEC_R || which == PRCG_VEC_P || which == PRCG_VEC_S,
            "prcg_batch_get_vector: vector %d is not part of a batch session (PRCG_VEC_X, _R, _P, _S)", which);
     BHIP(h, hipSetDevice(b->dev));
     const int64_t N = b->N(), v = b->voff[(size_t)s], n = b->n[(size_t)s];
+    if (tilde) {                                   // the pair array (r~,s~) follows (x,p) and (r,s)
+        launch_copy(b->sc, b->tmp.d(), 1, b->state.d() + 4 * N + 2 * v + (which == PRCG_VEC_ST ? 1 : 0), 2, n);
+        return batch_d2h(b, out, b->tmp.d(), n);
+    }
     const int idx = which == PRCG_VEC_X ? 0 : which == PRCG_VEC_R ? 1 : which == PRCG_VEC_P ? 2 : 3;
     if (b->hs) return batch_d2h(b, out, b->state.d() + idx * N + v, n);
     // pairs (x,p) and (r,s): component (idx >> 1) of pair array (idx & 1)

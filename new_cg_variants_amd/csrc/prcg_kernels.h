@@ -329,6 +329,20 @@ int launch_small_batch(hipStream_t st, const SmallArgs* desc, int count, int mod
 // vectors carry the bits of the single session's start-up launches; the inner products are summed in the order of the loop
 // (thread-sequential rows, wave butterfly, 16 waves), not of those launches.
 int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, int count, bool hs);
+// ---- the same batch, preconditioned by a diagonal scaling d = inv_diag applied inside the one-workgroup solver ----
+// What a Jacobi system holds beside its SmallArgs: the pairs (r~,s~) (pipelined only; read at entry, written at exit) and d.
+// jac[i] belongs to desc[i].  Pipelined: xp = (x,p), rs = (r,s), ts = (r~,s~); Hestenes-Stiefel: xp = x, rs = r, hs_p, hs_s, and
+// r~ = d r is formed anew in every iteration.  dots[k] = {mu, delta, gamma, nu, rr} (HS: {mu, -, -, nu, rr}), nu = r~.r, rr = r.r.
+struct SmallJacobi { double* ts; const double* d; };
+// the preconditioned bodies sum five inner products: 128 B more LDS than small_lds_bytes
+size_t small_lds_bytes_jacobi(int n, int nnz, int mode);
+// small_fits with the preconditioned need: the same mode, or false where only the extra 128 B no longer fit
+bool small_fits_jacobi(int64_t n, int64_t nnz, int max_row_len, int* mode);
+// lds: the largest small_lds_bytes_jacobi among the launch's systems
+int launch_small_batch_jacobi(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, int count, int mode, size_t lds, bool hs,
+                              int k0, int iters, int meurant);
+// pipelined: x = x0, r = b - A x0, r~ = d r, p = r~, s = A p, s~ = d s; HS: r~ = d r, p = r~, s = A p; row 0 of the scalars in the loop's order
+int launch_small_batch_init_jacobi(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs);
 
 // ---- fused vector updates + inner products -----------------------------------------
 struct PipeUpdateArgs {

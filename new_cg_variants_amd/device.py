@@ -693,11 +693,17 @@ class DeviceBatch:
         except Exception:
             pass
 
-    def begin(self, variant, B, X0, max_iter, hist_mask=0):
+    def begin(self, variant, B, X0, max_iter, hist_mask=0, inv_diag=None):
         """variant: L.PIPE_PR, L.PIPE_PR_M or L.HS.  B, X0: a list of vectors, one per system, or one 2-D array (n_sys, n) when
-        all sizes agree.  hist_mask: 0 or L.HIST_UPDATED_RESIDUAL_2_NORM."""
+        all sizes agree.  hist_mask: 0 or L.HIST_UPDATED_RESIDUAL_2_NORM.  inv_diag: None, or -- in the form of B -- every
+        system's reciprocal diagonal: the session is then preconditioned by that scaling inside the one-workgroup solver
+        (prcg.h: prcg_batch_begin_jacobi), and a pipelined one also serves get_vector('rt' / 'st', s)."""
         b, x0 = batch_vectors('B', B, self.sizes), batch_vectors('X0', X0, self.sizes)
-        self._check(self._lib.prcg_batch_begin(self._b, int(variant), L.ptr(b), L.ptr(x0), int(max_iter), int(hist_mask)))
+        if inv_diag is None:
+            self._check(self._lib.prcg_batch_begin(self._b, int(variant), L.ptr(b), L.ptr(x0), int(max_iter), int(hist_mask)))
+        else:
+            d = batch_vectors('inv_diag', inv_diag, self.sizes)
+            self._check(self._lib.prcg_batch_begin_jacobi(self._b, int(variant), L.ptr(b), L.ptr(x0), L.ptr(d), int(max_iter), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def iterate(self, iters):
