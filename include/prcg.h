@@ -471,6 +471,26 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
  *                      LDS and lies within 128 bytes of the cap -- the fifth inner product needs 128 bytes more (the text names the
  *                      first such system).
  *   prcg_batch_iterate enqueues; every system advances by iters (k + iters <= max_iter).  prcg_batch_sync waits.
+ *   prcg_batch_set_stop  rr_stop: n_sys thresholds on r.r, one per system (for a tolerance tol on the 2-norm of the updated residual:
+ *                      tol * tol), finite and >= 0; NULL clears them.  They are copied at the call -- the caller's buffer is theirs
+ *                      again on return -- and apply to sessions BEGUN afterwards (prcg_batch_begin and prcg_batch_begin_jacobi,
+ *                      signatures unchanged); an open session is not affected.  In such a session every system stops by itself,
+ *                      decided inside its workgroup without the host: after iteration k, and at k = 0 on the initial state, on row k
+ *                      of its scalars, mu = [0], nu = [3], rr = [PRCG_S_RR], in this order:
+ *                        1. rr <= rr_stop[s]                                   -> stop, status 1 (converged);
+ *                        2. else !(0 < mu && mu < inf && 0 < nu && nu < inf)   -> stop, status 2 (breakdown: the next step's
+ *                           alpha = nu / mu would not be that of an SPD system);
+ *                        3. else go on (status 0, stop iteration -1).
+ *                      A system stopped at k keeps the complete state of iteration k: x, r, p, s (and r~, s~) are those of
+ *                      iteration k, scalar rows 0..k and coefficient rows 1..k are written, later rows stay at the zeros that begin
+ *                      set, and later prcg_batch_iterate calls leave the system untouched -- its workgroup returns at once, which
+ *                      makes room for the next one where the batch is larger than the chip.  A threshold of 0 stops on an exactly
+ *                      zero residual (b = A x0) and on breakdown only.  A system that does not stop carries the bits of a session
+ *                      without thresholds.  prcg_batch_iteration keeps counting what was launched, stopped systems or not.
+ *                      Refused: a NaN, infinite or negative threshold (the text names the system; the thresholds set before stay).
+ *   prcg_batch_get_stops  synchronises; k_stop[s], status[s] of the open session, n_sys int32 each: the iteration system s stopped
+ *                      at and why (1 converged, 2 breakdown), or -1 and 0 while it runs -- and for every system of a session begun
+ *                      without thresholds.  Refused without an open session.
  * Launch groups: the systems whose matrix lives in registers (n <= 1024, rows of at most 8) form one launch, those whose matrix
  * lives in LDS another; a call is one launch per group.
  * Bits: from the same state and scalars a system's iterations are those of a single small session on its matrix, bit for bit
@@ -489,7 +509,7 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
  * pipelined session begun with prcg_batch_begin_jacobi also PRCG_VEC_RT, _ST (refused in any other batch session);
  * prcg_batch_get_solutions: every x concatenated in system order, ONE copy; scalars / coefficients / history as
  * prcg_get_scalars / prcg_get_coefficients / prcg_get_history return them (history: max_iter doubles, nothing is written when
- * hist_mask was 0).  No setters, no recorder of state, no preconditioner but the diagonal scaling of prcg_batch_begin_jacobi (no
+ * hist_mask was 0; entries up to min(k, the system's stop iteration), zeros beyond).  No setters, no recorder of state, no preconditioner but the diagonal scaling of prcg_batch_begin_jacobi (no
  * block Jacobi, no callback). */
 typedef struct prcg_batch prcg_batch_t;
 int  prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
@@ -501,6 +521,8 @@ int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, con
 int prcg_batch_iterate(prcg_batch_t* b, int iters);
 int prcg_batch_sync(prcg_batch_t* b);
 int prcg_batch_iteration(const prcg_batch_t* b);
+int prcg_batch_set_stop(prcg_batch_t* b, const double* rr_stop);
+int prcg_batch_get_stops(prcg_batch_t* b, int32_t* k_stop, int32_t* status);
 int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out);
 int prcg_batch_get_solutions(prcg_batch_t* b, double* x_cat);
 int prcg_batch_get_scalars(prcg_batch_t* b, int k, int s, double* out);

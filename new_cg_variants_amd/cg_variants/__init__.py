@@ -37,7 +37,7 @@ import numpy as np
 
 from .. import _lib as L
 from ..callbacks import RECORDER_NAMES
-from ..device import DeviceBatch, DeviceCSR, batch_matrices, batch_vectors, multi_rhs_shape_error
+from ..device import DeviceBatch, DeviceCSR, batch_matrices, batch_thresholds, batch_vectors, multi_rhs_shape_error
 
 _OPERATORS = OrderedDict()   # small cache: figure_gen runs nine variants on one matrix
 _PATTERNS = {}               # cache key -> fingerprint of indptr / indices alone (update_values finds an operator by its pattern)
@@ -787,6 +787,7 @@ def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=F
     batch does not serve raises ValueError -- nothing falls back to a loop of sessions.  jacobi: a *_pcg_batch function,
     kwargs['preconditioner'] resolved to one reciprocal diagonal per system (prcg.h: prcg_batch_begin_jacobi)."""
     preconditioner = kwargs.pop('preconditioner', None)
+    rtol, atol = kwargs.pop('rtol', None), kwargs.pop('atol', None)
     if not jacobi and preconditioner is not None:
         raise ValueError(f'{name} takes no preconditioner: a batch runs the unpreconditioned one-workgroup solver')
     for key in ('x_true', 'w_replace'):
@@ -811,16 +812,34 @@ def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=F
         else:
             raise ValueError(f'{name}: callback {cname or repr(cb)} is not served by a batch (the updated_residual_2_norm recorder or none)')
     inv_diag = _batch_diagonals(name, preconditioner, sizes) if jacobi else None
+    at = np.concatenate([[0], np.cumsum(sizes)])
+    rr_stop = None
+    if rtol is not None or atol is not None:               # thr_s = max(rtol_s ||b_s||_2, atol_s)^2, a bound on r.r
+        try:
+            rt = batch_thresholds('rtol', 0.0 if rtol is None else rtol, n_sys)
+            ab = batch_thresholds('atol', 0.0 if atol is None else atol, n_sys)
+        except ValueError as e:
+            raise ValueError(f'{name}: {e}') from None
+        norms = np.array([np.linalg.norm(B[at[s]:at[s + 1]]) for s in range(n_sys)])
+        rr_stop = np.maximum(rt * norms, ab) ** 2
+        try:
+            rr_stop = batch_thresholds('max(rtol * ||b||, atol) ** 2', rr_stop, n_sys)
+        except ValueError as e:
+            raise ValueError(f'{name}: {e}') from None
     batch = DeviceBatch(matrices, mat_of, device=int(kwargs.get('device', 0)))
     try:
-        at = np.concatenate([[0], np.cumsum(sizes)])
         batch.begin(variant, [B[at[s]:at[s + 1]] for s in range(n_sys)], [X0[at[s]:at[s + 1]] for s in range(n_sys)], max_iter, hist_mask=mask,
-                    inv_diag=inv_diag)
+                    inv_diag=inv_diag, rr_stop=rr_stop)
         batch.iterate(max_iter - 1)
         batch.sync()
         outputs = [{'name': name, 'max_iter': max_iter, 'system': s} for s in range(n_sys)]
         for s in range(n_sys):
             outputs[s].update(batch.history(s))
+        if rr_stop is not None:
+            k_stop, status = batch.stops()
+            for s in range(n_sys):
+                outputs[s]['iterations'] = int(k_stop[s]) if status[s] else max_iter - 1
+                outputs[s]['status'] = ('max_iter', 'converged', 'breakdown')[int(status[s])]
     finally:
         batch.close()
     return outputs
@@ -835,7 +854,10 @@ def _make_batch(variant, name, where):
                  'matrix (every system uses it) or a sequence as long as bs (entries that are the same object share one upload); bs, x0s are '
                  f'lists of vectors or, when all sizes agree, 2-D arrays.  Returns a list of trial dicts, one per system, shaped like {single}\'s.  '
                  'callbacks: updated_residual_2_norm or none.  Every system must fit the one-workgroup solver (n <= 4096, matrix in registers '
-                 'or LDS): anything else is refused.')
+                 'or LDS): anything else is refused.  rtol= and/or atol= (a scalar, or one value per system): every system stops by itself '
+                 'once its updated residual satisfies r.r <= max(rtol ||b||_2, atol)^2, or at a breakdown (prcg.h: prcg_batch_set_stop); each '
+                 'trial dict then carries \'iterations\' (the stop iteration, max_iter - 1 for a system that ran out) and \'status\' '
+                 '(\'converged\', \'breakdown\', \'max_iter\'), and the history is zero beyond the stop.')
     f.__name__ = f.__qualname__ = name
     return f
 
@@ -855,7 +877,8 @@ def _make_pcg_batch(variant, name, where):
                  f'preconditioner applied inside it.  As, bs, x0s, callbacks and the result as {single[:-3]}cg_batch.  preconditioner: one object '
                  '(every system uses it: the sizes must agree) or a sequence with one per system; each must be a DIAGONAL scaling -- an object '
                  'carrying inv_diag (Jacobi), block Jacobi with bs == 1, or a callable that the exact probe shows to be v -> d * v --, anything '
-                 'else is a ValueError; None is the identity, as the reference\'s function without a preconditioner.')
+                 'else is a ValueError; None is the identity, as the reference\'s function without a preconditioner.  rtol= / atol= as '
+                 f'{single[:-3]}cg_batch.')
     f.__name__ = f.__qualname__ = name
     return f
 

@@ -10,6 +10,11 @@
 // whose matrix lives in LDS (mode 0); inside a group in system order.  An iteration call is one launch per group on the
 // handle's compute stream, begin one initialisation launch per group.  Nothing a system computes depends on its group's other
 // members: the launch's dynamic LDS is the group's largest need, each workgroup carves it by its own n and nnz.
+//
+// Thresholds set with prcg_batch_set_stop are kept on the host; a session begun while they are set adds one SmallStop per system
+// (sorted like the descriptors) and one stop word {iteration, status} per system (in SYSTEM order), and its iteration calls launch
+// the kernels that apply the stopping rule (prcg_kernels.h: SmallStop) inside each workgroup.  A session begun without them
+// launches what it always launched.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -80,9 +85,10 @@ struct prcg_batch {
     size_t lds[2] = {0, 0};                        // largest small_lds_bytes of each mode's members
     size_t lds_jac[2] = {0, 0};                    // ... and small_lds_bytes_jacobi
     Buf m_indptr, m_col, m_val;                    // the matrices, concatenated
-    Buf state, rhs, x0, dinv, dots, coef, desc, init, jac, tmp;
+    Buf state, rhs, x0, dinv, dots, coef, desc, init, jac, tmp, stop, words;
+    std::vector<double> rr_stop;                   // per system: the threshold on r.r of sessions begun from now on (empty: none)
     // ---- session ----
-    bool in_session = false, hs = false, jacobi = false;
+    bool in_session = false, hs = false, jacobi = false, stopping = false;
     int variant = 0, max_iter = 0, k = 0;
     uint32_t hist_mask = 0;
 
@@ -93,6 +99,7 @@ struct prcg_batch {
     const SmallArgs* desc_of(int m) const { return static_cast<const SmallArgs*>(desc.p) + (m == 1 ? 0 : count[1]); }
     const SmallInit* init_of(int m) const { return static_cast<const SmallInit*>(init.p) + (m == 1 ? 0 : count[1]); }
     const SmallJacobi* jac_of(int m) const { return static_cast<const SmallJacobi*>(jac.p) + (m == 1 ? 0 : count[1]); }
+    const SmallStop* stop_of(int m) const { return static_cast<const SmallStop*>(stop.p) + (m == 1 ? 0 : count[1]); }
 };
 
 #define BCHECK(h, cond, ...)                                                                  \
@@ -232,10 +239,18 @@ static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const do
     BHIP(h, b->coef.ensure((size_t)n_sys * (max_iter + 1) * kCoefStride * D));
     BHIP(h, b->desc.ensure((size_t)n_sys * sizeof(SmallArgs)));
     BHIP(h, b->init.ensure((size_t)n_sys * sizeof(SmallInit)));
+    const bool stopping = !b->rr_stop.empty();
+    if (stopping) {
+        BHIP(h, b->stop.ensure((size_t)n_sys * sizeof(SmallStop)));
+        BHIP(h, b->words.ensure((size_t)n_sys * 2 * sizeof(int32_t)));
+    }
+    b->stopping = stopping;
     b->variant = variant; b->hs = hs; b->jacobi = jacobi; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
     std::vector<SmallArgs> desc((size_t)n_sys);
     std::vector<SmallInit> init((size_t)n_sys);
     std::vector<SmallJacobi> jac(jacobi ? (size_t)n_sys : 0);
+    std::vector<SmallStop> stop(stopping ? (size_t)n_sys : 0);
+    std::vector<int32_t> words(stopping ? (size_t)n_sys * 2 : 0);
     double* st = b->state.d();
     for (int s = 0; s < n_sys; ++s) {
         const int64_t v = b->voff[(size_t)s];
@@ -249,6 +264,10 @@ static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const do
         init[(size_t)b->slot[(size_t)s]] = SmallInit{b->rhs.d() + v, b->x0.d() + v};
         // the pairs (r~,s~) follow (x,p) and (r,s); Hestenes-Stiefel holds no r~
         if (jacobi) jac[(size_t)b->slot[(size_t)s]] = SmallJacobi{hs ? nullptr : st + 4 * N + 2 * v, b->dinv.d() + v};
+        if (stopping) {                                // every system starts as {-1, 0}: running
+            stop[(size_t)b->slot[(size_t)s]] = SmallStop{b->rr_stop[(size_t)s], static_cast<int*>(b->words.p) + 2 * s};
+            words[(size_t)2 * s] = -1; words[(size_t)2 * s + 1] = 0;
+        }
     }
     hipStream_t sc = b->sc;
     BHIP(h, hipMemsetAsync(b->dots.p, 0, (size_t)n_sys * (max_iter + 1) * kNS * D, sc));
@@ -260,6 +279,10 @@ static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const do
     if (jacobi) {
         BHIP(h, hipMemcpyAsync(b->dinv.p, inv_diag, (size_t)N * D, hipMemcpyHostToDevice, sc));
         BHIP(h, hipMemcpyAsync(b->jac.p, jac.data(), (size_t)n_sys * sizeof(SmallJacobi), hipMemcpyHostToDevice, sc));
+    }
+    if (stopping) {
+        BHIP(h, hipMemcpyAsync(b->stop.p, stop.data(), (size_t)n_sys * sizeof(SmallStop), hipMemcpyHostToDevice, sc));
+        BHIP(h, hipMemcpyAsync(b->words.p, words.data(), (size_t)n_sys * 2 * sizeof(int32_t), hipMemcpyHostToDevice, sc));
     }
     BHIP(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
     for (int m = 1; m >= 0; --m) {                 // one initialisation launch per group
@@ -320,9 +343,15 @@ int prcg_batch_iterate(prcg_batch_t* b, int iters) {
     const int meurant = b->variant == PRCG_PIPE_PR_M ? 1 : 0;
     for (int m = 1; m >= 0; --m) {                 // one launch per group: every system advances by iters
         if (!b->count[m]) continue;
-        const int rc = b->jacobi ? launch_small_batch_jacobi(b->sc, b->desc_of(m), b->jac_of(m), b->count[m], m, b->lds_jac[m], b->hs, b->k,
-                                                             iters, meurant)
-                                 : launch_small_batch(b->sc, b->desc_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters, meurant);
+        int rc;
+        if (b->stopping)
+            rc = b->jacobi ? launch_small_batch_jacobi_stop(b->sc, b->desc_of(m), b->jac_of(m), b->stop_of(m), b->count[m], m, b->lds_jac[m],
+                                                            b->hs, b->k, iters, meurant)
+                           : launch_small_batch_stop(b->sc, b->desc_of(m), b->stop_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters, meurant);
+        else
+            rc = b->jacobi ? launch_small_batch_jacobi(b->sc, b->desc_of(m), b->jac_of(m), b->count[m], m, b->lds_jac[m], b->hs, b->k, iters,
+                                                       meurant)
+                           : launch_small_batch(b->sc, b->desc_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters, meurant);
         if (rc < 0) return batch_fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
     }
     b->k += iters;
@@ -337,6 +366,35 @@ int prcg_batch_sync(prcg_batch_t* b) {
 }
 
 int prcg_batch_iteration(const prcg_batch_t* b) { return b ? b->k : -1; }
+
+int prcg_batch_set_stop(prcg_batch_t* b, const double* rr_stop) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    if (!rr_stop) { b->rr_stop.clear(); return PRCG_OK; }
+    for (int s = 0; s < b->n_sys; ++s)
+        BCHECK(h, std::isfinite(rr_stop[s]) && rr_stop[s] >= 0.0, "prcg_batch_set_stop: rr_stop[%d] = %g: the threshold of system %d must be "
+               "finite and >= 0 (a bound on r.r; 0 stops on an exactly zero residual only)", s, rr_stop[s], s);
+    b->rr_stop.assign(rr_stop, rr_stop + b->n_sys);
+    return PRCG_OK;
+}
+
+int prcg_batch_get_stops(prcg_batch_t* b, int32_t* k_stop, int32_t* status) {
+    if (!b) return PRCG_EINVAL;
+    prcg_t* h = b->h;
+    BCHECK(h, b->in_session, "prcg_batch_get_stops: no open session");
+    BCHECK(h, k_stop && status, "prcg_batch_get_stops: null buffer");
+    BHIP(h, hipSetDevice(b->dev));
+    BHIP(h, hipStreamSynchronize(b->sc));
+    if (!b->stopping) {
+        for (int s = 0; s < b->n_sys; ++s) { k_stop[s] = -1; status[s] = 0; }
+        return PRCG_OK;
+    }
+    std::vector<int32_t> words((size_t)b->n_sys * 2);
+    BHIP(h, hipMemcpyAsync(words.data(), b->words.p, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b->sc));
+    BHIP(h, hipStreamSynchronize(b->sc));
+    for (int s = 0; s < b->n_sys; ++s) { k_stop[s] = words[(size_t)2 * s]; status[s] = words[(size_t)2 * s + 1]; }
+    return PRCG_OK;
+}
 
 static int batch_d2h(prcg_batch_t* b, double* dst, const double* src, int64_t count) {
     BHIP(b->h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->sc));
@@ -405,7 +463,14 @@ int prcg_batch_get_history(prcg_batch_t* b, int s, double* hist) {
     const int m = b->max_iter;
     std::vector<double> all((size_t)(m + 1) * kNS);
     if (int rc = batch_d2h(b, all.data(), b->dots_of(s), (int64_t)(m + 1) * kNS)) return rc;
-    for (int k = 0; k < m; ++k) hist[k] = k <= b->k ? std::sqrt(all[(size_t)k * kNS + PRCG_S_RR]) : 0.0;
+    int last = b->k;                               // a stopped system has entries up to its stop iteration
+    if (b->stopping) {
+        int32_t word[2];
+        BHIP(h, hipMemcpyAsync(word, static_cast<const int32_t*>(b->words.p) + 2 * s, sizeof(word), hipMemcpyDeviceToHost, b->sc));
+        BHIP(h, hipStreamSynchronize(b->sc));
+        if (word[0] >= 0 && word[0] < last) last = word[0];
+    }
+    for (int k = 0; k < m; ++k) hist[k] = k <= last ? std::sqrt(all[(size_t)k * kNS + PRCG_S_RR]) : 0.0;
     return PRCG_OK;
 }
 

@@ -343,6 +343,19 @@ int launch_small_batch_jacobi(hipStream_t st, const SmallArgs* desc, const Small
                               int k0, int iters, int meurant);
 // pipelined: x = x0, r = b - A x0, r~ = d r, p = r~, s = A p, s~ = d s; HS: r~ = d r, p = r~, s = A p; row 0 of the scalars in the loop's order
 int launch_small_batch_init_jacobi(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs);
+// ---- the same batches, every system stopped at its OWN residual threshold, decided inside its workgroup ----
+// stop[i] belongs to desc[i].  thr: a bound on r.r, finite and >= 0.  word: two ints in device memory, word[0] the iteration the
+// system stopped at (-1 while it runs), word[1] its status (0 running, 1 converged, 2 breakdown).  The rule, applied to row k of
+// the scalars (mu = dots[k][0], nu = dots[k][3], rr = dots[k][4]) after iteration k, and to row 0 by the launch with k0 == 0:
+//   rr <= thr -> converged;  else !(0 < mu < inf && 0 < nu < inf) -> breakdown (alpha = nu / mu is not an SPD system's);  else go on.
+// A system stopped at k holds the complete state of iteration k: its vectors, scalar rows 0..k, coefficient rows 1..k; later
+// rows are not written, and a later launch returns at once for it and stores nothing.  A system that never stops carries the
+// bits of launch_small_batch / launch_small_batch_jacobi.
+struct SmallStop { double thr; int* word; };
+int launch_small_batch_stop(hipStream_t st, const SmallArgs* desc, const SmallStop* stop, int count, int mode, size_t lds, bool hs, int k0,
+                            int iters, int meurant);
+int launch_small_batch_jacobi_stop(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, const SmallStop* stop, int count, int mode,
+                                   size_t lds, bool hs, int k0, int iters, int meurant);
 
 // ---- fused vector updates + inner products -----------------------------------------
 struct PipeUpdateArgs {

@@ -687,10 +687,41 @@ constexpr int kSmallMaxN = kSmallThreads * kSmallRows;
 //         nonzeros -- the paper's small test matrices (nos7: rows of 4-7, bcsstk03: 4-6).
 constexpr int kSmallRegLen = 8;
 
+// ---- stopping a system of a batch at its OWN residual threshold: the STOP form of the four bodies (rule: prcg_kernels.h) ----
+// Every thread of the workgroup must take the same exit, or some waves would wait at a barrier the others never reach.  The
+// operands of the rule are the same bits in all 1024 threads: thr comes from a load of one address that the launch never
+// writes; mu, nu, rr are either loaded from one address (row k0 of the scalars, which the launch only reads) or results of
+// wave_sum16, in which EVERY wave sums the same 16 LDS partials by the same butterfly and broadcasts lane 0's bits.  (The stop
+// word: small_stop_entry.)  readfirstlane makes the verdict a scalar, so the branch on it is a scalar branch.
+__device__ __forceinline__ int small_stop_rule(double mu, double nu, double rr, double thr) {
+    const double inf = __builtin_huge_val();
+    int v = 0;
+    if (rr <= thr) v = 1;                                                        // converged
+    else if (!(0.0 < mu && mu < inf && 0.0 < nu && nu < inf)) v = 2;             // breakdown: a = nu / mu is not an SPD system's
+    return __builtin_amdgcn_readfirstlane(v);
+}
+// On entry, before the first barrier: true if this workgroup has nothing to do -- its system stopped in an earlier launch
+// (nothing is stored), or the session is at its start and the rule fires on row 0 (thread 0 records {0, status}; the state of
+// iteration 0 is already in memory).  b = 0 ends here: rr = 0 <= thr whatever mu is.  No barrier separates thread 0's store from
+// a later wave's load of the word: a wave that already sees {0, status} returns by the first test where it would have returned by
+// the rule -- the same exit either way.  Every other store to the word follows the body's barriers.
+__device__ __forceinline__ bool small_stop_entry(const SmallArgs& a, const SmallStop& st) {
+    if (__builtin_amdgcn_readfirstlane(st.word[0]) >= 0) return true;
+    if (a.k0 != 0) return false;
+    const int v = small_stop_rule(a.dots[0], a.dots[3], a.dots[4], st.thr);
+    if (v && threadIdx.x == 0) { st.word[0] = 0; st.word[1] = v; }
+    return v != 0;
+}
+// after the body's final stores: thread 0 records where and why the system stopped
+__device__ __forceinline__ void small_stop_record(const SmallStop& st, int k, int status) {
+    if (status && threadIdx.x == 0) { st.word[0] = k; st.word[1] = status; }
+}
+
 // The body is a device function of its argument: k_small_pipe_pr hands it the launch's SmallArgs, k_small_pipe_pr_batch the
 // descriptor of workgroup blockIdx.x -- one body, so that a system of a batch carries the single solver's bits.
-template <int MODE>
-__device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a) {
+template <int MODE, bool STOP = false>
+__device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const SmallStop& stop = SmallStop{}) {
+    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
     const int n = a.n, nnz = a.nnz;
@@ -741,6 +772,8 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a) {
 
     double2* cur = rsA;
     double2* nxt = rsB;
+    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
+    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
     for (int it = 1; it <= a.iters; ++it) {
         // coefficients (pipe_pr_cg.py:64-66,75), identical in every thread
         const double al = nu / mu;
@@ -796,6 +829,10 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a) {
         }
         lds_barrier();                                           // everybody has read red before it is rewritten
         double2* tmp = cur; cur = nxt; nxt = tmp;
+        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
+            stop_status = small_stop_rule(mu, nu, nu, stop_thr);
+            if (stop_status) { stop_k = a.k0 + it; break; }
+        }
     }
 
     double2* XPo = reinterpret_cast<double2*>(a.xp);
@@ -805,6 +842,7 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a) {
         const int row = tid + j * kSmallThreads;
         if (row < n) { XPo[row] = make_double2(xr[j], pr[j]); RSo[row] = cur[row]; }
     }
+    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
 }
 template <int MODE>
 __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { small_pipe_pr_body<MODE>(a); }
@@ -816,8 +854,9 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { 
 // k_hs_update_p / the row sums of csr_matvec:  a = nu / mu;  x += a p;  r -= a s;  nu' = r.r;  b = nu' / nu;  p = r + b p;
 // s = A p;  mu = p.s  -- two workgroup-wide sums (the two reductions that make Hestenes-Stiefel what it is), three barriers.
 // Scalars as the launches leave them: dots[k] = {mu_k, -, -, nu_k, rr_k}, coef[k] = {a_k, b_k}.
-template <int MODE>
-__device__ __forceinline__ void small_hs_body(const SmallArgs& a) {
+template <int MODE, bool STOP = false>
+__device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallStop& stop = SmallStop{}) {
+    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
     const int n = a.n, nnz = a.nnz;
@@ -858,6 +897,8 @@ __device__ __forceinline__ void small_hs_body(const SmallArgs& a) {
 
     double* cur = pA;                                            // holds p_{k-1}
     double* nxt = pB;
+    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
+    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
     for (int it = 1; it <= a.iters; ++it) {
         const double al = nu / mu;                               // a = nu / mu                       hs_cg.py:55
         double acc = 0.0;
@@ -913,12 +954,17 @@ __device__ __forceinline__ void small_hs_body(const SmallArgs& a) {
         nu = nun;
         lds_barrier();                                           // everybody has read red before it is rewritten
         double* tmp = cur; cur = nxt; nxt = tmp;
+        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
+            stop_status = small_stop_rule(mu, nu, nu, stop_thr);
+            if (stop_status) { stop_k = a.k0 + it; break; }
+        }
     }
 #pragma unroll
     for (int j = 0; j < ROWS; ++j) {
         const int row = tid + j * kSmallThreads;
         if (row < n) { a.xp[row] = xr[j]; a.rs[row] = rr_[j]; a.hs_p[row] = pr[j]; a.hs_s[row] = sr[j]; }
     }
+    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
 }
 template <int MODE>
 __global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small_hs_body<MODE>(a); }
@@ -930,8 +976,9 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small
 // Five sums per iteration: mu = p.s, delta = r.s~, gamma = s~.s, nu = r~.r, rr = r.r, in the order of the unpreconditioned
 // body (thread-sequential rows, wave butterfly, 16 waves): red is [16 waves][5].  Still two barriers per iteration.
 // dots[k] = {mu, delta, gamma, nu, rr}, coef[k] = {al, bt, nu_pred}.
-template <int MODE>
-__device__ __forceinline__ void small_pipe_pr_pcg_body(const SmallArgs& a, const SmallJacobi& jc) {
+template <int MODE, bool STOP = false>
+__device__ __forceinline__ void small_pipe_pr_pcg_body(const SmallArgs& a, const SmallJacobi& jc, const SmallStop& stop = SmallStop{}) {
+    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
     const int n = a.n, nnz = a.nnz;
@@ -979,6 +1026,8 @@ __device__ __forceinline__ void small_pipe_pr_pcg_body(const SmallArgs& a, const
 
     double2* cur = tsA;
     double2* nxt = tsB;
+    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
+    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
     for (int it = 1; it <= a.iters; ++it) {
         // coefficients (pipe_pr_cg.py:174-175,187), identical in every thread
         const double al = nu / mu;
@@ -1041,6 +1090,10 @@ __device__ __forceinline__ void small_pipe_pr_pcg_body(const SmallArgs& a, const
         }
         lds_barrier();                                           // everybody has read red before it is rewritten
         double2* tmp = cur; cur = nxt; nxt = tmp;
+        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
+            stop_status = small_stop_rule(mu, nu, rr, stop_thr);
+            if (stop_status) { stop_k = a.k0 + it; break; }
+        }
     }
 
     double2* XPo = reinterpret_cast<double2*>(a.xp);
@@ -1051,13 +1104,15 @@ __device__ __forceinline__ void small_pipe_pr_pcg_body(const SmallArgs& a, const
         const int row = tid + j * kSmallThreads;
         if (row < n) { XPo[row] = make_double2(xr[j], pr[j]); RSo[row] = make_double2(rr_[j], sr[j]); TSo[row] = cur[row]; }
     }
+    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
 }
 
 // Hestenes-Stiefel with the same scaling (hs_cg.py:70-131): small_hs_body with r~ = d r formed in registers after r -= a s.
 // The first reduction point carries two sums, nu' = r.r~ and rr = r.r (red is [16 waves][2]); b = nu' / nu; p = r~ + b p;
 // s = A p; mu = p.s.  The barriers of small_hs_body.  dots[k] = {mu, -, -, nu, rr}, coef[k] = {a, b}.
-template <int MODE>
-__device__ __forceinline__ void small_hs_pcg_body(const SmallArgs& a, const SmallJacobi& jc) {
+template <int MODE, bool STOP = false>
+__device__ __forceinline__ void small_hs_pcg_body(const SmallArgs& a, const SmallJacobi& jc, const SmallStop& stop = SmallStop{}) {
+    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
     const int n = a.n, nnz = a.nnz;
@@ -1098,6 +1153,8 @@ __device__ __forceinline__ void small_hs_pcg_body(const SmallArgs& a, const Smal
 
     double* cur = pA;                                            // holds p_{k-1}
     double* nxt = pB;
+    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
+    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
     for (int it = 1; it <= a.iters; ++it) {
         const double al = nu / mu;                               // a = nu / mu                       hs_cg.py:116
         double rt[ROWS];
@@ -1158,12 +1215,17 @@ __device__ __forceinline__ void small_hs_pcg_body(const SmallArgs& a, const Smal
         nu = nun;
         lds_barrier();                                           // everybody has read red before it is rewritten
         double* tmp = cur; cur = nxt; nxt = tmp;
+        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
+            stop_status = small_stop_rule(mu, nu, rrn, stop_thr);
+            if (stop_status) { stop_k = a.k0 + it; break; }
+        }
     }
 #pragma unroll
     for (int j = 0; j < ROWS; ++j) {
         const int row = tid + j * kSmallThreads;
         if (row < n) { a.xp[row] = xr[j]; a.rs[row] = rr_[j]; a.hs_p[row] = pr[j]; a.hs_s[row] = sr[j]; }
     }
+    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
 }
 
 // ---- a BATCH of small systems: one launch, workgroup blockIdx.x solves system desc[blockIdx.x] (prcg_batch.cpp) ----
@@ -1257,6 +1319,36 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_hs_pcg_batch(const Smal
     SmallArgs a = desc[blockIdx.x];
     a.k0 = k0; a.iters = iters; a.meurant = 0;
     small_hs_pcg_body<MODE>(a, jac[blockIdx.x]);
+}
+
+// ---- the batches with a stop: stop[blockIdx.x] belongs to desc[blockIdx.x]; the STOP form of the same four bodies ----
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_batch_stop(const SmallArgs* __restrict__ desc, const SmallStop* __restrict__ stop,
+                                                                            int k0, int iters, int meurant) {
+    SmallArgs a = desc[blockIdx.x];
+    a.k0 = k0; a.iters = iters; a.meurant = meurant;
+    small_pipe_pr_body<MODE, true>(a, stop[blockIdx.x]);
+}
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs_batch_stop(const SmallArgs* __restrict__ desc, const SmallStop* __restrict__ stop,
+                                                                       int k0, int iters) {
+    SmallArgs a = desc[blockIdx.x];
+    a.k0 = k0; a.iters = iters; a.meurant = 0;
+    small_hs_body<MODE, true>(a, stop[blockIdx.x]);
+}
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_pcg_batch_stop(const SmallArgs* __restrict__ desc, const SmallJacobi* __restrict__ jac,
+                                                                                const SmallStop* __restrict__ stop, int k0, int iters, int meurant) {
+    SmallArgs a = desc[blockIdx.x];
+    a.k0 = k0; a.iters = iters; a.meurant = meurant;
+    small_pipe_pr_pcg_body<MODE, true>(a, jac[blockIdx.x], stop[blockIdx.x]);
+}
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs_pcg_batch_stop(const SmallArgs* __restrict__ desc, const SmallJacobi* __restrict__ jac,
+                                                                           const SmallStop* __restrict__ stop, int k0, int iters) {
+    SmallArgs a = desc[blockIdx.x];
+    a.k0 = k0; a.iters = iters; a.meurant = 0;
+    small_hs_pcg_body<MODE, true>(a, jac[blockIdx.x], stop[blockIdx.x]);
 }
 
 // k_small_batch_init with the scaling (pipe_pr_cg.py:122-140, hs_cg.py:84-90):  x = x0;  r = b - A x0;  r~ = d r;  p = r~;  s = A p;
@@ -1774,6 +1866,55 @@ int launch_small_batch_jacobi(hipStream_t st, const SmallArgs* desc, const Small
     } else {
         if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, k0, iters, meurant);
         else hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, k0, iters, meurant);
+    }
+    return PRCG_LAUNCH_OK() ? count : -1;
+}
+
+// ---- the two batch launchers with a per-system stop (SmallStop, prcg_kernels.h): the dynamic-LDS attribute as above ----
+int launch_small_batch_stop(hipStream_t st, const SmallArgs* desc, const SmallStop* stop, int count, int mode, size_t lds, bool hs, int k0,
+                            int iters, int meurant) {
+    constexpr int kMaxDev = 64;
+    static bool attr_done[kMaxDev] = {};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
+    if (dev >= kMaxDev || !attr_done[dev]) {
+        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_batch_stop<0>), reinterpret_cast<const void*>(k_small_pipe_pr_batch_stop<1>),
+                              reinterpret_cast<const void*>(k_small_hs_batch_stop<0>), reinterpret_cast<const void*>(k_small_hs_batch_stop<1>)};
+        for (const void* f : fns)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
+        if (dev < kMaxDev) attr_done[dev] = true;
+    }
+    if (hs) {
+        if (mode == 1) hipLaunchKernelGGL(k_small_hs_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters);
+        else hipLaunchKernelGGL(k_small_hs_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters);
+    } else {
+        if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters, meurant);
+        else hipLaunchKernelGGL(k_small_pipe_pr_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters, meurant);
+    }
+    return PRCG_LAUNCH_OK() ? count : -1;
+}
+int launch_small_batch_jacobi_stop(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, const SmallStop* stop, int count, int mode,
+                                   size_t lds, bool hs, int k0, int iters, int meurant) {
+    constexpr int kMaxDev = 64;
+    static bool attr_done[kMaxDev] = {};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
+    if (dev >= kMaxDev || !attr_done[dev]) {
+        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_pcg_batch_stop<0>),
+                              reinterpret_cast<const void*>(k_small_pipe_pr_pcg_batch_stop<1>),
+                              reinterpret_cast<const void*>(k_small_hs_pcg_batch_stop<0>), reinterpret_cast<const void*>(k_small_hs_pcg_batch_stop<1>)};
+        for (const void* f : fns)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
+        if (dev < kMaxDev) attr_done[dev] = true;
+    }
+    if (hs) {
+        if (mode == 1) hipLaunchKernelGGL(k_small_hs_pcg_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters);
+        else hipLaunchKernelGGL(k_small_hs_pcg_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters);
+    } else {
+        if (mode == 1)
+            hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters, meurant);
+        else
+            hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters, meurant);
     }
     return PRCG_LAUNCH_OK() ? count : -1;
 }

@@ -624,6 +624,20 @@ def batch_vectors(name, V, sizes):
     return out
 
 
+def batch_thresholds(name, v, n_sys):
+    """One finite value >= 0 per system (1-D float64) from a scalar -- every system's -- or a sequence of n_sys; ValueError names
+    the count or the first system whose value is NaN, infinite or negative.  Pure host work."""
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(n_sys, float(a))
+    if a.shape != (n_sys,):
+        raise ValueError(f'{name} must be one value or {n_sys} values, one per system -- got shape {tuple(a.shape)}')
+    bad = np.flatnonzero(~(np.isfinite(a) & (a >= 0)))
+    if bad.size:
+        raise ValueError(f'{name}[{bad[0]}] = {a[bad[0]]}: the value of system {bad[0]} must be finite and >= 0')
+    return np.ascontiguousarray(a)
+
+
 class DeviceBatch:
     """A batch of small independent systems A_s x_s = b_s solved in ONE launch, one workgroup per system (prcg.h:
     prcg_batch_create): what a Python loop over ``DeviceCSR(A).begin(...); iterate(...)`` computes for matrices that fit the
@@ -693,16 +707,20 @@ class DeviceBatch:
         except Exception:
             pass
 
-    def begin(self, variant, B, X0, max_iter, hist_mask=0, inv_diag=None):
+    def begin(self, variant, B, X0, max_iter, hist_mask=0, inv_diag=None, rr_stop=None):
         """variant: L.PIPE_PR, L.PIPE_PR_M or L.HS.  B, X0: a list of vectors, one per system, or one 2-D array (n_sys, n) when
         all sizes agree.  hist_mask: 0 or L.HIST_UPDATED_RESIDUAL_2_NORM.  inv_diag: None, or -- in the form of B -- every
         system's reciprocal diagonal: the session is then preconditioned by that scaling inside the one-workgroup solver
-        (prcg.h: prcg_batch_begin_jacobi), and a pipelined one also serves get_vector('rt' / 'st', s)."""
+        (prcg.h: prcg_batch_begin_jacobi), and a pipelined one also serves get_vector('rt' / 'st', s).  rr_stop: None, or a
+        threshold on r.r -- one per system, or a scalar for all --: every system of THIS session then stops by itself, converged
+        or broken down, by the rule of prcg.h: prcg_batch_set_stop; stops() tells where and why."""
         b, x0 = batch_vectors('B', B, self.sizes), batch_vectors('X0', X0, self.sizes)
+        d = None if inv_diag is None else batch_vectors('inv_diag', inv_diag, self.sizes)
+        thr = None if rr_stop is None else batch_thresholds('rr_stop', rr_stop, self.n_sys)
+        self._check(self._lib.prcg_batch_set_stop(self._b, L.ptr(thr)))      # (None clears what an earlier session set)
         if inv_diag is None:
             self._check(self._lib.prcg_batch_begin(self._b, int(variant), L.ptr(b), L.ptr(x0), int(max_iter), int(hist_mask)))
         else:
-            d = batch_vectors('inv_diag', inv_diag, self.sizes)
             self._check(self._lib.prcg_batch_begin_jacobi(self._b, int(variant), L.ptr(b), L.ptr(x0), L.ptr(d), int(max_iter), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
@@ -715,6 +733,13 @@ class DeviceBatch:
     @property
     def k(self):
         return self._lib.prcg_batch_iteration(self._b)
+
+    def stops(self):
+        """(k_stop, status), int32 arrays of n_sys: the iteration every system stopped at and why (1 converged, 2 breakdown); -1
+        and 0 for a system that still runs, and for every system of a session begun without rr_stop.  Synchronises."""
+        k_stop, status = np.empty(self.n_sys, dtype=np.int32), np.empty(self.n_sys, dtype=np.int32)
+        self._check(self._lib.prcg_batch_get_stops(self._b, L.ptr(k_stop), L.ptr(status)))
+        return k_stop, status
 
     def get_vector(self, name, s):
         out = np.empty(self.sizes[s])
