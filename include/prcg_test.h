@@ -164,12 +164,24 @@ int prcg_plan_gather(int rank, int doubles_per_table, const double* tables, int 
  * out[4], out[5]: workgroups and waves per workgroup of the open session's LAST launch that left inner-product partials,
  * as that launch ran: the one-launch pipelined, predict-and-recompute, Chronopoulos-Gear and Ghysels-Vanroose iterations,
  * the product launches of their two-launch forms and of Hestenes-Stiefel, and a product with a dot epilogue (the start-up
- * inner products of prcg_solve_begin; not a recorder's).  On a window operator out[5] is the workgroup size the launcher
- * instantiated, whatever the epilogue; other operators report 4.  out[4] = 0: no such launch yet in this session (out[5]
+ * inner products of prcg_solve_begin; not a recorder's) -- on every operator family: sliced rows and CSR-adaptive tiles run
+ * the one-launch pipelined iteration and the products with a dot epilogue.  On a window operator out[5] is the workgroup size
+ * the launcher instantiated, whatever the epilogue; other operators report 4.  out[4] = 0: no such launch yet in this session (out[5]
  * is then what a one-launch pipelined iteration would take).  Both are cleared when a session opens.
  * Returns the number of int64 written, -needed if capacity is too small, -1 on a bad argument.  tests/device_order.py
  * rebuilds the launch's reduction tree from it. */
 int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity);
+/* Diagnostic (tests): which row every lane of every slice of a sliced-row operator finishes -- the other half of what the
+ * summation order of a slice launch's inner products depends on (prcg_debug_layout's out[4]: its workgroups; four waves per
+ * workgroup; wave v of workgroup b takes slices xcd_remap(b) * 4 + v, + 4 * workgroups, ... of the table, one row per lane
+ * and slice).  out[64 * t + l] = the row of lane l of slice t in table (launch) order, -1 for an idle lane: read back from
+ * the device tables the kernels read -- the slice descriptors {first row, end row, .., rows_off, ..} and, for a slice that
+ * names its rows (rows_off >= 0: sorting windows, rows with skips), entry rows_off + l of the (row, length) stream.
+ * Returns 64 * slices, -needed if capacity is smaller (out may then be null), 0 if the resident operator has no sliced
+ * rows, -1 on a bad argument or a descriptor that points outside the stream.  On sliced-row and CSR-adaptive operators
+ * prcg_debug_layout's out[4] follows the products with a dot epilogue (one launch over all tiles: sessions without a
+ * communicator) as well as the one-launch pipelined iteration. */
+int64_t prcg_debug_slice_rows(const prcg_t* h, int32_t* out, int64_t capacity);
 /* Capacity rule of every vector a matrix-product launch reads (window pages are whole 64-column blocks, the narrow
  * column encodings decode a few out-of-tile bytes per tile): n_rows + n_ghost entries of `components` doubles plus
  * 65,536 spare entries must lie between the pointer and the end of its allocation.  The engine evaluates this at

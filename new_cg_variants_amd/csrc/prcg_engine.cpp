@@ -411,9 +411,11 @@ int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, S
         if (epi != kEpiNone) note_partials_launch(h, grid);
         return grid;
     }
-    if (h->sell)
-        return launch_sell_spmv(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.sell_per_cu);
-    return launch_spmv(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.kn);
+    const int grid = h->sell
+        ? launch_sell_spmv(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.sell_per_cu)
+        : launch_spmv(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.kn);
+    if (epi != kEpiNone) note_partials_launch(h, grid);
+    return grid;
 }
 int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask) {
     SRCCHK(h, {rs, 2});
@@ -3608,6 +3610,27 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity) {
         std::vector<Tile> t((size_t)nt);
         if (nt && hipMemcpy(t.data(), h->tiles.p, (size_t)nt * sizeof(Tile), hipMemcpyDeviceToHost) != hipSuccess) return -1;
         for (int64_t i = 0; i < nt; ++i) { out[8 + 2 * i] = t[(size_t)i].row_begin; out[9 + 2 * i] = t[(size_t)i].row_end; }
+    }
+    return need;
+}
+
+int64_t prcg_debug_slice_rows(const prcg_t* h, int32_t* out, int64_t capacity) {
+    if (!h || !h->have_csr) return -1;
+    if (!h->sell) return 0;
+    const int64_t ns = (int64_t)h->nst_int + h->nst_bnd;
+    const int64_t need = 64 * ns;
+    if (capacity < need || !out) return -need;
+    // both tables as the kernels read them (slice_row): the descriptors, and the (row, length) pairs of the slices that name rows
+    std::vector<SellSlice> s((size_t)ns);
+    if (ns && hipMemcpy(s.data(), h->sslices.p, (size_t)ns * sizeof(SellSlice), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const int64_t npairs = (int64_t)(h->srows.bytes / (2 * sizeof(int32_t)));
+    std::vector<int32_t> pairs((size_t)npairs * 2);
+    if (npairs && hipMemcpy(pairs.data(), h->srows.p, (size_t)npairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (int64_t t = 0; t < ns; ++t) {
+        const SellSlice& d = s[(size_t)t];
+        if (d.rows_off >= 0 && (int64_t)d.rows_off + 64 > npairs) return -1;
+        for (int l = 0; l < 64; ++l)
+            out[64 * t + l] = d.rows_off < 0 ? (d.rb + l < d.re ? d.rb + l : -1) : pairs[(size_t)2 * (d.rows_off + l)];
     }
     return need;
 }

@@ -33,6 +33,12 @@ The update kernels other than k_pipe_update (k_hs_update_xr, k_pr_update, k_gv_u
 thread two NEIGHBOURING elements per trip -- thread (block b, lane t): elements (b*trips + j)*512 + 2t, then + 1 -- and the
 same wave / block / final tree: ``pair_sum``.
 
+``UnitTree`` is the tile tree of the two families that are no window operators -- sliced rows (prcg_sell.hip) and CSR-adaptive
+tiles (prcg_kernels.hip: k_spmv_tiles), always four waves per workgroup: a wave's units (slices: one row per lane; tiles:
+ceil(rows / 64) rows per lane) come from DeviceCSR.layout()'s 'slice_rows' (prcg_debug_slice_rows) or 'tiles'.  A row of the
+CSR-adaptive tiles that is longer than a tile is summed by its whole wave: ``LongRowOperator`` is the matrix with those rows
+multiplied that way.
+
 ``Routed`` lets a schedule whose inner products come from different launches (Hestenes-Stiefel: nu from the update
 kernel, mu from the tile launch) plug into the oracle: the oracle calls ``dot`` in a fixed order per advance.
 """
@@ -210,3 +216,114 @@ class OneLaunchTree:
 
     def dot(self, a, b):
         return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
+class UnitTree:
+    """The summation order of the inner products a launch of the sliced-row kernels (prcg_sell.hip: k_sell_win, k_sell_tiles)
+    or of the CSR-adaptive tile kernel (prcg_kernels.hip: k_spmv_tiles) leaves, whatever its epilogue:
+
+      wave v of workgroup b takes UNITS (slices / tiles) xcd_remap(b, grid) * wpb + v, + grid * wpb, ... of the table, in
+      that order; one lane-private accumulator per inner product, starting at +0.0, adds the rows the lane finishes
+      unit   : an ordered list of 64-lane row vectors, one per step, -1: the lane finishes no row in that step
+      wave   : xor butterfly       block : waves 0..wpb-1 in order (block_reduce_store)      final : the 256-thread tree
+
+    ``units``: a sequence of integer arrays of shape (steps, 64) -- steps may differ from unit to unit and may be 0."""
+
+    def __init__(self, units, grid, wpb=4):
+        grid, wpb = int(grid), int(wpb)
+        assert grid > 0 and wpb > 0, (grid, wpb)
+        units = [np.asarray(u, dtype=np.int64).reshape(-1, 64) for u in units]
+        W = grid * wpb
+        waves = []
+        for b in range(grid):
+            for v in range(wpb):
+                mine = [units[t] for t in range(xcd_remap(b, grid) * wpb + v, len(units), W)]
+                waves.append(np.concatenate(mine, axis=0) if mine else np.zeros((0, 64), dtype=np.int64))
+        steps = max(w.shape[0] for w in waves)
+        # idx[b, v, step, lane] = row summed by that lane at that step, -1: none
+        idx = -np.ones((grid * wpb, steps, 64), dtype=np.int64)
+        for i, w in enumerate(waves):
+            idx[i, :w.shape[0]] = w
+        self.idx = idx.reshape(grid, wpb, steps, 64)
+        self.grid, self.wpb = grid, wpb
+        covered = np.sort(self.idx[self.idx >= 0])
+        assert covered.size > 0 and np.array_equal(covered, np.arange(covered[0], covered[-1] + 1)), 'every row summed exactly once'
+        self.rows = (int(covered[0]), int(covered[-1]) + 1)
+
+    @classmethod
+    def from_tiles(cls, layout):
+        """CSR-adaptive tiles (process_tile) from layout()['tiles']: lane l of the tile's wave finishes rows rb + l, rb + 64 + l,
+        ... below re -- ceil(rows / 64) steps; a long-row tile is one row, finished by lane 0 after the wave has summed it."""
+        assert not layout['window'] and not layout['sliced'] and layout['grid'] > 0, {k: v for k, v in layout.items() if np.ndim(v) == 0}
+        lane = np.arange(64)
+        units = []
+        for rb, re in np.asarray(layout['tiles'], dtype=np.int64):
+            rows = rb + 64 * np.arange(-(-(re - rb) // 64))[:, None] + lane[None, :]
+            units.append(np.where(rows < re, rows, -1))
+        return cls(units, layout['grid'], layout['waves_per_block'])
+
+    @classmethod
+    def from_slices(cls, layout):
+        """sliced rows (slice_row) from layout()['slice_rows']: lane l finishes ONE row per slice -- rb + l, or the row the
+        slice names for that lane; -1: an idle lane (a ragged, cut or padded slice)."""
+        assert layout['sliced'] and layout['grid'] > 0, {k: v for k, v in layout.items() if np.ndim(v) == 0}
+        return cls([r[None, :] for r in np.asarray(layout['slice_rows'], dtype=np.int64)], layout['grid'], layout['waves_per_block'])
+
+    @classmethod
+    def of(cls, layout):
+        return cls.from_slices(layout) if layout['sliced'] else cls.from_tiles(layout)
+
+    def sum(self, prod):
+        prod = np.asarray(prod, dtype=np.float64)
+        ext = np.concatenate([prod, [0.0]])            # index -1 -> +0.0 (adding it changes nothing: acc starts at +0.0)
+        acc = np.zeros(self.idx.shape[:2] + (64,))
+        for step in range(self.idx.shape[2]):
+            acc = acc + ext[self.idx[:, :, step, :]]
+        waves = _butterfly(acc)                        # (grid, wpb)
+        partial = waves[:, 0]
+        for v in range(1, self.wpb):
+            partial = partial + waves[:, v]
+        return _final_tree(partial)
+
+    def dot(self, a, b):
+        return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
+def long_row_sum(prod):
+    """a long row of the CSR-adaptive tiles (process_tile: more nonzeros than the tile cap): lane l adds the products l, l + 64,
+    ... left to right from +0.0, the wave butterfly gives the row result -- NOT SciPy's left-to-right sum."""
+    prod = np.asarray(prod, dtype=np.float64)
+    padded = np.zeros(-(-prod.shape[0] // 64) * 64)
+    padded[:prod.shape[0]] = prod                      # (a lane past the end adds nothing; +0.0 here is the same value)
+    acc = np.zeros(64)
+    for chunk in padded.reshape(-1, 64):
+        acc = acc + chunk
+    return np.float64(_butterfly(acc))
+
+
+def tile_cap_nnz(tile_steps):
+    """most nonzeros of a CSR-adaptive tile (prcg_kernels.hip: kCap) for schedule()['tile_steps']; a longer row is a long row"""
+    return 256 * int(tile_steps) - 3
+
+
+class LongRowOperator:
+    """A as the CSR-adaptive tile kernels multiply it: ``@`` is SciPy's product (every row left to right) except in rows
+    with more than `cap` nonzeros, which are summed as the device sums them (long_row_sum).  Forwards what the oracle and
+    the tests ask of an operator besides ``A @ v``: .shape and .diagonal()."""
+
+    def __init__(self, A, cap):
+        self.A, self.cap = A.tocsr(), int(cap)
+        self.shape = self.A.shape
+        self.long_rows = np.flatnonzero(np.diff(self.A.indptr) > self.cap)
+
+    def diagonal(self):
+        return self.A.diagonal()
+
+    def __matmul__(self, v):
+        y = self.A @ v
+        v = np.asarray(v, dtype=np.float64)
+        assert v.ndim == 1
+        for i in self.long_rows:
+            lo, hi = self.A.indptr[i], self.A.indptr[i + 1]
+            y[i] = long_row_sum(self.A.data[lo:hi] * v[self.A.indices[lo:hi]])
+        return y

@@ -1,15 +1,18 @@
 """CPU: the model of the device's summation order (tests/device_order.py) on its own -- synthetic layouts, no GPU.
 
 What tests/test_trajectory_oracle.py relies on: the tile tree sums every row exactly once in the order the kernel does
-(OneLaunchTree), the pair-layout update-kernel tree (pair_sum), the XCD remap, the per-product routing (Routed) -- and that
-ONE row summed twice, dropped or taken from a stale buffer at ONE iteration of a run hundreds of iterations long changes
+(OneLaunchTree), the pair-layout update-kernel tree (pair_sum), the XCD remap, the per-product routing (Routed), the unit
+tree of the sliced-row and CSR-adaptive launches (UnitTree: variable steps per unit, named rows, idle lanes) with the long-row
+product of the CSR-adaptive tiles (LongRowOperator: what tests/test_trajectory_irregular.py relies on) -- and that ONE row summed twice, dropped or taken from a stale buffer at ONE iteration of a run hundreds of iterations long changes
 the bits of that iteration's inner products (so a bit-for-bit comparison with the device sees it)."""
 import math
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
-from device_order import (OneLaunchTree, Routed, device_sum, first_mismatch, pair_dot, pair_sum, xcd_remap)
+from device_order import (LongRowOperator, OneLaunchTree, Routed, UnitTree, device_sum, first_mismatch, long_row_sum, pair_dot, pair_sum,
+                          tile_cap_nnz, xcd_remap)
 from oracle import ne_oracle as orc
 
 
@@ -187,3 +190,208 @@ def test_one_wrong_row_at_one_iteration_of_a_long_run_shows_in_the_bits(matrices
     nan = clean.copy()
     nan[17, 2] = np.nan
     assert first_mismatch(nan, nan) == 17           # NaN never passes as equal
+
+
+# ---- UnitTree: sliced rows and CSR-adaptive tiles (tests/test_trajectory_irregular.py) ------------------------------------
+def unit_layout(grid, tiles=None, slice_rows=None):
+    """what DeviceCSR.layout() returns for a CSR-adaptive operator (tiles) or a sliced-row operator (slice_rows)"""
+    sliced = slice_rows is not None
+    return {'window': False, 'geometry': -1, 'rows_per_tile': 0, 'grid': grid, 'waves_per_block': 4, 'interior_tiles': 0, 'sweep_waves': 0,
+            'tiles': np.zeros((0, 2), dtype=np.int64) if tiles is None else np.asarray(tiles, dtype=np.int64), 'sliced': sliced,
+            'slice_rows': np.asarray(slice_rows, dtype=np.int32).reshape(-1, 64) if sliced else np.zeros((0, 64), dtype=np.int32)}
+
+
+def tiles_of(sizes):
+    re = np.cumsum(sizes)
+    return np.stack([re - sizes, re], axis=1)
+
+
+def synthetic_units(kind, count, rng):
+    """a layout's unit table with `count` units.  'tiles': CSR-adaptive tiles of 1..256 rows with 63, 64, 65, 129, 256 and a
+    one-row tile among them; 'full': full slices and a ragged last one; 'cut': slices of 1..64 consecutive rows (the idle lanes
+    behind); 'named': sorting windows of four slices whose rows are named in a permuted order, the idle lanes of a window in the
+    middle of its last slice's lanes"""
+    if kind == 'tiles':
+        sizes = rng.integers(1, 257, count)
+        special = [63, 64, 65, 129, 256, 1]
+        sizes[rng.permutation(count)[:min(count, len(special))]] = special[:min(count, len(special))]
+        return {'tiles': tiles_of(sizes)}
+    lane = np.arange(64)
+    if kind == 'full':
+        rows = 64 * np.arange(count)[:, None] + lane[None, :]
+        rows[-1, 25:] = -1
+        return {'slice_rows': rows}
+    if kind == 'cut':
+        t = tiles_of(rng.integers(1, 65, count))
+        rows = t[:, :1] + lane[None, :]
+        return {'slice_rows': np.where(rows < t[:, 1:], rows, -1)}
+    out, first = [], 0
+    for w in range(0, count, 4):
+        ns = min(4, count - w)
+        nrows = 64 * ns - int(rng.integers(0, 40))
+        win = -np.ones(64 * ns, dtype=np.int64)
+        keep = np.sort(rng.permutation(64 * ns)[:nrows])             # (idle lanes anywhere in the window)
+        win[keep] = first + rng.permutation(nrows)
+        out.append(win.reshape(ns, 64))
+        first += nrows
+    return {'slice_rows': np.concatenate(out)}
+
+
+UNIT_CASES = [(g, kind, shape) for g in (1, 7, 8, 9, 143) for kind in ('tiles', 'full', 'cut', 'named')
+              for shape in ('fewer_than_waves', 'three_per_wave', 'partial_round')]
+
+
+@pytest.mark.parametrize('grid,kind,shape', UNIT_CASES)
+def test_unit_tree_on_synthetic_units(grid, kind, shape):
+    """Every row once (the constructor asserts it), whatever the unit: a valid summation within 1e-13 * sum|terms| of the
+    exactly rounded sum, np.float64 out, exact on integers; a wave's steps are the steps of its units one after the other."""
+    count = tiles_for(grid, 4, shape)
+    rng = np.random.default_rng(grid * 100 + len(kind) * 10 + len(shape))
+    lay = unit_layout(grid, **synthetic_units(kind, count, rng))
+    tree = UnitTree.of(lay)
+    assert tree.idx.shape[:2] == (grid, 4) and tree.idx.shape[3] == 64
+    n = tree.rows[1]
+    assert tree.rows[0] == 0 and np.count_nonzero(tree.idx >= 0) == n
+    if kind == 'tiles':
+        steps = -(-(lay['tiles'][:, 1] - lay['tiles'][:, 0]) // 64)
+        per_wave = [sum(steps[xcd_remap(b, grid) * 4 + v::grid * 4]) for b in range(grid) for v in range(4)]
+        assert tree.idx.shape[2] == max(per_wave)
+        sizes = lay['tiles'][:, 1] - lay['tiles'][:, 0]
+        assert count < 6 or {1, 63, 64, 65, 129, 256} <= set(sizes.tolist())
+        for one in np.flatnonzero(sizes == 1):                 # a one-row tile: lane 0 alone
+            where = np.argwhere(tree.idx == lay['tiles'][one, 0])
+            assert where.shape == (1, 4) and where[0, 3] == 0
+            b, v, st = where[0, :3]
+            assert (tree.idx[b, v, st, 1:] == -1).all()
+    else:
+        assert tree.idx.shape[2] == -(-count // (grid * 4))
+    if shape == 'fewer_than_waves':
+        assert (tree.idx[:, :, 0, :] < 0).all(axis=2).sum() == grid * 4 - count          # waves without a unit add nothing
+    prod = rng.standard_normal(n) * np.exp(rng.uniform(-8, 8, n))
+    got = tree.sum(prod)
+    assert type(got) is np.float64
+    assert abs(got - math.fsum(prod)) <= 1e-13 * math.fsum(np.abs(prod))
+    a, b = rng.standard_normal(n), rng.standard_normal(n)
+    assert tree.dot(a, b) == tree.sum(a * b)
+    ints = rng.integers(-1000, 1000, n).astype(np.float64)
+    assert tree.sum(ints) == ints.sum()
+
+
+def test_unit_tree_refuses_a_row_summed_twice_or_never():
+    rows = 64 * np.arange(5)[:, None] + np.arange(64)[None, :]
+    UnitTree.of(unit_layout(2, slice_rows=rows))
+    twice = rows.copy()
+    twice[3] = twice[2]
+    with pytest.raises(AssertionError, match='exactly once'):
+        UnitTree.of(unit_layout(2, slice_rows=twice))
+    with pytest.raises(AssertionError, match='exactly once'):
+        UnitTree.of(unit_layout(2, slice_rows=np.delete(rows, 2, axis=0)))
+    with pytest.raises(AssertionError, match='exactly once'):
+        UnitTree.of(unit_layout(2, tiles=[[0, 100], [90, 200]]))
+
+
+@pytest.mark.parametrize('grid,wpb,rows,shape', [c for c in LAYOUTS if c[0] in (7, 9) or c[1] == 4])
+def test_unit_tree_built_like_a_window_layout_gives_the_bits_of_the_tile_tree(grid, wpb, rows, shape):
+    nt = tiles_for(grid, wpb, shape)
+    lay = synthetic_layout(nt, rows, grid, wpb, last_rows=rows - 39)
+    lane = np.arange(64)
+    units = []
+    for rb, re in lay['tiles']:
+        r = rb + 64 * np.arange(rows // 64)[:, None] + lane[None, :]
+        units.append(np.where(r < re, r, -1))                 # (a window tile has rows_per_tile / 64 steps, idle or not)
+    unit, tile = UnitTree(units, grid, wpb), OneLaunchTree(lay)
+    assert np.array_equal(unit.idx, tile.idx)
+    rng = np.random.default_rng(grid + wpb + rows)
+    for _ in range(3):
+        prod = rng.standard_normal(int(lay['tiles'][-1, 1]))
+        assert unit.sum(prod) == tile.sum(prod)
+
+
+def test_unit_tree_discriminates():
+    """What the device's order could differ in without losing a row -- each changes bits of the sum of a fixed random vector
+    (three vectors: 'at least one bit' of any of the three sums), so the bit-for-bit comparison with the device sees it."""
+    rng = np.random.default_rng(2024)
+    grid = 9
+    named = synthetic_units('named', 3 * grid * 4, rng)['slice_rows']
+    n = int(named.max()) + 1
+    vecs = [rng.standard_normal(n) for _ in range(3)]
+
+    def sums(tree, vecs=vecs):
+        assert tree.rows == (0, vecs[0].shape[0])
+        return [tree.sum(v) for v in vecs]
+    ref = sums(UnitTree.of(unit_layout(grid, slice_rows=named)))
+    # two slices exchanged between two waves of one workgroup
+    swapped = named.copy()
+    swapped[[0, 1]] = swapped[[1, 0]]
+    assert sums(UnitTree.of(unit_layout(grid, slice_rows=swapped))) != ref
+    # the same slice table, the rows taken as consecutive instead of as named
+    flat = -np.ones_like(named)
+    flat[named >= 0] = np.arange(n)
+    assert np.array_equal(flat >= 0, named >= 0)
+    assert sums(UnitTree.of(unit_layout(grid, slice_rows=flat))) != ref
+    # a 65-row tile: two steps of ONE wave (row 64 joins lane 0's accumulator) -- not a unit of 64 rows and a unit of one
+    sizes = np.full(3 * grid * 4, 64)
+    sizes[5] = 65
+    t = tiles_of(sizes)
+    vecs_t = [rng.standard_normal(int(t[-1, 1])) for _ in range(3)]
+    ref_t = sums(UnitTree.of(unit_layout(grid, tiles=t)), vecs_t)
+    split = np.concatenate([t[:5], [[t[5, 0], t[5, 0] + 64], [t[5, 0] + 64, t[5, 1]]], t[6:]])
+    assert sums(UnitTree.of(unit_layout(grid, tiles=split)), vecs_t) != ref_t
+    # a long row: 64 lane sums and the butterfly, not left to right
+    long = [rng.standard_normal(2500) for _ in range(3)]
+    left = []
+    for p in long:
+        s = 0.0
+        for x in p:
+            s += x
+        left.append(s)
+    assert [long_row_sum(p) for p in long] != left
+    assert all(abs(long_row_sum(p) - math.fsum(p)) <= 1e-14 * math.fsum(np.abs(p)) for p in long)
+
+
+def long_row_matrix(rng, n, long_rows):
+    """random sparse rows of 3..40 entries, the rows in `long_rows` (row -> entries) long, a dominant diagonal"""
+    lens = rng.integers(3, 41, n)
+    for i, m in long_rows.items():
+        lens[i] = m
+    indptr = np.concatenate([[0], np.cumsum(lens)])
+    indices = np.concatenate([np.sort(rng.permutation(n)[:m]) for m in lens])
+    A = sp.csr_matrix((rng.standard_normal(indptr[-1]) * np.exp(rng.uniform(-3, 3, indptr[-1])), indices, indptr), shape=(n, n))
+    return A
+
+
+def test_long_row_operator():
+    """SciPy's product bit for bit while no row exceeds the cap; with long rows within DESIGN.md's bar for them, 1e-14 * sum|a_ij x_j|
+    per row, and NOT SciPy's bits; shape and diagonal forwarded; the cap of schedule()['tile_steps']."""
+    assert [tile_cap_nnz(s) for s in (1, 2, 4)] == [253, 509, 1021]
+    rng = np.random.default_rng(11)
+    n = 3000
+    A = long_row_matrix(rng, n, {7: 509, 1200: 2000, 2999: 2600, 40: 510})
+    x = rng.standard_normal(n)
+    plain = LongRowOperator(A, 2600)
+    assert plain.long_rows.size == 0 and np.array_equal(plain @ x, A @ x)
+    op = LongRowOperator(A, tile_cap_nnz(2))
+    assert list(op.long_rows) == [40, 1200, 2999]                # (a row of exactly the cap is no long row)
+    assert op.shape == A.shape and np.array_equal(op.diagonal(), A.diagonal())
+    got, want = op @ x, A @ x
+    short = np.setdiff1d(np.arange(n), op.long_rows)
+    assert np.array_equal(got[short], want[short])
+    bound = 1e-14 * (abs(A) @ np.abs(x))
+    assert (np.abs(got - want) <= bound).all()
+    assert np.count_nonzero(got != want) >= 1
+    assert (got[[1200, 2999]] != want[[1200, 2999]]).any()       # a row of >= 2000 entries shows the other order
+    for i in op.long_rows:
+        lo, hi = A.indptr[i], A.indptr[i + 1]
+        terms = A.data[lo:hi] * x[A.indices[lo:hi]]
+        assert abs(got[i] - math.fsum(terms)) <= 1e-14 * math.fsum(np.abs(terms))
+        # the model of the lanes: lane l sums terms l, l + 64, ... left to right
+        lanes = []
+        for l in range(64):
+            s = 0.0
+            for t in terms[l::64]:
+                s += t
+            lanes.append(s)
+        v = np.array(lanes)
+        for off in (32, 16, 8, 4, 2, 1):
+            v = v + v[np.arange(64) ^ off]                       # the xor butterfly itself, every lane
+        assert (v == v[0]).all() and got[i] == v[0]

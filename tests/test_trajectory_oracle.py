@@ -35,25 +35,9 @@ import pytest
 
 from device_order import OneLaunchTree, Routed, device_dot, first_mismatch, pair_sum
 from oracle import ne_oracle as orc
+from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, run_device, run_oracle
 
 pytestmark = pytest.mark.gpu
-
-FOUR = ['error_A_norm', 'residual_2_norm', 'error_2_norm', 'updated_residual_2_norm']
-
-# method -> (device variant, family, Jacobi, [(device scalar slot, oracle state field)]: the inner products the method defines)
-PIPE_SLOTS = [('S_MU', 'mu'), ('S_DELTA', 'dl'), ('S_GAMMA', 'gm'), ('S_NU', 'nu')]
-LAG_SLOTS = [('S_MU', 'mu'), ('S_DELTA', 'eta'), ('S_NU', 'nu')]        # (mu is derived: eta - (b / a) nu, cg_cg.py:67)
-HS_SLOTS = [('S_MU', 'mu'), ('S_NU', 'nu')]
-METHODS = {
-    'pipe_pr_pcg': ('PIPE_PR', 'pipe', True, PIPE_SLOTS), 'pipe_p_pcg': ('PIPE_P', 'pipe', True, PIPE_SLOTS),
-    'pipe_pr_m_pcg': ('PIPE_PR_M', 'pipe', True, PIPE_SLOTS), 'pipe_p_m_pcg': ('PIPE_P_M', 'pipe', True, PIPE_SLOTS),
-    'pr_pcg': ('PR', 'pr', True, PIPE_SLOTS), 'm_pcg': ('M', 'pr', True, PIPE_SLOTS),
-    'pr_cg': ('PR', 'pr', False, PIPE_SLOTS), 'm_cg': ('M', 'pr', False, PIPE_SLOTS),     # (the oracle's pr_pcg / m_pcg with the identity)
-    'cg_cg': ('CG_CG', 'cg', False, LAG_SLOTS), 'cg_pcg': ('CG_CG', 'cg', True, LAG_SLOTS),
-    'gv_cg': ('GV', 'gv', False, LAG_SLOTS), 'gv_pcg': ('GV', 'gv', True, LAG_SLOTS),
-    'hs_cg': ('HS', 'hs', False, HS_SLOTS), 'hs_pcg': ('HS', 'hs', True, HS_SLOTS),
-}
-ORACLE_NAME = {'pr_cg': 'pr_pcg', 'm_cg': 'm_pcg'}
 
 # operator -> knobs of the handle (every handle: PRCG_SMALL=0, the one-workgroup solver of tiny systems has its own order)
 OPERATORS = {
@@ -99,7 +83,6 @@ CASES = [
     ('hs_cg', 'bcsstk03', 800, {}), ('hs_cg', 's3_plain', 150, {}), ('hs_cg', 'lap3d_40', 150, {}), ('hs_cg', 'lap2d_400', 150, {}),
     ('hs_pcg', 'nos7', 400, {}), ('hs_pcg', 'lap2d_300', 150, {}), ('hs_pcg', 'lap2d_400', 150, {}),
 ]
-CHUNKS = (1, 2, 37)          # prcg_iterate calls of mode (b), then the rest: state read at k = 3 (odd), k = 40 (even) and the end
 
 
 def case_id(c):
@@ -145,43 +128,6 @@ def oracle_dots(family, tree, start_tree):
     if family == 'gv':
         return Routed(tree.sum), Routed(pair_sum)
     return Routed(pair_sum, tree.sum), Routed(pair_sum, start_tree.sum)         # hs: nu, mu
-
-
-def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep):
-    """the oracle's trajectory: rows (mu, dl, gm, nu, eta, alpha, beta) per state, recorder histories, (x, r) at the states in `keep`"""
-    rows, snaps = [], {}
-
-    def tap(st):
-        rows.append((st.mu, st.dl, st.gm, st.nu, st.eta, st.alpha, st.beta))
-        if st.k in keep:
-            snaps[st.k] = (st.x.copy(), st.r.copy())
-    kw = {'preconditioner': jacobi} if METHODS[method][2] else {}
-    ref = getattr(orc, ORACLE_NAME.get(method, method))(A, b, np.zeros(A.shape[0]), max_iter, dot=dot, dot0=dot0, square=lambda a: a * a,
-                                                         callbacks=FOUR, x_true=x_true, tap=tap, **kw)
-    return np.array(rows, dtype=np.float64), ref, snaps
-
-
-FIELD = {'mu': 0, 'dl': 1, 'gm': 2, 'nu': 3, 'eta': 4, 'alpha': 5, 'beta': 6}
-
-
-def run_device(L, op, variant, b, x_true, inv_diag, max_iter, recorders):
-    """one session: mode (a) all four recorders, one prcg_iterate call; mode (b) the recurrence residual only, calls of CHUNKS
-    and the rest, x and r read after each"""
-    n = b.shape[0]
-    op.begin(variant, b, np.zeros(n), max_iter, x_true=x_true if recorders else None, inv_diag=inv_diag, hist_mask=15 if recorders else 1)
-    out = {'schedule': op.schedule(), 'start_layout': op.layout(), 'state': {}}
-    if recorders:
-        op.iterate(max_iter - 1)
-    else:
-        for chunk in CHUNKS + (max_iter,):
-            op.iterate(min(chunk, max_iter - 1 - op.k))
-            out['state'][int(op.k)] = (op.get_vector('x'), op.get_vector('r'))
-    op.sync()
-    out['scalars'] = np.array([op.get_scalars(k) for k in range(max_iter)])
-    out['coef'] = np.array([op.get_coefficients(k)[:2] for k in range(1, max_iter)])
-    out['hist'] = op.history()
-    out['layout'] = op.layout()
-    return out
 
 
 def same_tree(a, b):
