@@ -11,7 +11,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iin
 TRANSPORT := tests/transport/libthreads_ccl.so
 # ... and one that connects ranks living in separate PROCESSES that share one GPU (the driver's launch shape, rehearsed on one GPU)
 TRANSPORT_P := tests/transport/libprocs_ccl.so
-OBJS := $(CSRC)/prcg_kernels.o $(CSRC)/prcg_win.o $(CSRC)/prcg_sell.o $(CSRC)/prcg_blockjac.o $(CSRC)/prcg_rhs2.o $(CSRC)/prcg_engine.o $(CSRC)/prcg_batch.o $(CSRC)/prcg_plan.o $(CSRC)/prcg_rccl.o
+OBJS := $(CSRC)/prcg_kernels.o $(CSRC)/prcg_win.o $(CSRC)/prcg_sell.o $(CSRC)/prcg_blockjac.o $(CSRC)/prcg_rhs2.o $(CSRC)/prcg_small.o $(CSRC)/prcg_engine.o $(CSRC)/prcg_batch.o $(CSRC)/prcg_plan.o $(CSRC)/prcg_rccl.o
 
 all: $(OUT) $(TRANSPORT) $(TRANSPORT_P)
 
@@ -28,6 +28,9 @@ $(CSRC)/prcg_blockjac.o: $(CSRC)/prcg_blockjac.hip $(CSRC)/prcg_kernels.h $(CSRC
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
 $(CSRC)/prcg_rhs2.o: $(CSRC)/prcg_rhs2.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
+
+$(CSRC)/prcg_small.o: $(CSRC)/prcg_small.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
 $(CSRC)/prcg_batch.o: $(CSRC)/prcg_batch.cpp $(CSRC)/prcg_batch.h $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h include/prcg.h include/prcg_test.h

@@ -1,5 +1,5 @@
-// A batch of small independent systems A_s x_s = b_s, every one solved by the one-workgroup solver (k_small_pipe_pr /
-// k_small_hs, prcg_kernels.hip), all of them in the same launch: blockIdx.x selects the system.  Implements the prcg_batch_*
+// A batch of small independent systems A_s x_s = b_s, every one solved by the one-workgroup solver (k_small_pipe_pr_batch /
+// k_small_hs_batch, prcg_small.hip), all of them in the same launch: blockIdx.x selects the system.  Implements the prcg_batch_*
 // entries of include/prcg.h and the planner hook prcg_plan_small_batch of include/prcg_test.h.  Host code only.
 //
 // Layout on the device: the matrices concatenated (every matrix uploaded once, however many systems use it); per session the
@@ -12,9 +12,9 @@
 // members: the launch's dynamic LDS is the group's largest need, each workgroup carves it by its own n and nnz.
 //
 // Thresholds set with prcg_batch_set_stop are kept on the host; a session begun while they are set adds one SmallStop per system
-// (sorted like the descriptors) and one stop word {iteration, status} per system (in SYSTEM order), and its iteration calls launch
-// the kernels that apply the stopping rule (prcg_kernels.h: SmallStop) inside each workgroup.  A session begun without them
-// launches what it always launched.
+// (sorted like the descriptors) and one stop word {iteration, status} per system (in SYSTEM order), and its iteration calls hand
+// them to the launch (SmallBatchArgs::stop), which then applies the stopping rule (prcg_kernels.h: SmallStop) inside each
+// workgroup.  A session begun without them launches the kernels without the rule.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -61,8 +61,7 @@ int plan_groups(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* 
     bool have[2] = {false, false};
     for (int s = 0; s < n_sys; ++s) {
         int mode = 0;
-        if (nnz[s] < 0 || !(jacobi ? small_fits_jacobi(n[s], nnz[s], max_row_len[s], &mode) : small_fits(n[s], nnz[s], max_row_len[s], &mode)))
-            return -s - 1;
+        if (nnz[s] < 0 || !small_fits(n[s], nnz[s], max_row_len[s], &mode, jacobi)) return -s - 1;
         mode_out[s] = mode;
         have[mode] = true;
     }
@@ -82,8 +81,7 @@ struct prcg_batch {
     std::vector<const int*> indptr, col;           // per system: its matrix on the device
     std::vector<const double*> val;
     int count[2] = {0, 0};                         // systems of mode 0 / mode 1
-    size_t lds[2] = {0, 0};                        // largest small_lds_bytes of each mode's members
-    size_t lds_jac[2] = {0, 0};                    // ... and small_lds_bytes_jacobi
+    size_t lds[2][2] = {};                         // [mode][jacobi]: largest small_lds_bytes of the mode's members
     Buf m_indptr, m_col, m_val;                    // the matrices, concatenated
     Buf state, rhs, x0, dinv, dots, coef, desc, init, jac, tmp, stop, words;
     std::vector<double> rr_stop;                   // per system: the threshold on r.r of sessions begun from now on (empty: none)
@@ -195,10 +193,10 @@ int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64
         b->col[(size_t)s] = static_cast<const int*>(b->m_col.p) + nnz_off[m];
         b->val[(size_t)s] = b->m_val.d() + nnz_off[m];
         ++b->count[md];
-        const size_t need = small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], md);
-        if (need > b->lds[md]) b->lds[md] = need;
-        const size_t need_jac = small_lds_bytes_jacobi(b->n[(size_t)s], b->nnz[(size_t)s], md);
-        if (need_jac > b->lds_jac[md]) b->lds_jac[md] = need_jac;
+        for (int j = 0; j < 2; ++j) {
+            const size_t need = small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], md, j == 1);
+            if (need > b->lds[md][j]) b->lds[md][j] = need;
+        }
     }
     int at[2] = {b->count[1], 0};                  // descriptors: mode 1 first, then mode 0, each in system order
     for (int s = 0; s < n_sys; ++s) b->slot[(size_t)s] = at[b->mode[(size_t)s]]++;
@@ -216,11 +214,24 @@ void prcg_batch_destroy(prcg_batch_t* b) {
 
 }  // extern "C"
 
-// what prcg_batch_begin and prcg_batch_begin_jacobi (inv_diag non-null) share: every argument has been checked
-static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
-                       uint32_t hist_mask) {
+// prcg_batch_begin and prcg_batch_begin_jacobi (jacobi: inv_diag is an argument, fn names the entry in the error texts)
+static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant, const double* rhs, const double* x0, const double* inv_diag,
+                       int max_iter, uint32_t hist_mask) {
+    if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    const bool jacobi = inv_diag != nullptr;
+    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
+           "%s: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", fn, variant);
+    BCHECK(h, rhs && x0 && (inv_diag || !jacobi), jacobi ? "%s: null rhs, x0 or inv_diag" : "%s: null rhs or x0", fn);
+    BCHECK(h, max_iter >= 1, "%s: max_iter = %d, must be at least 1", fn, max_iter);
+    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+           "%s: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", fn, hist_mask);
+    for (int s = 0; jacobi && s < b->n_sys; ++s) {
+        int mode = 0;
+        BCHECK(h, small_fits(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode, true),
+               "%s: system %d (n = %d, nnz = %d) fits the one-workgroup solver without a preconditioner but not with one: "
+               "the preconditioned solver needs %zu bytes of LDS, 128 more, and the cap is 159744", fn, s, b->n[(size_t)s], b->nnz[(size_t)s],
+               small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], 0, true));
+    }
     BHIP(h, hipSetDevice(b->dev));
     b->in_session = false;
     const int n_sys = b->n_sys;
@@ -287,9 +298,8 @@ static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const do
     BHIP(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
     for (int m = 1; m >= 0; --m) {                 // one initialisation launch per group
         if (!b->count[m]) continue;
-        const int rc = jacobi ? launch_small_batch_init_jacobi(sc, b->desc_of(m), b->init_of(m), b->jac_of(m), b->count[m], hs)
-                              : launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), b->count[m], hs);
-        if (rc < 0) return batch_fail(h, PRCG_EHIP, "%s: kernel launch failed", jacobi ? "prcg_batch_begin_jacobi" : "prcg_batch_begin");
+        if (launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), jacobi ? b->jac_of(m) : nullptr, b->count[m], hs) < 0)
+            return batch_fail(h, PRCG_EHIP, "%s: kernel launch failed", fn);
     }
     BHIP(h, hipStreamSynchronize(sc));
     b->in_session = true;
@@ -299,37 +309,12 @@ static int batch_begin(prcg_batch_t* b, int variant, const double* rhs, const do
 extern "C" {
 
 int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask) {
-    if (!b) return PRCG_EINVAL;
-    prcg_t* h = b->h;
-    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
-           "prcg_batch_begin: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", variant);
-    BCHECK(h, rhs && x0, "prcg_batch_begin: null rhs or x0");
-    BCHECK(h, max_iter >= 1, "prcg_batch_begin: max_iter = %d, must be at least 1", max_iter);
-    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
-           "prcg_batch_begin: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", hist_mask);
-    return batch_begin(b, variant, rhs, x0, nullptr, max_iter, hist_mask);
+    return batch_begin(b, "prcg_batch_begin", false, variant, rhs, x0, nullptr, max_iter, hist_mask);
 }
 
 int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
                             uint32_t hist_mask) {
-    if (!b) return PRCG_EINVAL;
-    prcg_t* h = b->h;
-    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
-           "prcg_batch_begin_jacobi: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)",
-           variant);
-    BCHECK(h, rhs && x0 && inv_diag, "prcg_batch_begin_jacobi: null rhs, x0 or inv_diag");
-    BCHECK(h, max_iter >= 1, "prcg_batch_begin_jacobi: max_iter = %d, must be at least 1", max_iter);
-    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
-           "prcg_batch_begin_jacobi: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)",
-           hist_mask);
-    for (int s = 0; s < b->n_sys; ++s) {
-        int mode = 0;
-        BCHECK(h, small_fits_jacobi(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode),
-               "prcg_batch_begin_jacobi: system %d (n = %d, nnz = %d) fits the one-workgroup solver without a preconditioner but not with one: "
-               "the preconditioned solver needs %zu bytes of LDS, 128 more, and the cap is 159744", s, b->n[(size_t)s], b->nnz[(size_t)s],
-               small_lds_bytes_jacobi(b->n[(size_t)s], b->nnz[(size_t)s], 0));
-    }
-    return batch_begin(b, variant, rhs, x0, inv_diag, max_iter, hist_mask);
+    return batch_begin(b, "prcg_batch_begin_jacobi", true, variant, rhs, x0, inv_diag, max_iter, hist_mask);
 }
 
 int prcg_batch_iterate(prcg_batch_t* b, int iters) {
@@ -343,15 +328,8 @@ int prcg_batch_iterate(prcg_batch_t* b, int iters) {
     const int meurant = b->variant == PRCG_PIPE_PR_M ? 1 : 0;
     for (int m = 1; m >= 0; --m) {                 // one launch per group: every system advances by iters
         if (!b->count[m]) continue;
-        int rc;
-        if (b->stopping)
-            rc = b->jacobi ? launch_small_batch_jacobi_stop(b->sc, b->desc_of(m), b->jac_of(m), b->stop_of(m), b->count[m], m, b->lds_jac[m],
-                                                            b->hs, b->k, iters, meurant)
-                           : launch_small_batch_stop(b->sc, b->desc_of(m), b->stop_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters, meurant);
-        else
-            rc = b->jacobi ? launch_small_batch_jacobi(b->sc, b->desc_of(m), b->jac_of(m), b->count[m], m, b->lds_jac[m], b->hs, b->k, iters,
-                                                       meurant)
-                           : launch_small_batch(b->sc, b->desc_of(m), b->count[m], m, b->lds[m], b->hs, b->k, iters, meurant);
+        const SmallBatchArgs g{b->desc_of(m), b->jacobi ? b->jac_of(m) : nullptr, b->stopping ? b->stop_of(m) : nullptr, b->k, iters, meurant};
+        const int rc = launch_small_batch(b->sc, g, b->count[m], m, b->lds[m][b->jacobi], b->hs);
         if (rc < 0) return batch_fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
     }
     b->k += iters;

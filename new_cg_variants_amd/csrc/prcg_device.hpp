@@ -1,6 +1,6 @@
 // Device-side helpers shared by the kernel translation units of libprcg.so (gfx950 only).
-// Included by prcg_kernels.hip (CSR-adaptive tile kernels, vector updates) and prcg_win.hip
-// (row-per-lane window kernels).  Everything here is internal linkage on purpose.
+// Included by prcg_kernels.hip (CSR-adaptive tile kernels, vector updates), prcg_win.hip
+// (row-per-lane window kernels) and the other kernel files.  Everything here is internal linkage on purpose.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,6 +71,15 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for the wave's
+// outstanding GLOBAL stores (vmcnt(0)); thread 0 of the one-workgroup solvers (prcg_small.hip) streams the per-iteration scalars
+// to memory, and waiting for their acknowledgement twice per iteration cost ~3 us of a 4.5 us iteration.
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 
 template <int NV> struct VecT;

@@ -1,4 +1,5 @@
-// Launch wrappers of the gfx950 kernels (definitions: prcg_kernels.hip).
+// Launch wrappers of the gfx950 kernels (definitions: prcg_kernels.hip and, one file per kernel family, prcg_win.hip, prcg_sell.hip,
+// prcg_blockjac.hip, prcg_rhs2.hip, prcg_small.hip).
 // Internal to libprcg.so -- the public boundary is include/prcg.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -303,7 +304,7 @@ int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices,
 // the bytes plan_sell's fill pass would have produced from these values.  Reads A.indptr, A.rows and, for rows with skips, A.col16.
 int launch_sell_set_values(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* val_csr, double* sval);
 
-// ---- small systems: the whole pipelined solve in one launch of one workgroup -------------
+// ---- small systems: the whole solve in one launch of one workgroup (prcg_small.hip) -------------
 struct SmallArgs {
     int n, nnz;
     const int* indptr; const int* col; const double* val;
@@ -314,48 +315,44 @@ struct SmallArgs {
     int k0, iters, meurant;
     double* hs_p; double* hs_s;   // launch_small_hs: xp = x, rs = r, and the direction and its product
 };
-bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode);
+// The fit rule: true and *mode = 1 (matrix in registers) or 0 (matrix in LDS beside the vectors); jacobi: the need of the bodies
+// preconditioned by a diagonal scaling, which sum five inner products -- 128 B more LDS -- so a matrix in LDS may fit without
+// the scaling and not with it (the mode of one that fits both ways is the same).  small_lds_bytes: the dynamic LDS of one system.
+size_t small_lds_bytes(int n, int nnz, int mode, bool jacobi = false);
+bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, bool jacobi = false);
+// The single sessions.  The dynamic-LDS attribute of every kernel of the family is set, and its result checked, on first use on
+// each device: a launch fails (-1) where it could not be set.
 int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode);
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode);      // Hestenes-Stiefel, same storage
 // ---- a batch of small systems: the same solver, one workgroup per system, blockIdx.x selects the system (prcg_batch.cpp) ----
-// desc: `count` SmallArgs in DEVICE memory, all of one mode (k0, iters, meurant in them are ignored: the launch carries them);
-// lds: the largest small_lds_bytes(n, nnz, mode) among them -- each workgroup carves it by its own n and nnz.
+// desc: `count` SmallArgs in DEVICE memory, all of one mode (k0, iters, meurant in them are ignored: the launch carries them).
 // Results of a system are those of launch_small_pipe_pr / launch_small_hs with its descriptor, bit for bit, whatever its
-// position or company in the launch.  The dynamic-LDS attribute is set, and its result checked, on first use on each device.
-struct SmallInit { const double* b; const double* x0; };       // right-hand side and initial guess of one system
-size_t small_lds_bytes(int n, int nnz, int mode);
-int launch_small_batch(hipStream_t st, const SmallArgs* desc, int count, int mode, size_t lds, bool hs, int k0, int iters, int meurant);
-// x = x0, r = b - A x0, p = r, s = A p and row 0 of every system's scalars in ONE launch; init[i] belongs to desc[i].  The
-// vectors carry the bits of the single session's start-up launches; the inner products are summed in the order of the loop
-// (thread-sequential rows, wave butterfly, 16 waves), not of those launches.
-int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, int count, bool hs);
-// ---- the same batch, preconditioned by a diagonal scaling d = inv_diag applied inside the one-workgroup solver ----
-// What a Jacobi system holds beside its SmallArgs: the pairs (r~,s~) (pipelined only; read at entry, written at exit) and d.
-// jac[i] belongs to desc[i].  Pipelined: xp = (x,p), rs = (r,s), ts = (r~,s~); Hestenes-Stiefel: xp = x, rs = r, hs_p, hs_s, and
-// r~ = d r is formed anew in every iteration.  dots[k] = {mu, delta, gamma, nu, rr} (HS: {mu, -, -, nu, rr}), nu = r~.r, rr = r.r.
+// position or company in the launch.
+// jac (or null): the batch preconditioned by a diagonal scaling d = inv_diag applied inside the one-workgroup solver.  What a
+// Jacobi system holds beside its SmallArgs: the pairs (r~,s~) (pipelined only; read at entry, written at exit) and d.  jac[i]
+// belongs to desc[i].  Pipelined: xp = (x,p), rs = (r,s), ts = (r~,s~); Hestenes-Stiefel: xp = x, rs = r, hs_p, hs_s, and r~ = d r
+// is formed anew in every iteration.  dots[k] = {mu, delta, gamma, nu, rr} (HS: {mu, -, -, nu, rr}), nu = r~.r, rr = r.r.
 struct SmallJacobi { double* ts; const double* d; };
-// the preconditioned bodies sum five inner products: 128 B more LDS than small_lds_bytes
-size_t small_lds_bytes_jacobi(int n, int nnz, int mode);
-// small_fits with the preconditioned need: the same mode, or false where only the extra 128 B no longer fit
-bool small_fits_jacobi(int64_t n, int64_t nnz, int max_row_len, int* mode);
-// lds: the largest small_lds_bytes_jacobi among the launch's systems
-int launch_small_batch_jacobi(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, int count, int mode, size_t lds, bool hs,
-                              int k0, int iters, int meurant);
-// pipelined: x = x0, r = b - A x0, r~ = d r, p = r~, s = A p, s~ = d s; HS: r~ = d r, p = r~, s = A p; row 0 of the scalars in the loop's order
-int launch_small_batch_init_jacobi(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs);
-// ---- the same batches, every system stopped at its OWN residual threshold, decided inside its workgroup ----
-// stop[i] belongs to desc[i].  thr: a bound on r.r, finite and >= 0.  word: two ints in device memory, word[0] the iteration the
-// system stopped at (-1 while it runs), word[1] its status (0 running, 1 converged, 2 breakdown).  The rule, applied to row k of
-// the scalars (mu = dots[k][0], nu = dots[k][3], rr = dots[k][4]) after iteration k, and to row 0 by the launch with k0 == 0:
+// stop (or null): every system stopped at its OWN residual threshold, decided inside its workgroup.  stop[i] belongs to desc[i].
+// thr: a bound on r.r, finite and >= 0.  word: two ints in device memory, word[0] the iteration the system stopped at (-1 while
+// it runs), word[1] its status (0 running, 1 converged, 2 breakdown).  The rule, applied to row k of the scalars (mu = dots[k][0],
+// nu = dots[k][3], rr = dots[k][4]) after iteration k, and to row 0 by the launch with k0 == 0:
 //   rr <= thr -> converged;  else !(0 < mu < inf && 0 < nu < inf) -> breakdown (alpha = nu / mu is not an SPD system's);  else go on.
 // A system stopped at k holds the complete state of iteration k: its vectors, scalar rows 0..k, coefficient rows 1..k; later
 // rows are not written, and a later launch returns at once for it and stores nothing.  A system that never stops carries the
-// bits of launch_small_batch / launch_small_batch_jacobi.
+// bits of the launch without `stop`.
 struct SmallStop { double thr; int* word; };
-int launch_small_batch_stop(hipStream_t st, const SmallArgs* desc, const SmallStop* stop, int count, int mode, size_t lds, bool hs, int k0,
-                            int iters, int meurant);
-int launch_small_batch_jacobi_stop(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, const SmallStop* stop, int count, int mode,
-                                   size_t lds, bool hs, int k0, int iters, int meurant);
+// one launch of a batch: the arrays above (device memory) and where the session stands
+struct SmallBatchArgs { const SmallArgs* desc; const SmallJacobi* jac; const SmallStop* stop; int k0, iters, meurant; };
+// lds: the largest small_lds_bytes(n, nnz, mode, jac != null) among the launch's systems -- each workgroup carves it by its own
+// n and nnz
+int launch_small_batch(hipStream_t st, const SmallBatchArgs& g, int count, int mode, size_t lds, bool hs);
+// x = x0, r = b - A x0, [r~ = d r,] p = r~, s = A p [, pipelined: s~ = d s] and row 0 of every system's scalars in ONE launch;
+// init[i] belongs to desc[i]; jac null: no scaling (r~ is r).  The vectors carry the bits of the single session's start-up
+// launches; the inner products are summed in the order of the loop (thread-sequential rows, wave butterfly, 16 waves), not of
+// those launches.
+struct SmallInit { const double* b; const double* x0; };       // right-hand side and initial guess of one system
+int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs);
 
 // ---- fused vector updates + inner products -----------------------------------------
 struct PipeUpdateArgs {

@@ -658,764 +658,6 @@ __global__ __launch_bounds__(kBlock) void k_gv_update1(CgArgs a, int trips) {
     block_reduce_store<5>(acc, a.partials, 0);
 }
 
-// ======================================================================================
-// Small systems (n <= 4096): the whole pipelined solve in ONE launch of ONE workgroup.
-// nos7 (n=729) or bcsstk03 (n=112) cannot fill a chip; with one launch per kernel they are
-// launch-bound (~12 us per iteration).  Here 1024 threads keep (r,s) in LDS (double-buffered,
-// like the one-launch schedule above), x and p of their own rows in registers, the matrix
-// in registers or LDS, and iterate `iters` times with two
-// barriers per iteration.  Same arithmetic per element; rows are summed left to right.
-// Inner products: thread-sequential over its rows (row = tid, tid+1024, ...), wave butterfly,
-// 16 waves in order.  Every thread reaches every barrier (trip counts are uniform).
-// ======================================================================================
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for the wave's
-// outstanding GLOBAL stores (vmcnt(0)); thread 0 streams the per-iteration scalars to memory,
-// and waiting for their acknowledgement twice per iteration cost ~3 us of a 4.5 us iteration.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-static_assert(kPartialStride == 8, "k_small_pipe_pr indexes the scalar history (PRCG_NUM_SCALARS doubles per iteration) with kPartialStride");
-constexpr int kSmallThreads = 1024;
-constexpr int kSmallRows = 4;                    // rows per thread -> n <= 4096
-constexpr int kSmallMaxN = kSmallThreads * kSmallRows;
-
-// MODE 0: matrix in LDS (any row length, up to 4 rows per thread)
-// MODE 1: matrix in REGISTERS: n <= 1024 (one row per thread) and every row <= kSmallRegLen
-//         nonzeros -- the paper's small test matrices (nos7: rows of 4-7, bcsstk03: 4-6).
-constexpr int kSmallRegLen = 8;
-
-// ---- stopping a system of a batch at its OWN residual threshold: the STOP form of the four bodies (rule: prcg_kernels.h) ----
-// Every thread of the workgroup must take the same exit, or some waves would wait at a barrier the others never reach.  The
-// operands of the rule are the same bits in all 1024 threads: thr comes from a load of one address that the launch never
-// writes; mu, nu, rr are either loaded from one address (row k0 of the scalars, which the launch only reads) or results of
-// wave_sum16, in which EVERY wave sums the same 16 LDS partials by the same butterfly and broadcasts lane 0's bits.  (The stop
-// word: small_stop_entry.)  readfirstlane makes the verdict a scalar, so the branch on it is a scalar branch.
-__device__ __forceinline__ int small_stop_rule(double mu, double nu, double rr, double thr) {
-    const double inf = __builtin_huge_val();
-    int v = 0;
-    if (rr <= thr) v = 1;                                                        // converged
-    else if (!(0.0 < mu && mu < inf && 0.0 < nu && nu < inf)) v = 2;             // breakdown: a = nu / mu is not an SPD system's
-    return __builtin_amdgcn_readfirstlane(v);
-}
-// On entry, before the first barrier: true if this workgroup has nothing to do -- its system stopped in an earlier launch
-// (nothing is stored), or the session is at its start and the rule fires on row 0 (thread 0 records {0, status}; the state of
-// iteration 0 is already in memory).  b = 0 ends here: rr = 0 <= thr whatever mu is.  No barrier separates thread 0's store from
-// a later wave's load of the word: a wave that already sees {0, status} returns by the first test where it would have returned by
-// the rule -- the same exit either way.  Every other store to the word follows the body's barriers.
-__device__ __forceinline__ bool small_stop_entry(const SmallArgs& a, const SmallStop& st) {
-    if (__builtin_amdgcn_readfirstlane(st.word[0]) >= 0) return true;
-    if (a.k0 != 0) return false;
-    const int v = small_stop_rule(a.dots[0], a.dots[3], a.dots[4], st.thr);
-    if (v && threadIdx.x == 0) { st.word[0] = 0; st.word[1] = v; }
-    return v != 0;
-}
-// after the body's final stores: thread 0 records where and why the system stopped
-__device__ __forceinline__ void small_stop_record(const SmallStop& st, int k, int status) {
-    if (status && threadIdx.x == 0) { st.word[0] = k; st.word[1] = status; }
-}
-
-// The body is a device function of its argument: k_small_pipe_pr hands it the launch's SmallArgs, k_small_pipe_pr_batch the
-// descriptor of workgroup blockIdx.x -- one body, so that a system of a batch carries the single solver's bits.
-template <int MODE, bool STOP = false>
-__device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const SmallStop& stop = SmallStop{}) {
-    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
-    const int n = a.n, nnz = a.nnz;
-    double2* rsA = reinterpret_cast<double2*>(smem);
-    double2* rsB = rsA + n;
-    double* red = reinterpret_cast<double*>(rsB + n);          // [16 waves][4]
-    double* lval = red + 64;
-    int* lcol = reinterpret_cast<int*>(lval + (MODE == 0 ? nnz : 0));
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
-    const double2* __restrict__ XPg = reinterpret_cast<const double2*>(a.xp);
-    const double2* __restrict__ RSg = reinterpret_cast<const double2*>(a.rs);
-    double xr[ROWS], pr[ROWS];
-    int rbeg[ROWS], rend[ROWS];
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        xr[j] = 0.0; pr[j] = 0.0; rbeg[j] = 0; rend[j] = 0;
-        if (row < n) {
-            const double2 xp = XPg[row];
-            xr[j] = xp.x; pr[j] = xp.y;
-            rsA[row] = RSg[row];
-            rbeg[j] = a.indptr[row]; rend[j] = a.indptr[row + 1];
-        }
-    }
-    // MODE 1: this thread's row, padded with (0.0, own column) -- adding +-0.0 products at the
-    // END of the row sum cannot change it (x + 0.0 == x, and a finite entry times 0.0 is 0.0;
-    // inf/nan entries poison the row either way)... except that 0.0 * inf = nan: so padded
-    // slots are skipped by a length test instead of being multiplied.
-    double rv[kSmallRegLen];
-    int rc[kSmallRegLen];
-    int rlen = 0;
-    if constexpr (MODE == 1) {
-        rlen = rend[0] - rbeg[0];
-#pragma unroll
-        for (int q = 0; q < kSmallRegLen; ++q) {
-            const bool ok = q < rlen;
-            rv[q] = ok ? a.val[rbeg[0] + q] : 0.0;
-            rc[q] = ok ? a.col[rbeg[0] + q] : 0;
-        }
-    } else {
-        for (int q = tid; q < nnz; q += kSmallThreads) { lval[q] = a.val[q]; lcol[q] = a.col[q]; }
-    }
-    // inner products of the incoming state
-    double mu = a.dots[(size_t)a.k0 * kPartialStride + 0], dl = a.dots[(size_t)a.k0 * kPartialStride + 1];
-    double gm = a.dots[(size_t)a.k0 * kPartialStride + 2], nu = a.dots[(size_t)a.k0 * kPartialStride + 3];
-    __syncthreads();
-
-    double2* cur = rsA;
-    double2* nxt = rsB;
-    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
-    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
-    for (int it = 1; it <= a.iters; ++it) {
-        // coefficients (pipe_pr_cg.py:64-66,75), identical in every thread
-        const double al = nu / mu;
-        const double a2 = al * al;
-        const double nup = a.meurant ? (-nu + a2 * gm) : ((nu - (2 * al) * dl) + a2 * gm);
-        const double bt = nup / nu;
-        if (tid == 0) {
-            double* cf = a.coef + (size_t)(a.k0 + it) * 4;
-            cf[0] = al; cf[1] = bt; cf[2] = nup;
-        }
-        double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            const int row = tid + j * kSmallThreads;
-            if (row < n) {
-                double wr = 0.0, us = 0.0;                       // (A r)_i, (A s)_i, left to right
-                if constexpr (MODE == 1) {
-                    double2 g[kSmallRegLen];
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q) g[q] = cur[rc[q]];      // all gathers in flight
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q)
-                        if (q < rlen) { wr += rv[q] * g[q].x; us += rv[q] * g[q].y; }
-                } else {
-                    for (int q = rbeg[j]; q < rend[j]; ++q) {
-                        const double v = lval[q];
-                        const double2 g = cur[lcol[q]];
-                        wr += v * g.x; us += v * g.y;
-                    }
-                }
-                const double2 rs = cur[row];
-                xr[j] = xr[j] + al * pr[j];                      // x += a p
-                const double rn = rs.x - al * rs.y;              // r -= a s
-                const double wn = wr - al * us;                  // w -= a u
-                const double pn = rn + bt * pr[j];               // p = r + b p
-                const double sn = wn + bt * rs.y;                // s = w + b s
-                pr[j] = pn;
-                nxt[row] = make_double2(rn, sn);
-                acc0 += pn * sn; acc1 += rn * sn; acc2 += sn * sn; acc3 += rn * rn;
-            }
-        }
-        acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2); acc3 = wave_sum(acc3);
-        if (lane == 0) { red[wv * 4 + 0] = acc0; red[wv * 4 + 1] = acc1; red[wv * 4 + 2] = acc2; red[wv * 4 + 3] = acc3; }
-        lds_barrier();                                           // nxt complete, red complete
-        // 16 wave partials -> every wave sums them with the same butterfly (lanes 0..15 hold them)
-        mu = wave_sum16(red[(lane & 15) * 4 + 0]);
-        dl = wave_sum16(red[(lane & 15) * 4 + 1]);
-        gm = wave_sum16(red[(lane & 15) * 4 + 2]);
-        nu = wave_sum16(red[(lane & 15) * 4 + 3]);
-        if (tid == 0) {
-            double* d = a.dots + (size_t)(a.k0 + it) * kPartialStride;
-            d[0] = mu; d[1] = dl; d[2] = gm; d[3] = nu; d[4] = nu;
-        }
-        lds_barrier();                                           // everybody has read red before it is rewritten
-        double2* tmp = cur; cur = nxt; nxt = tmp;
-        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
-            stop_status = small_stop_rule(mu, nu, nu, stop_thr);
-            if (stop_status) { stop_k = a.k0 + it; break; }
-        }
-    }
-
-    double2* XPo = reinterpret_cast<double2*>(a.xp);
-    double2* RSo = reinterpret_cast<double2*>(a.rs);
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        if (row < n) { XPo[row] = make_double2(xr[j], pr[j]); RSo[row] = cur[row]; }
-    }
-    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { small_pipe_pr_body<MODE>(a); }
-
-// ---- Hestenes-Stiefel, the whole solve of a SMALL system in one launch of one workgroup (hs_cg.py:54-62) ----
-// BASELINE config 1 is bcsstk03 (n = 112) under hs_cg: two launches and two kernel boundaries per iteration cost it 9-10 us each.
-// Same storage as k_small_pipe_pr (matrix in registers or LDS, the gather source in LDS: here the direction p, double-buffered);
-// x, r, p, s of a thread's rows live in its registers.  Per iteration, with the expressions and roundings of k_hs_update_xr /
-// k_hs_update_p / the row sums of csr_matvec:  a = nu / mu;  x += a p;  r -= a s;  nu' = r.r;  b = nu' / nu;  p = r + b p;
-// s = A p;  mu = p.s  -- two workgroup-wide sums (the two reductions that make Hestenes-Stiefel what it is), three barriers.
-// Scalars as the launches leave them: dots[k] = {mu_k, -, -, nu_k, rr_k}, coef[k] = {a_k, b_k}.
-template <int MODE, bool STOP = false>
-__device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallStop& stop = SmallStop{}) {
-    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
-    const int n = a.n, nnz = a.nnz;
-    double* pA = reinterpret_cast<double*>(smem);
-    double* pB = pA + n;
-    double* red = pB + n + (n & 1);                              // [16 waves]
-    double* lval = red + 16;
-    int* lcol = reinterpret_cast<int*>(lval + (MODE == 0 ? nnz : 0));
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double xr[ROWS], rr_[ROWS], pr[ROWS], sr[ROWS];
-    int rbeg[ROWS], rend[ROWS];
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        xr[j] = 0.0; rr_[j] = 0.0; pr[j] = 0.0; sr[j] = 0.0; rbeg[j] = 0; rend[j] = 0;
-        if (row < n) {
-            xr[j] = a.xp[row]; rr_[j] = a.rs[row]; pr[j] = a.hs_p[row]; sr[j] = a.hs_s[row];
-            pA[row] = pr[j];
-            rbeg[j] = a.indptr[row]; rend[j] = a.indptr[row + 1];
-        }
-    }
-    double rv[kSmallRegLen];
-    int rc[kSmallRegLen];
-    int rlen = 0;
-    if constexpr (MODE == 1) {
-        rlen = rend[0] - rbeg[0];
-#pragma unroll
-        for (int q = 0; q < kSmallRegLen; ++q) {
-            const bool ok = q < rlen;
-            rv[q] = ok ? a.val[rbeg[0] + q] : 0.0;
-            rc[q] = ok ? a.col[rbeg[0] + q] : 0;
-        }
-    } else {
-        for (int q = tid; q < nnz; q += kSmallThreads) { lval[q] = a.val[q]; lcol[q] = a.col[q]; }
-    }
-    double mu = a.dots[(size_t)a.k0 * kPartialStride + 0], nu = a.dots[(size_t)a.k0 * kPartialStride + 3];
-    __syncthreads();
-
-    double* cur = pA;                                            // holds p_{k-1}
-    double* nxt = pB;
-    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
-    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
-    for (int it = 1; it <= a.iters; ++it) {
-        const double al = nu / mu;                               // a = nu / mu                       hs_cg.py:55
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            if (tid + j * kSmallThreads < n) {
-                xr[j] = xr[j] + al * pr[j];                      // x += a p
-                rr_[j] = rr_[j] - al * sr[j];                    // r -= a s
-                acc += rr_[j] * rr_[j];
-            }
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) red[wv] = acc;
-        lds_barrier();
-        const double nun = wave_sum16(red[lane & 15]);           // nu' = r.r                          :58
-        const double bt = nun / nu;                              // b = nu' / nu                       :59
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            const int row = tid + j * kSmallThreads;
-            if (row < n) { pr[j] = rr_[j] + bt * pr[j]; nxt[row] = pr[j]; }     // p = r + b p           :60
-        }
-        lds_barrier();                                           // the new direction is complete (and red has been read)
-        double accm = 0.0;
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            const int row = tid + j * kSmallThreads;
-            if (row < n) {
-                double sp = 0.0;                                 // (A p)_i, left to right
-                if constexpr (MODE == 1) {
-                    double g[kSmallRegLen];
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q) g[q] = nxt[rc[q]];
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q)
-                        if (q < rlen) sp += rv[q] * g[q];
-                } else {
-                    for (int q = rbeg[j]; q < rend[j]; ++q) sp += lval[q] * nxt[lcol[q]];
-                }
-                sr[j] = sp;                                      // s = A p                            :61
-                accm += pr[j] * sp;
-            }
-        }
-        accm = wave_sum(accm);
-        if (lane == 0) red[wv] = accm;
-        lds_barrier();
-        mu = wave_sum16(red[lane & 15]);                         // mu = p.s                           :62
-        if (tid == 0) {
-            double* cf = a.coef + (size_t)(a.k0 + it) * 4;
-            cf[0] = al; cf[1] = bt;
-            double* d = a.dots + (size_t)(a.k0 + it) * kPartialStride;
-            d[0] = mu; d[3] = nun; d[4] = nun;
-        }
-        nu = nun;
-        lds_barrier();                                           // everybody has read red before it is rewritten
-        double* tmp = cur; cur = nxt; nxt = tmp;
-        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
-            stop_status = small_stop_rule(mu, nu, nu, stop_thr);
-            if (stop_status) { stop_k = a.k0 + it; break; }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        if (row < n) { a.xp[row] = xr[j]; a.rs[row] = rr_[j]; a.hs_p[row] = pr[j]; a.hs_s[row] = sr[j]; }
-    }
-    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small_hs_body<MODE>(a); }
-
-// ---- the one-workgroup solvers preconditioned by a diagonal scaling d (Jacobi: d = 1 / diag A), pipe_pr_cg.py:109-193 ----
-// Storage of small_pipe_pr_body with one more pair: LDS holds (r~,s~), double-buffered -- the gather source, as (r,s) is
-// there --; a thread keeps x, p, r, s and d of its own rows in registers.  Per row (A r~)_i and (A s~)_i are summed left to
-// right from +0.0, then the expressions and order of fused_row_update<true, true> (prcg_device.hpp) with w = A r~ recomputed.
-// Five sums per iteration: mu = p.s, delta = r.s~, gamma = s~.s, nu = r~.r, rr = r.r, in the order of the unpreconditioned
-// body (thread-sequential rows, wave butterfly, 16 waves): red is [16 waves][5].  Still two barriers per iteration.
-// dots[k] = {mu, delta, gamma, nu, rr}, coef[k] = {al, bt, nu_pred}.
-template <int MODE, bool STOP = false>
-__device__ __forceinline__ void small_pipe_pr_pcg_body(const SmallArgs& a, const SmallJacobi& jc, const SmallStop& stop = SmallStop{}) {
-    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
-    const int n = a.n, nnz = a.nnz;
-    double2* tsA = reinterpret_cast<double2*>(smem);
-    double2* tsB = tsA + n;
-    double* red = reinterpret_cast<double*>(tsB + n);          // [16 waves][5]
-    double* lval = red + 80;
-    int* lcol = reinterpret_cast<int*>(lval + (MODE == 0 ? nnz : 0));
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
-    const double2* __restrict__ XPg = reinterpret_cast<const double2*>(a.xp);
-    const double2* __restrict__ RSg = reinterpret_cast<const double2*>(a.rs);
-    const double2* __restrict__ TSg = reinterpret_cast<const double2*>(jc.ts);
-    double xr[ROWS], pr[ROWS], rr_[ROWS], sr[ROWS], dr[ROWS];
-    int rbeg[ROWS], rend[ROWS];
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        xr[j] = 0.0; pr[j] = 0.0; rr_[j] = 0.0; sr[j] = 0.0; dr[j] = 0.0; rbeg[j] = 0; rend[j] = 0;
-        if (row < n) {
-            const double2 xp = XPg[row];
-            const double2 rs = RSg[row];
-            xr[j] = xp.x; pr[j] = xp.y; rr_[j] = rs.x; sr[j] = rs.y; dr[j] = jc.d[row];
-            tsA[row] = TSg[row];
-            rbeg[j] = a.indptr[row]; rend[j] = a.indptr[row + 1];
-        }
-    }
-    double rv[kSmallRegLen];                                     // MODE 1: this thread's row (padded slots skipped by a length test)
-    int rc[kSmallRegLen];
-    int rlen = 0;
-    if constexpr (MODE == 1) {
-        rlen = rend[0] - rbeg[0];
-#pragma unroll
-        for (int q = 0; q < kSmallRegLen; ++q) {
-            const bool ok = q < rlen;
-            rv[q] = ok ? a.val[rbeg[0] + q] : 0.0;
-            rc[q] = ok ? a.col[rbeg[0] + q] : 0;
-        }
-    } else {
-        for (int q = tid; q < nnz; q += kSmallThreads) { lval[q] = a.val[q]; lcol[q] = a.col[q]; }
-    }
-    double mu = a.dots[(size_t)a.k0 * kPartialStride + 0], dl = a.dots[(size_t)a.k0 * kPartialStride + 1];
-    double gm = a.dots[(size_t)a.k0 * kPartialStride + 2], nu = a.dots[(size_t)a.k0 * kPartialStride + 3];
-    __syncthreads();
-
-    double2* cur = tsA;
-    double2* nxt = tsB;
-    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
-    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
-    for (int it = 1; it <= a.iters; ++it) {
-        // coefficients (pipe_pr_cg.py:174-175,187), identical in every thread
-        const double al = nu / mu;
-        const double a2 = al * al;
-        const double nup = a.meurant ? (-nu + a2 * gm) : ((nu - (2 * al) * dl) + a2 * gm);
-        const double bt = nup / nu;
-        if (tid == 0) {
-            double* cf = a.coef + (size_t)(a.k0 + it) * 4;
-            cf[0] = al; cf[1] = bt; cf[2] = nup;
-        }
-        double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, acc4 = 0.0;
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            const int row = tid + j * kSmallThreads;
-            if (row < n) {
-                double wr = 0.0, us = 0.0;                       // (A r~)_i, (A s~)_i, left to right
-                if constexpr (MODE == 1) {
-                    double2 g[kSmallRegLen];
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q) g[q] = cur[rc[q]];      // all gathers in flight
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q)
-                        if (q < rlen) { wr += rv[q] * g[q].x; us += rv[q] * g[q].y; }
-                } else {
-                    for (int q = rbeg[j]; q < rend[j]; ++q) {
-                        const double v = lval[q];
-                        const double2 g = cur[lcol[q]];
-                        wr += v * g.x; us += v * g.y;
-                    }
-                }
-                const double2 ts = cur[row];
-                const double ut = dr[j] * us;                    // u~ = M^-1 u
-                const double wt = dr[j] * wr;                    // w~ = M^-1 w
-                xr[j] = xr[j] + al * pr[j];                      // x += a p
-                const double rn = rr_[j] - al * sr[j];           // r -= a s
-                const double rtn = ts.x - al * ts.y;             // r~ -= a s~
-                const double wn = wr - al * us;                  // w -= a u
-                const double wtn = wt - al * ut;                 // w~ -= a u~
-                const double pn = rtn + bt * pr[j];              // p = r~ + b p
-                const double sn = wn + bt * sr[j];               // s = w + b s
-                const double stn = wtn + bt * ts.y;              // s~ = w~ + b s~
-                pr[j] = pn; rr_[j] = rn; sr[j] = sn;
-                nxt[row] = make_double2(rtn, stn);
-                acc0 += pn * sn; acc1 += rn * stn; acc2 += stn * sn; acc3 += rtn * rn; acc4 += rn * rn;
-            }
-        }
-        acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2); acc3 = wave_sum(acc3); acc4 = wave_sum(acc4);
-        if (lane == 0) {
-            red[wv * 5 + 0] = acc0; red[wv * 5 + 1] = acc1; red[wv * 5 + 2] = acc2; red[wv * 5 + 3] = acc3; red[wv * 5 + 4] = acc4;
-        }
-        lds_barrier();                                           // nxt complete, red complete
-        mu = wave_sum16(red[(lane & 15) * 5 + 0]);
-        dl = wave_sum16(red[(lane & 15) * 5 + 1]);
-        gm = wave_sum16(red[(lane & 15) * 5 + 2]);
-        nu = wave_sum16(red[(lane & 15) * 5 + 3]);
-        const double rr = wave_sum16(red[(lane & 15) * 5 + 4]);
-        if (tid == 0) {
-            double* d = a.dots + (size_t)(a.k0 + it) * kPartialStride;
-            d[0] = mu; d[1] = dl; d[2] = gm; d[3] = nu; d[4] = rr;
-        }
-        lds_barrier();                                           // everybody has read red before it is rewritten
-        double2* tmp = cur; cur = nxt; nxt = tmp;
-        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
-            stop_status = small_stop_rule(mu, nu, rr, stop_thr);
-            if (stop_status) { stop_k = a.k0 + it; break; }
-        }
-    }
-
-    double2* XPo = reinterpret_cast<double2*>(a.xp);
-    double2* RSo = reinterpret_cast<double2*>(a.rs);
-    double2* TSo = reinterpret_cast<double2*>(jc.ts);
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        if (row < n) { XPo[row] = make_double2(xr[j], pr[j]); RSo[row] = make_double2(rr_[j], sr[j]); TSo[row] = cur[row]; }
-    }
-    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
-}
-
-// Hestenes-Stiefel with the same scaling (hs_cg.py:70-131): small_hs_body with r~ = d r formed in registers after r -= a s.
-// The first reduction point carries two sums, nu' = r.r~ and rr = r.r (red is [16 waves][2]); b = nu' / nu; p = r~ + b p;
-// s = A p; mu = p.s.  The barriers of small_hs_body.  dots[k] = {mu, -, -, nu, rr}, coef[k] = {a, b}.
-template <int MODE, bool STOP = false>
-__device__ __forceinline__ void small_hs_pcg_body(const SmallArgs& a, const SmallJacobi& jc, const SmallStop& stop = SmallStop{}) {
-    if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int ROWS = MODE == 1 ? 1 : kSmallRows;
-    const int n = a.n, nnz = a.nnz;
-    double* pA = reinterpret_cast<double*>(smem);
-    double* pB = pA + n;
-    double* red = pB + n + (n & 1);                              // [16 waves][2]
-    double* lval = red + 32;
-    int* lcol = reinterpret_cast<int*>(lval + (MODE == 0 ? nnz : 0));
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double xr[ROWS], rr_[ROWS], pr[ROWS], sr[ROWS], dr[ROWS];
-    int rbeg[ROWS], rend[ROWS];
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        xr[j] = 0.0; rr_[j] = 0.0; pr[j] = 0.0; sr[j] = 0.0; dr[j] = 0.0; rbeg[j] = 0; rend[j] = 0;
-        if (row < n) {
-            xr[j] = a.xp[row]; rr_[j] = a.rs[row]; pr[j] = a.hs_p[row]; sr[j] = a.hs_s[row]; dr[j] = jc.d[row];
-            pA[row] = pr[j];
-            rbeg[j] = a.indptr[row]; rend[j] = a.indptr[row + 1];
-        }
-    }
-    double rv[kSmallRegLen];
-    int rc[kSmallRegLen];
-    int rlen = 0;
-    if constexpr (MODE == 1) {
-        rlen = rend[0] - rbeg[0];
-#pragma unroll
-        for (int q = 0; q < kSmallRegLen; ++q) {
-            const bool ok = q < rlen;
-            rv[q] = ok ? a.val[rbeg[0] + q] : 0.0;
-            rc[q] = ok ? a.col[rbeg[0] + q] : 0;
-        }
-    } else {
-        for (int q = tid; q < nnz; q += kSmallThreads) { lval[q] = a.val[q]; lcol[q] = a.col[q]; }
-    }
-    double mu = a.dots[(size_t)a.k0 * kPartialStride + 0], nu = a.dots[(size_t)a.k0 * kPartialStride + 3];
-    __syncthreads();
-
-    double* cur = pA;                                            // holds p_{k-1}
-    double* nxt = pB;
-    int stop_k = 0, stop_status = 0;                             // STOP: where and why the loop was left early
-    const double stop_thr = stop.thr;                            // (read once: the loop's stores could alias the descriptor)
-    for (int it = 1; it <= a.iters; ++it) {
-        const double al = nu / mu;                               // a = nu / mu                       hs_cg.py:116
-        double rt[ROWS];
-        double acc = 0.0, accr = 0.0;
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            rt[j] = 0.0;
-            if (tid + j * kSmallThreads < n) {
-                xr[j] = xr[j] + al * pr[j];                      // x += a p
-                rr_[j] = rr_[j] - al * sr[j];                    // r -= a s
-                rt[j] = dr[j] * rr_[j];                          // r~ = M^-1 r                        :118
-                acc += rr_[j] * rt[j];
-                accr += rr_[j] * rr_[j];
-            }
-        }
-        acc = wave_sum(acc); accr = wave_sum(accr);
-        if (lane == 0) { red[wv * 2 + 0] = acc; red[wv * 2 + 1] = accr; }
-        lds_barrier();
-        const double nun = wave_sum16(red[(lane & 15) * 2 + 0]); // nu' = r.r~                         :119
-        const double rrn = wave_sum16(red[(lane & 15) * 2 + 1]); // rr = r.r
-        const double bt = nun / nu;                              // b = nu' / nu
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            const int row = tid + j * kSmallThreads;
-            if (row < n) { pr[j] = rt[j] + bt * pr[j]; nxt[row] = pr[j]; }      // p = r~ + b p
-        }
-        lds_barrier();                                           // the new direction is complete (and red has been read)
-        double accm = 0.0;
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            const int row = tid + j * kSmallThreads;
-            if (row < n) {
-                double sp = 0.0;                                 // (A p)_i, left to right
-                if constexpr (MODE == 1) {
-                    double g[kSmallRegLen];
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q) g[q] = nxt[rc[q]];
-#pragma unroll
-                    for (int q = 0; q < kSmallRegLen; ++q)
-                        if (q < rlen) sp += rv[q] * g[q];
-                } else {
-                    for (int q = rbeg[j]; q < rend[j]; ++q) sp += lval[q] * nxt[lcol[q]];
-                }
-                sr[j] = sp;                                      // s = A p
-                accm += pr[j] * sp;
-            }
-        }
-        accm = wave_sum(accm);
-        if (lane == 0) red[wv * 2 + 0] = accm;
-        lds_barrier();
-        mu = wave_sum16(red[(lane & 15) * 2 + 0]);               // mu = p.s
-        if (tid == 0) {
-            double* cf = a.coef + (size_t)(a.k0 + it) * 4;
-            cf[0] = al; cf[1] = bt;
-            double* d = a.dots + (size_t)(a.k0 + it) * kPartialStride;
-            d[0] = mu; d[3] = nun; d[4] = rrn;
-        }
-        nu = nun;
-        lds_barrier();                                           // everybody has read red before it is rewritten
-        double* tmp = cur; cur = nxt; nxt = tmp;
-        if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
-            stop_status = small_stop_rule(mu, nu, rrn, stop_thr);
-            if (stop_status) { stop_k = a.k0 + it; break; }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int row = tid + j * kSmallThreads;
-        if (row < n) { a.xp[row] = xr[j]; a.rs[row] = rr_[j]; a.hs_p[row] = pr[j]; a.hs_s[row] = sr[j]; }
-    }
-    if constexpr (STOP) small_stop_record(stop, stop_k, stop_status);
-}
-
-// ---- a BATCH of small systems: one launch, workgroup blockIdx.x solves system desc[blockIdx.x] (prcg_batch.cpp) ----
-// The descriptors live in device memory, one SmallArgs per system with pointers into the batch's concatenated matrix, state,
-// scalar and coefficient buffers; blockIdx.x is uniform, so a workgroup reads its descriptor with uniform loads.  Where the
-// session stands (k0, iters, meurant) is the same for every system and comes with the launch.  Each workgroup carves the
-// launch's dynamic LDS by its OWN n and nnz (the bodies do), so a system's bits do not depend on its neighbours in the launch.
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_batch(const SmallArgs* __restrict__ desc, int k0, int iters, int meurant) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = meurant;
-    small_pipe_pr_body<MODE>(a);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs_batch(const SmallArgs* __restrict__ desc, int k0, int iters) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = 0;
-    small_hs_body<MODE>(a);
-}
-
-// Initial state of every system of a batch in ONE launch (pipe_pr_cg.py:22-28, hs_cg.py:22-27), workgroup blockIdx.x for system
-// desc[blockIdx.x]:  x = x0;  r = b - A x0;  p = r;  s = A p  -- row sums left to right from +0.0 and the expressions of the
-// single session's start-up launches, so the four vectors carry its bits -- and the inner products of row 0 of the scalars
-// (pipelined: mu = p.s, delta = r.s, gamma = s.s, nu = rr = r.r; Hestenes-Stiefel: mu, nu = rr), summed in the order of the LOOP:
-// thread-sequential over rows tid, tid + 1024, ..., wave butterfly, 16 waves.  (The single session sums its initial products in
-// the order of its start-up launches: row 0 may differ from it in the last bit.)  The matrix is read from memory: once.
-template <bool HS>
-__global__ __launch_bounds__(kSmallThreads) void k_small_batch_init(const SmallArgs* __restrict__ desc, const SmallInit* __restrict__ init) {
-    __shared__ double rl[kSmallMaxN];                            // r (= p): the source of s = A p
-    __shared__ double red[64];                                   // [16 waves][4]
-    const SmallArgs a = desc[blockIdx.x];
-    const SmallInit in = init[blockIdx.x];
-    const int n = a.n;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double xr[kSmallRows], rr_[kSmallRows];
-#pragma unroll
-    for (int j = 0; j < kSmallRows; ++j) {
-        const int row = tid + j * kSmallThreads;
-        xr[j] = 0.0; rr_[j] = 0.0;
-        if (row < n) {
-            double t = 0.0;                                      // (A x0)_i, left to right
-            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) t += a.val[q] * in.x0[a.col[q]];
-            xr[j] = in.x0[row];                                  // x = x0
-            rr_[j] = in.b[row] - t;                              // r = b - A x
-            rl[row] = rr_[j];
-        }
-    }
-    __syncthreads();
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-#pragma unroll
-    for (int j = 0; j < kSmallRows; ++j) {
-        const int row = tid + j * kSmallThreads;
-        if (row < n) {
-            double sp = 0.0;                                     // (A p)_i, p = r, left to right
-            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) sp += a.val[q] * rl[a.col[q]];
-            const double rn = rr_[j];
-            if constexpr (HS) {
-                a.xp[row] = xr[j]; a.rs[row] = rn; a.hs_p[row] = rn; a.hs_s[row] = sp;
-            } else {
-                reinterpret_cast<double2*>(a.xp)[row] = make_double2(xr[j], rn);
-                reinterpret_cast<double2*>(a.rs)[row] = make_double2(rn, sp);
-            }
-            acc0 += rn * sp; acc1 += rn * sp; acc2 += sp * sp; acc3 += rn * rn;      // p.s, r.s (p = r), s.s, r.r
-        }
-    }
-    acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2); acc3 = wave_sum(acc3);
-    if (lane == 0) { red[wv * 4 + 0] = acc0; red[wv * 4 + 1] = acc1; red[wv * 4 + 2] = acc2; red[wv * 4 + 3] = acc3; }
-    __syncthreads();
-    const double mu = wave_sum16(red[(lane & 15) * 4 + 0]);
-    const double dl = wave_sum16(red[(lane & 15) * 4 + 1]);
-    const double gm = wave_sum16(red[(lane & 15) * 4 + 2]);
-    const double nu = wave_sum16(red[(lane & 15) * 4 + 3]);
-    if (tid == 0) {
-        double* d = a.dots;                                      // row 0
-        d[0] = mu; d[3] = nu; d[4] = nu;
-        if constexpr (!HS) { d[1] = dl; d[2] = gm; }
-    }
-}
-
-// ---- the batch preconditioned by a diagonal scaling: jac[blockIdx.x] belongs to desc[blockIdx.x] ----
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_pcg_batch(const SmallArgs* __restrict__ desc, const SmallJacobi* __restrict__ jac,
-                                                                           int k0, int iters, int meurant) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = meurant;
-    small_pipe_pr_pcg_body<MODE>(a, jac[blockIdx.x]);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs_pcg_batch(const SmallArgs* __restrict__ desc, const SmallJacobi* __restrict__ jac,
-                                                                      int k0, int iters) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = 0;
-    small_hs_pcg_body<MODE>(a, jac[blockIdx.x]);
-}
-
-// ---- the batches with a stop: stop[blockIdx.x] belongs to desc[blockIdx.x]; the STOP form of the same four bodies ----
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_batch_stop(const SmallArgs* __restrict__ desc, const SmallStop* __restrict__ stop,
-                                                                            int k0, int iters, int meurant) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = meurant;
-    small_pipe_pr_body<MODE, true>(a, stop[blockIdx.x]);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs_batch_stop(const SmallArgs* __restrict__ desc, const SmallStop* __restrict__ stop,
-                                                                       int k0, int iters) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = 0;
-    small_hs_body<MODE, true>(a, stop[blockIdx.x]);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_pcg_batch_stop(const SmallArgs* __restrict__ desc, const SmallJacobi* __restrict__ jac,
-                                                                                const SmallStop* __restrict__ stop, int k0, int iters, int meurant) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = meurant;
-    small_pipe_pr_pcg_body<MODE, true>(a, jac[blockIdx.x], stop[blockIdx.x]);
-}
-template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs_pcg_batch_stop(const SmallArgs* __restrict__ desc, const SmallJacobi* __restrict__ jac,
-                                                                           const SmallStop* __restrict__ stop, int k0, int iters) {
-    SmallArgs a = desc[blockIdx.x];
-    a.k0 = k0; a.iters = iters; a.meurant = 0;
-    small_hs_pcg_body<MODE, true>(a, jac[blockIdx.x], stop[blockIdx.x]);
-}
-
-// k_small_batch_init with the scaling (pipe_pr_cg.py:122-140, hs_cg.py:84-90):  x = x0;  r = b - A x0;  r~ = d r;  p = r~;  s = A p;
-// pipelined also s~ = d s.  Row 0 of the scalars, summed in the loop's order: pipelined {p.s, r.s~, s~.s, r~.r, r.r},
-// Hestenes-Stiefel {p.s, -, -, r~.r, r.r}.
-template <bool HS>
-__global__ __launch_bounds__(kSmallThreads) void k_small_batch_init_jacobi(const SmallArgs* __restrict__ desc, const SmallInit* __restrict__ init,
-                                                                           const SmallJacobi* __restrict__ jac) {
-    __shared__ double pl[kSmallMaxN];                            // p (= r~): the source of s = A p
-    __shared__ double red[80];                                   // [16 waves][5]
-    const SmallArgs a = desc[blockIdx.x];
-    const SmallInit in = init[blockIdx.x];
-    const SmallJacobi jc = jac[blockIdx.x];
-    const int n = a.n;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double xr[kSmallRows], rr_[kSmallRows], rt[kSmallRows];
-#pragma unroll
-    for (int j = 0; j < kSmallRows; ++j) {
-        const int row = tid + j * kSmallThreads;
-        xr[j] = 0.0; rr_[j] = 0.0; rt[j] = 0.0;
-        if (row < n) {
-            double t = 0.0;                                      // (A x0)_i, left to right
-            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) t += a.val[q] * in.x0[a.col[q]];
-            xr[j] = in.x0[row];                                  // x = x0
-            rr_[j] = in.b[row] - t;                              // r = b - A x
-            rt[j] = jc.d[row] * rr_[j];                          // r~ = M^-1 r
-            pl[row] = rt[j];
-        }
-    }
-    __syncthreads();
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, acc4 = 0.0;
-#pragma unroll
-    for (int j = 0; j < kSmallRows; ++j) {
-        const int row = tid + j * kSmallThreads;
-        if (row < n) {
-            double sp = 0.0;                                     // (A p)_i, p = r~, left to right
-            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) sp += a.val[q] * pl[a.col[q]];
-            const double rn = rr_[j], pn = rt[j];
-            if constexpr (HS) {
-                a.xp[row] = xr[j]; a.rs[row] = rn; a.hs_p[row] = pn; a.hs_s[row] = sp;
-            } else {
-                const double stn = jc.d[row] * sp;               // s~ = M^-1 s
-                reinterpret_cast<double2*>(a.xp)[row] = make_double2(xr[j], pn);
-                reinterpret_cast<double2*>(a.rs)[row] = make_double2(rn, sp);
-                reinterpret_cast<double2*>(jc.ts)[row] = make_double2(pn, stn);
-                acc1 += rn * stn; acc2 += stn * sp;              // r.s~, s~.s
-            }
-            acc0 += pn * sp; acc3 += pn * rn; acc4 += rn * rn;   // p.s, r~.r, r.r
-        }
-    }
-    acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2); acc3 = wave_sum(acc3); acc4 = wave_sum(acc4);
-    if (lane == 0) {
-        red[wv * 5 + 0] = acc0; red[wv * 5 + 1] = acc1; red[wv * 5 + 2] = acc2; red[wv * 5 + 3] = acc3; red[wv * 5 + 4] = acc4;
-    }
-    __syncthreads();
-    const double mu = wave_sum16(red[(lane & 15) * 5 + 0]);
-    const double dl = wave_sum16(red[(lane & 15) * 5 + 1]);
-    const double gm = wave_sum16(red[(lane & 15) * 5 + 2]);
-    const double nu = wave_sum16(red[(lane & 15) * 5 + 3]);
-    const double rr = wave_sum16(red[(lane & 15) * 5 + 4]);
-    if (tid == 0) {
-        double* d = a.dots;                                      // row 0
-        d[0] = mu; d[3] = nu; d[4] = rr;
-        if constexpr (!HS) { d[1] = dl; d[2] = gm; }
-    }
-}
-
 // ---- fixed-order final reduction of per-block partials --------------------------------
 constexpr int kFinalThreads = 256;   // same tree as the fused last-block reduction
 __global__ __launch_bounds__(kFinalThreads) void k_reduce_final(
@@ -1763,160 +1005,6 @@ int launch_pipe_fused(hipStream_t st, const CsrDev& A, const Tile* tiles, int nt
                                                     f.in_new, f.partials, kn, f.coef_out, fz);
     return launch_tiles_steps<2, kEpiPipeFusedP>(steps, st, A, tiles, ntiles, f.in_old, f.xp, mask, f.dots_prev, nullptr,
                                                  f.in_new, f.partials, kn, f.coef_out, fz);
-}
-
-size_t small_lds_bytes(int n, int nnz, int mode) {
-    return (size_t)2 * n * 16 + 64 * 8 + (mode == 0 ? (size_t)nnz * 12 + 16 : 0);
-}
-// mode 1 (matrix in registers) if n <= 1024 and the longest row has <= 8 nonzeros; mode 0
-// (matrix in LDS) if it fits beside the vectors; otherwise the multi-launch schedule is
-// faster (measured: bcsstk14, 63 k nonzeros re-read through L2 by one CU: 58 us/iteration).
-constexpr size_t kSmallLdsCap = 156 * 1024;
-bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode) {
-    if (n < 1 || n > kSmallMaxN) return false;
-    if (n <= kSmallThreads && max_row_len <= kSmallRegLen) { *mode = 1; return true; }
-    const size_t cap = kSmallLdsCap;
-    if (nnz < (1 << 20) && small_lds_bytes((int)n, (int)nnz, 0) <= cap && max_row_len <= 64) { *mode = 0; return true; }
-    return false;
-}
-// the preconditioned bodies: red is [16][5] instead of [16][4]
-size_t small_lds_bytes_jacobi(int n, int nnz, int mode) { return small_lds_bytes(n, nnz, mode) + 16 * 8; }
-bool small_fits_jacobi(int64_t n, int64_t nnz, int max_row_len, int* mode) {
-    if (!small_fits(n, nnz, max_row_len, mode)) return false;
-    return *mode == 1 || small_lds_bytes_jacobi((int)n, (int)nnz, 0) <= kSmallLdsCap;
-}
-// (xp = x, rs = r, hs_p = p, hs_s = s: separate arrays, as the Hestenes-Stiefel sessions hold them)
-int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode) {
-    const size_t lds = small_lds_bytes(a.n, a.nnz, mode);        // (sized for the pipelined solver's pairs: more than the directions need)
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_hs<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_hs<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
-    if (mode == 1) hipLaunchKernelGGL(k_small_hs<1>, dim3(1), dim3(kSmallThreads), lds, st, a);
-    else hipLaunchKernelGGL(k_small_hs<0>, dim3(1), dim3(kSmallThreads), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 1 : -1;
-}
-int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode) {
-    const size_t lds = small_lds_bytes(a.n, a.nnz, mode);
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_pipe_pr<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_pipe_pr<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
-    if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr<1>, dim3(1), dim3(kSmallThreads), lds, st, a);
-    else hipLaunchKernelGGL(k_small_pipe_pr<0>, dim3(1), dim3(kSmallThreads), lds, st, a);
-    return PRCG_LAUNCH_OK() ? 1 : -1;
-}
-
-// ---- batch of small systems: `count` workgroups, one per descriptor (all of one mode; lds: the largest small_lds_bytes among them)
-int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, int count, bool hs) {
-    if (hs) hipLaunchKernelGGL(k_small_batch_init<true>, dim3(count), dim3(kSmallThreads), 0, st, desc, init);
-    else hipLaunchKernelGGL(k_small_batch_init<false>, dim3(count), dim3(kSmallThreads), 0, st, desc, init);
-    return PRCG_LAUNCH_OK() ? count : -1;
-}
-int launch_small_batch(hipStream_t st, const SmallArgs* desc, int count, int mode, size_t lds, bool hs, int k0, int iters, int meurant) {
-    // the kernels may ask for more dynamic LDS than the default 64 KB.  The attribute belongs to the CURRENT device: set once per
-    // device, and only a SUCCESSFUL call counts as done
-    constexpr int kMaxDev = 64;
-    static bool attr_done[kMaxDev] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
-    if (dev >= kMaxDev || !attr_done[dev]) {
-        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_batch<0>), reinterpret_cast<const void*>(k_small_pipe_pr_batch<1>),
-                              reinterpret_cast<const void*>(k_small_hs_batch<0>), reinterpret_cast<const void*>(k_small_hs_batch<1>)};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-        if (dev < kMaxDev) attr_done[dev] = true;
-    }
-    if (hs) {
-        if (mode == 1) hipLaunchKernelGGL(k_small_hs_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters);
-        else hipLaunchKernelGGL(k_small_hs_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters);
-    } else {
-        if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters, meurant);
-        else hipLaunchKernelGGL(k_small_pipe_pr_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, k0, iters, meurant);
-    }
-    return PRCG_LAUNCH_OK() ? count : -1;
-}
-
-int launch_small_batch_init_jacobi(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs) {
-    if (hs) hipLaunchKernelGGL(k_small_batch_init_jacobi<true>, dim3(count), dim3(kSmallThreads), 0, st, desc, init, jac);
-    else hipLaunchKernelGGL(k_small_batch_init_jacobi<false>, dim3(count), dim3(kSmallThreads), 0, st, desc, init, jac);
-    return PRCG_LAUNCH_OK() ? count : -1;
-}
-int launch_small_batch_jacobi(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, int count, int mode, size_t lds, bool hs,
-                              int k0, int iters, int meurant) {
-    // the dynamic-LDS attribute, per device and checked, as in launch_small_batch
-    constexpr int kMaxDev = 64;
-    static bool attr_done[kMaxDev] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
-    if (dev >= kMaxDev || !attr_done[dev]) {
-        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_pcg_batch<0>), reinterpret_cast<const void*>(k_small_pipe_pr_pcg_batch<1>),
-                              reinterpret_cast<const void*>(k_small_hs_pcg_batch<0>), reinterpret_cast<const void*>(k_small_hs_pcg_batch<1>)};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-        if (dev < kMaxDev) attr_done[dev] = true;
-    }
-    if (hs) {
-        if (mode == 1) hipLaunchKernelGGL(k_small_hs_pcg_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, k0, iters);
-        else hipLaunchKernelGGL(k_small_hs_pcg_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, k0, iters);
-    } else {
-        if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, k0, iters, meurant);
-        else hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, k0, iters, meurant);
-    }
-    return PRCG_LAUNCH_OK() ? count : -1;
-}
-
-// ---- the two batch launchers with a per-system stop (SmallStop, prcg_kernels.h): the dynamic-LDS attribute as above ----
-int launch_small_batch_stop(hipStream_t st, const SmallArgs* desc, const SmallStop* stop, int count, int mode, size_t lds, bool hs, int k0,
-                            int iters, int meurant) {
-    constexpr int kMaxDev = 64;
-    static bool attr_done[kMaxDev] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
-    if (dev >= kMaxDev || !attr_done[dev]) {
-        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_batch_stop<0>), reinterpret_cast<const void*>(k_small_pipe_pr_batch_stop<1>),
-                              reinterpret_cast<const void*>(k_small_hs_batch_stop<0>), reinterpret_cast<const void*>(k_small_hs_batch_stop<1>)};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-        if (dev < kMaxDev) attr_done[dev] = true;
-    }
-    if (hs) {
-        if (mode == 1) hipLaunchKernelGGL(k_small_hs_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters);
-        else hipLaunchKernelGGL(k_small_hs_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters);
-    } else {
-        if (mode == 1) hipLaunchKernelGGL(k_small_pipe_pr_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters, meurant);
-        else hipLaunchKernelGGL(k_small_pipe_pr_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, stop, k0, iters, meurant);
-    }
-    return PRCG_LAUNCH_OK() ? count : -1;
-}
-int launch_small_batch_jacobi_stop(hipStream_t st, const SmallArgs* desc, const SmallJacobi* jac, const SmallStop* stop, int count, int mode,
-                                   size_t lds, bool hs, int k0, int iters, int meurant) {
-    constexpr int kMaxDev = 64;
-    static bool attr_done[kMaxDev] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
-    if (dev >= kMaxDev || !attr_done[dev]) {
-        const void* fns[4] = {reinterpret_cast<const void*>(k_small_pipe_pr_pcg_batch_stop<0>),
-                              reinterpret_cast<const void*>(k_small_pipe_pr_pcg_batch_stop<1>),
-                              reinterpret_cast<const void*>(k_small_hs_pcg_batch_stop<0>), reinterpret_cast<const void*>(k_small_hs_pcg_batch_stop<1>)};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-        if (dev < kMaxDev) attr_done[dev] = true;
-    }
-    if (hs) {
-        if (mode == 1) hipLaunchKernelGGL(k_small_hs_pcg_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters);
-        else hipLaunchKernelGGL(k_small_hs_pcg_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters);
-    } else {
-        if (mode == 1)
-            hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch_stop<1>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters, meurant);
-        else
-            hipLaunchKernelGGL(k_small_pipe_pr_pcg_batch_stop<0>, dim3(count), dim3(kSmallThreads), lds, st, desc, jac, stop, k0, iters, meurant);
-    }
-    return PRCG_LAUNCH_OK() ? count : -1;
 }
 
 int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a) {

@@ -14,37 +14,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_run
+from small_batch_common import NINE, VARIANTS, csr_cat, plan, shape_of, slots, system
 
-VARIANTS = ['PIPE_PR', 'PIPE_PR_M', 'HS']
-# name -> (n, mode): 1 = matrix in registers, 0 = matrix in LDS (small_fits' rules, evaluated on the committed fixtures)
-NINE = [('bcsstk03', 112, 1), ('nos4', 100, 1), ('bcsstm22', 138, 1), ('nos7', 729, 1), ('lap32x32', 1024, 1),
-        ('494_bus', 494, 0), ('model_48_8_3', 48, 0), ('lap40x40', 1600, 0), ('lap33x32', 1056, 0)]
 ITERS = 200
-
-
-def system(matrices, name):
-    """(A, b) of one of the nine systems: b from the fixture, ones for the Laplacians"""
-    from new_cg_variants_amd import problems
-    if name.startswith('lap'):
-        nx, ny = (int(q) for q in name[3:].split('x'))
-        A = problems.laplace_2d(nx, ny)
-        return A, np.ones(A.shape[0])
-    A, z = matrices[name]
-    return A, np.asarray(z['b'], dtype=np.float64)
-
-
-def shape_of(A):
-    return A.shape[0], A.nnz, int(np.diff(A.indptr).max())
-
-
-def plan(shapes):
-    from new_cg_variants_amd import _lib as L
-    n = np.array([s[0] for s in shapes], dtype=np.int64)
-    nnz = np.array([s[1] for s in shapes], dtype=np.int64)
-    mrl = np.array([s[2] for s in shapes], dtype=np.int32)
-    mode, group = np.full(len(shapes), -1, dtype=np.int32), np.full(len(shapes), -1, dtype=np.int32)
-    rc = L.lib().prcg_plan_small_batch(len(shapes), L.ptr(n), L.ptr(nnz), L.ptr(mrl), L.ptr(mode), L.ptr(group))
-    return rc, mode, group
 
 
 # ---- CPU -------------------------------------------------------------------------------------------------------------------
@@ -153,10 +125,6 @@ def amd():
     import new_cg_variants_amd.cg_variants as cgv
     from new_cg_variants_amd import _lib, device, problems
     return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
-
-
-def slots(variant):
-    return [0, 3, 4] if variant == 'HS' else [0, 1, 2, 3, 4]
 
 
 def read_system(op, s, iters, variant, begin=None):
@@ -329,15 +297,6 @@ def test_against_the_oracles_golden_histories(amd, matrices, fn, method):
         prefix = PREFIX_FLOOR[name]
         assert trial['name'] == fn and trial['max_iter'] == max_iter and trial['updated_residual_2_norm'].shape == (max_iter,)
         np.testing.assert_allclose(trial['updated_residual_2_norm'][:prefix], ref[:prefix], rtol=1e-12, atol=0, err_msg=f'{name}/{fn}')
-
-
-def csr_cat(mats):
-    rows_off = np.concatenate([[0], np.cumsum([A.shape[0] for A in mats])]).astype(np.int64)
-    nnz_off = np.concatenate([[0], np.cumsum([A.nnz for A in mats])]).astype(np.int64)
-    indptr = np.concatenate([np.asarray(A.indptr, dtype=np.int32) for A in mats])
-    indices = np.concatenate([np.asarray(A.indices, dtype=np.int32) for A in mats])
-    data = np.concatenate([np.asarray(A.data, dtype=np.float64) for A in mats])
-    return rows_off, nnz_off, indptr, indices, data
 
 
 @pytest.mark.gpu

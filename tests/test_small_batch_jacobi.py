@@ -20,49 +20,12 @@ import pytest
 import scipy.sparse as sp
 
 from conftest import ROOT, load_run
-from device_order import _butterfly
-from test_small_batch import NINE, VARIANTS, csr_cat, plan, shape_of, slots, system
+from small_batch_common import (CONVERGED, FLAVOUR, NINE, VARIANTS, csr_cat, holds_oracle, jacobi_of, oracle_stopped, plan, run_stopping_batch,
+                                shape_of, slots, system, thresholds, vectors_of, wg_dot, wg_sum)
 
 ITERS = 60
 STOPS = (0, 1, 7, 8, 60)                 # where the vectors are read: 0, 1, 7, 60 against the oracle, 8 for the forced step from 7
-FLAVOUR = {'PIPE_PR': 'pr', 'PIPE_PR_M': 'pr_m'}
 CAP = 156 * 1024
-
-
-def vectors_of(variant):
-    return ('x', 'r', 'p', 's') if variant == 'HS' else ('x', 'r', 'p', 's', 'rt', 'st')
-
-
-# ---- the workgroup's sum: rows tid, tid + 1024, ... in sequence; wave butterfly; the 16 wave partials by xor 8, 4, 2, 1 ----
-def wg_sum(prod):
-    prod = np.asarray(prod, dtype=np.float64)
-    assert prod.ndim == 1 and prod.size <= 4096
-    padded = np.zeros(4096)
-    padded[:prod.size] = prod                                    # rows past n are never added on the device: + 0.0 is the same value
-    rows = padded.reshape(4, 1024)
-    acc = np.zeros(1024)
-    for j in range(4):
-        acc = acc + rows[j]
-    v = _butterfly(acc.reshape(16, 64))                          # (16,): one partial per wave
-    off = 8
-    while off >= 1:
-        v = v[:off] + v[off:2 * off]
-        off //= 2
-    return v[0]
-
-
-def wg_dot(a, b):
-    return wg_sum(a * b)
-
-
-def plan_jacobi(shapes):
-    from new_cg_variants_amd import _lib as L
-    n = np.array([s[0] for s in shapes], dtype=np.int64)
-    nnz = np.array([s[1] for s in shapes], dtype=np.int64)
-    mrl = np.array([s[2] for s in shapes], dtype=np.int32)
-    mode, group = np.full(len(shapes), -1, dtype=np.int32), np.full(len(shapes), -1, dtype=np.int32)
-    rc = L.lib().prcg_plan_small_batch_jacobi(len(shapes), L.ptr(n), L.ptr(nnz), L.ptr(mrl), L.ptr(mode), L.ptr(group))
-    return rc, mode, group
 
 
 def near_cap_matrix():
@@ -109,24 +72,24 @@ def test_workgroup_sum_model():
 def test_planner_hook_under_the_preconditioned_fit_rule(matrices):
     shapes = [shape_of(system(matrices, name)[0]) for name, _, _ in NINE]
     rc, mode, group = plan(shapes)
-    rc_j, mode_j, group_j = plan_jacobi(shapes)
+    rc_j, mode_j, group_j = plan(shapes, jacobi=True)
     assert rc_j == rc == 2 and mode_j.tolist() == mode.tolist() == [m for _, _, m in NINE] and group_j.tolist() == group.tolist()
     # what fits neither
     big = shape_of(matrices['bcsstk14'][0])
-    assert plan_jacobi(shapes + [big])[0] == plan(shapes + [big])[0] == -(9 + 1)
+    assert plan(shapes + [big], jacobi=True)[0] == plan(shapes + [big])[0] == -(9 + 1)
     # a matrix in LDS at the cap exactly: fits without a preconditioner, not with the extra 128 bytes
     near = shape_of(near_cap_matrix())
     assert near == (1500, 9268, 7)
     rc, mode, _ = plan(shapes[:2] + [near])
     assert rc == 2 and mode.tolist() == [1, 1, 0]
-    assert plan_jacobi(shapes[:2] + [near])[0] == -(2 + 1)
-    assert plan_jacobi([near] + shapes)[0] == -(0 + 1)
+    assert plan(shapes[:2] + [near], jacobi=True)[0] == -(2 + 1)
+    assert plan([near] + shapes, jacobi=True)[0] == -(0 + 1)
     # 128 bytes below the cap (16 nonzeros fewer would be 192): the first shape the preconditioned rule takes
     for nnz, fits in ((9268, False), (9258, False), (9257, True)):
         assert 32 * 1500 + 528 + 12 * nnz + 128 <= CAP if fits else 32 * 1500 + 528 + 12 * nnz + 128 > CAP
-        assert (plan_jacobi([(1500, nnz, 7)])[0] == 1) == fits and plan([(1500, nnz, 7)])[0] == 1
+        assert (plan([(1500, nnz, 7)], jacobi=True)[0] == 1) == fits and plan([(1500, nnz, 7)])[0] == 1
     # the register mode never depends on the LDS need; bad arguments as the unpreconditioned hook
-    assert plan_jacobi([(1024, 8 * 1024, 8)])[0] == 1
+    assert plan([(1024, 8 * 1024, 8)], jacobi=True)[0] == 1
     from new_cg_variants_amd import _lib as L
     assert L.lib().prcg_plan_small_batch_jacobi(0, None, None, None, None, None) == 0
 
@@ -243,10 +206,6 @@ def nine(matrices):
     return [system(matrices, name) for name, _, _ in NINE]
 
 
-def jacobi_of(systems):
-    return [1 / A.diagonal() for A, _ in systems]
-
-
 def read_vectors(batch, s, variant):
     return {v: batch.get_vector(v, s) for v in vectors_of(variant)}
 
@@ -313,15 +272,15 @@ def stopped(amd, nine):
     return get
 
 
-def oracle_run(A, b, variant, prec_of=None):
-    """the oracle under the workgroup's sum: vectors at STOPS, scalars {mu, delta, gamma, nu, rr}, coefficients, history"""
+def oracle_run(A, b, variant, prec_of=None, iters=ITERS, stops=STOPS):
+    """the oracle under the workgroup's sum: vectors at `stops`, scalars {mu, delta, gamma, nu, rr}, coefficients, history"""
     import oracle.ne_oracle as O
     prec = (prec_of or O.jacobi)(A)
     hs = variant == 'HS'
     with np.errstate(all='ignore'):
         st = (O.hs_start if hs else O.pipe_start)(A, b, np.zeros(b.size), prec=prec, dot=wg_dot)
         at, scalars, coef = {}, [], []
-        for k in range(ITERS + 1):
+        for k in range(iters + 1):
             if k:
                 a = st.alpha
                 if hs:
@@ -332,7 +291,7 @@ def oracle_run(A, b, variant, prec_of=None):
                     coef.append([a, st.beta, st.nu_pred])
             assert st.k == k
             scalars.append([st.mu, 0.0 if hs else st.dl, 0.0 if hs else st.gm, st.nu, wg_dot(st.r, st.r)])
-            if k in STOPS:
+            if k in stops:
                 at[k] = {v: np.array(getattr(st, v), copy=True) for v in vectors_of(variant)}
         scalars = np.array(scalars)
         return dict(at=at, scalars=scalars, coef=np.array(coef), hist=np.sqrt(scalars[:, 4]))
@@ -356,6 +315,63 @@ def test_whole_trajectory_against_the_oracle(amd, nine, base, stopped, variant):
             for v in vectors_of(variant):
                 assert np.array_equal(got[v], want['at'][k][v], equal_nan=True), (name, k, v)
         same(cut, rec, variant, name)                            # ... and the run that stopped to be read is the run
+
+
+def tall_systems():
+    """Two systems whose threads hold a THIRD and a FOURTH row (the nine stop at n = 1600: two rows).  Diagonal 2.5 + (i mod 7) / 7,
+    -1 between rows i and i + 1, b_i = 1 + 0.25 sin(0.37 i).  (a) n = 2100, tridiagonal throughout: three rows per thread, the
+    third in 52 threads; (b) n = 3080, coupled only for 2180 <= i < 3079 (or the matrix would not fit LDS beside the vectors):
+    four rows per thread, the fourth in 8 threads.  Both live in LDS, at 143,304 and 157,624 bytes of the 159,744 (+ 128 with
+    Jacobi)."""
+    out = []
+    for n, first in ((2100, 0), (3080, 2180)):
+        i = np.arange(n)
+        link = ((i >= first) & (i < n - 1)).astype(float)[:-1]
+        A = sp.csr_matrix(sp.diags([-link, 2.5 + (i % 7) / 7, -link], [-1, 0, 1]))
+        A.eliminate_zeros()
+        A.sort_indices()
+        out.append((A, 1 + 0.25 * np.sin(0.37 * i)))
+    assert [shape_of(A)[:2] for A, _ in out] == [(2100, 6298), (3080, 4878)]
+    assert [32 * A.shape[0] + 512 + 12 * A.nnz + 16 for A, _ in out] == [143304, 157624] and 157624 + 128 <= CAP
+    return out
+
+
+@pytest.mark.gpu
+def test_third_and_fourth_row_of_a_thread(amd):
+    """12 iterations of the three variants on tall_systems(), one batch: the Jacobi session against the oracle as in
+    test_whole_trajectory_against_the_oracle; d = ones against the unpreconditioned session; and a session stopped at
+    (1e-3 ||b||)^2 -- strictly inside the run -- against the stopping oracle, as test_small_batch_stop.py holds the nine."""
+    iters, at = 12, (0, 1, 12)
+    systems = tall_systems()
+    rc, mode, _ = plan([shape_of(A) for A, _ in systems], jacobi=True)
+    assert rc == 1 and mode.tolist() == [0, 0]
+    thr = thresholds([b for _, b in systems], rtol=1e-3)
+    for variant in VARIANTS:
+        idx, ncoef = slots(variant), 2 if variant == 'HS' else 3
+        # the inputs: finite histories, and a stop strictly inside the run
+        wants = [oracle_run(A, b, variant, iters=iters, stops=at) for A, b in systems]
+        halts = [oracle_stopped(A, b, variant, t, iters) for (A, b), t in zip(systems, thr)]
+        for want, halt in zip(wants, halts):
+            assert np.all(np.isfinite(want['hist'])) and want['hist'][0] > 0, variant
+            assert halt['status'] == CONVERGED and 1 < halt['k_stop'] < iters, (variant, halt['k_stop'])
+        recs = run_batch(amd, systems, variant, jacobi_of(systems), chunks=(1, iters - 1), stops=at)
+        for s, (rec, want) in enumerate(zip(recs, wants)):
+            assert rec['scalars'].shape == (iters + 1, 8) and rec['hist'].shape == (iters + 1,)
+            assert np.array_equal(rec['row0'][idx], want['scalars'][0, idx]), (variant, s, 'row 0')
+            assert np.array_equal(rec['scalars'][:, idx], want['scalars'][:, idx]), (variant, s, 'scalars')
+            assert np.array_equal(rec['coef'][:, :ncoef], want['coef'][:, :ncoef]), (variant, s, 'coefficients')
+            assert np.array_equal(rec['hist'], want['hist']), (variant, s, 'history')
+            for k in at:
+                for v in vectors_of(variant):
+                    assert np.array_equal(rec['at'][k][v], want['at'][k][v]), (variant, s, k, v)
+        ones = run_batch(amd, systems, variant, [np.ones(b.size) for _, b in systems], chunks=(iters,))
+        plain = run_batch(amd, systems, variant, None, chunks=(iters,))
+        for s, (a, b) in enumerate(zip(ones, plain)):
+            same(a, b, variant, (variant, s), ks=(0, iters), vectors=('x', 'r', 'p', 's'))
+            assert np.array_equal(a['scalars'][:, :5], b['scalars'][:, :5]), (variant, s)
+            assert np.all(np.isfinite(b['hist'])) and b['hist'][iters] > 0
+        for s, (rec, halt) in enumerate(zip(run_stopping_batch(amd, systems, variant, thr, chunks=(iters,)), halts)):
+            holds_oracle(rec, halt, variant, iters, (variant, s))
 
 
 @pytest.mark.gpu

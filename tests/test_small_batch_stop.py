@@ -21,71 +21,18 @@ import pytest
 import scipy.sparse as sp
 
 from conftest import ROOT
-from test_small_batch import NINE, VARIANTS, slots, system
-from test_small_batch_jacobi import vectors_of, wg_dot
+from small_batch_common import (BREAKDOWN, CONVERGED, NINE, VARIANTS, holds_oracle, jacobi_of, oracle_stopped, rule, run_stopping_batch, system,
+                                thresholds)
 
 ITERS = 150
 RTOL = 1e-8
-FLAVOUR = {'PIPE_PR': 'pr', 'PIPE_PR_M': 'pr_m'}
-CONVERGED, BREAKDOWN = 1, 2
 NAMES = [name for name, _, _ in NINE]
-
-
-def rule(mu, nu, rr, thr):
-    if rr <= thr:
-        return CONVERGED
-    if not (0 < mu < np.inf and 0 < nu < np.inf):
-        return BREAKDOWN
-    return 0
-
-
-def thresholds(bs, rtol=0.0, atol=0.0):
-    """thr_s = max(rtol ||b_s||_2, atol)^2, the expression of cg_variants._run_batch"""
-    norms = np.array([np.linalg.norm(b) for b in bs])
-    return np.maximum(rtol * norms, atol) ** 2
 
 
 def indefinite():
     """A = diag(+1 x 32, -1 x 32), b = ones: mu = p.s = 0 on the initial state, with the Jacobi scaling (d = +-1: nu = 0 too) and
     without -- a breakdown at k = 0"""
     return sp.csr_matrix(sp.diags(np.concatenate([np.ones(32), -np.ones(32)]))), np.ones(64)
-
-
-def names_of(variant, jacobi):
-    return vectors_of(variant) if jacobi else ('x', 'r', 'p', 's')
-
-
-def oracle_stopped(A, b, variant, thr, iters, jacobi=True):
-    """the oracle under the workgroup's sum, stepped until the rule fires or `iters` iterations are done.  last: the iteration
-    whose state it holds (k_stop, or iters); scalars: rows 0..last {mu, delta, gamma, nu, rr}; coef: rows 1..last"""
-    import oracle.ne_oracle as O
-    prec = O.jacobi(A) if jacobi else None
-    hs = variant == 'HS'
-
-    def row(st):
-        return [st.mu, 0.0 if hs else st.dl, 0.0 if hs else st.gm, st.nu, wg_dot(st.r, st.r)]
-    with np.errstate(all='ignore'):
-        st = (O.hs_start if hs else O.pipe_start)(A, b, np.zeros(b.size), prec=prec, dot=wg_dot)
-        at0 = {v: np.array(getattr(st, v), copy=True) for v in names_of(variant, jacobi)}
-        scalars, coef = [row(st)], []
-        k_stop, status = -1, rule(st.mu, st.nu, scalars[0][4], thr)
-        if status:
-            k_stop = 0
-        while not status and st.k < iters:
-            a = st.alpha
-            if hs:
-                O.hs_advance(A, st, prec=prec, dot=wg_dot)
-                coef.append([a, st.beta, 0.0])
-            else:
-                O.pipe_advance(A, st, flavour=FLAVOUR[variant], prec=prec, dot=wg_dot, square=lambda q: q * q)
-                coef.append([a, st.beta, st.nu_pred])
-            scalars.append(row(st))
-            status = rule(st.mu, st.nu, scalars[-1][4], thr)
-            if status:
-                k_stop = st.k
-        scalars = np.array(scalars)
-        return dict(k_stop=k_stop, status=status, last=st.k, at0=at0, at={v: np.array(getattr(st, v), copy=True) for v in at0},
-                    scalars=scalars, coef=np.array(coef).reshape(-1, 3), hist=np.sqrt(scalars[:, 4]))
 
 
 @pytest.fixture(scope='module')
@@ -257,39 +204,8 @@ def amd():
     return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
 
 
-def jacobi_of(systems):
-    return [1 / A.diagonal() for A, _ in systems]
-
-
-def run_batch(amd, systems, variant, rr_stop, chunks=(ITERS,), jacobi=True, mat_of=None, matrices=None, read=None):
-    """one DeviceBatch session over `systems` [(A, b)], x0 = 0, Jacobi or unpreconditioned, rr_stop None: no thresholds.  One
-    record per system of `read` (default: all): the stop word, the vectors at k = 0 and at the end, every row of the scalars
-    and coefficients, the history."""
-    L = amd['L']
-    mats = [A for A, _ in systems] if matrices is None else matrices
-    batch = amd['device'].DeviceBatch(mats, mat_of)
-    names = names_of(variant, jacobi)
-    total = sum(chunks)
-    read = range(len(systems)) if read is None else read
-    try:
-        batch.begin(getattr(L, variant), [b for _, b in systems], [np.zeros(b.size) for _, b in systems], total + 1, hist_mask=1,
-                    inv_diag=jacobi_of(systems) if jacobi else None, rr_stop=rr_stop)
-        recs = {s: {'at0': {v: batch.get_vector(v, s) for v in names}} for s in read}
-        for c in chunks:
-            batch.iterate(c)
-        batch.sync()
-        assert batch.k == total                                  # what was launched, stopped systems or not
-        k_stop, status = batch.stops()
-        assert k_stop.dtype == status.dtype == np.int32 and k_stop.shape == status.shape == (len(systems),)
-        for s, rec in recs.items():
-            rec['k_stop'], rec['status'] = int(k_stop[s]), int(status[s])
-            rec['at'] = {v: batch.get_vector(v, s) for v in names}
-            rec['scalars'] = np.array([batch.get_scalars(k, s) for k in range(total + 1)])
-            rec['coef'] = np.array([batch.get_coefficients(k, s) for k in range(1, total + 1)])
-            rec['hist'] = batch.history(s)['updated_residual_2_norm']
-        return [recs[s] for s in read]
-    finally:
-        batch.close()
+def run_batch(amd, systems, variant, rr_stop, chunks=(ITERS,), **kw):
+    return run_stopping_batch(amd, systems, variant, rr_stop, chunks, **kw)
 
 
 def same(a, b, what=''):
@@ -301,23 +217,6 @@ def same(a, b, what=''):
             assert np.array_equal(a[key][v], b[key][v], equal_nan=True), (what, key, v)
     for key in ('scalars', 'coef', 'hist'):
         assert a[key].shape == b[key].shape and np.array_equal(a[key], b[key], equal_nan=True), (what, key)
-
-
-def holds_oracle(rec, want, variant, total, what=''):
-    """a device record of `total` launched iterations against oracle_stopped"""
-    idx, ncoef, last = slots(variant), 2 if variant == 'HS' else 3, want['last']
-    assert (rec['k_stop'], rec['status']) == (want['k_stop'], want['status']), (what, 'stop word', rec['k_stop'], rec['status'])
-    assert last == (want['k_stop'] if want['status'] else total)
-    for v in want['at']:
-        assert np.array_equal(rec['at0'][v], want['at0'][v]), (what, 'k = 0', v)
-        assert np.array_equal(rec['at'][v], want['at'][v]), (what, 'at the stop', v)
-    assert rec['scalars'].shape == (total + 1, 8) and rec['coef'].shape == (total, 3) and rec['hist'].shape == (total + 1,)
-    assert np.array_equal(rec['scalars'][:last + 1, idx], want['scalars'][:, idx]), (what, 'scalars')
-    assert np.array_equal(rec['coef'][:last, :ncoef], want['coef'][:, :ncoef]), (what, 'coefficients')
-    assert np.array_equal(rec['scalars'][last + 1:], np.zeros((total - last, 8))), (what, 'scalar rows beyond the stop')
-    assert np.array_equal(rec['coef'][last:], np.zeros((total - last, 3))), (what, 'coefficient rows beyond the stop')
-    assert np.array_equal(rec['hist'][:last + 1], want['hist']), (what, 'history')
-    assert np.array_equal(rec['hist'][last + 1:], np.zeros(total - last)), (what, 'history beyond the stop')
 
 
 @pytest.fixture(scope='module')

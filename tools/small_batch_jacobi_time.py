@@ -12,65 +12,19 @@ median are reported.  Two figures per leg: `solve` = begin + iterations, `iterat
 to `iters` whatever the residual does: a system that has converged -- nos7 under Jacobi breaks down near k = 125 -- goes on
 through the same instructions on inf / nan.)
 One record per measurement on stderr, ONE JSON line on stdout."""
-import json, os, sys, time
+import json, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import scipy.sparse as sp
+from small_batch_timing import load_system, options, summary, timed, timed_loop
 from new_cg_variants_amd import _lib as L
 from new_cg_variants_amd.device import DeviceBatch, DeviceCSR
 
-
-def load_matrix(name):
-    z = np.load(os.path.join(ROOT, 'tests', 'golden', f'matrix_{name}.npz'))
-    n = int(z['n'])
-    return sp.csr_matrix((z['data'], z['indices'], z['indptr']), shape=(n, n)), z
-
-
-opt = dict(sizes='1,16,256,1024', iters='1000', repeats='5')
-for a in sys.argv[1:]:
-    k, _, v = a.partition('=')
-    if k not in opt or not v:
-        sys.exit(f'unknown argument {a!r}\n{__doc__}')
-    opt[k] = v
+opt = options(dict(sizes='1,16,256,1024', iters='1000', repeats='5'), __doc__)
 SIZES, ITERS, REPEATS = [int(q) for q in opt['sizes'].split(',')], int(opt['iters']), int(opt['repeats'])
-
-
-def timed_batch(batch, variant, B, X0, D):
-    t0 = time.perf_counter()
-    batch.begin(variant, B, X0, ITERS + 1, hist_mask=1, inv_diag=D)
-    t1 = time.perf_counter()
-    batch.iterate(ITERS)
-    batch.sync()
-    t2 = time.perf_counter()
-    return t2 - t0, t2 - t1
-
-
-def timed_loop(op, variant, B, X0, d):
-    solve = it = 0.0
-    for b, x0 in zip(B, X0):
-        t0 = time.perf_counter()
-        op.begin(variant, b, x0, ITERS + 1, hist_mask=1, inv_diag=d)
-        t1 = time.perf_counter()
-        op.iterate(ITERS)
-        op.sync()
-        t2 = time.perf_counter()
-        solve += t2 - t0
-        it += t2 - t1
-    return solve, it
-
-
-def summary(samples):
-    a = np.array(samples) * 1e3
-    return {'solve_ms_best': float(a[:, 0].min()), 'solve_ms_median': float(np.median(a[:, 0])),
-            'iterate_ms_best': float(a[:, 1].min()), 'iterate_ms_median': float(np.median(a[:, 1]))}
-
 
 result = {'iters': ITERS, 'cases': []}
 for name, vname in (('nos7', 'PIPE_PR'), ('bcsstk03', 'HS')):
-    A, z = load_matrix(name)
+    A, b0 = load_system(name)
     n, variant = A.shape[0], getattr(L, vname)
-    b0 = np.asarray(z['b'], dtype=np.float64)
     d = 1 / A.diagonal()
     op = DeviceCSR(A)
     op.begin(variant, b0, np.zeros(n), ITERS + 1, hist_mask=1, inv_diag=d)
@@ -80,16 +34,16 @@ for name, vname in (('nos7', 'PIPE_PR'), ('bcsstk03', 'HS')):
         X0 = np.zeros((nb, n))
         D = np.tile(d, (nb, 1))
         batch = DeviceBatch([A], np.zeros(nb, dtype=np.int32))
-        timed_batch(batch, variant, B, X0, D)            # warm-up of the three legs
-        timed_batch(batch, variant, B, X0, None)
-        timed_loop(op, variant, B[:min(nb, 4)], X0[:min(nb, 4)], d)
+        timed(batch, variant, B, X0, ITERS, inv_diag=D)            # warm-up of the three legs
+        timed(batch, variant, B, X0, ITERS)
+        timed_loop(op, variant, B[:min(nb, 4)], X0[:min(nb, 4)], ITERS, inv_diag=d)
         reps_loop = REPEATS if nb < 256 else min(REPEATS, 2)
         tj, tu, tl = [], [], []
         for r in range(REPEATS):
-            tu.append(timed_batch(batch, variant, B, X0, None))
-            tj.append(timed_batch(batch, variant, B, X0, D))
+            tu.append(timed(batch, variant, B, X0, ITERS))
+            tj.append(timed(batch, variant, B, X0, ITERS, inv_diag=D))
             if r < reps_loop:
-                tl.append(timed_loop(op, variant, B, X0, d))
+                tl.append(timed_loop(op, variant, B, X0, ITERS, inv_diag=d))
         # the batch and the loop computed the same thing: the last system's history, while two summation orders still agree
         hb = batch.history(nb - 1)['updated_residual_2_norm'][:5]
         hl = op.history()['updated_residual_2_norm'][:5]

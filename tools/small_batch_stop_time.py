@@ -13,61 +13,24 @@ Method of small_batch_time.py: every leg is timed with the host clock around wor
 of each; `repeats` windows each, alternated; the best and the median are reported.  Two figures per leg: `solve` = begin +
 iterations, `iterate` = the iterations alone.  One process.
 One record per measurement on stderr, ONE JSON line on stdout."""
-import json, os, sys, time
+import json, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import scipy.sparse as sp
+from small_batch_timing import NINE, load_system, options, summary, timed
 from new_cg_variants_amd import _lib as L
-from new_cg_variants_amd import problems
 from new_cg_variants_amd.device import DeviceBatch
 
-NINE = ['bcsstk03', 'nos4', 'bcsstm22', 'nos7', 'lap32x32', '494_bus', 'model_48_8_3', 'lap40x40', 'lap33x32']
-
-
-def load_system(name):
-    if name.startswith('lap'):
-        nx, ny = (int(q) for q in name[3:].split('x'))
-        A = problems.laplace_2d(nx, ny)
-        return A, np.ones(A.shape[0])
-    z = np.load(os.path.join(ROOT, 'tests', 'golden', f'matrix_{name}.npz'))
-    n = int(z['n'])
-    return sp.csr_matrix((z['data'], z['indices'], z['indptr']), shape=(n, n)), np.asarray(z['b'], dtype=np.float64)
-
-
-opt = dict(sizes='1,16,256,1024', iters='1000', mix_iters='150', repeats='5')
-for a in sys.argv[1:]:
-    k, _, v = a.partition('=')
-    if k not in opt or not v:
-        sys.exit(f'unknown argument {a!r}\n{__doc__}')
-    opt[k] = v
+opt = options(dict(sizes='1,16,256,1024', iters='1000', mix_iters='150', repeats='5'), __doc__)
 SIZES, ITERS, MIX_ITERS, REPEATS = [int(q) for q in opt['sizes'].split(',')], int(opt['iters']), int(opt['mix_iters']), int(opt['repeats'])
-
-
-def timed(batch, variant, B, X0, D, iters, rr_stop):
-    t0 = time.perf_counter()
-    batch.begin(variant, B, X0, iters + 1, hist_mask=1, inv_diag=D, rr_stop=rr_stop)
-    t1 = time.perf_counter()
-    batch.iterate(iters)
-    batch.sync()
-    t2 = time.perf_counter()
-    return t2 - t0, t2 - t1
-
-
-def summary(samples):
-    a = np.array(samples) * 1e3
-    return {'solve_ms_best': float(a[:, 0].min()), 'solve_ms_median': float(np.median(a[:, 0])),
-            'iterate_ms_best': float(a[:, 1].min()), 'iterate_ms_median': float(np.median(a[:, 1]))}
 
 
 def compare(batch, variant, B, X0, D, iters, rr_stop):
     """windows of the session with thresholds and without, alternated after a warm-up of each; the stop words of the last one with"""
-    timed(batch, variant, B, X0, D, iters, rr_stop)
-    timed(batch, variant, B, X0, D, iters, None)
+    timed(batch, variant, B, X0, iters, inv_diag=D, rr_stop=rr_stop)
+    timed(batch, variant, B, X0, iters, inv_diag=D)
     ts, tp = [], []
     for _ in range(REPEATS):
-        tp.append(timed(batch, variant, B, X0, D, iters, None))
-        ts.append(timed(batch, variant, B, X0, D, iters, rr_stop))
+        tp.append(timed(batch, variant, B, X0, iters, inv_diag=D))
+        ts.append(timed(batch, variant, B, X0, iters, inv_diag=D, rr_stop=rr_stop))
     k_stop, status = batch.stops()
     return summary(ts), summary(tp), k_stop, status
 
