@@ -11,7 +11,9 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iin
 TRANSPORT := tests/transport/libthreads_ccl.so
 # ... and one that connects ranks living in separate PROCESSES that share one GPU (the driver's launch shape, rehearsed on one GPU)
 TRANSPORT_P := tests/transport/libprocs_ccl.so
-OBJS := $(CSRC)/prcg_kernels.o $(CSRC)/prcg_win.o $(CSRC)/prcg_sell.o $(CSRC)/prcg_blockjac.o $(CSRC)/prcg_rhs2.o $(CSRC)/prcg_small.o $(CSRC)/prcg_engine.o $(CSRC)/prcg_batch.o $(CSRC)/prcg_plan.o $(CSRC)/prcg_rccl.o
+OBJS := $(CSRC)/prcg_kernels.o $(CSRC)/prcg_win.o $(CSRC)/prcg_sell.o $(CSRC)/prcg_blockjac.o $(CSRC)/prcg_rhs2.o $(CSRC)/prcg_small.o $(CSRC)/prcg_engine.o $(CSRC)/prcg_session.o $(CSRC)/prcg_multi.o $(CSRC)/prcg_batch.o $(CSRC)/prcg_plan.o $(CSRC)/prcg_rccl.o
+# prcg_handle.h and what it includes: every host file that sees the handle depends on all of it
+HANDLE_H := $(CSRC)/prcg_handle.h $(CSRC)/prcg_kernels.h $(CSRC)/prcg_bjvar.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_plan.h $(CSRC)/prcg_rccl.h include/prcg.h
 
 all: $(OUT) $(TRANSPORT) $(TRANSPORT_P)
 
@@ -33,10 +35,16 @@ $(CSRC)/prcg_rhs2.o: $(CSRC)/prcg_rhs2.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_g
 $(CSRC)/prcg_small.o: $(CSRC)/prcg_small.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
-$(CSRC)/prcg_batch.o: $(CSRC)/prcg_batch.cpp $(CSRC)/prcg_batch.h $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h include/prcg.h include/prcg_test.h
+$(CSRC)/prcg_engine.o: $(CSRC)/prcg_engine.cpp $(HANDLE_H) include/prcg_test.h
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
-$(CSRC)/prcg_engine.o: $(CSRC)/prcg_engine.cpp $(CSRC)/prcg_kernels.h $(CSRC)/prcg_batch.h $(CSRC)/prcg_bjvar.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_plan.h $(CSRC)/prcg_rccl.h include/prcg.h include/prcg_test.h
+$(CSRC)/prcg_session.o: $(CSRC)/prcg_session.cpp $(HANDLE_H)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
+
+$(CSRC)/prcg_multi.o: $(CSRC)/prcg_multi.cpp $(HANDLE_H)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
+
+$(CSRC)/prcg_batch.o: $(CSRC)/prcg_batch.cpp $(HANDLE_H) include/prcg_test.h
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
 $(CSRC)/prcg_plan.o: $(CSRC)/prcg_plan.cpp $(CSRC)/prcg_plan.h $(CSRC)/prcg_geometry.h
@@ -54,7 +62,11 @@ $(TRANSPORT): tests/transport/threads_ccl.hip
 $(TRANSPORT_P): tests/transport/procs_ccl.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -fPIC -shared $< -o $@ -lrt
 
+# the objects libprcg.so is linked from, for scripts that relink it with one of them replaced (tools/build_variants.sh)
+print-objs:
+	@echo $(OBJS)
+
 clean:
 	rm -f $(OBJS) $(OUT) $(TRANSPORT) $(TRANSPORT_P)
 
-.PHONY: all clean
+.PHONY: all clean print-objs

@@ -24,16 +24,11 @@
 
 #include "../../include/prcg.h"
 #include "../../include/prcg_test.h"
-#include "prcg_batch.h"
-#include "prcg_kernels.h"
+#include "prcg_handle.h"
 
 using namespace prcg;
 
 namespace {
-
-constexpr int kNS = PRCG_NUM_SCALARS;
-constexpr int kCoefStride = 4;
-static_assert(kPartialStride == PRCG_NUM_SCALARS, "the small-system kernels index the scalar history with kPartialStride");
 
 struct Buf {
     void* p = nullptr;
@@ -100,15 +95,6 @@ struct prcg_batch {
     const SmallStop* stop_of(int m) const { return static_cast<const SmallStop*>(stop.p) + (m == 1 ? 0 : count[1]); }
 };
 
-#define BCHECK(h, cond, ...)                                                                  \
-    do { if (!(cond)) return batch_fail(h, PRCG_EINVAL, __VA_ARGS__); } while (0)
-#define BHIP(h, expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess)                                                                \
-            return batch_fail(h, PRCG_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-    } while (0)
-
 extern "C" {
 
 int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
@@ -126,60 +112,59 @@ int prcg_plan_small_batch_jacobi(int n_sys, const int64_t* n, const int64_t* nnz
 int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
                       const int32_t* indices, const double* data, int n_sys, const int32_t* mat_of, prcg_batch_t** out) {
     if (!h) return PRCG_EINVAL;
-    BCHECK(h, out, "prcg_batch_create: null output pointer");
+    CHECK(h, out, "prcg_batch_create: null output pointer");
     *out = nullptr;
-    BCHECK(h, rows_off && nnz_off && indptr && indices && data && mat_of, "prcg_batch_create: null pointer argument");
-    BCHECK(h, n_sys >= 1, "prcg_batch_create: n_sys = %d: a batch holds at least one system", n_sys);
-    BCHECK(h, n_mat >= 1, "prcg_batch_create: n_mat = %d: a batch holds at least one matrix", n_mat);
-    const BatchHost host = batch_host(h);
-    BCHECK(h, !host.comm, "prcg_batch_create: the handle carries a communicator: a batch runs on one GPU, on a handle without one");
-    BCHECK(h, rows_off[0] == 0 && nnz_off[0] == 0, "prcg_batch_create: inconsistent offsets: rows_off[0] and nnz_off[0] must be 0");
+    CHECK(h, rows_off && nnz_off && indptr && indices && data && mat_of, "prcg_batch_create: null pointer argument");
+    CHECK(h, n_sys >= 1, "prcg_batch_create: n_sys = %d: a batch holds at least one system", n_sys);
+    CHECK(h, n_mat >= 1, "prcg_batch_create: n_mat = %d: a batch holds at least one matrix", n_mat);
+    CHECK(h, !h->multi(), "prcg_batch_create: the handle carries a communicator: a batch runs on one GPU, on a handle without one");
+    CHECK(h, rows_off[0] == 0 && nnz_off[0] == 0, "prcg_batch_create: inconsistent offsets: rows_off[0] and nnz_off[0] must be 0");
     std::vector<int> mrl((size_t)n_mat, 0);
     for (int m = 0; m < n_mat; ++m) {
         const int64_t nm = rows_off[m + 1] - rows_off[m], zm = nnz_off[m + 1] - nnz_off[m];
-        BCHECK(h, nm >= 1 && zm >= 0 && nm < (1 << 30) && zm < (1ll << 31),
+        CHECK(h, nm >= 1 && zm >= 0 && nm < (1 << 30) && zm < (1ll << 31),
                "prcg_batch_create: inconsistent offsets: matrix %d has %lld rows and %lld nonzeros", m, (long long)nm, (long long)zm);
         const int32_t* ip = indptr + rows_off[m] + m;            // n_m + 1 entries per matrix
-        BCHECK(h, ip[0] == 0 && ip[nm] == zm, "prcg_batch_create: inconsistent offsets: indptr of matrix %d runs from %d to %d, its "
+        CHECK(h, ip[0] == 0 && ip[nm] == zm, "prcg_batch_create: inconsistent offsets: indptr of matrix %d runs from %d to %d, its "
                "nonzeros number %lld (indptr is zero-based per matrix)", m, ip[0], ip[nm], (long long)zm);
         for (int64_t i = 0; i < nm; ++i) {
-            BCHECK(h, ip[i + 1] >= ip[i], "prcg_batch_create: inconsistent offsets: indptr of matrix %d decreases at row %lld", m, (long long)i);
+            CHECK(h, ip[i + 1] >= ip[i], "prcg_batch_create: inconsistent offsets: indptr of matrix %d decreases at row %lld", m, (long long)i);
             if (ip[i + 1] - ip[i] > mrl[(size_t)m]) mrl[(size_t)m] = ip[i + 1] - ip[i];
         }
         const int32_t* ci = indices + nnz_off[m];
         for (int64_t q = 0; q < zm; ++q)
-            BCHECK(h, ci[q] >= 0 && ci[q] < nm, "prcg_batch_create: column index %d of matrix %d (nonzero %lld) lies outside its %lld columns",
+            CHECK(h, ci[q] >= 0 && ci[q] < nm, "prcg_batch_create: column index %d of matrix %d (nonzero %lld) lies outside its %lld columns",
                    ci[q], m, (long long)q, (long long)nm);
     }
     std::vector<int64_t> sn((size_t)n_sys), sz((size_t)n_sys);
     std::vector<int32_t> sl((size_t)n_sys), mode((size_t)n_sys), group((size_t)n_sys);
     for (int s = 0; s < n_sys; ++s) {
         const int m = mat_of[s];
-        BCHECK(h, m >= 0 && m < n_mat, "prcg_batch_create: mat_of[%d] = %d lies outside [0, %d): system %d names no matrix", s, m, n_mat, s);
+        CHECK(h, m >= 0 && m < n_mat, "prcg_batch_create: mat_of[%d] = %d lies outside [0, %d): system %d names no matrix", s, m, n_mat, s);
         sn[(size_t)s] = rows_off[m + 1] - rows_off[m]; sz[(size_t)s] = nnz_off[m + 1] - nnz_off[m]; sl[(size_t)s] = mrl[(size_t)m];
     }
     const int ng = plan_groups(n_sys, sn.data(), sz.data(), sl.data(), mode.data(), group.data());
     if (ng < 0) {
         const int s = -ng - 1;
-        return batch_fail(h, PRCG_EINVAL, "prcg_batch_create: system %d (n = %lld, nnz = %lld, longest row %d) does not fit the one-workgroup "
+        return fail(h, PRCG_EINVAL, "prcg_batch_create: system %d (n = %lld, nnz = %lld, longest row %d) does not fit the one-workgroup "
                           "solver (at most 4096 rows, and the matrix in registers or in LDS beside the vectors); a batch has no other "
                           "schedule: solve it in a session of its own", s, (long long)sn[(size_t)s], (long long)sz[(size_t)s], sl[(size_t)s]);
     }
     prcg_batch* b = new (std::nothrow) prcg_batch();
-    if (!b) return batch_fail(h, PRCG_ENOMEM, "out of host memory");
+    if (!b) return fail(h, PRCG_ENOMEM, "out of host memory");
     struct Guard { prcg_batch* b; ~Guard() { delete b; } } guard{b};      // (released on success)
-    b->h = h; b->dev = host.dev; b->sc = host.sc; b->n_sys = n_sys;
-    BHIP(h, hipSetDevice(b->dev));
+    b->h = h; b->dev = h->dev; b->sc = h->sc; b->n_sys = n_sys;
+    HIPCHK(h, hipSetDevice(b->dev));
     const int64_t rows_all = rows_off[n_mat], nnz_all = nnz_off[n_mat];
-    BHIP(h, b->m_indptr.ensure((size_t)(rows_all + n_mat) * sizeof(int32_t)));
-    BHIP(h, b->m_col.ensure((size_t)nnz_all * sizeof(int32_t)));
-    BHIP(h, b->m_val.ensure((size_t)nnz_all * sizeof(double)));
-    BHIP(h, hipMemcpyAsync(b->m_indptr.p, indptr, (size_t)(rows_all + n_mat) * sizeof(int32_t), hipMemcpyHostToDevice, b->sc));
+    HIPCHK(h, b->m_indptr.ensure((size_t)(rows_all + n_mat) * sizeof(int32_t)));
+    HIPCHK(h, b->m_col.ensure((size_t)nnz_all * sizeof(int32_t)));
+    HIPCHK(h, b->m_val.ensure((size_t)nnz_all * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(b->m_indptr.p, indptr, (size_t)(rows_all + n_mat) * sizeof(int32_t), hipMemcpyHostToDevice, b->sc));
     if (nnz_all) {
-        BHIP(h, hipMemcpyAsync(b->m_col.p, indices, (size_t)nnz_all * sizeof(int32_t), hipMemcpyHostToDevice, b->sc));
-        BHIP(h, hipMemcpyAsync(b->m_val.p, data, (size_t)nnz_all * sizeof(double), hipMemcpyHostToDevice, b->sc));
+        HIPCHK(h, hipMemcpyAsync(b->m_col.p, indices, (size_t)nnz_all * sizeof(int32_t), hipMemcpyHostToDevice, b->sc));
+        HIPCHK(h, hipMemcpyAsync(b->m_val.p, data, (size_t)nnz_all * sizeof(double), hipMemcpyHostToDevice, b->sc));
     }
-    BHIP(h, hipStreamSynchronize(b->sc));
+    HIPCHK(h, hipStreamSynchronize(b->sc));
     b->n.resize((size_t)n_sys); b->nnz.resize((size_t)n_sys); b->mode.resize((size_t)n_sys); b->slot.resize((size_t)n_sys);
     b->mrl.resize((size_t)n_sys);
     b->voff.assign((size_t)n_sys + 1, 0);
@@ -219,41 +204,41 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
                        int max_iter, uint32_t hist_mask) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
+    CHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
            "%s: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", fn, variant);
-    BCHECK(h, rhs && x0 && (inv_diag || !jacobi), jacobi ? "%s: null rhs, x0 or inv_diag" : "%s: null rhs or x0", fn);
-    BCHECK(h, max_iter >= 1, "%s: max_iter = %d, must be at least 1", fn, max_iter);
-    BCHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+    CHECK(h, rhs && x0 && (inv_diag || !jacobi), jacobi ? "%s: null rhs, x0 or inv_diag" : "%s: null rhs or x0", fn);
+    CHECK(h, max_iter >= 1, "%s: max_iter = %d, must be at least 1", fn, max_iter);
+    CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
            "%s: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", fn, hist_mask);
     for (int s = 0; jacobi && s < b->n_sys; ++s) {
         int mode = 0;
-        BCHECK(h, small_fits(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode, true),
+        CHECK(h, small_fits(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode, true),
                "%s: system %d (n = %d, nnz = %d) fits the one-workgroup solver without a preconditioner but not with one: "
                "the preconditioned solver needs %zu bytes of LDS, 128 more, and the cap is 159744", fn, s, b->n[(size_t)s], b->nnz[(size_t)s],
                small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], 0, true));
     }
-    BHIP(h, hipSetDevice(b->dev));
+    HIPCHK(h, hipSetDevice(b->dev));
     b->in_session = false;
     const int n_sys = b->n_sys;
     const int64_t N = b->N();
     const size_t D = sizeof(double);
     const bool hs = variant == PRCG_HS;
-    BHIP(h, b->state.ensure((size_t)(jacobi && !hs ? 6 : 4) * N * D));
+    HIPCHK(h, b->state.ensure((size_t)(jacobi && !hs ? 6 : 4) * N * D));
     if (jacobi) {
-        BHIP(h, b->dinv.ensure((size_t)N * D));
-        BHIP(h, b->jac.ensure((size_t)n_sys * sizeof(SmallJacobi)));
+        HIPCHK(h, b->dinv.ensure((size_t)N * D));
+        HIPCHK(h, b->jac.ensure((size_t)n_sys * sizeof(SmallJacobi)));
     }
-    BHIP(h, b->rhs.ensure((size_t)N * D));
-    BHIP(h, b->x0.ensure((size_t)N * D));
-    BHIP(h, b->tmp.ensure((size_t)N * D));
-    BHIP(h, b->dots.ensure((size_t)n_sys * (max_iter + 1) * kNS * D));
-    BHIP(h, b->coef.ensure((size_t)n_sys * (max_iter + 1) * kCoefStride * D));
-    BHIP(h, b->desc.ensure((size_t)n_sys * sizeof(SmallArgs)));
-    BHIP(h, b->init.ensure((size_t)n_sys * sizeof(SmallInit)));
+    HIPCHK(h, b->rhs.ensure((size_t)N * D));
+    HIPCHK(h, b->x0.ensure((size_t)N * D));
+    HIPCHK(h, b->tmp.ensure((size_t)N * D));
+    HIPCHK(h, b->dots.ensure((size_t)n_sys * (max_iter + 1) * kNS * D));
+    HIPCHK(h, b->coef.ensure((size_t)n_sys * (max_iter + 1) * kCoefStride * D));
+    HIPCHK(h, b->desc.ensure((size_t)n_sys * sizeof(SmallArgs)));
+    HIPCHK(h, b->init.ensure((size_t)n_sys * sizeof(SmallInit)));
     const bool stopping = !b->rr_stop.empty();
     if (stopping) {
-        BHIP(h, b->stop.ensure((size_t)n_sys * sizeof(SmallStop)));
-        BHIP(h, b->words.ensure((size_t)n_sys * 2 * sizeof(int32_t)));
+        HIPCHK(h, b->stop.ensure((size_t)n_sys * sizeof(SmallStop)));
+        HIPCHK(h, b->words.ensure((size_t)n_sys * 2 * sizeof(int32_t)));
     }
     b->stopping = stopping;
     b->variant = variant; b->hs = hs; b->jacobi = jacobi; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
@@ -281,27 +266,27 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
         }
     }
     hipStream_t sc = b->sc;
-    BHIP(h, hipMemsetAsync(b->dots.p, 0, (size_t)n_sys * (max_iter + 1) * kNS * D, sc));
-    BHIP(h, hipMemsetAsync(b->coef.p, 0, (size_t)n_sys * (max_iter + 1) * kCoefStride * D, sc));
-    BHIP(h, hipMemcpyAsync(b->rhs.p, rhs, (size_t)N * D, hipMemcpyHostToDevice, sc));
-    BHIP(h, hipMemcpyAsync(b->x0.p, x0, (size_t)N * D, hipMemcpyHostToDevice, sc));
-    BHIP(h, hipMemcpyAsync(b->desc.p, desc.data(), (size_t)n_sys * sizeof(SmallArgs), hipMemcpyHostToDevice, sc));
-    BHIP(h, hipMemcpyAsync(b->init.p, init.data(), (size_t)n_sys * sizeof(SmallInit), hipMemcpyHostToDevice, sc));
+    HIPCHK(h, hipMemsetAsync(b->dots.p, 0, (size_t)n_sys * (max_iter + 1) * kNS * D, sc));
+    HIPCHK(h, hipMemsetAsync(b->coef.p, 0, (size_t)n_sys * (max_iter + 1) * kCoefStride * D, sc));
+    HIPCHK(h, hipMemcpyAsync(b->rhs.p, rhs, (size_t)N * D, hipMemcpyHostToDevice, sc));
+    HIPCHK(h, hipMemcpyAsync(b->x0.p, x0, (size_t)N * D, hipMemcpyHostToDevice, sc));
+    HIPCHK(h, hipMemcpyAsync(b->desc.p, desc.data(), (size_t)n_sys * sizeof(SmallArgs), hipMemcpyHostToDevice, sc));
+    HIPCHK(h, hipMemcpyAsync(b->init.p, init.data(), (size_t)n_sys * sizeof(SmallInit), hipMemcpyHostToDevice, sc));
     if (jacobi) {
-        BHIP(h, hipMemcpyAsync(b->dinv.p, inv_diag, (size_t)N * D, hipMemcpyHostToDevice, sc));
-        BHIP(h, hipMemcpyAsync(b->jac.p, jac.data(), (size_t)n_sys * sizeof(SmallJacobi), hipMemcpyHostToDevice, sc));
+        HIPCHK(h, hipMemcpyAsync(b->dinv.p, inv_diag, (size_t)N * D, hipMemcpyHostToDevice, sc));
+        HIPCHK(h, hipMemcpyAsync(b->jac.p, jac.data(), (size_t)n_sys * sizeof(SmallJacobi), hipMemcpyHostToDevice, sc));
     }
     if (stopping) {
-        BHIP(h, hipMemcpyAsync(b->stop.p, stop.data(), (size_t)n_sys * sizeof(SmallStop), hipMemcpyHostToDevice, sc));
-        BHIP(h, hipMemcpyAsync(b->words.p, words.data(), (size_t)n_sys * 2 * sizeof(int32_t), hipMemcpyHostToDevice, sc));
+        HIPCHK(h, hipMemcpyAsync(b->stop.p, stop.data(), (size_t)n_sys * sizeof(SmallStop), hipMemcpyHostToDevice, sc));
+        HIPCHK(h, hipMemcpyAsync(b->words.p, words.data(), (size_t)n_sys * 2 * sizeof(int32_t), hipMemcpyHostToDevice, sc));
     }
-    BHIP(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
+    HIPCHK(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
     for (int m = 1; m >= 0; --m) {                 // one initialisation launch per group
         if (!b->count[m]) continue;
         if (launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), jacobi ? b->jac_of(m) : nullptr, b->count[m], hs) < 0)
-            return batch_fail(h, PRCG_EHIP, "%s: kernel launch failed", fn);
+            return fail(h, PRCG_EHIP, "%s: kernel launch failed", fn);
     }
-    BHIP(h, hipStreamSynchronize(sc));
+    HIPCHK(h, hipStreamSynchronize(sc));
     b->in_session = true;
     return PRCG_OK;
 }
@@ -320,17 +305,17 @@ int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, con
 int prcg_batch_iterate(prcg_batch_t* b, int iters) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session, "prcg_batch_iterate: no open session");
-    BCHECK(h, iters >= 0, "prcg_batch_iterate: negative count");
-    BCHECK(h, b->k + iters <= b->max_iter, "prcg_batch_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters, b->max_iter, b->k);
+    CHECK(h, b->in_session, "prcg_batch_iterate: no open session");
+    CHECK(h, iters >= 0, "prcg_batch_iterate: negative count");
+    CHECK(h, b->k + iters <= b->max_iter, "prcg_batch_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters, b->max_iter, b->k);
     if (iters == 0) return PRCG_OK;
-    BHIP(h, hipSetDevice(b->dev));
+    HIPCHK(h, hipSetDevice(b->dev));
     const int meurant = b->variant == PRCG_PIPE_PR_M ? 1 : 0;
     for (int m = 1; m >= 0; --m) {                 // one launch per group: every system advances by iters
         if (!b->count[m]) continue;
         const SmallBatchArgs g{b->desc_of(m), b->jacobi ? b->jac_of(m) : nullptr, b->stopping ? b->stop_of(m) : nullptr, b->k, iters, meurant};
         const int rc = launch_small_batch(b->sc, g, b->count[m], m, b->lds[m][b->jacobi], b->hs);
-        if (rc < 0) return batch_fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
+        if (rc < 0) return fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
     }
     b->k += iters;
     return PRCG_OK;
@@ -338,8 +323,8 @@ int prcg_batch_iterate(prcg_batch_t* b, int iters) {
 
 int prcg_batch_sync(prcg_batch_t* b) {
     if (!b) return PRCG_EINVAL;
-    BHIP(b->h, hipSetDevice(b->dev));
-    BHIP(b->h, hipStreamSynchronize(b->sc));
+    HIPCHK(b->h, hipSetDevice(b->dev));
+    HIPCHK(b->h, hipStreamSynchronize(b->sc));
     return PRCG_OK;
 }
 
@@ -350,7 +335,7 @@ int prcg_batch_set_stop(prcg_batch_t* b, const double* rr_stop) {
     prcg_t* h = b->h;
     if (!rr_stop) { b->rr_stop.clear(); return PRCG_OK; }
     for (int s = 0; s < b->n_sys; ++s)
-        BCHECK(h, std::isfinite(rr_stop[s]) && rr_stop[s] >= 0.0, "prcg_batch_set_stop: rr_stop[%d] = %g: the threshold of system %d must be "
+        CHECK(h, std::isfinite(rr_stop[s]) && rr_stop[s] >= 0.0, "prcg_batch_set_stop: rr_stop[%d] = %g: the threshold of system %d must be "
                "finite and >= 0 (a bound on r.r; 0 stops on an exactly zero residual only)", s, rr_stop[s], s);
     b->rr_stop.assign(rr_stop, rr_stop + b->n_sys);
     return PRCG_OK;
@@ -359,39 +344,39 @@ int prcg_batch_set_stop(prcg_batch_t* b, const double* rr_stop) {
 int prcg_batch_get_stops(prcg_batch_t* b, int32_t* k_stop, int32_t* status) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session, "prcg_batch_get_stops: no open session");
-    BCHECK(h, k_stop && status, "prcg_batch_get_stops: null buffer");
-    BHIP(h, hipSetDevice(b->dev));
-    BHIP(h, hipStreamSynchronize(b->sc));
+    CHECK(h, b->in_session, "prcg_batch_get_stops: no open session");
+    CHECK(h, k_stop && status, "prcg_batch_get_stops: null buffer");
+    HIPCHK(h, hipSetDevice(b->dev));
+    HIPCHK(h, hipStreamSynchronize(b->sc));
     if (!b->stopping) {
         for (int s = 0; s < b->n_sys; ++s) { k_stop[s] = -1; status[s] = 0; }
         return PRCG_OK;
     }
     std::vector<int32_t> words((size_t)b->n_sys * 2);
-    BHIP(h, hipMemcpyAsync(words.data(), b->words.p, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b->sc));
-    BHIP(h, hipStreamSynchronize(b->sc));
+    HIPCHK(h, hipMemcpyAsync(words.data(), b->words.p, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b->sc));
+    HIPCHK(h, hipStreamSynchronize(b->sc));
     for (int s = 0; s < b->n_sys; ++s) { k_stop[s] = words[(size_t)2 * s]; status[s] = words[(size_t)2 * s + 1]; }
     return PRCG_OK;
 }
 
 static int batch_d2h(prcg_batch_t* b, double* dst, const double* src, int64_t count) {
-    BHIP(b->h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->sc));
-    BHIP(b->h, hipStreamSynchronize(b->sc));
+    HIPCHK(b->h, hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->sc));
+    HIPCHK(b->h, hipStreamSynchronize(b->sc));
     return PRCG_OK;
 }
 
 int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session && out, "prcg_batch_get_vector: no session or null buffer");
-    BCHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_vector: system %d outside [0, %d)", s, b->n_sys);
+    CHECK(h, b->in_session && out, "prcg_batch_get_vector: no session or null buffer");
+    CHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_vector: system %d outside [0, %d)", s, b->n_sys);
     const bool tilde = which == PRCG_VEC_RT || which == PRCG_VEC_ST;
-    BCHECK(h, !tilde || (b->jacobi && !b->hs), "prcg_batch_get_vector: vector %d (PRCG_VEC_RT / _ST) is held by a pipelined session begun "
+    CHECK(h, !tilde || (b->jacobi && !b->hs), "prcg_batch_get_vector: vector %d (PRCG_VEC_RT / _ST) is held by a pipelined session begun "
            "with prcg_batch_begin_jacobi only: this session is %s", which, b->jacobi ? "Hestenes-Stiefel, which forms r~ anew in every iteration"
                                                                                      : "unpreconditioned");
-    BCHECK(h, tilde || which == PRCG_VEC_X || which == PRCG_VEC_R || which == PRCG_VEC_P || which == PRCG_VEC_S,
+    CHECK(h, tilde || which == PRCG_VEC_X || which == PRCG_VEC_R || which == PRCG_VEC_P || which == PRCG_VEC_S,
            "prcg_batch_get_vector: vector %d is not part of a batch session (PRCG_VEC_X, _R, _P, _S)", which);
-    BHIP(h, hipSetDevice(b->dev));
+    HIPCHK(h, hipSetDevice(b->dev));
     const int64_t N = b->N(), v = b->voff[(size_t)s], n = b->n[(size_t)s];
     if (tilde) {                                   // the pair array (r~,s~) follows (x,p) and (r,s)
         launch_copy(b->sc, b->tmp.d(), 1, b->state.d() + 4 * N + 2 * v + (which == PRCG_VEC_ST ? 1 : 0), 2, n);
@@ -407,8 +392,8 @@ int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out) {
 int prcg_batch_get_solutions(prcg_batch_t* b, double* x_cat) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session && x_cat, "prcg_batch_get_solutions: no session or null buffer");
-    BHIP(h, hipSetDevice(b->dev));
+    CHECK(h, b->in_session && x_cat, "prcg_batch_get_solutions: no session or null buffer");
+    HIPCHK(h, hipSetDevice(b->dev));
     const int64_t N = b->N();
     if (b->hs) return batch_d2h(b, x_cat, b->state.d(), N);
     launch_copy(b->sc, b->tmp.d(), 1, b->state.d(), 2, N);       // the x of every (x,p) pair, all systems at once
@@ -418,34 +403,34 @@ int prcg_batch_get_solutions(prcg_batch_t* b, double* x_cat) {
 int prcg_batch_get_scalars(prcg_batch_t* b, int k, int s, double* out) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session && out && k >= 0 && k <= b->max_iter && s >= 0 && s < b->n_sys, "prcg_batch_get_scalars: bad argument");
-    BHIP(h, hipSetDevice(b->dev));
+    CHECK(h, b->in_session && out && k >= 0 && k <= b->max_iter && s >= 0 && s < b->n_sys, "prcg_batch_get_scalars: bad argument");
+    HIPCHK(h, hipSetDevice(b->dev));
     return batch_d2h(b, out, b->dots_of(s) + (size_t)k * kNS, kNS);
 }
 
 int prcg_batch_get_coefficients(prcg_batch_t* b, int k, int s, double* out) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session && out && k >= 1 && k <= b->max_iter && s >= 0 && s < b->n_sys, "prcg_batch_get_coefficients: bad argument");
-    BHIP(h, hipSetDevice(b->dev));
+    CHECK(h, b->in_session && out && k >= 1 && k <= b->max_iter && s >= 0 && s < b->n_sys, "prcg_batch_get_coefficients: bad argument");
+    HIPCHK(h, hipSetDevice(b->dev));
     return batch_d2h(b, out, b->coef_of(s) + (size_t)k * kCoefStride, 3);
 }
 
 int prcg_batch_get_history(prcg_batch_t* b, int s, double* hist) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
-    BCHECK(h, b->in_session && hist, "prcg_batch_get_history: no session or null buffer");
-    BCHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_history: system %d outside [0, %d)", s, b->n_sys);
+    CHECK(h, b->in_session && hist, "prcg_batch_get_history: no session or null buffer");
+    CHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_history: system %d outside [0, %d)", s, b->n_sys);
     if (!(b->hist_mask & PRCG_HIST_UPDATED_RESIDUAL_2_NORM)) return PRCG_OK;
-    BHIP(h, hipSetDevice(b->dev));
+    HIPCHK(h, hipSetDevice(b->dev));
     const int m = b->max_iter;
     std::vector<double> all((size_t)(m + 1) * kNS);
     if (int rc = batch_d2h(b, all.data(), b->dots_of(s), (int64_t)(m + 1) * kNS)) return rc;
     int last = b->k;                               // a stopped system has entries up to its stop iteration
     if (b->stopping) {
         int32_t word[2];
-        BHIP(h, hipMemcpyAsync(word, static_cast<const int32_t*>(b->words.p) + 2 * s, sizeof(word), hipMemcpyDeviceToHost, b->sc));
-        BHIP(h, hipStreamSynchronize(b->sc));
+        HIPCHK(h, hipMemcpyAsync(word, static_cast<const int32_t*>(b->words.p) + 2 * s, sizeof(word), hipMemcpyDeviceToHost, b->sc));
+        HIPCHK(h, hipStreamSynchronize(b->sc));
         if (word[0] >= 0 && word[0] < last) last = word[0];
     }
     for (int k = 0; k < m; ++k) hist[k] = k <= last ? std::sqrt(all[(size_t)k * kNS + PRCG_S_RR]) : 0.0;

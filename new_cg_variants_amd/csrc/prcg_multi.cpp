@@ -1,0 +1,400 @@
+// Sessions with two or four right-hand sides: prcg_solve_begin_multi (Hestenes-Stiefel, predict-and-recompute),
+// prcg_solve_begin_multi_pipe (pipelined predict-and-recompute), their iterations (iterate_multi, called by prcg_iterate)
+// and the per-column getters.  Built from the services of prcg_engine.cpp and open_session (prcg_handle.h); the kernels:
+// prcg_rhs2.hip.  Host code only.
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <vector>
+
+#include "../../include/prcg.h"
+#include "prcg_handle.h"
+
+using namespace prcg;
+
+namespace {
+
+// Two right-hand sides in one Hestenes-Stiefel session (hs_cg.py:54-62 / hs_pcg :116-125 for each column): the vector
+// kernels of prcg_rhs2.hip around ONE two-vector product of [p_0 p_1] -- the operator is streamed once for both systems.
+// Four right-hand sides are two PAIR GROUPS, each a complete state of this kind (its own arrays, block partials and rows of
+// dots / coef: group g's rows follow group g - 1's max_iter + 1 iterations), around ONE product of both groups' directions.
+bool pr2(const prcg_t* h) { return h->rhs2 && is_pr(h->variant); }
+// the session keeps one scalar and one coefficient row per column and iteration, each in the single-session order
+bool two_rows(const prcg_t* h) { return pr2(h) || h->pipe2; }
+// pair group g (Handle::grp[g]): its first row of dots / coef ...
+int row0(const prcg_t* h, int g) { return g * (h->max_iter + 1) * (pr2(h) ? 2 : 1); }
+// ... and its block partials: the first group's are the handle's, the second group has its own
+double* part_a(prcg_t* h, int g) { return (g == 0 ? h->partA : h->partA1).d(); }
+double* part_b(prcg_t* h, int g) { return (g == 0 ? h->partB : h->partB1).d(); }
+// s = A p of every column: one two-vector product, or with two pair groups one product of [P_0 P_1 | P_2 P_3]
+int multi_product(prcg_t* h, int k) {
+    PairBufs* G = h->grp;
+    bool on = false;
+    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+    if (h->groups == 2) LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, G[0].p.d(), G[1].p.d(), G[0].s.d(), G[1].s.d()));
+    else LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, G[0].p.d(), G[0].s.d(), 3));
+    prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+    return PRCG_OK;
+}
+Hs2Args hs2_args(prcg_t* h, int k, int g) {
+    const PairBufs& G = h->grp[g];
+    Hs2Args a{};
+    a.n = h->n;
+    a.x = G.x.d(); a.r = G.r.d(); a.rt = h->prec ? G.rt.d() : nullptr; a.p = G.p.d(); a.s = G.s.d();
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, row0(h, g) + k - 1) : nullptr;
+    a.dots_cur = dots_at(h, row0(h, g) + k);
+    a.coef_out = coef_at(h, row0(h, g) + k);
+    a.partials = part_a(h, g);
+    return a;
+}
+// s = A p for every column, then per group mu_c = p.s (a launch of its own: the multi-vector products have no dot epilogue)
+int hs2_product_and_mu(prcg_t* h, int k) {
+    int rc = multi_product(h, k);
+    if (rc) return rc;
+    for (int g = 0; g < h->groups; ++g) {
+        Hs2Args a = hs2_args(h, k, g);
+        a.partials = part_b(h, g);
+        const int grid = launch_hs2_dot_ps(h->sc, a);
+        LAUNCHCHK(h, grid);
+        launch_reduce_final(h->sc, a.partials, grid, dots_at(h, row0(h, g) + k), kHs2Mu, kHs2Mu, 2);
+    }
+    return PRCG_OK;
+}
+int iterate_hs2(prcg_t* h, int k) {
+    for (int g = 0; g < h->groups; ++g) {
+        const Hs2Args a = hs2_args(h, k, g);
+        bool on = false;
+        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);             // (the sample: the first group's update launch)
+        const int g1 = launch_hs2_update_xr(h->sc, a);
+        LAUNCHCHK(h, g1);
+        prof_end(h, h->ev_upd, h->n_ev_upd, on);
+        launch_reduce_final(h->sc, a.partials, g1, dots_at(h, row0(h, g) + k), kHs2Nu, kHs2Nu, 4);     // nu_0, rr_0, nu_1, rr_1
+        LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));
+    }
+    return hs2_product_and_mu(h, k);
+}
+
+// Two right-hand sides in one predict-and-recompute session (pr_cg.py:146-158 for each column; PRCG_M: Meurant's prediction):
+// update, ONE two-vector product of [p_0 p_1], the three inner products that need s, one reduction launch per column.
+Pr2Args pr2_args(prcg_t* h, int k, int g) {
+    const PairBufs& G = h->grp[g];
+    Pr2Args a{};
+    a.n = h->n;
+    a.x = G.x.d(); a.r = G.r.d(); a.p = G.p.d(); a.s = G.s.d();
+    a.rt = h->prec ? G.rt.d() : nullptr; a.st = h->prec ? G.st.d() : nullptr;
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, row0(h, g) + 2 * (k - 1)) : nullptr;   // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
+    a.coef_out = coef_at(h, row0(h, g) + 2 * k);
+    a.part0 = part_a(h, g); a.part1 = part_b(h, g);
+    a.meurant = meurant(h->variant);
+    return a;
+}
+// s = A p for every column, (s~ = d s), mu, dl, gm; then the five sums of each column: rows 2 k and 2 k + 1 of its group
+// (g_upd[g]: the grid of group g's update launch, whose partials the sums include)
+int pr2_product_and_sums(prcg_t* h, int k, const int* g_upd) {
+    int rc = multi_product(h, k);
+    if (rc) return rc;
+    for (int g = 0; g < h->groups; ++g) {
+        const Pr2Args a = pr2_args(h, k, g);
+        const int grid = launch_pr2_dots(h->sc, a);
+        LAUNCHCHK(h, grid);
+        CHECK(h, grid == g_upd[g], "two-RHS session: the update and the dots launch disagree on the grid (%d, %d)", g_upd[g], grid);
+        const int row = row0(h, g) + 2 * k;
+        launch_reduce_final(h->sc, a.part0, grid, dots_at(h, row), 0, 0, 5);
+        launch_reduce_final(h->sc, a.part1, grid, dots_at(h, row + 1), 0, 0, 5);
+    }
+    return PRCG_OK;
+}
+int iterate_pr2(prcg_t* h, int k) {
+    int g_upd[2] = {0, 0};
+    for (int g = 0; g < h->groups; ++g) {
+        const Pr2Args a = pr2_args(h, k, g);
+        bool on = false;
+        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);             // (the sample: the first group's update launch)
+        g_upd[g] = launch_pr2_update(h->sc, a);
+        LAUNCHCHK(h, g_upd[g]);
+        prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    }
+    return pr2_product_and_sums(h, k, g_upd);
+}
+
+// Two right-hand sides in one pipelined predict-and-recompute session (pipe_pr_cg.py:61-75 / :169-187 for each column; the
+// flavours that recompute w): ONE update launch for both columns, one reduction launch per column, ONE product of four vectors
+// [w_0 u_0 | w_1 u_1] = A [r_0 s_0 | r_1 s_1] (with Jacobi of the (r~,s~) pairs) -- the operator is streamed once for both systems.
+Pipe2Args pipe2_args(prcg_t* h, int k) {
+    Pipe2Args a{};
+    a.n = h->n;
+    for (int c = 0; c < 2; ++c) {
+        a.xp[c] = h->cxp[c].d(); a.rs[c] = h->crs[c].d(); a.wu[c] = h->cwu[c].d();
+        a.rst[c] = h->prec ? h->crst[c].d() : nullptr;
+    }
+    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.dots_prev = k > 0 ? dots_at(h, 2 * (k - 1)) : nullptr;                // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
+    a.coef_out = coef_at(h, 2 * k);
+    a.part0 = h->partA.d(); a.part1 = h->partB.d();
+    a.meurant = meurant(h->variant);
+    return a;
+}
+// the five sums of each column from the block partials an update (or dots) launch of `grid` blocks left: rows 2 k, 2 k + 1
+void pipe2_reduce(prcg_t* h, int k, int grid) {
+    launch_reduce_final(h->sc, h->partA.d(), grid, dots_at(h, 2 * k), 0, 0, 5);
+    launch_reduce_final(h->sc, h->partB.d(), grid, dots_at(h, 2 * k + 1), 0, 0, 5);
+}
+// (w_c, u_c) = A (r_c, s_c) of both columns (Jacobi: A (r~_c, s~_c)): one launch on sliced rows, else two two-vector launches
+int pipe2_product(prcg_t* h) {
+    DevBuf* src = h->prec ? h->crst : h->crs;
+    LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, src[0].d(), src[1].d(), h->cwu[0].d(), h->cwu[1].d()));
+    return PRCG_OK;
+}
+int iterate_pipe2(prcg_t* h, int k) {
+    const Pipe2Args a = pipe2_args(h, k);
+    bool on = false;
+    prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
+    const int grid = launch_pipe2_update(h->sc, a);
+    LAUNCHCHK(h, grid);
+    prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    pipe2_reduce(h, k, grid);
+    prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+    const int rc = pipe2_product(h);
+    if (rc) return rc;
+    prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+    return PRCG_OK;
+}
+
+// what no session with several right-hand sides serves, refused in the name of the entry that was called
+int refuse_unserved(prcg_t* h, const char* who, uint32_t hist_mask) {
+    CHECK(h, !h->multi(), "%s: a communicator is set on the handle: the two-RHS session runs on one GPU", who);
+    CHECK(h, h->g == 0, "%s: n_ghost = %lld > 0: the two-RHS session serves whole operators only", who, (long long)h->g);
+    CHECK(h, h->cb == nullptr, "%s: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
+                               "session serves Jacobi (inv_diag) or none", who);
+    CHECK(h, !h->have_block_jacobi(), "%s: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
+                            "session serves Jacobi (inv_diag) or none", who);
+    CHECK(h, h->replace_fn == nullptr, "%s: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session", who);
+    CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+          "%s: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the two-RHS session", who);
+    return PRCG_OK;
+}
+
+}  // namespace
+
+int prcg::iterate_multi(prcg_t* h, int k) {
+    return h->pipe2 ? iterate_pipe2(h, k) : pr2(h) ? iterate_pr2(h, k) : iterate_hs2(h, k);
+}
+
+extern "C" {
+
+// ---- two or four right-hand sides in one session: Hestenes-Stiefel, predict-and-recompute (PRCG_PR, PRCG_M) ----
+int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
+                           const double* inv_diag, uint32_t hist_mask) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, nrhs == 2 || nrhs == 4, "prcg_solve_begin_multi: nrhs = %d: the multi-RHS session serves exactly 2 right-hand sides "
+                                     "(or 4, as two pairs)", nrhs);
+    CHECK(h, variant == PRCG_HS || is_pr(variant), "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg), "
+                                                   "PRCG_PR (pr_cg / pr_pcg) and PRCG_M (m_cg / m_pcg) only", variant);
+    if (int rc = refuse_unserved(h, "prcg_solve_begin_multi", hist_mask)) return rc;
+    bool have_all = b && x0;
+    for (int j = 0; have_all && j < nrhs; ++j) have_all = b[j] && x0[j];
+    CHECK(h, have_all, "prcg_solve_begin_multi: null b or x0");
+    const int64_t n = h->n, ne = h->n + kGatherPad;
+    const size_t D = sizeof(double);
+    const int groups = nrhs / 2;
+    const bool pr = is_pr(variant);
+    // X and P feed the product: like every product source they carry the spare entries behind row n.  The second pair
+    // group's arrays (and its block partials) follow the first's, and only a four-RHS session asks for them.
+    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D, tilde = inv_diag ? vec : 16, part = (size_t)8192 * kPartialStride * D;
+    PairBufs* const G = h->grp;
+    int rc;
+    if (groups == 1 && !pr)
+        rc = open_session(h, "prcg_solve_begin_multi", PRCG_HS, max_iter, hist_mask, inv_diag, false,
+                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, tilde}});
+    else if (groups == 1)
+        rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
+                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, tilde}, {&G[0].st, tilde}}, 2);
+    else
+        rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
+                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, tilde}, {&G[0].st, pr ? tilde : 16},
+                           {&G[1].x, src}, {&G[1].p, src}, {&G[1].r, vec}, {&G[1].s, vec}, {&G[1].rt, tilde}, {&G[1].st, pr ? tilde : 16},
+                           {&h->partA1, part}, {&h->partB1, part}}, (pr ? 2 : 1) * 2);
+    if (rc) return rc;
+    h->rhs2 = true;
+    h->groups = groups;
+    h->spmm4 = groups == 2 && spmm4_one_launch(h);
+    for (int g = 0; g < groups; ++g) {
+        if ((rc = upload_pairs(h, "prcg_solve_begin_multi", G[g].x.d(), x0[2 * g], x0[2 * g + 1]))) return rc;
+        if ((rc = upload_pairs(h, "prcg_solve_begin_multi", G[g].r.d(), b[2 * g], b[2 * g + 1]))) return rc;
+    }
+    hipStream_t sc = h->sc;
+    // r = b - A x0 for every column (hs_cg.py:23): one product of [x0_0 x0_1] (| [x0_2 x0_3]), parked in S
+    if (groups == 2) LAUNCHCHK(h, eng_spmm4(h, sc, 0, G[0].x.d(), G[1].x.d(), G[0].s.d(), G[1].s.d()));
+    else LAUNCHCHK(h, eng_spmm2(h, sc, 0, G[0].x.d(), G[0].s.d(), 3));
+    for (int g = 0; g < groups; ++g) launch_sub(sc, G[g].r.d(), 1, G[g].r.d(), 1, G[g].s.d(), 1, 2 * n);
+    if (pr2(h)) {
+        int g0[2] = {0, 0};
+        for (int g = 0; g < groups; ++g) {
+            g0[g] = launch_pr2_init_dots(sc, pr2_args(h, 0, g));             // (r~ = d r); nu = r~.r, r.r   pr_cg.py:108-109
+            LAUNCHCHK(h, g0[g]);
+            launch_copy(sc, G[g].p.d(), 1, h->prec ? G[g].rt.d() : G[g].r.d(), 1, 2 * n);   // p = r~ (r)   :110
+        }
+        if ((rc = pr2_product_and_sums(h, 0, g0))) return rc;                // s = A p, (s~ = d s), mu, dl, gm   :111-116
+        HIPCHK(h, hipStreamSynchronize(sc));
+        h->in_session = true;
+        return PRCG_OK;
+    }
+    for (int g = 0; g < groups; ++g) {
+        const Hs2Args a = hs2_args(h, 0, g);
+        const int g1 = launch_hs2_init_dots(sc, a);                          // (r~ = d r); nu = r.r~, r.r   :25 / :86-88
+        LAUNCHCHK(h, g1);
+        launch_reduce_final(sc, a.partials, g1, dots_at(h, row0(h, g)), kHs2Nu, kHs2Nu, 4);
+        launch_copy(sc, G[g].p.d(), 1, h->prec ? G[g].rt.d() : G[g].r.d(), 1, 2 * n);   // p = r~ (r)   :24 / :87
+    }
+    if ((rc = hs2_product_and_mu(h, 0))) return rc;                          // s = A p, mu = p.s   :26-27
+    HIPCHK(h, hipStreamSynchronize(sc));
+    h->in_session = true;
+    return PRCG_OK;
+}
+
+// ---- two right-hand sides in one pipelined predict-and-recompute session (PRCG_PIPE_PR, PRCG_PIPE_PR_M) ----
+int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
+                                const double* inv_diag, uint32_t hist_mask) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, variant != PRCG_PIPE_P && variant != PRCG_PIPE_P_M, "prcg_solve_begin_multi_pipe: variant %d: the stored-w flavours (PRCG_PIPE_P, "
+          "PRCG_PIPE_P_M) are not served: the pipelined two-RHS session recomputes w = A r in its four-vector product", variant);
+    CHECK(h, pipe_recompute(variant), "prcg_solve_begin_multi_pipe: variant %d: the pipelined two-RHS session serves PRCG_PIPE_PR (pipe_pr_cg / "
+                                      "pipe_pr_pcg) and PRCG_PIPE_PR_M (pipe_pr_m_cg / pipe_pr_m_pcg) only", variant);
+    CHECK(h, nrhs == 2, "prcg_solve_begin_multi_pipe: nrhs = %d: the pipelined session serves exactly 2 right-hand sides (its product is the "
+                        "four-vector one; an eight-vector product does not exist)", nrhs);
+    if (int rc = refuse_unserved(h, "prcg_solve_begin_multi_pipe", hist_mask)) return rc;
+    CHECK(h, b && x0 && b[0] && b[1] && x0[0] && x0[1], "prcg_solve_begin_multi_pipe: null b or x0");
+    const int64_t n = h->n, ne = h->n + kGatherPad;
+    const size_t D = sizeof(double);
+    // the pair array that feeds the product -- (r,s), with Jacobi (r~,s~) -- carries the spare entries of every product source
+    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D;
+    int rc = open_session(h, "prcg_solve_begin_multi_pipe", variant, max_iter, hist_mask, inv_diag, false,
+                          {{&h->cxp[0], vec}, {&h->cxp[1], vec}, {&h->crs[0], inv_diag ? vec : src}, {&h->crs[1], inv_diag ? vec : src},
+                           {&h->cwu[0], vec}, {&h->cwu[1], vec}, {&h->crst[0], inv_diag ? src : 16}, {&h->crst[1], inv_diag ? src : 16},
+                           {&h->b, vec}}, 2);
+    if (rc) return rc;
+    h->rhs2 = true;
+    h->groups = 1;
+    h->pipe2 = true;
+    h->spmm4 = spmm4_one_launch(h);
+    if ((rc = upload_pairs(h, "prcg_solve_begin_multi_pipe", h->tmp_ext.d(), x0[0], x0[1]))) return rc;
+    if ((rc = upload_pairs(h, "prcg_solve_begin_multi_pipe", h->b.d(), b[0], b[1]))) return rc;
+    hipStream_t sc = h->sc;
+    DevBuf* in = h->prec ? h->crst : h->crs;                                  // the product's source pairs
+    // r = b - A x0 of both columns: one two-vector product of [x0_0 x0_1]   (pipe_pr_cg.py:22-23)
+    LAUNCHCHK(h, eng_spmm2(h, sc, 0, h->tmp_ext.d(), h->t1.d(), 3));
+    for (int c = 0; c < 2; ++c) {
+        launch_copy(sc, h->cxp[c].d(), 2, h->tmp_ext.d() + c, 2, n);                       // x = x0
+        launch_sub(sc, h->crs[c].d(), 2, h->b.d() + c, 2, h->t1.d() + c, 2, n);             // r = b - A x
+        if (h->prec) launch_mul(sc, h->crst[c].d(), 2, h->dinv.d(), 1, h->crs[c].d(), 2, n);   // r~ = M^-1 r    :124
+        launch_copy(sc, h->cxp[c].d() + 1, 2, in[c].d(), 2, n);                             // p = r (r~)     :24 / :125
+    }
+    // s = A p: p is r (r~), so the product of the source pairs -- their second halves still zero -- leaves it in w's place
+    if ((rc = pipe2_product(h))) return rc;
+    for (int c = 0; c < 2; ++c) {
+        launch_copy(sc, h->crs[c].d() + 1, 2, h->cwu[c].d(), 2, n);                         // s = A p        :26 / :127
+        if (h->prec) launch_mul(sc, h->crst[c].d() + 1, 2, h->dinv.d(), 1, h->crs[c].d() + 1, 2, n);   // s~ = M^-1 s   :128
+    }
+    // (w, u) = A (r, s) (A (r~, s~)): w = A p again, the bits of `w = s.copy()` (:27 / :129), and u = A w = A s (A s~)   :28 / :131
+    if ((rc = pipe2_product(h))) return rc;
+    const int grid = launch_pipe2_dots(sc, pipe2_args(h, 0));                               // mu, delta, gamma, nu, r.r   :25-36 / :126-140
+    LAUNCHCHK(h, grid);
+    pipe2_reduce(h, 0, grid);
+    HIPCHK(h, hipStreamSynchronize(sc));
+    h->in_session = true;
+    return PRCG_OK;
+}
+
+// (column j of a four-RHS session: column j % 2 of pair group j / 2 -- per column what a two-RHS session returns)
+#define NEED_RHS2(h, name, j)                                                                                        \
+    do {                                                                                                              \
+        CHECK(h, (h)->in_session && (h)->rhs2, name ": no open two-RHS session (prcg_solve_begin_multi)");             \
+        CHECK(h, (j) >= 0 && (j) < 2 * (h)->groups, (h)->groups == 2 ? name ": right-hand side %d out of range (0 .. 3)"  \
+                                                                    : name ": right-hand side %d out of range (0, 1)", (int)(j)); \
+    } while (0)
+
+int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_vector_rhs", j);
+    CHECK(h, out, "prcg_get_vector_rhs: null buffer");
+    if (h->pipe2) {
+        // column j's pairs: (x,p), (r,s), (w,u) -- w = A r, u = A s as the iteration's product left them -- and with Jacobi (r~,s~)
+        const double* src = which == PRCG_VEC_X ? h->cxp[j].d() : which == PRCG_VEC_P ? h->cxp[j].d() + 1 :
+                            which == PRCG_VEC_R ? h->crs[j].d() : which == PRCG_VEC_S ? h->crs[j].d() + 1 :
+                            which == PRCG_VEC_W ? h->cwu[j].d() : which == PRCG_VEC_U ? h->cwu[j].d() + 1 :
+                            (which == PRCG_VEC_RT && h->prec) ? h->crst[j].d() : (which == PRCG_VEC_ST && h->prec) ? h->crst[j].d() + 1 : nullptr;
+        CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the pipelined two-RHS session (x, r, p, s, w, u; rt, st with Jacobi; "
+                      "w~ and u~ are formed in registers and never stored)", which);
+        int rc = prcg_sync(h);
+        if (rc) return rc;
+        launch_copy(h->sc, h->t1.d(), 1, src, 2, h->n);
+        return d2h(h, out, h->t1.d(), h->n);
+    }
+    const PairBufs& G = h->grp[j / 2];
+    const DevBuf* src = which == PRCG_VEC_X ? &G.x : which == PRCG_VEC_R ? &G.r : which == PRCG_VEC_P ? &G.p :
+                        which == PRCG_VEC_S ? &G.s : (which == PRCG_VEC_RT && h->prec) ? &G.rt :
+                        (which == PRCG_VEC_ST && h->prec && pr2(h)) ? &G.st : nullptr;
+    CHECK(h, src, "prcg_get_vector_rhs: vector %d is not part of the two-RHS session (x, r, p, s; rt with Jacobi; st with Jacobi "
+                  "in a PRCG_PR / PRCG_M session)", which);
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    launch_copy(h->sc, h->t1.d(), 1, src->d() + j % 2, 2, h->n);
+    return d2h(h, out, h->t1.d(), h->n);
+}
+
+int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_scalars_rhs", j);
+    CHECK(h, out && k >= 0 && k <= h->max_iter, "prcg_get_scalars_rhs: bad argument");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    double row[kNS];
+    const int first = row0(h, j / 2);
+    j %= 2;
+    if ((rc = d2h(h, row, dots_at(h, first + (two_rows(h) ? 2 * k + j : k)), kNS))) return rc;
+    for (int q = 0; q < kNS; ++q) out[q] = 0.0;
+    if (two_rows(h)) {
+        for (int q = 0; q <= PRCG_S_RR; ++q) out[q] = row[q];         // mu, dl, gm, nu, rr: the column's own row
+        return PRCG_OK;
+    }
+    out[PRCG_S_MU] = row[kHs2Mu + j]; out[PRCG_S_NU] = row[kHs2Nu + 2 * j]; out[PRCG_S_RR] = row[kHs2Rr + 2 * j];
+    return PRCG_OK;
+}
+
+int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_coefficients_rhs", j);
+    CHECK(h, out && k >= 1 && k <= h->max_iter, "prcg_get_coefficients_rhs: bad argument");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    double row[kCoefStride];
+    const int first = row0(h, j / 2);
+    j %= 2;
+    if ((rc = d2h(h, row, coef_at(h, first + (two_rows(h) ? 2 * k + j : k)), kCoefStride))) return rc;
+    if (two_rows(h)) { out[0] = row[0]; out[1] = row[1]; out[2] = row[2]; return PRCG_OK; }     // a, b, the predicted nu
+    out[0] = row[2 * j]; out[1] = row[2 * j + 1]; out[2] = 0.0;      // Hestenes-Stiefel predicts no nu
+    return PRCG_OK;
+}
+
+int prcg_get_history_rhs(prcg_t* h, int j, double* hist) {
+    if (!h) return PRCG_EINVAL;
+    NEED_RHS2(h, "prcg_get_history_rhs", j);
+    CHECK(h, hist, "prcg_get_history_rhs: null buffer");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    if (!(h->hist_mask & PRCG_HIST_UPDATED_RESIDUAL_2_NORM)) return PRCG_OK;
+    const int m = h->max_iter;
+    const int rows = two_rows(h) ? 2 : 1;
+    std::vector<double> all((size_t)(m + 1) * rows * kNS);
+    if ((rc = d2h(h, all.data(), dots_at(h, row0(h, j / 2)), (int64_t)(m + 1) * rows * kNS))) return rc;
+    j %= 2;
+    for (int k = 0; k < m; ++k) {
+        const double rr = two_rows(h) ? all[(size_t)(2 * k + j) * kNS + PRCG_S_RR] : all[(size_t)k * kNS + kHs2Rr + 2 * j];
+        hist[k] = k <= h->k ? std::sqrt(rr) : 0.0;
+    }
+    return PRCG_OK;
+}
+
+}  // extern "C"

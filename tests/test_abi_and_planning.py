@@ -36,6 +36,25 @@ def test_library_exports_every_declared_symbol():
     assert lib.prcg_version() == 1
 
 
+def test_one_object_list():
+    """The Makefile's OBJS is the one list of what libprcg.so is linked from: every source file under csrc/ has its object
+    in it, and the A/B build scripts take their link line from `make print-objs`, naming only the object they rebuild."""
+    import glob
+    import subprocess
+    objs = subprocess.run(['make', '-s', '-C', ROOT, 'print-objs'], check=True, capture_output=True, text=True).stdout.split()
+    csrc = os.path.join(ROOT, 'new_cg_variants_amd', 'csrc')
+    sources = sorted(glob.glob(os.path.join(csrc, '*.cpp')) + glob.glob(os.path.join(csrc, '*.hip')))
+    assert len(sources) >= 12
+    for src in sources:
+        assert os.path.relpath(os.path.splitext(src)[0] + '.o', ROOT) in objs, f'{src}: its object is not in OBJS'
+    assert len(objs) == len(set(objs)) == len(sources)
+    for script, own in (('build_variants.sh', 'prcg_win.o'), ('build_sell_variants.sh', 'prcg_sell.o')):
+        text = open(os.path.join(ROOT, 'tools', script)).read()
+        assert 'make -s print-objs' in text, script
+        named = set(re.findall(r'csrc\\?/(prcg_\w+\.o)', text))
+        assert named == {own}, f'{script} names {sorted(named)}'
+
+
 def test_no_cpu_fallback_without_gpu():
     """On a machine without a GPU creating a handle must fail loudly."""
     import torch

@@ -1,4 +1,4 @@
-"""A used handle opens every session exactly as a fresh one does (csrc/prcg_engine.cpp: open_session resets the whole
+"""A used handle opens every session exactly as a fresh one does (csrc/prcg_session.cpp: open_session resets the whole
 Session in one place).  cg_variants caches operators so that all nine variants run on ONE handle; here a handle runs a
 sequence of sessions of every family, and each is compared -- on the 64-bit patterns, as tests/test_xp_deferred.py does --
 with the same session on a handle that has never run anything else: every state vector the session serves, the scalars of

@@ -7,7 +7,7 @@ sum of the one-launch pipelined iteration, partials pending across prcg_iterate 
 four-launch predict-and-recompute forms, the unfused Chronopoulos-Gear and Ghysels-Vanroose forms that only these operators
 still run -- changes bits from the iteration at which it goes wrong.
 
-Which launch sums which inner product on these operators (new_cg_variants_amd/csrc/prcg_engine.cpp; "unit tree": the per-lane
+Which launch sums which inner product on these operators (new_cg_variants_amd/csrc/prcg_session.cpp; "unit tree": the per-lane
 sums of the slice / tile launch, block_reduce_store and the 256-thread final tree, UnitTree built from DeviceCSR.layout():
 'slice_rows' or 'tiles', and the workgroups of the launch; "pair tree": the update kernels' two neighbouring elements per
 thread, pair_sum; "pipelined update tree": k_pipe_update, device_dot):

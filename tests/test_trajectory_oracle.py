@@ -5,7 +5,7 @@ every iteration bit for bit, x and r bit for bit, hundreds of iterations: a stal
 wrong, a race or a deferred store applied in the wrong phase changes bits from the iteration at which it happens
 (tests/test_device_order.py shows that for the model's side on the CPU).
 
-Which launch sums which inner product (new_cg_variants_amd/csrc/prcg_engine.cpp; "tile tree": k_win_tiles' per-lane sums,
+Which launch sums which inner product (new_cg_variants_amd/csrc/prcg_session.cpp; "tile tree": k_win_tiles' per-lane sums,
 win_block_reduce_store and the 256-thread final tree, OneLaunchTree built from prcg_debug_layout's workgroups and waves per
 workgroup of the launch; "pair tree": the update kernels' two neighbouring elements per thread, pair_sum; "pipelined update
 tree": k_pipe_update, device_dot):
