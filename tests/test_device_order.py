@@ -4,7 +4,9 @@ What tests/test_trajectory_oracle.py relies on: the tile tree sums every row exa
 (OneLaunchTree), the pair-layout update-kernel tree (pair_sum), the XCD remap, the per-product routing (Routed), the unit
 tree of the sliced-row and CSR-adaptive launches (UnitTree: variable steps per unit, named rows, idle lanes) with the long-row
 product of the CSR-adaptive tiles (LongRowOperator: what tests/test_trajectory_irregular.py relies on) -- and that ONE row summed twice, dropped or taken from a stale buffer at ONE iteration of a run hundreds of iterations long changes
-the bits of that iteration's inner products (so a bit-for-bit comparison with the device sees it)."""
+the bits of that iteration's inner products (so a bit-for-bit comparison with the device sees it); likewise ONE wrong
+application of a block-Jacobi preconditioner -- a stale u~, one block summed in another order -- which is what
+tests/test_trajectory_stored_tilde.py is there to see."""
 import math
 
 import numpy as np
@@ -190,6 +192,78 @@ def test_one_wrong_row_at_one_iteration_of_a_long_run_shows_in_the_bits(matrices
     nan = clean.copy()
     nan[17, 2] = np.nan
     assert first_mismatch(nan, nan) == 17           # NaN never passes as equal
+
+
+class FaultyBlockJacobi:
+    """BlockJacobi with ONE fault at ONE application: 'stale' hands back what the application two before returned (in the
+    pipelined flavours that recompute w: the u~ of the previous iteration, left in its buffer); 'reversed' sums the columns of
+    ONE block in descending order -- the block with the largest result among those where the order shows in the bits."""
+
+    def __init__(self, P, kind, at_call):
+        self.P, self.kind, self.at, self.calls, self.seen, self.changed = P, kind, at_call, 0, [], 0
+
+    def __call__(self, v):
+        out = self.P(v)
+        self.seen = (self.seen + [out.copy()])[-3:]
+        self.calls += 1
+        if self.calls - 1 != self.at:
+            return out
+        if self.kind == 'stale':
+            self.changed = int(np.count_nonzero(self.seen[0] != out))
+            return self.seen[0].copy()
+        bs, B = self.P.bs, self.P.inv_blocks
+        nf = out.shape[0] // bs
+        V = np.asarray(v, dtype=np.float64)[:nf * bs].reshape(nf, bs)
+        rev = B[:nf, :, bs - 1] * V[:, bs - 1:bs]
+        for j in range(bs - 2, -1, -1):
+            rev = rev + B[:nf, :, j] * V[:, j:j + 1]
+        fwd = out[:nf * bs].reshape(nf, bs)
+        shows = (rev != fwd).any(axis=1)
+        assert shows.any()
+        k = int(np.argmax(np.where(shows, np.abs(fwd).max(axis=1), -1.0)))
+        self.changed = int(np.count_nonzero(rev[k] != fwd[k]))
+        out = out.copy()
+        out[k * bs:(k + 1) * bs] = rev[k]
+        return out
+
+
+@pytest.mark.parametrize('kind', ['stale', 'reversed'])
+def test_one_wrong_application_of_block_jacobi_in_a_long_run_shows_in_the_bits(matrices, kind):
+    """What tests/test_trajectory_stored_tilde.py is for, on the model's side: pipe_pr_pcg on bcsstk03 (n = 112) under
+    BlockJacobi(A, 8) with the sums of that schedule (the pipelined update tree for every inner product), 90 iterations --
+    below the oracle's first non-positive nu at k = 128 --, then again with one fault in the u~ that iteration 50 uses
+    (M^-1 is applied to r, s, u at the start and to u, then w, in every iteration: application 3 + 2 (50 - 2)).  The trajectories
+    agree bit for bit before iteration 50.  A stale u~ (all 112 entries of another iteration) differs at 50: u~ enters s~ =
+    (w~ - a u~) + b s~ there, hence delta and gamma.  One block summed in reverse order changes the last bit of at most 8
+    entries of u~, which may stay below the rounding of those two 112-term sums; s~ of iteration 50 carries it into r~, p, s and
+    u of 51 and into every inner product by 52 -- the first difference lies in 50..52.  From the first difference on every
+    iteration differs, the last one included."""
+    import new_cg_variants_amd.cg_variants as cgv
+    from device_order import device_dot
+    A, z = matrices['bcsstk03']
+    n = A.shape[0]
+    P = cgv.BlockJacobi(A, 8)
+    iters, k_bad = 90, 50
+
+    def run(M):
+        rows = []
+        orc.pipe_pr_pcg(A, z['b'], np.zeros(n), iters, preconditioner=M, dot=device_dot, dot0=device_dot, square=lambda a: a * a,
+                        tap=lambda st: rows.append((st.mu, st.dl, st.gm, st.nu, st.eta, st.alpha, st.beta)))
+        return np.array(rows)
+
+    clean = run(P)
+    assert np.isfinite(clean).all() and clean.shape == (iters, 7) and (clean[:, [0, 1, 2, 3]] != 0).all()
+    assert first_mismatch(run(FaultyBlockJacobi(P, kind, -1)), clean) == -1          # the wrapper alone changes nothing
+    M = FaultyBlockJacobi(P, kind, 3 + 2 * (k_bad - 2))
+    faulty = run(M)
+    assert M.calls == 3 + 2 * (iters - 1)
+    first = first_mismatch(faulty, clean)
+    if kind == 'stale':
+        assert M.changed == n and first == k_bad, (M.changed, first)
+    else:
+        assert 1 <= M.changed <= 8 and k_bad <= first <= k_bad + 2, (M.changed, first)
+    differs = (faulty != clean).any(axis=1)
+    assert differs[first:].all() and differs[-1] and not differs[:first].any()
 
 
 # ---- UnitTree: sliced rows and CSR-adaptive tiles (tests/test_trajectory_irregular.py) ------------------------------------

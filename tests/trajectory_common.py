@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE shared by the whole-trajectory tests (tests/test_trajectory_oracle.py: window operators;
-tests/test_trajectory_irregular.py: sliced rows and CSR-adaptive tiles): the method table, one oracle run with taps and one
-device session in either of the two modes the tests compare."""
+tests/test_trajectory_irregular.py: sliced rows and CSR-adaptive tiles; tests/test_trajectory_stored_tilde.py: block-Jacobi and
+host-callback sessions on either): the method table, one oracle run with taps and one device session in either of the two
+modes the tests compare."""
 import numpy as np
 
 from oracle import ne_oracle as orc
@@ -27,32 +28,37 @@ CHUNKS = (1, 2, 37)          # prcg_iterate calls of mode (b), then the rest: st
 FIELD = {'mu': 0, 'dl': 1, 'gm': 2, 'nu': 3, 'eta': 4, 'alpha': 5, 'beta': 6}
 
 
-def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep):
-    """the oracle's trajectory: rows (mu, dl, gm, nu, eta, alpha, beta) per state, recorder histories, (x, r) at the states in `keep`"""
+def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep, vectors='xr'):
+    """the oracle's trajectory: rows (mu, dl, gm, nu, eta, alpha, beta) per state, recorder histories, (x, r) at the states in
+    `keep` (`vectors`: other fields of the oracle's state in their place, e.g. ('x', 'r', 'ut', 'wt')); `jacobi`: the callable
+    the oracle takes as preconditioner= (any callable, not only a diagonal)"""
     rows, snaps = [], {}
 
     def tap(st):
         rows.append((st.mu, st.dl, st.gm, st.nu, st.eta, st.alpha, st.beta))
         if st.k in keep:
-            snaps[st.k] = (st.x.copy(), st.r.copy())
+            snaps[st.k] = tuple(getattr(st, v).copy() for v in vectors)
     kw = {'preconditioner': jacobi} if METHODS[method][2] else {}
     ref = getattr(orc, ORACLE_NAME.get(method, method))(A, b, np.zeros(A.shape[0]), max_iter, dot=dot, dot0=dot0, square=lambda a: a * a,
                                                          callbacks=FOUR, x_true=x_true, tap=tap, **kw)
     return np.array(rows, dtype=np.float64), ref, snaps
 
 
-def run_device(L, op, variant, b, x_true, inv_diag, max_iter, recorders):
+def run_device(L, op, variant, b, x_true, inv_diag, max_iter, recorders, *, block_jacobi=None, block_jacobi_var=None, preconditioner=None,
+               vectors='xr'):
     """one session: mode (a) all four recorders, one prcg_iterate call; mode (b) the recurrence residual only, calls of CHUNKS
-    and the rest, x and r read after each"""
+    and the rest, x and r (`vectors`: those state vectors) read after each.  The preconditioner is at most one of inv_diag /
+    block_jacobi / block_jacobi_var / preconditioner, as DeviceCSR.begin takes them."""
     n = b.shape[0]
-    op.begin(variant, b, np.zeros(n), max_iter, x_true=x_true if recorders else None, inv_diag=inv_diag, hist_mask=15 if recorders else 1)
+    op.begin(variant, b, np.zeros(n), max_iter, x_true=x_true if recorders else None, inv_diag=inv_diag, hist_mask=15 if recorders else 1,
+             block_jacobi=block_jacobi, block_jacobi_var=block_jacobi_var, preconditioner=preconditioner)
     out = {'schedule': op.schedule(), 'start_layout': op.layout(), 'state': {}}
     if recorders:
         op.iterate(max_iter - 1)
     else:
         for chunk in CHUNKS + (max_iter,):
             op.iterate(min(chunk, max_iter - 1 - op.k))
-            out['state'][int(op.k)] = (op.get_vector('x'), op.get_vector('r'))
+            out['state'][int(op.k)] = tuple(op.get_vector(v) for v in vectors)
     op.sync()
     out['scalars'] = np.array([op.get_scalars(k) for k in range(max_iter)])
     out['coef'] = np.array([op.get_coefficients(k)[:2] for k in range(1, max_iter)])
