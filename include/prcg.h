@@ -439,6 +439,36 @@ int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out);
 /* max_iter doubles: column j's updated_residual_2_norm history (nothing is written when hist_mask was 0) */
 int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
 
+/* ---- a single PIPELINED session stopped at a residual threshold, decided on the device ------------------------------------
+ *   prcg_set_stop      rr_stop: NULL clears the threshold; else *rr_stop is a threshold on r.r (for a tolerance tol on the 2-norm
+ *                      of the updated residual: tol * tol), finite and >= 0, else PRCG_EINVAL (the threshold set before stays).
+ *                      It is copied at the call and applies to single sessions BEGUN afterwards with prcg_solve_begin (signature
+ *                      unchanged); an open session is not affected.  Such a session stops by itself, decided on the device without
+ *                      the host: after iteration k, and at k = 0 on the initial state, on row k of its scalars, mu = [0], nu = [3],
+ *                      rr = [PRCG_S_RR], by the rule of prcg_batch_set_stop below, in this order:
+ *                        1. rr <= *rr_stop                                     -> stop, status 1 (converged);
+ *                        2. else !(0 < mu && mu < inf && 0 < nu && nu < inf)   -> stop, status 2 (breakdown);
+ *                        3. else go on (status 0, stop iteration -1).
+ *                      A session stopped at k keeps the complete state of iteration k: x, r, p, s, w, u (with Jacobi r~, s~ too;
+ *                      the 'p' flavours their stored w and w~) are those of iteration k, scalar rows 0..k and coefficient rows 1..k
+ *                      are written; prcg_get_scalars / prcg_get_coefficients of later rows and later entries of every history
+ *                      read as zero.  The launches prcg_iterate had enqueued beyond the stop return at once and store nothing;
+ *                      prcg_sync resolves the stop -- after it prcg_iteration reports k -- and prcg_iterate on a stopped session
+ *                      is a no-op that returns PRCG_OK.  A threshold of 0 stops on an exactly zero residual (b = A x0) and on
+ *                      breakdown only.  A session that never stops carries the bits of a session without a threshold.
+ *                      Served while a threshold is set: the four pipelined variants (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_PIPE_P,
+ *                      PRCG_PIPE_P_M) on one GPU, unpreconditioned or with inv_diag, on the one-launch schedule or the
+ *                      one-workgroup solver.  prcg_solve_begin refuses everything else (PRCG_EINVAL, the text says what is served)
+ *                      -- another variant, a communicator or ghost rows, a host-callback or block-Jacobi preconditioner in force
+ *                      (the stored-tilde schedule), PRCG_FUSED=0, a replace hook -- and nothing falls back to a schedule that
+ *                      cannot stop.  In a session begun with a threshold prcg_set_vector, prcg_set_scalars and prcg_set_iteration
+ *                      are refused.  Sessions with several right-hand sides ignore the threshold.
+ *   prcg_get_stop      synchronises; *k_stop, *status of the open single session: the iteration it stopped at and why (1 converged,
+ *                      2 breakdown), or -1 and 0 while it runs -- and for a session begun without a threshold.  Refused without an
+ *                      open single session. */
+int prcg_set_stop(prcg_t* h, const double* rr_stop);
+int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status);
+
 /* ---- a BATCH of small independent systems, solved in one launch, one workgroup per system --------------------------------
  * Replaces the reference's loop over matrices and methods around `method(A, b, x0, max_iter, ...)` (numerical_experiments/
  * figure_gen.py:59, :245-339: the convergence table is small matrices times nine methods), and the loop a time stepper or a

@@ -98,6 +98,8 @@ _SIGNATURES = {
     'prcg_batch_iterate': (C.c_int, [_P, C.c_int]),
     'prcg_batch_sync': (C.c_int, [_P]),
     'prcg_batch_iteration': (C.c_int, [_P]),
+    'prcg_set_stop': (C.c_int, [_P, _P]),
+    'prcg_get_stop': (C.c_int, [_P, _P, _P]),
     'prcg_batch_set_stop': (C.c_int, [_P, _P]),
     'prcg_batch_get_stops': (C.c_int, [_P, _P, _P]),
     'prcg_batch_get_vector': (C.c_int, [_P, C.c_int, C.c_int, _P]),

@@ -506,6 +506,9 @@ def _state_vectors(variant, prec):
     return ['x', 'r', 'p', 's', 'w', 'u'] + (['rt', 'st', 'wt', 'ut'] if prec else [])
 
 
+_PIPELINED = (L.PIPE_PR, L.PIPE_PR_M, L.PIPE_P, L.PIPE_P_M)
+
+
 def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w_replace=None):
     device = int(kwargs.get('device', 0))
     if A.format != 'csr':
@@ -519,6 +522,19 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         inv_diag, prec_fn = None, preconditioner
     else:
         inv_diag, prec_fn = _diagonal_of(preconditioner, n)
+    # rtol= / atol=: the pipelined variants stop by themselves on the device (prcg.h: prcg_set_stop); the other functions never
+    # took the keywords and keep passing them by, like any keyword they do not know
+    rr_stop = None
+    if variant in _PIPELINED and (kwargs.get('rtol') is not None or kwargs.get('atol') is not None):
+        bvec = np.asarray(b, dtype=np.float64)
+        if bvec.shape != (n,):
+            raise ValueError(f'{name}: b must have shape ({n},), got {tuple(bvec.shape)}')
+        thr = _stop_thresholds(name, kwargs.pop('rtol', None), kwargs.pop('atol', None), [bvec])
+        if thr is not None:
+            if prec_fn is not None:
+                raise ValueError(f'{name}: rtol= / atol= serve no preconditioner but a diagonal scaling: a callable or block-Jacobi '
+                                 'preconditioner runs the stored-tilde schedule, which cannot stop on the device')
+            rr_stop = float(thr[0])
 
     mask = 0
     foreign = []          # callables we must call ourselves, every iteration
@@ -579,7 +595,7 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
     elif blocks is not None:
         op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=blocks)
     else:
-        op.begin(variant, b, x0, max_iter, x_true=x_true, inv_diag=inv_diag, hist_mask=mask, preconditioner=prec_fn)
+        op.begin(variant, b, x0, max_iter, x_true=x_true, inv_diag=inv_diag, hist_mask=mask, preconditioner=prec_fn, rr_stop=rr_stop)
 
     def call_host(k):
         env = {'output': output, 'k': k, 'max_iter': max_iter, 'A': A, 'b': b, 'x0': x0, 'n': n,
@@ -601,15 +617,24 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         for cb in foreign:
             cb(**env)
 
+    def stopped():
+        return rr_stop is not None and op.stop()[0] >= 0
+
     if foreign or light:
         call_host(0)
         for k in range(1, max_iter):
+            if stopped():                  # the state of the stop iteration was the last one the callbacks saw
+                break
             op.iterate(1)
             call_host(k)
     else:
         op.iterate(max_iter - 1)
     op.sync()
     output.update(op.history())
+    if rr_stop is not None:
+        k_stop, status = op.stop()
+        output['iterations'] = k_stop if status else max_iter - 1
+        output['status'] = ('max_iter', 'converged', 'breakdown')[status]
     return output
 
 
@@ -781,6 +806,26 @@ def _batch_diagonals(name, preconditioner, sizes):
     return [np.ones(n) if d is None else d for n in sizes]
 
 
+def _stop_thresholds(name, rtol, atol, rhs):
+    """rtol / atol (each None, one value, or one value per system) -> the thresholds on r.r the device stops at, one per
+    right-hand side in ``rhs``: thr_s = max(rtol_s ||b_s||_2, atol_s)^2; None when neither is given.  Shared by the batches and
+    the pipelined single functions (one system).  Pure host work; ValueError names the function, the keyword and the system."""
+    if rtol is None and atol is None:
+        return None
+    n_sys = len(rhs)
+    try:
+        rt = batch_thresholds('rtol', 0.0 if rtol is None else rtol, n_sys)
+        ab = batch_thresholds('atol', 0.0 if atol is None else atol, n_sys)
+    except ValueError as e:
+        raise ValueError(f'{name}: {e}') from None
+    norms = np.array([np.linalg.norm(b) for b in rhs])
+    rr_stop = np.maximum(rt * norms, ab) ** 2
+    try:
+        return batch_thresholds('max(rtol * ||b||, atol) ** 2', rr_stop, n_sys)
+    except ValueError as e:
+        raise ValueError(f'{name}: {e}') from None
+
+
 def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=False):
     """A batch of small independent systems in ONE launch, one workgroup per system (prcg.h: prcg_batch_create): what a loop
     of `name`'s single function over the systems computes.  Every argument is checked before the device is touched; what the
@@ -813,19 +858,7 @@ def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=F
             raise ValueError(f'{name}: callback {cname or repr(cb)} is not served by a batch (the updated_residual_2_norm recorder or none)')
     inv_diag = _batch_diagonals(name, preconditioner, sizes) if jacobi else None
     at = np.concatenate([[0], np.cumsum(sizes)])
-    rr_stop = None
-    if rtol is not None or atol is not None:               # thr_s = max(rtol_s ||b_s||_2, atol_s)^2, a bound on r.r
-        try:
-            rt = batch_thresholds('rtol', 0.0 if rtol is None else rtol, n_sys)
-            ab = batch_thresholds('atol', 0.0 if atol is None else atol, n_sys)
-        except ValueError as e:
-            raise ValueError(f'{name}: {e}') from None
-        norms = np.array([np.linalg.norm(B[at[s]:at[s + 1]]) for s in range(n_sys)])
-        rr_stop = np.maximum(rt * norms, ab) ** 2
-        try:
-            rr_stop = batch_thresholds('max(rtol * ||b||, atol) ** 2', rr_stop, n_sys)
-        except ValueError as e:
-            raise ValueError(f'{name}: {e}') from None
+    rr_stop = _stop_thresholds(name, rtol, atol, [B[at[s]:at[s + 1]] for s in range(n_sys)])
     batch = DeviceBatch(matrices, mat_of, device=int(kwargs.get('device', 0)))
     try:
         batch.begin(variant, [B[at[s]:at[s + 1]] for s in range(n_sys)], [X0[at[s]:at[s + 1]] for s in range(n_sys)], max_iter, hist_mask=mask,

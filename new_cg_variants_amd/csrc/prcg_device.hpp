@@ -177,6 +177,67 @@ __device__ __forceinline__ Coefs predict(const double* __restrict__ dp, int meur
     return c;
 }
 
+// THE stop rule (contract: SmallStop, prcg_kernels.h), on the scalars of a complete iteration: 0 go on, 1 converged, 2 breakdown.
+// The one-workgroup solvers (prcg_small.hip), the prologue of the one-launch iteration (fused_prologue below) and the final
+// reduction (k_reduce_final_stop) all decide with this comparison.  Callers hand it operands that are the same bits in every
+// thread that branches on the verdict; readfirstlane makes it a scalar, so the branch on it is a scalar branch.
+__device__ __forceinline__ int stop_rule(double mu, double nu, double rr, double thr) {
+    const double inf = __builtin_huge_val();
+    int v = 0;
+    if (rr <= thr) v = 1;                                                        // converged
+    else if (!(0.0 < mu && mu < inf && 0.0 < nu && nu < inf)) v = 2;             // breakdown: a = nu / mu is not an SPD system's
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Prologue of the single-GPU one-launch pipelined iteration (k_win_tiles, k_sell_tiles, k_sell_win, k_spmv_tiles; also the
+// one-launch predict-and-recompute iteration, which never carries a stop word).  The inner products of the previous iteration
+// are either still one row of partials per workgroup of the previous launch -- every workgroup of this launch sums them in the
+// fixed 256-thread tree (sum_prev_partials), workgroup 0 stores the row for the history -- or already reduced (`reduced`).  From
+// them the coefficients of this iteration (predict), which workgroup 0 stores to coef_out.
+//
+// With a stop word (fz.word; prcg_set_stop) the launch may have nothing to do.  Returns false: the workgroup returns at once.
+//  1. The word names an iteration BEFORE fz.word_k: the session stopped in an earlier launch.  The word was complete before this
+//     launch began (kernel boundary), so every wave of every workgroup reads the same value and leaves here, before any barrier
+//     and before anything is written -- the pending partials are stale: the launch that should have written them left like this.
+//     (A word that names word_k itself is either the same case, left by the final reduction or the session start -- then the
+//     reduced row is read, the rule below fires again, nothing is written -- or the store of workgroup 0 of THIS launch, seen by
+//     a wave that started late: it goes on and reaches that verdict itself, with the rest of its workgroup.  Leaving on it here
+//     would let waves of one workgroup part BEFORE the barriers of the sum.)
+//  2. The rule on {mu, nu, rr} of iteration word_k.  The sums are the same bits in every thread of every workgroup (one tree over
+//     one buffer; tot_s is read behind the barrier that completes it), thr is a kernel argument: every wave of the launch reaches
+//     the same verdict, behind the last barrier of the sum and before the next one, so whole workgroups leave together and no
+//     workgroup needs to see another's store.  Thread 0 of workgroup 0 records {word_k, status}; the row of iteration word_k has
+//     been stored (it belongs to the state of the stop), no coefficient, tile or row of iteration word_k + 1 is touched.
+// A session that never stops executes, beside these tests, exactly the code of a session without a word: the same bits.
+template <int NWAVES>
+__device__ __forceinline__ bool fused_prologue(const FusedPrev& fz, const double* __restrict__ reduced, int meurant,
+                                               double* __restrict__ coef_out, Coefs& cf) {
+    if (fz.word) {
+        const int at = __builtin_amdgcn_readfirstlane(fz.word[0]);
+        if (at >= 0 && at < fz.word_k) return false;
+    }
+    double mu, nu, rr;
+    if (fz.nprev > 0) {
+        double dsum[5];
+        sum_prev_partials<5, NWAVES>(fz.prev_partials, fz.nprev, 0, dsum);
+        if (blockIdx.x == 0 && threadIdx.x < 5) fz.dots_prev_out[threadIdx.x] = dsum[threadIdx.x];
+        cf = predict(dsum, meurant);
+        mu = dsum[0]; nu = dsum[3]; rr = dsum[4];
+    } else {
+        cf = predict(reduced, meurant);
+        mu = reduced[0]; nu = reduced[3]; rr = reduced[4];
+    }
+    if (fz.word) {
+        const int verdict = stop_rule(mu, nu, rr, fz.thr);
+        if (verdict) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) { fz.word[0] = fz.word_k; fz.word[1] = verdict; }
+            return false;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { coef_out[0] = cf.al; coef_out[1] = cf.bt; coef_out[2] = cf.nup; }
+    return true;
+}
+
 // Extra per-row operands of the one-launch iteration (see FusedState): kernel arguments
 struct FusedRowPtrs {
     double2* XP; double2* IN_NEW; double2* RS; const double* D; double* W; double* WT;

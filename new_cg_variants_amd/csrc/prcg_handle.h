@@ -181,6 +181,13 @@ struct Session {
     double* pend_buf = nullptr;
     int last_grid = 0;           // workgroups of the session's last launch that left inner-product partials (prcg_debug_layout) ...
     int last_wpb = 0;            // ... and its waves per workgroup (window operators: what launch_win_v instantiated; else 0)
+    // ---- stopped at a residual threshold, decided on the device (prcg_set_stop; pipelined single sessions) ----
+    bool stop = false;           // the session was begun with a threshold ...
+    double thr = 0.0;            // ... on r.r
+    int* word = nullptr;         // ... and this is its stop word in device memory (Handle::stop_word): {-1, 0} while it runs, {k_stop, status}
+                                 // once a launch's prologue, the final reduction or the one-workgroup solver has stopped it
+    int stopped_k = -1;          // what prcg_sync has read from the word: the iteration whose state the session holds (-1: running) ...
+    int stop_status = 0;         // ... and why (1 converged, 2 breakdown)
 };
 
 // One PAIR GROUP of a session with two or four right-hand sides: the interleaved n x 2 arrays X, R, P, S, RT of two columns
@@ -260,6 +267,9 @@ struct Handle : Operator, Session {
     const unsigned char* bjv_code_d() const { return static_cast<const unsigned char*>(bjv_bytes.p); }
     const unsigned char* bjv_bidx_d() const { return bjv_code_d() + bjv_plan.ntiles * kBjvLanes; }
     prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
+    // residual threshold for single sessions begun from now on (prcg_set_stop); the word a session with one stops itself through
+    bool stop_set = false; double stop_thr = 0.0;
+    DevBuf stop_word;
     std::vector<double> cb_in, cb_out;
     DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
 

@@ -89,6 +89,12 @@ struct FusedPrev {
     // expressions, the same bits.  xphase 0: the launch closes itself; 1 (SKIP): no store to XP; 2 (APPLY): rebuild
     // first, xcoef = the skipped iteration's stored coefficients {a, b} (coef[k-1]: the very doubles that launch used).
     int xphase; const double* xcoef;
+    // single session stopped at a residual threshold (prcg_set_stop; single-GPU form of the one-launch iteration only): the
+    // session's stop word -- two ints in device memory, the layout and the rule of SmallStop below -- or null: no threshold.
+    // word_k: the iteration whose scalars this launch's prologue sums or reads (the launch itself is iteration word_k + 1).
+    // A launch that finds the session stopped, or stops it, returns before it has written a coefficient or a row: the state of
+    // the stop iteration stays as its own launch wrote it (fused_prologue, prcg_device.hpp).
+    int* word; double thr; int word_k;
 };
 // State of the one-launch pipelined iteration (pipe_pr_cg.py:61-75 unpreconditioned, :169-187 Jacobi):
 // the two-vector product of the SpMM input pair array `in_old` with the NEXT vector update applied row
@@ -322,7 +328,10 @@ size_t small_lds_bytes(int n, int nnz, int mode, bool jacobi = false);
 bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, bool jacobi = false);
 // The single sessions.  The dynamic-LDS attribute of every kernel of the family is set, and its result checked, on first use on
 // each device: a launch fails (-1) where it could not be set.
-int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode);
+// stop (or null; SmallStop below, declared here for the launcher): the single session stopped at a residual threshold -- the
+// STOP form of the batch's body on the session's own word
+struct SmallStop;
+int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop = nullptr);
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode);      // Hestenes-Stiefel, same storage
 // ---- a batch of small systems: the same solver, one workgroup per system, blockIdx.x selects the system (prcg_batch.cpp) ----
 // desc: `count` SmallArgs in DEVICE memory, all of one mode (k0, iters, meurant in them are ignored: the launch carries them).
@@ -464,6 +473,11 @@ int launch_gv_update1(hipStream_t st, const CgArgs& a, bool dots_only);   // x,r
 // out[dst_first..+count) = fixed-order sum over blocks b of partials[b][src_first..+count)
 void launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
                          int src_first, int dst_first, int count);
+// The stop form (single sessions with a threshold: FusedPrev::word): out[0..5) = the five sums of slots 0..5 -- the same kernel
+// code, the same tree, the same bits -- then the rule of SmallStop on {mu, nu, rr} = out[0], out[3], out[4], which are the scalars
+// of iteration k: a stop is recorded as {k, status} in stop.word.  If the word is already set the launch returns at once and
+// writes nothing: its partials belong to a launch that returned early.
+void launch_reduce_final_stop(hipStream_t st, const double* partials, int nparts, double* out, const SmallStop& stop, int k);
 
 // ---- small utility kernels (strided so they can address one half of a pair array) ----
 void launch_copy(hipStream_t st, double* dst, int ds, const double* src, int ss, int64_t n);

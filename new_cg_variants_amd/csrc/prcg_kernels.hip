@@ -249,38 +249,12 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(
     if constexpr (epi_fused(EPI)) {
         // ep_r = the reduced inner products of the previous iteration; bit 2 of write_mask =
         // Meurant's prediction; aux = where alpha, beta, nu_pred of this iteration are kept
-        if (fz.nprev > 0) {
-            // The previous launch left one row of partial inner products per block.  Every
-            // block of THIS launch sums them itself, in the same fixed order (thread t: rows
-            // t, t+256, ...; butterfly; waves in order), so no separate reduction launch is
-            // needed and all blocks get bit-identical coefficients.  The kernel boundary
-            // makes the partials visible; nothing is exchanged inside a launch.
-            __shared__ double redp[kWaves][5];
-            __shared__ double dsum[5];
-            double tot[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int j = threadIdx.x; j < fz.nprev; j += kBlock) {
-#pragma unroll
-                for (int q = 0; q < 5; ++q) tot[q] += fz.prev_partials[(size_t)j * kPartialStride + q];
-            }
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const double v = wave_sum(tot[q]);
-                if (lane == 0) redp[wv][q] = v;
-            }
-            __syncthreads();
-            if (threadIdx.x < 5) {
-                double v = redp[0][threadIdx.x];
-#pragma unroll
-                for (int w = 1; w < kWaves; ++w) v += redp[w][threadIdx.x];
-                dsum[threadIdx.x] = v;
-                if (blockIdx.x == 0) fz.dots_prev_out[threadIdx.x] = v;    // history / get_scalars
-            }
-            __syncthreads();
-            cf = predict(dsum, (write_mask >> 2) & 1);
-        } else {
-            cf = predict(ep_r, (write_mask >> 2) & 1);
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) { aux[0] = cf.al; aux[1] = cf.bt; aux[2] = cf.nup; }
+        // If the previous launch left one row of partial inner products per block, every block of THIS launch sums them
+        // itself, in the same fixed order (thread t: rows t, t+256, ...; butterfly; waves in order: sum_prev_partials with four
+        // waves IS that tree), so no separate reduction launch is needed and all blocks get bit-identical coefficients.  The
+        // kernel boundary makes the partials visible; nothing is exchanged inside a launch.  A session with a stop word may end
+        // here, before anything is loaded or stored (fused_prologue).
+        if (!fused_prologue<kWaves>(fz, ep_r, (write_mask >> 2) & 1, aux, cf)) return;
     }
 
     // Tile order: wave `slot` takes tiles slot, slot+W, ... so the whole chip sweeps the
@@ -660,11 +634,11 @@ __global__ __launch_bounds__(kBlock) void k_gv_update1(CgArgs a, int trips) {
 
 // ---- fixed-order final reduction of per-block partials --------------------------------
 constexpr int kFinalThreads = 256;   // same tree as the fused last-block reduction
-__global__ __launch_bounds__(kFinalThreads) void k_reduce_final(
-    const double* __restrict__ partials, int nparts, double* __restrict__ out,
-    int src_first, int dst_first, int count)
+// the tree up to the four wave sums of every slot (red), complete behind the barrier; slot q's total is red[0][q] + red[1][q] +
+// red[2][q] + red[3][q], added in that order by whoever needs it
+__device__ __forceinline__ void reduce_final_waves(const double* __restrict__ partials, int nparts, int src_first, int count,
+                                                   double (&red)[kFinalThreads / 64][kPartialStride])
 {
-    __shared__ double red[kFinalThreads / 64][kPartialStride];
     double acc[kPartialStride];
 #pragma unroll
     for (int q = 0; q < kPartialStride; ++q) acc[q] = 0.0;
@@ -680,10 +654,34 @@ __global__ __launch_bounds__(kFinalThreads) void k_reduce_final(
         if (lane == 0) red[wv][q] = v;
     }
     __syncthreads();
-    if ((int)threadIdx.x < count) {
-        double v = red[0][threadIdx.x];
-        for (int w = 1; w < kFinalThreads / 64; ++w) v += red[w][threadIdx.x];
-        out[dst_first + threadIdx.x] = v;
+}
+__device__ __forceinline__ double reduce_final_total(const double (&red)[kFinalThreads / 64][kPartialStride], int q) {
+    double v = red[0][q];
+    for (int w = 1; w < kFinalThreads / 64; ++w) v += red[w][q];
+    return v;
+}
+__global__ __launch_bounds__(kFinalThreads) void k_reduce_final(
+    const double* __restrict__ partials, int nparts, double* __restrict__ out,
+    int src_first, int dst_first, int count)
+{
+    __shared__ double red[kFinalThreads / 64][kPartialStride];
+    reduce_final_waves(partials, nparts, src_first, count, red);
+    if ((int)threadIdx.x < count) out[dst_first + threadIdx.x] = reduce_final_total(red, threadIdx.x);
+}
+// The stop form (launch_reduce_final_stop, prcg_kernels.h): the five sums of a pipelined iteration by the code above, then the
+// rule on them.  The word is tested first: it was complete before this launch began (only a launch's end or this kernel's thread 0
+// writes it), so all four waves read the same value and leave together, before the barrier.  Thread 0 then adds the wave sums of
+// mu, nu, rr in the order threads 0, 3, 4 add them: the bits they store, and the bits the next launch's prologue would have had.
+__global__ __launch_bounds__(kFinalThreads) void k_reduce_final_stop(
+    const double* __restrict__ partials, int nparts, double* __restrict__ out, SmallStop stop, int k)
+{
+    if (__builtin_amdgcn_readfirstlane(stop.word[0]) >= 0) return;
+    __shared__ double red[kFinalThreads / 64][kPartialStride];
+    reduce_final_waves(partials, nparts, 0, 5, red);
+    if (threadIdx.x < 5) out[threadIdx.x] = reduce_final_total(red, threadIdx.x);
+    if (threadIdx.x == 0) {
+        const int verdict = stop_rule(reduce_final_total(red, 0), reduce_final_total(red, 3), reduce_final_total(red, 4), stop.thr);
+        if (verdict) { stop.word[0] = k; stop.word[1] = verdict; }
     }
 }
 
@@ -1069,6 +1067,10 @@ int launch_gv_update1(hipStream_t st, const CgArgs& a, bool dots_only) {
         else hipLaunchKernelGGL((k_gv_update1<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     }
     return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+
+void launch_reduce_final_stop(hipStream_t st, const double* partials, int nparts, double* out, const SmallStop& stop, int k) {
+    hipLaunchKernelGGL(k_reduce_final_stop, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, out, stop, k);
 }
 
 void launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,

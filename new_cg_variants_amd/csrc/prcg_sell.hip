@@ -112,16 +112,9 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
     if constexpr (epi_fused(EPI)) {
         // inner products of the previous iteration: one row of partials per workgroup of the previous launch, summed by
-        // every workgroup of this one in the fixed 256-thread tree (as k_spmv_tiles / k_win_tiles do)
-        if (fz.nprev > 0) {
-            double dsum[5];
-            sum_prev_partials<5, kWaves>(fz.prev_partials, fz.nprev, 0, dsum);
-            if (blockIdx.x == 0 && threadIdx.x < 5) fz.dots_prev_out[threadIdx.x] = dsum[threadIdx.x];
-            cf = predict(dsum, (write_mask >> 2) & 1);
-        } else {
-            cf = predict(ep_r, (write_mask >> 2) & 1);
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) { aux[0] = cf.al; aux[1] = cf.bt; aux[2] = cf.nup; }
+        // every workgroup of this one in the fixed 256-thread tree (as k_spmv_tiles / k_win_tiles do); a session with a stop word
+        // may end here, before anything is loaded or stored (fused_prologue)
+        if (!fused_prologue<kWaves>(fz, ep_r, (write_mask >> 2) & 1, aux, cf)) return;
     }
 
     const int nblk = gridDim.x;
@@ -309,15 +302,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
     if constexpr (epi_fused(EPI)) {
-        if (fz.nprev > 0) {
-            double dsum[5];
-            sum_prev_partials<5, kWaves>(fz.prev_partials, fz.nprev, 0, dsum);
-            if (blockIdx.x == 0 && threadIdx.x < 5) fz.dots_prev_out[threadIdx.x] = dsum[threadIdx.x];
-            cf = predict(dsum, (write_mask >> 2) & 1);
-        } else {
-            cf = predict(ep_r, (write_mask >> 2) & 1);
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) { aux[0] = cf.al; aux[1] = cf.bt; aux[2] = cf.nup; }
+        if (!fused_prologue<kWaves>(fz, ep_r, (write_mask >> 2) & 1, aux, cf)) return;       // (as k_sell_tiles)
     }
 
     const int nblk = gridDim.x;

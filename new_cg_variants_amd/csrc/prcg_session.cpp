@@ -153,9 +153,33 @@ PipeUpdateArgs pipe_args(prcg_t* h, int k) {
 // make dots[pend_k] real if the last fused launch left it as block partials
 void fused_flush(prcg_t* h) {
     if (h->pend_parts > 0) {
-        launch_reduce_final(h->sc, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k), 0, 0, 5);
+        // a session with a threshold: the reduction also DECIDES on the row it sums (the iteration has no later launch whose
+        // prologue would), and returns at once if the session has stopped -- its partials are then stale
+        if (h->stop && h->fused) launch_reduce_final_stop(h->sc, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k), SmallStop{h->thr, h->word}, h->pend_k);
+        else launch_reduce_final(h->sc, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k), 0, 0, 5);
         h->pend_parts = 0;
     }
+}
+
+// A session with a threshold, every stream idle (prcg_sync): has the device stopped it?  The word tells.  prcg_iterate counted and
+// enqueued without knowing: launches k_stop + 1 .. h->k returned at once and wrote nothing, so the host's picture goes back to
+// iteration k_stop -- the iteration count; the input pairs, which every enqueued launch flipped once on the host only (the parity of
+// the difference says which buffer launch k_stop wrote; the one-workgroup solver works in place: no flip); and no partials are
+// pending (the reduction that would sum them returns at once as well).  Idempotent: once resolved, nothing more is enqueued.
+int resolve_stop(prcg_t* h) {
+    if (!h->in_session || !h->stop || h->stopped_k >= 0) return PRCG_OK;
+    int w[2] = {-1, 0};
+    HIPCHK(h, hipMemcpy(w, h->word, sizeof w, hipMemcpyDeviceToHost));
+    if (w[0] < 0) return PRCG_OK;
+    if (!h->small && ((h->k - w[0]) & 1)) {
+        double* const bufA = h->prec ? h->rst.d() : h->rs.d();
+        double* const bufB = h->prec ? h->rst2.d() : h->rs2.d();
+        h->rs_cur = (h->rs_cur == bufA) ? bufB : bufA;
+    }
+    h->pend_parts = 0;
+    h->k = w[0];
+    h->stopped_k = w[0]; h->stop_status = w[1];
+    return PRCG_OK;
 }
 
 // The session runs the deferred (x,p) store: single GPU, window operator, no recorder that reads x between two launches
@@ -164,7 +188,7 @@ void fused_flush(prcg_t* h) {
 bool xp_deferred(const prcg_t* h) {
     const Session& s = *h;
     return h->opt.want_xp_defer && s.in_session && is_pipe(s.variant) && s.fused && !s.fused_comm && !s.small && h->win && !h->multi() &&
-           !records_state(s.hist_mask);
+           !records_state(s.hist_mask) && !s.stop;      // (with a threshold every launch closes itself: a stop leaves ONE iteration's state)
 }
 
 // what both one-launch pipelined schedules hand their kernel: the state of iteration k-1 and where iteration k goes
@@ -204,6 +228,7 @@ int iterate_pipe_fused(prcg_t* h, int k) {
     f.prev = prev;
     f.prev.xphase = h->xphase;
     f.prev.xcoef = h->xphase == 2 ? coef_at(h, k - 1) : nullptr;
+    if (h->stop) { f.prev.word = h->word; f.prev.thr = h->thr; f.prev.word_k = k - 1; }      // the prologue may stop the session at k - 1
     const int grid = eng_fused(h, h->sc, f);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
@@ -843,6 +868,9 @@ int begin_pipe(prcg_t* h) {
     //  kernel for kernels of ANOTHER stream to become resident, which has only ever been validated with one rank)
     h->fused_comm = h->peer || (h->opt.want_fused && h->opt.want_fused_comm_rccl && h->multi() && h->win && h->gather);
     if (h->fused_comm) h->fused = true;        // state layout, derived vectors: as the one-launch schedule
+    // a session with a threshold runs the single-GPU one-launch schedule or the one-workgroup solver (what prcg_solve_begin let
+    // through selects it); every launch closes itself (xp_deferred), so a stopped session holds one complete iteration
+    CHECK(h, !h->stop || (h->fused && !h->fused_comm), "prcg_solve_begin: a stop threshold is set and the session did not get the one-launch schedule");
     HIPCHK(h, h->xp.ensure((size_t)2 * n * D, h->sc));
     HIPCHK(h, h->rs.ensure((size_t)2 * (h->prec ? n : ne) * D, h->sc));
     HIPCHK(h, h->rs2.ensure((h->fused && !h->prec) ? (size_t)2 * ne * D : 16, h->sc));
@@ -898,7 +926,9 @@ int begin_pipe(prcg_t* h) {
     PipeUpdateArgs a = pipe_args(h, 0);
     const int grid = launch_pipe_dots(sc, a);                           // nu, mu, delta, gamma
     LAUNCHCHK(h, grid);
-    launch_reduce_final(sc, h->partA.d(), grid, dots_at(h, 0), 0, 0, 5);
+    // (with a threshold: the rule on row 0 rides on its reduction -- b = A x0 stops the session before its first iteration)
+    if (h->stop) launch_reduce_final_stop(sc, h->partA.d(), grid, dots_at(h, 0), SmallStop{h->thr, h->word}, 0);
+    else launch_reduce_final(sc, h->partA.d(), grid, dots_at(h, 0), 0, 0, 5);
     if ((rc = allreduce(h, dots_at(h, 0), 5, sc))) return rc;
     if (h->gather) {
         // COLLECTIVE part, the same on every rank of a merged-exchange session whatever schedule the rank itself
@@ -1117,6 +1147,12 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     //  four right-hand sides: twice the rows again, one set per pair group)
     HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * rows_per_iteration * kNS * D, h->sc));
     HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * rows_per_iteration * kCoefStride * D, h->sc));
+    if (h->stop_set) {
+        // the stop word of a session with a threshold: {-1, 0} = running (prcg_solve_begin arms it; other session types leave it alone)
+        static const int kRunning[2] = {-1, 0};
+        if (!h->stop_word.p) HIPCHK(h, h->stop_word.alloc(16));
+        HIPCHK(h, hipMemcpyAsync(h->stop_word.p, kRunning, sizeof kRunning, hipMemcpyHostToDevice, h->sc));
+    }
     if (inv_diag) return h2d(h, h->dinv.d(), inv_diag, h->n);
     return PRCG_OK;
 }
@@ -1134,6 +1170,18 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     CHECK(h, !(hist_mask & (PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) || x_true,
           "prcg_solve_begin: error histories need x_true");
     CHECK(h, h->g == 0 || (h->multi() && h->have_halo), "ghost columns need a communicator and a halo plan");
+    if (h->stop_set) {
+        // a threshold is set (prcg_set_stop): only sessions that can stop on the device are begun -- nothing falls back
+#define STOP_SERVED "a stop threshold is set (prcg_set_stop), which serves the pipelined variants (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_PIPE_P, " \
+                    "PRCG_PIPE_P_M) on one GPU, unpreconditioned or with inv_diag, on the one-launch schedule or the one-workgroup solver"
+        CHECK(h, is_pipe(variant), "prcg_solve_begin: " STOP_SERVED "; variant %d is not pipelined (prcg_set_stop(h, NULL) clears the threshold)", variant);
+        CHECK(h, !h->multi() && h->g == 0, "prcg_solve_begin: " STOP_SERVED "; this handle has a communicator or ghost rows");
+        CHECK(h, inv_diag || !(h->cb || h->have_block_jacobi()),
+              "prcg_solve_begin: " STOP_SERVED "; a host-callback or block-Jacobi preconditioner is in force (the stored-tilde schedule cannot stop)");
+        CHECK(h, h->opt.want_fused, "prcg_solve_begin: " STOP_SERVED "; PRCG_FUSED=0 selects the two-kernel schedule, which cannot stop");
+        CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set");
+#undef STOP_SERVED
+    }
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries: the
     // narrow column encodings decode a few out-of-tile bytes per tile against the tile's own base
     // (products nobody reads); the pad keeps those gathers inside the allocation without a test
@@ -1142,6 +1190,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     int rc = open_session(h, "prcg_solve_begin", variant, max_iter, hist_mask, inv_diag, x_true != nullptr,
                           {{&h->x, (size_t)n * D}, {&h->b, (size_t)n * D}, {&h->xt, (size_t)n * D}, {&h->e_ext, (size_t)ne * D}});
     if (rc) return rc;
+    if (h->stop_set) { h->stop = true; h->thr = h->stop_thr; h->word = h->stop_word.i(); }
     if ((rc = h2d(h, h->x.d(), x0, n))) return rc;
     if ((rc = h2d(h, h->b.d(), b, n))) return rc;
     if (x_true && (rc = h2d(h, h->xt.d(), x_true, n))) return rc;
@@ -1164,6 +1213,7 @@ int prcg_iterate(prcg_t* h, int iters) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_iterate: no open session");
     CHECK(h, iters >= 0, "prcg_iterate: negative count");
+    if (h->stopped_k >= 0) return PRCG_OK;       // stopped at its threshold (prcg_sync has seen the word): a no-op
     CHECK(h, h->k + iters <= h->max_iter, "prcg_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters,
           h->max_iter, h->k);
     HIPCHK(h, hipSetDevice(h->dev));
@@ -1181,9 +1231,10 @@ int prcg_iterate(prcg_t* h, int iters) {
         // all `iters` iterations inside one launch of one workgroup (Hestenes-Stiefel or pipelined)
         if (h->small_hs) hs_flush(h);
         const SmallArgs sa = small_args(h, iters);
+        const SmallStop ss{h->thr, h->word};
         bool on = false;
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, 0, on);
-        LAUNCHCHK(h, h->small_hs ? launch_small_hs(h->sc, sa, h->small_mode) : launch_small_pipe_pr(h->sc, sa, h->small_mode));
+        LAUNCHCHK(h, h->small_hs ? launch_small_hs(h->sc, sa, h->small_mode) : launch_small_pipe_pr(h->sc, sa, h->small_mode, h->stop ? &ss : nullptr));
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->k += iters;
         return PRCG_OK;
@@ -1225,6 +1276,26 @@ int prcg_sync(prcg_t* h) {
                                             "(communication stream starved or a peer stalled); results are invalid. "
                                             "PRCG_FUSED_COMM=0 selects the two-kernel schedule");
     }
+    return resolve_stop(h);
+}
+
+int prcg_set_stop(prcg_t* h, const double* rr_stop) {
+    if (!h) return PRCG_EINVAL;
+    if (!rr_stop) { h->stop_set = false; h->stop_thr = 0.0; return PRCG_OK; }
+    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "prcg_set_stop: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop stops "
+                                                         "the session; NULL clears it)", *rr_stop);
+    h->stop_set = true; h->stop_thr = *rr_stop;
+    return PRCG_OK;
+}
+
+int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status) {
+    if (!h) return PRCG_EINVAL;
+    CHECK(h, h->in_session, "prcg_get_stop: no open session");
+    NOT_RHS2(h, "prcg_get_stop");
+    CHECK(h, k_stop && status, "prcg_get_stop: null buffer");
+    int rc = prcg_sync(h);
+    if (rc) return rc;
+    *k_stop = h->stopped_k; *status = h->stopped_k >= 0 ? h->stop_status : 0;
     return PRCG_OK;
 }
 
@@ -1248,6 +1319,7 @@ int prcg_set_iteration(prcg_t* h, int k) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_set_iteration: no open session");
     NOT_RHS2(h, "prcg_set_iteration");
+    CHECK(h, !h->stop, "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop): its state is not set from outside");
     CHECK(h, k >= 0 && k < h->max_iter, "prcg_set_iteration: k out of range");
     h->k = k;
     if (h->peer && is_pipe(h->variant)) {
@@ -1308,6 +1380,7 @@ int prcg_set_vector(prcg_t* h, int which, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in, "prcg_set_vector: no session or null buffer");
     NOT_RHS2(h, "prcg_set_vector");
+    CHECK(h, !h->stop, "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int64_t n = h->n;
@@ -1330,6 +1403,7 @@ int prcg_get_scalars(prcg_t* h, int k, double* out) {
     NOT_RHS2(h, "prcg_get_scalars");
     int rc = prcg_sync(h);
     if (rc) return rc;
+    if (h->stopped_k >= 0 && k > h->stopped_k) { memset(out, 0, kNS * sizeof(double)); return PRCG_OK; }      // beyond the stop: not part of the run
     return d2h(h, out, dots_at(h, k), kNS);
 }
 
@@ -1337,6 +1411,7 @@ int prcg_set_scalars(prcg_t* h, int k, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in && k >= 0 && k <= h->max_iter, "prcg_set_scalars: bad argument");
     NOT_RHS2(h, "prcg_set_scalars");
+    CHECK(h, !h->stop, "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     if ((rc = h2d(h, dots_at(h, k), in, kNS))) return rc;
@@ -1354,6 +1429,7 @@ int prcg_get_coefficients(prcg_t* h, int k, double* out) {
     NOT_RHS2(h, "prcg_get_coefficients");
     int rc = prcg_sync(h);
     if (rc) return rc;
+    if (h->stopped_k >= 0 && k > h->stopped_k) { memset(out, 0, 3 * sizeof(double)); return PRCG_OK; }
     return d2h(h, out, coef_at(h, k), 3);
 }
 

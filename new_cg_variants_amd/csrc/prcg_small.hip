@@ -10,7 +10,8 @@
 //
 // Two methods, each ONE body: small_pipe_pr_body (pipe_pr_cg.py:61-75, with a diagonal scaling :109-193) and small_hs_body
 // (hs_cg.py:54-62, :70-131), templated on where the matrix lives (MODE), on the scaling (JAC) and on the per-system stop (STOP).
-// The single sessions launch them on the launch's SmallArgs (k_small_pipe_pr, k_small_hs), a batch on the descriptor of
+// The single sessions launch them on the launch's SmallArgs (k_small_pipe_pr, k_small_hs; k_small_pipe_pr_stop: a session with a
+// residual threshold, the STOP form on the session's own word), a batch on the descriptor of
 // workgroup blockIdx.x (k_small_pipe_pr_batch, k_small_hs_batch) -- one body, so that a system of a batch carries the single
 // solver's bits.  Host side at the end: the fit rules and the launchers.
 #include <hip/hip_runtime.h>
@@ -126,14 +127,8 @@ __device__ __forceinline__ double small_red_get(const double* red, int q) {
 // writes; mu, nu, rr are either loaded from one address (row k0 of the scalars, which the launch only reads) or results of
 // small_red_get, in which EVERY wave sums the same 16 LDS partials by the same butterfly and broadcasts lane 0's bits -- behind
 // the barrier that completes them, which is why every body keeps exactly its barriers.  (The stop word: small_stop_entry.)
-// readfirstlane makes the verdict a scalar, so the branch on it is a scalar branch.
-__device__ __forceinline__ int small_stop_rule(double mu, double nu, double rr, double thr) {
-    const double inf = __builtin_huge_val();
-    int v = 0;
-    if (rr <= thr) v = 1;                                                        // converged
-    else if (!(0.0 < mu && mu < inf && 0.0 < nu && nu < inf)) v = 2;             // breakdown: a = nu / mu is not an SPD system's
-    return __builtin_amdgcn_readfirstlane(v);
-}
+// The comparison itself is stop_rule (prcg_device.hpp), shared with the one-launch schedule of single sessions; readfirstlane
+// there makes the verdict a scalar, so the branch on it is a scalar branch.
 // On entry, before the first barrier: true if this workgroup has nothing to do -- its system stopped in an earlier launch
 // (nothing is stored), or the session is at its start and the rule fires on row 0 (thread 0 records {0, status}; the state of
 // iteration 0 is already in memory).  b = 0 ends here: rr = 0 <= thr whatever mu is.  No barrier separates thread 0's store from
@@ -142,7 +137,7 @@ __device__ __forceinline__ int small_stop_rule(double mu, double nu, double rr, 
 __device__ __forceinline__ bool small_stop_entry(const SmallArgs& a, const SmallStop& st) {
     if (__builtin_amdgcn_readfirstlane(st.word[0]) >= 0) return true;
     if (a.k0 != 0) return false;
-    const int v = small_stop_rule(a.dots[0], a.dots[3], a.dots[4], st.thr);
+    const int v = stop_rule(a.dots[0], a.dots[3], a.dots[4], st.thr);
     if (v && threadIdx.x == 0) { st.word[0] = 0; st.word[1] = v; }
     return v != 0;
 }
@@ -246,7 +241,7 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const Sma
         lds_barrier();                                           // everybody has read red before it is rewritten
         double2* tmp = cur; cur = nxt; nxt = tmp;
         if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
-            stop_status = small_stop_rule(mu, nu, rr, stop_thr);
+            stop_status = stop_rule(mu, nu, rr, stop_thr);
             if (stop_status) { stop_k = a.k0 + it; break; }
         }
     }
@@ -349,7 +344,7 @@ __device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallJac
         lds_barrier();                                           // everybody has read red before it is rewritten
         double* tmp = cur; cur = nxt; nxt = tmp;
         if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
-            stop_status = small_stop_rule(mu, nu, rrn, stop_thr);
+            stop_status = stop_rule(mu, nu, rrn, stop_thr);
             if (stop_status) { stop_k = a.k0 + it; break; }
         }
     }
@@ -366,6 +361,9 @@ template <int MODE>
 __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { small_pipe_pr_body<MODE, false, false>(a, SmallJacobi{}, SmallStop{}); }
 template <int MODE>
 __global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small_hs_body<MODE, false, false>(a, SmallJacobi{}, SmallStop{}); }
+// ... stopped at a residual threshold (prcg_set_stop): the STOP form of the body on the session's own word
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_stop(SmallArgs a, SmallStop stop) { small_pipe_pr_body<MODE, false, true>(a, SmallJacobi{}, stop); }
 
 // ---- a BATCH of small systems: one launch, workgroup blockIdx.x solves system desc[blockIdx.x] (prcg_batch.cpp) ----
 // The descriptors live in device memory, one SmallArgs per system with pointers into the batch's concatenated matrix, state,
@@ -490,6 +488,8 @@ const SmallBatchFn kSmallBatchFn[2][2][2][2] = {
     {{{k_small_hs_batch<0, false, false>, k_small_hs_batch<0, false, true>}, {k_small_hs_batch<0, true, false>, k_small_hs_batch<0, true, true>}},
      {{k_small_hs_batch<1, false, false>, k_small_hs_batch<1, false, true>}, {k_small_hs_batch<1, true, false>, k_small_hs_batch<1, true, true>}}}};
 const SmallSingleFn kSmallSingleFn[2][2] = {{k_small_pipe_pr<0>, k_small_pipe_pr<1>}, {k_small_hs<0>, k_small_hs<1>}};      // [hs][mode]
+using SmallSingleStopFn = void (*)(SmallArgs, SmallStop);
+const SmallSingleStopFn kSmallSingleStopFn[2] = {k_small_pipe_pr_stop<0>, k_small_pipe_pr_stop<1>};                         // [mode]
 
 // The kernels may ask for more dynamic LDS than the default 64 KB.  The attribute belongs to the CURRENT device: set for all of
 // them on first use on each device, and only a SUCCESSFUL round counts as done.
@@ -504,6 +504,8 @@ bool small_lds_attribute() {
         if (!set(reinterpret_cast<const void*>((&kSmallBatchFn[0][0][0][0])[i]))) return false;
     for (int i = 0; i < 4; ++i)
         if (!set(reinterpret_cast<const void*>((&kSmallSingleFn[0][0])[i]))) return false;
+    for (int i = 0; i < 2; ++i)
+        if (!set(reinterpret_cast<const void*>(kSmallSingleStopFn[i]))) return false;
     if (dev < kMaxDev) attr_done[dev] = true;
     return true;
 }
@@ -514,7 +516,12 @@ int launch_small_single(hipStream_t st, const SmallArgs& a, int mode, bool hs) {
 }
 }  // namespace
 
-int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode) { return launch_small_single(st, a, mode, false); }
+int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop) {
+    if (!stop) return launch_small_single(st, a, mode, false);
+    if (!small_lds_attribute()) return -1;
+    hipLaunchKernelGGL(kSmallSingleStopFn[mode == 1], dim3(1), dim3(kSmallThreads), small_lds_bytes(a.n, a.nnz, mode), st, a, *stop);
+    return hipGetLastError() == hipSuccess ? 1 : -1;
+}
 // (xp = x, rs = r, hs_p = p, hs_s = s: separate arrays, as the Hestenes-Stiefel sessions hold them)
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode) { return launch_small_single(st, a, mode, true); }
 

@@ -1042,17 +1042,10 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
         // inner products of the previous iteration: still one row of partials per block of the
         // previous launch -- every block of this launch sums them in the same fixed order
         // (thread t: rows t, t+B, ...; butterfly; waves in order), see prcg_kernels.hip
-        if (fz.nprev > 0) {
-            // (the 256-thread tree of k_reduce_final whatever this workgroup's size: the sums do not depend on whether an
-            //  iteration's partials were reduced here or by the reduction launch that ends a prcg_iterate call)
-            double dsum[5];
-            sum_prev_partials<5, WPB>(fz.prev_partials, fz.nprev, 0, dsum);
-            if (blockIdx.x == 0 && threadIdx.x < 5) fz.dots_prev_out[threadIdx.x] = dsum[threadIdx.x];
-            cf = predict(dsum, (write_mask >> 2) & 1);
-        } else {
-            cf = predict(PR1 ? fz.dots_old : ep_r, (write_mask >> 2) & 1);
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) { aux[0] = cf.al; aux[1] = cf.bt; aux[2] = cf.nup; }
+        // (the 256-thread tree of k_reduce_final whatever this workgroup's size: the sums do not depend on whether an
+        //  iteration's partials were reduced here or by the reduction launch that ends a prcg_iterate call)
+        // A session with a stop word (FusedPrev::word) may end here: nothing has been requested, loaded or stored yet.
+        if (!fused_prologue<WPB>(fz, PR1 ? fz.dots_old : ep_r, (write_mask >> 2) & 1, aux, cf)) return;
     }
 
     if constexpr (epi_lag(EPI)) {

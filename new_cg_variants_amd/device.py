@@ -323,8 +323,11 @@ class DeviceCSR:
 
     # -- solver session ------------------------------------------------------------------------
     def begin(self, variant, b, x0, max_iter, x_true=None, inv_diag=None, hist_mask=0, preconditioner=None, block_jacobi=None,
-              block_jacobi_var=None):
-        """inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
+              block_jacobi_var=None, rr_stop=None):
+        """rr_stop: None, or a threshold on r.r, finite and >= 0: THIS session then stops by itself on the device, converged or
+        broken down, by the rule of prcg.h: prcg_set_stop (pipelined variants on one GPU, unpreconditioned or with inv_diag;
+        anything else is refused); stop() tells where and why.
+        inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
         the ceil(n/bs) x bs x bs inverses of the diagonal blocks (prcg.h: prcg_set_block_jacobi); inv_blocks None: the blocks
         BUILT ON THE DEVICE from the operator (build_block_jacobi) -- rebuilt only when blocks of that bs built from the
         current values are not in force already (after update_values, after a session that removed or replaced them).
@@ -373,6 +376,8 @@ class DeviceCSR:
             self.set_block_jacobi_var(block_jacobi_var[0], block_jacobi_var[1])
         else:
             self.set_block_jacobi(0, None)
+        thr = None if rr_stop is None else np.array([rr_stop], dtype=np.float64)
+        self._check(self._lib.prcg_set_stop(self._h, L.ptr(thr)))            # (None clears what an earlier session set)
         self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
                                                L.ptr(xt), L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
@@ -456,6 +461,13 @@ class DeviceCSR:
     @property
     def k(self):
         return self._lib.prcg_iteration(self._h)
+
+    def stop(self):
+        """(k_stop, status) of the open single session: the iteration it stopped at and why (1 converged, 2 breakdown); (-1, 0)
+        while it runs, and for a session begun without rr_stop.  Synchronises."""
+        k_stop, status = C.c_int32(-1), C.c_int32(0)
+        self._check(self._lib.prcg_get_stop(self._h, C.byref(k_stop), C.byref(status)))
+        return int(k_stop.value), int(status.value)
 
     def schedule(self):
         """Flags of the schedule the current session runs (prcg.h PRCG_SCHED_*)."""
