@@ -500,11 +500,37 @@ int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status);
  *                      prcg_batch_begin's.  Refused beside what prcg_batch_begin refuses: null inv_diag; a system whose matrix lives in
  *                      LDS and lies within 128 bytes of the cap -- the fifth inner product needs 128 bytes more (the text names the
  *                      first such system).
+ *   prcg_batch_begin_block_jacobi  the same three variants preconditioned by POINT-BLOCK JACOBI applied inside the one-workgroup
+ *                      solver: blocks that follow a partition of each system, every size in 1..8 (a uniform bs is the partition 0,
+ *                      bs, 2 bs, ..., n with a short last block) -- prcg_set_block_jacobi_var for a batch.  nblk_off: n_sys + 1
+ *                      int64 from 0, system s has nb_s = nblk_off[s+1] - nblk_off[s] blocks.  block_ptr: the partitions concatenated,
+ *                      nb_s + 1 entries per system starting at nblk_off[s] + s, zero-based PER SYSTEM, first entry 0, last entry n_s
+ *                      (the convention of indptr per matrix).  inv_blocks: the inverses of the diagonal blocks in the PACKED format
+ *                      of prcg_set_block_jacobi_var -- block k as m_k x m_k doubles, row-major, no padding -- the systems
+ *                      concatenated in system order.  Blocks belong to the SYSTEM, as inv_diag does: two systems on one matrix may
+ *                      differ.  Values are not inspected: a nan poisons its own system only.  The apply is word for word the loop
+ *                      of prcg_set_block_jacobi_var: row start + a of a block forms acc = B[a][0] * v[start], then acc = acc +
+ *                      B[a][j] * v[start+j] for j ascending, every product and sum rounded, no FMA -- the bits of
+ *                      VarBlockJacobi.__call__ and BlockJacobi.__call__ (cg_variants).  The rows of a block exchange v through LDS
+ *                      inside the iteration; a block may lie anywhere in its system.  State, scalars, history and accessors are
+ *                      those of prcg_batch_begin_jacobi: the pipelined state is x, p, r, s, r~, s~ (w = A r~ and u = A s~ formed
+ *                      anew in every iteration), scalars {mu, delta, gamma, nu, rr}, Hestenes-Stiefel {mu, -, -, nu, rr};
+ *                      PRCG_VEC_RT / _ST are readable in pipelined sessions; prcg_batch_iterate / _sync and the accessors serve
+ *                      the session unchanged, and so does the stop (prcg_batch_set_stop / prcg_batch_get_stops).  Invariant: with
+ *                      every block of size 1 and inv_blocks = d a system carries the bits of prcg_batch_begin_jacobi with inv_diag =
+ *                      d (acc = B[0][0] * v is d * v).  Fit rule: that of prcg_batch_begin_jacobi, byte for byte -- matrix in registers:
+ *                      always fits; matrix in LDS: 32 n + 640 + 12 nnz + 16 <= 159744 bytes.  The exchange adds no LDS: it uses the
+ *                      buffer that otherwise takes the next iterate's pairs (the new r~, s~ overwrite the old in place), at the
+ *                      price of one barrier more per iteration.  So n up to 4096 is served, four rows per thread.
+ *                      Refused, each with PRCG_EINVAL and a text that names the reason and the first offending system, nothing
+ *                      changed (an open session goes on): a null pointer; nblk_off not from 0 or decreasing; a partition whose
+ *                      first entry is not 0 or whose last is not n_s; a block size outside 1..8 (system, block and size are
+ *                      named); a variant, history bit or max_iter that the other begins refuse; a system that does not fit.
  *   prcg_batch_iterate enqueues; every system advances by iters (k + iters <= max_iter).  prcg_batch_sync waits.
  *   prcg_batch_set_stop  rr_stop: n_sys thresholds on r.r, one per system (for a tolerance tol on the 2-norm of the updated residual:
  *                      tol * tol), finite and >= 0; NULL clears them.  They are copied at the call -- the caller's buffer is theirs
- *                      again on return -- and apply to sessions BEGUN afterwards (prcg_batch_begin and prcg_batch_begin_jacobi,
- *                      signatures unchanged); an open session is not affected.  In such a session every system stops by itself,
+ *                      again on return -- and apply to sessions BEGUN afterwards (prcg_batch_begin, prcg_batch_begin_jacobi and
+ *                      prcg_batch_begin_block_jacobi, signatures unchanged); an open session is not affected.  In such a session every system stops by itself,
  *                      decided inside its workgroup without the host: after iteration k, and at k = 0 on the initial state, on row k
  *                      of its scalars, mu = [0], nu = [3], rr = [PRCG_S_RR], in this order:
  *                        1. rr <= rr_stop[s]                                   -> stop, status 1 (converged);
@@ -536,11 +562,12 @@ int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status);
  * solver (a batch has no other schedule); begin -- another variant, another history bit, null rhs or x0, max_iter < 1.
  * Errors are reported through prcg_last_error of the handle the batch was created on.
  * Accessors (they synchronise): s = the system.  prcg_batch_get_vector: PRCG_VEC_X, _R, _P, _S, the system's n doubles, and in a
- * pipelined session begun with prcg_batch_begin_jacobi also PRCG_VEC_RT, _ST (refused in any other batch session);
+ * pipelined session begun with prcg_batch_begin_jacobi or prcg_batch_begin_block_jacobi also PRCG_VEC_RT, _ST (refused in any
+ * other batch session);
  * prcg_batch_get_solutions: every x concatenated in system order, ONE copy; scalars / coefficients / history as
  * prcg_get_scalars / prcg_get_coefficients / prcg_get_history return them (history: max_iter doubles, nothing is written when
- * hist_mask was 0; entries up to min(k, the system's stop iteration), zeros beyond).  No setters, no recorder of state, no preconditioner but the diagonal scaling of prcg_batch_begin_jacobi (no
- * block Jacobi, no callback). */
+ * hist_mask was 0; entries up to min(k, the system's stop iteration), zeros beyond).  No setters, no recorder of state, no preconditioner but the diagonal scaling of prcg_batch_begin_jacobi and the
+ * blocks of prcg_batch_begin_block_jacobi (no inverses built on the device, no callback). */
 typedef struct prcg_batch prcg_batch_t;
 int  prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
                        const int32_t* indices, const double* data, int n_sys, const int32_t* mat_of, prcg_batch_t** out);
@@ -548,6 +575,8 @@ void prcg_batch_destroy(prcg_batch_t* b);
 int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask);
 int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
                             uint32_t hist_mask);
+int prcg_batch_begin_block_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const int64_t* nblk_off,
+                                  const int64_t* block_ptr, const double* inv_blocks, int max_iter, uint32_t hist_mask);
 int prcg_batch_iterate(prcg_batch_t* b, int iters);
 int prcg_batch_sync(prcg_batch_t* b);
 int prcg_batch_iteration(const prcg_batch_t* b);

@@ -199,6 +199,13 @@ int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const
  * fits prcg_plan_small_batch and not this one.  Arguments and return value as prcg_plan_small_batch. */
 int prcg_plan_small_batch_jacobi(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
                                  int32_t* group_out);
+/* The same classification under the fit rule of prcg_batch_begin_block_jacobi (prcg.h): the Jacobi rule plus the LDS that the
+ * exchange between a block's rows adds, which is 0 bytes -- it goes through the buffer of the next iterate's pairs.  A system
+ * whose matrix lives in LDS fits if 32 n + 640 + 12 nnz + 16 <= 159744 bytes, a system whose matrix lives in registers always:
+ * a system fits this rule exactly if it fits prcg_plan_small_batch_jacobi's, n up to 4096.  A hook of its own so that the rule
+ * may part from the Jacobi rule without a change to its callers.  Arguments and return value as prcg_plan_small_batch. */
+int prcg_plan_small_batch_blocks(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
+                                 int32_t* group_out);
 /* the tile caps the device kernels were compiled for */
 void prcg_tile_caps(int* cap_nnz, int* cap_rows);
 

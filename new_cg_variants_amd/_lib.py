@@ -95,6 +95,7 @@ _SIGNATURES = {
     'prcg_batch_destroy': (None, [_P]),
     'prcg_batch_begin': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_uint32]),
     'prcg_batch_begin_jacobi': (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint32]),
+    'prcg_batch_begin_block_jacobi': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_uint32]),
     'prcg_batch_iterate': (C.c_int, [_P, C.c_int]),
     'prcg_batch_sync': (C.c_int, [_P]),
     'prcg_batch_iteration': (C.c_int, [_P]),
@@ -109,6 +110,7 @@ _SIGNATURES = {
     'prcg_batch_get_history': (C.c_int, [_P, C.c_int, _P]),
     'prcg_plan_small_batch': (C.c_int, [C.c_int, _P, _P, _P, _P, _P]),
     'prcg_plan_small_batch_jacobi': (C.c_int, [C.c_int, _P, _P, _P, _P, _P]),
+    'prcg_plan_small_batch_blocks': (C.c_int, [C.c_int, _P, _P, _P, _P, _P]),
     'prcg_set_profiling': (C.c_int, [_P, C.c_int]),
     'prcg_get_timings': (C.c_int, [_P, C.POINTER(Timings)]),
     'prcg_solve': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_uint32, _P, _P, C.POINTER(Timings)]),

@@ -806,6 +806,64 @@ def _batch_diagonals(name, preconditioner, sizes):
     return [np.ones(n) if d is None else d for n in sizes]
 
 
+def _batch_blocks(name, preconditioner, sizes):
+    """The systems' partitions and packed inverses, one pair (block_ptr, inv_blocks) per system (DeviceBatch.begin's
+    block_jacobi), from the `preconditioner` of a *_bpcg_batch function: one object (every system uses it: the sizes must agree)
+    or a sequence with one per system.  An object carrying block_ptr / inv_blocks (VarBlockJacobi) is taken as it is; one
+    carrying bs / inv_blocks (BlockJacobi: (ceil(n/bs), bs, bs), the short last block inside an identity) becomes the partition
+    0, bs, 2 bs, ..., n with the last block cut to its m x m part; an object carrying inv_diag (Jacobi) or a callable that the
+    exact probe of _diagonal_of shows to be v -> d * v is a partition of ones; None is the identity.  Host work only; ValueError
+    for anything else, for a partition prcg_batch_begin_block_jacobi would refuse and for blocks that do not match the system."""
+    n_sys = len(sizes)
+
+    def resolve(prec, n, where):
+        if prec is None:
+            return np.arange(n + 1, dtype=np.int64), np.ones(n)
+        inv = getattr(prec, 'inv_blocks', None)
+        if inv is not None and getattr(prec, 'block_ptr', None) is not None:
+            ptr = np.ascontiguousarray(prec.block_ptr, dtype=np.int64)
+            if ptr.ndim == 1 and ptr.size and ptr[-1] != n:
+                raise ValueError(f'{name}: {where} carries a partition of {int(ptr[-1])} rows, the system has size {n}')
+            ptr = _checked_partition(f'{name}: {where}', ptr, n)
+            inv = L.f64(inv).reshape(-1)
+            if inv.size != int(np.sum(np.diff(ptr) ** 2)):
+                raise ValueError(f'{name}: {where} carries {inv.size} entries of inv_blocks, its partition needs '
+                                 f'{int(np.sum(np.diff(ptr) ** 2))} (packed: block k is m_k x m_k)')
+            return ptr, inv
+        if inv is not None and getattr(prec, 'bs', None) is not None:
+            bs, inv = int(prec.bs), L.f64(inv)
+            if not 1 <= bs <= 8:
+                raise ValueError(f'{name}: {where} has block size {bs}, outside 1..8')
+            nb = -(-n // bs)
+            if inv.shape != (nb, bs, bs):
+                raise ValueError(f'{name}: {where} carries inv_blocks of shape {tuple(inv.shape)}, a system of size {n} with bs = {bs} '
+                                 f'has ({nb}, {bs}, {bs})')
+            ptr = np.minimum(np.arange(nb + 1, dtype=np.int64) * bs, n)
+            m = n - bs * (nb - 1)
+            return ptr, np.concatenate([inv[:nb - 1].reshape(-1), inv[nb - 1, :m, :m].reshape(-1)])
+        if not callable(prec) and getattr(prec, 'inv_diag', None) is None:
+            raise ValueError(f'{name}: {where} is neither a block-Jacobi object (bs / inv_blocks or block_ptr / inv_blocks), nor carries '
+                             'inv_diag, nor is callable')
+        d, fn = _diagonal_of(prec, n)
+        if fn is not None:
+            raise ValueError(f'{name}: {where} is a callable that is not a diagonal scaling: a batch applies block Jacobi (BlockJacobi, '
+                             'VarBlockJacobi), Jacobi or a callable v -> d * v')
+        d = np.ones(n) if d is None else np.asarray(d, dtype=np.float64)
+        if d.shape != (n,):
+            raise ValueError(f'{name}: {where} carries a diagonal of shape {tuple(d.shape)}, the system has size {n}')
+        return np.arange(n + 1, dtype=np.int64), d
+    if isinstance(preconditioner, (list, tuple)):
+        if len(preconditioner) != n_sys:
+            raise ValueError(f'{name}: preconditioner must be one object or a sequence of {n_sys}, one per system -- got {len(preconditioner)}')
+        return [resolve(prec, n, f'preconditioner[{s}]') for s, (prec, n) in enumerate(zip(preconditioner, sizes))]
+    if preconditioner is not None and len(set(sizes)) != 1:
+        raise ValueError(f'{name}: one preconditioner object for {n_sys} systems of different sizes {sorted(set(sizes))}: pass a sequence '
+                         'with one per system')
+    if preconditioner is None:
+        return [resolve(None, n, 'preconditioner') for n in sizes]
+    return [resolve(preconditioner, sizes[0], 'preconditioner')] * n_sys
+
+
 def _stop_thresholds(name, rtol, atol, rhs):
     """rtol / atol (each None, one value, or one value per system) -> the thresholds on r.r the device stops at, one per
     right-hand side in ``rhs``: thr_s = max(rtol_s ||b_s||_2, atol_s)^2; None when neither is given.  Shared by the batches and
@@ -826,14 +884,15 @@ def _stop_thresholds(name, rtol, atol, rhs):
         raise ValueError(f'{name}: {e}') from None
 
 
-def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=False):
+def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=False, blocks=False):
     """A batch of small independent systems in ONE launch, one workgroup per system (prcg.h: prcg_batch_create): what a loop
     of `name`'s single function over the systems computes.  Every argument is checked before the device is touched; what the
     batch does not serve raises ValueError -- nothing falls back to a loop of sessions.  jacobi: a *_pcg_batch function,
-    kwargs['preconditioner'] resolved to one reciprocal diagonal per system (prcg.h: prcg_batch_begin_jacobi)."""
+    kwargs['preconditioner'] resolved to one reciprocal diagonal per system (prcg.h: prcg_batch_begin_jacobi); blocks: a
+    *_bpcg_batch function, resolved to one partition with its inverses per system (prcg.h: prcg_batch_begin_block_jacobi)."""
     preconditioner = kwargs.pop('preconditioner', None)
     rtol, atol = kwargs.pop('rtol', None), kwargs.pop('atol', None)
-    if not jacobi and preconditioner is not None:
+    if not jacobi and not blocks and preconditioner is not None:
         raise ValueError(f'{name} takes no preconditioner: a batch runs the unpreconditioned one-workgroup solver')
     for key in ('x_true', 'w_replace'):
         if kwargs.get(key) is not None:
@@ -857,12 +916,13 @@ def _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, jacobi=F
         else:
             raise ValueError(f'{name}: callback {cname or repr(cb)} is not served by a batch (the updated_residual_2_norm recorder or none)')
     inv_diag = _batch_diagonals(name, preconditioner, sizes) if jacobi else None
+    block_jacobi = _batch_blocks(name, preconditioner, sizes) if blocks else None
     at = np.concatenate([[0], np.cumsum(sizes)])
     rr_stop = _stop_thresholds(name, rtol, atol, [B[at[s]:at[s + 1]] for s in range(n_sys)])
     batch = DeviceBatch(matrices, mat_of, device=int(kwargs.get('device', 0)))
     try:
         batch.begin(variant, [B[at[s]:at[s + 1]] for s in range(n_sys)], [X0[at[s]:at[s + 1]] for s in range(n_sys)], max_iter, hist_mask=mask,
-                    inv_diag=inv_diag, rr_stop=rr_stop)
+                    inv_diag=inv_diag, rr_stop=rr_stop, block_jacobi=block_jacobi)
         batch.iterate(max_iter - 1)
         batch.sync()
         outputs = [{'name': name, 'max_iter': max_iter, 'system': s} for s in range(n_sys)]
@@ -921,6 +981,28 @@ pipe_pr_m_pcg_batch = _make_pcg_batch(L.PIPE_PR_M, 'pipe_pr_m_pcg_batch', 'pipe_
 hs_pcg_batch = _make_pcg_batch(L.HS, 'hs_pcg_batch', 'hs_cg.py:70')
 
 
+def _make_bpcg_batch(variant, name, where):
+    single = name[:-len('_bpcg_batch')]
+
+    def f(As, bs, x0s, max_iter, preconditioner=None, callbacks=[], **kwargs):
+        kwargs['preconditioner'] = preconditioner
+        return _run_batch(variant, name, As, bs, x0s, max_iter, callbacks, kwargs, blocks=True)
+    f.__doc__ = (f'{single}_pcg ({where}) for a BATCH of small independent systems, all solved in one launch, one workgroup per system, '
+                 f'preconditioned by POINT-BLOCK JACOBI applied inside it.  As, bs, x0s, callbacks, rtol= / atol= and the result as '
+                 f'{single}_pcg_batch.  preconditioner: one object (every system uses it: the sizes must agree) or a sequence with one per '
+                 'system -- BlockJacobi, VarBlockJacobi (or any object carrying bs / inv_blocks or block_ptr / inv_blocks; every block size in '
+                 '1..8); Jacobi or a callable v -> d * v is a partition of ones; None is the identity; anything else is a ValueError.  A '
+                 'system that fits the one-workgroup solver with a diagonal scaling fits it with blocks (prcg.h: '
+                 'prcg_batch_begin_block_jacobi).')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+pipe_pr_bpcg_batch = _make_bpcg_batch(L.PIPE_PR, 'pipe_pr_bpcg_batch', 'pipe_pr_cg.py:201')
+pipe_pr_m_bpcg_batch = _make_bpcg_batch(L.PIPE_PR_M, 'pipe_pr_m_bpcg_batch', 'pipe_pr_cg.py:213')
+hs_bpcg_batch = _make_bpcg_batch(L.HS, 'hs_bpcg_batch', 'hs_cg.py:70')
+
+
 def _make(variant, name, preconditioned):
     def take_w_replace(kwargs):
         # gv_cg.py:9 / :93 take a residual-replacement predicate (default: never); the other variants swallow the keyword
@@ -966,4 +1048,5 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
            'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
            'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch', 'pipe_pr_pcg_batch', 'pipe_pr_m_pcg_batch', 'hs_pcg_batch',
+           'pipe_pr_bpcg_batch', 'pipe_pr_m_bpcg_batch', 'hs_bpcg_batch',
            'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi']

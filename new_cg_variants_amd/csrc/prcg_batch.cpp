@@ -4,7 +4,9 @@
 //
 // Layout on the device: the matrices concatenated (every matrix uploaded once, however many systems use it); per session the
 // systems' state concatenated in system order -- pipelined: the pairs (x,p) and (r,s); Hestenes-Stiefel: x, r, p, s; a session
-// begun with prcg_batch_begin_jacobi adds the pairs (r~,s~) (pipelined) and the systems' inverse diagonals d --, one
+// begun with prcg_batch_begin_jacobi adds the pairs (r~,s~) (pipelined) and the systems' inverse diagonals d; one begun with
+// prcg_batch_begin_block_jacobi the same pairs, the packed inverses of every system's blocks and one table entry per row
+// (SmallBlocks::tab, derived here from the partitions in O(n)) --, one
 // scalar history [max_iter+1][PRCG_NUM_SCALARS] and one coefficient history [max_iter+1][4] per system, and one descriptor
 // (SmallArgs) per system, sorted by LAUNCH GROUP: the systems whose matrix lives in registers (mode 1) first, then those
 // whose matrix lives in LDS (mode 0); inside a group in system order.  An iteration call is one launch per group on the
@@ -49,14 +51,14 @@ struct Buf {
     double* d() const { return static_cast<double*>(p); }
 };
 
-// launch groups of a batch: mode 1 first, then mode 0; group ids count the groups that exist.  jacobi: the fit rule of the
-// preconditioned bodies (128 B more LDS)
+// launch groups of a batch: mode 1 first, then mode 0; group ids count the groups that exist.  prec: the fit rule of the
+// preconditioned bodies (kSmallPrecJacobi and kSmallPrecBlocks: 128 B more LDS)
 int plan_groups(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out, int32_t* group_out,
-                bool jacobi = false) {
+                int prec = kSmallPrecNone) {
     bool have[2] = {false, false};
     for (int s = 0; s < n_sys; ++s) {
         int mode = 0;
-        if (nnz[s] < 0 || !small_fits(n[s], nnz[s], max_row_len[s], &mode, jacobi)) return -s - 1;
+        if (nnz[s] < 0 || !small_fits(n[s], nnz[s], max_row_len[s], &mode, prec)) return -s - 1;
         mode_out[s] = mode;
         have[mode] = true;
     }
@@ -76,12 +78,14 @@ struct prcg_batch {
     std::vector<const int*> indptr, col;           // per system: its matrix on the device
     std::vector<const double*> val;
     int count[2] = {0, 0};                         // systems of mode 0 / mode 1
-    size_t lds[2][2] = {};                         // [mode][jacobi]: largest small_lds_bytes of the mode's members
+    size_t lds[2][3] = {};                         // [mode][prec]: largest small_lds_bytes of the mode's members
     Buf m_indptr, m_col, m_val;                    // the matrices, concatenated
     Buf state, rhs, x0, dinv, dots, coef, desc, init, jac, tmp, stop, words;
+    Buf binv, btab, blk;                           // block Jacobi: the packed inverses, the per-row table, one SmallBlocks per system
     std::vector<double> rr_stop;                   // per system: the threshold on r.r of sessions begun from now on (empty: none)
     // ---- session ----
-    bool in_session = false, hs = false, jacobi = false, stopping = false;
+    bool in_session = false, hs = false, jacobi = false, stopping = false;      // jacobi: preconditioned, by d or by blocks
+    int prec = kSmallPrecNone;
     int variant = 0, max_iter = 0, k = 0;
     uint32_t hist_mask = 0;
 
@@ -92,6 +96,7 @@ struct prcg_batch {
     const SmallArgs* desc_of(int m) const { return static_cast<const SmallArgs*>(desc.p) + (m == 1 ? 0 : count[1]); }
     const SmallInit* init_of(int m) const { return static_cast<const SmallInit*>(init.p) + (m == 1 ? 0 : count[1]); }
     const SmallJacobi* jac_of(int m) const { return static_cast<const SmallJacobi*>(jac.p) + (m == 1 ? 0 : count[1]); }
+    const SmallBlocks* blk_of(int m) const { return static_cast<const SmallBlocks*>(blk.p) + (m == 1 ? 0 : count[1]); }
     const SmallStop* stop_of(int m) const { return static_cast<const SmallStop*>(stop.p) + (m == 1 ? 0 : count[1]); }
 };
 
@@ -106,7 +111,13 @@ int prcg_plan_small_batch(int n_sys, const int64_t* n, const int64_t* nnz, const
 int prcg_plan_small_batch_jacobi(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
                                  int32_t* group_out) {
     if (n_sys < 1 || !n || !nnz || !max_row_len || !mode_out || !group_out) return 0;
-    return plan_groups(n_sys, n, nnz, max_row_len, mode_out, group_out, true);
+    return plan_groups(n_sys, n, nnz, max_row_len, mode_out, group_out, kSmallPrecJacobi);
+}
+
+int prcg_plan_small_batch_blocks(int n_sys, const int64_t* n, const int64_t* nnz, const int32_t* max_row_len, int32_t* mode_out,
+                                 int32_t* group_out) {
+    if (n_sys < 1 || !n || !nnz || !max_row_len || !mode_out || !group_out) return 0;
+    return plan_groups(n_sys, n, nnz, max_row_len, mode_out, group_out, kSmallPrecBlocks);
 }
 
 int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64_t* nnz_off, const int32_t* indptr,
@@ -178,8 +189,8 @@ int prcg_batch_create(prcg_t* h, int n_mat, const int64_t* rows_off, const int64
         b->col[(size_t)s] = static_cast<const int*>(b->m_col.p) + nnz_off[m];
         b->val[(size_t)s] = b->m_val.d() + nnz_off[m];
         ++b->count[md];
-        for (int j = 0; j < 2; ++j) {
-            const size_t need = small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], md, j == 1);
+        for (int j = 0; j < 3; ++j) {
+            const size_t need = small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], md, j);
             if (need > b->lds[md][j]) b->lds[md][j] = need;
         }
     }
@@ -199,23 +210,69 @@ void prcg_batch_destroy(prcg_batch_t* b) {
 
 }  // extern "C"
 
-// prcg_batch_begin and prcg_batch_begin_jacobi (jacobi: inv_diag is an argument, fn names the entry in the error texts)
-static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant, const double* rhs, const double* x0, const double* inv_diag,
-                       int max_iter, uint32_t hist_mask) {
+// the blocks of prcg_batch_begin_block_jacobi as the caller passes them
+struct BlockArgs { const int64_t* nblk_off; const int64_t* block_ptr; const double* inv_blocks; };
+
+// prcg_batch_begin, prcg_batch_begin_jacobi (prec = kSmallPrecJacobi: inv_diag is an argument) and prcg_batch_begin_block_jacobi
+// (prec = kSmallPrecBlocks: blocks is); fn names the entry in the error texts
+static int batch_begin(prcg_batch_t* b, const char* fn, int prec, int variant, const double* rhs, const double* x0, const double* inv_diag,
+                       const BlockArgs* blocks, int max_iter, uint32_t hist_mask) {
     if (!b) return PRCG_EINVAL;
     prcg_t* h = b->h;
+    const bool jacobi = prec != kSmallPrecNone, blk = prec == kSmallPrecBlocks;
     CHECK(h, variant == PRCG_PIPE_PR || variant == PRCG_PIPE_PR_M || variant == PRCG_HS,
            "%s: variant %d is not served by a batch (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_HS: the one-workgroup solver's)", fn, variant);
-    CHECK(h, rhs && x0 && (inv_diag || !jacobi), jacobi ? "%s: null rhs, x0 or inv_diag" : "%s: null rhs or x0", fn);
+    if (blk) CHECK(h, rhs && x0 && blocks->nblk_off && blocks->block_ptr && blocks->inv_blocks,
+                   "%s: null rhs, x0, nblk_off, block_ptr or inv_blocks", fn);
+    else CHECK(h, rhs && x0 && (inv_diag || !jacobi), jacobi ? "%s: null rhs, x0 or inv_diag" : "%s: null rhs or x0", fn);
     CHECK(h, max_iter >= 1, "%s: max_iter = %d, must be at least 1", fn, max_iter);
     CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
            "%s: history bits %u: a batch records the updated residual only (PRCG_HIST_UPDATED_RESIDUAL_2_NORM or 0)", fn, hist_mask);
-    for (int s = 0; jacobi && s < b->n_sys; ++s) {
+    // block Jacobi: the partitions, and from them one table entry per row and the size of the packed inverses
+    std::vector<int2> tab;
+    std::vector<int64_t> inv_off;                  // per system (+1): first double of its inverses in inv_blocks
+    if (blk) {
+        const int64_t* off = blocks->nblk_off;
+        CHECK(h, off[0] == 0, "%s: nblk_off[0] is %lld, not 0", fn, (long long)off[0]);
+        for (int s = 0; s < b->n_sys; ++s)
+            CHECK(h, off[s + 1] >= off[s], "%s: nblk_off decreases at system %d (%lld after %lld)", fn, s, (long long)off[s + 1], (long long)off[s]);
+        for (int s = 0; s < b->n_sys; ++s) {
+            const int64_t nb = off[s + 1] - off[s], n = b->n[(size_t)s];
+            const int64_t* ptr = blocks->block_ptr + off[s] + s;       // nb + 1 entries per system
+            CHECK(h, ptr[0] == 0, "%s: the partition of system %d starts at %lld, not 0 (block_ptr is zero-based per system)", fn, s,
+                   (long long)ptr[0]);
+            CHECK(h, ptr[nb] == n, "%s: the partition of system %d ends at %lld, not at its n = %lld", fn, s, (long long)ptr[nb], (long long)n);
+            for (int64_t k = 0; k < nb; ++k)
+                CHECK(h, ptr[k + 1] - ptr[k] >= 1 && ptr[k + 1] - ptr[k] <= 8, "%s: system %d, block %lld has size %lld, outside 1..8", fn, s,
+                       (long long)k, (long long)(ptr[k + 1] - ptr[k]));
+        }
+        for (int s = 0; s < b->n_sys; ++s) {
+            int mode = 0;
+            CHECK(h, small_fits(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode, kSmallPrecBlocks),
+                   "%s: system %d (n = %d, nnz = %d) fits the one-workgroup solver without a preconditioner but not with one: "
+                   "the preconditioned solver needs %zu bytes of LDS, 128 more, and the cap is 159744", fn, s, b->n[(size_t)s], b->nnz[(size_t)s], small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], 0, kSmallPrecBlocks));
+        }
+        tab.resize((size_t)b->N());
+        inv_off.assign((size_t)b->n_sys + 1, 0);
+        for (int s = 0; s < b->n_sys; ++s) {
+            const int64_t nb = off[s + 1] - off[s];
+            const int64_t* ptr = blocks->block_ptr + off[s] + s;
+            int2* row = tab.data() + b->voff[(size_t)s];
+            int at = 0;                                // < 8 n <= 32768: offsets inside a system fit an int
+            for (int64_t k = 0; k < nb; ++k) {
+                const int start = (int)ptr[k], m = (int)(ptr[k + 1] - ptr[k]);
+                for (int a = 0; a < m; ++a) row[start + a] = make_int2(start | (m << 16), at + a * m);
+                at += m * m;
+            }
+            inv_off[(size_t)s + 1] = inv_off[(size_t)s] + at;
+        }
+    }
+    for (int s = 0; prec == kSmallPrecJacobi && s < b->n_sys; ++s) {
         int mode = 0;
-        CHECK(h, small_fits(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode, true),
+        CHECK(h, small_fits(b->n[(size_t)s], b->nnz[(size_t)s], b->mrl[(size_t)s], &mode, kSmallPrecJacobi),
                "%s: system %d (n = %d, nnz = %d) fits the one-workgroup solver without a preconditioner but not with one: "
                "the preconditioned solver needs %zu bytes of LDS, 128 more, and the cap is 159744", fn, s, b->n[(size_t)s], b->nnz[(size_t)s],
-               small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], 0, true));
+               small_lds_bytes(b->n[(size_t)s], b->nnz[(size_t)s], 0, kSmallPrecJacobi));
     }
     HIPCHK(h, hipSetDevice(b->dev));
     b->in_session = false;
@@ -224,7 +281,11 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
     const size_t D = sizeof(double);
     const bool hs = variant == PRCG_HS;
     HIPCHK(h, b->state.ensure((size_t)(jacobi && !hs ? 6 : 4) * N * D));
-    if (jacobi) {
+    if (blk) {
+        HIPCHK(h, b->binv.ensure((size_t)inv_off[(size_t)n_sys] * D));
+        HIPCHK(h, b->btab.ensure((size_t)N * sizeof(int2)));
+        HIPCHK(h, b->blk.ensure((size_t)n_sys * sizeof(SmallBlocks)));
+    } else if (jacobi) {
         HIPCHK(h, b->dinv.ensure((size_t)N * D));
         HIPCHK(h, b->jac.ensure((size_t)n_sys * sizeof(SmallJacobi)));
     }
@@ -241,10 +302,11 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
         HIPCHK(h, b->words.ensure((size_t)n_sys * 2 * sizeof(int32_t)));
     }
     b->stopping = stopping;
-    b->variant = variant; b->hs = hs; b->jacobi = jacobi; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
+    b->variant = variant; b->hs = hs; b->jacobi = jacobi; b->prec = prec; b->max_iter = max_iter; b->hist_mask = hist_mask; b->k = 0;
     std::vector<SmallArgs> desc((size_t)n_sys);
     std::vector<SmallInit> init((size_t)n_sys);
-    std::vector<SmallJacobi> jac(jacobi ? (size_t)n_sys : 0);
+    std::vector<SmallJacobi> jac(prec == kSmallPrecJacobi ? (size_t)n_sys : 0);
+    std::vector<SmallBlocks> sblk(blk ? (size_t)n_sys : 0);
     std::vector<SmallStop> stop(stopping ? (size_t)n_sys : 0);
     std::vector<int32_t> words(stopping ? (size_t)n_sys * 2 : 0);
     double* st = b->state.d();
@@ -259,7 +321,9 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
         desc[(size_t)b->slot[(size_t)s]] = a;
         init[(size_t)b->slot[(size_t)s]] = SmallInit{b->rhs.d() + v, b->x0.d() + v};
         // the pairs (r~,s~) follow (x,p) and (r,s); Hestenes-Stiefel holds no r~
-        if (jacobi) jac[(size_t)b->slot[(size_t)s]] = SmallJacobi{hs ? nullptr : st + 4 * N + 2 * v, b->dinv.d() + v};
+        if (blk) sblk[(size_t)b->slot[(size_t)s]] = SmallBlocks{hs ? nullptr : st + 4 * N + 2 * v, static_cast<const int2*>(b->btab.p) + v,
+                                                                 b->binv.d() + inv_off[(size_t)s]};
+        else if (jacobi) jac[(size_t)b->slot[(size_t)s]] = SmallJacobi{hs ? nullptr : st + 4 * N + 2 * v, b->dinv.d() + v};
         if (stopping) {                                // every system starts as {-1, 0}: running
             stop[(size_t)b->slot[(size_t)s]] = SmallStop{b->rr_stop[(size_t)s], static_cast<int*>(b->words.p) + 2 * s};
             words[(size_t)2 * s] = -1; words[(size_t)2 * s + 1] = 0;
@@ -272,7 +336,12 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
     HIPCHK(h, hipMemcpyAsync(b->x0.p, x0, (size_t)N * D, hipMemcpyHostToDevice, sc));
     HIPCHK(h, hipMemcpyAsync(b->desc.p, desc.data(), (size_t)n_sys * sizeof(SmallArgs), hipMemcpyHostToDevice, sc));
     HIPCHK(h, hipMemcpyAsync(b->init.p, init.data(), (size_t)n_sys * sizeof(SmallInit), hipMemcpyHostToDevice, sc));
-    if (jacobi) {
+    if (blk) {
+        if (inv_off[(size_t)n_sys])
+            HIPCHK(h, hipMemcpyAsync(b->binv.p, blocks->inv_blocks, (size_t)inv_off[(size_t)n_sys] * D, hipMemcpyHostToDevice, sc));
+        HIPCHK(h, hipMemcpyAsync(b->btab.p, tab.data(), (size_t)N * sizeof(int2), hipMemcpyHostToDevice, sc));
+        HIPCHK(h, hipMemcpyAsync(b->blk.p, sblk.data(), (size_t)n_sys * sizeof(SmallBlocks), hipMemcpyHostToDevice, sc));
+    } else if (jacobi) {
         HIPCHK(h, hipMemcpyAsync(b->dinv.p, inv_diag, (size_t)N * D, hipMemcpyHostToDevice, sc));
         HIPCHK(h, hipMemcpyAsync(b->jac.p, jac.data(), (size_t)n_sys * sizeof(SmallJacobi), hipMemcpyHostToDevice, sc));
     }
@@ -283,7 +352,8 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
     HIPCHK(h, hipStreamSynchronize(sc));             // (desc / init leave scope; the caller's buffers are theirs again)
     for (int m = 1; m >= 0; --m) {                 // one initialisation launch per group
         if (!b->count[m]) continue;
-        if (launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), jacobi ? b->jac_of(m) : nullptr, b->count[m], hs) < 0)
+        if (launch_small_batch_init(sc, b->desc_of(m), b->init_of(m), prec == kSmallPrecJacobi ? b->jac_of(m) : nullptr, b->count[m], hs,
+                                    blk ? b->blk_of(m) : nullptr) < 0)
             return fail(h, PRCG_EHIP, "%s: kernel launch failed", fn);
     }
     HIPCHK(h, hipStreamSynchronize(sc));
@@ -294,12 +364,18 @@ static int batch_begin(prcg_batch_t* b, const char* fn, bool jacobi, int variant
 extern "C" {
 
 int prcg_batch_begin(prcg_batch_t* b, int variant, const double* rhs, const double* x0, int max_iter, uint32_t hist_mask) {
-    return batch_begin(b, "prcg_batch_begin", false, variant, rhs, x0, nullptr, max_iter, hist_mask);
+    return batch_begin(b, "prcg_batch_begin", kSmallPrecNone, variant, rhs, x0, nullptr, nullptr, max_iter, hist_mask);
 }
 
 int prcg_batch_begin_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const double* inv_diag, int max_iter,
                             uint32_t hist_mask) {
-    return batch_begin(b, "prcg_batch_begin_jacobi", true, variant, rhs, x0, inv_diag, max_iter, hist_mask);
+    return batch_begin(b, "prcg_batch_begin_jacobi", kSmallPrecJacobi, variant, rhs, x0, inv_diag, nullptr, max_iter, hist_mask);
+}
+
+int prcg_batch_begin_block_jacobi(prcg_batch_t* b, int variant, const double* rhs, const double* x0, const int64_t* nblk_off,
+                                  const int64_t* block_ptr, const double* inv_blocks, int max_iter, uint32_t hist_mask) {
+    const BlockArgs blocks{nblk_off, block_ptr, inv_blocks};
+    return batch_begin(b, "prcg_batch_begin_block_jacobi", kSmallPrecBlocks, variant, rhs, x0, nullptr, &blocks, max_iter, hist_mask);
 }
 
 int prcg_batch_iterate(prcg_batch_t* b, int iters) {
@@ -313,8 +389,9 @@ int prcg_batch_iterate(prcg_batch_t* b, int iters) {
     const int meurant = b->variant == PRCG_PIPE_PR_M ? 1 : 0;
     for (int m = 1; m >= 0; --m) {                 // one launch per group: every system advances by iters
         if (!b->count[m]) continue;
-        const SmallBatchArgs g{b->desc_of(m), b->jacobi ? b->jac_of(m) : nullptr, b->stopping ? b->stop_of(m) : nullptr, b->k, iters, meurant};
-        const int rc = launch_small_batch(b->sc, g, b->count[m], m, b->lds[m][b->jacobi], b->hs);
+        const SmallBatchArgs g{b->desc_of(m), b->prec == kSmallPrecJacobi ? b->jac_of(m) : nullptr, b->stopping ? b->stop_of(m) : nullptr, b->k,
+                               iters, meurant};
+        const int rc = launch_small_batch(b->sc, g, b->count[m], m, b->lds[m][b->prec], b->hs, b->prec == kSmallPrecBlocks ? b->blk_of(m) : nullptr);
         if (rc < 0) return fail(h, PRCG_EHIP, "prcg_batch_iterate: kernel launch failed (or the dynamic-LDS attribute could not be set)");
     }
     b->k += iters;
@@ -372,7 +449,7 @@ int prcg_batch_get_vector(prcg_batch_t* b, int which, int s, double* out) {
     CHECK(h, s >= 0 && s < b->n_sys, "prcg_batch_get_vector: system %d outside [0, %d)", s, b->n_sys);
     const bool tilde = which == PRCG_VEC_RT || which == PRCG_VEC_ST;
     CHECK(h, !tilde || (b->jacobi && !b->hs), "prcg_batch_get_vector: vector %d (PRCG_VEC_RT / _ST) is held by a pipelined session begun "
-           "with prcg_batch_begin_jacobi only: this session is %s", which, b->jacobi ? "Hestenes-Stiefel, which forms r~ anew in every iteration"
+           "with prcg_batch_begin_jacobi or prcg_batch_begin_block_jacobi only: this session is %s", which, b->jacobi ? "Hestenes-Stiefel, which forms r~ anew in every iteration"
                                                                                      : "unpreconditioned");
     CHECK(h, tilde || which == PRCG_VEC_X || which == PRCG_VEC_R || which == PRCG_VEC_P || which == PRCG_VEC_S,
            "prcg_batch_get_vector: vector %d is not part of a batch session (PRCG_VEC_X, _R, _P, _S)", which);

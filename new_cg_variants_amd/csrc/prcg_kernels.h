@@ -324,8 +324,11 @@ struct SmallArgs {
 // The fit rule: true and *mode = 1 (matrix in registers) or 0 (matrix in LDS beside the vectors); jacobi: the need of the bodies
 // preconditioned by a diagonal scaling, which sum five inner products -- 128 B more LDS -- so a matrix in LDS may fit without
 // the scaling and not with it (the mode of one that fits both ways is the same).  small_lds_bytes: the dynamic LDS of one system.
-size_t small_lds_bytes(int n, int nnz, int mode, bool jacobi = false);
-bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, bool jacobi = false);
+// prec: kSmallPrecNone, kSmallPrecJacobi (`jacobi` above) or kSmallPrecBlocks -- block Jacobi (SmallBlocks below), which needs
+// what the scaling needs: its rows exchange through the buffer of the successor.
+enum { kSmallPrecNone = 0, kSmallPrecJacobi = 1, kSmallPrecBlocks = 2 };
+size_t small_lds_bytes(int n, int nnz, int mode, int prec = kSmallPrecNone);
+bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, int prec = kSmallPrecNone);
 // The single sessions.  The dynamic-LDS attribute of every kernel of the family is set, and its result checked, on first use on
 // each device: a launch fails (-1) where it could not be set.
 // stop (or null; SmallStop below, declared here for the launcher): the single session stopped at a residual threshold -- the
@@ -342,6 +345,14 @@ int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode);      // Heste
 // belongs to desc[i].  Pipelined: xp = (x,p), rs = (r,s), ts = (r~,s~); Hestenes-Stiefel: xp = x, rs = r, hs_p, hs_s, and r~ = d r
 // is formed anew in every iteration.  dots[k] = {mu, delta, gamma, nu, rr} (HS: {mu, -, -, nu, rr}), nu = r~.r, rr = r.r.
 struct SmallJacobi { double* ts; const double* d; };
+// blk (or null; then jac is null): the batch preconditioned by point-block Jacobi applied inside the one-workgroup solver, blocks
+// of 1..8 rows following a partition of the system.  blk[i] belongs to desc[i].  ts: as SmallJacobi's.  tab: one int2 per row,
+// x = first row of the row's block | (size of the block << 16), y = offset of the row's row of the block's inverse in inv.  inv: the
+// inverses, packed (block k: m_k x m_k row-major, no padding).  Row start + a forms (M^-1 v)_{start+a} = acc, acc = B[a][0] v[start],
+// acc = acc + B[a][j] v[start+j] for j = 1 .. m-1, every product and sum rounded: the loop of k_bjvar_apply (prcg_blockjac.hip).
+// The rows of a block exchange v through LDS, in the buffer of the successor: the pipelined body puts (w,u) there and writes the
+// new (r~,s~) over the old, Hestenes-Stiefel puts r where the next direction goes.  Scalars and state as with jac.
+struct SmallBlocks { double* ts; const int2* tab; const double* inv; };
 // stop (or null): every system stopped at its OWN residual threshold, decided inside its workgroup.  stop[i] belongs to desc[i].
 // thr: a bound on r.r, finite and >= 0.  word: two ints in device memory, word[0] the iteration the system stopped at (-1 while
 // it runs), word[1] its status (0 running, 1 converged, 2 breakdown).  The rule, applied to row k of the scalars (mu = dots[k][0],
@@ -353,15 +364,16 @@ struct SmallJacobi { double* ts; const double* d; };
 struct SmallStop { double thr; int* word; };
 // one launch of a batch: the arrays above (device memory) and where the session stands
 struct SmallBatchArgs { const SmallArgs* desc; const SmallJacobi* jac; const SmallStop* stop; int k0, iters, meurant; };
-// lds: the largest small_lds_bytes(n, nnz, mode, jac != null) among the launch's systems -- each workgroup carves it by its own
-// n and nnz
-int launch_small_batch(hipStream_t st, const SmallBatchArgs& g, int count, int mode, size_t lds, bool hs);
+// lds: the largest small_lds_bytes(n, nnz, mode, prec) among the launch's systems -- each workgroup carves it by its own
+// n and nnz.  blk: the block-Jacobi kernels (g.jac is ignored); they take it beside g, so the others keep their arguments
+int launch_small_batch(hipStream_t st, const SmallBatchArgs& g, int count, int mode, size_t lds, bool hs, const SmallBlocks* blk = nullptr);
 // x = x0, r = b - A x0, [r~ = d r,] p = r~, s = A p [, pipelined: s~ = d s] and row 0 of every system's scalars in ONE launch;
-// init[i] belongs to desc[i]; jac null: no scaling (r~ is r).  The vectors carry the bits of the single session's start-up
+// init[i] belongs to desc[i]; jac null: no scaling (r~ is r); blk: r~ = M^-1 r and s~ = M^-1 s by the blocks (jac is ignored).  The vectors carry the bits of the single session's start-up
 // launches; the inner products are summed in the order of the loop (thread-sequential rows, wave butterfly, 16 waves), not of
 // those launches.
 struct SmallInit { const double* b; const double* x0; };       // right-hand side and initial guess of one system
-int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs);
+int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs,
+                            const SmallBlocks* blk = nullptr);
 
 // ---- fused vector updates + inner products -----------------------------------------
 struct PipeUpdateArgs {

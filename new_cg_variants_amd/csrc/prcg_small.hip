@@ -9,10 +9,11 @@
 // uniform).
 //
 // Two methods, each ONE body: small_pipe_pr_body (pipe_pr_cg.py:61-75, with a diagonal scaling :109-193) and small_hs_body
-// (hs_cg.py:54-62, :70-131), templated on where the matrix lives (MODE), on the scaling (JAC) and on the per-system stop (STOP).
+// (hs_cg.py:54-62, :70-131), templated on where the matrix lives (MODE), on the preconditioner (PREC: none, a diagonal scaling, or
+// point-block Jacobi with blocks of 1..8 rows -- a batch's only) and on the per-system stop (STOP).
 // The single sessions launch them on the launch's SmallArgs (k_small_pipe_pr, k_small_hs; k_small_pipe_pr_stop: a session with a
 // residual threshold, the STOP form on the session's own word), a batch on the descriptor of
-// workgroup blockIdx.x (k_small_pipe_pr_batch, k_small_hs_batch) -- one body, so that a system of a batch carries the single
+// workgroup blockIdx.x (k_small_pipe_pr_batch, k_small_hs_batch; with block Jacobi k_small_pipe_pr_blocks, k_small_hs_blocks) -- one body, so that a system of a batch carries the single
 // solver's bits.  Host side at the end: the fit rules and the launchers.
 #include <hip/hip_runtime.h>
 
@@ -121,6 +122,56 @@ __device__ __forceinline__ double small_red_get(const double* red, int q) {
     return wave_sum16(red[(threadIdx.x & 15) * K + q]);
 }
 
+// ---- point-block Jacobi: the rows of a thread in their blocks ----
+// Row start + a of a block of m rows (1..8) forms (M^-1 v)_{start+a} from the block's m entries of v, which its rows exchange
+// through LDS, and its own row B[a][0..m) of the block's inverse:  acc = B[a][0] v[start];  acc = acc + B[a][j] v[start+j],
+// j = 1 .. m-1 -- every product and sum rounded, the loop of k_block_jacobi_var (prcg_blockjac.hip), so VarBlockJacobi.__call__
+// carries its bits.  A block may lie anywhere: across waves, and across rows 1023/1024, ... (a thread's first and second row);
+// the barrier between the stores of v and these loads is the caller's.  Where B[a] lives: MODE 1 (one row per thread) in eight
+// registers, loaded once per launch; MODE 0 (up to four rows per thread) in memory, read through L2 in every iteration -- 32
+// doubles per thread would not fit beside the state, and LDS is the matrix's.  The loads of v are unrolled and predicated like
+// the gathers of small_row_product; index min(j, m-1) keeps a load hoisted above its predicate inside the block.
+template <int MODE> struct SmallBlockRows {
+    int2 tab[kSmallRowsOf<MODE>];                                // row j of the thread: SmallBlocks::tab, {start | m << 16, offset of B[a]}
+    const double* inv;                                           // MODE 0: B[a] is read from memory, inv + tab[j].y
+    double b[kSmallRegLen];                                      // MODE 1: B[a] of the thread's one row
+};
+template <int MODE>
+__device__ __forceinline__ void small_block_stage(SmallBlockRows<MODE>& k, const SmallBlocks& bk, int n) {
+    static_assert(kSmallRegLen == 8, "a block has at most 8 rows");
+#pragma unroll
+    for (int j = 0; j < kSmallRowsOf<MODE>; ++j) {
+        const int row = threadIdx.x + j * kSmallThreads;
+        k.tab[j] = make_int2(1 << 16, 0);
+        if (row < n) k.tab[j] = bk.tab[row];
+    }
+    k.inv = bk.inv;
+    if constexpr (MODE == 1) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) k.b[q] = (threadIdx.x < n && q < (k.tab[0].x >> 16)) ? bk.inv[k.tab[0].y + q] : 0.0;
+    }
+}
+template <int MODE, typename V>
+__device__ __forceinline__ V small_block_apply(const SmallBlockRows<MODE>& k, int j, const V* src) {
+    const int start = k.tab[j].x & 0xffff, m = k.tab[j].x >> 16;
+    if constexpr (MODE == 1) {
+        V g[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) g[q] = src[start + (q < m ? q : m - 1)];      // all loads in flight
+        V acc = vmul(k.b[0], g[0]);
+#pragma unroll
+        for (int q = 1; q < 8; ++q)
+            if (q < m) vacc(acc, vmul(k.b[q], g[q]));
+        return acc;
+    } else {
+        const double* __restrict__ b = k.inv + k.tab[j].y;
+        V acc = vmul(b[0], src[start]);
+#pragma unroll 1                                                 // (unrolled, four rows' loads in flight at once spill to scratch)
+        for (int q = 1; q < m; ++q) vacc(acc, vmul(b[q], src[start + q]));
+        return acc;
+    }
+}
+
 // ---- stopping a system of a batch at its OWN residual threshold: the STOP form of the bodies (rule: prcg_kernels.h) ----
 // Every thread of the workgroup must take the same exit, or some waves would wait at a barrier the others never reach.  The
 // operands of the rule are the same bits in all 1024 threads: thr comes from a load of one address that the launch never
@@ -153,9 +204,16 @@ __device__ __forceinline__ void small_stop_record(const SmallStop& st, int k, in
 // expressions with d dropped, not multiplied by one.  Sums per iteration: mu = p.s, delta = r.s~, gamma = s~.s, nu = r~.r, with
 // JAC also rr = r.r (without: rr = nu): red is [16 waves][4 or 5].  Two barriers per iteration.
 // dots[k] = {mu, delta, gamma, nu, rr}, coef[k] = {al, bt, nu_pred}.
-template <int MODE, bool JAC, bool STOP>
-__device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const SmallJacobi& jc, const SmallStop& stop) {
+// PREC == kSmallPrecBlocks (M^-1 by blocks, bk; jc.ts holds the pairs (r~,s~), jc.d is not read): everything above with u~ and w~
+// from the block apply.  The row products of ALL the thread's rows come first and go to LDS as pairs (w,u); one barrier; then
+// each row forms (w~,u~) from its block's pairs and goes on as with the scaling.  The pairs go where the successor would
+// (nxt), and the successor goes where the source is: once the products are done a row's (r~,s~) in cur is read by its own
+// thread only, which overwrites it with the new one -- so the two buffers are not swapped, LDS holds what it holds with the
+// scaling, and the iteration has three barriers: cur is gathered from, and nxt written, only behind the two of the sums.
+template <int MODE, int PREC, bool STOP>
+__device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const SmallJacobi& jc, const SmallBlocks& bk, const SmallStop& stop) {
     if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
+    constexpr bool JAC = PREC != kSmallPrecNone, BLK = PREC == kSmallPrecBlocks;
     constexpr int ROWS = kSmallRowsOf<MODE>, K = JAC ? 5 : 4;
     const int n = a.n, tid = threadIdx.x;
     const SmallLds<double2> l = small_carve<MODE, double2, K>(n, a.nnz);
@@ -171,12 +229,15 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const Sma
             const double2 xp = XPg[row];
             const double2 rs = RSg[row];
             xr[j] = xp.x; pr[j] = xp.y;
-            if constexpr (JAC) { rr_[j] = rs.x; sr[j] = rs.y; dr[j] = jc.d[row]; l.cur[row] = TSg[row]; }
+            if constexpr (JAC) { rr_[j] = rs.x; sr[j] = rs.y; l.cur[row] = TSg[row]; }
             else l.cur[row] = rs;
+            if constexpr (PREC == kSmallPrecJacobi) dr[j] = jc.d[row];
         }
     }
     SmallMatrix<MODE> m;
     small_stage<MODE>(m, a, l.lval, l.lcol);
+    SmallBlockRows<MODE> kb;
+    if constexpr (BLK) small_block_stage<MODE>(kb, bk, n);
     // inner products of the incoming state
     const double* row0 = a.dots + (size_t)a.k0 * kPartialStride;
     double mu = row0[0], dl = row0[1], gm = row0[2], nu = row0[3];
@@ -197,19 +258,36 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const Sma
             cf[0] = al; cf[1] = bt; cf[2] = nup;
         }
         double acc[K] = {};
+        double2 wu1;                                             // MODE 1 keeps its row's pair; MODE 0 reads its rows' back
+        if constexpr (BLK) {                                     // every row's (w,u) to its block's rows
+#pragma unroll
+            for (int j = 0; j < ROWS; ++j) {
+                const int row = tid + j * kSmallThreads;
+                if (row < n) { wu1 = small_row_product<MODE>(m, j, cur); nxt[row] = wu1; }
+            }
+            lds_barrier();                                       // the pairs are complete, and cur has been gathered from
+        }
 #pragma unroll
         for (int j = 0; j < ROWS; ++j) {
             const int row = tid + j * kSmallThreads;
             if (row < n) {
-                const double2 wu = small_row_product<MODE>(m, j, cur);      // w = (A r~)_i, u = (A s~)_i
+                double2 wu;                                      // w = (A r~)_i, u = (A s~)_i
+                if constexpr (BLK) wu = MODE == 1 ? wu1 : nxt[row];
+                else wu = small_row_product<MODE>(m, j, cur);
                 const double2 ts = cur[row];
                 xr[j] = xr[j] + al * pr[j];                      // x += a p
                 const double rtn = ts.x - al * ts.y;             // r~ -= a s~
                 const double wn = wu.x - al * wu.y;              // w -= a u
                 double rn = rtn, sn, stn;
                 if constexpr (JAC) {
-                    const double ut = dr[j] * wu.y;              // u~ = M^-1 u
-                    const double wt = dr[j] * wu.x;              // w~ = M^-1 w
+                    double ut, wt;
+                    if constexpr (BLK) {
+                        const double2 t = small_block_apply<MODE>(kb, j, nxt);
+                        wt = t.x; ut = t.y;                      // w~ = M^-1 w, u~ = M^-1 u
+                    } else {
+                        ut = dr[j] * wu.y;                       // u~ = M^-1 u
+                        wt = dr[j] * wu.x;                       // w~ = M^-1 w
+                    }
                     rn = rr_[j] - al * sr[j];                    // r -= a s
                     const double wtn = wt - al * ut;             // w~ -= a u~
                     sn = wn + bt * sr[j];                        // s = w + b s
@@ -221,7 +299,8 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const Sma
                 }
                 const double pn = rtn + bt * pr[j];              // p = r~ + b p
                 pr[j] = pn;
-                nxt[row] = make_double2(rtn, stn);
+                if constexpr (BLK) cur[row] = make_double2(rtn, stn);
+                else nxt[row] = make_double2(rtn, stn);
                 acc[0] += pn * sn; acc[1] += rn * stn; acc[2] += stn * sn; acc[3] += rtn * rn;
                 if constexpr (JAC) acc[4] += rn * rn;
             }
@@ -239,7 +318,7 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const Sma
             d[0] = mu; d[1] = dl; d[2] = gm; d[3] = nu; d[4] = rr;
         }
         lds_barrier();                                           // everybody has read red before it is rewritten
-        double2* tmp = cur; cur = nxt; nxt = tmp;
+        if constexpr (!BLK) { double2* tmp = cur; cur = nxt; nxt = tmp; }
         if constexpr (STOP) {                                    // the iteration is complete: the rule, on this iterate's scalars
             stop_status = stop_rule(mu, nu, rr, stop_thr);
             if (stop_status) { stop_k = a.k0 + it; break; }
@@ -269,9 +348,12 @@ __device__ __forceinline__ void small_pipe_pr_body(const SmallArgs& a, const Sma
 // registers;]  nu' = r.r~ [and rr = r.r, the same sum without the scaling];  b = nu' / nu;  p = r~ + b p;  s = A p;  mu = p.s  --
 // two reduction points (the two reductions that make Hestenes-Stiefel what it is), four barriers; red is [16 waves][1 or 2].
 // Scalars as the launches leave them: dots[k] = {mu_k, -, -, nu_k, rr_k}, coef[k] = {a_k, b_k}.
-template <int MODE, bool JAC, bool STOP>
-__device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallJacobi& jc, const SmallStop& stop) {
+// PREC == kSmallPrecBlocks: r~ = M^-1 r by blocks (bk).  The new r of every row goes to `nxt` -- free until the new direction
+// is stored there, behind the barrier of nu' --, one barrier, then each row forms r~ from its block's entries: five barriers.
+template <int MODE, int PREC, bool STOP>
+__device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallJacobi& jc, const SmallBlocks& bk, const SmallStop& stop) {
     if constexpr (STOP) { if (small_stop_entry(a, stop)) return; }
+    constexpr bool JAC = PREC != kSmallPrecNone, BLK = PREC == kSmallPrecBlocks;
     constexpr int ROWS = kSmallRowsOf<MODE>, K = JAC ? 2 : 1;
     const int n = a.n, tid = threadIdx.x;
     const SmallLds<double> l = small_carve<MODE, double, K>(n, a.nnz);
@@ -282,12 +364,14 @@ __device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallJac
         xr[j] = 0.0; rr_[j] = 0.0; pr[j] = 0.0; sr[j] = 0.0; dr[j] = 0.0;
         if (row < n) {
             xr[j] = a.xp[row]; rr_[j] = a.rs[row]; pr[j] = a.hs_p[row]; sr[j] = a.hs_s[row];
-            if constexpr (JAC) dr[j] = jc.d[row];
+            if constexpr (PREC == kSmallPrecJacobi) dr[j] = jc.d[row];
             l.cur[row] = pr[j];
         }
     }
     SmallMatrix<MODE> m;
     small_stage<MODE>(m, a, l.lval, l.lcol);
+    SmallBlockRows<MODE> kb;
+    if constexpr (BLK) small_block_stage<MODE>(kb, bk, n);
     double mu = a.dots[(size_t)a.k0 * kPartialStride + 0], nu = a.dots[(size_t)a.k0 * kPartialStride + 3];
     __syncthreads();
 
@@ -305,10 +389,25 @@ __device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallJac
             if (tid + j * kSmallThreads < n) {
                 xr[j] = xr[j] + al * pr[j];                      // x += a p
                 rr_[j] = rr_[j] - al * sr[j];                    // r -= a s
-                rt[j] = rr_[j];
-                if constexpr (JAC) rt[j] = dr[j] * rr_[j];       // r~ = M^-1 r                        :118
-                acc[0] += rr_[j] * rt[j];
-                if constexpr (JAC) acc[1] += rr_[j] * rr_[j];
+                if constexpr (BLK) {
+                    nxt[tid + j * kSmallThreads] = rr_[j];       // ... to its block's rows
+                } else {
+                    rt[j] = rr_[j];
+                    if constexpr (JAC) rt[j] = dr[j] * rr_[j];   // r~ = M^-1 r                        :118
+                    acc[0] += rr_[j] * rt[j];
+                    if constexpr (JAC) acc[1] += rr_[j] * rr_[j];
+                }
+            }
+        }
+        if constexpr (BLK) {
+            lds_barrier();                                       // r complete
+#pragma unroll
+            for (int j = 0; j < ROWS; ++j) {
+                if (tid + j * kSmallThreads < n) {
+                    rt[j] = small_block_apply<MODE>(kb, j, nxt); // r~ = M^-1 r
+                    acc[0] += rr_[j] * rt[j];
+                    acc[1] += rr_[j] * rr_[j];
+                }
             }
         }
         small_red_put<K>(l.red, acc);
@@ -358,12 +457,12 @@ __device__ __forceinline__ void small_hs_body(const SmallArgs& a, const SmallJac
 
 // ---- the single sessions: one workgroup, the launch's SmallArgs ----
 template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { small_pipe_pr_body<MODE, false, false>(a, SmallJacobi{}, SmallStop{}); }
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr(SmallArgs a) { small_pipe_pr_body<MODE, kSmallPrecNone, false>(a, SmallJacobi{}, SmallBlocks{}, SmallStop{}); }
 template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small_hs_body<MODE, false, false>(a, SmallJacobi{}, SmallStop{}); }
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small_hs_body<MODE, kSmallPrecNone, false>(a, SmallJacobi{}, SmallBlocks{}, SmallStop{}); }
 // ... stopped at a residual threshold (prcg_set_stop): the STOP form of the body on the session's own word
 template <int MODE>
-__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_stop(SmallArgs a, SmallStop stop) { small_pipe_pr_body<MODE, false, true>(a, SmallJacobi{}, stop); }
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_stop(SmallArgs a, SmallStop stop) { small_pipe_pr_body<MODE, kSmallPrecNone, true>(a, SmallJacobi{}, SmallBlocks{}, stop); }
 
 // ---- a BATCH of small systems: one launch, workgroup blockIdx.x solves system desc[blockIdx.x] (prcg_batch.cpp) ----
 // The descriptors live in device memory, one SmallArgs per system with pointers into the batch's concatenated matrix, state,
@@ -382,12 +481,24 @@ __device__ __forceinline__ SmallSystem small_system(const SmallBatchArgs& g) {
 template <int MODE, bool JAC, bool STOP>
 __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_batch(SmallBatchArgs g) {
     const SmallSystem s = small_system<JAC, STOP>(g);
-    small_pipe_pr_body<MODE, JAC, STOP>(s.a, s.jac, s.stop);
+    small_pipe_pr_body<MODE, JAC ? kSmallPrecJacobi : kSmallPrecNone, STOP>(s.a, s.jac, SmallBlocks{}, s.stop);
 }
 template <int MODE, bool JAC, bool STOP>
 __global__ __launch_bounds__(kSmallThreads) void k_small_hs_batch(SmallBatchArgs g) {
     const SmallSystem s = small_system<JAC, STOP>(g);
-    small_hs_body<MODE, JAC, STOP>(s.a, s.jac, s.stop);
+    small_hs_body<MODE, JAC ? kSmallPrecJacobi : kSmallPrecNone, STOP>(s.a, s.jac, SmallBlocks{}, s.stop);
+}
+// ... preconditioned by point-block Jacobi: blk[blockIdx.x] belongs to desc[blockIdx.x] (g.jac is not read)
+template <int MODE, bool STOP>
+__global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_blocks(SmallBatchArgs g, const SmallBlocks* __restrict__ blk) {
+    const SmallSystem s = small_system<false, STOP>(g);
+    const SmallBlocks bk = blk[blockIdx.x];
+    small_pipe_pr_body<MODE, kSmallPrecBlocks, STOP>(s.a, SmallJacobi{bk.ts, nullptr}, bk, s.stop);
+}
+template <int MODE, bool STOP>
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs_blocks(SmallBatchArgs g, const SmallBlocks* __restrict__ blk) {
+    const SmallSystem s = small_system<false, STOP>(g);
+    small_hs_body<MODE, kSmallPrecBlocks, STOP>(s.a, SmallJacobi{}, blk[blockIdx.x], s.stop);
 }
 
 // Initial state of every system of a batch in ONE launch (pipe_pr_cg.py:22-28, :122-140; hs_cg.py:22-27, :84-90), workgroup
@@ -397,17 +508,22 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_hs_batch(SmallBatchArgs
 // without the scaling r~ IS r, s~ IS s), summed in the order of the LOOP: thread-sequential over rows tid, tid + 1024, ..., wave
 // butterfly, 16 waves.  (The single session sums its initial products in the order of its start-up launches: row 0 may differ
 // from it in the last bit.)  The matrix is read from memory: once.
-template <bool HS, bool JAC>
+// PREC == kSmallPrecBlocks: r~ = M^-1 r and s~ = M^-1 s by blocks (blk[blockIdx.x]; small_block_apply, the blocks' rows read from
+// memory).  The rows of a block exchange r, then s, through pl, each time between two barriers.
+template <bool HS, int PREC>
 __global__ __launch_bounds__(kSmallThreads) void k_small_batch_init(const SmallArgs* __restrict__ desc, const SmallInit* __restrict__ init,
-                                                                    const SmallJacobi* __restrict__ jac) {
+                                                                    const SmallJacobi* __restrict__ jac, const SmallBlocks* __restrict__ blk) {
+    constexpr bool JAC = PREC != kSmallPrecNone, BLK = PREC == kSmallPrecBlocks;
     constexpr int K = JAC ? 5 : 4;
     __shared__ double pl[kSmallMaxN];                            // p (= r~): the source of s = A p
     __shared__ double red[16 * K];
     const SmallArgs a = desc[blockIdx.x];
     const SmallInit in = init[blockIdx.x];
     SmallJacobi jc{};
-    if constexpr (JAC) jc = jac[blockIdx.x];
+    if constexpr (PREC == kSmallPrecJacobi) jc = jac[blockIdx.x];
     const int n = a.n, tid = threadIdx.x;
+    SmallBlockRows<0> kb;
+    if constexpr (BLK) { const SmallBlocks bk = blk[blockIdx.x]; jc.ts = bk.ts; small_block_stage<0>(kb, bk, n); }
     double xr[kSmallRows], rr_[kSmallRows], rt[kSmallRows];
 #pragma unroll
     for (int j = 0; j < kSmallRows; ++j) {
@@ -419,24 +535,52 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_batch_init(const SmallA
             xr[j] = in.x0[row];                                  // x = x0
             rr_[j] = in.b[row] - t;                              // r = b - A x
             rt[j] = rr_[j];
-            if constexpr (JAC) rt[j] = jc.d[row] * rr_[j];       // r~ = M^-1 r
+            if constexpr (PREC == kSmallPrecJacobi) rt[j] = jc.d[row] * rr_[j];       // r~ = M^-1 r
             pl[row] = rt[j];
         }
     }
     __syncthreads();
+    if constexpr (BLK) {                                         // pl holds r: r~ = M^-1 r, then pl holds p = r~
+#pragma unroll
+        for (int j = 0; j < kSmallRows; ++j)
+            if (tid + j * kSmallThreads < n) rt[j] = small_block_apply<0>(kb, j, pl);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kSmallRows; ++j)
+            if (tid + j * kSmallThreads < n) pl[tid + j * kSmallThreads] = rt[j];
+        __syncthreads();
+    }
+    double spv[BLK ? kSmallRows : 1];
+    if constexpr (BLK && !HS) {                                  // s = A p of every row, exchanged through pl for s~ = M^-1 s
+#pragma unroll
+        for (int j = 0; j < kSmallRows; ++j) {
+            const int row = tid + j * kSmallThreads;
+            spv[j] = 0.0;
+            if (row < n)
+                for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) spv[j] += a.val[q] * pl[a.col[q]];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kSmallRows; ++j)
+            if (tid + j * kSmallThreads < n) pl[tid + j * kSmallThreads] = spv[j];
+        __syncthreads();
+    }
     double acc[K] = {};
 #pragma unroll
     for (int j = 0; j < kSmallRows; ++j) {
         const int row = tid + j * kSmallThreads;
         if (row < n) {
             double sp = 0.0;                                     // (A p)_i, p = r~, left to right
-            for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) sp += a.val[q] * pl[a.col[q]];
+            if constexpr (BLK && !HS) sp = spv[j];
+            else
+                for (int q = a.indptr[row]; q < a.indptr[row + 1]; ++q) sp += a.val[q] * pl[a.col[q]];
             const double rn = rr_[j], pn = rt[j];
             if constexpr (HS) {
                 a.xp[row] = xr[j]; a.rs[row] = rn; a.hs_p[row] = pn; a.hs_s[row] = sp;
             } else {
                 double stn = sp;
-                if constexpr (JAC) stn = jc.d[row] * sp;         // s~ = M^-1 s
+                if constexpr (PREC == kSmallPrecJacobi) stn = jc.d[row] * sp;         // s~ = M^-1 s
+                if constexpr (BLK) stn = small_block_apply<0>(kb, j, pl);
                 reinterpret_cast<double2*>(a.xp)[row] = make_double2(xr[j], pn);
                 reinterpret_cast<double2*>(a.rs)[row] = make_double2(rn, sp);
                 if constexpr (JAC) reinterpret_cast<double2*>(jc.ts)[row] = make_double2(pn, stn);
@@ -461,17 +605,17 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_batch_init(const SmallA
 }  // namespace
 
 // ---- host side: the fit rules ----
-size_t small_lds_bytes(int n, int nnz, int mode, bool jacobi) {
-    return (size_t)2 * n * 16 + (jacobi ? 80 : 64) * 8 + (mode == 0 ? (size_t)nnz * 12 + 16 : 0);
+size_t small_lds_bytes(int n, int nnz, int mode, int prec) {
+    return (size_t)2 * n * 16 + (prec ? 80 : 64) * 8 + (mode == 0 ? (size_t)nnz * 12 + 16 : 0);
 }
 // mode 1 (matrix in registers) if n <= 1024 and the longest row has <= 8 nonzeros; mode 0
 // (matrix in LDS) if it fits beside the vectors; otherwise the multi-launch schedule is
 // faster (measured: bcsstk14, 63 k nonzeros re-read through L2 by one CU: 58 us/iteration).
 constexpr size_t kSmallLdsCap = 156 * 1024;
-bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, bool jacobi) {
+bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, int prec) {
     if (n < 1 || n > kSmallMaxN) return false;
     if (n <= kSmallThreads && max_row_len <= kSmallRegLen) { *mode = 1; return true; }
-    if (nnz < (1 << 20) && small_lds_bytes((int)n, (int)nnz, 0, jacobi) <= kSmallLdsCap && max_row_len <= 64) { *mode = 0; return true; }
+    if (nnz < (1 << 20) && small_lds_bytes((int)n, (int)nnz, 0, prec) <= kSmallLdsCap && max_row_len <= 64) { *mode = 0; return true; }
     return false;
 }
 
@@ -487,6 +631,11 @@ const SmallBatchFn kSmallBatchFn[2][2][2][2] = {
       {k_small_pipe_pr_batch<1, true, false>, k_small_pipe_pr_batch<1, true, true>}}},
     {{{k_small_hs_batch<0, false, false>, k_small_hs_batch<0, false, true>}, {k_small_hs_batch<0, true, false>, k_small_hs_batch<0, true, true>}},
      {{k_small_hs_batch<1, false, false>, k_small_hs_batch<1, false, true>}, {k_small_hs_batch<1, true, false>, k_small_hs_batch<1, true, true>}}}};
+using SmallBlocksFn = void (*)(SmallBatchArgs, const SmallBlocks*);
+// [hs][mode][stop]
+const SmallBlocksFn kSmallBlocksFn[2][2][2] = {
+    {{k_small_pipe_pr_blocks<0, false>, k_small_pipe_pr_blocks<0, true>}, {k_small_pipe_pr_blocks<1, false>, k_small_pipe_pr_blocks<1, true>}},
+    {{k_small_hs_blocks<0, false>, k_small_hs_blocks<0, true>}, {k_small_hs_blocks<1, false>, k_small_hs_blocks<1, true>}}};
 const SmallSingleFn kSmallSingleFn[2][2] = {{k_small_pipe_pr<0>, k_small_pipe_pr<1>}, {k_small_hs<0>, k_small_hs<1>}};      // [hs][mode]
 using SmallSingleStopFn = void (*)(SmallArgs, SmallStop);
 const SmallSingleStopFn kSmallSingleStopFn[2] = {k_small_pipe_pr_stop<0>, k_small_pipe_pr_stop<1>};                         // [mode]
@@ -502,6 +651,8 @@ bool small_lds_attribute() {
     const auto set = [](const void* f) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
     for (int i = 0; i < 16; ++i)
         if (!set(reinterpret_cast<const void*>((&kSmallBatchFn[0][0][0][0])[i]))) return false;
+    for (int i = 0; i < 8; ++i)
+        if (!set(reinterpret_cast<const void*>((&kSmallBlocksFn[0][0][0])[i]))) return false;
     for (int i = 0; i < 4; ++i)
         if (!set(reinterpret_cast<const void*>((&kSmallSingleFn[0][0])[i]))) return false;
     for (int i = 0; i < 2; ++i)
@@ -526,15 +677,19 @@ int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const Sma
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode) { return launch_small_single(st, a, mode, true); }
 
 // ---- batch of small systems: `count` workgroups, one per descriptor (all of one mode; lds: the largest small_lds_bytes among them)
-int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs) {
-    auto k = hs ? (jac ? k_small_batch_init<true, true> : k_small_batch_init<true, false>)
-                : (jac ? k_small_batch_init<false, true> : k_small_batch_init<false, false>);
-    hipLaunchKernelGGL(k, dim3(count), dim3(kSmallThreads), 0, st, desc, init, jac);
+int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs,
+                            const SmallBlocks* blk) {
+    const int prec = blk ? kSmallPrecBlocks : jac ? kSmallPrecJacobi : kSmallPrecNone;
+    decltype(&k_small_batch_init<false, 0>) const fn[2][3] = {
+        {k_small_batch_init<false, kSmallPrecNone>, k_small_batch_init<false, kSmallPrecJacobi>, k_small_batch_init<false, kSmallPrecBlocks>},
+        {k_small_batch_init<true, kSmallPrecNone>, k_small_batch_init<true, kSmallPrecJacobi>, k_small_batch_init<true, kSmallPrecBlocks>}};
+    hipLaunchKernelGGL(fn[hs][prec], dim3(count), dim3(kSmallThreads), 0, st, desc, init, jac, blk);
     return hipGetLastError() == hipSuccess ? count : -1;
 }
-int launch_small_batch(hipStream_t st, const SmallBatchArgs& g, int count, int mode, size_t lds, bool hs) {
+int launch_small_batch(hipStream_t st, const SmallBatchArgs& g, int count, int mode, size_t lds, bool hs, const SmallBlocks* blk) {
     if (!small_lds_attribute()) return -1;
-    hipLaunchKernelGGL(kSmallBatchFn[hs][mode == 1][g.jac != nullptr][g.stop != nullptr], dim3(count), dim3(kSmallThreads), lds, st, g);
+    if (blk) hipLaunchKernelGGL(kSmallBlocksFn[hs][mode == 1][g.stop != nullptr], dim3(count), dim3(kSmallThreads), lds, st, g, blk);
+    else hipLaunchKernelGGL(kSmallBatchFn[hs][mode == 1][g.jac != nullptr][g.stop != nullptr], dim3(count), dim3(kSmallThreads), lds, st, g);
     return hipGetLastError() == hipSuccess ? count : -1;
 }
 

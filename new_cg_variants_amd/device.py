@@ -645,6 +645,34 @@ def batch_vectors(name, V, sizes):
     return out
 
 
+def batch_blocks(name, blocks, sizes):
+    """(nblk_off, block_ptr, inv_blocks) as prcg_batch_begin_block_jacobi takes them (prcg.h) from one (block_ptr, inv_blocks)
+    per system: block_ptr the system's partition (nb + 1 entries, zero-based, from 0 to n_s), inv_blocks its packed inverses
+    (block k as m_k x m_k row-major; any shape with sum of m_k^2 entries).  Pure host work; ValueError names the system and what
+    is wrong with its shapes -- the partition's values are the library's to refuse."""
+    blocks = list(blocks)
+    if len(blocks) != len(sizes):
+        raise ValueError(f'{name} must hold {len(sizes)} pairs (block_ptr, inv_blocks), one per system -- got {len(blocks)}')
+    ptrs, invs = [], []
+    for s, pair in enumerate(blocks):
+        try:
+            ptr, inv = pair
+        except (TypeError, ValueError):
+            raise ValueError(f'{name}[{s}] must be a pair (block_ptr, inv_blocks)') from None
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+        inv = np.ascontiguousarray(inv, dtype=np.float64).reshape(-1)
+        if ptr.ndim != 1 or ptr.size < 1:
+            raise ValueError(f'{name}[{s}]: block_ptr must be a one-dimensional array of nb + 1 entries, got shape {ptr.shape}')
+        need = int(np.sum(np.diff(ptr) ** 2))
+        if inv.size != need:
+            raise ValueError(f'{name}[{s}]: inv_blocks holds {inv.size} entries, the partition\'s blocks have {need} (packed: block k is '
+                             'm_k x m_k, no padding)')
+        ptrs.append(ptr)
+        invs.append(inv)
+    nblk_off = np.concatenate([[0], np.cumsum([p.size - 1 for p in ptrs])]).astype(np.int64)
+    return nblk_off, np.concatenate(ptrs), np.concatenate(invs) if invs else np.empty(0)
+
+
 def batch_thresholds(name, v, n_sys):
     """One finite value >= 0 per system (1-D float64) from a scalar -- every system's -- or a sequence of n_sys; ValueError names
     the count or the first system whose value is NaN, infinite or negative.  Pure host work."""
@@ -728,18 +756,27 @@ class DeviceBatch:
         except Exception:
             pass
 
-    def begin(self, variant, B, X0, max_iter, hist_mask=0, inv_diag=None, rr_stop=None):
+    def begin(self, variant, B, X0, max_iter, hist_mask=0, inv_diag=None, rr_stop=None, block_jacobi=None):
         """variant: L.PIPE_PR, L.PIPE_PR_M or L.HS.  B, X0: a list of vectors, one per system, or one 2-D array (n_sys, n) when
         all sizes agree.  hist_mask: 0 or L.HIST_UPDATED_RESIDUAL_2_NORM.  inv_diag: None, or -- in the form of B -- every
         system's reciprocal diagonal: the session is then preconditioned by that scaling inside the one-workgroup solver
         (prcg.h: prcg_batch_begin_jacobi), and a pipelined one also serves get_vector('rt' / 'st', s).  rr_stop: None, or a
         threshold on r.r -- one per system, or a scalar for all --: every system of THIS session then stops by itself, converged
-        or broken down, by the rule of prcg.h: prcg_batch_set_stop; stops() tells where and why."""
+        or broken down, by the rule of prcg.h: prcg_batch_set_stop; stops() tells where and why.  block_jacobi: None, or one
+        pair (block_ptr, inv_blocks) per system -- its partition (every size in 1..8) and the packed inverses of its diagonal
+        blocks, what VarBlockJacobi carries --: the session is preconditioned by point-block Jacobi inside the one-workgroup
+        solver (prcg.h: prcg_batch_begin_block_jacobi); state and accessors as with inv_diag, with which it cannot be combined."""
+        if inv_diag is not None and block_jacobi is not None:
+            raise ValueError('inv_diag and block_jacobi are mutually exclusive: a session has one preconditioner')
         b, x0 = batch_vectors('B', B, self.sizes), batch_vectors('X0', X0, self.sizes)
+        blocks = None if block_jacobi is None else batch_blocks('block_jacobi', block_jacobi, self.sizes)
         d = None if inv_diag is None else batch_vectors('inv_diag', inv_diag, self.sizes)
         thr = None if rr_stop is None else batch_thresholds('rr_stop', rr_stop, self.n_sys)
         self._check(self._lib.prcg_batch_set_stop(self._b, L.ptr(thr)))      # (None clears what an earlier session set)
-        if inv_diag is None:
+        if blocks is not None:
+            self._check(self._lib.prcg_batch_begin_block_jacobi(self._b, int(variant), L.ptr(b), L.ptr(x0), L.ptr(blocks[0]), L.ptr(blocks[1]),
+                                                                L.ptr(blocks[2]), int(max_iter), int(hist_mask)))
+        elif inv_diag is None:
             self._check(self._lib.prcg_batch_begin(self._b, int(variant), L.ptr(b), L.ptr(x0), int(max_iter), int(hist_mask)))
         else:
             self._check(self._lib.prcg_batch_begin_jacobi(self._b, int(variant), L.ptr(b), L.ptr(x0), L.ptr(d), int(max_iter), int(hist_mask)))
