@@ -158,9 +158,13 @@ int prcg_plan_gather(int rank, int doubles_per_table, const double* tables, int 
                      const int32_t* peer_rank, const int64_t* recv_ptr, int64_t slot_doubles,
                      int32_t* ghost_src);
 /* Diagnostic (tests): how the resident operator is laid out for the window-tile launches, i.e. everything the summation
- * order of their inner products depends on.  out[0..8) = {1 if window operator, window geometry id, rows per window tile,
+ * order of their inner products depends on.  out[0..10) = {1 if window operator, window geometry id, rows per window tile,
  * number of tiles T, out[4], out[5], interior tiles, (waves a sweep table assumes) << 8 -- bit 0 is always 0 (it marked the
- * retired XCD-chunked tile order)}, then T pairs (first row, end row) in table order.
+ * retired XCD-chunked tile order), out[8], out[9]}, then T pairs (first row, end row) in table order (interior tiles first).
+ * out[8], out[9]: with a communicator the two-kernel schedules run a product with a dot epilogue as TWO launches, the interior
+ * tiles [0, out[6]) and then the tiles that read ghost rows [out[6], T), whose partial rows lie end to end (interior first) under
+ * one final tree.  After such a product out[4], out[5] describe the boundary launch and out[8], out[9] are the workgroups and
+ * waves per workgroup of the interior launch; 0, 0 whenever the last launch that left partials ran over all its tiles.
  * out[4], out[5]: workgroups and waves per workgroup of the open session's LAST launch that left inner-product partials,
  * as that launch ran: the one-launch pipelined, predict-and-recompute, Chronopoulos-Gear and Ghysels-Vanroose iterations,
  * the product launches of their two-launch forms and of Hestenes-Stiefel, and a product with a dot epilogue (the start-up

@@ -101,6 +101,7 @@ void note_partials_launch(prcg_t* h, int grid) {
     if (grid <= 0) return;
     const WinLaunchShape s = h->win ? win_last_launch() : WinLaunchShape{grid, 0};
     h->last_grid = s.grid; h->last_wpb = s.wpb;
+    h->int_grid = 0; h->int_wpb = 0;         // (one launch over its tiles, until overlapped_spmv says otherwise)
 }
 int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, SpmvEpilogue epi, const double* ep_r,
              const double* ep_d, double* ep_st, double* partials) {
@@ -1507,7 +1508,7 @@ int prcg_plan_gather(int rank, int doubles_per_table, const double* tables, int 
 int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity) {
     if (!h || !h->have_csr || !out) return -1;
     const int64_t nt = h->win ? (int64_t)h->nwt_int + h->nwt_bnd : (int64_t)h->nt_int + h->nt_bnd;
-    const int64_t need = 8 + 2 * nt;
+    const int64_t need = 10 + 2 * nt;
     if (capacity < need) return -need;
     out[0] = h->win ? 1 : 0;
     out[1] = h->win ? h->win_geom : -1;
@@ -1520,15 +1521,18 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity) {
                             : win_fused_waves_per_block(h->win_geom, h->win_vd, h->fused_comm, h->nwt_int + h->nwt_bnd, h->opt.want_big, h->sweep_waves));
     out[6] = h->win ? h->nwt_int : h->nt_int;
     out[7] = h->win ? (int64_t)h->sweep_waves << 8 : 0;    // bit 0: always 0 (was the retired XCD-chunked tile order); >> 8: waves of a sweep table
-    std::vector<int32_t> rows((size_t)nt * 2);
+    // a product with a dot epilogue in TWO launches (a communicator session's overlapped product): out[4], out[5] are the boundary
+    // launch's, these the interior launch's, whose partial rows lie first -- 0, 0: the last launch ran over all the tiles
+    out[8] = h->int_grid;
+    out[9] = h->int_wpb;
     if (h->win) {
         std::vector<WTile> t((size_t)nt);
         if (nt && hipMemcpy(t.data(), h->wtiles.p, (size_t)nt * sizeof(WTile), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        for (int64_t i = 0; i < nt; ++i) { out[8 + 2 * i] = t[(size_t)i].rb; out[9 + 2 * i] = t[(size_t)i].re; }
+        for (int64_t i = 0; i < nt; ++i) { out[10 + 2 * i] = t[(size_t)i].rb; out[11 + 2 * i] = t[(size_t)i].re; }
     } else {
         std::vector<Tile> t((size_t)nt);
         if (nt && hipMemcpy(t.data(), h->tiles.p, (size_t)nt * sizeof(Tile), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        for (int64_t i = 0; i < nt; ++i) { out[8 + 2 * i] = t[(size_t)i].row_begin; out[9 + 2 * i] = t[(size_t)i].row_end; }
+        for (int64_t i = 0; i < nt; ++i) { out[10 + 2 * i] = t[(size_t)i].row_begin; out[11 + 2 * i] = t[(size_t)i].row_end; }
     }
     return need;
 }

@@ -181,6 +181,8 @@ struct Session {
     double* pend_buf = nullptr;
     int last_grid = 0;           // workgroups of the session's last launch that left inner-product partials (prcg_debug_layout) ...
     int last_wpb = 0;            // ... and its waves per workgroup (window operators: what launch_win_v instantiated; else 0)
+    int int_grid = 0;            // that launch was the BOUNDARY half of a product in two launches (overlapped_spmv with a communicator):
+    int int_wpb = 0;             // ... workgroups and waves per workgroup of the interior half, whose partial rows come first (else 0)
     // ---- stopped at a residual threshold, decided on the device (prcg_set_stop; pipelined single sessions) ----
     bool stop = false;           // the session was begun with a threshold ...
     double thr = 0.0;            // ... on r.r

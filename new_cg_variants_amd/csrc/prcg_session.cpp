@@ -122,9 +122,12 @@ int overlapped_spmv(prcg_t* h, int k, double* x_ext, double* y, SpmvEpilogue epi
     const int g1 = eng_spmv(h, h->sc, 1, x_ext, y, epi, ep_r, ep_d, ep_st, h->partB.d());
     LAUNCHCHK(h, g1);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+    // (the interior launch's shape, for prcg_debug_layout: the boundary launch's replaces it as "the last launch")
+    const int int_grid = epi != kEpiNone ? h->last_grid : 0, int_wpb = epi != kEpiNone ? h->last_wpb : 0;
     HIPCHK(h, hipStreamWaitEvent(h->sc, h->e_halo, 0));
     const int g2 = eng_spmv(h, h->sc, 2, x_ext, y, epi, ep_r, ep_d, ep_st, h->partB.d() + (size_t)g1 * kPartialStride);
     LAUNCHCHK(h, g2);
+    if (g1 > 0 && g2 > 0) { h->int_grid = int_grid; h->int_wpb = int_wpb; }
     *nparts = g1 + g2;
     return PRCG_OK;
 }
@@ -776,9 +779,9 @@ int record(prcg_t* h, int k) {
         launch_sub(h->sc, h->e_ext.d(), 1, x_ptr(h), x_stride(h), h->xt.d(), 1, n);
         int grid = 0;
         // (a recorder's product, no inner product of the method: prcg_debug_layout keeps the iteration's launch)
-        const int it_grid = h->last_grid, it_wpb = h->last_wpb;
+        const int it_grid = h->last_grid, it_wpb = h->last_wpb, it_int_grid = h->int_grid, it_int_wpb = h->int_wpb;
         if ((rc = dist_spmv(h, h->e_ext.d(), h->t1.d(), kEpiDotXY, nullptr, nullptr, nullptr, &grid))) return rc;
-        h->last_grid = it_grid; h->last_wpb = it_wpb;
+        h->last_grid = it_grid; h->last_wpb = it_wpb; h->int_grid = it_int_grid; h->int_wpb = it_int_wpb;
         launch_reduce_final(h->sc, h->partB.d(), grid, dots_at(h, k), 0, PRCG_S_ERRA2, 1);
     }
     return allreduce(h, dots_at(h, k) + PRCG_S_RES2, 3, h->sc);

@@ -485,13 +485,16 @@ class DeviceCSR:
         """Diagnostic (prcg_test.h: prcg_debug_layout): what the summation order of a tile launch's inner products depends
         on -- tile rows in table order, and 'grid' / 'waves_per_block' of the session's LAST launch that left inner-product
         partials (any schedule's iteration launch, or the start-up products right after begin(); never a recorder's;
-        grid 0: none yet).  Every session leaves the partials of an iteration from ONE tile launch, so one pair suffices.
+        grid 0: none yet).  A session without a communicator leaves the partials of an iteration from ONE tile launch; with one,
+        the two-kernel schedules run a product with a dot epilogue as two launches -- 'grid' / 'waves_per_block' are then the
+        boundary launch's (tiles[interior_tiles:]) and 'interior_grid' / 'interior_waves_per_block' the interior launch's
+        (tiles[:interior_tiles], its partial rows first); both 0 when the last such launch ran over all the tiles.
         'sliced': the operator runs on sliced rows; 'slice_rows' (prcg_debug_slice_rows): then the row of every lane of
         every slice in launch order, shape (slices, 64), -1 for an idle lane -- else shape (0, 64)."""
         need = -int(self._lib.prcg_debug_layout(self._h, L.ptr(np.zeros(1, dtype=np.int64)), 0))
-        out = np.zeros(max(need, 8), dtype=np.int64)
+        out = np.zeros(max(need, 10), dtype=np.int64)
         got = int(self._lib.prcg_debug_layout(self._h, L.ptr(out), out.size))
-        if got < 8:
+        if got < 10:
             raise RuntimeError('prcg_debug_layout failed')
         need = -int(self._lib.prcg_debug_slice_rows(self._h, None, 0))
         if need < 0 or need % 64:                      # (-1: an error; -needed is a multiple of 64)
@@ -499,8 +502,9 @@ class DeviceCSR:
         rows = np.zeros(need, dtype=np.int32)
         if need and int(self._lib.prcg_debug_slice_rows(self._h, L.ptr(rows), rows.size)) != need:
             raise RuntimeError('prcg_debug_slice_rows failed')
-        return {'window': bool(out[0]), 'geometry': int(out[1]), 'rows_per_tile': int(out[2]), 'tiles': out[8:got].reshape(-1, 2).copy(),
+        return {'window': bool(out[0]), 'geometry': int(out[1]), 'rows_per_tile': int(out[2]), 'tiles': out[10:got].reshape(-1, 2).copy(),
                 'grid': int(out[4]), 'waves_per_block': int(out[5]), 'interior_tiles': int(out[6]), 'sweep_waves': int(out[7]) >> 8,
+                'interior_grid': int(out[8]), 'interior_waves_per_block': int(out[9]),
                 'sliced': need > 0, 'slice_rows': rows.reshape(-1, 64)}
 
     def operator_bytes(self):

@@ -39,6 +39,12 @@ ceil(rows / 64) rows per lane) come from DeviceCSR.layout()'s 'slice_rows' (prcg
 CSR-adaptive tiles that is longer than a tile is summed by its whole wave: ``LongRowOperator`` is the matrix with those rows
 multiplied that way.
 
+SEVERAL RANKS (tests/test_trajectory_ranks.py): every rank sums ITS rows with its own tree and the ranks' values are added in rank
+order, v = s[0]; v += s[r] -- ``RankSum``.  A rank's tree is one of the above built from that rank's layout(), or ``PeerLaunchTree``
+(the one-launch iteration over the direct peer exchange: one wave is the communication wave, the others' tiles shift by one slot, a
+few boundary tiles go to the communication wave) or ``TwoLaunchTree`` (a product with a dot epilogue run as an interior and a
+boundary launch whose partial rows lie end to end under one final tree).
+
 ``Routed`` lets a schedule whose inner products come from different launches (Hestenes-Stiefel: nu from the update
 kernel, mu from the tile launch) plug into the oracle: the oracle calls ``dot`` in a fixed order per advance.
 """
@@ -216,6 +222,135 @@ class OneLaunchTree:
 
     def dot(self, a, b):
         return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
+RELAY_TILES = 8          # prcg_win.hip: kRelayTiles -- boundary tiles the communication wave of the peer exchange takes itself
+
+
+class _TileWaves:
+    """One launch of k_win_tiles with any assignment of tiles to waves: ``assign(b, v)`` -> the tiles (indices into `tiles`) wave
+    v of workgroup b takes, in order.  lane l adds rows rb + j*64 + l (j = 0..M-1) of each, from +0.0; butterfly; waves 0..wpb-1
+    in order -> ``partials(prod)``: one value per workgroup, in workgroup order (the rows of the launch's partials buffer)."""
+
+    def __init__(self, tiles, M, grid, wpb, assign):
+        grid, wpb = int(grid), int(wpb)
+        assert grid > 0 and wpb > 0, (grid, wpb)
+        mine = [[list(assign(b, v)) for v in range(wpb)] for b in range(grid)]
+        steps = max(1, max(len(m) for row in mine for m in row)) * M
+        # idx[b, v, step, lane] = row summed by that lane at that step, -1: none
+        idx = -np.ones((grid, wpb, steps, 64), dtype=np.int64)
+        lane = np.arange(64)
+        for b in range(grid):
+            for v in range(wpb):
+                for i, t in enumerate(mine[b][v]):
+                    rb, re = tiles[t]
+                    for j in range(M):
+                        rows = rb + j * 64 + lane
+                        idx[b, v, i * M + j] = np.where(rows < re, rows, -1)
+        self.idx, self.grid, self.wpb = idx, grid, wpb
+
+    def partials(self, prod):
+        ext = np.concatenate([np.asarray(prod, dtype=np.float64), [0.0]])     # index -1 -> +0.0 (acc starts at +0.0)
+        acc = np.zeros(self.idx.shape[:2] + (64,))
+        for step in range(self.idx.shape[2]):
+            acc = acc + ext[self.idx[:, :, step, :]]
+        waves = _butterfly(acc)                        # (grid, wpb)
+        partial = waves[:, 0]
+        for v in range(1, self.wpb):
+            partial = partial + waves[:, v]
+        return partial
+
+
+def _assert_every_row_once(tiles, *launches):
+    covered = np.sort(np.concatenate([l.idx[l.idx >= 0] for l in launches]))
+    assert np.array_equal(covered, np.arange(tiles[:, 0].min(), tiles[:, 1].max())), 'every row summed exactly once'
+
+
+class PeerLaunchTree:
+    """OneLaunchTree's sibling for the one-launch iteration over the DIRECT PEER EXCHANGE (prcg_win.hip: k_win_tiles<.., DEF> with
+    fz.px set): wave slot s = xcd_remap(b) * WPB + v; slot 0 is the launch's communication wave; every other wave takes tiles
+    s - 1, s - 1 + (W - 1), ... below tend with W = grid * WPB.  A rank with 1..RELAY_TILES boundary tiles (the tiles behind
+    layout()['interior_tiles']): tend = the interior tiles, and the communication wave takes the boundary tiles one after
+    another; else tend = all tiles and the communication wave adds nothing.  Workgroup partials under the 256-thread tree
+    (sum_prev_partials<5, WPB> of workgroup 0 of the next launch, or k_peer_collect): ``sum`` is ONE RANK's slot."""
+
+    def __init__(self, layout):
+        assert layout['window'] and layout['grid'] > 0, layout
+        tiles = np.asarray(layout['tiles'], dtype=np.int64)
+        grid, wpb = int(layout['grid']), int(layout['waves_per_block'])
+        nt, nt_int = tiles.shape[0], int(layout['interior_tiles'])
+        assert 0 <= nt_int <= nt, (nt_int, nt)
+        W = grid * wpb
+        self.relayed = 0 < nt - nt_int <= RELAY_TILES
+        tend = nt_int if self.relayed else nt
+
+        def assign(b, v):
+            s = xcd_remap(b, grid) * wpb + v
+            if s == 0:
+                return range(nt_int, nt) if self.relayed else range(0)
+            return range(s - 1, tend, W - 1)             # (W == 1: the launch is its communication wave alone -- no other slot)
+        self.launch = _TileWaves(tiles, int(layout['rows_per_tile']) // 64, grid, wpb, assign)
+        self.idx, self.grid, self.wpb = self.launch.idx, grid, wpb
+        _assert_every_row_once(tiles, self.launch)
+
+    def sum(self, prod):
+        return _final_tree(self.launch.partials(prod))
+
+    def dot(self, a, b):
+        return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
+class TwoLaunchTree:
+    """A product with a dot epilogue as the two-kernel schedules run it WITH A COMMUNICATOR (prcg_session.cpp: overlapped_spmv):
+    the interior tiles [0, interior_tiles) in one launch ('interior_grid' workgroups of 'interior_waves_per_block' waves, partial
+    rows [0, g1)), the tiles that read ghost rows in a second ('grid' x 'waves_per_block', rows [g1, g1 + g2)), each with the plain
+    assignment over ITS tiles (wave slot s takes its s-th, (s + W)-th, ... tile); ONE 256-thread tree over the g1 + g2 rows."""
+
+    def __init__(self, layout):
+        assert layout['window'] and layout['grid'] > 0 and layout['interior_grid'] > 0, {k: v for k, v in layout.items() if np.ndim(v) == 0}
+        tiles = np.asarray(layout['tiles'], dtype=np.int64)
+        nt, nt_int = tiles.shape[0], int(layout['interior_tiles'])
+        assert 0 < nt_int < nt, (nt_int, nt)
+        M = int(layout['rows_per_tile']) // 64
+
+        def plain(first, count, grid, wpb):
+            return _TileWaves(tiles, M, grid, wpb, lambda b, v: range(first + xcd_remap(b, grid) * wpb + v, first + count, grid * wpb))
+        self.interior = plain(0, nt_int, int(layout['interior_grid']), int(layout['interior_waves_per_block']))
+        self.boundary = plain(nt_int, nt - nt_int, int(layout['grid']), int(layout['waves_per_block']))
+        _assert_every_row_once(tiles, self.interior, self.boundary)
+
+    def sum(self, prod):
+        return _final_tree(np.concatenate([self.interior.partials(prod), self.boundary.partials(prod)]))
+
+    def dot(self, a, b):
+        return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
+class RankSum:
+    """An inner product of a multi-rank session: rank r sums ITS rows [offsets[r], offsets[r + 1]) of the product array with its
+    own tree (per_rank_sums[r], a callable on the rank's block in the rank's local row numbers -- ranks may carry different
+    trees), and the ranks' sums are added in rank order STARTING FROM RANK 0's VALUE, v = s[0]; v += s[r] (k_gather_unpack,
+    peer_collect, the all-reduce of tests/transport/threads_ccl.hip) -- not from 0.0: 0.0 + (-0.0) is +0.0."""
+
+    def __init__(self, offsets, per_rank_sums):
+        self.offsets = [int(o) for o in offsets]
+        self.sums = list(per_rank_sums)
+        assert len(self.offsets) == len(self.sums) + 1 and self.offsets[0] == 0 and all(a < b for a, b in zip(self.offsets, self.offsets[1:]))
+
+    def slots(self, prod):
+        prod = np.asarray(prod, dtype=np.float64)
+        assert prod.shape == (self.offsets[-1],), (prod.shape, self.offsets[-1])
+        return [np.float64(s(prod[lo:hi])) for s, lo, hi in zip(self.sums, self.offsets, self.offsets[1:])]
+
+    def __call__(self, prod):
+        s = self.slots(prod)
+        v = s[0]
+        for r in range(1, len(s)):
+            v = v + s[r]
+        return np.float64(v)
+
+    def dot(self, a, b):
+        return self(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
 
 
 class UnitTree:

@@ -6,15 +6,20 @@ tree of the sliced-row and CSR-adaptive launches (UnitTree: variable steps per u
 product of the CSR-adaptive tiles (LongRowOperator: what tests/test_trajectory_irregular.py relies on) -- and that ONE row summed twice, dropped or taken from a stale buffer at ONE iteration of a run hundreds of iterations long changes
 the bits of that iteration's inner products (so a bit-for-bit comparison with the device sees it); likewise ONE wrong
 application of a block-Jacobi preconditioner -- a stale u~, one block summed in another order -- which is what
-tests/test_trajectory_stored_tilde.py is there to see."""
+tests/test_trajectory_stored_tilde.py is there to see.
+
+What tests/test_trajectory_ranks.py relies on (the last section): the trees of ONE RANK of a multi-rank session -- the one-launch
+iteration over the peer exchange (PeerLaunchTree: a communication wave, <= 8 boundary tiles relayed to it), a product in two
+launches (TwoLaunchTree) -- and the rank-order sum (RankSum); and that ranks added in another order, a slot added twice, a
+boundary tile's rows lost or a halo one iteration stale, at ONE iteration of a run, change the bits from there on."""
 import math
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from device_order import (LongRowOperator, OneLaunchTree, Routed, UnitTree, device_sum, first_mismatch, long_row_sum, pair_dot, pair_sum,
-                          tile_cap_nnz, xcd_remap)
+from device_order import (RELAY_TILES, LongRowOperator, OneLaunchTree, PeerLaunchTree, RankSum, Routed, TwoLaunchTree, UnitTree, device_sum,
+                          first_mismatch, long_row_sum, pair_dot, pair_sum, tile_cap_nnz, xcd_remap)
 from oracle import ne_oracle as orc
 
 
@@ -469,3 +474,227 @@ def test_long_row_operator():
         for off in (32, 16, 8, 4, 2, 1):
             v = v + v[np.arange(64) ^ off]                       # the xor butterfly itself, every lane
         assert (v == v[0]).all() and got[i] == v[0]
+
+
+# ---- several ranks: PeerLaunchTree, TwoLaunchTree, RankSum (tests/test_trajectory_ranks.py) -------------------------------------
+def rank_layout(ntiles, nbnd, grid, wpb, rows_per_tile=64, last_rows=None):
+    """what DeviceCSR.layout() returns for one rank of a row-block run: `ntiles` consecutive tiles of the rank's local rows, the
+    nbnd tiles next to the cuts (half of them at the block's first rows, the others at its last) BEHIND the interior ones in the
+    table, as the planner orders them; the block's last tile `last_rows` long"""
+    rb = rows_per_tile * np.arange(ntiles)
+    re = rb + rows_per_tile
+    if last_rows is not None:
+        re[-1] = rb[-1] + last_rows
+    lo = nbnd // 2
+    order = list(range(lo, ntiles - (nbnd - lo))) + list(range(lo)) + list(range(ntiles - (nbnd - lo), ntiles))
+    return {'window': True, 'geometry': 0, 'rows_per_tile': rows_per_tile, 'tiles': np.stack([rb, re], axis=1)[order], 'grid': grid,
+            'waves_per_block': wpb, 'interior_tiles': ntiles - nbnd, 'sweep_waves': 0, 'interior_grid': 0, 'interior_waves_per_block': 0}
+
+
+def as_two_launches(lay):
+    """the same rank after an overlapped product: the interior launch keeps the shape, the boundary launch has one wave per tile"""
+    nb = lay['tiles'].shape[0] - lay['interior_tiles']
+    return dict(lay, interior_grid=lay['grid'], interior_waves_per_block=lay['waves_per_block'], grid=-(-nb // lay['waves_per_block']))
+
+
+BOUNDARY = (0, 3, RELAY_TILES, RELAY_TILES + 1)            # both sides of kRelayTiles, and a rank that reads no ghost rows
+
+
+@pytest.mark.parametrize('wpb', [4, 8])
+@pytest.mark.parametrize('grid', [1, 8, 9, 256])
+@pytest.mark.parametrize('nranks', [2, 3, 4])
+def test_rank_trees_on_synthetic_layouts(nranks, grid, wpb):
+    """Ranks with 0, 3, 8 and 9 boundary tiles (which of them: shifted by the case) on `grid` workgroups of `wpb` waves; rank 1 has
+    fewer tiles than waves, the others a last round that only some waves take.  Every tree sums every row of its rank once (the
+    constructors assert it) and the rank-order sum of each kind of tree is a valid summation: within 1e-13 * sum|terms| of the
+    exactly rounded sum, exact on integers, np.float64 out."""
+    W = grid * wpb
+    rng = np.random.default_rng(nranks * 10000 + grid * 10 + wpb)
+    lays = []
+    for r in range(nranks):
+        nbnd = BOUNDARY[(r + grid + wpb // 4) % 4]
+        nt = max(nbnd + 1, W - 3) if r == 1 else 2 * W + max(1, W // 3)
+        lays.append(rank_layout(nt, nbnd, grid, wpb, last_rows=25))
+    assert lays[1]['tiles'].shape[0] < W or W <= RELAY_TILES + 4
+    offsets = np.concatenate([[0], np.cumsum([int(l['tiles'][:, 1].max()) for l in lays])])
+    peer = [PeerLaunchTree(l) for l in lays]
+    plain = [OneLaunchTree(l) for l in lays]
+    for l, t, o in zip(lays, peer, plain):
+        nb = l['tiles'].shape[0] - l['interior_tiles']
+        assert t.relayed == (0 < nb <= RELAY_TILES)
+        assert np.array_equal(np.sort(t.idx[t.idx >= 0]), np.sort(o.idx[o.idx >= 0]))          # the same rows, each once
+        s0 = [(b, v) for b in range(grid) for v in range(wpb) if xcd_remap(b, grid) * wpb + v == 0]
+        assert s0 == [(0, 0)]
+        comm = t.idx[0, 0]
+        # the communication wave: the boundary tiles one after another when it relays them, else nothing
+        want = np.concatenate([np.arange(rb, re) for rb, re in l['tiles'][l['interior_tiles']:]]) if t.relayed else np.zeros(0)
+        assert np.array_equal(np.sort(comm[comm >= 0]), np.sort(want))
+    kinds = {'peer': [t.sum for t in peer], 'gather': [t.sum for t in plain],
+             'two launches': [TwoLaunchTree(as_two_launches(l)).sum if 0 < l['interior_tiles'] < l['tiles'].shape[0] else pair_sum for l in lays],
+             'mixed': [(peer[r].sum, device_sum, pair_sum, plain[r].sum)[r] for r in range(nranks)]}
+    n = int(offsets[-1])
+    prod = rng.standard_normal(n) * np.exp(rng.uniform(-8, 8, n))
+    ints = rng.integers(-1000, 1000, n).astype(np.float64)
+    for kind, sums in kinds.items():
+        rs = RankSum(offsets, sums)
+        got = rs(prod)
+        assert type(got) is np.float64, kind
+        assert abs(got - math.fsum(prod)) <= 1e-13 * math.fsum(np.abs(prod)), kind
+        assert rs(ints) == ints.sum(), kind
+        a = rng.standard_normal(n)
+        assert rs.dot(a, prod) == rs(a * prod)
+        slots = rs.slots(prod)
+        want = slots[0]
+        for v in slots[1:]:
+            want = want + v
+        assert len(slots) == nranks and got == want, kind
+
+
+def test_peer_tree_assignment_and_its_difference_from_the_plain_one():
+    """The assignment on a layout small enough to write down, both sides of kRelayTiles; a launch of one workgroup of two
+    waves; and on a rank WITHOUT boundary tiles the peer tree covers the rows of OneLaunchTree and differs from it in bits (every
+    wave's tiles are shifted by one slot and stride W - 1)."""
+    def tiles_of_wave(tree, lay, b, v):
+        col = tree.idx[b, v, :, 0]
+        first = {int(rb): i for i, (rb, re) in enumerate(lay['tiles'])}
+        return [first[int(x)] for x in col[col >= 0] if int(x) in first]
+    lay = rank_layout(7, 2, 1, 4)                               # table: interior tiles 0..4, boundary tiles 5, 6
+    t = PeerLaunchTree(lay)
+    assert t.relayed and [tiles_of_wave(t, lay, 0, v) for v in range(4)] == [[5, 6], [0, 3], [1, 4], [2]]
+    lay = rank_layout(14, 9, 1, 4)                              # nine boundary tiles: they stay with all the waves
+    t = PeerLaunchTree(lay)
+    assert not t.relayed and [tiles_of_wave(t, lay, 0, v) for v in range(4)] == [[], [0, 3, 6, 9, 12], [1, 4, 7, 10, 13], [2, 5, 8, 11]]
+    lay = rank_layout(3, 1, 1, 2)
+    assert [tiles_of_wave(PeerLaunchTree(lay), lay, 0, v) for v in range(2)] == [[2], [0, 1]]
+    with pytest.raises(AssertionError, match='exactly once'):
+        PeerLaunchTree(dict(lay, tiles=lay['tiles'][[0, 1, 1]]))
+    lay = rank_layout(3 * 9 * 4, 0, 9, 4, last_rows=25)
+    peer, plain = PeerLaunchTree(lay), OneLaunchTree(lay)
+    assert not peer.relayed and (peer.idx[0, 0] < 0).all()
+    assert np.array_equal(np.sort(peer.idx[peer.idx >= 0]), np.sort(plain.idx[plain.idx >= 0]))
+    rng = np.random.default_rng(3)
+    vecs = [rng.standard_normal(int(lay['tiles'][:, 1].max())) for _ in range(3)]
+    assert [peer.sum(v) for v in vecs] != [plain.sum(v) for v in vecs]
+    assert all(abs(peer.sum(v) - plain.sum(v)) <= 2e-13 * math.fsum(np.abs(v)) for v in vecs)
+
+
+def test_rank_sum_starts_from_rank_zero():
+    """v = s[0]; v += s[r]: a sum that started from +0.0 would turn a first slot of -0.0 into +0.0"""
+    rs = RankSum([0, 2, 4], [lambda p: np.float64(-0.0), lambda p: np.float64(-0.0)])
+    assert np.signbit(rs(np.zeros(4)))
+    order = []
+    rs = RankSum([0, 1, 3, 6], [lambda p, r=r: order.append((r, p.shape[0])) or p.sum() for r in range(3)])
+    assert rs(np.arange(6.0)) == 15.0 and order == [(0, 1), (1, 2), (2, 3)]
+    big = RankSum([0, 1, 2, 3], [lambda p: p[0]] * 3)
+    assert big(np.array([1.0, 2.0 ** -53, 2.0 ** -53])) == 1.0 and big(np.array([2.0 ** -53, 2.0 ** -53, 1.0])) == 1.0 + 2.0 ** -52
+
+
+class StaleHaloOperator:
+    """A as `nranks` row blocks multiply it, ONE product (call `at`, counted from 0) reading its GHOST columns -- the columns
+    outside the rank's own rows -- from the vector of the call two before (the same product of the previous iteration: a halo one
+    iteration stale).  Every row is still SciPy's left-to-right sum: only the values of the ghost entries differ."""
+
+    def __init__(self, A, offsets, at):
+        self.A, self.offsets, self.at, self.calls, self.seen, self.changed = A.tocsr(), [int(o) for o in offsets], at, 0, [], 0
+        self.shape = A.shape
+
+    def diagonal(self):
+        return self.A.diagonal()
+
+    def __matmul__(self, v):
+        v = np.asarray(v, dtype=np.float64)
+        self.seen = (self.seen + [v.copy()])[-3:]
+        self.calls += 1
+        y = self.A @ v
+        if self.calls - 1 != self.at:
+            return y
+        stale = self.seen[0]
+        for lo, hi in zip(self.offsets, self.offsets[1:]):
+            mixed = stale.copy()
+            mixed[lo:hi] = v[lo:hi]
+            y[lo:hi] = self.A[lo:hi] @ mixed
+        self.changed = int(np.count_nonzero(y != self.A @ v))
+        return y
+
+
+class FaultyRankSum(RankSum):
+    """RankSum with ONE fault in every inner product of ONE iteration (calls 4 (k - 1) .. 4 (k - 1) + 3 of pipe_pr_pcg's advance):
+    'reversed' adds the ranks from the last to the first -- FROM that iteration on, as a rank with the wrong order would: most sums
+    of a few slots of like size have the same bits in either order --, 'twice' adds rank 1's slot twice, 'tile_dropped' leaves the rows of
+    rank 1's first boundary tile out of its sum."""
+
+    def __init__(self, offsets, sums, kind, k_bad, drop_rows=None):
+        super().__init__(offsets, sums)
+        self.kind, self.k_bad, self.calls, self.drop_rows = kind, k_bad, 0, drop_rows
+
+    def __call__(self, prod):
+        k = self.calls // 4 + 1
+        self.calls += 1
+        if self.kind is None or k < self.k_bad or (k > self.k_bad and self.kind != 'reversed'):
+            return super().__call__(prod)
+        if self.kind == 'tile_dropped':
+            p = np.array(prod, dtype=np.float64)
+            p[self.drop_rows] = 0.0
+            return super().__call__(p)
+        s = self.slots(prod)
+        if self.kind == 'reversed':
+            s = s[::-1]
+        v = s[0]
+        for r in range(1, len(s)):
+            v = v + s[r]
+        return np.float64(v + s[1]) if self.kind == 'twice' else np.float64(v)
+
+
+@pytest.mark.parametrize('kind,nranks', [('reversed', 4), ('twice', 2), ('tile_dropped', 2), ('stale_halo', 2)])
+def test_one_wrong_exchange_at_one_iteration_of_a_multi_rank_run_shows_in_the_bits(kind, nranks):
+    """What tests/test_trajectory_ranks.py is for, on the model's side: pipe_pr_pcg with Jacobi on a small band (the 5-point stencil
+    on a 7 x 430 grid: n = 3010, 7-row halo, still converging at iteration 60 -- on the ex2b band Jacobi is the inverse to rounding,
+    the run sits in a two-cycle of rounding noise from iteration 6 on and a wrong bit heals) in `nranks` row blocks, every rank on 4 workgroups of 4 waves with the peer tree (the boundary tiles next to the cuts
+    relayed to the communication wave), the ranks added in rank order; 90 iterations, then again with one fault at iteration 50.
+    Two ranks, except for the reversed order: s[0] + s[1] = s[1] + s[0] bit for bit, an order shows from three ranks on -- and
+    even then it leaves most sums' bits alone (7 of 8 tried with three slots of like size), so that fault runs on four ranks and
+    stays in force from iteration 50 on: it must show by iteration 52 like the stale halo.  The
+    trajectories agree bit for bit before iteration 50 and differ from 50 (a wrong sum: that iteration's inner products), or
+    within the next two iterations (a stale halo reaches u of iteration 50, w and s of 51 and every inner product by 52), and
+    at every iteration after the first difference."""
+    from new_cg_variants_amd import problems
+    iters, k_bad = 90, 50
+    A = problems.laplace_2d(7, 430)
+    n = A.shape[0]
+    b, x0, _ = problems.reference_rhs(A, n)
+    # (uneven blocks: the problem is symmetric under a reversal of the rows, and so would the outer ranks' sums be)
+    offsets = np.round(n * np.array({2: [0, 0.43, 1], 4: [0, 0.19, 0.4, 0.73, 1]}[nranks])).astype(np.int64)
+    lays = []
+    for r in range(nranks):
+        nt = -(-int(offsets[r + 1] - offsets[r]) // 64)
+        nbnd = (r > 0) + (r < nranks - 1)
+        lay = rank_layout(nt, nbnd, 4, 4, last_rows=int(offsets[r + 1] - offsets[r]) - 64 * (nt - 1))
+        lays.append(lay)
+    trees = [PeerLaunchTree(l) for l in lays]
+    assert all(t.relayed for t in trees)
+    rb, re = lays[1]['tiles'][lays[1]['interior_tiles']]
+    drop = np.arange(offsets[1] + rb, offsets[1] + re)
+
+    def run(fault, op=A):
+        rows = []
+        dot = FaultyRankSum(offsets, [t.sum for t in trees], fault, k_bad, drop)
+        orc.pipe_pr_pcg(op, b, x0, iters, preconditioner=orc.jacobi(A), dot=Routed(dot), dot0=Routed(RankSum(offsets, [device_sum] * nranks)),
+                        square=lambda a: a * a, tap=lambda st: rows.append((st.mu, st.dl, st.gm, st.nu, st.eta, st.alpha, st.beta)))
+        assert dot.calls == 4 * (iters - 1)
+        return np.array(rows)
+
+    clean = run(None)
+    assert np.isfinite(clean).all() and clean.shape == (iters, 7) and (clean[:, [0, 1, 2, 3]] > 0).all()
+    if kind == 'stale_halo':
+        assert first_mismatch(run(None, StaleHaloOperator(A, offsets, -1)), clean) == -1       # the wrapper alone changes nothing
+        op = StaleHaloOperator(A, offsets, 3 + 2 * (k_bad - 1))          # three products at the start, then u = A s~, w = A r~ per iteration
+        faulty = run(None, op)
+        assert op.calls == 3 + 2 * (iters - 1) and 1 <= op.changed <= 14 * (nranks - 1), op.changed
+        lo, hi = k_bad, k_bad + 2
+    else:
+        faulty = run(kind)
+        lo, hi = k_bad, k_bad + (2 if kind == 'reversed' else 0)
+    first = first_mismatch(faulty, clean)
+    assert lo <= first <= hi, (kind, first)
+    differs = (faulty != clean).any(axis=1)
+    assert differs[first:].all() and differs[-1] and not differs[:first].any()

@@ -241,70 +241,7 @@ def test_two_ranks_through_rccl_when_the_box_allows_it(tmp_path):
 # ranks on one device).  Real inter-rank data: what rank r reads in its ghost rows was computed by the
 # kernels of rank r +- 1.
 # ---------------------------------------------------------------------------------------
-def run_ranks_in_threads(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15, offsets=None, peer=False, chunks=None):
-    """Solve with `nranks` row blocks, one thread per rank, all on cuda:0.  Returns (x, histories of rank 0, schedules).
-    peer: connect the ranks' exchange buffers (direct peer exchange; same process: device addresses instead of IPC handles).
-    chunks: lengths of the prcg_iterate calls (default: one call)."""
-    import threading
-    from new_cg_variants_amd import _lib as L
-    from new_cg_variants_amd import partition, problems
-    from new_cg_variants_amd.device import DeviceCSR
-    path = os.path.join(ROOT, 'tests', 'transport', 'libthreads_ccl.so')
-    assert os.path.exists(path), 'build it with `make` (tests/transport/threads_ccl.hip)'
-    n = A.shape[0]
-    b, x0, x_true = problems.reference_rhs(A, n)
-    offsets, parts = partition.split_serial(A, nranks, offsets)
-    uid = np.zeros(128, dtype=np.uint8)
-    L.check(None, L.lib().prcg_comm_unique_id(path.encode(), L.ptr(uid)))
-    out = [None] * nranks
-    errs = []
-
-    def rank_main(r):
-        try:
-            A_local, ghost_ids, halo = parts[r]
-            lo, hi = int(offsets[r]), int(offsets[r + 1])
-            op = DeviceCSR(A_local, comm_init=(r, nranks, uid.tobytes(), path), halo=halo,
-                           knobs=knobs[r] if isinstance(knobs, list) else knobs)
-            if peer:
-                assert partition.connect_peer_exchange(op, r, gather_objects), 'peer exchange did not connect'
-            y = op.matvec(x_true[lo:hi] * (1.0 + np.arange(lo, hi)))[0]
-            op.begin(variant, b[lo:hi], x0[lo:hi], iters + 1, x_true=x_true[lo:hi],
-                     inv_diag=None if inv_diag is None else inv_diag[lo:hi], hist_mask=hist_mask)
-            sched = op.schedule()
-            for c in (chunks or [iters]):
-                op.iterate(c)
-            op.sync()
-            out[r] = (op.get_vector('x'), op.history(), sched, y)
-            op.close()
-        except Exception as exc:           # noqa: BLE001 -- reported by the caller
-            errs.append((r, repr(exc)))
-
-    # all-gather of Python objects among the rank threads (what torch.distributed.all_gather_object is between processes)
-    box = {}
-    barrier = threading.Barrier(nranks)
-    seq = [0] * nranks
-
-    def gather_objects(obj):
-        r = int(threading.current_thread().name.split('-')[-1])
-        key = seq[r]
-        seq[r] += 1
-        box[(key, r)] = obj
-        barrier.wait(timeout=120)
-        res = [box[(key, q)] for q in range(nranks)]
-        barrier.wait(timeout=120)
-        return res
-
-    threads = [threading.Thread(target=rank_main, args=(r,), name=f'rank-{r}', daemon=True) for r in range(nranks)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(timeout=240)          # (daemon threads: a rank that never returns fails the test instead of hanging pytest)
-    assert not errs, errs
-    assert all(o is not None for o in out), 'a rank did not finish'
-    x = np.concatenate([o[0] for o in out])
-    y = np.concatenate([o[3] for o in out])
-    assert np.array_equal(y, A @ (x_true * (1.0 + np.arange(n)))), 'distributed SpMV differs from the global product'
-    return x, out[0][1], [o[2] for o in out]
+from ranks_common import run_ranks_in_threads  # noqa: E402  (shared with tests/test_trajectory_ranks.py)
 
 
 @pytest.mark.gpu

@@ -23,6 +23,8 @@ METHODS = {
     # the pipelined flavours without a preconditioner (another epilogue of the one-launch iteration: kEpiPipeFused / FusedP)
     'pipe_pr_cg': ('PIPE_PR', 'pipe', False, PIPE_SLOTS), 'pipe_p_cg': ('PIPE_P', 'pipe', False, PIPE_SLOTS),
 }
+# ... and the Meurant flavours without one: run by tests/test_trajectory_ranks.py only (METHODS parametrises other files)
+ALL_METHODS = dict(METHODS, pipe_pr_m_cg=('PIPE_PR_M', 'pipe', False, PIPE_SLOTS), pipe_p_m_cg=('PIPE_P_M', 'pipe', False, PIPE_SLOTS))
 ORACLE_NAME = {'pr_cg': 'pr_pcg', 'm_cg': 'm_pcg'}
 CHUNKS = (1, 2, 37)          # prcg_iterate calls of mode (b), then the rest: state read at k = 3 (odd), k = 40 (even) and the end
 FIELD = {'mu': 0, 'dl': 1, 'gm': 2, 'nu': 3, 'eta': 4, 'alpha': 5, 'beta': 6}
@@ -38,7 +40,7 @@ def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep, vectors=
         rows.append((st.mu, st.dl, st.gm, st.nu, st.eta, st.alpha, st.beta))
         if st.k in keep:
             snaps[st.k] = tuple(getattr(st, v).copy() for v in vectors)
-    kw = {'preconditioner': jacobi} if METHODS[method][2] else {}
+    kw = {'preconditioner': jacobi} if ALL_METHODS[method][2] else {}
     ref = getattr(orc, ORACLE_NAME.get(method, method))(A, b, np.zeros(A.shape[0]), max_iter, dot=dot, dot0=dot0, square=lambda a: a * a,
                                                          callbacks=FOUR, x_true=x_true, tap=tap, **kw)
     return np.array(rows, dtype=np.float64), ref, snaps
