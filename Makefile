@@ -26,7 +26,7 @@ $(CSRC)/prcg_win.o: $(CSRC)/prcg_win.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geo
 $(CSRC)/prcg_sell.o: $(CSRC)/prcg_sell.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
-$(CSRC)/prcg_blockjac.o: $(CSRC)/prcg_blockjac.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h
+$(CSRC)/prcg_blockjac.o: $(CSRC)/prcg_blockjac.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c $< -o $@
 
 $(CSRC)/prcg_rhs2.o: $(CSRC)/prcg_rhs2.hip $(CSRC)/prcg_kernels.h $(CSRC)/prcg_geometry.h $(CSRC)/prcg_device.hpp

@@ -427,8 +427,41 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
  * order: exchanging the two right-hand sides exchanges the two results bit for bit. */
 int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
                                 int max_iter, const double* inv_diag, uint32_t hist_mask);
-/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi; PRCG_PR / PRCG_M sessions with Jacobi also _ST; pipelined sessions: see
- * prcg_solve_begin_multi_pipe); out: n_rows host doubles */
+/* ---- TWO or FOUR right-hand sides preconditioned by POINT-BLOCK JACOBI, in one session -----------------------------------
+ * Replaces two (four) calls of the reference's hs_pcg (hs_cg.py:70), pr_pcg (pr_cg.py:166) or m_pcg (pr_cg.py:172) on one matrix
+ * with `preconditioner` the point-block Jacobi IN FORCE ON THE HANDLE: the blocks prcg_set_block_jacobi, prcg_build_block_jacobi,
+ * prcg_set_block_jacobi_var or prcg_build_block_jacobi_var put there.  (A Newton loop: prcg_update_values, prcg_build_block_jacobi,
+ * this call.)  The blocks stay on the handle afterwards as after a single session; a later prcg_set_csr drops them, a later
+ * prcg_update_values leaves them frozen.
+ *   variant: PRCG_HS, PRCG_PR or PRCG_M.  nrhs: 2 or 4 (two pair groups: columns (0, 1) and (2, 3) carry the bits of two two-RHS
+ *   block sessions begun with those pairs, around ONE product of both groups' directions, PRCG_SCHED_SPMM4 as above).  b, x0: nrhs
+ *   pointers to n_rows host doubles each.  hist_mask: 0 or PRCG_HIST_UPDATED_RESIDUAL_2_NORM.
+ * State per pair group: the interleaved n x 2 arrays X, R, P, S of prcg_solve_begin_multi, r~ a STORED vector and, for PRCG_PR /
+ * PRCG_M, s~ too.  M^-1 v is, word for word, the loop of prcg_set_block_jacobi / _var (acc = B[a][0] * v[start]; acc = acc +
+ * B[a][j] * v[start + j] for ascending j, every product and sum rounded), applied to both columns in one launch that reads every
+ * block once and leaves, in the same launch, the partial sums of the inner products that need the result:
+ *   Hestenes-Stiefel  r~ = M^-1 r is formed anew in every iteration: update (x, r), BLOCK launch (r~; nu = r.r~, rr = r.r),
+ *                     reduction, p = r~ + b p, product, mu = p.s (the vector launch of prcg_solve_begin_multi), reduction;
+ *   PRCG_PR / PRCG_M  r~ is recurred (r~ -= a s~), s~ = M^-1 s is applied once per iteration: update (x, r, r~, p; nu, rr from this
+ *                     vector launch), product, BLOCK launch (s~; mu = p.s, delta = r.s~, gamma = s~.s), ONE reduction launch for the
+ *                     five sums of both columns.  At the start nu and rr come from a block launch as well (r~ = M^-1 r).
+ * Every inner product is summed in one fixed order that depends on n and the partition only (the sums of a
+ * block launch by tile -- lane t the row tile_row0 + t, butterfly, waves in order, tiles in order through the final tree).  Each
+ * column has its own scalars; nothing of one column enters another; exchanging the right-hand sides exchanges the results bit
+ * for bit; a NaN stays in its column.
+ * A new entry: prcg_solve_begin_multi and prcg_solve_begin_multi_pipe keep refusing a handle with blocks set.  Refused here
+ * (PRCG_EINVAL, the text names the reason; the handle and an open session stay as they were): no operator, no blocks on the handle,
+ * another variant (the pipelined ones: a follow-up), nrhs outside {2, 4}, a communicator, n_ghost > 0, a replace hook, another
+ * history bit, null b or x0, max_iter < 1.
+ * prcg_iterate / prcg_sync / prcg_iteration / prcg_set_profiling / prcg_get_timings serve the session as they are; prcg_schedule
+ * reports PRCG_SCHED_RHS2 or PRCG_SCHED_RHS4, PRCG_SCHED_BLOCK_JACOBI (| PRCG_SCHED_BLOCK_JACOBI_VAR for a partition) and
+ * PRCG_SCHED_SPMM4 where it applies.  State is read per column with the calls below: vectors PRCG_VEC_X, _R, _P, _S, _RT, for
+ * PRCG_PR / PRCG_M also _ST; scalars {mu, -, -, nu, rr} (PRCG_PR / PRCG_M: {mu, delta, gamma, nu, rr}); the single-column
+ * accessors are refused while it is open.  A later prcg_solve_begin* opens an ordinary session. */
+int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0,
+                                        int max_iter, uint32_t hist_mask);
+/* which: PRCG_VEC_X, _R, _P, _S (and _RT with Jacobi or block Jacobi; PRCG_PR / PRCG_M sessions with either also _ST; pipelined
+ * sessions: see prcg_solve_begin_multi_pipe); out: n_rows host doubles */
 int prcg_get_vector_rhs(prcg_t* h, int which, int j, double* out);
 /* PRCG_NUM_SCALARS doubles: mu, nu, rr of column j at iteration k in their slots (PRCG_PR / PRCG_M sessions: mu, delta,
  * gamma, nu, rr; pipelined sessions the same), every other slot 0 */

@@ -87,6 +87,7 @@ _SIGNATURES = {
     'prcg_get_history': (C.c_int, [_P, _P]),
     'prcg_solve_begin_multi': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_uint32]),
     'prcg_solve_begin_multi_pipe': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_uint32]),
+    'prcg_solve_begin_multi_block_jacobi': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_uint32]),
     'prcg_get_vector_rhs': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'prcg_get_scalars_rhs': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'prcg_get_coefficients_rhs': (C.c_int, [_P, C.c_int, C.c_int, _P]),

@@ -665,7 +665,21 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
         inv_diag, prec_fn = _diagonal_of(preconditioner, n)
     if prec_fn is not None:
         kind = 'a block-Jacobi preconditioner' if isinstance(prec_fn, (DeviceBlockJacobi, VarBlockJacobi)) or _blocks_of(prec_fn) is not None else 'a preconditioner that is no diagonal scaling'
-        raise ValueError(f'{name}: {kind} is not served by the two-RHS session (Jacobi(A), a callable that acts as a diagonal, or None)')
+        hint = f"; blocks: {name.replace('_pcg_multi', '_bpcg_multi')}" if kind.startswith('a block') and name in ('hs_pcg_multi', 'pr_pcg_multi', 'm_pcg_multi') else ''
+        raise ValueError(f'{name}: {kind} is not served by the two-RHS session (Jacobi(A), a callable that acts as a diagonal, or None{hint})')
+    mask, light = _multi_callbacks(name, callbacks)
+    op = _operator(A, int(kwargs.get('device', 0)))
+    op.set_replace_hook(None)
+    op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
+    if pipelined:
+        op.begin_multi_pipe(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    else:
+        op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    return _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs)
+
+
+def _multi_callbacks(name, callbacks):
+    """(hist_mask, light host callbacks) of a multi-RHS session's callbacks; ValueError for what the session does not serve"""
     mask = 0
     light = []
     for cb in callbacks:
@@ -679,13 +693,12 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
         else:
             raise ValueError(f'{name}: callback {cname or cb!r} needs the state vectors every iteration: not served by the two-RHS '
                              'session (the updated_residual_2_norm recorder and light host callbacks are)')
-    op = _operator(A, int(kwargs.get('device', 0)))
-    op.set_replace_hook(None)
-    op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
-    if pipelined:
-        op.begin_multi_pipe(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
-    else:
-        op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+    return mask, light
+
+
+def _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs):
+    """run the multi-RHS session just begun on `op` to max_iter - 1 iterations; the list of per-column trial dicts"""
+    n, nrhs = A.shape[0], B.shape[0]
     outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(nrhs)]
 
     def call_host(k):
@@ -706,6 +719,73 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
     for j in range(nrhs):
         outputs[j].update(op.history(rhs=j))
     return outputs
+
+
+def _run_multi_blocks(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs):
+    """Two or four right-hand sides of one matrix in ONE session of `variant` (L.HS, L.PR, L.M) preconditioned by point-block Jacobi on
+    the device (prcg.h: prcg_solve_begin_multi_block_jacobi).  Shapes, callbacks, x_true and w_replace are checked as _run_multi checks
+    them, before the device is touched; a preconditioner that carries no blocks raises ValueError naming the function to use."""
+    if A.format != 'csr':
+        A = A.tocsr()
+    n = A.shape[0]
+    B, X0 = np.asarray(B, dtype=np.float64), np.asarray(X0, dtype=np.float64)
+    for nm, V, want in (('B', B, None), ('X0', X0, B.shape[0] if B.ndim == 2 else None)):
+        err = multi_rhs_shape_error(nm, V.shape, n, want)
+        if err:
+            raise ValueError(f'{name}: {err}')
+    for key in ('x_true', 'w_replace'):
+        if kwargs.get(key) is not None:
+            raise ValueError(f'{name}: {key} is not served by the two-RHS session')
+    other = name.replace('_bpcg_multi', '_pcg_multi')
+    built = isinstance(preconditioner, DeviceBlockJacobi)
+    var = isinstance(preconditioner, VarBlockJacobi)
+    blocks = None if built or var or preconditioner is None else _blocks_of(preconditioner)
+    if not (built or var) and (blocks is None or getattr(preconditioner, 'inv_diag', None) is not None):
+        what = ('no preconditioner' if preconditioner is None else
+                'a diagonal scaling' if getattr(preconditioner, 'inv_diag', None) is not None else 'a preconditioner that carries no blocks')
+        raise ValueError(f'{name}: {what}: the block session takes BlockJacobi, DeviceBlockJacobi, VarBlockJacobi, DeviceVarBlockJacobi or an '
+                         f'object carrying bs / inv_blocks; use {other} (Jacobi(A), a callable that acts as a diagonal, or None)')
+    if (built or var) and preconditioner.n != n:
+        raise ValueError(f'{type(preconditioner).__name__}: made for a matrix of {preconditioner.n} rows, the system has {n}')
+    if blocks is not None and (not 1 <= blocks[0] <= 8 or blocks[1].shape != (-(-n // blocks[0]), blocks[0], blocks[0])):
+        raise ValueError(f'{name}: need 1 <= bs <= 8 and inv_blocks of shape (ceil(n/bs), bs, bs); got bs={blocks[0]}, {blocks[1].shape}')
+    mask, light = _multi_callbacks(name, callbacks)
+    op = _operator(A, int(kwargs.get('device', 0)))
+    op.set_replace_hook(None)
+    try:
+        if var:
+            on_device = isinstance(preconditioner, DeviceVarBlockJacobi)       # built there: the object's blocks are never read
+            op.begin_multi_block_jacobi(variant, B, X0, max_iter, hist_mask=mask,
+                                        block_jacobi_var=(preconditioner.block_ptr, None if on_device else preconditioner.inv_blocks))
+        elif built:
+            op.begin_multi_block_jacobi(variant, B, X0, max_iter, hist_mask=mask, block_jacobi=(preconditioner.bs, None))
+        else:
+            op.begin_multi_block_jacobi(variant, B, X0, max_iter, hist_mask=mask, block_jacobi=blocks)
+    except ValueError as e:
+        if 'diagonal block' not in str(e) or not (built or var):
+            raise
+        raise ValueError(f'{type(preconditioner).__name__}: ' + str(e).split(': ', 1)[-1]) from None      # the library's text, this object's name
+    return _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs)
+
+
+def _make_bpcg_multi(variant, name, where):
+    single = name[:-len('_bpcg_multi')]
+
+    def f(A, B, X0, max_iter, preconditioner, callbacks=[], **kwargs):
+        return _run_multi_blocks(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs)
+    f.__doc__ = (f'{single}_pcg ({where}) for TWO or FOUR right-hand sides of one matrix, preconditioned by POINT-BLOCK JACOBI applied on the '
+                 'device: B, X0 of shape (2, n) or (4, n); returns a list of two or four trial dicts.  preconditioner: BlockJacobi, '
+                 'DeviceBlockJacobi, VarBlockJacobi, DeviceVarBlockJacobi or an object carrying bs / inv_blocks; None, a diagonal or any '
+                 f'other callable is a ValueError naming {single}_pcg_multi.  One session (prcg.h: prcg_solve_begin_multi_block_jacobi): per '
+                 'iteration one pass over the operator for all systems and one pass over the blocks per pair of systems, with the inner '
+                 'products that need M^-1 formed in the launch that applies it.')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+hs_bpcg_multi = _make_bpcg_multi(L.HS, 'hs_bpcg_multi', 'hs_cg.py:70')
+pr_bpcg_multi = _make_bpcg_multi(L.PR, 'pr_bpcg_multi', 'pr_cg.py:166')
+m_bpcg_multi = _make_bpcg_multi(L.M, 'm_bpcg_multi', 'pr_cg.py:172')
 
 
 def hs_cg_multi(A, B, X0, max_iter, callbacks=[], **kwargs):
@@ -1048,5 +1128,5 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'hs_cg_multi', 'hs_pcg_multi', 'pr_cg_multi', 'pr_pcg_multi', 'm_cg_multi', 'm_pcg_multi',
            'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
            'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch', 'pipe_pr_pcg_batch', 'pipe_pr_m_pcg_batch', 'hs_pcg_batch',
-           'pipe_pr_bpcg_batch', 'pipe_pr_m_bpcg_batch', 'hs_bpcg_batch',
+           'pipe_pr_bpcg_batch', 'pipe_pr_m_bpcg_batch', 'hs_bpcg_batch', 'hs_bpcg_multi', 'pr_bpcg_multi', 'm_bpcg_multi',
            'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi']

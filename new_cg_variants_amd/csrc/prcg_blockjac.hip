@@ -25,11 +25,13 @@
 #include <hip/hip_runtime.h>
 
 #include "prcg_kernels.h"
+#include "prcg_device.hpp"
 
 namespace prcg {
 namespace {
 
 constexpr int kBjBlock = 256;    // lanes per workgroup = entries per (tile, j) line of the device layout
+static_assert(kBjBlock == kBlock, "block_reduce_store sums the four waves of a 256-lane workgroup");
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -317,7 +319,151 @@ __global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_build(double* __r
         if (j < L) out[(int64_t)j * kBjBlock] = j < m ? E[j] : 0.0;
 }
 
+// ---- M^-1 on an interleaved n x 2 array WITH the inner products that need the result, in one launch: the block-Jacobi sessions
+// with two or four right-hand sides (prcg_solve_begin_multi_block_jacobi).  The apply is k_block_jacobi_pair's (k_block_jacobi_var_pair's):
+// one 16-byte load per row, the pair parked in LDS, one barrier, the block's entries read from LDS as a broadcast, the row of the
+// inverse loaded with coalesced reads and used for BOTH columns; one 16-byte store of (z_0, z_1).  Two modes:
+//   kBjDotsNu   z = M^-1 r -> r~;  partials of nu_c = r_c.z_c and rr_c = r_c.r_c                       (m + 4) * 8 useful bytes per row
+//   kBjDotsPr   z = M^-1 s -> s~;  partials of mu_c = p_c.s_c, dl_c = r_c.z_c, gm_c = z_c.s_c          (m + 8) * 8
+// Sums: ONE partial row per tile.  Lane t holds the products of row tile_row0 + t -- a lane WITHOUT a row holds +0.0 and stays to
+// the end: the block reduction has a barrier of its own, so nobody returns after the first one -- xor butterfly per wave, waves
+// 0..3 in order (block_reduce_store / block_reduce_store2), the tile partials in tile order by the final tree.  The tiles are a
+// function of n and the partition alone.  The uniform tiles of 256 - 256 % bs rows are the greedy tiles of bjvar_plan on the uniform
+// partition, and both forms then sum in the same tree -- with ONE exception: where a short last block fits into the 256 % bs lanes
+// a full tile leaves idle (n mod (256 - 256 % bs) in 1 .. 256 % bs) the greedy tiling takes it into the last full tile while the
+// uniform kernel gives it a tile of its own; for such n the two forms have different trees and need not give equal bits.
+// Each column has its own accumulators; no branch on a value.
+// Partial rows: NU with part1 == nullptr writes [nu_0 rr_0 nu_1 rr_1] to slots 3..6 of part0 (the Hestenes-Stiefel scalar row);
+// otherwise column c's sums go to part[c] in the single-session slots (NU: 3, 4; PR: 0, 1, 2).
+template <int MODE>
+__device__ __forceinline__ void bj_dots_finish(const BjDotsArgs& a, int64_t i, bool live, d2_t own, d2_t z, d2_t pv, d2_t rv) {
+    if (live) reinterpret_cast<d2_t*>(a.z)[i] = z;
+    if constexpr (MODE == kBjDotsNu) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};                   // nu_0, rr_0, nu_1, rr_1
+        if (live) { acc[0] = own.x * z.x; acc[1] = own.x * own.x; acc[2] = own.y * z.y; acc[3] = own.y * own.y; }
+        if (a.part1) block_reduce_store2<2>(acc, a.part0, a.part1, kPr2Nu);       // (uniform over the launch)
+        else block_reduce_store<4>(acc, a.part0, kHs2Nu);
+    } else {
+        double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};         // mu_0, dl_0, gm_0, mu_1, dl_1, gm_1
+        if (live) {
+            acc[0] = pv.x * own.x; acc[1] = rv.x * z.x; acc[2] = z.x * own.x;
+            acc[3] = pv.y * own.y; acc[4] = rv.y * z.y; acc[5] = z.y * own.y;
+        }
+        block_reduce_store2<3>(acc, a.part0, a.part1, kPr2Mu);
+    }
+}
+
+template <int BS, int MODE>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_dots(BjDotsArgs a, const double* __restrict__ blk) {
+    constexpr int TR = (kBjBlock / BS) * BS;
+    __shared__ d2_t sv[kBjBlock];
+    const int t = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * TR;
+    const int64_t i = row0 + t;
+    const bool live = t < TR && i < a.n;
+    d2_t own = {0.0, 0.0}, pv = {0.0, 0.0}, rv = {0.0, 0.0}, z = {0.0, 0.0};
+    double b[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) b[j] = 0.0;
+    if (live) {
+        own = reinterpret_cast<const d2_t*>(a.v)[i];
+        sv[t] = own;
+        const double* bp = blk + ((int64_t)blockIdx.x * BS) * kBjBlock + t;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) b[j] = bp[(int64_t)j * kBjBlock];
+        if constexpr (MODE == kBjDotsPr) { pv = reinterpret_cast<const d2_t*>(a.p)[i]; rv = reinterpret_cast<const d2_t*>(a.r)[i]; }
+    }
+    __syncthreads();
+    if (live) {
+        const int c0 = t - t % BS;                            // first lane of this row's block
+        const int64_t cols = a.n - (row0 + c0);               // columns the block really has (>= BS except in a short last block)
+        d2_t v = sv[c0];
+        z.x = b[0] * v.x; z.y = b[0] * v.y;
+#pragma unroll
+        for (int j = 1; j < BS; ++j)
+            if (j < cols) {
+                v = sv[c0 + j];
+                z.x = z.x + b[j] * v.x;
+                z.y = z.y + b[j] * v.y;
+            }
+    }
+    bj_dots_finish<MODE>(a, i, live, own, z, pv, rv);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_dots(BjDotsArgs a, const long long* __restrict__ tiles,
+                                                                    const unsigned char* __restrict__ code, const double* __restrict__ blk) {
+    __shared__ d2_t sv[kBjBlock + kBjvPad];
+    const int t = threadIdx.x;
+    const long long* tw = tiles + (int64_t)blockIdx.x * 4;
+    const int64_t i = tw[0] + t;
+    const int cd = code[(int64_t)blockIdx.x * kBjBlock + t];
+    const bool live = !(cd & kBjvDeadBit);
+    const int aa = cd & 7, m = ((cd >> 3) & 7) + 1;
+    d2_t own = {0.0, 0.0}, pv = {0.0, 0.0}, rv = {0.0, 0.0}, z = {0.0, 0.0};
+    double b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = 0.0;
+    if (live) {
+        own = reinterpret_cast<const d2_t*>(a.v)[i];
+        sv[t] = own;
+        const double* bp = blk + tw[1] * kBjBlock + t;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < m) b[j] = bp[(int64_t)j * kBjBlock];
+        if constexpr (MODE == kBjDotsPr) { pv = reinterpret_cast<const d2_t*>(a.p)[i]; rv = reinterpret_cast<const d2_t*>(a.r)[i]; }
+    }
+    __syncthreads();
+    if (live) {
+        const int c0 = t - aa;                                // first lane of this row's block
+        d2_t v = sv[c0];
+        z.x = b[0] * v.x; z.y = b[0] * v.y;
+#pragma unroll
+        for (int j = 1; j < 8; ++j)
+            if (j < m) {
+                v = sv[c0 + j];
+                z.x = z.x + b[j] * v.x;
+                z.y = z.y + b[j] * v.y;
+            }
+    }
+    bj_dots_finish<MODE>(a, i, live, own, z, pv, rv);
+}
+
+template <int BS>
+void launch_dots(hipStream_t st, int mode, const BjDotsArgs& a, const double* blk) {
+    const dim3 grid(bj_grid(a.n, BS)), block(kBjBlock);
+    if (mode == kBjDotsNu) hipLaunchKernelGGL((k_block_jacobi_dots<BS, kBjDotsNu>), grid, block, 0, st, a, blk);
+    else hipLaunchKernelGGL((k_block_jacobi_dots<BS, kBjDotsPr>), grid, block, 0, st, a, blk);
+}
+
 }  // namespace
+
+int64_t block_jacobi_tiles(int64_t n, int bs) { return (bs < 1 || bs > 8 || n <= 0) ? 0 : bj_grid(n, bs); }
+
+int launch_block_jacobi_dots(hipStream_t st, int mode, const BjDotsArgs& a, int bs, const double* blocks) {
+    if (a.n <= 0 || (mode != kBjDotsNu && mode != kBjDotsPr)) return -1;
+    switch (bs) {
+    case 1: launch_dots<1>(st, mode, a, blocks); break;
+    case 2: launch_dots<2>(st, mode, a, blocks); break;
+    case 3: launch_dots<3>(st, mode, a, blocks); break;
+    case 4: launch_dots<4>(st, mode, a, blocks); break;
+    case 5: launch_dots<5>(st, mode, a, blocks); break;
+    case 6: launch_dots<6>(st, mode, a, blocks); break;
+    case 7: launch_dots<7>(st, mode, a, blocks); break;
+    case 8: launch_dots<8>(st, mode, a, blocks); break;
+    default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? bj_grid(a.n, bs) : -1;
+}
+
+int launch_block_jacobi_var_dots(hipStream_t st, int mode, const BjDotsArgs& a, int64_t ntiles, const long long* tiles,
+                                 const unsigned char* code, const double* blocks) {
+    if (ntiles <= 0 || (mode != kBjDotsNu && mode != kBjDotsPr)) return -1;
+    const dim3 grid((unsigned)ntiles), block(kBjBlock);
+    if (mode == kBjDotsNu) hipLaunchKernelGGL(k_block_jacobi_var_dots<kBjDotsNu>, grid, block, 0, st, a, tiles, code, blocks);
+    else hipLaunchKernelGGL(k_block_jacobi_var_dots<kBjDotsPr>, grid, block, 0, st, a, tiles, code, blocks);
+    return hipGetLastError() == hipSuccess ? (int)ntiles : -1;
+}
 
 int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t ntiles, const long long* tiles,
                             const unsigned char* code, const double* blocks) {

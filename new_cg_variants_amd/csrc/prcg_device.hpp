@@ -119,6 +119,27 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NQ], double* pa
     }
 }
 
+// block_reduce_store for two columns: acc = (column 0's NQ sums, column 1's NQ sums) -> part[c][block][slot0 + q]
+template <int NQ>
+__device__ __forceinline__ void block_reduce_store2(double (&acc)[2 * NQ], double* part0, double* part1, int slot0) {
+    __shared__ double red[kWaves][2 * NQ];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 2 * NQ; ++q) {
+        const double v = wave_sum(acc[q]);
+        if (lane == 0) red[wv][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * NQ) {
+        double v = red[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) v += red[w][threadIdx.x];
+        double* part = threadIdx.x < NQ ? part0 : part1;
+        const int q = threadIdx.x < NQ ? threadIdx.x : threadIdx.x - NQ;
+        part[(size_t)blockIdx.x * kPartialStride + slot0 + q] = v;
+    }
+}
+
 // Every block of a launch sums the block partials the PREVIOUS launch left (slots slot0 .. slot0 + NQ) itself, in
 // the order of k_reduce_final (a 256-thread tree: thread v rows v, v + 256, ...; butterfly over each 64 lanes; the
 // four wave sums in order) whatever the block's own size: a block of NWAVES < 4 waves lets each thread play

@@ -144,6 +144,8 @@ struct Session {
     bool pipe2 = false;          // session type "pipelined predict-and-recompute, two right-hand sides" (prcg_solve_begin_multi_pipe):
                                  // rhs2 with one group, variant PRCG_PIPE_PR / PRCG_PIPE_PR_M, per column the pair arrays cxp, crs, cwu
                                  // (crst) around ONE product of four vectors (spmm4: in one launch); two scalar / coefficient rows per iteration
+    int bj_tiles = 0;            // two or four right-hand sides with block Jacobi (prcg_solve_begin_multi_block_jacobi: rhs2 && bj_session): the
+                                 // tiles of a block launch = the partial rows each of Handle::bjpart holds
     // ---- schedule ----
     bool fused = false;          // pipelined: the one-launch-per-iteration kernel
     bool fused_comm = false;     // ... with a communicator: the interior launch waits in-kernel for the reduction
@@ -245,6 +247,8 @@ struct Handle : Operator, Session {
     PairBufs grp[2];             // two right-hand sides: grp[0]; four: grp[1] is the SECOND pair group (columns 2, 3).  Hestenes-Stiefel: dots /
                                  // coef hold both columns per row; predict-and-recompute: one row per column and iteration
     DevBuf partA1, partB1;       // ... the second group's block partials (the first group's: partA / partB)
+    DevBuf bjpart[2][2];         // ... with block Jacobi: the partial rows of group g's block launches (k_block_jacobi_dots: one per TILE, about
+                                 // n / 255 -- more than partA's 8192 at large n), column c in bjpart[g][c] (Hestenes-Stiefel: both in [g][0])
     DevBuf x4b, y4b;             // prcg_spmm4: the second source / destination pair array (the first: tmp_ext / t1)
     DevBuf cxp[2], crs[2], cwu[2], crst[2];   // pipelined, two right-hand sides: column c's pairs (x,p), (r,s), (w,u) and with Jacobi (r~,s~) (Pipe2Args)
     DevBuf pub, pub_err;         // publication record of the reduced inner products / timeout flag

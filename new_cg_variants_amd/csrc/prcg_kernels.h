@@ -443,6 +443,9 @@ struct Pr2Args {
     int meurant;
 };
 int launch_pr2_update(hipStream_t st, const Pr2Args& a);      // x, r, (rt), p; partials nu_c (slot 3), rr_c (4) of part[c]
+// ... with r~ and s~ STORED vectors whatever `d` says (a.d is not read): r~ -= a s~ from rt, st.  The same kernel instantiation as
+// launch_pr2_update with a diagonal; the block-Jacobi session selects it without one
+int launch_pr2_update_stored(hipStream_t st, const Pr2Args& a);
 int launch_pr2_init_dots(hipStream_t st, const Pr2Args& a);   // ... of the initial state: no update, (rt = d r)
 int launch_pr2_dots(hipStream_t st, const Pr2Args& a);        // (st = d s); partials mu_c, dl_c, gm_c (slots 0..2) of part[c]
 
@@ -485,6 +488,12 @@ int launch_gv_update1(hipStream_t st, const CgArgs& a, bool dots_only);   // x,r
 // out[dst_first..+count) = fixed-order sum over blocks b of partials[b][src_first..+count)
 void launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
                          int src_first, int dst_first, int count);
+// up to kMaxReduceJobs such reductions in ONE launch, one workgroup each: job j's result carries the bits of launch_reduce_final
+// with its arguments (the same tree by the same code)
+constexpr int kMaxReduceJobs = 4;
+struct ReduceJob { const double* partials; int nparts; double* out; int src_first, dst_first, count; };
+struct ReduceJobs { ReduceJob job[kMaxReduceJobs]; };
+void launch_reduce_final_jobs(hipStream_t st, const ReduceJobs& jobs, int njobs);
 // The stop form (single sessions with a threshold: FusedPrev::word): out[0..5) = the five sums of slots 0..5 -- the same kernel
 // code, the same tree, the same bits -- then the rule of SmallStop on {mu, nu, rr} = out[0], out[3], out[4], which are the scalars
 // of iteration k: a stop is recorded as {k, status} in stop.word.  If the word is already set the launch returns at once and
@@ -518,6 +527,24 @@ int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const doub
                             const unsigned char* code, const double* blocks);
 int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
                                  const unsigned char* code, const double* blocks, int mask);
+// ---- M^-1 on an interleaved n x 2 array with the inner products that need the result, in ONE launch (block-Jacobi sessions with
+// two or four right-hand sides: prcg_solve_begin_multi_block_jacobi).  v: the source pairs (NU: r; PR: s), z: the result (r~ / s~);
+// p, r: read by PR only.  One partial row per TILE (a tile: 256 - 256 % bs rows, or a tile of the partition's table): part0 / part1
+// hold block_jacobi_tiles(n, bs) (the partition's ntiles) rows of kPartialStride doubles.
+//   kBjDotsNu: nu_c = r_c.z_c, rr_c = r_c.r_c -- part1 null: [nu_0 rr_0 nu_1 rr_1] in slots 3..6 of part0 (the Hs2Args scalar row);
+//              else column c's two sums in slots 3, 4 of part[c] (the Pr2Args slots)
+//   kBjDotsPr: mu_c = p_c.s_c, dl_c = r_c.z_c, gm_c = z_c.s_c in slots 0..2 of part[c]
+// The launchers return the grid (= the number of partial rows written), -1 on failure.
+enum { kBjDotsNu = 0, kBjDotsPr = 1 };
+struct BjDotsArgs {
+    int64_t n;
+    const double* v; double* z; const double* p; const double* r;
+    double* part0; double* part1;
+};
+int64_t block_jacobi_tiles(int64_t n, int bs);
+int launch_block_jacobi_dots(hipStream_t st, int mode, const BjDotsArgs& a, int bs, const double* blocks);
+int launch_block_jacobi_var_dots(hipStream_t st, int mode, const BjDotsArgs& a, int64_t ntiles, const long long* tiles,
+                                 const unsigned char* code, const double* blocks);
 // gather, invert, store: every double of the layout is written; *first_bad as in launch_block_jacobi_build
 int launch_block_jacobi_var_build(hipStream_t st, double* blocks, int64_t ntiles, const long long* tiles, const unsigned char* code,
                                   const unsigned char* bidx, const int* indptr, const int* col, const double* val, long long* first_bad);

@@ -636,6 +636,18 @@ __global__ __launch_bounds__(kBlock) void k_gv_update1(CgArgs a, int trips) {
 constexpr int kFinalThreads = 256;   // same tree as the fused last-block reduction
 // the tree up to the four wave sums of every slot (red), complete behind the barrier; slot q's total is red[0][q] + red[1][q] +
 // red[2][q] + red[3][q], added in that order by whoever needs it
+// (the part of the tree behind a thread's own rows: butterfly per wave, the wave sums parked in red, the barrier -- shared by
+// every walk over the rows, so that none of them can drift from the others)
+__device__ __forceinline__ void reduce_final_wave_sums(const double (&acc)[kPartialStride], double (&red)[kFinalThreads / 64][kPartialStride])
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < kPartialStride; ++q) {
+        const double v = wave_sum(acc[q]);
+        if (lane == 0) red[wv][q] = v;
+    }
+    __syncthreads();
+}
 __device__ __forceinline__ void reduce_final_waves(const double* __restrict__ partials, int nparts, int src_first, int count,
                                                    double (&red)[kFinalThreads / 64][kPartialStride])
 {
@@ -647,13 +659,7 @@ __device__ __forceinline__ void reduce_final_waves(const double* __restrict__ pa
         for (int q = 0; q < kPartialStride; ++q)
             if (q < count) acc[q] += partials[(size_t)j * kPartialStride + src_first + q];
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < kPartialStride; ++q) {
-        const double v = wave_sum(acc[q]);
-        if (lane == 0) red[wv][q] = v;
-    }
-    __syncthreads();
+    reduce_final_wave_sums(acc, red);
 }
 __device__ __forceinline__ double reduce_final_total(const double (&red)[kFinalThreads / 64][kPartialStride], int q) {
     double v = red[0][q];
@@ -667,6 +673,45 @@ __global__ __launch_bounds__(kFinalThreads) void k_reduce_final(
     __shared__ double red[kFinalThreads / 64][kPartialStride];
     reduce_final_waves(partials, nparts, src_first, count, red);
     if ((int)threadIdx.x < count) out[dst_first + threadIdx.x] = reduce_final_total(red, threadIdx.x);
+}
+// several independent reductions in one launch (launch_reduce_final_jobs): workgroup b is k_reduce_final with job b's arguments.
+// The jobs of the block-Jacobi multi-RHS sessions have one partial row per TILE (16 090 at n = 4.1 M: 63 rows per thread), and a
+// thread's rows are 256 rows apart, so the walk is a chain of load latencies.  Here a thread has the loads of kFinalBatch of its
+// rows in flight before it adds them -- the same rows, added in the same order into the same accumulators as reduce_final_waves
+// adds them (a row past the end is loaded from a clamped index and not added), then reduce_final_wave_sums and reduce_final_total,
+// the very code k_reduce_final runs: hence the same bits.
+constexpr int kFinalBatch = 8;
+__global__ __launch_bounds__(kFinalThreads) void k_reduce_final_jobs(ReduceJobs jobs)
+{
+    __shared__ double red[kFinalThreads / 64][kPartialStride];
+    ReduceJob j = jobs.job[0];
+#pragma unroll
+    for (int q = 1; q < kMaxReduceJobs; ++q)
+        if ((int)blockIdx.x == q) j = jobs.job[q];
+    const double* __restrict__ partials = j.partials;
+    double acc[kPartialStride];
+#pragma unroll
+    for (int q = 0; q < kPartialStride; ++q) acc[q] = 0.0;
+    for (int r0 = threadIdx.x; r0 < j.nparts; r0 += kFinalBatch * kFinalThreads) {
+        double v[kFinalBatch][kPartialStride];
+#pragma unroll
+        for (int u = 0; u < kFinalBatch; ++u) {
+            const int r = r0 + u * kFinalThreads;
+            const size_t rl = r < j.nparts ? r : r0;
+#pragma unroll
+            for (int q = 0; q < kPartialStride; ++q) v[u][q] = q < j.count ? partials[rl * kPartialStride + j.src_first + q] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < kFinalBatch; ++u) {
+            if (r0 + u * kFinalThreads < j.nparts) {
+#pragma unroll
+                for (int q = 0; q < kPartialStride; ++q)
+                    if (q < j.count) acc[q] += v[u][q];
+            }
+        }
+    }
+    reduce_final_wave_sums(acc, red);
+    if ((int)threadIdx.x < j.count) j.out[j.dst_first + threadIdx.x] = reduce_final_total(red, threadIdx.x);
 }
 // The stop form (launch_reduce_final_stop, prcg_kernels.h): the five sums of a pipelined iteration by the code above, then the
 // rule on them.  The word is tested first: it was complete before this launch began (only a launch's end or this kernel's thread 0
@@ -1076,6 +1121,11 @@ void launch_reduce_final_stop(hipStream_t st, const double* partials, int nparts
 void launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
                          int src_first, int dst_first, int count) {
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, out, src_first, dst_first, count);
+}
+
+void launch_reduce_final_jobs(hipStream_t st, const ReduceJobs& jobs, int njobs) {
+    if (njobs < 1 || njobs > kMaxReduceJobs) return;
+    hipLaunchKernelGGL(k_reduce_final_jobs, dim3(njobs), dim3(kFinalThreads), 0, st, jobs);
 }
 
 void launch_copy(hipStream_t st, double* dst, int ds, const double* src, int ss, int64_t n) {

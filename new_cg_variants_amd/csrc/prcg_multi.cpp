@@ -1,5 +1,6 @@
 // Sessions with two or four right-hand sides: prcg_solve_begin_multi (Hestenes-Stiefel, predict-and-recompute),
-// prcg_solve_begin_multi_pipe (pipelined predict-and-recompute), their iterations (iterate_multi, called by prcg_iterate)
+// prcg_solve_begin_multi_pipe (pipelined predict-and-recompute), prcg_solve_begin_multi_block_jacobi (Hestenes-Stiefel and
+// predict-and-recompute preconditioned by the handle's point-block Jacobi), their iterations (iterate_multi, called by prcg_iterate)
 // and the per-column getters.  Built from the services of prcg_engine.cpp and open_session (prcg_handle.h); the kernels:
 // prcg_rhs2.hip.  Host code only.
 #include <hip/hip_runtime_api.h>
@@ -41,7 +42,7 @@ Hs2Args hs2_args(prcg_t* h, int k, int g) {
     Hs2Args a{};
     a.n = h->n;
     a.x = G.x.d(); a.r = G.r.d(); a.rt = h->prec ? G.rt.d() : nullptr; a.p = G.p.d(); a.s = G.s.d();
-    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.d = (h->prec && !h->bj_session) ? h->dinv.d() : nullptr;      // (block Jacobi: r~ is a stored vector, no diagonal)
     a.dots_prev = k > 0 ? dots_at(h, row0(h, g) + k - 1) : nullptr;
     a.dots_cur = dots_at(h, row0(h, g) + k);
     a.coef_out = coef_at(h, row0(h, g) + k);
@@ -83,7 +84,7 @@ Pr2Args pr2_args(prcg_t* h, int k, int g) {
     a.n = h->n;
     a.x = G.x.d(); a.r = G.r.d(); a.p = G.p.d(); a.s = G.s.d();
     a.rt = h->prec ? G.rt.d() : nullptr; a.st = h->prec ? G.st.d() : nullptr;
-    a.d = h->prec ? h->dinv.d() : nullptr;
+    a.d = (h->prec && !h->bj_session) ? h->dinv.d() : nullptr;      // (block Jacobi: r~, s~ are stored vectors, no diagonal)
     a.dots_prev = k > 0 ? dots_at(h, row0(h, g) + 2 * (k - 1)) : nullptr;   // rows 2 (k - 1), 2 (k - 1) + 1: the columns' sums of k - 1
     a.coef_out = coef_at(h, row0(h, g) + 2 * k);
     a.part0 = part_a(h, g); a.part1 = part_b(h, g);
@@ -117,6 +118,90 @@ int iterate_pr2(prcg_t* h, int k) {
         prof_end(h, h->ev_upd, h->n_ev_upd, on);
     }
     return pr2_product_and_sums(h, k, g_upd);
+}
+
+// ---- two or four right-hand sides preconditioned by the handle's point-block Jacobi (prcg_solve_begin_multi_block_jacobi) ----
+// The state and the scalar rows of the sessions above; r~ (and s~) are stored vectors, and M^-1 is ONE launch per group that
+// applies the blocks to both columns and leaves, in the same launch, the partials of the inner products that need the result
+// (prcg_blockjac.hip: k_block_jacobi_dots / k_block_jacobi_var_dots) -- one partial row per tile in the session's own arrays.
+//   Hestenes-Stiefel: update_xr (unpreconditioned: x, r) -> block NU (r~ = M^-1 r; nu, rr) -> reduce -> update_p -> product ->
+//                     dot_ps -> reduce                                                           (hs_cg.py:116-125 per column)
+//   PR / M:           update (r~ -= a s~ from the stored vectors) -> product -> block PR (s~ = M^-1 s; mu, dl, gm) -> ONE
+//                     reduction launch for both columns' five sums                               (pr_cg.py:146-158 per column)
+double* bj_part(prcg_t* h, int g, int c) { return h->bjpart[g][c].d(); }
+// one block launch of group g; the grid is checked against the partial rows the session allocated BEFORE anything is launched
+int bj2_launch(prcg_t* h, int mode, int g, bool two_arrays, const double* v, double* z) {
+    const PairBufs& G = h->grp[g];
+    const int64_t tiles = h->bj_var ? h->bjv_plan.ntiles : block_jacobi_tiles(h->n, h->bj_bs);
+    const size_t need = (size_t)tiles * kPartialStride * sizeof(double);
+    CHECK(h, tiles > 0 && tiles == h->bj_tiles && h->bjpart[g][0].bytes >= need && (!two_arrays || h->bjpart[g][1].bytes >= need),
+          "block-Jacobi multi-RHS session: a block launch of %lld tiles does not match the %d partial rows the session allocated",
+          (long long)tiles, h->bj_tiles);
+    BjDotsArgs a{};
+    a.n = h->n; a.v = v; a.z = z; a.p = G.p.d(); a.r = G.r.d();
+    a.part0 = bj_part(h, g, 0); a.part1 = two_arrays ? bj_part(h, g, 1) : nullptr;
+    const int grid = h->bj_var ? launch_block_jacobi_var_dots(h->sc, mode, a, tiles, h->bjv_tiles_d(), h->bjv_code_d(), h->bj_blocks.d())
+                               : launch_block_jacobi_dots(h->sc, mode, a, h->bj_bs, h->bj_blocks.d());
+    LAUNCHCHK(h, grid);
+    CHECK(h, grid == h->bj_tiles, "block-Jacobi multi-RHS session: a block launch ran %d workgroups, the session allocated %d partial rows",
+          grid, h->bj_tiles);
+    return PRCG_OK;
+}
+// Hestenes-Stiefel: r~ = M^-1 r, nu_c, rr_c of group g -> scalar row k
+int bj2_hs_nu(prcg_t* h, int k, int g) {
+    const PairBufs& G = h->grp[g];
+    if (int rc = bj2_launch(h, kBjDotsNu, g, false, G.r.d(), G.rt.d())) return rc;
+    ReduceJobs J{};                                             // (the final tree with a thread's loads batched: one row per tile)
+    J.job[0] = ReduceJob{bj_part(h, g, 0), h->bj_tiles, dots_at(h, row0(h, g) + k), kHs2Nu, kHs2Nu, 4};            // nu_0, rr_0, nu_1, rr_1
+    launch_reduce_final_jobs(h->sc, J, 1);
+    return PRCG_OK;
+}
+int iterate_bj_hs2(prcg_t* h, int k) {
+    for (int g = 0; g < h->groups; ++g) {
+        const Hs2Args a = hs2_args(h, k, g);                    // a.d null: x += a p, r -= a s only (its own partials of r.r stay unused)
+        bool on = false;
+        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
+        LAUNCHCHK(h, launch_hs2_update_xr(h->sc, a));
+        prof_end(h, h->ev_upd, h->n_ev_upd, on);
+        if (int rc = bj2_hs_nu(h, k, g)) return rc;
+        LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));            // p = r~ + b p (a.rt)
+    }
+    return hs2_product_and_mu(h, k);
+}
+// s = A p for every column; per group s~ = M^-1 s with mu, dl, gm; then the five sums of each column in one reduction launch: mu, dl,
+// gm from the tile partials, nu, rr from the update launch's (g_upd[g] blocks) -- at k = 0 from the tile partials too (block NU)
+int bj2_pr_product_and_sums(prcg_t* h, int k, const int* g_upd) {
+    int rc = multi_product(h, k);
+    if (rc) return rc;
+    for (int g = 0; g < h->groups; ++g) {
+        const PairBufs& G = h->grp[g];
+        if ((rc = bj2_launch(h, kBjDotsPr, g, true, G.s.d(), G.st.d()))) return rc;
+        const int row = row0(h, g) + 2 * k;
+        ReduceJobs J{};
+        int nj = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (g_upd) {
+                J.job[nj++] = ReduceJob{bj_part(h, g, c), h->bj_tiles, dots_at(h, row + c), kPr2Mu, kPr2Mu, 3};
+                J.job[nj++] = ReduceJob{c == 0 ? part_a(h, g) : part_b(h, g), g_upd[g], dots_at(h, row + c), kPr2Nu, kPr2Nu, 2};
+            } else {
+                J.job[nj++] = ReduceJob{bj_part(h, g, c), h->bj_tiles, dots_at(h, row + c), 0, 0, 5};
+            }
+        }
+        launch_reduce_final_jobs(h->sc, J, nj);
+    }
+    return PRCG_OK;
+}
+int iterate_bj_pr2(prcg_t* h, int k) {
+    int g_upd[2] = {0, 0};
+    for (int g = 0; g < h->groups; ++g) {
+        const Pr2Args a = pr2_args(h, k, g);
+        bool on = false;
+        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
+        g_upd[g] = launch_pr2_update_stored(h->sc, a);
+        LAUNCHCHK(h, g_upd[g]);
+        prof_end(h, h->ev_upd, h->n_ev_upd, on);
+    }
+    return bj2_pr_product_and_sums(h, k, g_upd);
 }
 
 // Two right-hand sides in one pipelined predict-and-recompute session (pipe_pr_cg.py:61-75 / :169-187 for each column; the
@@ -179,6 +264,7 @@ int refuse_unserved(prcg_t* h, const char* who, uint32_t hist_mask) {
 }  // namespace
 
 int prcg::iterate_multi(prcg_t* h, int k) {
+    if (h->bj_session) return pr2(h) ? iterate_bj_pr2(h, k) : iterate_bj_hs2(h, k);
     return h->pipe2 ? iterate_pipe2(h, k) : pr2(h) ? iterate_pr2(h, k) : iterate_hs2(h, k);
 }
 
@@ -302,6 +388,80 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     const int grid = launch_pipe2_dots(sc, pipe2_args(h, 0));                               // mu, delta, gamma, nu, r.r   :25-36 / :126-140
     LAUNCHCHK(h, grid);
     pipe2_reduce(h, 0, grid);
+    HIPCHK(h, hipStreamSynchronize(sc));
+    h->in_session = true;
+    return PRCG_OK;
+}
+
+// ---- two or four right-hand sides preconditioned by the point-block Jacobi in force on the handle ----
+int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const double* const* b, const double* const* x0, int max_iter,
+                                        uint32_t hist_mask) {
+    if (!h) return PRCG_EINVAL;
+    const char* const who = "prcg_solve_begin_multi_block_jacobi";
+    CHECK(h, h->have_csr, "%s: call prcg_set_csr first", who);
+    // (a handle with a communicator cannot hold blocks at all: these two come first so that each refusal names its own reason)
+    CHECK(h, !h->multi(), "%s: a communicator is set on the handle: the multi-RHS session runs on one GPU", who);
+    CHECK(h, h->g == 0, "%s: n_ghost = %lld > 0: the multi-RHS session serves whole operators only", who, (long long)h->g);
+    CHECK(h, h->have_block_jacobi(), "%s: no block-Jacobi preconditioner is set on the handle (prcg_set_block_jacobi, prcg_build_block_jacobi, "
+                                     "prcg_set_block_jacobi_var, prcg_build_block_jacobi_var; prcg_set_csr drops the blocks): without blocks "
+                                     "the session is prcg_solve_begin_multi", who);
+    CHECK(h, !is_pipe(variant), "%s: variant %d: the pipelined variants are not served with blocks (a follow-up: their session is "
+                                "prcg_solve_begin_multi_pipe, Jacobi or none); PRCG_HS, PRCG_PR and PRCG_M are", who, variant);
+    CHECK(h, variant == PRCG_HS || is_pr(variant), "%s: variant %d: the block-Jacobi multi-RHS session serves PRCG_HS (hs_pcg), PRCG_PR (pr_pcg) "
+                                                   "and PRCG_M (m_pcg) only", who, variant);
+    CHECK(h, nrhs == 2 || nrhs == 4, "%s: nrhs = %d: the session serves exactly 2 right-hand sides (or 4, as two pairs)", who, nrhs);
+    CHECK(h, h->replace_fn == nullptr, "%s: a replace hook is set (prcg_set_replace_hook): not served by the multi-RHS session", who);
+    CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
+          "%s: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the multi-RHS session", who);
+    bool have_all = b && x0;
+    for (int j = 0; have_all && j < nrhs; ++j) have_all = b[j] && x0[j];
+    CHECK(h, have_all, "%s: null b or x0", who);
+    CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
+    const int64_t n = h->n, ne = h->n + kGatherPad;
+    const size_t D = sizeof(double);
+    const int groups = nrhs / 2;
+    const bool pr = is_pr(variant);
+    const int64_t tiles = h->bj_var ? h->bjv_plan.ntiles : block_jacobi_tiles(n, h->bj_bs);
+    CHECK(h, tiles > 0 && tiles <= INT32_MAX, "%s: the blocks on the handle give %lld tiles", who, (long long)tiles);
+    // X and P feed the product (spare entries behind row n); r~ and, for PR / M, s~ are stored vectors of full size.  bjp: one partial
+    // row per tile of a block launch; part: the update launch's block partials of the second group (PR / M: nu, rr)
+    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D, bjp = (size_t)tiles * kPartialStride * D,
+                 part = (size_t)8192 * kPartialStride * D;
+    PairBufs* const G = h->grp;
+    int rc;
+    if (groups == 1)
+        rc = open_session(h, who, variant, max_iter, hist_mask, nullptr, false,
+                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, vec}, {&G[0].st, pr ? vec : 16},
+                           {&h->bjpart[0][0], bjp}, {&h->bjpart[0][1], pr ? bjp : 16}}, pr ? 2 : 1);
+    else
+        rc = open_session(h, who, variant, max_iter, hist_mask, nullptr, false,
+                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, vec}, {&G[0].st, pr ? vec : 16},
+                           {&G[1].x, src}, {&G[1].p, src}, {&G[1].r, vec}, {&G[1].s, vec}, {&G[1].rt, vec}, {&G[1].st, pr ? vec : 16},
+                           {&h->partA1, part}, {&h->partB1, part}, {&h->bjpart[0][0], bjp}, {&h->bjpart[0][1], pr ? bjp : 16},
+                           {&h->bjpart[1][0], bjp}, {&h->bjpart[1][1], pr ? bjp : 16}}, (pr ? 2 : 1) * 2);
+    if (rc) return rc;
+    CHECK(h, h->bj_session, "%s: the session did not open with the handle's blocks", who);
+    h->rhs2 = true;
+    h->groups = groups;
+    h->spmm4 = groups == 2 && spmm4_one_launch(h);
+    h->bj_tiles = (int)tiles;
+    for (int g = 0; g < groups; ++g) {
+        if ((rc = upload_pairs(h, who, G[g].x.d(), x0[2 * g], x0[2 * g + 1]))) return rc;
+        if ((rc = upload_pairs(h, who, G[g].r.d(), b[2 * g], b[2 * g + 1]))) return rc;
+    }
+    hipStream_t sc = h->sc;
+    // r = b - A x0 for every column: one product of [x0_0 x0_1] (| [x0_2 x0_3]), parked in S
+    if (groups == 2) LAUNCHCHK(h, eng_spmm4(h, sc, 0, G[0].x.d(), G[1].x.d(), G[0].s.d(), G[1].s.d()));
+    else LAUNCHCHK(h, eng_spmm2(h, sc, 0, G[0].x.d(), G[0].s.d(), 3));
+    for (int g = 0; g < groups; ++g) launch_sub(sc, G[g].r.d(), 1, G[g].r.d(), 1, G[g].s.d(), 1, 2 * n);
+    for (int g = 0; g < groups; ++g) {
+        // r~ = M^-1 r; nu = r~.r, r.r   (hs_cg.py:86-88 / pr_cg.py:107-109); p = r~
+        if (pr) { if ((rc = bj2_launch(h, kBjDotsNu, g, true, G[g].r.d(), G[g].rt.d()))) return rc; }
+        else if ((rc = bj2_hs_nu(h, 0, g))) return rc;
+        launch_copy(sc, G[g].p.d(), 1, G[g].rt.d(), 1, 2 * n);
+    }
+    // s = A p; Hestenes-Stiefel: mu = p.s; PR / M: s~ = M^-1 s, mu, dl, gm and the five sums of row 0
+    if ((rc = pr ? bj2_pr_product_and_sums(h, 0, nullptr) : hs2_product_and_mu(h, 0))) return rc;
     HIPCHK(h, hipStreamSynchronize(sc));
     h->in_session = true;
     return PRCG_OK;

@@ -150,27 +150,6 @@ __global__ __launch_bounds__(kBlock) void k_hs2_dot_ps(Hs2Args a, int trips) {
 // so predict() serves each column as it serves a single session; the block partials of column c go to part[c] in the
 // same slots (the update fills 3..4, the dots kernel 0..2) and one launch_reduce_final per column sums all five.
 
-// block_reduce_store for two columns: acc = (column 0's NQ sums, column 1's NQ sums) -> part[c][block][slot0 + q]
-template <int NQ>
-__device__ __forceinline__ void block_reduce_store2(double (&acc)[2 * NQ], double* part0, double* part1, int slot0) {
-    __shared__ double red[kWaves][2 * NQ];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 2 * NQ; ++q) {
-        const double v = wave_sum(acc[q]);
-        if (lane == 0) red[wv][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * NQ) {
-        double v = red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v += red[w][threadIdx.x];
-        double* part = threadIdx.x < NQ ? part0 : part1;
-        const int q = threadIdx.x < NQ ? threadIdx.x : threadIdx.x - NQ;
-        part[(size_t)blockIdx.x * kPartialStride + slot0 + q] = v;
-    }
-}
-
 // (a_c, b_c) = predict(column c's sums of k - 1); x += a p; r -= a s; r~ -= a s~ (without Jacobi r~ IS the new r);
 // p = r~ + b p; partials of nu_c = r~.r and rr_c = r.r   (pr_cg.py:146-151, :157)
 // DOTS_ONLY, the initial state: (r~ = d r); nu_c, rr_c   (:107-109)
@@ -421,6 +400,11 @@ int launch_pr2_update(hipStream_t st, const Pr2Args& a) {
     const Chunking c = chunking(a.n);
     if (a.d) hipLaunchKernelGGL((k_pr2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     else     hipLaunchKernelGGL((k_pr2_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_pr2_update_stored(hipStream_t st, const Pr2Args& a) {
+    const Chunking c = chunking(a.n);
+    hipLaunchKernelGGL((k_pr2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 int launch_pr2_init_dots(hipStream_t st, const Pr2Args& a) {

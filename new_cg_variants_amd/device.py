@@ -363,6 +363,17 @@ class DeviceCSR:
         else:
             self._prec_fn = None
             self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
+        self._put_blocks(block_jacobi, block_jacobi_var)
+        thr = None if rr_stop is None else np.array([rr_stop], dtype=np.float64)
+        self._check(self._lib.prcg_set_stop(self._h, L.ptr(thr)))            # (None clears what an earlier session set)
+        self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
+                                               L.ptr(xt), L.ptr(dv), int(hist_mask)))
+        self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
+
+    def _put_blocks(self, block_jacobi, block_jacobi_var):
+        """The blocks a session asks for, put in force on the handle (begin, begin_multi_block_jacobi): (bs, inv_blocks) or
+        (block_ptr, inv_blocks_packed) are set; inv_blocks None means BUILT on the device, rebuilt only when blocks of that bs /
+        partition built from the current values are not in force already; neither: whatever blocks are set are removed."""
         if block_jacobi is not None and block_jacobi[1] is None:
             if self._bj_built is None or self._bj_built != int(block_jacobi[0]):
                 self.build_block_jacobi(int(block_jacobi[0]))
@@ -376,11 +387,6 @@ class DeviceCSR:
             self.set_block_jacobi_var(block_jacobi_var[0], block_jacobi_var[1])
         else:
             self.set_block_jacobi(0, None)
-        thr = None if rr_stop is None else np.array([rr_stop], dtype=np.float64)
-        self._check(self._lib.prcg_set_stop(self._h, L.ptr(thr)))            # (None clears what an earlier session set)
-        self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
-                                               L.ptr(xt), L.ptr(dv), int(hist_mask)))
-        self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def clear_preconditioners(self):
         """Remove a host-callback or block-Jacobi preconditioner an earlier session set on this handle."""
@@ -405,6 +411,29 @@ class DeviceCSR:
         bp = (C.c_void_p * nrhs)(*[B[j].ctypes.data for j in range(nrhs)])
         xp = (C.c_void_p * nrhs)(*[X0[j].ctypes.data for j in range(nrhs)])
         self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), nrhs, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
+        self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
+
+    def begin_multi_block_jacobi(self, variant, B, X0, max_iter, block_jacobi=None, block_jacobi_var=None, hist_mask=0):
+        """Two or four right-hand sides in ONE session preconditioned by point-block Jacobi on the device (prcg.h:
+        prcg_solve_begin_multi_block_jacobi): B, X0 of shape (2, n) or (4, n).  variant: L.HS (hs_pcg), L.PR (pr_pcg) or L.M (m_pcg).
+        Exactly one of block_jacobi=(bs, inv_blocks) / (bs, None) and block_jacobi_var=(block_ptr, inv_blocks_packed) /
+        (block_ptr, None), with the conventions of begin: None means built on the device from the operator's current values,
+        rebuilt only if such blocks are not in force already.  hist_mask: 0 or updated_residual_2_norm.
+        Every iteration streams the operator once for all systems and reads every block once per pair of systems.  iterate /
+        sync / k serve the session as they are; state is read per column: get_vector(name, rhs=j) (x, r, p, s, rt; PR / M: st),
+        get_scalars(k, rhs=j), get_coefficients(k, rhs=j), history(rhs=j).  The blocks stay on the handle afterwards."""
+        B = _pair_of_vectors('B', B, self.n)
+        X0 = _pair_of_vectors('X0', X0, self.n, nrhs=B.shape[0])
+        nrhs = B.shape[0]
+        if (block_jacobi is None) == (block_jacobi_var is None):
+            raise ValueError('begin_multi_block_jacobi: exactly one of block_jacobi= and block_jacobi_var= must be given '
+                             '(without blocks the session is begin_multi)')
+        self._prec_fn = None
+        self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
+        self._put_blocks(block_jacobi, block_jacobi_var)
+        bp = (C.c_void_p * nrhs)(*[B[j].ctypes.data for j in range(nrhs)])
+        xp = (C.c_void_p * nrhs)(*[X0[j].ctypes.data for j in range(nrhs)])
+        self._check(self._lib.prcg_solve_begin_multi_block_jacobi(self._h, int(variant), nrhs, bp, xp, int(max_iter), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def begin_multi_pipe(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
@@ -516,7 +545,8 @@ class DeviceCSR:
 
     def get_vector(self, name, *, rhs=None):
         """rhs=j: column j of a two- or four-RHS session (begin_multi): x, r, p, s; with Jacobi rt, and in an L.PR / L.M session st.
-        In a pipelined two-RHS session (begin_multi_pipe) also w and u, and with Jacobi rt and st."""
+        In a pipelined two-RHS session (begin_multi_pipe) also w and u, and with Jacobi rt and st.  In a block-Jacobi session
+        (begin_multi_block_jacobi) x, r, p, s, rt, and for L.PR / L.M st."""
         out = np.empty(self.n)
         if rhs is None:
             self._check(self._lib.prcg_get_vector(self._h, L.VEC[name], L.ptr(out)))
