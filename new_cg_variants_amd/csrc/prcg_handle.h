@@ -401,6 +401,10 @@ int place_session_vectors(prcg_t* h, size_t xp_bytes, size_t rs_bytes);
 // ---- prcg_session.cpp: every session, whichever file begins it, is opened here ----
 int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
                  std::initializer_list<Lead> lead, int rows_per_iteration = 1);
+// ... with a list made at run time (prcg_multi.cpp: open_pairs).  Hidden: the library exports the symbols it always did
+__attribute__((visibility("hidden")))
+int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
+                 const Lead* lead, size_t count, int rows_per_iteration);
 
 // ---- prcg_multi.cpp: iteration k of the open session with two or four right-hand sides (Session::rhs2) ----
 int iterate_multi(prcg_t* h, int k);

@@ -1,8 +1,10 @@
 // Sessions with two or four right-hand sides: prcg_solve_begin_multi (Hestenes-Stiefel, predict-and-recompute),
 // prcg_solve_begin_multi_pipe (pipelined predict-and-recompute), prcg_solve_begin_multi_block_jacobi (Hestenes-Stiefel and
 // predict-and-recompute preconditioned by the handle's point-block Jacobi), their iterations (iterate_multi, called by prcg_iterate)
-// and the per-column getters.  Built from the services of prcg_engine.cpp and open_session (prcg_handle.h); the kernels:
-// prcg_rhs2.hip.  Host code only.
+// and the per-column getters.  The first and the last entry are their argument checks around open_pairs and start_pairs, the
+// ONE way a session of pair groups is opened and started; with blocks the iterations branch at one step (h->bj_session).  The
+// pipelined session has a state layout of its own.  Built from the services of prcg_engine.cpp and open_session
+// (prcg_handle.h); the kernels: prcg_rhs2.hip, prcg_blockjac.hip.  Host code only.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -37,6 +39,47 @@ int multi_product(prcg_t* h, int k) {
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     return PRCG_OK;
 }
+
+// ---- the same sessions preconditioned by the handle's point-block Jacobi (prcg_solve_begin_multi_block_jacobi: h->bj_session) ----
+// The state and the scalar rows are those above; r~ (and s~) are stored vectors, and M^-1 is ONE launch per group that
+// applies the blocks to both columns and leaves, in the same launch, the partials of the inner products that need the result
+// (prcg_blockjac.hip: k_block_jacobi_dots / k_block_jacobi_var_dots) -- one partial row per tile in the session's own arrays.
+// The iterations below branch on h->bj_session at the one step that differs:
+//   Hestenes-Stiefel: update_xr (unpreconditioned: x, r) -> block NU (r~ = M^-1 r; nu, rr) -> reduce -> update_p -> product ->
+//                     dot_ps -> reduce                                                           (hs_cg.py:116-125 per column)
+//   PR / M:           update (r~ -= a s~ from the stored vectors) -> product -> block PR (s~ = M^-1 s; mu, dl, gm) -> ONE
+//                     reduction launch for both columns' five sums                               (pr_cg.py:146-158 per column)
+double* bj_part(prcg_t* h, int g, int c) { return h->bjpart[g][c].d(); }
+// the tiles of a block launch with the blocks on the handle = the partial rows a session allocates (0: the blocks give none)
+int64_t bj_tile_count(const prcg_t* h) { return h->bj_var ? h->bjv_plan.ntiles : block_jacobi_tiles(h->n, h->bj_bs); }
+// one block launch of group g; the grid is checked against the partial rows the session allocated BEFORE anything is launched
+int bj2_launch(prcg_t* h, int mode, int g, bool two_arrays, const double* v, double* z) {
+    const PairBufs& G = h->grp[g];
+    const int64_t tiles = bj_tile_count(h);
+    const size_t need = (size_t)tiles * kPartialStride * sizeof(double);
+    CHECK(h, tiles > 0 && tiles == h->bj_tiles && h->bjpart[g][0].bytes >= need && (!two_arrays || h->bjpart[g][1].bytes >= need),
+          "block-Jacobi multi-RHS session: a block launch of %lld tiles does not match the %d partial rows the session allocated",
+          (long long)tiles, h->bj_tiles);
+    BjDotsArgs a{};
+    a.n = h->n; a.v = v; a.z = z; a.p = G.p.d(); a.r = G.r.d();
+    a.part0 = bj_part(h, g, 0); a.part1 = two_arrays ? bj_part(h, g, 1) : nullptr;
+    const int grid = h->bj_var ? launch_block_jacobi_var_dots(h->sc, mode, a, tiles, h->bjv_tiles_d(), h->bjv_code_d(), h->bj_blocks.d())
+                               : launch_block_jacobi_dots(h->sc, mode, a, h->bj_bs, h->bj_blocks.d());
+    LAUNCHCHK(h, grid);
+    CHECK(h, grid == h->bj_tiles, "block-Jacobi multi-RHS session: a block launch ran %d workgroups, the session allocated %d partial rows",
+          grid, h->bj_tiles);
+    return PRCG_OK;
+}
+// Hestenes-Stiefel: r~ = M^-1 r, nu_c, rr_c of group g -> scalar row k
+int bj2_hs_nu(prcg_t* h, int k, int g) {
+    const PairBufs& G = h->grp[g];
+    if (int rc = bj2_launch(h, kBjDotsNu, g, false, G.r.d(), G.rt.d())) return rc;
+    ReduceJobs J{};                                             // (the final tree with a thread's loads batched: one row per tile)
+    J.job[0] = ReduceJob{bj_part(h, g, 0), h->bj_tiles, dots_at(h, row0(h, g) + k), kHs2Nu, kHs2Nu, 4};            // nu_0, rr_0, nu_1, rr_1
+    launch_reduce_final_jobs(h->sc, J, 1);
+    return PRCG_OK;
+}
+
 Hs2Args hs2_args(prcg_t* h, int k, int g) {
     const PairBufs& G = h->grp[g];
     Hs2Args a{};
@@ -70,8 +113,11 @@ int iterate_hs2(prcg_t* h, int k) {
         const int g1 = launch_hs2_update_xr(h->sc, a);
         LAUNCHCHK(h, g1);
         prof_end(h, h->ev_upd, h->n_ev_upd, on);
-        launch_reduce_final(h->sc, a.partials, g1, dots_at(h, row0(h, g) + k), kHs2Nu, kHs2Nu, 4);     // nu_0, rr_0, nu_1, rr_1
-        LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));
+        // nu_0, rr_0, nu_1, rr_1.  Blocks: a.d is null, so the update moved x and r only (its own partials of r.r stay unused) and
+        // the block launch leaves r~ and the sums; else the update's partials hold them
+        if (h->bj_session) { if (int rc = bj2_hs_nu(h, k, g)) return rc; }
+        else launch_reduce_final(h->sc, a.partials, g1, dots_at(h, row0(h, g) + k), kHs2Nu, kHs2Nu, 4);
+        LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));            // p = r~ + b p
     }
     return hs2_product_and_mu(h, k);
 }
@@ -91,12 +137,35 @@ Pr2Args pr2_args(prcg_t* h, int k, int g) {
     a.meurant = meurant(h->variant);
     return a;
 }
+// Blocks.  Per group s~ = M^-1 s with mu, dl, gm; then the five sums of each column in one reduction launch: mu, dl, gm from the
+// tile partials, nu, rr from the update launch's (g_upd[g] blocks) -- at the start (g_upd null) from the tile partials too (block NU)
+int bj2_pr_sums(prcg_t* h, int k, int g, const int* g_upd) {
+    const PairBufs& G = h->grp[g];
+    if (int rc = bj2_launch(h, kBjDotsPr, g, true, G.s.d(), G.st.d())) return rc;
+    const int row = row0(h, g) + 2 * k;
+    ReduceJobs J{};
+    int nj = 0;
+    for (int c = 0; c < 2; ++c) {
+        if (g_upd) {
+            J.job[nj++] = ReduceJob{bj_part(h, g, c), h->bj_tiles, dots_at(h, row + c), kPr2Mu, kPr2Mu, 3};
+            J.job[nj++] = ReduceJob{c == 0 ? part_a(h, g) : part_b(h, g), g_upd[g], dots_at(h, row + c), kPr2Nu, kPr2Nu, 2};
+        } else {
+            J.job[nj++] = ReduceJob{bj_part(h, g, c), h->bj_tiles, dots_at(h, row + c), 0, 0, 5};
+        }
+    }
+    launch_reduce_final_jobs(h->sc, J, nj);
+    return PRCG_OK;
+}
 // s = A p for every column, (s~ = d s), mu, dl, gm; then the five sums of each column: rows 2 k and 2 k + 1 of its group
 // (g_upd[g]: the grid of group g's update launch, whose partials the sums include)
 int pr2_product_and_sums(prcg_t* h, int k, const int* g_upd) {
     int rc = multi_product(h, k);
     if (rc) return rc;
     for (int g = 0; g < h->groups; ++g) {
+        if (h->bj_session) {
+            if ((rc = bj2_pr_sums(h, k, g, g_upd))) return rc;
+            continue;
+        }
         const Pr2Args a = pr2_args(h, k, g);
         const int grid = launch_pr2_dots(h->sc, a);
         LAUNCHCHK(h, grid);
@@ -113,95 +182,12 @@ int iterate_pr2(prcg_t* h, int k) {
         const Pr2Args a = pr2_args(h, k, g);
         bool on = false;
         if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);             // (the sample: the first group's update launch)
-        g_upd[g] = launch_pr2_update(h->sc, a);
+        // (blocks: r~ -= a s~ from the stored vectors, no diagonal)
+        g_upd[g] = h->bj_session ? launch_pr2_update_stored(h->sc, a) : launch_pr2_update(h->sc, a);
         LAUNCHCHK(h, g_upd[g]);
         prof_end(h, h->ev_upd, h->n_ev_upd, on);
     }
     return pr2_product_and_sums(h, k, g_upd);
-}
-
-// ---- two or four right-hand sides preconditioned by the handle's point-block Jacobi (prcg_solve_begin_multi_block_jacobi) ----
-// The state and the scalar rows of the sessions above; r~ (and s~) are stored vectors, and M^-1 is ONE launch per group that
-// applies the blocks to both columns and leaves, in the same launch, the partials of the inner products that need the result
-// (prcg_blockjac.hip: k_block_jacobi_dots / k_block_jacobi_var_dots) -- one partial row per tile in the session's own arrays.
-//   Hestenes-Stiefel: update_xr (unpreconditioned: x, r) -> block NU (r~ = M^-1 r; nu, rr) -> reduce -> update_p -> product ->
-//                     dot_ps -> reduce                                                           (hs_cg.py:116-125 per column)
-//   PR / M:           update (r~ -= a s~ from the stored vectors) -> product -> block PR (s~ = M^-1 s; mu, dl, gm) -> ONE
-//                     reduction launch for both columns' five sums                               (pr_cg.py:146-158 per column)
-double* bj_part(prcg_t* h, int g, int c) { return h->bjpart[g][c].d(); }
-// one block launch of group g; the grid is checked against the partial rows the session allocated BEFORE anything is launched
-int bj2_launch(prcg_t* h, int mode, int g, bool two_arrays, const double* v, double* z) {
-    const PairBufs& G = h->grp[g];
-    const int64_t tiles = h->bj_var ? h->bjv_plan.ntiles : block_jacobi_tiles(h->n, h->bj_bs);
-    const size_t need = (size_t)tiles * kPartialStride * sizeof(double);
-    CHECK(h, tiles > 0 && tiles == h->bj_tiles && h->bjpart[g][0].bytes >= need && (!two_arrays || h->bjpart[g][1].bytes >= need),
-          "block-Jacobi multi-RHS session: a block launch of %lld tiles does not match the %d partial rows the session allocated",
-          (long long)tiles, h->bj_tiles);
-    BjDotsArgs a{};
-    a.n = h->n; a.v = v; a.z = z; a.p = G.p.d(); a.r = G.r.d();
-    a.part0 = bj_part(h, g, 0); a.part1 = two_arrays ? bj_part(h, g, 1) : nullptr;
-    const int grid = h->bj_var ? launch_block_jacobi_var_dots(h->sc, mode, a, tiles, h->bjv_tiles_d(), h->bjv_code_d(), h->bj_blocks.d())
-                               : launch_block_jacobi_dots(h->sc, mode, a, h->bj_bs, h->bj_blocks.d());
-    LAUNCHCHK(h, grid);
-    CHECK(h, grid == h->bj_tiles, "block-Jacobi multi-RHS session: a block launch ran %d workgroups, the session allocated %d partial rows",
-          grid, h->bj_tiles);
-    return PRCG_OK;
-}
-// Hestenes-Stiefel: r~ = M^-1 r, nu_c, rr_c of group g -> scalar row k
-int bj2_hs_nu(prcg_t* h, int k, int g) {
-    const PairBufs& G = h->grp[g];
-    if (int rc = bj2_launch(h, kBjDotsNu, g, false, G.r.d(), G.rt.d())) return rc;
-    ReduceJobs J{};                                             // (the final tree with a thread's loads batched: one row per tile)
-    J.job[0] = ReduceJob{bj_part(h, g, 0), h->bj_tiles, dots_at(h, row0(h, g) + k), kHs2Nu, kHs2Nu, 4};            // nu_0, rr_0, nu_1, rr_1
-    launch_reduce_final_jobs(h->sc, J, 1);
-    return PRCG_OK;
-}
-int iterate_bj_hs2(prcg_t* h, int k) {
-    for (int g = 0; g < h->groups; ++g) {
-        const Hs2Args a = hs2_args(h, k, g);                    // a.d null: x += a p, r -= a s only (its own partials of r.r stay unused)
-        bool on = false;
-        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-        LAUNCHCHK(h, launch_hs2_update_xr(h->sc, a));
-        prof_end(h, h->ev_upd, h->n_ev_upd, on);
-        if (int rc = bj2_hs_nu(h, k, g)) return rc;
-        LAUNCHCHK(h, launch_hs2_update_p(h->sc, a));            // p = r~ + b p (a.rt)
-    }
-    return hs2_product_and_mu(h, k);
-}
-// s = A p for every column; per group s~ = M^-1 s with mu, dl, gm; then the five sums of each column in one reduction launch: mu, dl,
-// gm from the tile partials, nu, rr from the update launch's (g_upd[g] blocks) -- at k = 0 from the tile partials too (block NU)
-int bj2_pr_product_and_sums(prcg_t* h, int k, const int* g_upd) {
-    int rc = multi_product(h, k);
-    if (rc) return rc;
-    for (int g = 0; g < h->groups; ++g) {
-        const PairBufs& G = h->grp[g];
-        if ((rc = bj2_launch(h, kBjDotsPr, g, true, G.s.d(), G.st.d()))) return rc;
-        const int row = row0(h, g) + 2 * k;
-        ReduceJobs J{};
-        int nj = 0;
-        for (int c = 0; c < 2; ++c) {
-            if (g_upd) {
-                J.job[nj++] = ReduceJob{bj_part(h, g, c), h->bj_tiles, dots_at(h, row + c), kPr2Mu, kPr2Mu, 3};
-                J.job[nj++] = ReduceJob{c == 0 ? part_a(h, g) : part_b(h, g), g_upd[g], dots_at(h, row + c), kPr2Nu, kPr2Nu, 2};
-            } else {
-                J.job[nj++] = ReduceJob{bj_part(h, g, c), h->bj_tiles, dots_at(h, row + c), 0, 0, 5};
-            }
-        }
-        launch_reduce_final_jobs(h->sc, J, nj);
-    }
-    return PRCG_OK;
-}
-int iterate_bj_pr2(prcg_t* h, int k) {
-    int g_upd[2] = {0, 0};
-    for (int g = 0; g < h->groups; ++g) {
-        const Pr2Args a = pr2_args(h, k, g);
-        bool on = false;
-        if (g == 0) prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-        g_upd[g] = launch_pr2_update_stored(h->sc, a);
-        LAUNCHCHK(h, g_upd[g]);
-        prof_end(h, h->ev_upd, h->n_ev_upd, on);
-    }
-    return bj2_pr_product_and_sums(h, k, g_upd);
 }
 
 // Two right-hand sides in one pipelined predict-and-recompute session (pipe_pr_cg.py:61-75 / :169-187 for each column; the
@@ -247,26 +233,111 @@ int iterate_pipe2(prcg_t* h, int k) {
     return PRCG_OK;
 }
 
-// what no session with several right-hand sides serves, refused in the name of the entry that was called
-int refuse_unserved(prcg_t* h, const char* who, uint32_t hist_mask) {
-    CHECK(h, !h->multi(), "%s: a communicator is set on the handle: the two-RHS session runs on one GPU", who);
-    CHECK(h, h->g == 0, "%s: n_ghost = %lld > 0: the two-RHS session serves whole operators only", who, (long long)h->g);
-    CHECK(h, h->cb == nullptr, "%s: a host-callback preconditioner is set (prcg_set_preconditioner): the two-RHS "
-                               "session serves Jacobi (inv_diag) or none", who);
-    CHECK(h, !h->have_block_jacobi(), "%s: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the two-RHS "
-                            "session serves Jacobi (inv_diag) or none", who);
-    CHECK(h, h->replace_fn == nullptr, "%s: a replace hook is set (prcg_set_replace_hook): not served by the two-RHS session", who);
+// What no session with several right-hand sides serves, refused in the name of the entry that was called (who) and of its
+// session (noun: "two-RHS" / "multi-RHS").  Two halves, because the block-Jacobi entry tests its variant and nrhs between them.
+// The handle: one GPU, a whole operator, and the preconditioner -- blocks wanted (the block-Jacobi entry) or refused
+int refuse_handle(prcg_t* h, const char* who, const char* noun, bool want_blocks) {
+    CHECK(h, !h->multi(), "%s: a communicator is set on the handle: the %s session runs on one GPU", who, noun);
+    CHECK(h, h->g == 0, "%s: n_ghost = %lld > 0: the %s session serves whole operators only", who, (long long)h->g, noun);
+    if (want_blocks) {
+        CHECK(h, h->have_block_jacobi(), "%s: no block-Jacobi preconditioner is set on the handle (prcg_set_block_jacobi, prcg_build_block_jacobi, "
+                                         "prcg_set_block_jacobi_var, prcg_build_block_jacobi_var; prcg_set_csr drops the blocks): without blocks "
+                                         "the session is prcg_solve_begin_multi", who);
+        return PRCG_OK;
+    }
+    CHECK(h, h->cb == nullptr, "%s: a host-callback preconditioner is set (prcg_set_preconditioner): the %s "
+                               "session serves Jacobi (inv_diag) or none", who, noun);
+    CHECK(h, !h->have_block_jacobi(), "%s: a block-Jacobi preconditioner is set (prcg_set_block_jacobi): the %s "
+                            "session serves Jacobi (inv_diag) or none", who, noun);
+    return PRCG_OK;
+}
+// ... the replace hook and the histories
+int refuse_hooks(prcg_t* h, const char* who, const char* noun, uint32_t hist_mask) {
+    CHECK(h, h->replace_fn == nullptr, "%s: a replace hook is set (prcg_set_replace_hook): not served by the %s session", who, noun);
     CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
-          "%s: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the two-RHS session", who);
+          "%s: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the %s session", who, noun);
+    return PRCG_OK;
+}
+int refuse_unserved(prcg_t* h, const char* who, uint32_t hist_mask) {
+    if (int rc = refuse_handle(h, who, "two-RHS", false)) return rc;
+    return refuse_hooks(h, who, "two-RHS", hist_mask);
+}
+// every b[j] and x0[j] of the nrhs columns is there
+bool have_columns(const double* const* b, const double* const* x0, int nrhs) {
+    bool all = b && x0;
+    for (int j = 0; all && j < nrhs; ++j) all = b[j] && x0[j];
+    return all;
+}
+
+// ---- one way to open and start a session of pair groups (prcg_solve_begin_multi, prcg_solve_begin_multi_block_jacobi) ----
+// The leading vectors of `groups` pair groups, in THE order every such session has allocated them (open_session: the order of
+// hipMalloc decides where a vector lies): per group x, p (product sources: the spare entries behind row n), r, s, r~, s~; the
+// second group's block partials of its update launch; with blocks (tiles > 0) one partial row per tile of a block launch, per
+// group and column.  r~ is a full vector with Jacobi or blocks, s~ in a PR / M session with either; what is not kept is 16 bytes.
+int open_pairs(prcg_t* h, const char* who, int variant, int groups, int max_iter, uint32_t hist_mask, const double* inv_diag, int64_t tiles) {
+    const size_t D = sizeof(double);
+    const bool pr = is_pr(variant);
+    const size_t src = (size_t)2 * (h->n + kGatherPad) * D, vec = (size_t)2 * h->n * D, tilde = (inv_diag || tiles) ? vec : 16,
+                 part = (size_t)8192 * kPartialStride * D, bjp = (size_t)tiles * kPartialStride * D;
+    Lead lead[18];
+    size_t count = 0;
+    for (int g = 0; g < groups; ++g) {
+        for (const Lead& l : {Lead{&h->grp[g].x, src}, Lead{&h->grp[g].p, src}, Lead{&h->grp[g].r, vec}, Lead{&h->grp[g].s, vec},
+                              Lead{&h->grp[g].rt, tilde}})
+            lead[count++] = l;
+        // (the one session that never asked for an s~ it does not keep: Hestenes-Stiefel, one group, no blocks -- it still does not,
+        //  so that it allocates and clears exactly what it did)
+        if (pr || groups == 2 || tiles) lead[count++] = Lead{&h->grp[g].st, pr ? tilde : 16};
+    }
+    if (groups == 2) { lead[count++] = Lead{&h->partA1, part}; lead[count++] = Lead{&h->partB1, part}; }
+    for (int g = 0; tiles && g < groups; ++g) { lead[count++] = Lead{&h->bjpart[g][0], bjp}; lead[count++] = Lead{&h->bjpart[g][1], pr ? bjp : 16}; }
+    return open_session(h, who, variant, max_iter, hist_mask, inv_diag, false, lead, count, (pr ? 2 : 1) * groups);
+}
+// The start of the session open_pairs opened: X0 and B per group, r = b - A x0, per group r~ / nu / rr and p = r~, the first
+// product and its sums -- Jacobi or none through the init kernels of prcg_rhs2.hip, blocks through the block launches.
+int start_pairs(prcg_t* h, const char* who, int groups, const double* const* b, const double* const* x0, int64_t tiles) {
+    PairBufs* const G = h->grp;
+    const int64_t n = h->n;
+    hipStream_t sc = h->sc;
+    int rc;
+    h->rhs2 = true;
+    h->groups = groups;
+    h->spmm4 = groups == 2 && spmm4_one_launch(h);
+    h->bj_tiles = (int)tiles;
+    for (int g = 0; g < groups; ++g) {
+        if ((rc = upload_pairs(h, who, G[g].x.d(), x0[2 * g], x0[2 * g + 1]))) return rc;
+        if ((rc = upload_pairs(h, who, G[g].r.d(), b[2 * g], b[2 * g + 1]))) return rc;
+    }
+    // r = b - A x0 for every column (hs_cg.py:23): one product of [x0_0 x0_1] (| [x0_2 x0_3]), parked in S
+    if (groups == 2) LAUNCHCHK(h, eng_spmm4(h, sc, 0, G[0].x.d(), G[1].x.d(), G[0].s.d(), G[1].s.d()));
+    else LAUNCHCHK(h, eng_spmm2(h, sc, 0, G[0].x.d(), G[0].s.d(), 3));
+    for (int g = 0; g < groups; ++g) launch_sub(sc, G[g].r.d(), 1, G[g].r.d(), 1, G[g].s.d(), 1, 2 * n);
+    int g0[2] = {0, 0};                                  // PR / M with Jacobi or none: the grids of the init launches, whose partials hold nu, rr
+    for (int g = 0; g < groups; ++g) {
+        // (r~ = M^-1 r); nu = r~.r, r.r   (hs_cg.py:25 / :86-88, pr_cg.py:107-109)
+        if (h->bj_session) {
+            if ((rc = pr2(h) ? bj2_launch(h, kBjDotsNu, g, true, G[g].r.d(), G[g].rt.d()) : bj2_hs_nu(h, 0, g))) return rc;
+        } else if (pr2(h)) {
+            g0[g] = launch_pr2_init_dots(sc, pr2_args(h, 0, g));
+            LAUNCHCHK(h, g0[g]);
+        } else {
+            const Hs2Args a = hs2_args(h, 0, g);
+            const int g1 = launch_hs2_init_dots(sc, a);
+            LAUNCHCHK(h, g1);
+            launch_reduce_final(sc, a.partials, g1, dots_at(h, row0(h, g)), kHs2Nu, kHs2Nu, 4);
+        }
+        launch_copy(sc, G[g].p.d(), 1, h->prec ? G[g].rt.d() : G[g].r.d(), 1, 2 * n);   // p = r~ (r)   hs_cg.py:24 / :87, pr_cg.py:110
+    }
+    // s = A p; Hestenes-Stiefel: mu = p.s (:26-27); PR / M: (s~ = M^-1 s), mu, dl, gm and the five sums of row 0 (pr_cg.py:111-116)
+    if ((rc = pr2(h) ? pr2_product_and_sums(h, 0, h->bj_session ? nullptr : g0) : hs2_product_and_mu(h, 0))) return rc;
+    HIPCHK(h, hipStreamSynchronize(sc));
+    h->in_session = true;
     return PRCG_OK;
 }
 
 }  // namespace
 
-int prcg::iterate_multi(prcg_t* h, int k) {
-    if (h->bj_session) return pr2(h) ? iterate_bj_pr2(h, k) : iterate_bj_hs2(h, k);
-    return h->pipe2 ? iterate_pipe2(h, k) : pr2(h) ? iterate_pr2(h, k) : iterate_hs2(h, k);
-}
+int prcg::iterate_multi(prcg_t* h, int k) { return h->pipe2 ? iterate_pipe2(h, k) : pr2(h) ? iterate_pr2(h, k) : iterate_hs2(h, k); }
 
 extern "C" {
 
@@ -279,65 +350,9 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     CHECK(h, variant == PRCG_HS || is_pr(variant), "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg), "
                                                    "PRCG_PR (pr_cg / pr_pcg) and PRCG_M (m_cg / m_pcg) only", variant);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi", hist_mask)) return rc;
-    bool have_all = b && x0;
-    for (int j = 0; have_all && j < nrhs; ++j) have_all = b[j] && x0[j];
-    CHECK(h, have_all, "prcg_solve_begin_multi: null b or x0");
-    const int64_t n = h->n, ne = h->n + kGatherPad;
-    const size_t D = sizeof(double);
-    const int groups = nrhs / 2;
-    const bool pr = is_pr(variant);
-    // X and P feed the product: like every product source they carry the spare entries behind row n.  The second pair
-    // group's arrays (and its block partials) follow the first's, and only a four-RHS session asks for them.
-    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D, tilde = inv_diag ? vec : 16, part = (size_t)8192 * kPartialStride * D;
-    PairBufs* const G = h->grp;
-    int rc;
-    if (groups == 1 && !pr)
-        rc = open_session(h, "prcg_solve_begin_multi", PRCG_HS, max_iter, hist_mask, inv_diag, false,
-                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, tilde}});
-    else if (groups == 1)
-        rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
-                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, tilde}, {&G[0].st, tilde}}, 2);
-    else
-        rc = open_session(h, "prcg_solve_begin_multi", variant, max_iter, hist_mask, inv_diag, false,
-                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, tilde}, {&G[0].st, pr ? tilde : 16},
-                           {&G[1].x, src}, {&G[1].p, src}, {&G[1].r, vec}, {&G[1].s, vec}, {&G[1].rt, tilde}, {&G[1].st, pr ? tilde : 16},
-                           {&h->partA1, part}, {&h->partB1, part}}, (pr ? 2 : 1) * 2);
-    if (rc) return rc;
-    h->rhs2 = true;
-    h->groups = groups;
-    h->spmm4 = groups == 2 && spmm4_one_launch(h);
-    for (int g = 0; g < groups; ++g) {
-        if ((rc = upload_pairs(h, "prcg_solve_begin_multi", G[g].x.d(), x0[2 * g], x0[2 * g + 1]))) return rc;
-        if ((rc = upload_pairs(h, "prcg_solve_begin_multi", G[g].r.d(), b[2 * g], b[2 * g + 1]))) return rc;
-    }
-    hipStream_t sc = h->sc;
-    // r = b - A x0 for every column (hs_cg.py:23): one product of [x0_0 x0_1] (| [x0_2 x0_3]), parked in S
-    if (groups == 2) LAUNCHCHK(h, eng_spmm4(h, sc, 0, G[0].x.d(), G[1].x.d(), G[0].s.d(), G[1].s.d()));
-    else LAUNCHCHK(h, eng_spmm2(h, sc, 0, G[0].x.d(), G[0].s.d(), 3));
-    for (int g = 0; g < groups; ++g) launch_sub(sc, G[g].r.d(), 1, G[g].r.d(), 1, G[g].s.d(), 1, 2 * n);
-    if (pr2(h)) {
-        int g0[2] = {0, 0};
-        for (int g = 0; g < groups; ++g) {
-            g0[g] = launch_pr2_init_dots(sc, pr2_args(h, 0, g));             // (r~ = d r); nu = r~.r, r.r   pr_cg.py:108-109
-            LAUNCHCHK(h, g0[g]);
-            launch_copy(sc, G[g].p.d(), 1, h->prec ? G[g].rt.d() : G[g].r.d(), 1, 2 * n);   // p = r~ (r)   :110
-        }
-        if ((rc = pr2_product_and_sums(h, 0, g0))) return rc;                // s = A p, (s~ = d s), mu, dl, gm   :111-116
-        HIPCHK(h, hipStreamSynchronize(sc));
-        h->in_session = true;
-        return PRCG_OK;
-    }
-    for (int g = 0; g < groups; ++g) {
-        const Hs2Args a = hs2_args(h, 0, g);
-        const int g1 = launch_hs2_init_dots(sc, a);                          // (r~ = d r); nu = r.r~, r.r   :25 / :86-88
-        LAUNCHCHK(h, g1);
-        launch_reduce_final(sc, a.partials, g1, dots_at(h, row0(h, g)), kHs2Nu, kHs2Nu, 4);
-        launch_copy(sc, G[g].p.d(), 1, h->prec ? G[g].rt.d() : G[g].r.d(), 1, 2 * n);   // p = r~ (r)   :24 / :87
-    }
-    if ((rc = hs2_product_and_mu(h, 0))) return rc;                          // s = A p, mu = p.s   :26-27
-    HIPCHK(h, hipStreamSynchronize(sc));
-    h->in_session = true;
-    return PRCG_OK;
+    CHECK(h, have_columns(b, x0, nrhs), "prcg_solve_begin_multi: null b or x0");
+    if (int rc = open_pairs(h, "prcg_solve_begin_multi", variant, nrhs / 2, max_iter, hist_mask, inv_diag, 0)) return rc;
+    return start_pairs(h, "prcg_solve_begin_multi", nrhs / 2, b, x0, 0);
 }
 
 // ---- two right-hand sides in one pipelined predict-and-recompute session (PRCG_PIPE_PR, PRCG_PIPE_PR_M) ----
@@ -351,7 +366,7 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     CHECK(h, nrhs == 2, "prcg_solve_begin_multi_pipe: nrhs = %d: the pipelined session serves exactly 2 right-hand sides (its product is the "
                         "four-vector one; an eight-vector product does not exist)", nrhs);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi_pipe", hist_mask)) return rc;
-    CHECK(h, b && x0 && b[0] && b[1] && x0[0] && x0[1], "prcg_solve_begin_multi_pipe: null b or x0");
+    CHECK(h, have_columns(b, x0, 2), "prcg_solve_begin_multi_pipe: null b or x0");
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
     // the pair array that feeds the product -- (r,s), with Jacobi (r~,s~) -- carries the spare entries of every product source
@@ -399,72 +414,21 @@ int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const 
     if (!h) return PRCG_EINVAL;
     const char* const who = "prcg_solve_begin_multi_block_jacobi";
     CHECK(h, h->have_csr, "%s: call prcg_set_csr first", who);
-    // (a handle with a communicator cannot hold blocks at all: these two come first so that each refusal names its own reason)
-    CHECK(h, !h->multi(), "%s: a communicator is set on the handle: the multi-RHS session runs on one GPU", who);
-    CHECK(h, h->g == 0, "%s: n_ghost = %lld > 0: the multi-RHS session serves whole operators only", who, (long long)h->g);
-    CHECK(h, h->have_block_jacobi(), "%s: no block-Jacobi preconditioner is set on the handle (prcg_set_block_jacobi, prcg_build_block_jacobi, "
-                                     "prcg_set_block_jacobi_var, prcg_build_block_jacobi_var; prcg_set_csr drops the blocks): without blocks "
-                                     "the session is prcg_solve_begin_multi", who);
+    // (a handle with a communicator cannot hold blocks at all: those two refusals come first so that each names its own reason)
+    if (int rc = refuse_handle(h, who, "multi-RHS", true)) return rc;
     CHECK(h, !is_pipe(variant), "%s: variant %d: the pipelined variants are not served with blocks (a follow-up: their session is "
                                 "prcg_solve_begin_multi_pipe, Jacobi or none); PRCG_HS, PRCG_PR and PRCG_M are", who, variant);
     CHECK(h, variant == PRCG_HS || is_pr(variant), "%s: variant %d: the block-Jacobi multi-RHS session serves PRCG_HS (hs_pcg), PRCG_PR (pr_pcg) "
                                                    "and PRCG_M (m_pcg) only", who, variant);
     CHECK(h, nrhs == 2 || nrhs == 4, "%s: nrhs = %d: the session serves exactly 2 right-hand sides (or 4, as two pairs)", who, nrhs);
-    CHECK(h, h->replace_fn == nullptr, "%s: a replace hook is set (prcg_set_replace_hook): not served by the multi-RHS session", who);
-    CHECK(h, (hist_mask & ~PRCG_HIST_UPDATED_RESIDUAL_2_NORM) == 0,
-          "%s: history bits other than PRCG_HIST_UPDATED_RESIDUAL_2_NORM are not served by the multi-RHS session", who);
-    bool have_all = b && x0;
-    for (int j = 0; have_all && j < nrhs; ++j) have_all = b[j] && x0[j];
-    CHECK(h, have_all, "%s: null b or x0", who);
+    if (int rc = refuse_hooks(h, who, "multi-RHS", hist_mask)) return rc;
+    CHECK(h, have_columns(b, x0, nrhs), "%s: null b or x0", who);
     CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
-    const int64_t n = h->n, ne = h->n + kGatherPad;
-    const size_t D = sizeof(double);
-    const int groups = nrhs / 2;
-    const bool pr = is_pr(variant);
-    const int64_t tiles = h->bj_var ? h->bjv_plan.ntiles : block_jacobi_tiles(n, h->bj_bs);
+    const int64_t tiles = bj_tile_count(h);
     CHECK(h, tiles > 0 && tiles <= INT32_MAX, "%s: the blocks on the handle give %lld tiles", who, (long long)tiles);
-    // X and P feed the product (spare entries behind row n); r~ and, for PR / M, s~ are stored vectors of full size.  bjp: one partial
-    // row per tile of a block launch; part: the update launch's block partials of the second group (PR / M: nu, rr)
-    const size_t src = (size_t)2 * ne * D, vec = (size_t)2 * n * D, bjp = (size_t)tiles * kPartialStride * D,
-                 part = (size_t)8192 * kPartialStride * D;
-    PairBufs* const G = h->grp;
-    int rc;
-    if (groups == 1)
-        rc = open_session(h, who, variant, max_iter, hist_mask, nullptr, false,
-                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, vec}, {&G[0].st, pr ? vec : 16},
-                           {&h->bjpart[0][0], bjp}, {&h->bjpart[0][1], pr ? bjp : 16}}, pr ? 2 : 1);
-    else
-        rc = open_session(h, who, variant, max_iter, hist_mask, nullptr, false,
-                          {{&G[0].x, src}, {&G[0].p, src}, {&G[0].r, vec}, {&G[0].s, vec}, {&G[0].rt, vec}, {&G[0].st, pr ? vec : 16},
-                           {&G[1].x, src}, {&G[1].p, src}, {&G[1].r, vec}, {&G[1].s, vec}, {&G[1].rt, vec}, {&G[1].st, pr ? vec : 16},
-                           {&h->partA1, part}, {&h->partB1, part}, {&h->bjpart[0][0], bjp}, {&h->bjpart[0][1], pr ? bjp : 16},
-                           {&h->bjpart[1][0], bjp}, {&h->bjpart[1][1], pr ? bjp : 16}}, (pr ? 2 : 1) * 2);
-    if (rc) return rc;
+    if (int rc = open_pairs(h, who, variant, nrhs / 2, max_iter, hist_mask, nullptr, tiles)) return rc;
     CHECK(h, h->bj_session, "%s: the session did not open with the handle's blocks", who);
-    h->rhs2 = true;
-    h->groups = groups;
-    h->spmm4 = groups == 2 && spmm4_one_launch(h);
-    h->bj_tiles = (int)tiles;
-    for (int g = 0; g < groups; ++g) {
-        if ((rc = upload_pairs(h, who, G[g].x.d(), x0[2 * g], x0[2 * g + 1]))) return rc;
-        if ((rc = upload_pairs(h, who, G[g].r.d(), b[2 * g], b[2 * g + 1]))) return rc;
-    }
-    hipStream_t sc = h->sc;
-    // r = b - A x0 for every column: one product of [x0_0 x0_1] (| [x0_2 x0_3]), parked in S
-    if (groups == 2) LAUNCHCHK(h, eng_spmm4(h, sc, 0, G[0].x.d(), G[1].x.d(), G[0].s.d(), G[1].s.d()));
-    else LAUNCHCHK(h, eng_spmm2(h, sc, 0, G[0].x.d(), G[0].s.d(), 3));
-    for (int g = 0; g < groups; ++g) launch_sub(sc, G[g].r.d(), 1, G[g].r.d(), 1, G[g].s.d(), 1, 2 * n);
-    for (int g = 0; g < groups; ++g) {
-        // r~ = M^-1 r; nu = r~.r, r.r   (hs_cg.py:86-88 / pr_cg.py:107-109); p = r~
-        if (pr) { if ((rc = bj2_launch(h, kBjDotsNu, g, true, G[g].r.d(), G[g].rt.d()))) return rc; }
-        else if ((rc = bj2_hs_nu(h, 0, g))) return rc;
-        launch_copy(sc, G[g].p.d(), 1, G[g].rt.d(), 1, 2 * n);
-    }
-    // s = A p; Hestenes-Stiefel: mu = p.s; PR / M: s~ = M^-1 s, mu, dl, gm and the five sums of row 0
-    if ((rc = pr ? bj2_pr_product_and_sums(h, 0, nullptr) : hs2_product_and_mu(h, 0))) return rc;
-    HIPCHK(h, hipStreamSynchronize(sc));
-    h->in_session = true;
-    return PRCG_OK;
+    return start_pairs(h, who, nrhs / 2, b, x0, tiles);
 }
 
 // (column j of a four-RHS session: column j % 2 of pair group j / 2 -- per column what a two-RHS session returns)

@@ -1126,6 +1126,10 @@ namespace prcg {
 // has computed the initial state.
 int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
                  std::initializer_list<Lead> lead, int rows_per_iteration) {
+    return open_session(h, who, variant, max_iter, hist_mask, inv_diag, have_xtrue, lead.begin(), lead.size(), rows_per_iteration);
+}
+int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
+                 const Lead* lead, size_t count, int rows_per_iteration) {
     CHECK(h, h->have_csr, "%s: call prcg_set_csr first", who);
     CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
     HIPCHK(h, hipSetDevice(h->dev));
@@ -1142,7 +1146,7 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     s.have_xtrue = have_xtrue;
     h->n_ev_spmv = h->n_ev_upd = 0;
     const size_t D = sizeof(double);
-    for (const Lead& l : lead) HIPCHK(h, l.buf->ensure(l.bytes, h->sc));
+    for (size_t i = 0; i < count; ++i) HIPCHK(h, lead[i].buf->ensure(lead[i].bytes, h->sc));
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries (dinv is a window source of
     // the Chronopoulos-Gear product launch)
     HIPCHK(h, h->dinv.ensure((size_t)(h->n + h->g + kGatherPad) * D, h->sc));

@@ -404,13 +404,9 @@ class DeviceCSR:
         get_coefficients(k, rhs=j), history(rhs=j)."""
         B = _pair_of_vectors('B', B, self.n)
         X0 = _pair_of_vectors('X0', X0, self.n, nrhs=B.shape[0])
-        nrhs = B.shape[0]
-        dv = None if inv_diag is None else L.f64(inv_diag)
-        if dv is not None and dv.shape != (self.n,):
-            raise ValueError(f'begin_multi: inv_diag must have shape ({self.n},), got {dv.shape}')
-        bp = (C.c_void_p * nrhs)(*[B[j].ctypes.data for j in range(nrhs)])
-        xp = (C.c_void_p * nrhs)(*[X0[j].ctypes.data for j in range(nrhs)])
-        self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), nrhs, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
+        dv = _diagonal('begin_multi', inv_diag, self.n)
+        self._check(self._lib.prcg_solve_begin_multi(self._h, int(variant), len(B), _row_pointers(B), _row_pointers(X0), int(max_iter),
+                                                     L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def begin_multi_block_jacobi(self, variant, B, X0, max_iter, block_jacobi=None, block_jacobi_var=None, hist_mask=0):
@@ -424,16 +420,14 @@ class DeviceCSR:
         get_scalars(k, rhs=j), get_coefficients(k, rhs=j), history(rhs=j).  The blocks stay on the handle afterwards."""
         B = _pair_of_vectors('B', B, self.n)
         X0 = _pair_of_vectors('X0', X0, self.n, nrhs=B.shape[0])
-        nrhs = B.shape[0]
         if (block_jacobi is None) == (block_jacobi_var is None):
             raise ValueError('begin_multi_block_jacobi: exactly one of block_jacobi= and block_jacobi_var= must be given '
                              '(without blocks the session is begin_multi)')
         self._prec_fn = None
         self._check(self._lib.prcg_set_preconditioner(self._h, None, None))
         self._put_blocks(block_jacobi, block_jacobi_var)
-        bp = (C.c_void_p * nrhs)(*[B[j].ctypes.data for j in range(nrhs)])
-        xp = (C.c_void_p * nrhs)(*[X0[j].ctypes.data for j in range(nrhs)])
-        self._check(self._lib.prcg_solve_begin_multi_block_jacobi(self._h, int(variant), nrhs, bp, xp, int(max_iter), int(hist_mask)))
+        self._check(self._lib.prcg_solve_begin_multi_block_jacobi(self._h, int(variant), len(B), _row_pointers(B), _row_pointers(X0),
+                                                                  int(max_iter), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def begin_multi_pipe(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
@@ -455,12 +449,9 @@ class DeviceCSR:
         X0 = L.f64(X0)
         if X0.shape != (2, self.n):
             raise ValueError(f'begin_multi_pipe: X0 must have shape (2, {self.n}), the same as B, got {tuple(X0.shape)}')
-        dv = None if inv_diag is None else L.f64(inv_diag)
-        if dv is not None and dv.shape != (self.n,):
-            raise ValueError(f'begin_multi_pipe: inv_diag must have shape ({self.n},), got {dv.shape}')
-        bp = (C.c_void_p * 2)(B[0].ctypes.data, B[1].ctypes.data)
-        xp = (C.c_void_p * 2)(X0[0].ctypes.data, X0[1].ctypes.data)
-        self._check(self._lib.prcg_solve_begin_multi_pipe(self._h, int(variant), 2, bp, xp, int(max_iter), L.ptr(dv), int(hist_mask)))
+        dv = _diagonal('begin_multi_pipe', inv_diag, self.n)
+        self._check(self._lib.prcg_solve_begin_multi_pipe(self._h, int(variant), 2, _row_pointers(B), _row_pointers(X0), int(max_iter),
+                                                          L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def set_replace_hook(self, fn):
@@ -881,6 +872,19 @@ def _pair_of_vectors(name, V, n, nrhs=None):
     if err:
         raise ValueError(err)
     return V
+
+
+def _row_pointers(V):
+    """the C array of row pointers a multi-RHS entry takes; V is C-contiguous float64 and outlives the call"""
+    return (C.c_void_p * len(V))(*[V[j].ctypes.data for j in range(len(V))])
+
+
+def _diagonal(who, inv_diag, n):
+    """inv_diag of a multi-RHS session as float64 of shape (n,), None as None, or ValueError in the name of the method"""
+    dv = None if inv_diag is None else L.f64(inv_diag)
+    if dv is not None and dv.shape != (n,):
+        raise ValueError(f'{who}: inv_diag must have shape ({n},), got {dv.shape}')
+    return dv
 
 
 def plan_tiles(indptr, row_class=None, cap_nnz=None, cap_rows=None):

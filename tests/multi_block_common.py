@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE of tests/test_multi_rhs_block_jacobi.py: the summation tree of the block launches of a block-Jacobi session
 with two or four right-hand sides (new_cg_variants_amd/csrc/prcg_blockjac.hip: k_block_jacobi_dots / k_block_jacobi_var_dots),
-restated in NumPy, and the oracle runs routed through it.
+restated in NumPy, and the oracle runs routed through it (the oracle column and the session read-out themselves are the shared ones
+of tests/multi_rhs_common.py).
 
   tiles  : the partition cut greedily into runs of consecutive whole blocks with at most 256 rows (prcg_bjvar.h: bjvar_plan); a
            uniform block size bs: tiles of 256 - 256 % bs rows, which are the greedy tiles of the partition 0, bs, 2 bs, .., n
@@ -16,8 +17,10 @@ Which sum follows which tree (prcg.h: prcg_solve_begin_multi_block_jacobi):
 """
 import numpy as np
 
+import multi_rhs_common as common
 import oracle.ne_oracle as orc
 from device_order import Routed, _butterfly, _final_tree, device_sum
+from multi_rhs_common import KEYS, assert_column_bits      # noqa: F401  (for tests/test_multi_rhs_block_jacobi.py)
 
 LANES = 256
 
@@ -77,14 +80,7 @@ def oracle_column(A, b, x0, iters, variant, prec, tree):
     """hs_pcg / pr_pcg / m_pcg of the oracle with M^-1 = `prec` and every inner product routed to the tree the device sums it with:
     the state after `iters` iterations, the scalars of every iteration, the coefficients used BY every iteration >= 1, the history.
     Scalars: [mu, delta, gamma, nu, rr] (Hestenes-Stiefel: delta = gamma = 0)."""
-    rows = []
     hs = variant == 'hs'
-
-    def tap(st):
-        rr_sum = tree if (hs or st.k == 0) else device_sum
-        rr = np.float64(rr_sum(st.r * st.r))
-        rows.append((st.mu, 0.0 if hs else st.dl, 0.0 if hs else st.gm, st.nu, rr, st.alpha, st.beta, 0.0 if hs else st.nu_pred))
-
     if hs:
         dot = Routed(tree, device_sum)                    # nu, mu -- at the start and in every advance
         dot0 = dot
@@ -92,58 +88,20 @@ def oracle_column(A, b, x0, iters, variant, prec, tree):
         dot = Routed(tree, tree, tree, device_sum)        # advance: mu, delta, gamma, nu
         dot0 = Routed(tree)                               # start: nu, mu, delta, gamma, all from block launches
     method = {'hs': orc.hs_pcg, 'pr': orc.pr_pcg, 'm': orc.m_pcg}[variant]
-    with np.errstate(all='ignore'):
-        out = method(A, b, x0, iters + 1, preconditioner=prec, dot=dot, dot0=dot0, square=lambda a: a * a, tap=tap)
-        st = out['_final_state']
-        rows = np.array(rows)
-        res = {'x': st.x, 'r': st.r, 'p': st.p, 's': st.s, 'rt': st.rt, 'st': None if hs else st.st,
-               'scalars': rows[:, :5], 'alpha': rows[:-1, 5], 'beta': rows[1:, 6], 'nu_pred': rows[1:, 7], 'hist': np.sqrt(rows[:, 4])}
-    for v in res.values():
-        if v is not None:
-            v.setflags(write=False)
-    return res
+    return common.oracle_column(method, A, b, x0, iters, tilde=('rt',) if hs else ('rt', 'st'),
+                                rr=lambda st: np.float64((tree if (hs or st.k == 0) else device_sum)(st.r * st.r)),
+                                preconditioner=prec, dot=dot, dot0=dot0, square=lambda a: a * a)
 
 
 def device_columns(op, L, variant, B, X0, iters, chunks=(1, 2, 7), **blocks):
     """A block-Jacobi multi-RHS session on `op` read through the per-column getters; blocks: block_jacobi= or block_jacobi_var="""
-    code = {'hs': L.HS, 'pr': L.PR, 'm': L.M}[variant]
-    op.begin_multi_block_jacobi(code, B, X0, iters + 1, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM, **blocks)
-    sched = op.schedule()
-    for c in chunks:                                    # calls of any length give the same session
-        op.iterate(min(c, iters - op.k))
-    op.iterate(iters - op.k)
-    op.sync()
-    assert op.k == iters
     hs = variant == 'hs'
-    served = (L.S_MU, L.S_NU, L.S_RR) if hs else (L.S_MU, L.S_DELTA, L.S_GAMMA, L.S_NU, L.S_RR)
-    cols = []
-    for j in range(np.asarray(B).shape[0]):
-        sc = np.array([op.get_scalars(k, rhs=j) for k in range(iters + 1)])
-        other = [q for q in range(L.NUM_SCALARS) if q not in served]
-        assert not sc[:, other].any(), 'slots the session does not serve are 0'
-        cf = np.array([op.get_coefficients(k, rhs=j) for k in range(1, iters + 1)]).reshape(iters, 3)
-        col = {v: op.get_vector(v, rhs=j) for v in ('x', 'r', 'p', 's', 'rt')}
-        col['st'] = None if hs else op.get_vector('st', rhs=j)
-        col.update(scalars=sc[:, [L.S_MU, L.S_DELTA, L.S_GAMMA, L.S_NU, L.S_RR]], alpha=cf[:, 0], beta=cf[:, 1], nu_pred=cf[:, 2],
-                   hist=op.history(rhs=j)['updated_residual_2_norm'])
-        cols.append(col)
-    return cols, sched
 
-
-KEYS = ('x', 'r', 'p', 's', 'rt', 'st', 'scalars', 'alpha', 'beta', 'nu_pred', 'hist')
-
-
-def assert_column_bits(got, want, what, keys=KEYS):
-    for q in keys:
-        if want[q] is None:
-            assert got[q] is None, (what, q)
-            continue
-        g, w = np.asarray(got[q]), np.asarray(want[q])
-        assert g.shape == w.shape, (what, q, g.shape, w.shape)
-        if not np.array_equal(g, w, equal_nan=True):
-            bad = np.argwhere(~((g == w) | (np.isnan(g) & np.isnan(w))))
-            raise AssertionError(f'{what}: {q} differs in {len(bad)} of {g.size} entries, first at {bad[0]}: '
-                                 f'got {g[tuple(bad[0])]!r} want {w[tuple(bad[0])]!r}')
+    def begin():
+        op.begin_multi_block_jacobi({'hs': L.HS, 'pr': L.PR, 'm': L.M}[variant], B, X0, iters + 1, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM,
+                                    **blocks)
+    return common.device_columns(op, L, begin, iters, np.asarray(B).shape[0], common.VECS + (('rt',) if hs else ('rt', 'st')),
+                                 common.served_slots(L, hs), chunks, report=common.served_slots(L, False))
 
 
 def assert_finite_nonzero(want, what, hs):

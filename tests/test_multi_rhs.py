@@ -4,6 +4,7 @@ cg_variants.hs_cg_multi / hs_pcg_multi).
 The session runs, per column, exactly the recurrence of hs_cg / hs_pcg, and every inner product is summed in the order
 tests/device_order.py: device_sum models.  So the oracle (oracle/ne_oracle.py) run with ``dot=device_dot`` is asked for
 EQUAL BITS: vectors, the three inner products of every iteration, both coefficients, the history.  No tolerance anywhere.
+The harness shared with the other multi-RHS files: tests/multi_rhs_common.py.
 
 The recorded history is compared with sqrt(device_dot(r_k, r_k)) of the oracle's r_k: the device records the square
 root of the r.r it sums (prcg_get_history does the same for single sessions), the oracle's own recorder calls
@@ -18,116 +19,25 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import oracle.ne_oracle as orc
-from device_order import device_dot
+import multi_rhs_common as common
+from multi_rhs_common import KNOBS, VECS, _raises, amd, operator, same, single_session, two_rhs      # noqa: F401  (amd: the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VECS = ('x', 'r', 'p', 's')
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import new_cg_variants_amd.cg_variants as cgv
-    import new_cg_variants_amd.callbacks as cbs
-    from new_cg_variants_amd import _lib, device, problems
-    return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
-
-
-def same(a, b):
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
+assert_column_bits = functools.partial(common.assert_column_bits, keys=common.HS_KEYS)
 
 
 def oracle_column(A, b, x0, iters, jacobi):
     """hs_cg / hs_pcg of the oracle with the device's summation order: the state after `iters` iterations, the scalars
     mu, nu, rr and the coefficients of every iteration, and the history the device records."""
-    rows = []
-
-    def dot(a, b):                   # numpy scalars: 0 / 0 is NaN as on the device, not Python's ZeroDivisionError
-        return np.float64(device_dot(a, b))
-
-    def tap(st):
-        rows.append((st.mu, st.nu, dot(st.r, st.r), st.alpha, st.beta))
-    with np.errstate(all='ignore'):
-        if jacobi:
-            out = orc.hs_pcg(A, b, x0, iters + 1, preconditioner=orc.jacobi(A), dot=dot, tap=tap)
-        else:
-            out = orc.hs_cg(A, b, x0, iters + 1, dot=dot, tap=tap)
-    st = out['_final_state']
-    rows = np.array(rows)
-    with np.errstate(all='ignore'):
-        res = {'x': st.x, 'r': st.r, 'p': st.p, 's': st.s, 'rt': st.rt, 'scalars': rows[:, :3],
-               'alpha': rows[:-1, 3],          # a used BY iteration k = nu / mu of iteration k - 1
-               'beta': rows[1:, 4], 'hist': np.sqrt(rows[:, 2])}
-    return res
+    return common.hs_column(A, b, x0, iters, jacobi, rt_without_jacobi=True)
 
 
 def device_columns(op, L, B, X0, iters, inv_diag, chunks=(1, 2, 7)):
     """The two-RHS session on `op`: the same quantities per column, read through the per-column getters."""
-    op.begin_multi(L.HS, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    for c in chunks:                                    # calls of any length give the same session
-        op.iterate(min(c, iters - op.k))
-    op.iterate(iters - op.k)
-    op.sync()
-    assert op.k == iters
-    cols = []
-    for j in range(2):
-        sc = np.array([op.get_scalars(k, rhs=j) for k in range(iters + 1)])
-        other = [q for q in range(L.NUM_SCALARS) if q not in (L.S_MU, L.S_NU, L.S_RR)]
-        assert not sc[:, other].any(), 'slots other than mu, nu, rr are 0'
-        cf = np.array([op.get_coefficients(k, rhs=j) for k in range(1, iters + 1)]).reshape(iters, 3)
-        col = {v: op.get_vector(v, rhs=j) for v in VECS}
-        col['rt'] = op.get_vector('rt', rhs=j) if inv_diag is not None else None
-        col.update(scalars=sc[:, [L.S_MU, L.S_NU, L.S_RR]], alpha=cf[:, 0], beta=cf[:, 1],
-                   hist=op.history(rhs=j)['updated_residual_2_norm'])
-        cols.append(col)
-    return cols, sched
-
-
-def assert_column_bits(got, want, what):
-    for q in ('x', 'r', 'p', 's', 'rt', 'scalars', 'alpha', 'beta', 'hist'):
-        if want[q] is None:
-            assert got[q] is None, (what, q)
-            continue
-        g, w = np.asarray(got[q]), np.asarray(want[q])
-        assert g.shape == w.shape, (what, q, g.shape, w.shape)
-        if not same(g, w):
-            bad = np.argwhere(~((g == w) | (np.isnan(g) & np.isnan(w))))
-            raise AssertionError(f'{what}: {q} differs in {len(bad)} of {g.size} entries, first at {bad[0]}: '
-                                 f'got {g[tuple(bad[0])]!r} want {w[tuple(bad[0])]!r}')
-
-
-def two_rhs(P, A, seed=7):
-    n = A.shape[0]
-    b0 = P.reference_rhs(A, n)[0]
-    b1 = np.random.default_rng(seed).standard_normal(n)
-    return np.stack([b0, b1])
-
-
-@functools.lru_cache(maxsize=None)
-def operator(name):
-    """One operator per product family of the two-vector product; `family` is asserted through schedule()."""
-    from new_cg_variants_amd import problems as P
-    if name == 's3_small':           # banded, 15 diagonals: window tiles with index streams
-        return P.WORKLOADS['s3_small']['make'](), dict(window=True, pattern=False, sliced_rows=False)
-    if name == 's1_small':           # 5-point stencil, 64 x 48
-        return P.WORKLOADS['s1_small']['make'](), dict(window=True, pattern=True, sliced_rows=False)
-    if name == 'lap3d':              # 7-point stencil, odd extents: pattern tiles, several workgroups, a ragged last tile
-        return P.laplace_3d(21, 17, 13), dict(window=True, pattern=True, sliced_rows=False)
-    if name == 'fem12':              # 3 unknowns per node, 27-point coupling: sliced rows
-        return P.fem_like_3d(12), dict(window=False, sliced_rows=True, sorted_windows=False)
-    if name == 'fem_irregular10':    # 1 / 3 / 6 unknowns per node, thinned coupling: sliced rows of varying length
-        return P.fem_irregular_3d(10), dict(window=False, sliced_rows=True)
-    if name == 'bcsstk14':           # golden matrix, what the planner picks for it: sliced rows
-        from conftest import load_matrix
-        return load_matrix('bcsstk14')[0], dict(window=False, sliced_rows=True)
-    if name == 'bcsstk14_csr':       # ... and with the sliced layout switched off (KNOBS): the CSR-adaptive tiles
-        from conftest import load_matrix
-        return load_matrix('bcsstk14')[0], dict(window=False, sliced_rows=False)
-    raise KeyError(name)
-
-
-KNOBS = {'bcsstk14_csr': {'PRCG_SELL': '0'}}
+    def begin():
+        op.begin_multi(L.HS, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
+    return common.device_columns(op, L, begin, iters, 2, VECS + (('rt',) if inv_diag is not None else ()), common.served_slots(L, True),
+                                 chunks)
 
 # K per operator: 60 where nothing else decides.  s3_small with Jacobi converges until r underflows to exact zeros (the
 # ORACLE's nu / mu is 0 / 0 from iteration 49 on): 40 there.  Every case is checked to stay finite in the oracle.
@@ -195,17 +105,6 @@ def test_columns_are_independent(amd, jacobi):
     assert_column_bits(a0[1], want, '(b0, 0): the column that broke down')
 
 
-def single_session(op, L, variant, b, x0, iters):
-    op.begin(variant, b, x0, iters + 1, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    op.iterate(iters)
-    op.sync()
-    vec = {v: op.get_vector(v) for v in VECS}
-    sc = np.array([op.get_scalars(k) for k in range(iters + 1)])
-    cf = np.array([op.get_coefficients(k) for k in range(1, iters + 1)])
-    return sched, vec, sc, cf, op.history()['updated_residual_2_norm']
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('variant', ['HS', 'PIPE_PR'])
 @pytest.mark.parametrize('name', ['s3_small', 'fem12'])
@@ -235,10 +134,6 @@ def test_single_sessions_did_not_move(amd, variant, name):
         for v_ in VECS:
             assert same(run[1][v_], first[1][v_]), (what, v_)
         assert same(run[2], first[2]) and same(run[3], first[3]) and same(run[4], first[4]), what
-
-
-def _raises(L, text):
-    return pytest.raises(L.PrcgError, match=text)
 
 
 @pytest.mark.gpu

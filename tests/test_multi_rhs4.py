@@ -5,8 +5,8 @@ A four-RHS session is two PAIR GROUPS -- columns (0, 1) and (2, 3), each a compl
 vector kernels -- around ONE product [S0 S1 | S2 S3] = A [P0 P1 | P2 P3]: a single launch that reads the operator once on
 sliced-row operators (schedule()['spmm4']), two two-vector launches on every other operator or with PRCG_SPMM4=0.
 
-Everything is asked for EQUAL BITS, as in tests/test_multi_rhs.py and tests/test_multi_rhs_pr.py, whose helpers and
-operators are used here: the product per column against scipy's csr_matvec and against matmat2 of its pair, the sessions
+Everything is asked for EQUAL BITS, as in tests/test_multi_rhs.py and tests/test_multi_rhs_pr.py, with the helpers and
+operators all of them share (tests/multi_rhs_common.py): the product per column against scipy's csr_matvec and against matmat2 of its pair, the sessions
 against the device-ordered oracle and against two two-RHS sessions.  No tolerance anywhere.
 
 Right-hand sides: reference_rhs(A, n)[0] and default_rng(s).standard_normal(n) for s = 7, 8, 9 (columns 0 and 1 are those of
@@ -21,61 +21,28 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import test_multi_rhs as HS2
-import test_multi_rhs_pr as PR2
-from test_multi_rhs_pr import KNOBS, assert_finite, operator, same
+import multi_rhs_common as common
+from multi_rhs_common import KNOBS, VECS, _raises, amd, assert_finite, four_rhs, operator, same, single_session      # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VECS = ('x', 'r', 'p', 's')
 PERM = (2, 0, 3, 1)
 
 
-@pytest.fixture(scope='module')
-def amd():
-    import new_cg_variants_amd.cg_variants as cgv
-    import new_cg_variants_amd.callbacks as cbs
-    from new_cg_variants_amd import _lib, device, problems
-    return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
-
-
-def four_rhs(A):
-    from new_cg_variants_amd import problems as P
-    n = A.shape[0]
-    return np.stack([P.reference_rhs(A, n)[0]] + [np.random.default_rng(s).standard_normal(n) for s in (7, 8, 9)])
-
-
-@functools.lru_cache(maxsize=None)
 def problem(name, x0_nonzero=False):
-    A, _ = operator(name)
-    n = A.shape[0]
-    B = four_rhs(A)
-    X0 = np.random.default_rng(11).standard_normal((4, n)) if x0_nonzero else np.zeros((4, n))
-    B.setflags(write=False)
-    X0.setflags(write=False)
-    return A, B, X0
+    return common.problem(name, 4, x0_nonzero)
 
 
 def oracle_column(A, b, x0, iters, jacobi, variant):
-    """One column of the oracle with the device's summation order, in the keys of test_multi_rhs_pr's columns; a
-    Hestenes-Stiefel column has no delta, gamma, predicted nu or st."""
+    """One column of the oracle with the device's summation order, in the keys of a predict-and-recompute column; a
+    Hestenes-Stiefel column has no delta, gamma, predicted nu or st (and, here, no rt without Jacobi)."""
     if variant != 'hs':
-        return PR2.oracle_column(A, b, x0, iters, jacobi, variant)
-    res = HS2.oracle_column(A, b, x0, iters, jacobi)
-    if not jacobi:
-        res['rt'] = None
-    for v in res.values():
-        if v is not None:
-            v.setflags(write=False)
-    return res
+        return common.pr_column(A, b, x0, iters, jacobi, variant)
+    return common.hs_column(A, b, x0, iters, jacobi, rt_without_jacobi=False)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name, variant, jacobi, iters, x0_nonzero, column):
-    """The oracle run of one column, computed once and shared (read-only).  column: 0 .. 3, or 'zero' (b = 0, x0 = 0)."""
-    A, B, X0 = problem(name, x0_nonzero)
-    if column == 'zero':
-        return oracle_column(A, np.zeros(A.shape[0]), np.zeros(A.shape[0]), iters, jacobi, variant)
-    return oracle_column(A, B[column], X0[column], iters, jacobi, variant)
+# reference(name, variant, jacobi, iters, x0_nonzero, column): the oracle run of one column, computed once and shared (read-only).
+# column: 0 .. 3, or 'zero' (b = 0, x0 = 0)
+reference = functools.partial(common.reference, oracle_column, 4)
 
 
 def check_finite(want, variant, what):
@@ -87,38 +54,19 @@ def check_finite(want, variant, what):
 
 
 def assert_column_bits(got, want, variant, what):
-    if variant == 'hs':
-        HS2.assert_column_bits(got, want, what)
-    else:
-        PR2.assert_column_bits(got, want, what)
+    common.assert_column_bits(got, want, what, common.HS_KEYS if variant == 'hs' else common.KEYS)
 
 
 def device_columns(op, L, variant, B, X0, iters, inv_diag, chunks=(1, 2, 7)):
     """A multi-RHS session of `variant` ('hs', 'pr', 'm') on `op` with as many columns as B has rows, read through the
     per-column getters: per column the vectors, the served scalars of every iteration, the coefficients, the history."""
-    v = {'hs': L.HS, 'pr': L.PR, 'm': L.M}[variant]
-    op.begin_multi(v, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    for c in chunks:                                    # calls of any length give the same session
-        op.iterate(min(c, iters - op.k))
-    op.iterate(iters - op.k)
-    op.sync()
-    assert op.k == iters
-    served = (L.S_MU, L.S_NU, L.S_RR) if variant == 'hs' else (L.S_MU, L.S_DELTA, L.S_GAMMA, L.S_NU, L.S_RR)
-    cols = []
-    for j in range(len(B)):
-        sc = np.array([op.get_scalars(k, rhs=j) for k in range(iters + 1)])
-        other = [q for q in range(L.NUM_SCALARS) if q not in served]
-        assert not sc[:, other].any(), 'slots the session does not serve are 0'
-        cf = np.array([op.get_coefficients(k, rhs=j) for k in range(1, iters + 1)]).reshape(iters, 3)
-        col = {q: op.get_vector(q, rhs=j) for q in VECS}
-        col['rt'] = op.get_vector('rt', rhs=j) if inv_diag is not None else None
-        col['st'] = op.get_vector('st', rhs=j) if inv_diag is not None and variant != 'hs' else None
-        col.update(scalars=sc[:, list(served)], alpha=cf[:, 0], beta=cf[:, 1], nu_pred=cf[:, 2],
-                   hist=op.history(rhs=j)['updated_residual_2_norm'])
-        if variant == 'hs':
-            assert not cf[:, 2].any(), 'Hestenes-Stiefel predicts no nu'
-        cols.append(col)
+    def begin():
+        op.begin_multi({'hs': L.HS, 'pr': L.PR, 'm': L.M}[variant], B, X0, iters + 1, inv_diag=inv_diag,
+                       hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
+    tilde = () if inv_diag is None else ('rt',) if variant == 'hs' else ('rt', 'st')
+    cols, sched = common.device_columns(op, L, begin, iters, len(B), VECS + tilde, common.served_slots(L, variant == 'hs'), chunks)
+    if variant == 'hs':
+        assert not any(col['nu_pred'].any() for col in cols), 'Hestenes-Stiefel predicts no nu'
     return cols, sched
 
 
@@ -418,12 +366,7 @@ def test_columns_are_independent(amd, variant):
 
 # ---- 6. nothing else moved --------------------------------------------------------------------------------------------------
 def single_pr(op, L, b, x0, iters):
-    op.begin(L.PR, b, x0, iters + 1, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    op.iterate(iters)
-    op.sync()
-    return (sched, {v: op.get_vector(v) for v in VECS}, np.array([op.get_scalars(k) for k in range(iters + 1)]),
-            np.array([op.get_coefficients(k) for k in range(1, iters + 1)]), op.history()['updated_residual_2_norm'])
+    return single_session(op, L, L.PR, b, x0, iters)
 
 
 def assert_single_equal(run, first, what):
@@ -469,10 +412,6 @@ def test_nothing_else_moved(amd, name):
 
 
 # ---- 7. refusals ------------------------------------------------------------------------------------------------------------
-def _raises(L, text):
-    return pytest.raises(L.PrcgError, match=text)
-
-
 @pytest.mark.gpu
 def test_refusals(amd):
     """nrhs 3 and 5, j = 4, the single-column accessors inside a four-RHS session, and every condition the two-RHS session

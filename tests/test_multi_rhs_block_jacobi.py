@@ -3,7 +3,8 @@ DeviceCSR.begin_multi_block_jacobi; cg_variants.hs_bpcg_multi / pr_bpcg_multi / 
 
 Per column the session runs the recurrence of hs_pcg / pr_pcg / m_pcg with M^-1 the point-block Jacobi on the handle, whose
 arithmetic BlockJacobi.__call__ / VarBlockJacobi.__call__ carry bit for bit, and every inner product is summed in a fixed order:
-those of the block launches in the tree tests/multi_block_common.py restates, the others in device_order.device_sum.  The oracle
+those of the block launches in the tree tests/multi_block_common.py restates, the others in device_order.device_sum (the harness
+shared with the other multi-RHS files: tests/multi_rhs_common.py).  The oracle
 (oracle/ne_oracle.py) run with those routed sums is asked for EQUAL BITS: vectors, every scalar row, alpha, beta, the predicted
 nu, the history.  np.array_equal with NaN equal to NaN; no tolerance anywhere.
 
@@ -22,17 +23,10 @@ import scipy.sparse as sp
 from device_order import device_sum
 from multi_block_common import (BlockTree, assert_column_bits, assert_finite_nonzero, device_columns, greedy_tiles, oracle_column,
                                 uniform_partition, uniform_tiles)
+from multi_rhs_common import amd, two_rhs      # noqa: F401  (amd: the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = 'prcg_solve_begin_multi_block_jacobi'
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import new_cg_variants_amd.cg_variants as cgv
-    import new_cg_variants_amd.callbacks as cbs
-    from new_cg_variants_amd import _lib, device, problems
-    return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
@@ -131,11 +125,6 @@ def test_model_sums_every_row_once_and_is_its_own_tree():
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def two_rhs(P, A, seed=7):
-    n = A.shape[0]
-    return np.stack([P.reference_rhs(A, n)[0], np.random.default_rng(seed).standard_normal(n)])
-
-
 def cyclic_partition(n):
     sizes = np.resize(np.arange(1, 9), n)
     ptr = np.concatenate([[0], np.cumsum(sizes)])

@@ -8,7 +8,8 @@ tests/device_order.py: device_sum models.  So the oracle (oracle/ne_oracle.py) r
 iteration, alpha, beta, the predicted nu, the history.  No tolerance anywhere; NaN equals NaN.
 
 The recorded history is compared with sqrt(device_dot(r_k, r_k)) of the oracle's r_k.  The oracle runs are computed once
-per (operator, flavour, preconditioner, right-hand side) and shared; nobody writes to them.
+per (operator, flavour, preconditioner, right-hand side) and shared; nobody writes to them.  The harness shared with the other multi-RHS files:
+tests/multi_rhs_common.py.
 """
 import ctypes as C
 import functools
@@ -19,159 +20,63 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import multi_rhs_common as common
 import oracle.ne_oracle as orc
-from device_order import chunking, device_dot
+from device_order import chunking
+from multi_rhs_common import KNOBS, _raises, amd, assert_finite, same, single_session      # noqa: F401  (amd: the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VECS = ('x', 'r', 'p', 's', 'w', 'u')
 KEYS = VECS + ('rt', 'st', 'scalars', 'alpha', 'beta', 'nu_pred', 'hist')
 NAMES = ('pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi')
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import new_cg_variants_amd.cg_variants as cgv
-    import new_cg_variants_amd.callbacks as cbs
-    from new_cg_variants_amd import _lib, device, problems
-    return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
-
-
-def same(a, b):
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
-
-
-def _dot(a, b):                      # numpy scalars: 0 / 0 is NaN as on the device, not Python's ZeroDivisionError
-    return np.float64(device_dot(a, b))
+assert_column_bits = functools.partial(common.assert_column_bits, keys=KEYS)
+single_session = functools.partial(single_session, vecs=VECS)
 
 
 def oracle_column(A, b, x0, iters, jacobi, flavour='pr'):
     """pipe_pr_cg / pipe_pr_pcg / pipe_pr_m_cg / pipe_pr_m_pcg of the oracle with the device's summation order and its a * a:
     the state after `iters` iterations, mu, delta, gamma, nu, rr of every iteration, the coefficients used BY every
     iteration >= 1, the recorded history."""
-    rows = []
-
-    def tap(st):
-        rows.append((st.mu, st.dl, st.gm, st.nu, _dot(st.r, st.r), st.alpha, st.beta, st.nu_pred))
     method = {('pr', False): orc.pipe_pr_cg, ('pr', True): orc.pipe_pr_pcg,
               ('pr_m', False): orc.pipe_pr_m_cg, ('pr_m', True): orc.pipe_pr_m_pcg}[(flavour, jacobi)]
-    with np.errstate(all='ignore'):
-        out = method(A, b, x0, iters + 1, preconditioner=orc.jacobi(A) if jacobi else None, dot=_dot,
-                     square=lambda a: a * a, tap=tap)
-        st = out['_final_state']
-        rows = np.array(rows, dtype=np.float64)
-        res = {'x': st.x, 'r': st.r, 'p': st.p, 's': st.s, 'w': st.w, 'u': st.u,
-               'rt': st.rt if jacobi else None, 'st': st.st if jacobi else None,
-               'scalars': rows[:, :5],
-               'alpha': rows[:-1, 5],          # a used BY iteration k = nu / mu of iteration k - 1
-               'beta': rows[1:, 6], 'nu_pred': rows[1:, 7], 'hist': np.sqrt(rows[:, 4])}
-    for v in res.values():
-        if v is not None:
-            v.setflags(write=False)
-    return res
+    return common.oracle_column(method, A, b, x0, iters, vecs=VECS, tilde=('rt', 'st') if jacobi else (),
+                                preconditioner=orc.jacobi(A) if jacobi else None, dot=common.dot, square=lambda a: a * a)
 
 
 def device_columns(op, L, variant, B, X0, iters, inv_diag, chunks=(1, 2, 7)):
     """A pipelined two-RHS session of `variant` on `op`, read through the per-column getters: per column the vectors, ALL
     scalar slots of every iteration, the three coefficients of every iteration >= 1 and the history; and the schedule."""
-    op.begin_multi_pipe(variant, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    for c in chunks:                                    # calls of any length give the same session
-        op.iterate(min(c, iters - op.k))
-    op.iterate(iters - op.k)
-    op.sync()
-    assert op.k == iters
-    served = [L.S_MU, L.S_DELTA, L.S_GAMMA, L.S_NU, L.S_RR]
-    cols = []
-    for j in range(2):
-        sc = np.array([op.get_scalars(k, rhs=j) for k in range(iters + 1)])
-        other = [q for q in range(L.NUM_SCALARS) if q not in served]
-        assert not sc[:, other].any(), 'slots the session does not serve are 0'
-        cf = np.array([op.get_coefficients(k, rhs=j) for k in range(1, iters + 1)]).reshape(iters, 3)
-        col = {v: op.get_vector(v, rhs=j) for v in VECS}
-        col['rt'] = op.get_vector('rt', rhs=j) if inv_diag is not None else None
-        col['st'] = op.get_vector('st', rhs=j) if inv_diag is not None else None
-        col.update(all_scalars=sc, scalars=sc[:, served], alpha=cf[:, 0], beta=cf[:, 1], nu_pred=cf[:, 2],
-                   hist=op.history(rhs=j)['updated_residual_2_norm'])
-        cols.append(col)
-    return cols, sched
+    def begin():
+        op.begin_multi_pipe(variant, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
+    return common.device_columns(op, L, begin, iters, 2, VECS + (('rt', 'st') if inv_diag is not None else ()),
+                                 common.served_slots(L, False), chunks)
 
 
-def assert_column_bits(got, want, what, keys=KEYS):
-    for q in keys:
-        if want[q] is None:
-            assert got[q] is None, (what, q)
-            continue
-        g, w = np.asarray(got[q]), np.asarray(want[q])
-        assert g.shape == w.shape, (what, q, g.shape, w.shape)
-        if not same(g, w):
-            bad = np.argwhere(~((g == w) | (np.isnan(g) & np.isnan(w))))
-            raise AssertionError(f'{what}: {q} differs in {len(bad)} of {g.size} entries, first at {bad[0]}: '
-                                 f'got {g[tuple(bad[0])]!r} want {w[tuple(bad[0])]!r}')
+# The pipelined session's product is the four-vector one: ONE launch on sliced rows, which its schedule() reports beside the shared
+# `family` keys (a two-RHS Hestenes-Stiefel session on the same operator reports spmm4 false)
+SPMM4 = {'s3_small': False, 'lap3d': False, 'fem12': True, 'fem_irregular10': True, 'bcsstk14': True, 'bcsstk14_csr': False}
 
 
-def assert_finite(want, what):
-    """a case whose oracle run breaks down is a wrong case: it fails, it is not skipped"""
-    assert np.isfinite(want['scalars']).all() and np.isfinite(want['x']).all(), f'{what}: the oracle run must stay finite'
-    assert (want['scalars'][:, [0, 3]] > 0).all(), f'{what}: mu, nu > 0 in the oracle run'
+# ... and the sizes at which the update kernel can go wrong: this file's own operators, tridiag<n>
+SIZES = [63, 64, 255, 257, 511, 513, 1025, 2049]
+common.OPERATORS.update({f'tridiag{n}': (functools.partial(sp.diags, [-1.0, 2.5, -1.0], [-1, 0, 1], shape=(n, n), format='csr'), {})
+                         for n in SIZES})
 
 
-def two_rhs(P, A, seed=7):
-    n = A.shape[0]
-    b0 = P.reference_rhs(A, n)[0]
-    b1 = np.random.default_rng(seed).standard_normal(n)
-    return np.stack([b0, b1])
-
-
-@functools.lru_cache(maxsize=None)
 def operator(name):
     """One operator per product family of the multi-vector products; `family` is asserted through schedule()."""
-    from new_cg_variants_amd import problems as P
-    if name == 's3_small':           # banded, 15 diagonals: window tiles with index streams
-        return P.WORKLOADS['s3_small']['make'](), dict(window=True, pattern=False, sliced_rows=False, spmm4=False)
-    if name == 'lap3d':              # 7-point stencil, odd extents: pattern tiles, several workgroups, a ragged last tile
-        return P.laplace_3d(21, 17, 13), dict(window=True, pattern=True, sliced_rows=False, spmm4=False)
-    if name == 'lap3d_two_trips':    # n = 1,050,804 > 2048 * 512: two trips per block, a ragged last block
-        return P.laplace_3d(102, 102, 101), dict(window=True)
-    if name == 'fem12':              # 3 unknowns per node, 27-point coupling: sliced rows, the product is ONE launch
-        return P.fem_like_3d(12), dict(window=False, sliced_rows=True, sorted_windows=False, spmm4=True)
-    if name == 'fem_irregular10':    # 1 / 3 / 6 unknowns per node, thinned coupling: sliced rows of varying length
-        return P.fem_irregular_3d(10), dict(window=False, sliced_rows=True, spmm4=True)
-    if name == 'bcsstk14':           # golden matrix, what the planner picks for it: sliced rows
-        from conftest import load_matrix
-        return load_matrix('bcsstk14')[0], dict(window=False, sliced_rows=True, spmm4=True)
-    if name == 'bcsstk14_csr':       # ... and with the sliced layout switched off (KNOBS): the CSR-adaptive tiles
-        from conftest import load_matrix
-        return load_matrix('bcsstk14')[0], dict(window=False, sliced_rows=False, spmm4=False)
-    if name.startswith('tridiag'):   # the sizes at which the update kernel can go wrong
-        n = int(name[len('tridiag'):])
-        return sp.diags([-1.0, 2.5, -1.0], [-1, 0, 1], shape=(n, n), format='csr'), {}
-    raise KeyError(name)
+    A, family = common.operator(name)
+    return A, dict(family, **({'spmm4': SPMM4[name]} if name in SPMM4 else {}))
 
 
-KNOBS = {'bcsstk14_csr': {'PRCG_SELL': '0'}}
-
-
-@functools.lru_cache(maxsize=None)
 def problem(name, x0_nonzero=False):
     """(A, B, X0) of an operator"""
-    from new_cg_variants_amd import problems as P
-    A, _ = operator(name)
-    n = A.shape[0]
-    B = two_rhs(P, A)
-    X0 = np.random.default_rng(11).standard_normal((2, n)) if x0_nonzero else np.zeros((2, n))
-    B.setflags(write=False)
-    X0.setflags(write=False)
-    return A, B, X0
+    return common.problem(name, 2, x0_nonzero)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name, flavour, jacobi, iters, x0_nonzero, column):
-    """The oracle run of one column, computed once and shared (read-only).  column: 0, 1, or 'zero' (b = 0, x0 = 0)."""
-    A, B, X0 = problem(name, x0_nonzero)
-    if column == 'zero':
-        return oracle_column(A, np.zeros(A.shape[0]), np.zeros(A.shape[0]), iters, jacobi, flavour)
-    return oracle_column(A, B[column], X0[column], iters, jacobi, flavour)
-
+# reference(name, flavour, jacobi, iters, x0_nonzero, column): the oracle run of one column, computed once and shared (read-only).
+# column: 0, 1, or 'zero' (b = 0, x0 = 0)
+reference = functools.partial(common.reference, oracle_column, 2)
 
 def variant_of(L, flavour):
     return {'pr': L.PIPE_PR, 'pr_m': L.PIPE_PR_M}[flavour]
@@ -221,7 +126,7 @@ def test_bits_against_the_device_ordered_oracle(amd, flavour, name, jacobi, iter
 # ---- 2. sizes at which the update kernel can go wrong ---------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize('jacobi', [False, True])
-@pytest.mark.parametrize('n', [63, 64, 255, 257, 511, 513, 1025, 2049])
+@pytest.mark.parametrize('n', SIZES)
 def test_update_kernel_sizes(amd, n, jacobi):
     """A lane with only its first element (n <= 256), a ragged second half, one block and several: both flavours, 5 iterations."""
     L = amd['L']
@@ -268,17 +173,6 @@ def test_two_trips_per_block(amd):
 
 
 # ---- 3. device against device -------------------------------------------------------------------------------------------
-def single_session(op, L, variant, b, x0, iters, inv_diag=None, vecs=VECS):
-    op.begin(variant, b, x0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    op.iterate(iters)
-    op.sync()
-    vec = {v: op.get_vector(v) for v in vecs}
-    sc = np.array([op.get_scalars(k) for k in range(iters + 1)])
-    cf = np.array([op.get_coefficients(k) for k in range(1, iters + 1)])
-    return sched, vec, sc, cf, op.history()['updated_residual_2_norm']
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('jacobi', [False, True])
 @pytest.mark.parametrize('name', ['s3_small', 'fem12'])
@@ -401,10 +295,6 @@ def test_nothing_left_behind(amd, name, single):
 
 
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------
-def _raises(L, text):
-    return pytest.raises(L.PrcgError, match=text)
-
-
 @pytest.mark.gpu
 def test_refusals(amd):
     """What the pipelined two-RHS session does not serve is PRCG_EINVAL with a text naming the reason; a refused begin leaves an
@@ -519,7 +409,7 @@ def test_refusals(amd):
 def _pr_reference_x(A, b, x0):
     """x after two iterations of the oracle's identity-preconditioned pr_pcg with the device's sums"""
     with np.errstate(all='ignore'):
-        out = orc.pr_pcg(A, b, x0, 3, preconditioner=lambda v: v, dot=_dot, square=lambda a: a * a)
+        out = orc.pr_pcg(A, b, x0, 3, preconditioner=lambda v: v, dot=common.dot, square=lambda a: a * a)
     return out['_final_state'].x
 
 

@@ -9,7 +9,7 @@ tolerance anywhere.
 
 The recorded history is compared with sqrt(device_dot(r_k, r_k)) of the oracle's r_k, as in tests/test_multi_rhs.py.
 The oracle runs are computed once per (operator, variant, preconditioner, right-hand side) and shared; nobody writes
-to them.
+to them.  The harness shared with the other multi-RHS files: tests/multi_rhs_common.py.
 """
 import ctypes as C
 import functools
@@ -19,152 +19,37 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import oracle.ne_oracle as orc
-from device_order import chunking, device_dot
+import multi_rhs_common as common
+from device_order import chunking
+from multi_rhs_common import KNOBS, VECS, _raises, amd, assert_column_bits, assert_finite, operator, same, single_session      # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VECS = ('x', 'r', 'p', 's')
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import new_cg_variants_amd.cg_variants as cgv
-    import new_cg_variants_amd.callbacks as cbs
-    from new_cg_variants_amd import _lib, device, problems
-    return dict(cgv=cgv, cbs=cbs, L=_lib, device=device, problems=problems)
-
-
-def same(a, b):
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
-
-
-def _dot(a, b):                      # numpy scalars: 0 / 0 is NaN as on the device, not Python's ZeroDivisionError
-    return np.float64(device_dot(a, b))
 
 
 def oracle_column(A, b, x0, iters, jacobi, variant='pr'):
     """pr_pcg / m_pcg of the oracle with the device's summation order and its a * a: the state after `iters` iterations,
     mu, delta, gamma, nu, rr of every iteration, the coefficients used BY every iteration >= 1, the recorded history."""
-    rows = []
-
-    def tap(st):
-        rows.append((st.mu, st.dl, st.gm, st.nu, _dot(st.r, st.r), st.alpha, st.beta, st.nu_pred))
-    method = {'pr': orc.pr_pcg, 'm': orc.m_pcg}[variant]
-    with np.errstate(all='ignore'):
-        out = method(A, b, x0, iters + 1, preconditioner=orc.jacobi(A) if jacobi else (lambda v: v), dot=_dot,
-                     square=lambda a: a * a, tap=tap)
-        st = out['_final_state']
-        rows = np.array(rows)
-        res = {'x': st.x, 'r': st.r, 'p': st.p, 's': st.s, 'rt': st.rt if jacobi else None, 'st': st.st if jacobi else None,
-               'scalars': rows[:, :5],
-               'alpha': rows[:-1, 5],          # a used BY iteration k = nu / mu of iteration k - 1
-               'beta': rows[1:, 6], 'nu_pred': rows[1:, 7], 'hist': np.sqrt(rows[:, 4])}
-    for v in res.values():
-        if v is not None:
-            v.setflags(write=False)
-    return res
+    return common.pr_column(A, b, x0, iters, jacobi, variant)
 
 
 def device_columns(op, L, variant, B, X0, iters, inv_diag, chunks=(1, 2, 7)):
     """A two-RHS session of `variant` on `op`, read through the per-column getters: per column the vectors, ALL scalar slots
     of every iteration, the three coefficients of every iteration >= 1 and the history; and the schedule."""
-    op.begin_multi(variant, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    for c in chunks:                                    # calls of any length give the same session
-        op.iterate(min(c, iters - op.k))
-    op.iterate(iters - op.k)
-    op.sync()
-    assert op.k == iters
-    served = (L.S_MU, L.S_NU, L.S_RR) if variant == L.HS else (L.S_MU, L.S_DELTA, L.S_GAMMA, L.S_NU, L.S_RR)
-    cols = []
-    for j in range(2):
-        sc = np.array([op.get_scalars(k, rhs=j) for k in range(iters + 1)])
-        other = [q for q in range(L.NUM_SCALARS) if q not in served]
-        assert not sc[:, other].any(), 'slots the session does not serve are 0'
-        cf = np.array([op.get_coefficients(k, rhs=j) for k in range(1, iters + 1)]).reshape(iters, 3)
-        col = {v: op.get_vector(v, rhs=j) for v in VECS}
-        col['rt'] = op.get_vector('rt', rhs=j) if inv_diag is not None else None
-        col['st'] = op.get_vector('st', rhs=j) if inv_diag is not None and variant != L.HS else None
-        col.update(all_scalars=sc, scalars=sc[:, [L.S_MU, L.S_DELTA, L.S_GAMMA, L.S_NU, L.S_RR]], alpha=cf[:, 0], beta=cf[:, 1],
-                   nu_pred=cf[:, 2], hist=op.history(rhs=j)['updated_residual_2_norm'])
-        cols.append(col)
-    return cols, sched
+    def begin():
+        op.begin_multi(variant, B, X0, iters + 1, inv_diag=inv_diag, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
+    tilde = () if inv_diag is None else ('rt',) if variant == L.HS else ('rt', 'st')
+    return common.device_columns(op, L, begin, iters, 2, VECS + tilde, common.served_slots(L, variant == L.HS), chunks,
+                                 report=common.served_slots(L, False))
 
 
-def assert_column_bits(got, want, what, keys=('x', 'r', 'p', 's', 'rt', 'st', 'scalars', 'alpha', 'beta', 'nu_pred', 'hist')):
-    for q in keys:
-        if want[q] is None:
-            assert got[q] is None, (what, q)
-            continue
-        g, w = np.asarray(got[q]), np.asarray(want[q])
-        assert g.shape == w.shape, (what, q, g.shape, w.shape)
-        if not same(g, w):
-            bad = np.argwhere(~((g == w) | (np.isnan(g) & np.isnan(w))))
-            raise AssertionError(f'{what}: {q} differs in {len(bad)} of {g.size} entries, first at {bad[0]}: '
-                                 f'got {g[tuple(bad[0])]!r} want {w[tuple(bad[0])]!r}')
-
-
-def assert_finite(want, what):
-    """a case whose oracle run breaks down is a wrong case: it fails, it is not skipped"""
-    assert np.isfinite(want['scalars']).all() and np.isfinite(want['x']).all(), f'{what}: the oracle run must stay finite'
-    assert (want['scalars'][:, [0, 3]] > 0).all(), f'{what}: mu, nu > 0 in the oracle run'
-
-
-def two_rhs(P, A, seed=7):
-    n = A.shape[0]
-    b0 = P.reference_rhs(A, n)[0]
-    b1 = np.random.default_rng(seed).standard_normal(n)
-    return np.stack([b0, b1])
-
-
-@functools.lru_cache(maxsize=None)
-def operator(name):
-    """One operator per product family of the two-vector product; `family` is asserted through schedule()."""
-    from new_cg_variants_amd import problems as P
-    if name == 's3_small':           # banded, 15 diagonals: window tiles with index streams
-        return P.WORKLOADS['s3_small']['make'](), dict(window=True, pattern=False, sliced_rows=False)
-    if name == 's1_small':           # 5-point stencil, 64 x 48
-        return P.WORKLOADS['s1_small']['make'](), dict(window=True, pattern=True, sliced_rows=False)
-    if name == 'lap3d':              # 7-point stencil, odd extents: pattern tiles, several workgroups, a ragged last tile
-        return P.laplace_3d(21, 17, 13), dict(window=True, pattern=True, sliced_rows=False)
-    if name == 'lap3d_two_trips':    # n = 1,050,804 > 2048 * 512: two trips per block, a ragged last block
-        return P.laplace_3d(102, 102, 101), dict(window=True)
-    if name == 'fem12':              # 3 unknowns per node, 27-point coupling: sliced rows
-        return P.fem_like_3d(12), dict(window=False, sliced_rows=True, sorted_windows=False)
-    if name == 'fem_irregular10':    # 1 / 3 / 6 unknowns per node, thinned coupling: sliced rows of varying length
-        return P.fem_irregular_3d(10), dict(window=False, sliced_rows=True)
-    if name == 'bcsstk14':           # golden matrix, what the planner picks for it: sliced rows
-        from conftest import load_matrix
-        return load_matrix('bcsstk14')[0], dict(window=False, sliced_rows=True)
-    if name == 'bcsstk14_csr':       # ... and with the sliced layout switched off (KNOBS): the CSR-adaptive tiles
-        from conftest import load_matrix
-        return load_matrix('bcsstk14')[0], dict(window=False, sliced_rows=False)
-    raise KeyError(name)
-
-
-KNOBS = {'bcsstk14_csr': {'PRCG_SELL': '0'}}
-
-
-@functools.lru_cache(maxsize=None)
 def problem(name, x0_nonzero=False):
-    """(A, B, X0) of an operator: the right-hand sides of tests/test_multi_rhs.py: two_rhs"""
-    from new_cg_variants_amd import problems as P
-    A, _ = operator(name)
-    n = A.shape[0]
-    B = two_rhs(P, A)
-    X0 = np.random.default_rng(11).standard_normal((2, n)) if x0_nonzero else np.zeros((2, n))
-    B.setflags(write=False)
-    X0.setflags(write=False)
-    return A, B, X0
+    """(A, B, X0) of an operator: the right-hand sides of tests/multi_rhs_common.py: two_rhs"""
+    return common.problem(name, 2, x0_nonzero)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name, variant, jacobi, iters, x0_nonzero, column):
-    """The oracle run of one column, computed once and shared (read-only).  column: 0, 1, or 'zero' (b = 0)."""
-    A, B, X0 = problem(name, x0_nonzero)
-    if column == 'zero':
-        return oracle_column(A, np.zeros(A.shape[0]), np.zeros(A.shape[0]), iters, jacobi, variant)
-    return oracle_column(A, B[column], X0[column], iters, jacobi, variant)
+# reference(name, variant, jacobi, iters, x0_nonzero, column): the oracle run of one column, computed once and shared (read-only).
+# column: 0, 1, or 'zero' (b = 0)
+reference = functools.partial(common.reference, oracle_column, 2)
 
 
 # K per case: 60 where nothing else decides.  s3_small with Jacobi: the oracle's nu reaches <= 0 at iteration 6 (Meurant's
@@ -259,17 +144,6 @@ def test_columns_are_independent(amd, jacobi):
     assert_column_bits(a0[1], want, '(b0, 0): the column that broke down')
 
 
-def single_session(op, L, variant, b, x0, iters):
-    op.begin(variant, b, x0, iters + 1, hist_mask=L.HIST_UPDATED_RESIDUAL_2_NORM)
-    sched = op.schedule()
-    op.iterate(iters)
-    op.sync()
-    vec = {v: op.get_vector(v) for v in VECS}
-    sc = np.array([op.get_scalars(k) for k in range(iters + 1)])
-    cf = np.array([op.get_coefficients(k) for k in range(1, iters + 1)])
-    return sched, vec, sc, cf, op.history()['updated_residual_2_norm']
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('name', ['fem12', 's3_small'])
 def test_nothing_else_moved(amd, name):
@@ -307,10 +181,6 @@ def test_nothing_else_moved(amd, name):
         assert not hs_a[j]['nu_pred'].any(), 'Hestenes-Stiefel predicts no nu: out[2] stays 0'
         assert not hs_a[j]['all_scalars'][:, [L.S_DELTA, L.S_GAMMA, L.S_RES2, L.S_ERRA2, L.S_ERR2]].any()
         assert_column_bits(pr2[j], reference(name, 'pr', True, multi_iters, False, j), f'{name}: the PR session in between, column {j}')
-
-
-def _raises(L, text):
-    return pytest.raises(L.PrcgError, match=text)
 
 
 @pytest.mark.gpu
