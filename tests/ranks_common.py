@@ -11,11 +11,12 @@ from conftest import ROOT
 
 
 def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15, offsets=None, peer=False, chunks=None, x0=None,
-              vectors=(), scalars=False):
+              vectors=(), scalars=False, read_start=False):
     """Solve with `nranks` row blocks, one thread per rank, all on cuda:0: begin(max_iter = iters + 1), then prcg_iterate calls of
     `chunks` (default: one call of `iters`), sync (raises if a wave of a one-launch iteration timed out).
     knobs: one dict for all ranks or a list, one per rank.  peer: connect the ranks' exchange buffers (direct peer exchange; same
-    process: device addresses instead of IPC handles).  x0: the start vector (default: problems.reference_rhs's).
+    process: device addresses instead of IPC handles).  x0: the GLOBAL start vector (default: problems.reference_rhs's, zeros);
+    read_start: the rank's rows of `vectors` are also read right after begin and stored under key 0 of 'state'.
     Returns (offsets, ranks): per rank a dict with 'schedule' (after begin), 'start_layout' and 'layout' (DeviceCSR.layout()
     after begin and after the run), 'hist', 'x', 'y' (the rank's rows of a probe product taken before the session), 'state'
     {k: the rank's rows of the state vectors named in `vectors`, read after each chunk}, and with scalars=True 'scalars'
@@ -47,6 +48,8 @@ def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15
             op.begin(variant, b[lo:hi], x0[lo:hi], iters + 1, x_true=x_true[lo:hi],
                      inv_diag=None if inv_diag is None else inv_diag[lo:hi], hist_mask=hist_mask)
             res = {'schedule': op.schedule(), 'start_layout': op.layout(), 'state': {}, 'y': y}
+            if read_start:
+                res['state'][0] = tuple(op.get_vector(v) for v in vectors)
             for c in (chunks or [iters]):
                 op.iterate(c)
                 if vectors:

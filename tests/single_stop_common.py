@@ -20,8 +20,8 @@ def vectors_of(method):
     return ('x', 'r', 'p', 's', 'w', 'u') + (('rt', 'st') if jac else ()) + (('wt',) if jac and flavour == 'p' else ())
 
 
-def trajectory(A, b, method, dot, dot0, iters, keep=None):
-    """The oracle (oracle/ne_oracle.py: pipe_start / pipe_advance) from x0 = 0, `iters` iterations, NO stopping: row k of
+def trajectory(A, b, method, dot, dot0, iters, keep=None, x0=None):
+    """The oracle (oracle/ne_oracle.py: pipe_start / pipe_advance) from x0 (None: zeros), `iters` iterations, NO stopping: row k of
     `scalars` = {mu, delta, gamma, nu, rr} of state k (rr = r.r summed like the others: row 0 by dot0, the start-up launch's
     order, later rows by dot, the iteration launch's), row k - 1 of `coef` = {a, b, predicted nu} of iteration k, `at[k]` the
     vectors of state k (keep: only at those k, None elsewhere; default every k).  A breakdown leaves inf / nan behind, as the
@@ -43,7 +43,7 @@ def trajectory(A, b, method, dot, dot0, iters, keep=None):
             return None
         return {v: np.array(getattr(st, v), copy=True) for v in names}
     with np.errstate(all='ignore'):
-        st = O.pipe_start(A, b, np.zeros(b.size), prec=prec, dot=dot0)
+        st = O.pipe_start(A, b, np.zeros(b.size) if x0 is None else x0, prec=prec, dot=dot0)
         scalars, coef, at = [[st.mu, st.dl, st.gm, st.nu, dot0(st.r, st.r)]], [], [snap(st)]
         for _ in range(iters):
             a = st.alpha
@@ -63,14 +63,16 @@ def stop_of(traj, thr):
     return -1, 0
 
 
-def run_session(L, op, method, b, inv_diag, max_iter, rr_stop, chunks, then=0):
-    """one device session from x0 = 0 with the recurrence residual recorded: prcg_iterate calls of `chunks` WITHOUT a
+def run_session(L, op, method, b, inv_diag, max_iter, rr_stop, chunks, then=0, x0=None):
+    """one device session from x0 (None: zeros) with the recurrence residual recorded: prcg_iterate calls of `chunks` WITHOUT a
     synchronisation between them, then prcg_sync; everything the session holds is read back.  then > 0: a further
-    prcg_iterate(then) and a second reading (`again`)."""
+    prcg_iterate(then) and a second reading (`again`).  With an x0, x and r are also read right after begin (`start`)."""
     variant = getattr(L, METHODS[method][0])
     names = vectors_of(method)
-    op.begin(variant, b, np.zeros(b.size), max_iter, inv_diag=inv_diag, hist_mask=1, rr_stop=rr_stop)
+    op.begin(variant, b, np.zeros(b.size) if x0 is None else x0, max_iter, inv_diag=inv_diag, hist_mask=1, rr_stop=rr_stop)
     out = {'schedule': op.schedule(), 'start_layout': op.layout()}
+    if x0 is not None:
+        out['start'] = (op.get_vector('x'), op.get_vector('r'))
     for c in chunks:
         op.iterate(c)
     op.sync()

@@ -65,8 +65,8 @@ def tall_system(n, first):
     return A, 1 + 0.25 * np.sin(0.37 * i)
 
 
-def trajectory(A, b, variant, prec, thr=None, free=FREE, cap=MAX_ITER - 1, at=(0, 1)):
-    """The oracle under the workgroup's sum with `prec` (a callable), x0 = 0, in ONE pass: stepped to iteration `free`, and on --
+def trajectory(A, b, variant, prec, thr=None, free=FREE, cap=MAX_ITER - 1, at=(0, 1), x0=None):
+    """The oracle under the workgroup's sum with `prec` (a callable), from x0 (None: zeros), in ONE pass: stepped to iteration `free`, and on --
     to `cap` at most -- until the stopping rule has fired for `thr` (None: no rule).  Returns (run, halt):
     run  -- the first `free` iterations as a session without thresholds leaves them: vec[k] for k in `at` and k = free, scalars
             rows 0..free {mu, delta, gamma, nu, rr}, coef rows 1..free, hist;
@@ -82,7 +82,7 @@ def trajectory(A, b, variant, prec, thr=None, free=FREE, cap=MAX_ITER - 1, at=(0
     def snap(st):
         return {v: np.array(getattr(st, v), copy=True) for v in names}
     with np.errstate(all='ignore'):
-        st = (O.hs_start if hs else O.pipe_start)(A, b, np.zeros(b.size), prec=prec, dot=wg_dot)
+        st = (O.hs_start if hs else O.pipe_start)(A, b, np.zeros(b.size) if x0 is None else x0, prec=prec, dot=wg_dot)
         scalars, coef, vec = [row(st)], [], {0: snap(st)}
         halt = None
 
@@ -116,8 +116,8 @@ def trajectory(A, b, variant, prec, thr=None, free=FREE, cap=MAX_ITER - 1, at=(0
 
 
 def run_blocks(amd, systems, variant, blocks, chunks, rr_stop=None, mat_of=None, matrices=None, max_iter=None, read=None,
-               inv_diag=None):
-    """one DeviceBatch session over `systems` [(A, b)], x0 = 0, begun with block_jacobi=blocks (or, blocks None, inv_diag).  One
+               inv_diag=None, x0s=None):
+    """one DeviceBatch session over `systems` [(A, b)], from x0s (one vector per system; None: zeros), begun with block_jacobi=blocks (or, blocks None, inv_diag).  One
     record per system of `read` (default: all), in the form holds_oracle takes -- the stop word, the vectors at k = 0 (at0) and
     at the end (at), every row of scalars and coefficients, the history -- plus vec[k] for every k a chunk ends on."""
     L = amd['L']
@@ -127,7 +127,8 @@ def run_blocks(amd, systems, variant, blocks, chunks, rr_stop=None, mat_of=None,
     total = sum(chunks)
     read = range(len(systems)) if read is None else read
     try:
-        batch.begin(getattr(L, variant), [b for _, b in systems], [np.zeros(b.size) for _, b in systems], max_iter or total + 1, hist_mask=1,
+        batch.begin(getattr(L, variant), [b for _, b in systems], [np.zeros(b.size) for _, b in systems] if x0s is None else x0s, max_iter or total + 1,
+                    hist_mask=1,
                     block_jacobi=blocks, inv_diag=inv_diag, rr_stop=rr_stop)
         recs = {s: {'at0': {v: batch.get_vector(v, s) for v in names}} for s in read}
         for rec in recs.values():

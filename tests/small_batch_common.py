@@ -102,9 +102,10 @@ def thresholds(bs, rtol=0.0, atol=0.0):
     return np.maximum(rtol * norms, atol) ** 2
 
 
-def oracle_stopped(A, b, variant, thr, iters, jacobi=True):
+def oracle_stopped(A, b, variant, thr, iters, jacobi=True, x0=None):
     """the oracle under the workgroup's sum, stepped until the rule fires or `iters` iterations are done.  last: the iteration
-    whose state it holds (k_stop, or iters); scalars: rows 0..last {mu, delta, gamma, nu, rr}; coef: rows 1..last"""
+    whose state it holds (k_stop, or iters); scalars: rows 0..last {mu, delta, gamma, nu, rr}; coef: rows 1..last.  x0: the start
+    vector (None: zeros)"""
     import oracle.ne_oracle as O
     prec = O.jacobi(A) if jacobi else None
     hs = variant == 'HS'
@@ -112,7 +113,7 @@ def oracle_stopped(A, b, variant, thr, iters, jacobi=True):
     def row(st):
         return [st.mu, 0.0 if hs else st.dl, 0.0 if hs else st.gm, st.nu, wg_dot(st.r, st.r)]
     with np.errstate(all='ignore'):
-        st = (O.hs_start if hs else O.pipe_start)(A, b, np.zeros(b.size), prec=prec, dot=wg_dot)
+        st = (O.hs_start if hs else O.pipe_start)(A, b, np.zeros(b.size) if x0 is None else x0, prec=prec, dot=wg_dot)
         at0 = {v: np.array(getattr(st, v), copy=True) for v in names_of(variant, jacobi)}
         scalars, coef = [row(st)], []
         k_stop, status = -1, rule(st.mu, st.nu, scalars[0][4], thr)
@@ -135,8 +136,8 @@ def oracle_stopped(A, b, variant, thr, iters, jacobi=True):
                     scalars=scalars, coef=np.array(coef).reshape(-1, 3), hist=np.sqrt(scalars[:, 4]))
 
 
-def run_stopping_batch(amd, systems, variant, rr_stop, chunks, jacobi=True, mat_of=None, matrices=None, read=None):
-    """one DeviceBatch session over `systems` [(A, b)], x0 = 0, Jacobi or unpreconditioned, rr_stop None: no thresholds.  One
+def run_stopping_batch(amd, systems, variant, rr_stop, chunks, jacobi=True, mat_of=None, matrices=None, read=None, x0s=None):
+    """one DeviceBatch session over `systems` [(A, b)], from x0s (one vector per system; None: zeros), Jacobi or unpreconditioned, rr_stop None: no thresholds.  One
     record per system of `read` (default: all): the stop word, the vectors at k = 0 and at the end, every row of the scalars
     and coefficients, the history."""
     L = amd['L']
@@ -146,7 +147,7 @@ def run_stopping_batch(amd, systems, variant, rr_stop, chunks, jacobi=True, mat_
     total = sum(chunks)
     read = range(len(systems)) if read is None else read
     try:
-        batch.begin(getattr(L, variant), [b for _, b in systems], [np.zeros(b.size) for _, b in systems], total + 1, hist_mask=1,
+        batch.begin(getattr(L, variant), [b for _, b in systems], [np.zeros(b.size) for _, b in systems] if x0s is None else x0s, total + 1, hist_mask=1,
                     inv_diag=jacobi_of(systems) if jacobi else None, rr_stop=rr_stop)
         recs = {s: {'at0': {v: batch.get_vector(v, s) for v in names}} for s in read}
         for c in chunks:

@@ -870,15 +870,26 @@ def test_one_workgroup_solver_for_small_systems(amd, matrices, matrix, variant):
     BASELINE config 1 is bcsstk03 under hs_cg).
     Per element the arithmetic is the one of the multi-launch schedules: from identical state
     vectors agree bit for bit, inner products to 1e-12; and it is deterministic."""
+    one_workgroup_solver(amd, matrices, matrix, variant)
+
+
+def one_workgroup_solver(amd, matrices, matrix, variant, x0=None, prefix_floor=None):
+    """the body of test_one_workgroup_solver_for_small_systems.  x0: the start vector of every session (None: zeros); with one,
+    x == x0 and r == b - A x0 are held bit for bit right after begin on both handles, and prefix_floor is that start's table of
+    floors in place of PREFIX_FLOOR (tests/test_warm_start.py)."""
     import time
     L = amd['L']
     A, z = matrices[matrix]
     n = A.shape[0]
     VAR = getattr(L, variant)
+    start = np.zeros(n) if x0 is None else x0
     small = amd['device'].DeviceCSR(A)                                  # default: one-workgroup solver
     multi = amd['device'].DeviceCSR(A, knobs={'PRCG_SMALL': '0'})       # one (HS: two) launch(es) per iteration
     for op in (small, multi):
-        op.begin(VAR, z['b'], np.zeros(n), 64)
+        op.begin(VAR, z['b'], start, 64)
+        if x0 is not None:
+            assert np.array_equal(op.get_vector('x'), x0), 'x right after begin'
+            assert np.array_equal(op.get_vector('r'), np.asarray(z['b'], dtype=np.float64) - A @ x0), 'r right after begin'
     assert small.schedule()['small'] == (matrix != 'bcsstk14') and not multi.schedule()['small']
     worst = 0.0
     for k in range(30):
@@ -905,7 +916,7 @@ def test_one_workgroup_solver_for_small_systems(amd, matrices, matrix, variant):
     iters = 3000
     runs, times = [], []
     for chunks in ((iters,), (1000, 1, 1999)):
-        small.begin(VAR, z['b'], np.zeros(n), iters + 1, hist_mask=1)
+        small.begin(VAR, z['b'], start, iters + 1, hist_mask=1)
         t0 = time.perf_counter()
         for c in chunks:
             small.iterate(c)
@@ -913,14 +924,15 @@ def test_one_workgroup_solver_for_small_systems(amd, matrices, matrix, variant):
         times.append(time.perf_counter() - t0)
         runs.append(small.history()['updated_residual_2_norm'])
     assert np.array_equal(runs[0], runs[1], equal_nan=True)
-    multi.begin(VAR, z['b'], np.zeros(n), iters + 1, hist_mask=1)
+    multi.begin(VAR, z['b'], start, iters + 1, hist_mask=1)
     t0 = time.perf_counter()
     multi.iterate(iters)
     multi.sync()
     dt_multi = time.perf_counter() - t0
-    prefix = PREFIX_FLOOR.get(matrix, 5)
+    prefix = (PREFIX_FLOOR if prefix_floor is None else prefix_floor).get(matrix, 5)
     np.testing.assert_allclose(runs[0][:prefix], multi.history()['updated_residual_2_norm'][:prefix], rtol=1e-12)
-    print(f'{matrix} (n={n}) {variant}: {iters} iterations in one launch {times[0] * 1e3:.2f} ms '
+    measured = first_k_beyond(runs[0], multi.history()['updated_residual_2_norm'])
+    print(f'{matrix} (n={n}) {variant}: the two histories leave 1e-12 of each other at k={measured} (floor {prefix}); {iters} iterations in one launch {times[0] * 1e3:.2f} ms '
           f'({times[0] / iters * 1e6:.2f} us/iteration) vs one launch per iteration {dt_multi * 1e3:.2f} ms '
           f'({dt_multi / iters * 1e6:.2f} us/iteration); forced-step scalar deviation {worst:.1e}')
     small.close()

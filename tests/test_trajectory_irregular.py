@@ -43,7 +43,7 @@ import pytest
 
 from device_order import LongRowOperator, Routed, UnitTree, device_dot, first_mismatch, pair_sum, tile_cap_nnz
 from oracle import ne_oracle as orc
-from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, run_device, run_oracle
+from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, holds_start, run_device, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -189,15 +189,23 @@ def test_whole_trajectory_on_sliced_rows_and_csr_tiles(amd, problem, trees, meth
     every inner product the method defines and the coefficients a, b of every iteration; the residual history of (a) and (b);
     in (b) x and r at k = 3, k = 40 and the end.  The recorder histories of (a): 1e-13 relative for the three 2-norms, 1e-11
     for the A-norm of the error (sums in another order by the recorder kernels), the bars of the window test."""
+    whole_trajectory(amd, problem, trees, method, operator, knobs)
+
+
+def whole_trajectory(amd, problem, trees, method, operator, knobs, x0=None, max_iter=ITERS):
+    """the body of test_whole_trajectory_on_sliced_rows_and_csr_tiles.  x0: the start vector of every session and of the oracle
+    (None: zeros); an array, or a callable (op, A, b) -> array that may run an earlier session on the handle
+    (tests/warm_start_common.py).  With one, x and r right after prcg_solve_begin are held first: x == x0 and r == b - A x0 (A: the
+    LongRowOperator where the operator has long rows), bit for bit."""
     L = amd['L']
     variant, family, jac, slots = METHODS[method]
     matrix, op_knobs, want = OPERATORS[operator]
     A, b, x_true, jacobi, inv_diag = problem(matrix)
-    max_iter = ITERS
     assert max_iter - 1 > sum(CHUNKS) + 1
     all_knobs = dict(op_knobs, PRCG_SMALL='0', **knobs)
     op = amd['device'].DeviceCSR(A, knobs=all_knobs)
-    runs = [run_device(L, op, getattr(L, variant), b, x_true, inv_diag if jac else None, max_iter, rec) for rec in (True, False)]
+    x0 = x0(op, A, b) if callable(x0) else x0
+    runs = [run_device(L, op, getattr(L, variant), b, x_true, inv_diag if jac else None, max_iter, rec, x0=x0) for rec in (True, False)]
     op.close()
     for mode, r in zip('ab', runs):
         s = r['schedule']
@@ -215,6 +223,9 @@ def test_whole_trajectory_on_sliced_rows_and_csr_tiles(amd, problem, trees, meth
     A_dev = LongRowOperator(A, tile_cap_nnz(runs[0]['schedule']['tile_steps'])) if want.get('long_rows') else A
     if want.get('long_rows'):
         assert A_dev.long_rows.size >= 1
+    if x0 is not None:
+        for r in runs:
+            holds_start(r['start'], 'xr', x0, b, A_dev)
     oracles = []
     for r in runs:
         if oracles and same_tree(r['layout'], runs[0]['layout']):
@@ -223,7 +234,7 @@ def test_whole_trajectory_on_sliced_rows_and_csr_tiles(amd, problem, trees, meth
         tree = trees(operator, r['layout']) if r['layout']['grid'] > 0 else None
         start_tree = trees(operator, r['start_layout']) if r['start_layout']['grid'] > 0 else None
         dot, dot0 = oracle_dots(family, tree, start_tree)
-        oracles.append(run_oracle(method, A_dev, b, x_true, jacobi, max_iter, dot, dot0, keep))
+        oracles.append(run_oracle(method, A_dev, b, x_true, jacobi, max_iter, dot, dot0, keep, x0=x0))
     cols = [FIELD[f] for _, f in slots]
     for mode, r, (rows, ref, snaps) in zip('ab', runs, oracles):
         want_dots = rows[:, cols]

@@ -35,7 +35,7 @@ import pytest
 
 from device_order import OneLaunchTree, Routed, device_dot, first_mismatch, pair_sum
 from oracle import ne_oracle as orc
-from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, run_device, run_oracle
+from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, holds_start, run_device, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -145,13 +145,24 @@ def test_whole_trajectory_of_the_default_schedule(amd, problem, method, operator
     iteration; the residual history of (a) and (b); in (b) x and r at k = 3, k = 40 and the end (multiply, then
     add, no FMA).  The recorder histories of (a): 1e-13 relative for the three 2-norms, 1e-11 for the A-norm of the error
     (sums in another order by the recorder kernels)."""
+    whole_trajectory(amd, problem, method, operator, max_iter, knobs)
+
+
+def whole_trajectory(amd, problem, method, operator, max_iter, knobs, x0=None):
+    """the body of test_whole_trajectory_of_the_default_schedule.  x0: the start vector of every session and of the oracle (None:
+    zeros); an array, or a callable (op, A, b) -> array that may run an earlier session on the handle (tests/warm_start_common.py).
+    With one, x and r right after prcg_solve_begin are held first: x == x0 and r == b - A x0, bit for bit."""
     L = amd['L']
     variant, family, jac, slots = METHODS[method]
     A, b, x_true, jacobi, inv_diag = problem(operator)
     assert max_iter - 1 > sum(CHUNKS)
     op = amd['device'].DeviceCSR(A, knobs=dict(OPERATORS[operator], PRCG_SMALL='0', **knobs))
-    runs = [run_device(L, op, getattr(L, variant), b, x_true, inv_diag if jac else None, max_iter, rec) for rec in (True, False)]
+    x0 = x0(op, A, b) if callable(x0) else x0
+    runs = [run_device(L, op, getattr(L, variant), b, x_true, inv_diag if jac else None, max_iter, rec, x0=x0) for rec in (True, False)]
     op.close()
+    if x0 is not None:
+        for r in runs:
+            holds_start(r['start'], 'xr', x0, b, A)
     for mode, r in zip('ab', runs):
         s = r['schedule']
         # the schedule of the table: window tiles, no reduction launches (one launch per iteration; hs and the two-launch forms:
@@ -181,7 +192,7 @@ def test_whole_trajectory_of_the_default_schedule(amd, problem, method, operator
         tree = OneLaunchTree(r['layout'])
         start_tree = OneLaunchTree(r['start_layout']) if r['start_layout']['grid'] > 0 else None
         dot, dot0 = oracle_dots(family, tree, start_tree)
-        oracles.append(run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep))
+        oracles.append(run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep, x0=x0))
     cols = [FIELD[f] for _, f in slots]
     for mode, r, (rows, ref, snaps) in zip('ab', runs, oracles):
         want = rows[:, cols]

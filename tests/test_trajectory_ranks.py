@@ -55,7 +55,7 @@ import pytest
 from device_order import OneLaunchTree, PeerLaunchTree, RankSum, Routed, TwoLaunchTree, device_sum, first_mismatch, pair_sum
 from oracle import ne_oracle as orc
 from ranks_common import run_ranks
-from trajectory_common import ALL_METHODS, CHUNKS, FIELD, FOUR, run_oracle
+from trajectory_common import ALL_METHODS, CHUNKS, FIELD, FOUR, holds_start, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -149,12 +149,12 @@ def chunk_lengths(iters):
     return out
 
 
-def run_case(L, A, method, nranks, transport, offsets, inv_diag, iters, recorders):
+def run_case(L, A, method, nranks, transport, offsets, inv_diag, iters, recorders, x0=None):
     variant, family, jac, _ = ALL_METHODS[method]
     knobs, peer, _ = TRANSPORTS[transport]
     return run_ranks(A, nranks, getattr(L, variant), iters, knobs=knobs, inv_diag=inv_diag if jac else None, hist_mask=15 if recorders else 1,
                      offsets=offsets, peer=peer, chunks=None if recorders else chunk_lengths(iters),
-                     vectors=() if recorders else state_vectors(family, jac), scalars=True)
+                     vectors=() if recorders else state_vectors(family, jac), scalars=True, x0=x0, read_start=x0 is not None and not recorders)
 
 
 def pipe_tree(rank):
@@ -212,11 +212,19 @@ def test_whole_trajectory_of_a_multi_rank_session(amd, problem, method, operator
     iteration on rank 0, and every rank's copy of them; one residual history; in (b) the concatenated x and r (with Jacobi r~,
     s~) at k = 3, k = 40 and the end.  The recorder histories of (a): 1e-13 relative for the three 2-norms, 1e-11 for the A-norm
     of the error (the recorder kernels sum per rank, then the all-reduce).  No wave timed out (sync() raises)."""
+    whole_trajectory(amd, problem, method, operator, nranks, transport, iters)
+
+
+def whole_trajectory(amd, problem, method, operator, nranks, transport, iters, x0=None):
+    """the body of test_whole_trajectory_of_a_multi_rank_session.  x0: the GLOBAL start vector of every session and of the oracle
+    (None: zeros).  With one, every rank's rows of x and r right after prcg_solve_begin are held first -- concatenated, x == x0 and
+    r == b - A x0 with the global product, bit for bit: the halo exchange of x0 -- and the case takes no figure from BREAKS: it
+    runs `iters` iterations and asserts that the oracle's mu and nu are finite and positive at every one of them."""
     L = amd['L']
     variant, family, jac, slots = ALL_METHODS[method]
     A, b, x_true, jacobi, inv_diag = problem(operator)
     off = OPERATORS[operator][1](nranks)
-    runs = [run_case(L, A, method, nranks, transport, off, inv_diag, iters, rec) for rec in (True, False)]
+    runs = [run_case(L, A, method, nranks, transport, off, inv_diag, iters, rec, x0=x0) for rec in (True, False)]
     offsets = runs[0][0]
     assert np.array_equal(offsets, runs[1][0])
     flags = TRANSPORTS[transport][2]
@@ -239,13 +247,17 @@ def test_whole_trajectory_of_a_multi_rank_session(amd, problem, method, operator
     for a, c in zip(runs[0][1], runs[1][1]):
         assert same_tree(a['layout'], c['layout']) and same_tree(a['start_layout'], c['start_layout'])
     keep = set(runs[1][1][0]['state'])
-    assert keep == set(np.cumsum(chunk_lengths(iters)).tolist()) and (iters < 41 or keep == {1, 3, 40, iters}), keep
     vectors = state_vectors(family, jac)
+    if x0 is not None:
+        keep.remove(0)
+        holds_start([np.concatenate([r['state'][0][i] for r in runs[1][1]]) for i in range(len(vectors))], vectors, x0, b, A)
+    assert keep == set(np.cumsum(chunk_lengths(iters)).tolist()) and (iters < 41 or keep == {1, 3, 40, iters}), keep
     dot, dot0 = oracle_dots(family, offsets, runs[0][1])
-    rows, ref, snaps = run_oracle(method, A, b, x_true, jacobi, FULL + 1, dot, dot0, keep, vectors=vectors)
+    rows, ref, snaps = run_oracle(method, A, b, x_true, jacobi, (FULL if x0 is None else iters) + 1, dot, dot0, keep, vectors=vectors, x0=x0)
     kb = first_breakdown(rows)
     print(f'{case_id((method, operator, nranks, transport, iters))}: oracle breakdown at k={kb}; workgroups x waves per rank: {shape_line(runs[0][1])}')
-    assert iters == iterations(kb), f'the oracle first breaks down at k={kb} under this case\'s trees: the case runs {iterations(kb)} iterations'
+    assert x0 is None or kb < 0, f'the oracle first breaks down at k={kb} under this case\'s trees, within the {iters} iterations of the run'
+    assert x0 is not None or iters == iterations(kb), f'the oracle first breaks down at k={kb} under this case\'s trees: the case runs {iterations(kb)} iterations'
     cols = [FIELD[f] for _, f in slots]
     want = rows[:iters + 1, cols]
     assert np.isfinite(want).all() and (want != 0).all()

@@ -50,7 +50,7 @@ import numpy as np
 import pytest
 
 from device_order import OneLaunchTree, Routed, UnitTree, chunking, device_sum, first_mismatch, pair_sum
-from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, run_device, run_oracle
+from trajectory_common import CHUNKS, FIELD, FOUR, METHODS, holds_start, run_device, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -249,6 +249,14 @@ def test_whole_trajectory_of_the_stored_tilde_schedule(amd, problem, preconditio
     state vector both sides keep (VECTORS: r~, s~, p, s, w, u as the family has them).  The recorder histories of
     (a): 1e-13 relative for the three 2-norms, 1e-11 for the A-norm of the error (sums in another order by the recorder
     kernels), the bars of the other two trajectory tests."""
+    whole_trajectory(amd, problem, preconditioner, trees, method, operator, prec, max_iter)
+
+
+def whole_trajectory(amd, problem, preconditioner, trees, method, operator, prec, max_iter, x0=None):
+    """the body of test_whole_trajectory_of_the_stored_tilde_schedule.  x0: the start vector of every session and of the oracle
+    (None: zeros); an array, or a callable (op, A, b) -> array that may run an earlier session on the handle
+    (tests/warm_start_common.py).  With one, the state right after prcg_solve_begin is held first: x == x0 and r == b - A x0, bit
+    for bit, and every vector of VECTORS equal to the oracle's state 0."""
     L = amd['L']
     variant, family, jac, slots = METHODS[method]
     assert jac
@@ -260,7 +268,8 @@ def test_whole_trajectory_of_the_stored_tilde_schedule(amd, problem, preconditio
     assert max_iter - 1 > sum(CHUNKS) + 1
     vectors = VECTORS[family]
     op = amd['device'].DeviceCSR(A, knobs=dict(op_knobs, PRCG_SMALL='0'))
-    runs = [run_device(L, op, getattr(L, variant), b, x_true, None, max_iter, rec, vectors=vectors, **device_preconditioner(kind, arg, M))
+    x0 = x0(op, A, b) if callable(x0) else x0
+    runs = [run_device(L, op, getattr(L, variant), b, x_true, None, max_iter, rec, vectors=vectors, x0=x0, **device_preconditioner(kind, arg, M))
             for rec in (True, False)]
     blocks = op.get_block_jacobi() if kind == 'bj_built' else op.get_block_jacobi_var() if kind == 'bjv_built' else None
     op.close()
@@ -273,6 +282,9 @@ def test_whole_trajectory_of_the_stored_tilde_schedule(amd, problem, preconditio
             M._layout()
         M._inv_blocks = np.ascontiguousarray(blocks)
     with_tile_tree = family in ('hs', 'cg')
+    if x0 is not None:
+        for r in runs:
+            holds_start(r['start'], vectors, x0, b, A)
     for mode, r in zip('ab', runs):
         s = r['schedule']
         # the stored-tilde schedule: no one-launch or prologue-summed form of any family, not the one-workgroup solver
@@ -297,7 +309,7 @@ def test_whole_trajectory_of_the_stored_tilde_schedule(amd, problem, preconditio
         tree = trees(operator, r['layout']) if with_tile_tree else None
         start_tree = trees(operator, r['start_layout']) if with_tile_tree else None
         dot, dot0 = oracle_dots(family, tree, start_tree)
-        oracles.append(run_oracle(method, A, b, x_true, M, max_iter, dot, dot0, keep, vectors=vectors))
+        oracles.append(run_oracle(method, A, b, x_true, M, max_iter, dot, dot0, keep | ({0} if x0 is not None else set()), vectors=vectors, x0=x0))
     cols = [FIELD[f] for _, f in slots]
     for mode, r, (rows, ref, snaps) in zip('ab', runs, oracles):
         want_dots = rows[:, cols]
@@ -313,6 +325,9 @@ def test_whole_trajectory_of_the_stored_tilde_schedule(amd, problem, preconditio
     assert np.array_equal(runs[0]['hist']['updated_residual_2_norm'], runs[1]['hist']['updated_residual_2_norm'])
     assert np.isfinite(runs[1]['hist']['updated_residual_2_norm']).all()
     snaps = oracles[1][2]
+    for r, (_, _, at) in zip(runs, oracles) if x0 is not None else ():
+        for name, got, want_v in zip(vectors, r['start'], at[0]):
+            assert np.array_equal(got, want_v), f'{name} right after prcg_solve_begin: {int(np.count_nonzero(got != want_v))} of {got.size} entries differ'
     for k in sorted(keep):
         for name, got, want_v in zip(vectors, runs[1]['state'][k], snaps[k]):
             differ = int(np.count_nonzero(got != want_v))

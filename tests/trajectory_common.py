@@ -30,10 +30,10 @@ CHUNKS = (1, 2, 37)          # prcg_iterate calls of mode (b), then the rest: st
 FIELD = {'mu': 0, 'dl': 1, 'gm': 2, 'nu': 3, 'eta': 4, 'alpha': 5, 'beta': 6}
 
 
-def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep, vectors='xr'):
+def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep, vectors='xr', x0=None):
     """the oracle's trajectory: rows (mu, dl, gm, nu, eta, alpha, beta) per state, recorder histories, (x, r) at the states in
     `keep` (`vectors`: other fields of the oracle's state in their place, e.g. ('x', 'r', 'ut', 'wt')); `jacobi`: the callable
-    the oracle takes as preconditioner= (any callable, not only a diagonal)"""
+    the oracle takes as preconditioner= (any callable, not only a diagonal); x0: the start vector (None: zeros)"""
     rows, snaps = [], {}
 
     def tap(st):
@@ -41,20 +41,35 @@ def run_oracle(method, A, b, x_true, jacobi, max_iter, dot, dot0, keep, vectors=
         if st.k in keep:
             snaps[st.k] = tuple(getattr(st, v).copy() for v in vectors)
     kw = {'preconditioner': jacobi} if ALL_METHODS[method][2] else {}
-    ref = getattr(orc, ORACLE_NAME.get(method, method))(A, b, np.zeros(A.shape[0]), max_iter, dot=dot, dot0=dot0, square=lambda a: a * a,
+    ref = getattr(orc, ORACLE_NAME.get(method, method))(A, b, np.zeros(A.shape[0]) if x0 is None else x0, max_iter, dot=dot, dot0=dot0, square=lambda a: a * a,
                                                          callbacks=FOUR, x_true=x_true, tap=tap, **kw)
     return np.array(rows, dtype=np.float64), ref, snaps
 
 
+def holds_start(start, vectors, x0, b, A, what=''):
+    """the state a session holds right after begin from a start vector, bit for bit: x == x0 and r == b - A x0 (A: what the
+    device multiplies with -- SciPy's product, rows summed left to right from +0.0, or LongRowOperator).  A failure here is the
+    start-up's, not iteration 1's."""
+    names = list(vectors)
+    x, r = start[names.index('x')], start[names.index('r')]
+    assert x.shape == x0.shape and np.array_equal(x, x0), f'{what}x right after begin: {int(np.count_nonzero(x != x0))} of {x0.size} entries differ from x0'
+    want = b - (A @ x0)
+    assert np.array_equal(r, want), \
+        f'{what}r right after begin: {int(np.count_nonzero(r != want))} of {want.size} entries differ from b - A x0, worst {np.max(np.abs(r - want)):.3e}'
+
+
 def run_device(L, op, variant, b, x_true, inv_diag, max_iter, recorders, *, block_jacobi=None, block_jacobi_var=None, preconditioner=None,
-               vectors='xr'):
+               vectors='xr', x0=None):
     """one session: mode (a) all four recorders, one prcg_iterate call; mode (b) the recurrence residual only, calls of CHUNKS
     and the rest, x and r (`vectors`: those state vectors) read after each.  The preconditioner is at most one of inv_diag /
-    block_jacobi / block_jacobi_var / preconditioner, as DeviceCSR.begin takes them."""
+    block_jacobi / block_jacobi_var / preconditioner, as DeviceCSR.begin takes them.  x0: the start vector (None: zeros); with
+    one, `vectors` are also read right after begin, in either mode ('start': the state at k = 0)."""
     n = b.shape[0]
-    op.begin(variant, b, np.zeros(n), max_iter, x_true=x_true if recorders else None, inv_diag=inv_diag, hist_mask=15 if recorders else 1,
+    op.begin(variant, b, np.zeros(n) if x0 is None else x0, max_iter, x_true=x_true if recorders else None, inv_diag=inv_diag, hist_mask=15 if recorders else 1,
              block_jacobi=block_jacobi, block_jacobi_var=block_jacobi_var, preconditioner=preconditioner)
     out = {'schedule': op.schedule(), 'start_layout': op.layout(), 'state': {}}
+    if x0 is not None:
+        out['start'] = tuple(op.get_vector(v) for v in vectors)
     if recorders:
         op.iterate(max_iter - 1)
     else:
