@@ -495,12 +495,44 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
  *                      -- another variant, a communicator or ghost rows, a host-callback or block-Jacobi preconditioner in force
  *                      (the stored-tilde schedule), PRCG_FUSED=0, a replace hook -- and nothing falls back to a schedule that
  *                      cannot stop.  In a session begun with a threshold prcg_set_vector, prcg_set_scalars and prcg_set_iteration
- *                      are refused.  Sessions with several right-hand sides ignore the threshold.
+ *                      are refused.  Sessions with several right-hand sides ignore the threshold; the pipelined two-RHS session
+ *                      stops each column at a threshold of its own (prcg_set_stop_rhs below), the others cannot stop.
  *   prcg_get_stop      synchronises; *k_stop, *status of the open single session: the iteration it stopped at and why (1 converged,
  *                      2 breakdown), or -1 and 0 while it runs -- and for a session begun without a threshold.  Refused without an
  *                      open single session. */
 int prcg_set_stop(prcg_t* h, const double* rr_stop);
 int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status);
+
+/* ---- each column of a PIPELINED TWO-RHS session stopped at its own residual threshold, decided on the device ------------------
+ * Two load cases of one matrix almost never converge at the same iteration: the session freezes the column that is done and
+ * keeps iterating the other.
+ *   prcg_set_stop_rhs  rr_stop: NULL clears the thresholds (nrhs is then not looked at); else nrhs thresholds on r.r, rr_stop[c]
+ *                      column c's, each finite and >= 0, else PRCG_EINVAL naming the column (what was set before stays).  nrhs
+ *                      must be 2: only the pipelined two-RHS session can stop.  The thresholds are copied at the call and apply
+ *                      to sessions BEGUN afterwards with prcg_solve_begin_multi_pipe (signature unchanged); an open session is
+ *                      not affected.  They are independent of prcg_set_stop: single sessions ignore these thresholds as multi-RHS
+ *                      sessions ignore that one.  While they are set prcg_solve_begin_multi and
+ *                      prcg_solve_begin_multi_block_jacobi refuse (PRCG_EINVAL; the text says what is served and that
+ *                      prcg_set_stop_rhs(h, 0, NULL) clears): nothing falls back to a session that cannot stop.
+ *                      The rule is prcg_set_stop's, applied to column c's OWN row k of scalars after iteration k, and at k = 0 on
+ *                      the initial state:
+ *                        1. rr <= rr_stop[c]                                   -> stop, status 1 (converged);
+ *                        2. else !(0 < mu && mu < inf && 0 < nu && nu < inf)   -> stop, status 2 (breakdown);
+ *                        3. else go on (status 0, stop iteration -1).
+ *                      A column stopped at k_c keeps the complete state of iteration k_c -- x, r, p, s, w, u, with Jacobi r~, s~ --
+ *                      its scalar rows 0..k_c and coefficient rows 1..k_c are written, and its later rows and later history entries
+ *                      read as zero through prcg_get_scalars_rhs, prcg_get_coefficients_rhs and prcg_get_history_rhs.  The other
+ *                      column runs on unaffected: from the stop onward it carries, bit for bit, what it carries in a session
+ *                      without thresholds, and a column that never stops carries those bits throughout.  A threshold of 0 stops on
+ *                      an exactly zero residual or on breakdown only.  prcg_sync resolves the stops.  Once BOTH columns have
+ *                      stopped prcg_iteration reports max(k_0, k_1) and prcg_iterate is a no-op returning PRCG_OK; while a column
+ *                      still runs prcg_iteration counts what was launched.  prcg_get_stop keeps refusing multi-RHS sessions, and
+ *                      they keep having no setters.
+ *   prcg_get_stops_rhs synchronises; k_stop[c], status[c] of every column of the open multi-RHS session: the iteration it stopped
+ *                      at and why (1 converged, 2 breakdown), or -1 and 0 for a column that still runs -- and for every column of a
+ *                      session begun without thresholds.  Refused without an open multi-RHS session and with a null buffer. */
+int prcg_set_stop_rhs(prcg_t* h, int nrhs, const double* rr_stop);
+int prcg_get_stops_rhs(prcg_t* h, int32_t* k_stop, int32_t* status);
 
 /* ---- a BATCH of small independent systems, solved in one launch, one workgroup per system --------------------------------
  * Replaces the reference's loop over matrices and methods around `method(A, b, x0, max_iter, ...)` (numerical_experiments/

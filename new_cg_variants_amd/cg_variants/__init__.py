@@ -668,14 +668,19 @@ def _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwa
         hint = f"; blocks: {name.replace('_pcg_multi', '_bpcg_multi')}" if kind.startswith('a block') and name in ('hs_pcg_multi', 'pr_pcg_multi', 'm_pcg_multi') else ''
         raise ValueError(f'{name}: {kind} is not served by the two-RHS session (Jacobi(A), a callable that acts as a diagonal, or None{hint})')
     mask, light = _multi_callbacks(name, callbacks)
+    # rtol= / atol=: the pipelined two-RHS session stops each column by itself on the device (prcg.h: prcg_set_stop_rhs); the other
+    # multi-RHS functions never took the keywords and keep passing them by, like any keyword they do not know
+    rr_stop = None
+    if pipelined and (kwargs.get('rtol') is not None or kwargs.get('atol') is not None):
+        rr_stop = _stop_thresholds(name, kwargs.pop('rtol', None), kwargs.pop('atol', None), [B[0], B[1]])
     op = _operator(A, int(kwargs.get('device', 0)))
     op.set_replace_hook(None)
     op.clear_preconditioners()            # (what an earlier solve left on the cached operator)
     if pipelined:
-        op.begin_multi_pipe(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
+        op.begin_multi_pipe(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask, rr_stop=rr_stop)
     else:
         op.begin_multi(variant, B, X0, max_iter, inv_diag=inv_diag, hist_mask=mask)
-    return _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs)
+    return _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs, stopping=rr_stop is not None)
 
 
 def _multi_callbacks(name, callbacks):
@@ -696,21 +701,35 @@ def _multi_callbacks(name, callbacks):
     return mask, light
 
 
-def _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs):
-    """run the multi-RHS session just begun on `op` to max_iter - 1 iterations; the list of per-column trial dicts"""
+def _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs, stopping=False):
+    """run the multi-RHS session just begun on `op` to max_iter - 1 iterations; the list of per-column trial dicts.  stopping: the
+    session was begun with per-column thresholds (begin_multi_pipe's rr_stop) -- a column's light host callbacks are called up to
+    the iteration it stopped at and no further, the loop ends once every column has stopped, and each trial gains 'iterations'
+    and 'status' (the words of the batch functions)."""
     n, nrhs = A.shape[0], B.shape[0]
     outputs = [{'name': name, 'max_iter': max_iter, 'rhs': j} for j in range(nrhs)]
+    running = [True] * nrhs
 
     def call_host(k):
         for j in range(nrhs):
+            if not running[j]:
+                continue
             env = {'output': outputs[j], 'k': k, 'max_iter': max_iter, 'A': A, 'b': B[j], 'x0': X0[j], 'n': n,
                    'kwargs': kwargs, 'callbacks': callbacks}
             for cb in light:
                 cb(**env)
 
+    def update_running():                  # the state of its stop iteration was the last one a column's callbacks saw
+        if stopping:
+            for j, (k_stop, _) in enumerate(op.stops_rhs()):
+                running[j] = k_stop < 0
+
     if light:
         call_host(0)
         for k in range(1, max_iter):
+            update_running()
+            if not any(running):
+                break
             op.iterate(1)
             call_host(k)
     else:
@@ -718,6 +737,10 @@ def _multi_drive(op, name, A, B, X0, max_iter, light, callbacks, kwargs):
     op.sync()
     for j in range(nrhs):
         outputs[j].update(op.history(rhs=j))
+    if stopping:
+        for j, (k_stop, status) in enumerate(op.stops_rhs()):
+            outputs[j]['iterations'] = k_stop if status else max_iter - 1
+            outputs[j]['status'] = ('max_iter', 'converged', 'breakdown')[status]
     return outputs
 
 
@@ -832,7 +855,10 @@ def _make_multi_pipe(variant, name, preconditioned, line):
            f'shaped like {single}\'s.  One pipelined session (prcg.h: prcg_solve_begin_multi_pipe): per iteration one update launch for both '
            'systems and ONE product of four vectors, so the operator is streamed once for both.  Prefer it where the operator dominates an '
            'iteration\'s traffic (assembled FEM matrices); on band and stencil operators two calls of the single function, one launch per '
-           'iteration each, may be faster (profiles/multi_rhs_pipe.md).  (4, n) is refused: nothing falls back to two sessions.')
+           'iteration each, may be faster (profiles/multi_rhs_pipe.md).  (4, n) is refused: nothing falls back to two sessions.  '
+           'rtol= / atol= (one value, or one per system): each system stops by itself on the device at r.r <= max(rtol ||b||, atol)^2 or '
+           'on breakdown (prcg.h: prcg_set_stop_rhs) while the other runs on; each trial then carries \'iterations\' and \'status\' '
+           '(\'converged\' / \'breakdown\' / \'max_iter\') and its history is zero beyond its stop.')
     if preconditioned:
         def f(A, B, X0, max_iter, preconditioner=None, callbacks=[], **kwargs):
             return _run_multi(variant, name, A, B, X0, max_iter, preconditioner, callbacks, kwargs)

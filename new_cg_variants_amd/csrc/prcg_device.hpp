@@ -140,6 +140,34 @@ __device__ __forceinline__ void block_reduce_store2(double (&acc)[2 * NQ], doubl
     }
 }
 
+// ... of a launch in which a column may be FROZEN (k_pipe2_update_stop): live[c] is the same in every thread of the launch (a scalar).
+// A living column's sums take the very steps of block_reduce_store2 -- wave_sum per accumulator, lane 0 into red, the barrier,
+// thread q adds the four wave sums in order -- so its partial row carries the same bits; a frozen column's accumulators are not
+// summed and its partial row is not written.
+template <int NQ>
+__device__ __forceinline__ void block_reduce_store2_live(double (&acc)[2 * NQ], double* part0, double* part1, int slot0, const bool (&live)[2]) {
+    __shared__ double red[kWaves][2 * NQ];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (!live[c]) continue;                                 // scalar branch
+#pragma unroll
+        for (int q = NQ * c; q < NQ * (c + 1); ++q) {
+            const double v = wave_sum(acc[q]);
+            if (lane == 0) red[wv][q] = v;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * NQ && live[threadIdx.x < NQ ? 0 : 1]) {
+        double v = red[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) v += red[w][threadIdx.x];
+        double* part = threadIdx.x < NQ ? part0 : part1;
+        const int q = threadIdx.x < NQ ? threadIdx.x : threadIdx.x - NQ;
+        part[(size_t)blockIdx.x * kPartialStride + slot0 + q] = v;
+    }
+}
+
 // Every block of a launch sums the block partials the PREVIOUS launch left (slots slot0 .. slot0 + NQ) itself, in
 // the order of k_reduce_final (a 256-thread tree: thread v rows v, v + 256, ...; butterfly over each 64 lanes; the
 // four wave sums in order) whatever the block's own size: a block of NWAVES < 4 waves lets each thread play
@@ -208,6 +236,20 @@ __device__ __forceinline__ int stop_rule(double mu, double nu, double rr, double
     if (rr <= thr) v = 1;                                                        // converged
     else if (!(0.0 < mu && mu < inf && 0.0 < nu && nu < inf)) v = 2;             // breakdown: a = nu / mu is not an SPD system's
     return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Head of a product launch with the epilogue kEpiNoneStop (ProductStop, prcg_kernels.h): true if the launch has nothing to do --
+// its column (NV == 4: both columns, the second word follows the first) stopped BEFORE iteration fz.word_k.  The words were
+// complete before the launch began, every wave reads the same values: a scalar branch, taken before anything is loaded or stored.
+template <int NV>
+__device__ __forceinline__ bool product_stopped(const FusedPrev& fz) {
+    const int at0 = __builtin_amdgcn_readfirstlane(fz.word[0]);
+    bool gone = at0 >= 0 && at0 < fz.word_k;
+    if constexpr (NV == 4) {
+        const int at1 = __builtin_amdgcn_readfirstlane(fz.word[2]);
+        gone = gone && at1 >= 0 && at1 < fz.word_k;
+    }
+    return gone;
 }
 
 // Prologue of the single-GPU one-launch pipelined iteration (k_win_tiles, k_sell_tiles, k_sell_win, k_spmv_tiles; also the

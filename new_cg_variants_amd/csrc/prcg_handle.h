@@ -192,6 +192,12 @@ struct Session {
                                  // once a launch's prologue, the final reduction or the one-workgroup solver has stopped it
     int stopped_k = -1;          // what prcg_sync has read from the word: the iteration whose state the session holds (-1: running) ...
     int stop_status = 0;         // ... and why (1 converged, 2 breakdown)
+    // ---- each column stopped at its own threshold (prcg_set_stop_rhs; the pipelined two-RHS session) ----
+    bool stop_rhs = false;               // the session was begun with per-column thresholds ...
+    double thr_rhs[2] = {0.0, 0.0};      // ... on r.r of column c; its stop word: Handle::stop_words_rhs + 2 c
+    int stopped_k_rhs[2] = {-1, -1};     // what prcg_sync has read from the words: the iteration whose state column c holds (-1: running) ...
+    int stop_status_rhs[2] = {0, 0};     // ... and why (1 converged, 2 breakdown)
+    bool all_stopped_rhs() const { return stop_rhs && stopped_k_rhs[0] >= 0 && stopped_k_rhs[1] >= 0; }
 };
 
 // One PAIR GROUP of a session with two or four right-hand sides: the interleaved n x 2 arrays X, R, P, S, RT of two columns
@@ -276,6 +282,10 @@ struct Handle : Operator, Session {
     // residual threshold for single sessions begun from now on (prcg_set_stop); the word a session with one stops itself through
     bool stop_set = false; double stop_thr = 0.0;
     DevBuf stop_word;
+    // ... and per column for pipelined two-RHS sessions begun from now on (prcg_set_stop_rhs); the columns' words: four ints, column c's
+    // {k, status} at 2 c (SmallStop's layout), allocated once, armed to {-1, 0} when such a session begins
+    bool stop_rhs_set = false; double stop_rhs_thr[2] = {0.0, 0.0};
+    DevBuf stop_words_rhs;
     std::vector<double> cb_in, cb_out;
     DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
 
@@ -382,6 +392,9 @@ int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, S
 int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask);
 bool spmm4_one_launch(const prcg_t* h);
 int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1);
+// ... the product of iteration k of a pipelined two-RHS session with thresholds: the stop forms of the same launches (ProductStop,
+// prcg_kernels.h) -- each two-vector launch skips by its own column's word, the one four-vector launch only when both columns stopped before k
+int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k);
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which = 0);
 void note_partials_launch(prcg_t* h, int grid);
 int exchange(prcg_t* h, double* vec_ext, int nc, hipStream_t st);
@@ -408,5 +421,7 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
 
 // ---- prcg_multi.cpp: iteration k of the open session with two or four right-hand sides (Session::rhs2) ----
 int iterate_multi(prcg_t* h, int k);
+// ... and what prcg_sync does for a session whose columns stop at their own thresholds (Session::stop_rhs): read the stop words
+int resolve_stops_rhs(prcg_t* h);
 
 }  // namespace prcg

@@ -135,7 +135,19 @@ enum SpmvEpilogue {
     kEpiCGOneJ = 16, // ... with Jacobi
     kEpiGVOne = 17,  // window kernels only: ONE launch per Ghysels-Vanroose iteration (unpreconditioned)
     kEpiPROneQ = 18, // window kernels only: one-launch predict-and-recompute iteration on the PACKED state, pairs (z, zs) and (p, x) (PrOne::q_old, px_old)
+    kEpiNoneStop = 19,   // two- and four-vector products only: the plain epilogue, in a launch that may have nothing to do (ProductStop below)
 };
+constexpr bool epi_plain(int e) { return e == kEpiNone || e == kEpiNoneStop; }     // no inner products: nothing but the product is stored
+// The product launch of iteration k of a pipelined two-RHS session whose columns stop at their own thresholds (prcg_set_stop_rhs;
+// kEpiNoneStop: instantiations of their own, so that a session without thresholds launches the kernels it always did).  word: the
+// stop word of the launch's column, two ints laid out as SmallStop's (below).  The product of iteration k belongs to the state of
+// iteration k, so a column that stops AT k still gets it: the launch returns at once, before anything is loaded or stored, only
+// if 0 <= word[0] < k.  The four-vector launch (sliced rows) serves both columns: `word` is then column 0's, column 1's follows
+// it (word + 2), and the launch returns only if BOTH stopped before k -- otherwise it runs as it is: a frozen column's sources have
+// not changed, so its destination is rewritten with the bits it holds.  The word was complete before the launch began (kernel
+// boundary); every wave reads the same value through readfirstlane and leaves on a scalar branch.  Travels in FusedPrev::word /
+// word_k, which the plain epilogue does not use otherwise.
+struct ProductStop { int* word; int k; };
 constexpr bool epi_pr_one(int e) { return e == kEpiPROne || e == kEpiPROneJ || e == kEpiPROneQ; }
 constexpr bool epi_cg_w(int e) { return e == kEpiCGW || e == kEpiCGWJ; }
 constexpr bool epi_gv_w(int e) { return e == kEpiGVW || e == kEpiGVWJ; }
@@ -180,6 +192,9 @@ int launch_spmv(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, 
 // [w u] = A [r s] on interleaved pairs.  write_mask: 1 = first, 2 = second, 3 = both.
 int launch_spmm2(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
                  const double* rs, double* wu, int write_mask, TileKnobs kn = TileKnobs{});
+// ... of a session whose columns stop (ProductStop): the same product, or nothing at all
+int launch_spmm2_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
+                      const double* rs, double* wu, int write_mask, const ProductStop& stop, TileKnobs kn = TileKnobs{});
 
 // One launch per iteration of pipe_pr_cg / pipe_pr_m_cg on ONE GPU: [w u] = A [r s] with the
 // vector update of the following iteration applied to each row as soon as its (w_i,u_i)
@@ -217,6 +232,8 @@ int launch_win_spmv(hipStream_t st, const WinDev& A, const WTile* tiles, int nti
                     SpmvEpilogue epi, const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu);
 int launch_win_spmm2(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
                      int write_mask, int per_cu);
+int launch_win_spmm2_stop(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
+                          int write_mask, const ProductStop& stop, int per_cu);      // (ProductStop: the same product, or nothing at all)
 int launch_win_pipe_fused(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const FusedState& f,
                           int per_cu);
 // waves per workgroup the one-launch pipelined iteration WOULD take (prcg_debug_layout before any launch of a session; after
@@ -304,6 +321,11 @@ int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int 
 // (n + g) x 2 with the spare entries of every product source, destinations n x 2; per column the bits of launch_sell_spmm2
 int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
                       double* dst0, double* dst1, int per_cu);
+// ... of a session whose columns stop (ProductStop): the same products, or nothing at all; the four-vector launch reads both words
+int launch_sell_spmm2_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
+                           const ProductStop& stop, int per_cu);
+int launch_sell_spmm4_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
+                           double* dst0, double* dst1, const ProductStop& stop, int per_cu);
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu);
 // New values on an unchanged pattern (prcg_update_values): sval, the re-laid value array A.val points to, rewritten from val_csr, the
 // nnz values in the caller's CSR order -- one wave per slice, every position of a slice written (no nonzero: 0), so that sval holds
@@ -464,6 +486,12 @@ struct Pipe2Args {
 };
 int launch_pipe2_update(hipStream_t st, const Pipe2Args& a);   // x, p, r, s, (r~, s~) of both columns; partials mu .. rr (slots 0..4) of part[c]
 int launch_pipe2_dots(hipStream_t st, const Pipe2Args& a);     // the five sums of the state as it stands: no update (initialisation)
+// The update of a session whose columns stop at their own thresholds (prcg_set_stop_rhs).  words: four ints in device memory, column
+// c's stop word at words + 2 c ({iteration it stopped at or -1, status}: SmallStop's layout; written by launch_reduce_final_stop).
+// A column whose word names an iteration is FROZEN: the launch loads and stores nothing of it -- no vector, no coefficient row,
+// no partial row (its reduction returns at once as well).  Both frozen: the launch returns in its prologue.  The other column
+// carries the bits of launch_pipe2_update: the same expressions, the same accumulation order, the same tree.
+int launch_pipe2_update_stop(hipStream_t st, const Pipe2Args& a, const int* words);
 
 struct PrArgs {   // non-pipelined predict-and-recompute (pr_pcg / m_pcg)
     int64_t n;

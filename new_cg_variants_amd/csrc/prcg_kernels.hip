@@ -246,6 +246,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(
     Coefs cf = {0.0, 0.0, 0.0};
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
+    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (nothing loaded, nothing stored, no barrier met)
     if constexpr (epi_fused(EPI)) {
         // ep_r = the reduced inner products of the previous iteration; bit 2 of write_mask =
         // Meurant's prediction; aux = where alpha, beta, nu_pred of this iteration are kept
@@ -303,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(
 
     if constexpr (epi_fused(EPI)) { if constexpr (!epi_prec(EPI)) acc[4] = acc[3]; block_reduce_store<5>(acc, partials, 0); }
     else if constexpr (EPI == kEpiCG) block_reduce_store<5>(acc, partials, 0);
-    else if constexpr (EPI != kEpiNone) {
+    else if constexpr (!epi_plain(EPI)) {
         double a3[3] = {acc[0], acc[1], acc[2]};
         block_reduce_store<3>(a3, partials, 0);
     }
@@ -1028,6 +1029,16 @@ int launch_spmm2(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles,
     if (ntiles <= 0) return 0;
     return launch_tiles_steps<2, kEpiNone>(steps, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr,
                                            nullptr, kn);
+}
+
+int launch_spmm2_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
+                      const double* rs, double* wu, int write_mask, const ProductStop& stop, TileKnobs kn)
+{
+    if (ntiles <= 0) return 0;
+    FusedPrev fz{};
+    fz.word = stop.word; fz.word_k = stop.k;
+    return launch_tiles_steps<2, kEpiNoneStop>(steps, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr,
+                                               nullptr, kn, nullptr, fz);
 }
 
 int launch_pipe_fused(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps, const FusedState& f, TileKnobs kn)

@@ -273,15 +273,32 @@ __global__ __launch_bounds__(kBlock) void k_pr2_dots(Pr2Args a, int trips) {
 // Per row and column the expressions of k_pipe_update (prcg_kernels.hip) in its order, multiply then add; column c has its own
 // Coefs and its own five accumulators [mu dl gm nu rr]; a thread's twelve 16-byte loads (two rows x two columns x three arrays;
 // sixteen with Jacobi, and two of d) are issued before any arithmetic.  Sums: the tree described at the head of this file.
-template <bool PREC, bool DOTS_ONLY>
-__global__ __launch_bounds__(kBlock) void k_pipe2_update(Pipe2Args a, int trips) {
+//
+// STOP (k_pipe2_update_stop; a session whose columns stop at their own thresholds, prcg_set_stop_rhs): `words` holds the columns' stop
+// words, column c's at words + 2 c.  The reduction that ended an earlier iteration wrote them (k_reduce_final_stop), so they were
+// complete before this launch began: every wave reads the same two values through readfirstlane and `live[c]` is a scalar.  A
+// column that has stopped is FROZEN -- the launch skips it on scalar branches: no scalar row read, no coefficient row, no load,
+// no store, no partial row -- and with both frozen the kernel returns here, before anything else.  The living column executes
+// the statements below in their order: its expressions, its accumulators and its tree are those of the kernel without STOP.
+template <bool PREC, bool DOTS_ONLY, bool STOP>
+__device__ __forceinline__ void pipe2_update_body(const Pipe2Args& a, int trips, const int* __restrict__ words) {
+    bool live[2] = {true, true};
+    if constexpr (STOP) {
+        live[0] = __builtin_amdgcn_readfirstlane(words[0]) < 0;
+        live[1] = __builtin_amdgcn_readfirstlane(words[2]) < 0;
+        if (!live[0] && !live[1]) return;
+    }
     Coefs cf[2] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
     if constexpr (!DOTS_ONLY) {
-        cf[0] = predict(a.dots_prev, a.meurant);
-        cf[1] = predict(a.dots_prev + kPartialStride, a.meurant);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (STOP && !live[c]) continue;
+            cf[c] = predict(a.dots_prev + c * kPartialStride, a.meurant);
+        }
         if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
+                if (STOP && !live[c]) continue;
                 double* co = a.coef_out + c * kPr2CoefStride;
                 co[0] = cf[c].al; co[1] = cf[c].bt; co[2] = cf[c].nup;
             }
@@ -309,6 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_pipe2_update(Pipe2Args a, int trips)
             const int64_t il = ok[e] ? ie : base;               // clamped: branch-free loads
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
+                if (STOP && !live[c]) continue;                 // scalar branch: a frozen column is not loaded
                 xp[c][e] = XP[c][il];
                 rs[c][e] = RS[c][il];
                 if constexpr (!DOTS_ONLY) wu[c][e] = WU[c][il];
@@ -323,6 +341,7 @@ __global__ __launch_bounds__(kBlock) void k_pipe2_update(Pipe2Args a, int trips)
             const int64_t ie = base + e * kBlock;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
+                if (STOP && !live[c]) continue;                 // ... nor updated, nor stored
                 double* ac = acc + 5 * c;
                 const double2 xpv = xp[c][e], rsv = rs[c][e];
                 if constexpr (DOTS_ONLY) {
@@ -366,7 +385,14 @@ __global__ __launch_bounds__(kBlock) void k_pipe2_update(Pipe2Args a, int trips)
         }
     }
     if constexpr (!PREC) { acc[4] = acc[3]; acc[9] = acc[8]; }      // unpreconditioned: rr IS nu
-    block_reduce_store2<5>(acc, a.part0, a.part1, 0);
+    if constexpr (STOP) block_reduce_store2_live<5>(acc, a.part0, a.part1, 0, live);
+    else block_reduce_store2<5>(acc, a.part0, a.part1, 0);
+}
+template <bool PREC, bool DOTS_ONLY>
+__global__ __launch_bounds__(kBlock) void k_pipe2_update(Pipe2Args a, int trips) { pipe2_update_body<PREC, DOTS_ONLY, false>(a, trips, nullptr); }
+template <bool PREC>
+__global__ __launch_bounds__(kBlock) void k_pipe2_update_stop(Pipe2Args a, int trips, const int* __restrict__ words) {
+    pipe2_update_body<PREC, false, true>(a, trips, words);
 }
 
 }  // namespace
@@ -424,6 +450,12 @@ int launch_pipe2_update(hipStream_t st, const Pipe2Args& a) {
     const Chunking c = chunking(a.n);
     if (a.d) hipLaunchKernelGGL((k_pipe2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     else     hipLaunchKernelGGL((k_pipe2_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_pipe2_update_stop(hipStream_t st, const Pipe2Args& a, const int* words) {
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_pipe2_update_stop<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, words);
+    else     hipLaunchKernelGGL((k_pipe2_update_stop<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, words);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 int launch_pipe2_dots(hipStream_t st, const Pipe2Args& a) {

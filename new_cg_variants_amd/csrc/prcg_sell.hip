@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     const double* __restrict__ ep_r, const double* __restrict__ ep_d, double* __restrict__ ep_st,
     double* __restrict__ partials, double* __restrict__ aux, FusedPrev fz)
 {
-    static_assert(NV != 4 || EPI == kEpiNone, "the four-vector product has the plain epilogue only");
+    static_assert(NV != 4 || epi_plain(EPI), "the four-vector product has the plain epilogue only");
     using V = typename VecT<NV>::type;
     const V* __restrict__ X = reinterpret_cast<const V*>(xin_);
     const double2* __restrict__ XA = reinterpret_cast<const double2*>(xin_);      // NV = 4: the two source pair arrays
@@ -110,6 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     Coefs cf = {0.0, 0.0, 0.0};
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
+    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (nothing loaded, nothing stored, no barrier met)
     if constexpr (epi_fused(EPI)) {
         // inner products of the previous iteration: one row of partials per workgroup of the previous launch, summed by
         // every workgroup of this one in the fixed 256-thread tree (as k_spmv_tiles / k_win_tiles do); a session with a stop word
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
 
     if constexpr (epi_fused(EPI)) { if constexpr (!epi_prec(EPI)) acc[4] = acc[3]; block_reduce_store<5>(acc, partials, 0); }
     else if constexpr (EPI == kEpiCG) block_reduce_store<5>(acc, partials, 0);
-    else if constexpr (EPI != kEpiNone) {
+    else if constexpr (!epi_plain(EPI)) {
         double a3[3] = {acc[0], acc[1], acc[2]};
         block_reduce_store<3>(a3, partials, 0);
     }
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     const V* __restrict__ X = reinterpret_cast<const V*>(xin_);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    static_assert(NV != 4 || EPI == kEpiNone, "the four-vector product has the plain epilogue only");
+    static_assert(NV != 4 || epi_plain(EPI), "the four-vector product has the plain epilogue only");
     using PV = typename PageT<NV>::type;
     const PV* __restrict__ XPG = reinterpret_cast<const PV*>(xin_);
     const PV* __restrict__ XPG1 = reinterpret_cast<const PV*>(ep_r);       // NV = 4: the second source pair array
@@ -301,6 +302,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     Coefs cf = {0.0, 0.0, 0.0};
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
+    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (as k_sell_tiles)
     if constexpr (epi_fused(EPI)) {
         if (!fused_prologue<kWaves>(fz, ep_r, (write_mask >> 2) & 1, aux, cf)) return;       // (as k_sell_tiles)
     }
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     if (t >= nslices) {                                   // (every wave joins the block's reduction)
         if constexpr (epi_fused(EPI)) { if constexpr (!epi_prec(EPI)) acc[4] = acc[3]; block_reduce_store<5>(acc, partials, 0); }
         else if constexpr (EPI == kEpiCG) block_reduce_store<5>(acc, partials, 0);
-        else if constexpr (EPI != kEpiNone) { double a3[3] = {acc[0], acc[1], acc[2]}; block_reduce_store<3>(a3, partials, 0); }
+        else if constexpr (!epi_plain(EPI)) { double a3[3] = {acc[0], acc[1], acc[2]}; block_reduce_store<3>(a3, partials, 0); }
         return;
     }
 
@@ -402,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
 
     if constexpr (epi_fused(EPI)) { if constexpr (!epi_prec(EPI)) acc[4] = acc[3]; block_reduce_store<5>(acc, partials, 0); }
     else if constexpr (EPI == kEpiCG) block_reduce_store<5>(acc, partials, 0);
-    else if constexpr (EPI != kEpiNone) {
+    else if constexpr (!epi_plain(EPI)) {
         double a3[3] = {acc[0], acc[1], acc[2]};
         block_reduce_store<3>(a3, partials, 0);
     }
@@ -579,6 +581,24 @@ int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int 
 {
     if (nslices <= 0) return 0;
     return launch_sell<4, kEpiNone>(st, A, slices, nslices, src0, dst0, 3, src1, nullptr, dst1, nullptr, nullptr, FusedPrev{}, per_cu);
+}
+
+int launch_sell_spmm2_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
+                           const ProductStop& stop, int per_cu)
+{
+    if (nslices <= 0) return 0;
+    FusedPrev fz{};
+    fz.word = stop.word; fz.word_k = stop.k;
+    return launch_sell<2, kEpiNoneStop>(st, A, slices, nslices, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, fz, per_cu);
+}
+
+int launch_sell_spmm4_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
+                           double* dst0, double* dst1, const ProductStop& stop, int per_cu)
+{
+    if (nslices <= 0) return 0;
+    FusedPrev fz{};
+    fz.word = stop.word; fz.word_k = stop.k;                 // (column 1's word follows column 0's: product_stopped<4>)
+    return launch_sell<4, kEpiNoneStop>(st, A, slices, nslices, src0, dst0, 3, src1, nullptr, dst1, nullptr, nullptr, fz, per_cu);
 }
 
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu)

@@ -1221,6 +1221,7 @@ int prcg_iterate(prcg_t* h, int iters) {
     CHECK(h, h->in_session, "prcg_iterate: no open session");
     CHECK(h, iters >= 0, "prcg_iterate: negative count");
     if (h->stopped_k >= 0) return PRCG_OK;       // stopped at its threshold (prcg_sync has seen the word): a no-op
+    if (h->all_stopped_rhs()) return PRCG_OK;    // ... both columns of a pipelined two-RHS session at theirs (prcg_set_stop_rhs)
     CHECK(h, h->k + iters <= h->max_iter, "prcg_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters,
           h->max_iter, h->k);
     HIPCHK(h, hipSetDevice(h->dev));
@@ -1283,7 +1284,8 @@ int prcg_sync(prcg_t* h) {
                                             "(communication stream starved or a peer stalled); results are invalid. "
                                             "PRCG_FUSED_COMM=0 selects the two-kernel schedule");
     }
-    return resolve_stop(h);
+    if (int rc = resolve_stop(h)) return rc;
+    return resolve_stops_rhs(h);
 }
 
 int prcg_set_stop(prcg_t* h, const double* rr_stop) {

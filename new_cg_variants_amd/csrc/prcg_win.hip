@@ -1038,6 +1038,7 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
     double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     Coefs cf = {0.0, 0.0, 0.0};
     constexpr bool PR1 = epi_pr_one(EPI);
+    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (nothing requested, loaded or stored, no barrier met)
     if constexpr ((FUSED || PR1) && DEF == 0) {
         // inner products of the previous iteration: still one row of partials per block of the
         // previous launch -- every block of this launch sums them in the same fixed order
@@ -1274,7 +1275,7 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
     else if constexpr (PR1) { if constexpr (EPI != kEpiPROneJ) acc[4] = acc[3]; win_block_reduce_store<WPB, 5>(acc, partials); }
     else if constexpr (epi_cg_w(EPI) || epi_gv_w(EPI) || epi_lag(EPI)) win_block_reduce_store<WPB, 5>(acc, partials);
     else if constexpr (EPI == kEpiCG) win_block_reduce_store<WPB, 5>(acc, partials);
-    else if constexpr (EPI != kEpiNone) {
+    else if constexpr (!epi_plain(EPI)) {
         double a3[3] = {acc[0], acc[1], acc[2]};
         win_block_reduce_store<WPB, 3>(a3, partials);
     }
@@ -1594,6 +1595,15 @@ int launch_win_spmm2(hipStream_t st, const WinDev& A, const WTile* tiles, int nt
     if (ntiles <= 0) return 0;
     return launch_win<2, kEpiNone>(geom, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    FusedPrev{}, per_cu);
+}
+
+int launch_win_spmm2_stop(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
+                          int write_mask, const ProductStop& stop, int per_cu)
+{
+    if (ntiles <= 0) return 0;
+    FusedPrev fz{};
+    fz.word = stop.word; fz.word_k = stop.k;
+    return launch_win<2, kEpiNoneStop>(geom, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, fz, per_cu);
 }
 
 int launch_win_pipe_fused(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const FusedState& f,

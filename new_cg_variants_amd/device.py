@@ -430,7 +430,7 @@ class DeviceCSR:
                                                                   int(max_iter), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
-    def begin_multi_pipe(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0):
+    def begin_multi_pipe(self, variant, B, X0, max_iter, inv_diag=None, hist_mask=0, rr_stop=None):
         """Two right-hand sides in ONE pipelined session (prcg.h: prcg_solve_begin_multi_pipe): B, X0 of shape (2, n), row j =
         right-hand side / start vector of system j.  Every iteration streams the operator once for both systems: the pipelined
         iteration's [w u] = A [r s] of both columns is one product of four vectors (one launch on sliced-row operators, see
@@ -441,7 +441,12 @@ class DeviceCSR:
         on band and stencil operators two single sessions, each ONE launch per iteration, may well be faster -- see
         profiles/multi_rhs_pipe.md for what was measured.
         iterate / sync / k serve the session as they are; state is read per column: get_vector(name, rhs=j) (x, r, p, s, w, u; with
-        Jacobi rt, st), get_scalars(k, rhs=j), get_coefficients(k, rhs=j), history(rhs=j)."""
+        Jacobi rt, st), get_scalars(k, rhs=j), get_coefficients(k, rhs=j), history(rhs=j).
+        rr_stop: None, or two thresholds on r.r, one per column, each finite and >= 0: THIS session then stops each column by itself
+        on the device at its own threshold, converged or broken down, by the rule of prcg.h: prcg_set_stop_rhs -- the stopped
+        column keeps the state of its stop iteration, the other runs on with the bits it has without thresholds; stops_rhs()
+        tells where and why."""
+        thr = None if rr_stop is None else batch_thresholds('rr_stop', np.asarray(rr_stop, dtype=np.float64).reshape(-1), 2)
         B = L.f64(B)
         if B.shape != (2, self.n):
             raise ValueError(f'begin_multi_pipe: B must have shape (2, {self.n}) -- the pipelined session serves exactly two right-hand '
@@ -450,6 +455,14 @@ class DeviceCSR:
         if X0.shape != (2, self.n):
             raise ValueError(f'begin_multi_pipe: X0 must have shape (2, {self.n}), the same as B, got {tuple(X0.shape)}')
         dv = _diagonal('begin_multi_pipe', inv_diag, self.n)
+        self._check(self._lib.prcg_set_stop_rhs(self._h, 2, L.ptr(thr)))        # (None clears what an earlier session set)
+        try:
+            self._begin_multi_pipe(variant, B, X0, max_iter, dv, hist_mask)
+        finally:
+            if thr is not None:                # the thresholds are this session's: the handle's other entries are served again
+                self._check(self._lib.prcg_set_stop_rhs(self._h, 0, None))
+
+    def _begin_multi_pipe(self, variant, B, X0, max_iter, dv, hist_mask):
         self._check(self._lib.prcg_solve_begin_multi_pipe(self._h, int(variant), 2, _row_pointers(B), _row_pointers(X0), int(max_iter),
                                                           L.ptr(dv), int(hist_mask)))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
@@ -488,6 +501,15 @@ class DeviceCSR:
         k_stop, status = C.c_int32(-1), C.c_int32(0)
         self._check(self._lib.prcg_get_stop(self._h, C.byref(k_stop), C.byref(status)))
         return int(k_stop.value), int(status.value)
+
+    def stops_rhs(self):
+        """[(k_stop, status), (k_stop, status)] of the open two-RHS session's columns: the iteration a column stopped at and why
+        (1 converged, 2 breakdown); (-1, 0) for a column that still runs, and for both in a session begun without rr_stop (four
+        entries in a four-RHS session).  Synchronises."""
+        k_stop, status = np.full(4, -1, dtype=np.int32), np.zeros(4, dtype=np.int32)
+        self._check(self._lib.prcg_get_stops_rhs(self._h, L.ptr(k_stop), L.ptr(status)))
+        nrhs = 4 if self.schedule()['rhs4'] else 2
+        return [(int(k_stop[c]), int(status[c])) for c in range(nrhs)]
 
     def schedule(self):
         """Flags of the schedule the current session runs (prcg.h PRCG_SCHED_*)."""
