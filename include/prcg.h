@@ -503,6 +503,36 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist);
 int prcg_set_stop(prcg_t* h, const double* rr_stop);
 int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status);
 
+/* ---- a single pipelined session WITH POINT-BLOCK JACOBI stopped at a residual threshold, decided on the device ----------------
+ * Blocks pay off in iteration counts, so this is the session whose max_iter is hardest to guess.  It runs the stored-tilde
+ * schedule (an update launch, the product, one launch that applies the blocks to w and u), which prcg_set_stop does not serve:
+ * it has a setter of its own, and every launch of an iteration a stop form of its own.
+ *   prcg_set_stop_block_jacobi  rr_stop: NULL clears the threshold; else *rr_stop is the threshold on r.r, finite and >= 0, else
+ *                      PRCG_EINVAL (what was set before stays).  It is copied at the call and applies to sessions BEGUN afterwards
+ *                      with prcg_solve_begin; an open session is not affected.  While it is set prcg_solve_begin serves PRCG_PIPE_PR,
+ *                      PRCG_PIPE_PR_M, PRCG_PIPE_P and PRCG_PIPE_P_M on one GPU with uniform or variable blocks in force
+ *                      (prcg_set_block_jacobi / prcg_set_block_jacobi_var, or built on the device), and refuses everything else
+ *                      with PRCG_EINVAL and a text that names this setter and how to clear it: another variant, no blocks in force
+ *                      (such a session stops through prcg_set_stop), an inv_diag argument (it overrides the blocks), a host-callback
+ *                      preconditioner, a communicator or ghost rows, a replace hook; prcg_solve_begin_multi,
+ *                      prcg_solve_begin_multi_pipe and prcg_solve_begin_multi_block_jacobi refuse as well.  Nothing falls back to a
+ *                      session that cannot stop.  Independent of prcg_set_stop: with both set, that setter's refusal of a session
+ *                      with blocks stands.  The rule is prcg_set_stop's, on row k of the scalars after iteration k and on row 0:
+ *                        1. rr <= *rr_stop                                     -> stop, status 1 (converged);
+ *                        2. else !(0 < mu && mu < inf && 0 < nu && nu < inf)   -> stop, status 2 (breakdown);
+ *                        3. else go on.
+ *                      Iteration k is: update k (skipped if the session stopped at k - 1 or earlier); the reduction that sums row
+ *                      k and applies the rule; the product and the block launch of k, which belong to the state of k and are
+ *                      skipped only if the session stopped BEFORE k.  A session stopped at k therefore holds the complete state of
+ *                      iteration k -- x, r, p, s, w, u, r~, s~, u~, w~, scalar rows 0..k, coefficient rows 1..k -- and every later
+ *                      launch returns at once and writes nothing.  A session that does not stop carries the bits of the session
+ *                      without a threshold; a session begun without one launches the kernels it always did.  prcg_sync resolves the
+ *                      stop and prcg_get_stop reads it; afterwards prcg_iteration is k, prcg_iterate is a no-op, scalar and
+ *                      coefficient rows and history entries beyond k read as zero.  prcg_set_vector, prcg_set_scalars and
+ *                      prcg_set_iteration are refused in such a session; recorders are allowed as with prcg_set_stop.  The
+ *                      one-workgroup solver is never taken: a session with blocks runs this schedule whatever n. */
+int prcg_set_stop_block_jacobi(prcg_t* h, const double* rr_stop);
+
 /* ---- each column of a PIPELINED TWO-RHS session stopped at its own residual threshold, decided on the device ------------------
  * Two load cases of one matrix almost never converge at the same iteration: the session freezes the column that is done and
  * keeps iterating the other.

@@ -509,7 +509,9 @@ def _state_vectors(variant, prec):
 _PIPELINED = (L.PIPE_PR, L.PIPE_PR_M, L.PIPE_P, L.PIPE_P_M)
 
 
-def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w_replace=None):
+def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w_replace=None, block_stop=False):
+    """block_stop: the caller is a pipe_*_bpcg function, whose preconditioner is a block-Jacobi object: rtol= / atol= then reach the
+    block session's own threshold (prcg.h: prcg_set_stop_block_jacobi) instead of being refused"""
     device = int(kwargs.get('device', 0))
     if A.format != 'csr':
         A = A.tocsr()
@@ -531,7 +533,7 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
             raise ValueError(f'{name}: b must have shape ({n},), got {tuple(bvec.shape)}')
         thr = _stop_thresholds(name, kwargs.pop('rtol', None), kwargs.pop('atol', None), [bvec])
         if thr is not None:
-            if prec_fn is not None:
+            if prec_fn is not None and not block_stop:
                 raise ValueError(f'{name}: rtol= / atol= serve no preconditioner but a diagonal scaling: a callable or block-Jacobi '
                                  'preconditioner runs the stored-tilde schedule, which cannot stop on the device')
             rr_stop = float(thr[0])
@@ -579,7 +581,7 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
     if var:
         on_device = isinstance(preconditioner, DeviceVarBlockJacobi)       # built there: the object's blocks are never read
         try:
-            op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask,
+            op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, rr_stop=rr_stop,
                      block_jacobi_var=(preconditioner.block_ptr, None if on_device else preconditioner.inv_blocks))
         except ValueError as e:
             if 'diagonal block' not in str(e):
@@ -587,13 +589,13 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
             raise ValueError('DeviceVarBlockJacobi: ' + str(e).split(': ', 1)[-1]) from None
     elif built:
         try:
-            op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=(preconditioner.bs, None))
+            op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=(preconditioner.bs, None), rr_stop=rr_stop)
         except ValueError as e:
             if 'diagonal block' not in str(e):
                 raise
             raise ValueError('DeviceBlockJacobi: ' + str(e).split(': ', 1)[-1]) from None      # the library's text, this object's name
     elif blocks is not None:
-        op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=blocks)
+        op.begin(variant, b, x0, max_iter, x_true=x_true, hist_mask=mask, block_jacobi=blocks, rr_stop=rr_stop)
     else:
         op.begin(variant, b, x0, max_iter, x_true=x_true, inv_diag=inv_diag, hist_mask=mask, preconditioner=prec_fn, rr_stop=rr_stop)
 
@@ -1127,6 +1129,30 @@ def _make(variant, name, preconditioned):
     return f
 
 
+def _make_bpcg(variant, name, where):
+    single = name[:-len('_bpcg')]
+
+    def f(A, b, x0, max_iter, preconditioner, callbacks=[], rtol=None, atol=None, **kwargs):
+        if not isinstance(preconditioner, (BlockJacobi, DeviceBlockJacobi, VarBlockJacobi)):
+            what = ('no preconditioner' if preconditioner is None else
+                    'a diagonal scaling' if getattr(preconditioner, 'inv_diag', None) is not None else f'a {type(preconditioner).__name__}')
+            raise ValueError(f'{name}: {what}: the function takes BlockJacobi, DeviceBlockJacobi, VarBlockJacobi or DeviceVarBlockJacobi; use '
+                             f'{single}_pcg (Jacobi(A), any callable, or None)')
+        kwargs.pop('w_replace', None)
+        if rtol is not None or atol is not None:
+            kwargs.update(rtol=rtol, atol=atol)
+        return _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, block_stop=True)
+    f.__doc__ = (f'{single}_pcg ({where}) preconditioned by POINT-BLOCK JACOBI applied on the device, in a session that can STOP by itself.  '
+                 'preconditioner: BlockJacobi, DeviceBlockJacobi, VarBlockJacobi or DeviceVarBlockJacobi; anything else is a ValueError before '
+                 f'the device is reached.  Without rtol= / atol= the result is {single}_pcg\'s with the same object, bit for bit.  rtol= and/or '
+                 'atol=: the session stops on the device once its updated residual satisfies r.r <= max(rtol ||b||_2, atol)^2, or at a '
+                 'breakdown (prcg.h: prcg_set_stop_block_jacobi); the trial dict then carries \'iterations\' and \'status\' (\'converged\' / '
+                 '\'breakdown\' / \'max_iter\'), histories are zero beyond the stop and callbacks are called up to the stop iteration and no '
+                 f'further.  ({single}_pcg keeps refusing rtol= / atol= with such an object.)')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
 hs_cg = _make(L.HS, 'hs_cg', False)                       # hs_cg.py:9
 hs_pcg = _make(L.HS, 'hs_pcg', True)                      # hs_cg.py:70
 pr_pcg = _make(L.PR, 'pr_pcg', True)                      # pr_cg.py:166
@@ -1147,6 +1173,10 @@ pipe_p_pcg = _make(L.PIPE_P, 'pipe_p_pcg', True)          # pipe_pr_cg.py:195
 pipe_pr_pcg = _make(L.PIPE_PR, 'pipe_pr_pcg', True)       # pipe_pr_cg.py:201
 pipe_p_m_pcg = _make(L.PIPE_P_M, 'pipe_p_m_pcg', True)    # pipe_pr_cg.py:207
 pipe_pr_m_pcg = _make(L.PIPE_PR_M, 'pipe_pr_m_pcg', True) # pipe_pr_cg.py:213
+pipe_p_bpcg = _make_bpcg(L.PIPE_P, 'pipe_p_bpcg', 'pipe_pr_cg.py:195')
+pipe_pr_bpcg = _make_bpcg(L.PIPE_PR, 'pipe_pr_bpcg', 'pipe_pr_cg.py:201')
+pipe_p_m_bpcg = _make_bpcg(L.PIPE_P_M, 'pipe_p_m_bpcg', 'pipe_pr_cg.py:207')
+pipe_pr_m_bpcg = _make_bpcg(L.PIPE_PR_M, 'pipe_pr_m_bpcg', 'pipe_pr_cg.py:213')
 
 __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr_pcg', 'm_cg', 'm_pcg',
            'pipe_p_cg', 'pipe_pr_cg', 'pipe_p_m_cg', 'pipe_pr_m_cg',
@@ -1155,4 +1185,5 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_pr_cg_multi', 'pipe_pr_pcg_multi', 'pipe_pr_m_cg_multi', 'pipe_pr_m_pcg_multi', 'clear_operator_cache', 'update_values',
            'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch', 'pipe_pr_pcg_batch', 'pipe_pr_m_pcg_batch', 'hs_pcg_batch',
            'pipe_pr_bpcg_batch', 'pipe_pr_m_bpcg_batch', 'hs_bpcg_batch', 'hs_bpcg_multi', 'pr_bpcg_multi', 'm_bpcg_multi',
-           'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi']
+           'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi',
+           'pipe_p_bpcg', 'pipe_pr_bpcg', 'pipe_p_m_bpcg', 'pipe_pr_m_bpcg']

@@ -62,8 +62,8 @@ __global__ __launch_bounds__(kBjBlock) void k_block_jacobi(double* __restrict__ 
 
 // both columns of the interleaved [w u] array: wt = M^-1 w (mask bit 0), ut = M^-1 u (mask bit 1)
 template <int BS>
-__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_pair(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
-                                                                int64_t n, const double* __restrict__ blk, int mask) {
+__device__ __forceinline__ void block_jacobi_pair_body(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                       int64_t n, const double* __restrict__ blk, int mask) {
     constexpr int TR = (kBjBlock / BS) * BS;
     __shared__ d2_t sv[kBjBlock];
     const int t = threadIdx.x;
@@ -91,6 +91,26 @@ __global__ __launch_bounds__(kBjBlock) void k_block_jacobi_pair(double* __restri
     if (mask & 1) wt[i] = aw;
     if (mask & 2) ut[i] = au;
 }
+template <int BS>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_pair(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                                int64_t n, const double* __restrict__ blk, int mask) {
+    block_jacobi_pair_body<BS>(wt, ut, wu, n, blk, mask);
+}
+// Head of the pair launch of iteration k of a session that stops (ProductStop, prcg_kernels.h; prcg_set_stop_block_jacobi): true if
+// the session stopped BEFORE iteration k -- the pair launch of the stop iteration itself belongs to that iteration's state.  The
+// word was complete before the launch began (kernel boundary), every wave reads the same value: a workgroup leaves as a whole on a
+// scalar branch, before anything is loaded or stored and before the kernel's barrier.
+__device__ __forceinline__ bool pair_stopped(const ProductStop& stop) {
+    const int at = __builtin_amdgcn_readfirstlane(stop.word[0]);
+    return at >= 0 && at < stop.k;
+}
+// ... the stop form: the same statements behind that head
+template <int BS>
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_pair_stop(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                                     int64_t n, const double* __restrict__ blk, int mask, ProductStop stop) {
+    if (pair_stopped(stop)) return;
+    block_jacobi_pair_body<BS>(wt, ut, wu, n, blk, mask);
+}
 
 inline int bj_grid(int64_t n, int bs) {
     const int64_t tr = (kBjBlock / bs) * bs;
@@ -105,6 +125,11 @@ template <int BS>
 void launch_two(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, const double* blk, int mask) {
     hipLaunchKernelGGL(k_block_jacobi_pair<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
                        blk, mask);
+}
+template <int BS>
+void launch_two_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, const double* blk, int mask, const ProductStop& stop) {
+    hipLaunchKernelGGL(k_block_jacobi_pair_stop<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
+                       blk, mask, stop);
 }
 
 // ---- the device build (prcg_build_block_jacobi): gather the diagonal blocks from the caller-order CSR arrays, invert them, store
@@ -219,9 +244,9 @@ __global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var(double* __restric
     dst[i * ds] = acc;
 }
 
-__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_pair(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
-                                                                    const long long* __restrict__ tiles, const unsigned char* __restrict__ code,
-                                                                    const double* __restrict__ blk, int mask) {
+__device__ __forceinline__ void block_jacobi_var_pair_body(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                           const long long* __restrict__ tiles, const unsigned char* __restrict__ code,
+                                                           const double* __restrict__ blk, int mask) {
     __shared__ d2_t sv[kBjBlock + kBjvPad];
     const int t = threadIdx.x;
     const long long* tw = tiles + (int64_t)blockIdx.x * 4;
@@ -248,6 +273,18 @@ __global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_pair(double* __re
         }
     if (mask & 1) wt[i] = aw;
     if (mask & 2) ut[i] = au;
+}
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_pair(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                                    const long long* __restrict__ tiles, const unsigned char* __restrict__ code,
+                                                                    const double* __restrict__ blk, int mask) {
+    block_jacobi_var_pair_body(wt, ut, wu, tiles, code, blk, mask);
+}
+// ... the stop form (pair_stopped above): the same statements behind the head
+__global__ __launch_bounds__(kBjBlock) void k_block_jacobi_var_pair_stop(double* __restrict__ wt, double* __restrict__ ut, const d2_t* __restrict__ wu,
+                                                                         const long long* __restrict__ tiles, const unsigned char* __restrict__ code,
+                                                                         const double* __restrict__ blk, int mask, ProductStop stop) {
+    if (pair_stopped(stop)) return;
+    block_jacobi_var_pair_body(wt, ut, wu, tiles, code, blk, mask);
 }
 
 // the device build for a partition: k_block_jacobi_build's scheme, lane per row, with the row's own m.
@@ -480,6 +517,15 @@ int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const d
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int launch_block_jacobi_var_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
+                                      const unsigned char* code, const double* blocks, int mask, const ProductStop& stop) {
+    if (ntiles <= 0) return 0;
+    if (!stop.word) return -1;
+    hipLaunchKernelGGL(k_block_jacobi_var_pair_stop, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), tiles,
+                       code, blocks, mask, stop);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_block_jacobi_var_build(hipStream_t st, double* blocks, int64_t ntiles, const long long* tiles, const unsigned char* code,
                                   const unsigned char* bidx, const int* indptr, const int* col, const double* val, long long* first_bad) {
     if (ntiles <= 0) return 0;
@@ -565,6 +611,24 @@ int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const doubl
     case 6: launch_two<6>(st, wt, ut, wu, n, blocks, mask); break;
     case 7: launch_two<7>(st, wt, ut, wu, n, blocks, mask); break;
     case 8: launch_two<8>(st, wt, ut, wu, n, blocks, mask); break;
+    default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_block_jacobi_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask,
+                                  const ProductStop& stop) {
+    if (n <= 0) return 0;
+    if (!stop.word) return -1;
+    switch (bs) {
+    case 1: launch_two_stop<1>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 2: launch_two_stop<2>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 3: launch_two_stop<3>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 4: launch_two_stop<4>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 5: launch_two_stop<5>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 6: launch_two_stop<6>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 7: launch_two_stop<7>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 8: launch_two_stop<8>(st, wt, ut, wu, n, blocks, mask, stop); break;
     default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -139,24 +139,22 @@ int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const do
     if (g0 < 0) return g0;
     return eng_spmm2(h, st, which, src1, dst1, 3);
 }
-namespace {
-int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, const ProductStop& stop) {
+int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const ProductStop& stop) {
     SRCCHK(h, {rs, 2});
     const TileRange t = tile_range(h, which);
-    if (h->win) return launch_win_spmm2_stop(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, 3, stop, h->opt.win_per_cu);
-    if (h->sell) return launch_sell_spmm2_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, 3, stop, h->opt.sell_per_cu);
-    return launch_spmm2_stop(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, 3, stop, h->opt.kn);
+    if (h->win) return launch_win_spmm2_stop(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, mask, stop, h->opt.win_per_cu);
+    if (h->sell) return launch_sell_spmm2_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, stop, h->opt.sell_per_cu);
+    return launch_spmm2_stop(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, stop, h->opt.kn);
 }
-}  // namespace
 int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k) {
     SRCCHK(h, {src0, 2}, {src1, 2});
     if (spmm4_one_launch(h)) {
         const TileRange t = tile_range(h, which);
         return launch_sell_spmm4_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, src0, src1, dst0, dst1, ProductStop{words, k}, h->opt.sell_per_cu);
     }
-    const int g0 = eng_spmm2_stop(h, st, which, src0, dst0, ProductStop{words, k});
+    const int g0 = eng_spmm2_stop(h, st, which, src0, dst0, 3, ProductStop{words, k});
     if (g0 < 0) return g0;
-    return eng_spmm2_stop(h, st, which, src1, dst1, ProductStop{words + 2, k});
+    return eng_spmm2_stop(h, st, which, src1, dst1, 3, ProductStop{words + 2, k});
 }
 // (only the window kernels have the deferred form that runs one class of tiles; the others always take every tile)
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which) {

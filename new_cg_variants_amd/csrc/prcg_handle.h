@@ -192,6 +192,8 @@ struct Session {
                                  // once a launch's prologue, the final reduction or the one-workgroup solver has stopped it
     int stopped_k = -1;          // what prcg_sync has read from the word: the iteration whose state the session holds (-1: running) ...
     int stop_status = 0;         // ... and why (1 converged, 2 breakdown)
+    bool stop_bj = false;        // ... `stop` of a BLOCK-JACOBI session (prcg_set_stop_block_jacobi): the stored-tilde two-kernel schedule, every
+                                 // launch of an iteration in its stop form on `word` (iterate_pipe); fused is off, nothing is ever pending
     // ---- each column stopped at its own threshold (prcg_set_stop_rhs; the pipelined two-RHS session) ----
     bool stop_rhs = false;               // the session was begun with per-column thresholds ...
     double thr_rhs[2] = {0.0, 0.0};      // ... on r.r of column c; its stop word: Handle::stop_words_rhs + 2 c
@@ -282,6 +284,8 @@ struct Handle : Operator, Session {
     // residual threshold for single sessions begun from now on (prcg_set_stop); the word a session with one stops itself through
     bool stop_set = false; double stop_thr = 0.0;
     DevBuf stop_word;
+    // ... and for pipelined single sessions WITH BLOCK JACOBI begun from now on (prcg_set_stop_block_jacobi; the same word)
+    bool stop_bj_set = false; double stop_bj_thr = 0.0;
     // ... and per column for pipelined two-RHS sessions begun from now on (prcg_set_stop_rhs); the columns' words: four ints, column c's
     // {k, status} at 2 c (SmallStop's layout), allocated once, armed to {-1, 0} when such a session begins
     bool stop_rhs_set = false; double stop_rhs_thr[2] = {0.0, 0.0};
@@ -395,6 +399,8 @@ int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const do
 // ... the product of iteration k of a pipelined two-RHS session with thresholds: the stop forms of the same launches (ProductStop,
 // prcg_kernels.h) -- each two-vector launch skips by its own column's word, the one four-vector launch only when both columns stopped before k
 int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k);
+// ... and the two-vector product of iteration stop.k of a single session that stops (prcg_set_stop_block_jacobi), with its write mask
+int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const ProductStop& stop);
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which = 0);
 void note_partials_launch(prcg_t* h, int grid);
 int exchange(prcg_t* h, double* vec_ext, int nc, hipStream_t st);

@@ -414,6 +414,13 @@ struct PipeUpdateArgs {
     int recompute_w;  // 'pr' flavours: w is overwritten by the following SpMM
 };
 int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a);
+// Update k of a STORED-TILDE session that stops at a threshold (prcg_set_stop_block_jacobi): the flavour with u~ and w~ as vectors
+// only (a.ut set, a.d null; anything else: -1), a kernel of its own so that a session without a threshold launches what it always
+// did.  word: the session's stop word ({iteration it stopped at or -1, status}: SmallStop's layout, written by
+// launch_reduce_final_stop on the same stream).  If 0 <= word[0] < k the session stopped before this update and the launch returns
+// at once: no load, no store, no coefficient row, no partial row, no barrier met.  Otherwise launch_pipe_update's statements in
+// their order: the same bits in every vector and the same partial rows.  Returns the grid, like launch_pipe_update.
+int launch_pipe_update_stop(hipStream_t st, const PipeUpdateArgs& a, const int* word, int k);
 // the four (five) inner products of the current pipe state, no update (initialisation)
 int launch_pipe_dots(hipStream_t st, const PipeUpdateArgs& a);
 
@@ -555,6 +562,13 @@ int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const doub
                             const unsigned char* code, const double* blocks);
 int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
                                  const unsigned char* code, const double* blocks, int mask);
+// ... the pair launches of iteration stop.k of a session that stops at a threshold (ProductStop; prcg_set_stop_block_jacobi), kernels
+// of their own: the pair launch belongs to the state of its iteration, so it runs unless the session stopped BEFORE stop.k
+// (0 <= stop.word[0] < stop.k: returns at once, nothing loaded or stored); otherwise the bits of the launches above.  0 / -1.
+int launch_block_jacobi_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask,
+                                  const ProductStop& stop);
+int launch_block_jacobi_var_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
+                                      const unsigned char* code, const double* blocks, int mask, const ProductStop& stop);
 // ---- M^-1 on an interleaved n x 2 array with the inner products that need the result, in ONE launch (block-Jacobi sessions with
 // two or four right-hand sides: prcg_solve_begin_multi_block_jacobi).  v: the source pairs (NU: r; PR: s), z: the result (r~ / s~);
 // p, r: read by PR only.  One partial row per TILE (a tile: 256 - 256 % bs rows, or a tile of the partition's table): part0 / part1

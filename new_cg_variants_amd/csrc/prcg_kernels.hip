@@ -413,6 +413,67 @@ __global__ __launch_bounds__(kBlock) void k_pipe_update(PipeUpdateArgs a, int tr
     block_reduce_store<5>(acc, a.partials, 0);
 }
 
+// The stop form of the STORED-TILDE flavour (launch_pipe_update_stop, prcg_kernels.h): update k of a block-Jacobi session begun with
+// a threshold (prcg_set_stop_block_jacobi).  A kernel of its own: k_pipe_update above stays as it is, instruction for instruction.
+// The word is tested first: the reduction that closed an earlier iteration wrote it (k_reduce_final_stop), so it was complete before
+// this launch began, every wave reads the same value through readfirstlane, and a workgroup leaves as a whole on a scalar branch --
+// before anything is loaded or stored and before the one barrier (block_reduce_store).  Behind the head: k_pipe_update<true, false>
+// with a.ut set and a.d null -- u~ and w~ loaded as vectors -- the same expressions in the same order (multiply, then add), the same
+// element order, the same accumulators and the same tree: the bits of that kernel in every vector and every partial row.
+__global__ __launch_bounds__(kBlock) void k_pipe_update_stop(PipeUpdateArgs a, int trips, const int* __restrict__ word, int k) {
+    const int at = __builtin_amdgcn_readfirstlane(word[0]);
+    if (at >= 0 && at < k) return;
+    const Coefs c = predict(a.dots_prev, a.meurant);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.coef_out[0] = c.al; a.coef_out[1] = c.bt; a.coef_out[2] = c.nup;
+    }
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // mu, dl, gm, nu, rr
+    const int64_t n = a.n;
+    double2* __restrict__ XP = reinterpret_cast<double2*>(a.xp);
+    double2* __restrict__ RS = reinterpret_cast<double2*>(a.rs);
+    double2* __restrict__ RST = reinterpret_cast<double2*>(a.rst);
+    double2* __restrict__ WU = reinterpret_cast<double2*>(a.wu);
+    double* __restrict__ WT = a.wt;
+    const double* __restrict__ UT = a.ut;
+    const bool recompute_w = a.recompute_w != 0;
+
+    int64_t base = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x;
+    for (int j = 0; j < trips; ++j, base += kElemsPerTrip) {
+        if (base >= n) break;
+        double2 xp[2], rs[2], wu[2], rst[2];
+        double wt[2], ut[2];
+        bool ok[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t ie = base + e * kBlock;
+            ok[e] = ie < n;
+            const int64_t il = ok[e] ? ie : base;      // clamped: branch-free loads
+            xp[e] = XP[il]; rs[e] = RS[il]; wu[e] = WU[il]; rst[e] = RST[il];
+            ut[e] = UT[il]; wt[e] = WT[il];
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {                  // element 0 then element 1: part of the reduction tree
+            if (!ok[e]) continue;
+            const int64_t ie = base + e * kBlock;
+            const double xn = xp[e].x + c.al * xp[e].y;             // x += a p
+            const double rn = rs[e].x - c.al * rs[e].y;             // r -= a s
+            const double wn = wu[e].x - c.al * wu[e].y;             // w -= a u
+            const double rtn = rst[e].x - c.al * rst[e].y;          // r~ -= a s~
+            const double wtn = wt[e] - c.al * ut[e];                // w~ -= a u~
+            const double pn = rtn + c.bt * xp[e].y;                 // p = r~ + b p
+            const double sn = wn + c.bt * rs[e].y;                  // s = w + b s
+            const double stn = wtn + c.bt * rst[e].y;               // s~ = w~ + b s~
+            XP[ie] = make_double2(xn, pn);
+            RS[ie] = make_double2(rn, sn);
+            RST[ie] = make_double2(rtn, stn);
+            if (!recompute_w) { a.wu[2 * ie] = wn; WT[ie] = wtn; }
+            acc[0] += pn * sn; acc[1] += rn * stn; acc[2] += stn * sn;
+            acc[3] += rtn * rn; acc[4] += rn * rn;
+        }
+    }
+    block_reduce_store<5>(acc, a.partials, 0);
+}
+
 // ---- Hestenes-Stiefel (hs_cg.py:54-61, hs_pcg :116-124) ------------------------------
 template <bool PREC, bool DOTS_ONLY>
 __global__ __launch_bounds__(kBlock) void k_hs_update_xr(HsArgs a, int trips, const double* __restrict__ prev_mu, int nprev,
@@ -1066,6 +1127,12 @@ int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a) {
     // preconditioned: the inverse diagonal, or u~ / w~ as vectors (host-callback preconditioner)
     if (a.d || a.ut) hipLaunchKernelGGL((k_pipe_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     else             hipLaunchKernelGGL((k_pipe_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_pipe_update_stop(hipStream_t st, const PipeUpdateArgs& a, const int* word, int k) {
+    if (!a.ut || a.d || !word) return -1;        // the stored-tilde flavour only: u~ and w~ are vectors
+    const Chunking c = chunking(a.n);
+    hipLaunchKernelGGL(k_pipe_update_stop, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, word, k);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 int launch_pipe_dots(hipStream_t st, const PipeUpdateArgs& a) {

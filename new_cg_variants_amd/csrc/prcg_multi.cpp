@@ -372,6 +372,9 @@ int prcg::iterate_multi(prcg_t* h, int k) { return h->pipe2 ? iterate_pipe2(h, k
 #define STOP_RHS_SERVED "per-column stop thresholds are set (prcg_set_stop_rhs), which serve the pipelined two-RHS session only "  \
                         "(prcg_solve_begin_multi_pipe: PRCG_PIPE_PR, PRCG_PIPE_PR_M, Jacobi or none); this session cannot stop -- "  \
                         "prcg_set_stop_rhs(h, 0, NULL) clears the thresholds"
+// ... and so is the threshold of block-Jacobi single sessions: no multi-RHS session is begun while it is set
+#define STOP_BJ_SERVED "a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves pipelined SINGLE sessions with point-block "  \
+                       "Jacobi only (prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_block_jacobi(h, NULL) clears the threshold"
 
 extern "C" {
 
@@ -385,6 +388,7 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
                                                    "PRCG_PR (pr_cg / pr_pcg) and PRCG_M (m_cg / m_pcg) only", variant);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi", hist_mask)) return rc;
     CHECK(h, !h->stop_rhs_set, "prcg_solve_begin_multi: " STOP_RHS_SERVED);
+    CHECK(h, !h->stop_bj_set, "prcg_solve_begin_multi: " STOP_BJ_SERVED);
     CHECK(h, have_columns(b, x0, nrhs), "prcg_solve_begin_multi: null b or x0");
     if (int rc = open_pairs(h, "prcg_solve_begin_multi", variant, nrhs / 2, max_iter, hist_mask, inv_diag, 0)) return rc;
     return start_pairs(h, "prcg_solve_begin_multi", nrhs / 2, b, x0, 0);
@@ -401,6 +405,7 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     CHECK(h, nrhs == 2, "prcg_solve_begin_multi_pipe: nrhs = %d: the pipelined session serves exactly 2 right-hand sides (its product is the "
                         "four-vector one; an eight-vector product does not exist)", nrhs);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi_pipe", hist_mask)) return rc;
+    CHECK(h, !h->stop_bj_set, "prcg_solve_begin_multi_pipe: " STOP_BJ_SERVED);
     CHECK(h, have_columns(b, x0, 2), "prcg_solve_begin_multi_pipe: null b or x0");
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
@@ -466,6 +471,7 @@ int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const 
     CHECK(h, nrhs == 2 || nrhs == 4, "%s: nrhs = %d: the session serves exactly 2 right-hand sides (or 4, as two pairs)", who, nrhs);
     if (int rc = refuse_hooks(h, who, "multi-RHS", hist_mask)) return rc;
     CHECK(h, !h->stop_rhs_set, "%s: " STOP_RHS_SERVED, who);
+    CHECK(h, !h->stop_bj_set, "%s: " STOP_BJ_SERVED, who);
     CHECK(h, have_columns(b, x0, nrhs), "%s: null b or x0", who);
     CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
     const int64_t tiles = bj_tile_count(h);

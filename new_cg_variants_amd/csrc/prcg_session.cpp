@@ -30,6 +30,23 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
     const int mask = pipe_recompute(h->variant) ? 3 : 2;
     bool on = false;
     int rc;
+    if (h->stop_bj) {
+        // a block-Jacobi session with a threshold (prcg_set_stop_block_jacobi): one stream, every launch in its stop form on the
+        // session's word, which is complete at each kernel boundary.  The reduction sums row k and decides on it (it returns at
+        // once if the session stopped earlier); the product and the pair launch of iteration k belong to the state of k, so they
+        // are skipped only if the session stopped BEFORE k -- stopped at k, it holds w, u, u~ (w~) of k as well.
+        const ProductStop ps{h->word, k};
+        launch_reduce_final_stop(h->sc, h->partA.d(), grid_upd, dots_at(h, k), SmallStop{h->thr, h->word}, k);
+        if (profile) prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
+        LAUNCHCHK(h, eng_spmm2_stop(h, h->sc, 0, in_ext, h->wu.d(), mask, ps));
+        if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
+        if (h->bj_var)
+            LAUNCHCHK(h, launch_block_jacobi_var_pair_stop(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->bjv_plan.ntiles, h->bjv_tiles_d(), h->bjv_code_d(),
+                                                           h->bj_blocks.d(), mask, ps));
+        else
+            LAUNCHCHK(h, launch_block_jacobi_pair_stop(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask, ps));
+        return PRCG_OK;
+    }
     if (!h->multi()) {
         // everything in order on one stream
         launch_reduce_final(h->sc, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5);
@@ -168,13 +185,15 @@ void fused_flush(prcg_t* h) {
 // enqueued without knowing: launches k_stop + 1 .. h->k returned at once and wrote nothing, so the host's picture goes back to
 // iteration k_stop -- the iteration count; the input pairs, which every enqueued launch flipped once on the host only (the parity of
 // the difference says which buffer launch k_stop wrote; the one-workgroup solver works in place: no flip); and no partials are
-// pending (the reduction that would sum them returns at once as well).  Idempotent: once resolved, nothing more is enqueued.
+// pending (the reduction that would sum them returns at once as well).  A block-Jacobi session (Session::stop_bj) runs the
+// two-kernel schedule: nothing is flipped and nothing is ever pending, only the count goes back.  Idempotent: once resolved,
+// nothing more is enqueued.
 int resolve_stop(prcg_t* h) {
     if (!h->in_session || !h->stop || h->stopped_k >= 0) return PRCG_OK;
     int w[2] = {-1, 0};
     HIPCHK(h, hipMemcpy(w, h->word, sizeof w, hipMemcpyDeviceToHost));
     if (w[0] < 0) return PRCG_OK;
-    if (!h->small && ((h->k - w[0]) & 1)) {
+    if (h->fused && !h->small && ((h->k - w[0]) & 1)) {       // (the two-kernel schedule of a block-Jacobi session flips nothing)
         double* const bufA = h->prec ? h->rst.d() : h->rs.d();
         double* const bufB = h->prec ? h->rst2.d() : h->rs2.d();
         h->rs_cur = (h->rs_cur == bufA) ? bufB : bufA;
@@ -332,7 +351,8 @@ int iterate_pipe(prcg_t* h, int k) {
     PipeUpdateArgs a = pipe_args(h, k);
     bool on = false;
     prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-    const int grid = launch_pipe_update(h->sc, a);
+    // (with a block-Jacobi threshold: update k is skipped if the session stopped at k - 1 or earlier)
+    const int grid = h->stop_bj ? launch_pipe_update_stop(h->sc, a, h->word, k) : launch_pipe_update(h->sc, a);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_upd, h->n_ev_upd, on);
     return pipe_spmm_and_reduce(h, k, grid, true);
@@ -873,7 +893,9 @@ int begin_pipe(prcg_t* h) {
     if (h->fused_comm) h->fused = true;        // state layout, derived vectors: as the one-launch schedule
     // a session with a threshold runs the single-GPU one-launch schedule or the one-workgroup solver (what prcg_solve_begin let
     // through selects it); every launch closes itself (xp_deferred), so a stopped session holds one complete iteration
-    CHECK(h, !h->stop || (h->fused && !h->fused_comm), "prcg_solve_begin: a stop threshold is set and the session did not get the one-launch schedule");
+    // -- or, with blocks (prcg_set_stop_block_jacobi), the stored-tilde two-kernel schedule, whose launches have stop forms of their own
+    CHECK(h, !h->stop || (h->stop_bj ? (h->bj_session && !h->fused) : (h->fused && !h->fused_comm)),
+          "prcg_solve_begin: a stop threshold is set and the session did not get the one-launch schedule");
     HIPCHK(h, h->xp.ensure((size_t)2 * n * D, h->sc));
     HIPCHK(h, h->rs.ensure((size_t)2 * (h->prec ? n : ne) * D, h->sc));
     HIPCHK(h, h->rs2.ensure((h->fused && !h->prec) ? (size_t)2 * ne * D : 16, h->sc));
@@ -1154,7 +1176,7 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     //  four right-hand sides: twice the rows again, one set per pair group)
     HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * rows_per_iteration * kNS * D, h->sc));
     HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * rows_per_iteration * kCoefStride * D, h->sc));
-    if (h->stop_set) {
+    if (h->stop_set || h->stop_bj_set) {
         // the stop word of a session with a threshold: {-1, 0} = running (prcg_solve_begin arms it; other session types leave it alone)
         static const int kRunning[2] = {-1, 0};
         if (!h->stop_word.p) HIPCHK(h, h->stop_word.alloc(16));
@@ -1189,6 +1211,20 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
         CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set");
 #undef STOP_SERVED
     }
+    if (h->stop_bj_set) {
+        // a threshold for block-Jacobi sessions is set (prcg_set_stop_block_jacobi): only what stops on the device is begun
+#define STOP_SERVED "a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves the pipelined variants (PRCG_PIPE_PR, " \
+                    "PRCG_PIPE_PR_M, PRCG_PIPE_P, PRCG_PIPE_P_M) on one GPU with point-block Jacobi in force"
+#define STOP_CLEARS "(prcg_set_stop_block_jacobi(h, NULL) clears the threshold)"
+        CHECK(h, is_pipe(variant), "prcg_solve_begin: " STOP_SERVED "; variant %d is not pipelined " STOP_CLEARS, variant);
+        CHECK(h, !h->multi() && h->g == 0, "prcg_solve_begin: " STOP_SERVED "; this handle has a communicator or ghost rows " STOP_CLEARS);
+        CHECK(h, !inv_diag, "prcg_solve_begin: " STOP_SERVED "; inv_diag overrides the blocks -- a session with a diagonal stops through prcg_set_stop " STOP_CLEARS);
+        CHECK(h, !h->cb, "prcg_solve_begin: " STOP_SERVED "; a host-callback preconditioner is in force " STOP_CLEARS);
+        CHECK(h, h->have_block_jacobi(), "prcg_solve_begin: " STOP_SERVED "; no blocks are in force -- a session without blocks stops through prcg_set_stop " STOP_CLEARS);
+        CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set " STOP_CLEARS);
+#undef STOP_CLEARS
+#undef STOP_SERVED
+    }
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries: the
     // narrow column encodings decode a few out-of-tile bytes per tile against the tile's own base
     // (products nobody reads); the pad keeps those gathers inside the allocation without a test
@@ -1198,6 +1234,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
                           {{&h->x, (size_t)n * D}, {&h->b, (size_t)n * D}, {&h->xt, (size_t)n * D}, {&h->e_ext, (size_t)ne * D}});
     if (rc) return rc;
     if (h->stop_set) { h->stop = true; h->thr = h->stop_thr; h->word = h->stop_word.i(); }
+    if (h->stop_bj_set) { h->stop = h->stop_bj = true; h->thr = h->stop_bj_thr; h->word = h->stop_word.i(); }
     if ((rc = h2d(h, h->x.d(), x0, n))) return rc;
     if ((rc = h2d(h, h->b.d(), b, n))) return rc;
     if (x_true && (rc = h2d(h, h->xt.d(), x_true, n))) return rc;
@@ -1297,6 +1334,15 @@ int prcg_set_stop(prcg_t* h, const double* rr_stop) {
     return PRCG_OK;
 }
 
+int prcg_set_stop_block_jacobi(prcg_t* h, const double* rr_stop) {
+    if (!h) return PRCG_EINVAL;
+    if (!rr_stop) { h->stop_bj_set = false; h->stop_bj_thr = 0.0; return PRCG_OK; }
+    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "prcg_set_stop_block_jacobi: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop "
+                                                         "stops the session; NULL clears it)", *rr_stop);
+    h->stop_bj_set = true; h->stop_bj_thr = *rr_stop;
+    return PRCG_OK;
+}
+
 int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_get_stop: no open session");
@@ -1328,7 +1374,7 @@ int prcg_set_iteration(prcg_t* h, int k) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_set_iteration: no open session");
     NOT_RHS2(h, "prcg_set_iteration");
-    CHECK(h, !h->stop, "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop): its state is not set from outside");
+    CHECK(h, !h->stop, "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi): its state is not set from outside");
     CHECK(h, k >= 0 && k < h->max_iter, "prcg_set_iteration: k out of range");
     h->k = k;
     if (h->peer && is_pipe(h->variant)) {
@@ -1389,7 +1435,7 @@ int prcg_set_vector(prcg_t* h, int which, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in, "prcg_set_vector: no session or null buffer");
     NOT_RHS2(h, "prcg_set_vector");
-    CHECK(h, !h->stop, "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop): its state is not set from outside");
+    CHECK(h, !h->stop, "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int64_t n = h->n;
@@ -1420,7 +1466,7 @@ int prcg_set_scalars(prcg_t* h, int k, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in && k >= 0 && k <= h->max_iter, "prcg_set_scalars: bad argument");
     NOT_RHS2(h, "prcg_set_scalars");
-    CHECK(h, !h->stop, "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop): its state is not set from outside");
+    CHECK(h, !h->stop, "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     if ((rc = h2d(h, dots_at(h, k), in, kNS))) return rc;
