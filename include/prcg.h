@@ -533,6 +533,40 @@ int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status);
  *                      one-workgroup solver is never taken: a session with blocks runs this schedule whatever n. */
 int prcg_set_stop_block_jacobi(prcg_t* h, const double* rr_stop);
 
+/* ---- a single HESTENES-STIEFEL session stopped at a residual threshold, decided on the device -----------------------------------
+ * hs_cg / hs_pcg is the method a user reaches for first, and the session whose max_iter had to be guessed longest.  Its iteration has
+ * two dependent reductions and no launch that holds all of a row's scalars at once, which prcg_set_stop does not serve: it has a
+ * setter of its own, and every launch of an iteration a stop form of its own.
+ *   prcg_set_stop_hs   rr_stop: NULL clears the threshold; else *rr_stop is the threshold on r.r, finite and >= 0, else PRCG_EINVAL
+ *                      (what was set before stays).  It is copied at the call and applies to sessions BEGUN afterwards with
+ *                      prcg_solve_begin; an open session is not affected.  While it is set prcg_solve_begin serves PRCG_HS on one
+ *                      GPU, unpreconditioned or with inv_diag, on the schedule without reduction launches or on the one-workgroup
+ *                      solver, and refuses everything else with PRCG_EINVAL and a text that names this setter and how to clear it:
+ *                      another variant, a communicator or ghost rows, a host-callback or block-Jacobi preconditioner in force (the
+ *                      stored-tilde schedule with reduction launches), PRCG_FUSED=0, a replace hook; prcg_solve_begin_multi,
+ *                      prcg_solve_begin_multi_pipe and prcg_solve_begin_multi_block_jacobi refuse as well.  Nothing falls back to a
+ *                      session that cannot stop.  Independent of prcg_set_stop and prcg_set_stop_block_jacobi: with one of those set,
+ *                      its own refusal of PRCG_HS stands.  The rule is prcg_set_stop's, on row k of the scalars after iteration k
+ *                      and on row 0; a Hestenes-Stiefel row is {mu_k = p_k.s_k, -, -, nu_k = r~_k.r_k, rr_k}:
+ *                        1. rr <= *rr_stop                                     -> stop, status 1 (converged);
+ *                        2. else !(0 < mu && mu < inf && 0 < nu && nu < inf)   -> stop, status 2 (breakdown);
+ *                        3. else go on.
+ *                      It is what a system of a Hestenes-Stiefel batch applies (prcg_batch_set_stop): a system in a batch and a
+ *                      single session stop at the same k on the same bits.  Iteration k is: the update of x, r (r~), whose prologue
+ *                      completes row k - 1 with mu and applies the rule to it (skipped, like everything after it, if that stops
+ *                      the session at k - 1); the update of p and the product s = A p with the partial sums of mu_k, which decide
+ *                      nothing and are skipped only if the session stopped BEFORE k.  The reduction that ends a prcg_iterate call
+ *                      completes and decides the last row.  A session stopped at k therefore holds the complete state of iteration
+ *                      k -- x, r, p, s (with inv_diag r~ too), scalar rows 0..k, coefficient rows 1..k -- and every later launch
+ *                      returns at once and writes nothing.  The product s_k = A p_k of the stop iteration is computed although rr_k
+ *                      is known before it: one product per solve, the price of one rule for every session type.  A session that
+ *                      does not stop carries the bits of the session without a threshold; a session begun without one launches the
+ *                      kernels it always did.  prcg_sync resolves the stop and prcg_get_stop reads it; afterwards prcg_iteration
+ *                      is k, prcg_iterate is a no-op, scalar and coefficient rows and history entries beyond k read as zero.
+ *                      prcg_set_vector, prcg_set_scalars and prcg_set_iteration are refused in such a session; recorders are
+ *                      allowed as with prcg_set_stop. */
+int prcg_set_stop_hs(prcg_t* h, const double* rr_stop);
+
 /* ---- each column of a PIPELINED TWO-RHS session stopped at its own residual threshold, decided on the device ------------------
  * Two load cases of one matrix almost never converge at the same iteration: the session freezes the column that is done and
  * keeps iterating the other.

@@ -103,6 +103,7 @@ _SIGNATURES = {
     'prcg_set_stop': (C.c_int, [_P, _P]),
     'prcg_get_stop': (C.c_int, [_P, _P, _P]),
     'prcg_set_stop_block_jacobi': (C.c_int, [_P, _P]),
+    'prcg_set_stop_hs': (C.c_int, [_P, _P]),
     'prcg_set_stop_rhs': (C.c_int, [_P, C.c_int, _P]),
     'prcg_get_stops_rhs': (C.c_int, [_P, _P, _P]),
     'prcg_batch_set_stop': (C.c_int, [_P, _P]),

@@ -509,9 +509,11 @@ def _state_vectors(variant, prec):
 _PIPELINED = (L.PIPE_PR, L.PIPE_PR_M, L.PIPE_P, L.PIPE_P_M)
 
 
-def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w_replace=None, block_stop=False):
+def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w_replace=None, block_stop=False, hs_stop=False):
     """block_stop: the caller is a pipe_*_bpcg function, whose preconditioner is a block-Jacobi object: rtol= / atol= then reach the
-    block session's own threshold (prcg.h: prcg_set_stop_block_jacobi) instead of being refused"""
+    block session's own threshold (prcg.h: prcg_set_stop_block_jacobi) instead of being refused.
+    hs_stop: the caller is hs_cg_stop / hs_pcg_stop: rtol= / atol= reach the Hestenes-Stiefel session's threshold (prcg.h:
+    prcg_set_stop_hs), which serves no preconditioner but a diagonal scaling"""
     device = int(kwargs.get('device', 0))
     if A.format != 'csr':
         A = A.tocsr()
@@ -524,10 +526,15 @@ def _run(variant, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, w
         inv_diag, prec_fn = None, preconditioner
     else:
         inv_diag, prec_fn = _diagonal_of(preconditioner, n)
-    # rtol= / atol=: the pipelined variants stop by themselves on the device (prcg.h: prcg_set_stop); the other functions never
-    # took the keywords and keep passing them by, like any keyword they do not know
+    if hs_stop and prec_fn is not None:
+        raise ValueError(f'{name}: the function takes no preconditioner but a diagonal scaling (None, Jacobi(A), or a callable that is '
+                         'one): a callable or block-Jacobi preconditioner runs the stored-tilde schedule with reduction launches, which '
+                         'cannot stop on the device; use hs_pcg')
+    # rtol= / atol=: the pipelined variants stop by themselves on the device (prcg.h: prcg_set_stop), and so do hs_cg_stop /
+    # hs_pcg_stop (prcg_set_stop_hs); the other functions never took the keywords and keep passing them by, like any keyword they
+    # do not know
     rr_stop = None
-    if variant in _PIPELINED and (kwargs.get('rtol') is not None or kwargs.get('atol') is not None):
+    if (variant in _PIPELINED or hs_stop) and (kwargs.get('rtol') is not None or kwargs.get('atol') is not None):
         bvec = np.asarray(b, dtype=np.float64)
         if bvec.shape != (n,):
             raise ValueError(f'{name}: b must have shape ({n},), got {tuple(bvec.shape)}')
@@ -1155,6 +1162,40 @@ def _make_bpcg(variant, name, where):
 
 hs_cg = _make(L.HS, 'hs_cg', False)                       # hs_cg.py:9
 hs_pcg = _make(L.HS, 'hs_pcg', True)                      # hs_cg.py:70
+hs_cg.__doc__ = ('hs_cg (hs_cg.py:9): max_iter - 1 iterations.  rtol= / atol= are passed by like any keyword the reference does not know; '
+                 'hs_cg_stop takes them and stops on the device.')
+hs_pcg.__doc__ = ('hs_pcg (hs_cg.py:70): max_iter - 1 iterations.  rtol= / atol= are passed by like any keyword the reference does not '
+                  'know; hs_pcg_stop takes them and stops on the device.')
+
+
+def _make_hs_stop(name, preconditioned, where):
+    single = name[:-len('_stop')]
+
+    def run(A, b, x0, max_iter, preconditioner, callbacks, rtol, atol, kwargs):
+        kwargs.pop('w_replace', None)
+        if rtol is not None or atol is not None:
+            kwargs.update(rtol=rtol, atol=atol)
+        return _run(L.HS, name, A, b, x0, max_iter, preconditioner, callbacks, kwargs, hs_stop=True)
+    if preconditioned:
+        def f(A, b, x0, max_iter, preconditioner=None, callbacks=[], rtol=None, atol=None, **kwargs):
+            return run(A, b, x0, max_iter, preconditioner, callbacks, rtol, atol, kwargs)
+    else:
+        def f(A, b, x0, max_iter, callbacks=[], rtol=None, atol=None, **kwargs):
+            kwargs.pop('preconditioner', None)
+            return run(A, b, x0, max_iter, None, callbacks, rtol, atol, kwargs)
+    f.__doc__ = (f'{single} ({where}) in a session that can STOP by itself.  ' +
+                 ('preconditioner: None, Jacobi(A) or a callable that is a diagonal scaling; anything else is a ValueError before the '
+                  'device is reached.  ' if preconditioned else '') +
+                 f'Without rtol= / atol= the result is {single}\'s, bit for bit.  rtol= and/or atol=: the session stops on the device once '
+                 'its updated residual satisfies r.r <= max(rtol ||b||_2, atol)^2, or at a breakdown (prcg.h: prcg_set_stop_hs); the trial '
+                 'dict then carries \'iterations\' and \'status\' (\'converged\' / \'breakdown\' / \'max_iter\'), histories are zero beyond '
+                 f'the stop and callbacks are called up to the stop iteration and no further.  ({single} itself keeps passing rtol= / atol= by.)')
+    f.__name__ = f.__qualname__ = name
+    return f
+
+
+hs_cg_stop = _make_hs_stop('hs_cg_stop', False, 'hs_cg.py:9')
+hs_pcg_stop = _make_hs_stop('hs_pcg_stop', True, 'hs_cg.py:70')
 pr_pcg = _make(L.PR, 'pr_pcg', True)                      # pr_cg.py:166
 m_pcg = _make(L.M, 'm_pcg', True)                         # pr_cg.py:172
 # the reference's unpreconditioned pr_cg / m_cg raise NameError (pr_cg.py:24,54); here
@@ -1186,4 +1227,4 @@ __all__ = ['hs_cg', 'hs_pcg', 'cg_cg', 'cg_pcg', 'gv_cg', 'gv_pcg', 'pr_cg', 'pr
            'pipe_pr_cg_batch', 'pipe_pr_m_cg_batch', 'hs_cg_batch', 'pipe_pr_pcg_batch', 'pipe_pr_m_pcg_batch', 'hs_pcg_batch',
            'pipe_pr_bpcg_batch', 'pipe_pr_m_bpcg_batch', 'hs_bpcg_batch', 'hs_bpcg_multi', 'pr_bpcg_multi', 'm_bpcg_multi',
            'invert_blocks', 'DeviceBlockJacobi', 'VarBlockJacobi', 'DeviceVarBlockJacobi',
-           'pipe_p_bpcg', 'pipe_pr_bpcg', 'pipe_p_m_bpcg', 'pipe_pr_m_bpcg']
+           'pipe_p_bpcg', 'pipe_pr_bpcg', 'pipe_p_m_bpcg', 'pipe_pr_m_bpcg', 'hs_cg_stop', 'hs_pcg_stop']

@@ -238,7 +238,8 @@ __device__ __forceinline__ int stop_rule(double mu, double nu, double rr, double
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-// Head of a product launch with the epilogue kEpiNoneStop (ProductStop, prcg_kernels.h): true if the launch has nothing to do --
+// Head of a product launch with the epilogue kEpiNoneStop or kEpiDotXYStop (ProductStop, prcg_kernels.h; also the Hestenes-Stiefel
+// window launch kEpiHS when it carries a word): true if the launch has nothing to do --
 // its column (NV == 4: both columns, the second word follows the first) stopped BEFORE iteration fz.word_k.  The words were
 // complete before the launch began, every wave reads the same values: a scalar branch, taken before anything is loaded or stored.
 template <int NV>
@@ -444,7 +445,7 @@ __device__ __forceinline__ void finish_row(int row, const typename VecT<NV>::typ
     if constexpr (NV == 1) {
         double* Y = reinterpret_cast<double*>(yout_);
         Y[row] = sum;
-        if constexpr (EPI == kEpiDotXY) acc[0] += X[row] * sum;
+        if constexpr (epi_dot_xy(EPI)) acc[0] += X[row] * sum;
         if constexpr (EPI == kEpiPR) {
             const double stv = ep_d ? ep_d[row] * sum : sum;
             if (ep_st) ep_st[row] = stv;

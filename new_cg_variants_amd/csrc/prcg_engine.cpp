@@ -146,6 +146,16 @@ int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, doubl
     if (h->sell) return launch_sell_spmm2_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, stop, h->opt.sell_per_cu);
     return launch_spmm2_stop(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, stop, h->opt.kn);
 }
+int eng_spmv_dot_stop(prcg_t* h, hipStream_t st, int which, const double* x, double* y, double* partials, const ProductStop& stop) {
+    SRCCHK(h, {x, 1});
+    if (h->win) return -1;
+    const TileRange t = tile_range(h, which);
+    const int grid = h->sell
+        ? launch_sell_spmv_dot_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, partials, stop, h->opt.sell_per_cu)
+        : launch_spmv_dot_stop(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, partials, stop, h->opt.kn);
+    note_partials_launch(h, grid);
+    return grid;
+}
 int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k) {
     SRCCHK(h, {src0, 2}, {src1, 2});
     if (spmm4_one_launch(h)) {

@@ -194,6 +194,8 @@ struct Session {
     int stop_status = 0;         // ... and why (1 converged, 2 breakdown)
     bool stop_bj = false;        // ... `stop` of a BLOCK-JACOBI session (prcg_set_stop_block_jacobi): the stored-tilde two-kernel schedule, every
                                  // launch of an iteration in its stop form on `word` (iterate_pipe); fused is off, nothing is ever pending
+    bool stop_hs = false;        // ... `stop` of a HESTENES-STIEFEL session (prcg_set_stop_hs): the schedule without reduction launches
+                                 // (iterate_hs_fused), every launch in its stop form on `word`, or the one-workgroup solver's
     // ---- each column stopped at its own threshold (prcg_set_stop_rhs; the pipelined two-RHS session) ----
     bool stop_rhs = false;               // the session was begun with per-column thresholds ...
     double thr_rhs[2] = {0.0, 0.0};      // ... on r.r of column c; its stop word: Handle::stop_words_rhs + 2 c
@@ -286,6 +288,8 @@ struct Handle : Operator, Session {
     DevBuf stop_word;
     // ... and for pipelined single sessions WITH BLOCK JACOBI begun from now on (prcg_set_stop_block_jacobi; the same word)
     bool stop_bj_set = false; double stop_bj_thr = 0.0;
+    // ... and for Hestenes-Stiefel single sessions begun from now on (prcg_set_stop_hs; the same word)
+    bool stop_hs_set = false; double stop_hs_thr = 0.0;
     // ... and per column for pipelined two-RHS sessions begun from now on (prcg_set_stop_rhs); the columns' words: four ints, column c's
     // {k, status} at 2 c (SmallStop's layout), allocated once, armed to {-1, 0} when such a session begins
     bool stop_rhs_set = false; double stop_rhs_thr[2] = {0.0, 0.0};
@@ -401,6 +405,9 @@ int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const do
 int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k);
 // ... and the two-vector product of iteration stop.k of a single session that stops (prcg_set_stop_block_jacobi), with its write mask
 int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const ProductStop& stop);
+// ... and y = A x with the partials of x.y (kEpiDotXY) of iteration stop.k of a Hestenes-Stiefel session that stops (prcg_set_stop_hs) on
+// sliced rows or CSR-adaptive tiles (a window operator runs launch_win_hs: -1 here)
+int eng_spmv_dot_stop(prcg_t* h, hipStream_t st, int which, const double* x, double* y, double* partials, const ProductStop& stop);
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which = 0);
 void note_partials_launch(prcg_t* h, int grid);
 int exchange(prcg_t* h, double* vec_ext, int nc, hipStream_t st);

@@ -136,8 +136,11 @@ enum SpmvEpilogue {
     kEpiGVOne = 17,  // window kernels only: ONE launch per Ghysels-Vanroose iteration (unpreconditioned)
     kEpiPROneQ = 18, // window kernels only: one-launch predict-and-recompute iteration on the PACKED state, pairs (z, zs) and (p, x) (PrOne::q_old, px_old)
     kEpiNoneStop = 19,   // two- and four-vector products only: the plain epilogue, in a launch that may have nothing to do (ProductStop below)
+    kEpiDotXYStop = 20,  // sliced rows and CSR-adaptive tiles, one vector: kEpiDotXY in a launch that may have nothing to do (ProductStop below)
 };
 constexpr bool epi_plain(int e) { return e == kEpiNone || e == kEpiNoneStop; }     // no inner products: nothing but the product is stored
+constexpr bool epi_dot_xy(int e) { return e == kEpiDotXY || e == kEpiDotXYStop; }  // partial[0] += x_i * y_i
+constexpr bool epi_product_stop(int e) { return e == kEpiNoneStop || e == kEpiDotXYStop; }     // the head of the launch reads ProductStop's word
 // The product launch of iteration k of a pipelined two-RHS session whose columns stop at their own thresholds (prcg_set_stop_rhs;
 // kEpiNoneStop: instantiations of their own, so that a session without thresholds launches the kernels it always did).  word: the
 // stop word of the launch's column, two ints laid out as SmallStop's (below).  The product of iteration k belongs to the state of
@@ -147,6 +150,9 @@ constexpr bool epi_plain(int e) { return e == kEpiNone || e == kEpiNoneStop; }  
 // not changed, so its destination is rewritten with the bits it holds.  The word was complete before the launch began (kernel
 // boundary); every wave reads the same value through readfirstlane and leaves on a scalar branch.  Travels in FusedPrev::word /
 // word_k, which the plain epilogue does not use otherwise.
+// kEpiDotXYStop: the product s = A p with mu = p.s of iteration k of a Hestenes-Stiefel session that stops (prcg_set_stop_hs) on sliced
+// rows or CSR-adaptive tiles, by the same head: the product of the stop iteration belongs to its state, so the launch returns only
+// if the session stopped BEFORE k; then no partial row is written either (the reduction that would sum them returns as well).
 struct ProductStop { int* word; int k; };
 constexpr bool epi_pr_one(int e) { return e == kEpiPROne || e == kEpiPROneJ || e == kEpiPROneQ; }
 constexpr bool epi_cg_w(int e) { return e == kEpiCGW || e == kEpiCGWJ; }
@@ -188,6 +194,10 @@ int launch_spmv(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, 
                 const double* x, double* y, SpmvEpilogue epi,
                 const double* ep_r, const double* ep_d, double* ep_st,
                 double* partials, TileKnobs kn = TileKnobs{});
+// y = A x with partial[0] += x_i * y_i (kEpiDotXY) of a Hestenes-Stiefel session that stops (ProductStop, kEpiDotXYStop): the same
+// product and the same partial rows, or nothing at all
+int launch_spmv_dot_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps, const double* x, double* y,
+                         double* partials, const ProductStop& stop, TileKnobs kn = TileKnobs{});
 
 // [w u] = A [r s] on interleaved pairs.  write_mask: 1 = first, 2 = second, 3 = both.
 int launch_spmm2(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
@@ -315,6 +325,8 @@ struct SellDev {
 };
 int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, SpmvEpilogue epi,
                      const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu);
+int launch_sell_spmv_dot_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, double* partials,
+                              const ProductStop& stop, int per_cu);      // (as launch_spmv_dot_stop)
 int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
                       int per_cu);
 // [dst0 | dst1] = A [src0 | src1] for two pair arrays in ONE walk of the operator (four right-hand sides in one session): sources
@@ -357,7 +369,7 @@ bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, int prec = k
 // STOP form of the batch's body on the session's own word
 struct SmallStop;
 int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop = nullptr);
-int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode);      // Hestenes-Stiefel, same storage
+int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop = nullptr);      // Hestenes-Stiefel, same storage
 // ---- a batch of small systems: the same solver, one workgroup per system, blockIdx.x selects the system (prcg_batch.cpp) ----
 // desc: `count` SmallArgs in DEVICE memory, all of one mode (k0, iters, meurant in them are ignored: the launch carries them).
 // Results of a system are those of launch_small_pipe_pr / launch_small_hs with its descriptor, bit for bit, whatever its
@@ -438,6 +450,19 @@ int launch_hs_update_xr(hipStream_t st, const HsArgs& a, const double* prev_mu =
 int launch_hs_update_p(hipStream_t st, const HsArgs& a, const double* prev_nu = nullptr, int nprev = 0,
                        double* dots_cur_w = nullptr);    // p = z + beta p
 int launch_hs_init_dots(hipStream_t st, const HsArgs& a);   // nu, rr of the initial state
+// The launches of iteration k of a Hestenes-Stiefel session that stops at a threshold (prcg_set_stop_hs), kernels of their own so
+// that a session without a threshold launches what it always did.  stop.word: the session's stop word, SmallStop's layout and rule.
+//   update_xr (launch A of iteration k): returns at once if the session stopped before k - 1.  Otherwise mu_k1 as above (workgroup 0
+//     stores it: it belongs to the state of a stop), then the rule on row k - 1 = {mu_k1, nu_k1, rr_k1}, nu and rr read from
+//     a.dots_prev, where the launch before stored them.  On a verdict thread 0 of workgroup 0 records {k - 1, status} and every
+//     workgroup returns: no coefficient, no vector, no partial row of iteration k is written.  No verdict: the bits of launch_hs_update_xr.
+//   update_p (CSR-adaptive tiles and sliced rows): returns at once if the session stopped before k; else the bits of launch_hs_update_p.
+//   launch_reduce_hs_mu_stop (the reduction that ends a prcg_iterate call, and the session's start with k = 0): returns at once if the
+//     word is set (the partials are stale); else row[0] = mu_k summed as launch_reduce_final sums one slot, then the rule on
+//     {mu_k, row[3], row[4]} and the record {k, status}.
+int launch_hs_update_xr_stop(hipStream_t st, const HsArgs& a, const double* prev_mu, int nprev, double* dots_prev_w, const SmallStop& stop, int k);
+int launch_hs_update_p_stop(hipStream_t st, const HsArgs& a, const double* prev_nu, int nprev, double* dots_cur_w, const int* word, int k);
+void launch_reduce_hs_mu_stop(hipStream_t st, const double* partials, int nparts, double* row, const SmallStop& stop, int k);
 
 // ---- Hestenes-Stiefel, TWO right-hand sides in one session (prcg_rhs2.hip; prcg_solve_begin_multi) ----
 // x, r, rt, p, s: interleaved n x 2 arrays, row i = (column 0, column 1) -- p and s are directly the input and output of the

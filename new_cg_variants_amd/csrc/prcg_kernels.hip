@@ -246,7 +246,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(
     Coefs cf = {0.0, 0.0, 0.0};
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
-    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (nothing loaded, nothing stored, no barrier met)
+    if constexpr (epi_product_stop(EPI)) { if (product_stopped<NV>(fz)) return; }      // (nothing loaded, nothing stored, no barrier met)
     if constexpr (epi_fused(EPI)) {
         // ep_r = the reduced inner products of the previous iteration; bit 2 of write_mask =
         // Meurant's prediction; aux = where alpha, beta, nu_pred of this iteration are kept
@@ -561,6 +561,113 @@ __global__ __launch_bounds__(kBlock) void k_hs_update_p(HsArgs a, int trips, con
     }
 }
 
+// The stop forms (launch_hs_update_xr_stop / launch_hs_update_p_stop, prcg_kernels.h): iteration k of a Hestenes-Stiefel session begun with
+// a threshold (prcg_set_stop_hs).  Kernels of their own: the two above stay as they are, instruction for instruction.  Behind their
+// heads they are the statements of k_hs_update_xr<PREC, false> and k_hs_update_p in their order -- the same expressions, the same
+// element order, the same accumulators and the same tree: the bits of those kernels in every vector and every partial row.
+// k_hs_update_xr_stop is launch A of iteration k and closes iteration k - 1:
+//  1. The word names an iteration BEFORE k - 1: the session stopped in an earlier launch.  The word was complete before this launch
+//     began (kernel boundary), so every wave of every workgroup reads the same value and leaves here, before any barrier and before
+//     anything is written.  (A word that names k - 1 itself was left by the reduction that ended the last prcg_iterate call or by the
+//     session's start -- then mu is read reduced, the rule below fires again and nothing is written -- or it is the store of
+//     workgroup 0 of THIS launch seen by a wave that started late: it goes on and reaches that verdict itself, with the rest of its
+//     workgroup.  Leaving on it here would let waves of one workgroup part BEFORE the barriers of the sum: fused_prologue.)
+//  2. The rule on row k - 1 = {mu, nu, rr}.  mu is the same bits in every thread of every workgroup (one tree over one buffer, read
+//     behind the barrier that completes it; or one load of a reduced word), nu and rr are loads of words that workgroup 0 of the
+//     launch before (or the session's start) stored before the kernel boundary, thr is a kernel argument: every wave of the launch
+//     reaches the same verdict (readfirstlane: a scalar branch), behind the last barrier of the sum and before the next one, so
+//     whole workgroups leave together.  Thread 0 of workgroup 0 records {k - 1, status}; mu of k - 1 has been stored (it belongs
+//     to the state of the stop); a_k, x, r, r~ and the partial rows of iteration k are not touched.
+// k_hs_update_p_stop decides nothing (mu_k does not exist before the product has run): it leaves at once, on a scalar branch and
+// before its sum, if the session stopped before k.
+template <bool PREC>
+__global__ __launch_bounds__(kBlock) void k_hs_update_xr_stop(HsArgs a, int trips, const double* __restrict__ prev_mu, int nprev,
+                                                              double* dots_prev_w, SmallStop stop, int k) {
+    const int at = __builtin_amdgcn_readfirstlane(stop.word[0]);
+    if (at >= 0 && at < k - 1) return;                          // 1.
+    double mu;
+    if (nprev > 0) {
+        // mu = <p,s> of the previous iteration: still the product launch's block partials
+        double m[1];
+        sum_prev_partials<1, kWaves>(prev_mu, nprev, 0, m);
+        mu = m[0];
+        if (blockIdx.x == 0 && threadIdx.x == 0) dots_prev_w[0] = mu;
+    } else {
+        mu = a.dots_prev[0];
+    }
+    const int verdict = stop_rule(mu, a.dots_prev[3], a.dots_prev[4], stop.thr);      // 2.
+    if (verdict) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { stop.word[0] = k - 1; stop.word[1] = verdict; }
+        return;
+    }
+    const double al = a.dots_prev[3] / mu;                      // a_k1 = nu/mu
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.coef_out[0] = al;
+    double acc[2] = {0.0, 0.0};   // nu, rr
+    int64_t i = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x * 2;
+    for (int j = 0; j < trips; ++j, i += kElemsPerTrip) {
+        if (i + 1 < a.n) {
+            // the thread's two elements as 16-byte loads and stores (same expressions, same order of the sums: element i, then i + 1)
+            double2 rn = *reinterpret_cast<const double2*>(a.r + i);
+            const double2 x2 = *reinterpret_cast<const double2*>(a.x + i), p2 = *reinterpret_cast<const double2*>(a.p + i);
+            const double2 s2 = *reinterpret_cast<const double2*>(a.s + i);
+            *reinterpret_cast<double2*>(a.x + i) = make_double2(x2.x + al * p2.x, x2.y + al * p2.y);
+            rn = make_double2(rn.x - al * s2.x, rn.y - al * s2.y);
+            *reinterpret_cast<double2*>(a.r + i) = rn;
+            if constexpr (PREC) {
+                const double2 d2 = *reinterpret_cast<const double2*>(a.d + i);
+                const double2 z = make_double2(d2.x * rn.x, d2.y * rn.y);      // r~ = M^-1 r
+                *reinterpret_cast<double2*>(a.rt + i) = z;
+                acc[0] += rn.x * z.x; acc[1] += rn.x * rn.x;
+                acc[0] += rn.y * z.y; acc[1] += rn.y * rn.y;
+            } else {
+                acc[0] += rn.x * rn.x;
+                acc[0] += rn.y * rn.y;
+            }
+        } else if (i < a.n) {
+            double rn = a.r[i];
+            a.x[i] = a.x[i] + al * a.p[i];
+            rn = rn - al * a.s[i];
+            a.r[i] = rn;
+            if constexpr (PREC) {
+                const double z = a.d[i] * rn;
+                a.rt[i] = z;
+                acc[0] += rn * z; acc[1] += rn * rn;
+            } else {
+                acc[0] += rn * rn;
+            }
+        }
+    }
+    if constexpr (!PREC) acc[1] = acc[0];
+    block_reduce_store<2>(acc, a.partials, 3);
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_update_p_stop(HsArgs a, int trips, const double* __restrict__ prev_nu, int nprev,
+                                                             double* dots_cur_w, const int* __restrict__ word, int k) {
+    const int at = __builtin_amdgcn_readfirstlane(word[0]);
+    if (at >= 0 && at < k) return;
+    double nu;
+    if (nprev > 0) {
+        double m[2];
+        sum_prev_partials<2, kWaves>(prev_nu, nprev, 3, m);     // nu_k, rr_k: still the update launch's block partials
+        nu = m[0];
+        if (blockIdx.x == 0 && threadIdx.x == 0) { dots_cur_w[3] = m[0]; dots_cur_w[4] = m[1]; }
+    } else {
+        nu = a.dots_cur[3];
+    }
+    const double bt = nu / a.dots_prev[3];                      // b_k = nu_k / nu_k1
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.coef_out[1] = bt;
+    const double* __restrict__ z = a.rt ? a.rt : a.r;
+    int64_t i = ((int64_t)blockIdx.x * trips) * kElemsPerTrip + threadIdx.x * 2;
+    for (int j = 0; j < trips; ++j, i += kElemsPerTrip) {
+        if (i + 1 < a.n) {                                      // the thread's two elements as 16-byte loads and stores
+            const double2 z2 = *reinterpret_cast<const double2*>(z + i), p2 = *reinterpret_cast<const double2*>(a.p + i);
+            *reinterpret_cast<double2*>(a.p + i) = make_double2(z2.x + bt * p2.x, z2.y + bt * p2.y);     // p = r~ + b p
+        } else if (i < a.n) {
+            a.p[i] = z[i] + bt * a.p[i];
+        }
+    }
+}
+
 // ---- non-pipelined predict-and-recompute (pr_cg.py:146-151) ---------------------------
 template <bool PREC, bool DOTS_ONLY>
 __global__ __launch_bounds__(kBlock) void k_pr_update(PrArgs a, int trips) {
@@ -788,6 +895,24 @@ __global__ __launch_bounds__(kFinalThreads) void k_reduce_final_stop(
     if (threadIdx.x < 5) out[threadIdx.x] = reduce_final_total(red, threadIdx.x);
     if (threadIdx.x == 0) {
         const int verdict = stop_rule(reduce_final_total(red, 0), reduce_final_total(red, 3), reduce_final_total(red, 4), stop.thr);
+        if (verdict) { stop.word[0] = k; stop.word[1] = verdict; }
+    }
+}
+
+// The stop form of the ONE-slot reduction that closes a Hestenes-Stiefel iteration (launch_reduce_hs_mu_stop, prcg_kernels.h): mu_k
+// from the product launch's partials by the code of k_reduce_final -- the same tree, the same bits --, stored to row[0]; nu_k and
+// rr_k are read from the row, where the launch before stored them (kernel boundary); then the rule.  The word is tested first, as in
+// k_reduce_final_stop: all four waves read the same value and leave together, before the barrier.
+__global__ __launch_bounds__(kFinalThreads) void k_reduce_hs_mu_stop(
+    const double* __restrict__ partials, int nparts, double* __restrict__ row, SmallStop stop, int k)
+{
+    if (__builtin_amdgcn_readfirstlane(stop.word[0]) >= 0) return;
+    __shared__ double red[kFinalThreads / 64][kPartialStride];
+    reduce_final_waves(partials, nparts, 0, 1, red);
+    if (threadIdx.x == 0) {
+        const double mu = reduce_final_total(red, 0);
+        row[0] = mu;
+        const int verdict = stop_rule(mu, row[3], row[4], stop.thr);
         if (verdict) { stop.word[0] = k; stop.word[1] = verdict; }
     }
 }
@@ -1084,6 +1209,15 @@ int launch_spmv(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, 
     return -1;
 }
 
+int launch_spmv_dot_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps, const double* x, double* y,
+                         double* partials, const ProductStop& stop, TileKnobs kn)
+{
+    if (ntiles <= 0) return 0;
+    FusedPrev fz{};
+    fz.word = stop.word; fz.word_k = stop.k;
+    return launch_tiles_steps<1, kEpiDotXYStop>(steps, st, A, tiles, ntiles, x, y, 3, nullptr, nullptr, nullptr, partials, kn, nullptr, fz);
+}
+
 int launch_spmm2(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
                  const double* rs, double* wu, int write_mask, TileKnobs kn)
 {
@@ -1160,6 +1294,23 @@ int launch_hs_update_p(hipStream_t st, const HsArgs& a, const double* prev_nu, i
     const Chunking c = chunking(a.n);
     hipLaunchKernelGGL(k_hs_update_p, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_nu, nprev, dots_cur_w);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+
+int launch_hs_update_xr_stop(hipStream_t st, const HsArgs& a, const double* prev_mu, int nprev, double* dots_prev_w, const SmallStop& stop, int k) {
+    if (!stop.word || k < 1) return -1;
+    const Chunking c = chunking(a.n);
+    if (a.d) hipLaunchKernelGGL((k_hs_update_xr_stop<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w, stop, k);
+    else     hipLaunchKernelGGL((k_hs_update_xr_stop<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w, stop, k);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+int launch_hs_update_p_stop(hipStream_t st, const HsArgs& a, const double* prev_nu, int nprev, double* dots_cur_w, const int* word, int k) {
+    if (!word) return -1;
+    const Chunking c = chunking(a.n);
+    hipLaunchKernelGGL(k_hs_update_p_stop, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_nu, nprev, dots_cur_w, word, k);
+    return PRCG_LAUNCH_OK() ? c.grid : -1;
+}
+void launch_reduce_hs_mu_stop(hipStream_t st, const double* partials, int nparts, double* row, const SmallStop& stop, int k) {
+    hipLaunchKernelGGL(k_reduce_hs_mu_stop, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, row, stop, k);
 }
 
 int launch_pr_update(hipStream_t st, const PrArgs& a) {

@@ -375,6 +375,9 @@ int prcg::iterate_multi(prcg_t* h, int k) { return h->pipe2 ? iterate_pipe2(h, k
 // ... and so is the threshold of block-Jacobi single sessions: no multi-RHS session is begun while it is set
 #define STOP_BJ_SERVED "a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves pipelined SINGLE sessions with point-block "  \
                        "Jacobi only (prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_block_jacobi(h, NULL) clears the threshold"
+// ... and the threshold of Hestenes-Stiefel single sessions (the Hestenes-Stiefel multi-RHS sessions do not stop: a follow-up)
+#define STOP_HS_SERVED "a Hestenes-Stiefel stop threshold is set (prcg_set_stop_hs), which serves SINGLE PRCG_HS sessions only "  \
+                       "(prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_hs(h, NULL) clears the threshold"
 
 extern "C" {
 
@@ -389,6 +392,7 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi", hist_mask)) return rc;
     CHECK(h, !h->stop_rhs_set, "prcg_solve_begin_multi: " STOP_RHS_SERVED);
     CHECK(h, !h->stop_bj_set, "prcg_solve_begin_multi: " STOP_BJ_SERVED);
+    CHECK(h, !h->stop_hs_set, "prcg_solve_begin_multi: " STOP_HS_SERVED);
     CHECK(h, have_columns(b, x0, nrhs), "prcg_solve_begin_multi: null b or x0");
     if (int rc = open_pairs(h, "prcg_solve_begin_multi", variant, nrhs / 2, max_iter, hist_mask, inv_diag, 0)) return rc;
     return start_pairs(h, "prcg_solve_begin_multi", nrhs / 2, b, x0, 0);
@@ -406,6 +410,7 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
                         "four-vector one; an eight-vector product does not exist)", nrhs);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi_pipe", hist_mask)) return rc;
     CHECK(h, !h->stop_bj_set, "prcg_solve_begin_multi_pipe: " STOP_BJ_SERVED);
+    CHECK(h, !h->stop_hs_set, "prcg_solve_begin_multi_pipe: " STOP_HS_SERVED);
     CHECK(h, have_columns(b, x0, 2), "prcg_solve_begin_multi_pipe: null b or x0");
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
@@ -472,6 +477,7 @@ int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const 
     if (int rc = refuse_hooks(h, who, "multi-RHS", hist_mask)) return rc;
     CHECK(h, !h->stop_rhs_set, "%s: " STOP_RHS_SERVED, who);
     CHECK(h, !h->stop_bj_set, "%s: " STOP_BJ_SERVED, who);
+    CHECK(h, !h->stop_hs_set, "%s: " STOP_HS_SERVED, who);
     CHECK(h, have_columns(b, x0, nrhs), "%s: null b or x0", who);
     CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
     const int64_t tiles = bj_tile_count(h);

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_tiles(
     Coefs cf = {0.0, 0.0, 0.0};
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
-    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (nothing loaded, nothing stored, no barrier met)
+    if constexpr (epi_product_stop(EPI)) { if (product_stopped<NV>(fz)) return; }      // (nothing loaded, nothing stored, no barrier met)
     if constexpr (epi_fused(EPI)) {
         // inner products of the previous iteration: one row of partials per workgroup of the previous launch, summed by
         // every workgroup of this one in the fixed 256-thread tree (as k_spmv_tiles / k_win_tiles do); a session with a stop word
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_win(
     Coefs cf = {0.0, 0.0, 0.0};
     const FusedRowPtrs fr{reinterpret_cast<double2*>(yout_), reinterpret_cast<double2*>(ep_st), reinterpret_cast<double2*>(fz.rs),
                           ep_d, fz.w, fz.wt, (write_mask & 8) != 0};
-    if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (as k_sell_tiles)
+    if constexpr (epi_product_stop(EPI)) { if (product_stopped<NV>(fz)) return; }      // (as k_sell_tiles)
     if constexpr (epi_fused(EPI)) {
         if (!fused_prologue<kWaves>(fz, ep_r, (write_mask >> 2) & 1, aux, cf)) return;       // (as k_sell_tiles)
     }
@@ -567,6 +567,15 @@ int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int n
     default: break;
     }
     return -1;
+}
+
+int launch_sell_spmv_dot_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, double* partials,
+                              const ProductStop& stop, int per_cu)
+{
+    if (nslices <= 0) return 0;
+    FusedPrev fz{};
+    fz.word = stop.word; fz.word_k = stop.k;
+    return launch_sell<1, kEpiDotXYStop>(st, A, slices, nslices, x, y, 3, nullptr, nullptr, nullptr, partials, nullptr, fz, per_cu);
 }
 
 int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,

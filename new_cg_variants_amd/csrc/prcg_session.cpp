@@ -186,8 +186,10 @@ void fused_flush(prcg_t* h) {
 // iteration k_stop -- the iteration count; the input pairs, which every enqueued launch flipped once on the host only (the parity of
 // the difference says which buffer launch k_stop wrote; the one-workgroup solver works in place: no flip); and no partials are
 // pending (the reduction that would sum them returns at once as well).  A block-Jacobi session (Session::stop_bj) runs the
-// two-kernel schedule: nothing is flipped and nothing is ever pending, only the count goes back.  Idempotent: once resolved,
-// nothing more is enqueued.
+// two-kernel schedule: nothing is flipped and nothing is ever pending, only the count goes back.  A Hestenes-Stiefel session
+// (Session::stop_hs) on a window operator flips its two direction buffers, once per enqueued iteration and on the host only like the
+// input pairs: the parity of the difference says which one launch B of k_stop wrote; on other operators and on the one-workgroup
+// solver p is updated in place; mu is not pending either.  Idempotent: once resolved, nothing more is enqueued.
 int resolve_stop(prcg_t* h) {
     if (!h->in_session || !h->stop || h->stopped_k >= 0) return PRCG_OK;
     int w[2] = {-1, 0};
@@ -198,7 +200,9 @@ int resolve_stop(prcg_t* h) {
         double* const bufB = h->prec ? h->rst2.d() : h->rs2.d();
         h->rs_cur = (h->rs_cur == bufA) ? bufB : bufA;
     }
+    if (h->stop_hs && h->win && !h->small_hs && ((h->k - w[0]) & 1)) h->p_cur = (h->p_cur == h->p.d()) ? h->p2.d() : h->p.d();
     h->pend_parts = 0;
+    h->hs_pend_mu = 0;
     h->k = w[0];
     h->stopped_k = w[0]; h->stop_status = w[1];
     return PRCG_OK;
@@ -397,9 +401,12 @@ int iterate_hs(prcg_t* h, int k) {
 }
 
 // make mu of iteration pend_k real if the last product launch left it as block partials
+// (a session with a threshold, prcg_set_stop_hs: the reduction also DECIDES on the row it completes -- the iteration has no later launch
+//  whose prologue would -- and returns at once if the session has stopped: its partials are then stale)
 void hs_flush(prcg_t* h) {
     if (h->hs_pend_mu > 0) {
-        launch_reduce_final(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), 0, PRCG_S_MU, 1);
+        if (h->stop_hs) launch_reduce_hs_mu_stop(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), SmallStop{h->thr, h->word}, h->pend_k);
+        else launch_reduce_final(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), 0, PRCG_S_MU, 1);
         h->hs_pend_mu = 0;
     }
 }
@@ -411,13 +418,20 @@ void hs_flush(prcg_t* h) {
 //   launch 2  [nu_k from launch 1's partials; b = nu_k / nu_k1]  window operators: p = z + b p_old formed while the
 //             input window is staged, s = A p, mu_k partials, p_k written to the other direction buffer;
 //             CSR-adaptive tiles: the p update (with that prologue) and the product are two launches.
+// A session with a threshold (prcg_set_stop_hs) decides where mu of the previous iteration becomes known: in the prologue of launch 1,
+// which applies the rule to row k - 1 = {mu_k1, nu_k1, rr_k1} and may stop the session at k - 1 (k_hs_update_xr_stop), or in the
+// reduction that ends the call (hs_flush).  Launch 2 and the product decide nothing (mu_k does not exist before they have run);
+// they return at once if the session stopped BEFORE k.  So the product s_k = A p_k of the stop iteration is computed although
+// rr_k was known before it: one product per solve, the price of one rule for every session type.
 int iterate_hs_fused(prcg_t* h, int k) {
     HsArgs a = hs_args(h, k);
     const bool have_mu = h->hs_pend_mu > 0 && h->pend_k == k - 1;
     if (!have_mu) hs_flush(h);
     bool on = false;
     prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-    const int g1 = launch_hs_update_xr(h->sc, a, have_mu ? h->partB.d() : nullptr, have_mu ? h->hs_pend_mu : 0, dots_at(h, k - 1));
+    const int g1 = h->stop_hs
+        ? launch_hs_update_xr_stop(h->sc, a, have_mu ? h->partB.d() : nullptr, have_mu ? h->hs_pend_mu : 0, dots_at(h, k - 1), SmallStop{h->thr, h->word}, k)
+        : launch_hs_update_xr(h->sc, a, have_mu ? h->partB.d() : nullptr, have_mu ? h->hs_pend_mu : 0, dots_at(h, k - 1));
     LAUNCHCHK(h, g1);
     prof_end(h, h->ev_upd, h->n_ev_upd, on);
     h->hs_pend_mu = 0;
@@ -427,6 +441,7 @@ int iterate_hs_fused(prcg_t* h, int k) {
         FusedPrev hs{};
         hs.prev_partials = h->partA.d(); hs.nprev = g1;
         hs.dots_prev_out = dots_at(h, k); hs.dots_old = dots_at(h, k - 1);
+        if (h->stop_hs) { hs.word = h->word; hs.word_k = k; }
         double* p_new = (h->p_cur == h->p.d()) ? h->p2.d() : h->p.d();
         SRCCHK2(h, {h->prec ? h->rt.d() : h->r.d(), 1}, {h->p_cur, 1});
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
@@ -438,9 +453,11 @@ int iterate_hs_fused(prcg_t* h, int k) {
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->p_cur = p_new;
     } else {
-        LAUNCHCHK(h, launch_hs_update_p(h->sc, a, h->partA.d(), g1, dots_at(h, k)));
+        LAUNCHCHK(h, h->stop_hs ? launch_hs_update_p_stop(h->sc, a, h->partA.d(), g1, dots_at(h, k), h->word, k)
+                                : launch_hs_update_p(h->sc, a, h->partA.d(), g1, dots_at(h, k)));
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
-        grid = eng_spmv(h, h->sc, 0, h->p_cur, h->s.d(), kEpiDotXY, nullptr, nullptr, nullptr, h->partB.d());
+        grid = h->stop_hs ? eng_spmv_dot_stop(h, h->sc, 0, h->p_cur, h->s.d(), h->partB.d(), ProductStop{h->word, k})
+                          : eng_spmv(h, h->sc, 0, h->p_cur, h->s.d(), kEpiDotXY, nullptr, nullptr, nullptr, h->partB.d());
         LAUNCHCHK(h, grid);
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     }
@@ -1077,6 +1094,9 @@ int begin_hs_pr(prcg_t* h) {
     h->small_hs = h->hs_fused && h->opt.want_small && !h->prec &&
                   !records_state(hist_mask) &&
                   small_fits(h->n, h->nnz, h->max_row_len, &h->small_mode);
+    // a session with a threshold (prcg_set_stop_hs) runs the schedule without reduction launches or the one-workgroup solver: what
+    // prcg_solve_begin let through selects one of them
+    CHECK(h, !h->stop_hs || h->hs_fused, "prcg_solve_begin: a Hestenes-Stiefel stop threshold is set and the session did not get the schedule without reduction launches");
     // r (r~) is the staged-window source of the Hestenes-Stiefel product launch: like every vector that feeds a
     // product it has the spare entries behind its end (a window page of the last tile may reach past row n)
     HIPCHK(h, h->r.ensure((size_t)(h->opt.debug_short_sources ? n : ne) * D, h->sc));
@@ -1116,7 +1136,10 @@ int begin_hs_pr(prcg_t* h) {
         if ((rc = allreduce(h, dots_at(h, 0) + PRCG_S_NU, 2, sc))) return rc;
         int grid = 0;
         if ((rc = dist_spmv(h, h->p.d(), h->s.d(), kEpiDotXY, nullptr, nullptr, nullptr, &grid))) return rc;
-        launch_reduce_final(sc, h->partB.d(), grid, dots_at(h, 0), 0, PRCG_S_MU, 1);   // mu = p.s  :27
+        // (with a threshold, prcg_set_stop_hs: the rule on row 0 rides on the reduction that completes it -- b = A x0 stops the session
+        //  before its first iteration)
+        if (h->stop_hs) launch_reduce_hs_mu_stop(sc, h->partB.d(), grid, dots_at(h, 0), SmallStop{h->thr, h->word}, 0);
+        else launch_reduce_final(sc, h->partB.d(), grid, dots_at(h, 0), 0, PRCG_S_MU, 1);   // mu = p.s  :27
         if ((rc = allreduce(h, dots_at(h, 0) + PRCG_S_MU, 1, sc))) return rc;
     } else {
         PrArgs a = pr_args(h, 0);
@@ -1176,7 +1199,7 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     //  four right-hand sides: twice the rows again, one set per pair group)
     HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * rows_per_iteration * kNS * D, h->sc));
     HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * rows_per_iteration * kCoefStride * D, h->sc));
-    if (h->stop_set || h->stop_bj_set) {
+    if (h->stop_set || h->stop_bj_set || h->stop_hs_set) {
         // the stop word of a session with a threshold: {-1, 0} = running (prcg_solve_begin arms it; other session types leave it alone)
         static const int kRunning[2] = {-1, 0};
         if (!h->stop_word.p) HIPCHK(h, h->stop_word.alloc(16));
@@ -1225,6 +1248,21 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
 #undef STOP_CLEARS
 #undef STOP_SERVED
     }
+    if (h->stop_hs_set) {
+        // a threshold for Hestenes-Stiefel sessions is set (prcg_set_stop_hs): only what stops on the device is begun
+#define STOP_SERVED "a Hestenes-Stiefel stop threshold is set (prcg_set_stop_hs), which serves PRCG_HS on one GPU, unpreconditioned or with inv_diag, " \
+                    "on the schedule without reduction launches or the one-workgroup solver"
+#define STOP_CLEARS "(prcg_set_stop_hs(h, NULL) clears the threshold)"
+        CHECK(h, variant == PRCG_HS, "prcg_solve_begin: " STOP_SERVED "; variant %d is not Hestenes-Stiefel " STOP_CLEARS, variant);
+        CHECK(h, !h->multi() && h->g == 0, "prcg_solve_begin: " STOP_SERVED "; this handle has a communicator or ghost rows " STOP_CLEARS);
+        CHECK(h, inv_diag || !(h->cb || h->have_block_jacobi()),
+              "prcg_solve_begin: " STOP_SERVED "; a host-callback or block-Jacobi preconditioner is in force (the stored-tilde schedule with reduction "
+              "launches cannot stop) " STOP_CLEARS);
+        CHECK(h, h->opt.want_fused, "prcg_solve_begin: " STOP_SERVED "; PRCG_FUSED=0 selects the schedule with reduction launches, which cannot stop " STOP_CLEARS);
+        CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set " STOP_CLEARS);
+#undef STOP_CLEARS
+#undef STOP_SERVED
+    }
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries: the
     // narrow column encodings decode a few out-of-tile bytes per tile against the tile's own base
     // (products nobody reads); the pad keeps those gathers inside the allocation without a test
@@ -1235,6 +1273,7 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     if (rc) return rc;
     if (h->stop_set) { h->stop = true; h->thr = h->stop_thr; h->word = h->stop_word.i(); }
     if (h->stop_bj_set) { h->stop = h->stop_bj = true; h->thr = h->stop_bj_thr; h->word = h->stop_word.i(); }
+    if (h->stop_hs_set) { h->stop = h->stop_hs = true; h->thr = h->stop_hs_thr; h->word = h->stop_word.i(); }
     if ((rc = h2d(h, h->x.d(), x0, n))) return rc;
     if ((rc = h2d(h, h->b.d(), b, n))) return rc;
     if (x_true && (rc = h2d(h, h->xt.d(), x_true, n))) return rc;
@@ -1279,7 +1318,7 @@ int prcg_iterate(prcg_t* h, int iters) {
         const SmallStop ss{h->thr, h->word};
         bool on = false;
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, 0, on);
-        LAUNCHCHK(h, h->small_hs ? launch_small_hs(h->sc, sa, h->small_mode) : launch_small_pipe_pr(h->sc, sa, h->small_mode, h->stop ? &ss : nullptr));
+        LAUNCHCHK(h, h->small_hs ? launch_small_hs(h->sc, sa, h->small_mode, h->stop ? &ss : nullptr) : launch_small_pipe_pr(h->sc, sa, h->small_mode, h->stop ? &ss : nullptr));
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->k += iters;
         return PRCG_OK;
@@ -1343,6 +1382,15 @@ int prcg_set_stop_block_jacobi(prcg_t* h, const double* rr_stop) {
     return PRCG_OK;
 }
 
+int prcg_set_stop_hs(prcg_t* h, const double* rr_stop) {
+    if (!h) return PRCG_EINVAL;
+    if (!rr_stop) { h->stop_hs_set = false; h->stop_hs_thr = 0.0; return PRCG_OK; }
+    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "prcg_set_stop_hs: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop "
+                                                         "stops the session; NULL clears it)", *rr_stop);
+    h->stop_hs_set = true; h->stop_hs_thr = *rr_stop;
+    return PRCG_OK;
+}
+
 int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_get_stop: no open session");
@@ -1374,7 +1422,7 @@ int prcg_set_iteration(prcg_t* h, int k) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_set_iteration: no open session");
     NOT_RHS2(h, "prcg_set_iteration");
-    CHECK(h, !h->stop, "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi): its state is not set from outside");
+    CHECK(h, !h->stop, "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
     CHECK(h, k >= 0 && k < h->max_iter, "prcg_set_iteration: k out of range");
     h->k = k;
     if (h->peer && is_pipe(h->variant)) {
@@ -1435,7 +1483,7 @@ int prcg_set_vector(prcg_t* h, int which, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in, "prcg_set_vector: no session or null buffer");
     NOT_RHS2(h, "prcg_set_vector");
-    CHECK(h, !h->stop, "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi): its state is not set from outside");
+    CHECK(h, !h->stop, "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int64_t n = h->n;
@@ -1466,7 +1514,7 @@ int prcg_set_scalars(prcg_t* h, int k, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in && k >= 0 && k <= h->max_iter, "prcg_set_scalars: bad argument");
     NOT_RHS2(h, "prcg_set_scalars");
-    CHECK(h, !h->stop, "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi): its state is not set from outside");
+    CHECK(h, !h->stop, "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     if ((rc = h2d(h, dots_at(h, k), in, kNS))) return rc;

@@ -463,6 +463,9 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_hs(SmallArgs a) { small
 // ... stopped at a residual threshold (prcg_set_stop): the STOP form of the body on the session's own word
 template <int MODE>
 __global__ __launch_bounds__(kSmallThreads) void k_small_pipe_pr_stop(SmallArgs a, SmallStop stop) { small_pipe_pr_body<MODE, kSmallPrecNone, true>(a, SmallJacobi{}, SmallBlocks{}, stop); }
+// ... and the Hestenes-Stiefel single session (prcg_set_stop_hs): what a system of a batch with a threshold runs, on the session's word
+template <int MODE>
+__global__ __launch_bounds__(kSmallThreads) void k_small_hs_stop(SmallArgs a, SmallStop stop) { small_hs_body<MODE, kSmallPrecNone, true>(a, SmallJacobi{}, SmallBlocks{}, stop); }
 
 // ---- a BATCH of small systems: one launch, workgroup blockIdx.x solves system desc[blockIdx.x] (prcg_batch.cpp) ----
 // The descriptors live in device memory, one SmallArgs per system with pointers into the batch's concatenated matrix, state,
@@ -638,7 +641,7 @@ const SmallBlocksFn kSmallBlocksFn[2][2][2] = {
     {{k_small_hs_blocks<0, false>, k_small_hs_blocks<0, true>}, {k_small_hs_blocks<1, false>, k_small_hs_blocks<1, true>}}};
 const SmallSingleFn kSmallSingleFn[2][2] = {{k_small_pipe_pr<0>, k_small_pipe_pr<1>}, {k_small_hs<0>, k_small_hs<1>}};      // [hs][mode]
 using SmallSingleStopFn = void (*)(SmallArgs, SmallStop);
-const SmallSingleStopFn kSmallSingleStopFn[2] = {k_small_pipe_pr_stop<0>, k_small_pipe_pr_stop<1>};                         // [mode]
+const SmallSingleStopFn kSmallSingleStopFn[2][2] = {{k_small_pipe_pr_stop<0>, k_small_pipe_pr_stop<1>}, {k_small_hs_stop<0>, k_small_hs_stop<1>}};      // [hs][mode]
 
 // The kernels may ask for more dynamic LDS than the default 64 KB.  The attribute belongs to the CURRENT device: set for all of
 // them on first use on each device, and only a SUCCESSFUL round counts as done.
@@ -655,26 +658,22 @@ bool small_lds_attribute() {
         if (!set(reinterpret_cast<const void*>((&kSmallBlocksFn[0][0][0])[i]))) return false;
     for (int i = 0; i < 4; ++i)
         if (!set(reinterpret_cast<const void*>((&kSmallSingleFn[0][0])[i]))) return false;
-    for (int i = 0; i < 2; ++i)
-        if (!set(reinterpret_cast<const void*>(kSmallSingleStopFn[i]))) return false;
+    for (int i = 0; i < 4; ++i)
+        if (!set(reinterpret_cast<const void*>((&kSmallSingleStopFn[0][0])[i]))) return false;
     if (dev < kMaxDev) attr_done[dev] = true;
     return true;
 }
-int launch_small_single(hipStream_t st, const SmallArgs& a, int mode, bool hs) {
+int launch_small_single(hipStream_t st, const SmallArgs& a, int mode, bool hs, const SmallStop* stop) {
     if (!small_lds_attribute()) return -1;
-    hipLaunchKernelGGL(kSmallSingleFn[hs][mode == 1], dim3(1), dim3(kSmallThreads), small_lds_bytes(a.n, a.nnz, mode), st, a);
+    if (stop) hipLaunchKernelGGL(kSmallSingleStopFn[hs][mode == 1], dim3(1), dim3(kSmallThreads), small_lds_bytes(a.n, a.nnz, mode), st, a, *stop);
+    else hipLaunchKernelGGL(kSmallSingleFn[hs][mode == 1], dim3(1), dim3(kSmallThreads), small_lds_bytes(a.n, a.nnz, mode), st, a);
     return hipGetLastError() == hipSuccess ? 1 : -1;
 }
 }  // namespace
 
-int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop) {
-    if (!stop) return launch_small_single(st, a, mode, false);
-    if (!small_lds_attribute()) return -1;
-    hipLaunchKernelGGL(kSmallSingleStopFn[mode == 1], dim3(1), dim3(kSmallThreads), small_lds_bytes(a.n, a.nnz, mode), st, a, *stop);
-    return hipGetLastError() == hipSuccess ? 1 : -1;
-}
+int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop) { return launch_small_single(st, a, mode, false, stop); }
 // (xp = x, rs = r, hs_p = p, hs_s = s: separate arrays, as the Hestenes-Stiefel sessions hold them)
-int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode) { return launch_small_single(st, a, mode, true); }
+int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop) { return launch_small_single(st, a, mode, true, stop); }
 
 // ---- batch of small systems: `count` workgroups, one per descriptor (all of one mode; lds: the largest small_lds_bytes among them)
 int launch_small_batch_init(hipStream_t st, const SmallArgs* desc, const SmallInit* init, const SmallJacobi* jac, int count, bool hs,

@@ -1039,6 +1039,8 @@ __global__ __launch_bounds__(64 * WPB, win_min_blocks(M, VD, DEF, WPB, NV, PG, C
     Coefs cf = {0.0, 0.0, 0.0};
     constexpr bool PR1 = epi_pr_one(EPI);
     if constexpr (EPI == kEpiNoneStop) { if (product_stopped<NV>(fz)) return; }      // (nothing requested, loaded or stored, no barrier met)
+    // (the Hestenes-Stiefel product launch of a session that stops, prcg_set_stop_hs: the same head, reached only through a word)
+    if constexpr (EPI == kEpiHS) { if (fz.word && product_stopped<NV>(fz)) return; }
     if constexpr ((FUSED || PR1) && DEF == 0) {
         // inner products of the previous iteration: still one row of partials per block of the
         // previous launch -- every block of this launch sums them in the same fixed order

@@ -327,8 +327,9 @@ class DeviceCSR:
         """rr_stop: None, or a threshold on r.r, finite and >= 0: THIS session then stops by itself on the device, converged or
         broken down, by the rule of prcg.h: prcg_set_stop (pipelined variants on one GPU, unpreconditioned or with inv_diag), or,
         with block_jacobi= / block_jacobi_var=, prcg_set_stop_block_jacobi (pipelined variants on one GPU with point-block Jacobi,
-        set or built on the device: the stored-tilde schedule, every launch in its stop form); anything else is refused.  stop()
-        tells where and why.
+        set or built on the device: the stored-tilde schedule, every launch in its stop form), or, for L.HS without blocks or a
+        callback, prcg_set_stop_hs (Hestenes-Stiefel on one GPU, unpreconditioned or with inv_diag); anything else is refused.
+        stop() tells where and why.
         inv_diag: Jacobi on the device.  block_jacobi=(bs, inv_blocks): point-block Jacobi on the device, inv_blocks
         the ceil(n/bs) x bs x bs inverses of the diagonal blocks (prcg.h: prcg_set_block_jacobi); inv_blocks None: the blocks
         BUILT ON THE DEVICE from the operator (build_block_jacobi) -- rebuilt only when blocks of that bs built from the
@@ -368,15 +369,20 @@ class DeviceCSR:
         self._put_blocks(block_jacobi, block_jacobi_var)
         thr = None if rr_stop is None else np.array([rr_stop], dtype=np.float64)
         blocks = block_jacobi is not None or block_jacobi_var is not None
+        # Hestenes-Stiefel without blocks or a callback stops through a setter of its own (prcg.h: prcg_set_stop_hs)
+        hs = int(variant) == L.HS and not blocks and preconditioner is None
         # each setter gets the threshold or None, which clears what an earlier session set: with blocks the block-Jacobi one
-        self._check(self._lib.prcg_set_stop(self._h, L.ptr(None if blocks else thr)))
+        self._check(self._lib.prcg_set_stop(self._h, L.ptr(None if blocks or hs else thr)))
         self._check(self._lib.prcg_set_stop_block_jacobi(self._h, L.ptr(thr if blocks else None)))
+        self._check(self._lib.prcg_set_stop_hs(self._h, L.ptr(thr if hs else None)))
         try:
             self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
                                                    L.ptr(xt), L.ptr(dv), int(hist_mask)))
         finally:
             if blocks and thr is not None:     # the threshold is this session's: the multi-RHS begins, which it refuses, are served again
                 self._check(self._lib.prcg_set_stop_block_jacobi(self._h, None))
+            if hs and thr is not None:         # (the same for the Hestenes-Stiefel one)
+                self._check(self._lib.prcg_set_stop_hs(self._h, None))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
 
     def _put_blocks(self, block_jacobi, block_jacobi_var):
