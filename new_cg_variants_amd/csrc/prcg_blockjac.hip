@@ -122,14 +122,13 @@ void launch_one(hipStream_t st, double* dst, int ds, const double* src, int ss, 
     hipLaunchKernelGGL(k_block_jacobi<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, dst, ds, src, ss, n, blk);
 }
 template <int BS>
-void launch_two(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, const double* blk, int mask) {
-    hipLaunchKernelGGL(k_block_jacobi_pair<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
-                       blk, mask);
-}
-template <int BS>
-void launch_two_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, const double* blk, int mask, const ProductStop& stop) {
-    hipLaunchKernelGGL(k_block_jacobi_pair_stop<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
-                       blk, mask, stop);
+void launch_two(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, const double* blk, int mask, const StopAt& stop) {
+    if (stop)
+        hipLaunchKernelGGL(k_block_jacobi_pair_stop<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
+                           blk, mask, stop.skips());
+    else
+        hipLaunchKernelGGL(k_block_jacobi_pair<BS>, dim3(bj_grid(n, BS)), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), n,
+                           blk, mask);
 }
 
 // ---- the device build (prcg_build_block_jacobi): gather the diagonal blocks from the caller-order CSR arrays, invert them, store
@@ -510,19 +509,14 @@ int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const doub
 }
 
 int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
-                                 const unsigned char* code, const double* blocks, int mask) {
+                                 const unsigned char* code, const double* blocks, int mask, const StopAt& stop) {
     if (ntiles <= 0) return 0;
-    hipLaunchKernelGGL(k_block_jacobi_var_pair, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), tiles,
-                       code, blocks, mask);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_block_jacobi_var_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
-                                      const unsigned char* code, const double* blocks, int mask, const ProductStop& stop) {
-    if (ntiles <= 0) return 0;
-    if (!stop.word) return -1;
-    hipLaunchKernelGGL(k_block_jacobi_var_pair_stop, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), tiles,
-                       code, blocks, mask, stop);
+    if (stop)
+        hipLaunchKernelGGL(k_block_jacobi_var_pair_stop, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), tiles,
+                           code, blocks, mask, stop.skips());
+    else
+        hipLaunchKernelGGL(k_block_jacobi_var_pair, dim3((unsigned)ntiles), dim3(kBjBlock), 0, st, wt, ut, reinterpret_cast<const d2_t*>(wu), tiles,
+                           code, blocks, mask);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -600,35 +594,18 @@ int launch_block_jacobi(hipStream_t st, double* dst, int dstride, const double* 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask) {
+int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask,
+                             const StopAt& stop) {
     if (n <= 0) return 0;
     switch (bs) {
-    case 1: launch_two<1>(st, wt, ut, wu, n, blocks, mask); break;
-    case 2: launch_two<2>(st, wt, ut, wu, n, blocks, mask); break;
-    case 3: launch_two<3>(st, wt, ut, wu, n, blocks, mask); break;
-    case 4: launch_two<4>(st, wt, ut, wu, n, blocks, mask); break;
-    case 5: launch_two<5>(st, wt, ut, wu, n, blocks, mask); break;
-    case 6: launch_two<6>(st, wt, ut, wu, n, blocks, mask); break;
-    case 7: launch_two<7>(st, wt, ut, wu, n, blocks, mask); break;
-    case 8: launch_two<8>(st, wt, ut, wu, n, blocks, mask); break;
-    default: return -1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_block_jacobi_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask,
-                                  const ProductStop& stop) {
-    if (n <= 0) return 0;
-    if (!stop.word) return -1;
-    switch (bs) {
-    case 1: launch_two_stop<1>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 2: launch_two_stop<2>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 3: launch_two_stop<3>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 4: launch_two_stop<4>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 5: launch_two_stop<5>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 6: launch_two_stop<6>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 7: launch_two_stop<7>(st, wt, ut, wu, n, blocks, mask, stop); break;
-    case 8: launch_two_stop<8>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 1: launch_two<1>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 2: launch_two<2>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 3: launch_two<3>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 4: launch_two<4>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 5: launch_two<5>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 6: launch_two<6>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 7: launch_two<7>(st, wt, ut, wu, n, blocks, mask, stop); break;
+    case 8: launch_two<8>(st, wt, ut, wu, n, blocks, mask, stop); break;
     default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;

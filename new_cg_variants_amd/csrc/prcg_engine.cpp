@@ -104,67 +104,42 @@ void note_partials_launch(prcg_t* h, int grid) {
     h->int_grid = 0; h->int_wpb = 0;         // (one launch over its tiles, until overlapped_spmv says otherwise)
 }
 int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, SpmvEpilogue epi, const double* ep_r,
-             const double* ep_d, double* ep_st, double* partials) {
+             const double* ep_d, double* ep_st, double* partials, const StopAt& stop) {
     SRCCHK(h, {x, 1});
     const TileRange t = tile_range(h, which);
     if (h->win) {
+        if (stop) return -1;      // (the window kernels have no stop form of this product: launch_win_hs serves such a session)
         const int grid = launch_win_spmv(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, x, y, epi, ep_r, ep_d, ep_st, partials,
                                          h->opt.win_per_cu);
         if (epi != kEpiNone) note_partials_launch(h, grid);
         return grid;
     }
     const int grid = h->sell
-        ? launch_sell_spmv(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.sell_per_cu)
-        : launch_spmv(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.kn);
+        ? launch_sell_spmv(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.sell_per_cu, stop)
+        : launch_spmv(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, epi, ep_r, ep_d, ep_st, partials, h->opt.kn, stop);
     if (epi != kEpiNone) note_partials_launch(h, grid);
     return grid;
 }
-int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask) {
+int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const StopAt& stop) {
     SRCCHK(h, {rs, 2});
     const TileRange t = tile_range(h, which);
-    if (h->win) return launch_win_spmm2(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, mask, h->opt.win_per_cu);
-    if (h->sell) return launch_sell_spmm2(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, h->opt.sell_per_cu);
-    return launch_spmm2(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, h->opt.kn);
+    if (h->win) return launch_win_spmm2(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, mask, h->opt.win_per_cu, stop);
+    if (h->sell) return launch_sell_spmm2(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, h->opt.sell_per_cu, stop);
+    return launch_spmm2(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, h->opt.kn, stop);
 }
 // [dst0 | dst1] = A [src0 | src1], two pair arrays: one launch on sliced rows (PRCG_SPMM4=0: never), else a two-vector
 // product per pair -- the same bits per column either way
 bool spmm4_one_launch(const prcg_t* h) { return h->sell && h->opt.want_spmm4; }
-int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1) {
+int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, const StopAt& stop) {
     SRCCHK(h, {src0, 2}, {src1, 2});
     if (spmm4_one_launch(h)) {
         const TileRange t = tile_range(h, which);
-        return launch_sell_spmm4(st, h->sdev(), h->sslice_ptr(t.first), t.count, src0, src1, dst0, dst1, h->opt.sell_per_cu);
+        return launch_sell_spmm4(st, h->sdev(), h->sslice_ptr(t.first), t.count, src0, src1, dst0, dst1, h->opt.sell_per_cu, stop);
     }
-    const int g0 = eng_spmm2(h, st, which, src0, dst0, 3);
+    const int g0 = eng_spmm2(h, st, which, src0, dst0, 3, stop);
     if (g0 < 0) return g0;
-    return eng_spmm2(h, st, which, src1, dst1, 3);
-}
-int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const ProductStop& stop) {
-    SRCCHK(h, {rs, 2});
-    const TileRange t = tile_range(h, which);
-    if (h->win) return launch_win_spmm2_stop(st, h->wdev(), h->wtile_ptr(t.first), t.count, h->win_geom, rs, wu, mask, stop, h->opt.win_per_cu);
-    if (h->sell) return launch_sell_spmm2_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, rs, wu, mask, stop, h->opt.sell_per_cu);
-    return launch_spmm2_stop(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, rs, wu, mask, stop, h->opt.kn);
-}
-int eng_spmv_dot_stop(prcg_t* h, hipStream_t st, int which, const double* x, double* y, double* partials, const ProductStop& stop) {
-    SRCCHK(h, {x, 1});
-    if (h->win) return -1;
-    const TileRange t = tile_range(h, which);
-    const int grid = h->sell
-        ? launch_sell_spmv_dot_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, x, y, partials, stop, h->opt.sell_per_cu)
-        : launch_spmv_dot_stop(st, csr_view(h, which), h->tile_ptr(t.first), t.count, h->steps, x, y, partials, stop, h->opt.kn);
-    note_partials_launch(h, grid);
-    return grid;
-}
-int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k) {
-    SRCCHK(h, {src0, 2}, {src1, 2});
-    if (spmm4_one_launch(h)) {
-        const TileRange t = tile_range(h, which);
-        return launch_sell_spmm4_stop(st, h->sdev(), h->sslice_ptr(t.first), t.count, src0, src1, dst0, dst1, ProductStop{words, k}, h->opt.sell_per_cu);
-    }
-    const int g0 = eng_spmm2_stop(h, st, which, src0, dst0, 3, ProductStop{words, k});
-    if (g0 < 0) return g0;
-    return eng_spmm2_stop(h, st, which, src1, dst1, 3, ProductStop{words + 2, k});
+    // (column 1 skips by its own word, which follows column 0's)
+    return eng_spmm2(h, st, which, src1, dst1, 3, stop ? StopAt{stop.thr, stop.word + 2, stop.k} : stop);
 }
 // (only the window kernels have the deferred form that runs one class of tiles; the others always take every tile)
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which) {

@@ -65,6 +65,18 @@ struct DevBuf {
 
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; };
 
+// How a session stops at a residual threshold, decided on the device.  A kind names both the request on the handle (its setter:
+// Handle::stop_req) and what the session begun from it runs (Session::stop_kind):
+//   kStopPipe         prcg_set_stop: a pipelined single session on the one-launch schedule (the prologue of launch k + 1 decides on
+//                     row k) or the one-workgroup solver
+//   kStopRhs          prcg_set_stop_rhs: the pipelined two-RHS session, each column at its own threshold (two stop words)
+//   kStopBlockJacobi  prcg_set_stop_block_jacobi: a pipelined single session with blocks, the stored-tilde two-kernel schedule, every
+//                     launch of an iteration in its stop form; fused is off, nothing is ever pending
+//   kStopHs           prcg_set_stop_hs: a Hestenes-Stiefel single session on the schedule without reduction launches
+//                     (iterate_hs_fused), every launch in its stop form, or the one-workgroup solver's
+// (in the order the begin paths consult the requests: refuse_unserved_stops)
+enum StopKind { kStopNone = -1, kStopPipe = 0, kStopRhs, kStopBlockJacobi, kStopHs, kNumStopKinds };
+
 // The resident operator: what plan_operator decided (OperatorShape) and the arrays prcg_set_csr uploaded.
 struct Operator : OperatorShape {
     bool have_csr = false;
@@ -185,23 +197,20 @@ struct Session {
     int last_wpb = 0;            // ... and its waves per workgroup (window operators: what launch_win_v instantiated; else 0)
     int int_grid = 0;            // that launch was the BOUNDARY half of a product in two launches (overlapped_spmv with a communicator):
     int int_wpb = 0;             // ... workgroups and waves per workgroup of the interior half, whose partial rows come first (else 0)
-    // ---- stopped at a residual threshold, decided on the device (prcg_set_stop; pipelined single sessions) ----
-    bool stop = false;           // the session was begun with a threshold ...
-    double thr = 0.0;            // ... on r.r
-    int* word = nullptr;         // ... and this is its stop word in device memory (Handle::stop_word): {-1, 0} while it runs, {k_stop, status}
-                                 // once a launch's prologue, the final reduction or the one-workgroup solver has stopped it
-    int stopped_k = -1;          // what prcg_sync has read from the word: the iteration whose state the session holds (-1: running) ...
-    int stop_status = 0;         // ... and why (1 converged, 2 breakdown)
-    bool stop_bj = false;        // ... `stop` of a BLOCK-JACOBI session (prcg_set_stop_block_jacobi): the stored-tilde two-kernel schedule, every
-                                 // launch of an iteration in its stop form on `word` (iterate_pipe); fused is off, nothing is ever pending
-    bool stop_hs = false;        // ... `stop` of a HESTENES-STIEFEL session (prcg_set_stop_hs): the schedule without reduction launches
-                                 // (iterate_hs_fused), every launch in its stop form on `word`, or the one-workgroup solver's
-    // ---- each column stopped at its own threshold (prcg_set_stop_rhs; the pipelined two-RHS session) ----
-    bool stop_rhs = false;               // the session was begun with per-column thresholds ...
-    double thr_rhs[2] = {0.0, 0.0};      // ... on r.r of column c; its stop word: Handle::stop_words_rhs + 2 c
-    int stopped_k_rhs[2] = {-1, -1};     // what prcg_sync has read from the words: the iteration whose state column c holds (-1: running) ...
-    int stop_status_rhs[2] = {0, 0};     // ... and why (1 converged, 2 breakdown)
-    bool all_stopped_rhs() const { return stop_rhs && stopped_k_rhs[0] >= 0 && stopped_k_rhs[1] >= 0; }
+    // ---- stopped at a residual threshold, decided on the device (arm_stop sets these; one set for every kind, sized for two columns) ----
+    StopKind stop_kind = kStopNone;      // how the session stops (kStopNone: it was begun without a threshold) ...
+    double thr[2] = {0.0, 0.0};          // ... at this threshold on r.r (kStopRhs: column c's; else [0])
+    int* word = nullptr;                 // ... through these stop words in device memory (Handle::stop_words), column c's at word + 2 c: {-1, 0}
+                                         // while it runs, {k_stop, status} once a launch's prologue, a deciding reduction or the one-workgroup
+                                         // solver has stopped it
+    int stopped_k[2] = {-1, -1};         // what prcg_sync has read from the words: the iteration whose state column c holds (-1: running) ...
+    int stop_status[2] = {0, 0};         // ... and why (1 converged, 2 breakdown)
+    bool stops() const { return stop_kind != kStopNone; }
+    int stop_cols() const { return stop_kind == kStopRhs ? 2 : 1; }
+    bool column_stopped(int c) const { return stops() && c < stop_cols() && stopped_k[c] >= 0; }
+    bool stopped() const { return column_stopped(0) && (stop_cols() == 1 || column_stopped(1)); }      // every column: prcg_iterate is a no-op
+    // how iteration k (of column c) stops: what every launcher of the iteration takes last -- none for a session without a threshold
+    StopAt stop_at(int k, int c = 0) const { return stops() ? StopAt{thr[c], word + 2 * c, k} : StopAt{}; }
 };
 
 // One PAIR GROUP of a session with two or four right-hand sides: the interleaved n x 2 arrays X, R, P, S, RT of two columns
@@ -283,17 +292,13 @@ struct Handle : Operator, Session {
     const unsigned char* bjv_code_d() const { return static_cast<const unsigned char*>(bjv_bytes.p); }
     const unsigned char* bjv_bidx_d() const { return bjv_code_d() + bjv_plan.ntiles * kBjvLanes; }
     prcg_replace_fn replace_fn = nullptr; void* replace_ctx = nullptr;       // gv_cg's w_replace predicate (prcg_set_replace_hook)
-    // residual threshold for single sessions begun from now on (prcg_set_stop); the word a session with one stops itself through
-    bool stop_set = false; double stop_thr = 0.0;
-    DevBuf stop_word;
-    // ... and for pipelined single sessions WITH BLOCK JACOBI begun from now on (prcg_set_stop_block_jacobi; the same word)
-    bool stop_bj_set = false; double stop_bj_thr = 0.0;
-    // ... and for Hestenes-Stiefel single sessions begun from now on (prcg_set_stop_hs; the same word)
-    bool stop_hs_set = false; double stop_hs_thr = 0.0;
-    // ... and per column for pipelined two-RHS sessions begun from now on (prcg_set_stop_rhs); the columns' words: four ints, column c's
-    // {k, status} at 2 c (SmallStop's layout), allocated once, armed to {-1, 0} when such a session begins
-    bool stop_rhs_set = false; double stop_rhs_thr[2] = {0.0, 0.0};
-    DevBuf stop_words_rhs;
+    // residual thresholds for sessions begun from now on, one request per kind (its setter's), independent of each other: with
+    // several set, each begin path refuses by the first it does not serve (refuse_unserved_stops).  thr[1]: kStopRhs only
+    struct StopRequest { bool set = false; double thr[2] = {0.0, 0.0}; };
+    StopRequest stop_req[kNumStopKinds];
+    // the words a session with a threshold stops itself through: four ints, column c's {k, status} at 2 c (SmallStop's layout),
+    // allocated once, armed to {-1, 0} when a session of any kind begins (arm_stop)
+    DevBuf stop_words;
     std::vector<double> cb_in, cb_out;
     DevBuf cb_stage, ut;         // staging for strided operands; u~ = M^-1 u of the pipelined variants
 
@@ -395,19 +400,19 @@ inline double* coef_at(prcg_t* h, int k) { return h->coef.d() + (size_t)k * kCoe
 
 // ---- prcg_engine.cpp: the services every session type is built from ----
 // the matrix products (which: 0 = every tile, 1 = interior tiles, 2 = tiles touching ghosts); they return the grid, -2 when refused
+// stop (Session::stop_at; none: the launches of a session without a threshold): the product of iteration stop.k in its stop form
+// (ProductStop, prcg_kernels.h) -- it skips if the session (the column) stopped BEFORE stop.k and decides nothing
+//   eng_spmv   kEpiDotXY on sliced rows or CSR-adaptive tiles only: a Hestenes-Stiefel session that stops (a window operator runs
+//              launch_win_hs: -1 here, as for any other epilogue)
+//   eng_spmm2  the two-vector product with its write mask
+//   eng_spmm4  stop.word is column 0's, column 1's follows it (word + 2): each two-vector launch skips by its own column's word, the
+//              one four-vector launch only when both columns stopped before stop.k
 int eng_spmv(prcg_t* h, hipStream_t st, int which, const double* x, double* y, SpmvEpilogue epi, const double* ep_r,
-             const double* ep_d, double* ep_st, double* partials);
-int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask);
+             const double* ep_d, double* ep_st, double* partials, const StopAt& stop = StopAt{});
+int eng_spmm2(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const StopAt& stop = StopAt{});
 bool spmm4_one_launch(const prcg_t* h);
-int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1);
-// ... the product of iteration k of a pipelined two-RHS session with thresholds: the stop forms of the same launches (ProductStop,
-// prcg_kernels.h) -- each two-vector launch skips by its own column's word, the one four-vector launch only when both columns stopped before k
-int eng_spmm4_stop(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1, int* words, int k);
-// ... and the two-vector product of iteration stop.k of a single session that stops (prcg_set_stop_block_jacobi), with its write mask
-int eng_spmm2_stop(prcg_t* h, hipStream_t st, int which, const double* rs, double* wu, int mask, const ProductStop& stop);
-// ... and y = A x with the partials of x.y (kEpiDotXY) of iteration stop.k of a Hestenes-Stiefel session that stops (prcg_set_stop_hs) on
-// sliced rows or CSR-adaptive tiles (a window operator runs launch_win_hs: -1 here)
-int eng_spmv_dot_stop(prcg_t* h, hipStream_t st, int which, const double* x, double* y, double* partials, const ProductStop& stop);
+int eng_spmm4(prcg_t* h, hipStream_t st, int which, const double* src0, const double* src1, double* dst0, double* dst1,
+              const StopAt& stop = StopAt{});
 int eng_fused(prcg_t* h, hipStream_t st, const FusedState& f, int which = 0);
 void note_partials_launch(prcg_t* h, int grid);
 int exchange(prcg_t* h, double* vec_ext, int nc, hipStream_t st);
@@ -432,9 +437,16 @@ __attribute__((visibility("hidden")))
 int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t hist_mask, const double* inv_diag, bool have_xtrue,
                  const Lead* lead, size_t count, int rows_per_iteration);
 
+// ... and so is every stop request consulted and every stop word armed.  "A request of kind K is set: does this begin path serve
+// it?" -- the requests in the order of StopKind, the first unserved one refuses in the name of the entry (who); a path consults only
+// the kinds it always did (the multi-RHS entries pass prcg_set_stop's by, prcg_solve_begin passes prcg_set_stop_rhs's by)
+enum BeginPath { kBeginSingle, kBeginMulti, kBeginMultiPipe };      // (kBeginMulti: prcg_solve_begin_multi and _multi_block_jacobi)
+int refuse_unserved_stops(prcg_t* h, const char* who, BeginPath path, int variant = -1, const double* inv_diag = nullptr);
+// the session just opened stops by the handle's request of `kind`: its thresholds copied, its words armed to "running" on the
+// compute stream (before the first deciding launch is enqueued)
+int arm_stop(prcg_t* h, StopKind kind);
+
 // ---- prcg_multi.cpp: iteration k of the open session with two or four right-hand sides (Session::rhs2) ----
 int iterate_multi(prcg_t* h, int k);
-// ... and what prcg_sync does for a session whose columns stop at their own thresholds (Session::stop_rhs): read the stop words
-int resolve_stops_rhs(prcg_t* h);
 
 }  // namespace prcg

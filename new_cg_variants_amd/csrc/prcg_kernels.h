@@ -154,6 +154,21 @@ constexpr bool epi_product_stop(int e) { return e == kEpiNoneStop || e == kEpiDo
 // rows or CSR-adaptive tiles, by the same head: the product of the stop iteration belongs to its state, so the launch returns only
 // if the session stopped BEFORE k; then no partial row is written either (the reduction that would sum them returns as well).
 struct ProductStop { int* word; int k; };
+// How iteration k of a session stops, as the HOST hands it from the session (Session::stop_at, prcg_handle.h) to a launcher: the
+// threshold on r.r, the stop word ({iteration, status}: SmallStop's layout and rule, below) and the iteration.  A null word is "no
+// threshold": every launcher that takes a StopAt takes it last, defaulted to none, launches with none the kernels it launches for a
+// session without a threshold, and with one the stop kernel of its own (so that a session without a threshold launches what it always
+// did).  The kernels receive what they always did: SmallStop{thr, word} where a launch DECIDES, ProductStop{word, k} where it only
+// skips, or the bare word.
+struct SmallStop;
+struct StopAt {
+    double thr = 0.0; int* word = nullptr; int k = 0;
+    explicit operator bool() const { return word != nullptr; }
+    SmallStop decides() const;
+    ProductStop skips() const { return ProductStop{word, k}; }
+};
+// what a plain product launch hands its kernel: an empty FusedPrev, with a stop carrying ProductStop in word / word_k
+inline FusedPrev product_prev(const StopAt& stop) { FusedPrev fz{}; fz.word = stop.word; fz.word_k = stop.k; return fz; }
 constexpr bool epi_pr_one(int e) { return e == kEpiPROne || e == kEpiPROneJ || e == kEpiPROneQ; }
 constexpr bool epi_cg_w(int e) { return e == kEpiCGW || e == kEpiCGWJ; }
 constexpr bool epi_gv_w(int e) { return e == kEpiGVW || e == kEpiGVWJ; }
@@ -193,18 +208,14 @@ struct CsrDev {
 int launch_spmv(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
                 const double* x, double* y, SpmvEpilogue epi,
                 const double* ep_r, const double* ep_d, double* ep_st,
-                double* partials, TileKnobs kn = TileKnobs{});
-// y = A x with partial[0] += x_i * y_i (kEpiDotXY) of a Hestenes-Stiefel session that stops (ProductStop, kEpiDotXYStop): the same
-// product and the same partial rows, or nothing at all
-int launch_spmv_dot_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps, const double* x, double* y,
-                         double* partials, const ProductStop& stop, TileKnobs kn = TileKnobs{});
+                double* partials, TileKnobs kn = TileKnobs{}, const StopAt& stop = StopAt{});
+// (stop: kEpiDotXY only, -1 for any other epilogue -- y = A x with partial[0] += x_i * y_i of a Hestenes-Stiefel session that stops
+//  (ProductStop, kEpiDotXYStop): the same product and the same partial rows, or nothing at all)
 
 // [w u] = A [r s] on interleaved pairs.  write_mask: 1 = first, 2 = second, 3 = both.
 int launch_spmm2(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
-                 const double* rs, double* wu, int write_mask, TileKnobs kn = TileKnobs{});
-// ... of a session whose columns stop (ProductStop): the same product, or nothing at all
-int launch_spmm2_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
-                      const double* rs, double* wu, int write_mask, const ProductStop& stop, TileKnobs kn = TileKnobs{});
+                 const double* rs, double* wu, int write_mask, TileKnobs kn = TileKnobs{}, const StopAt& stop = StopAt{});
+// (stop: the product of a session that stops (ProductStop, kEpiNoneStop): the same product, or nothing at all)
 
 // One launch per iteration of pipe_pr_cg / pipe_pr_m_cg on ONE GPU: [w u] = A [r s] with the
 // vector update of the following iteration applied to each row as soon as its (w_i,u_i)
@@ -241,9 +252,7 @@ struct WinDev {
 int launch_win_spmv(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* x, double* y,
                     SpmvEpilogue epi, const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu);
 int launch_win_spmm2(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
-                     int write_mask, int per_cu);
-int launch_win_spmm2_stop(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
-                          int write_mask, const ProductStop& stop, int per_cu);      // (ProductStop: the same product, or nothing at all)
+                     int write_mask, int per_cu, const StopAt& stop = StopAt{});      // (stop: as launch_spmm2)
 int launch_win_pipe_fused(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const FusedState& f,
                           int per_cu);
 // waves per workgroup the one-launch pipelined iteration WOULD take (prcg_debug_layout before any launch of a session; after
@@ -324,20 +333,16 @@ struct SellDev {
     int window;               // ... and the most granules a slice has (<= 64)
 };
 int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, SpmvEpilogue epi,
-                     const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu);
-int launch_sell_spmv_dot_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, double* partials,
-                              const ProductStop& stop, int per_cu);      // (as launch_spmv_dot_stop)
+                     const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu,
+                     const StopAt& stop = StopAt{});      // (stop: as launch_spmv)
 int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
-                      int per_cu);
+                      int per_cu, const StopAt& stop = StopAt{});      // (stop: as launch_spmm2)
 // [dst0 | dst1] = A [src0 | src1] for two pair arrays in ONE walk of the operator (four right-hand sides in one session): sources
 // (n + g) x 2 with the spare entries of every product source, destinations n x 2; per column the bits of launch_sell_spmm2
+// (stop: of a session whose columns stop (ProductStop): the same products, or nothing at all; stop.word is column 0's, the launch
+//  reads column 1's behind it)
 int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
-                      double* dst0, double* dst1, int per_cu);
-// ... of a session whose columns stop (ProductStop): the same products, or nothing at all; the four-vector launch reads both words
-int launch_sell_spmm2_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
-                           const ProductStop& stop, int per_cu);
-int launch_sell_spmm4_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
-                           double* dst0, double* dst1, const ProductStop& stop, int per_cu);
+                      double* dst0, double* dst1, int per_cu, const StopAt& stop = StopAt{});
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu);
 // New values on an unchanged pattern (prcg_update_values): sval, the re-laid value array A.val points to, rewritten from val_csr, the
 // nnz values in the caller's CSR order -- one wave per slice, every position of a slice written (no nonzero: 0), so that sval holds
@@ -365,9 +370,8 @@ size_t small_lds_bytes(int n, int nnz, int mode, int prec = kSmallPrecNone);
 bool small_fits(int64_t n, int64_t nnz, int max_row_len, int* mode, int prec = kSmallPrecNone);
 // The single sessions.  The dynamic-LDS attribute of every kernel of the family is set, and its result checked, on first use on
 // each device: a launch fails (-1) where it could not be set.
-// stop (or null; SmallStop below, declared here for the launcher): the single session stopped at a residual threshold -- the
-// STOP form of the batch's body on the session's own word
-struct SmallStop;
+// stop (or null; SmallStop below): the single session stopped at a residual threshold -- the STOP form of the batch's body on the
+// session's own word
 int launch_small_pipe_pr(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop = nullptr);
 int launch_small_hs(hipStream_t st, const SmallArgs& a, int mode, const SmallStop* stop = nullptr);      // Hestenes-Stiefel, same storage
 // ---- a batch of small systems: the same solver, one workgroup per system, blockIdx.x selects the system (prcg_batch.cpp) ----
@@ -396,6 +400,7 @@ struct SmallBlocks { double* ts; const int2* tab; const double* inv; };
 // rows are not written, and a later launch returns at once for it and stores nothing.  A system that never stops carries the
 // bits of the launch without `stop`.
 struct SmallStop { double thr; int* word; };
+inline SmallStop StopAt::decides() const { return SmallStop{thr, word}; }
 // one launch of a batch: the arrays above (device memory) and where the session stands
 struct SmallBatchArgs { const SmallArgs* desc; const SmallJacobi* jac; const SmallStop* stop; int k0, iters, meurant; };
 // lds: the largest small_lds_bytes(n, nnz, mode, prec) among the launch's systems -- each workgroup carves it by its own
@@ -425,14 +430,13 @@ struct PipeUpdateArgs {
     int meurant;      // nu prediction flavour
     int recompute_w;  // 'pr' flavours: w is overwritten by the following SpMM
 };
-int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a);
-// Update k of a STORED-TILDE session that stops at a threshold (prcg_set_stop_block_jacobi): the flavour with u~ and w~ as vectors
-// only (a.ut set, a.d null; anything else: -1), a kernel of its own so that a session without a threshold launches what it always
-// did.  word: the session's stop word ({iteration it stopped at or -1, status}: SmallStop's layout, written by
-// launch_reduce_final_stop on the same stream).  If 0 <= word[0] < k the session stopped before this update and the launch returns
-// at once: no load, no store, no coefficient row, no partial row, no barrier met.  Otherwise launch_pipe_update's statements in
-// their order: the same bits in every vector and the same partial rows.  Returns the grid, like launch_pipe_update.
-int launch_pipe_update_stop(hipStream_t st, const PipeUpdateArgs& a, const int* word, int k);
+// stop: update stop.k of a STORED-TILDE session that stops at a threshold (prcg_set_stop_block_jacobi): the flavour with u~ and w~ as
+// vectors only (a.ut set, a.d null; anything else: -1), a kernel of its own.  stop.word: the session's stop word ({iteration it
+// stopped at or -1, status}: SmallStop's layout, written by launch_reduce_final's stop form on the same stream).  If 0 <= word[0] <
+// stop.k the session stopped before this update and the launch returns at once: no load, no store, no coefficient row, no partial
+// row, no barrier met.  Otherwise the statements of the launch without a stop in their order: the same bits in every vector and the
+// same partial rows.  Returns the grid either way.
+int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a, const StopAt& stop = StopAt{});
 // the four (five) inner products of the current pipe state, no update (initialisation)
 int launch_pipe_dots(hipStream_t st, const PipeUpdateArgs& a);
 
@@ -444,25 +448,23 @@ struct HsArgs {
 // prev_mu / nprev: mu = <p,s> of iteration k-1 still as block partials (slot 0) of the product launch -- every
 // block sums them in the same fixed order and block 0 stores mu to dots_prev_w[0]; nprev == 0: a.dots_prev[0]
 int launch_hs_update_xr(hipStream_t st, const HsArgs& a, const double* prev_mu = nullptr, int nprev = 0,
-                        double* dots_prev_w = nullptr);   // x,r,(rt); partial nu (slot 3), rr (slot 4)
+                        double* dots_prev_w = nullptr, const StopAt& stop = StopAt{});   // x,r,(rt); partial nu (slot 3), rr (slot 4)
 // prev_nu / nprev: nu_k, rr_k still as block partials (slots 3, 4) of launch_hs_update_xr; block 0 stores them
 // to dots_cur_w[3], [4]
 int launch_hs_update_p(hipStream_t st, const HsArgs& a, const double* prev_nu = nullptr, int nprev = 0,
-                       double* dots_cur_w = nullptr);    // p = z + beta p
+                       double* dots_cur_w = nullptr, const StopAt& stop = StopAt{});    // p = z + beta p
 int launch_hs_init_dots(hipStream_t st, const HsArgs& a);   // nu, rr of the initial state
-// The launches of iteration k of a Hestenes-Stiefel session that stops at a threshold (prcg_set_stop_hs), kernels of their own so
-// that a session without a threshold launches what it always did.  stop.word: the session's stop word, SmallStop's layout and rule.
-//   update_xr (launch A of iteration k): returns at once if the session stopped before k - 1.  Otherwise mu_k1 as above (workgroup 0
-//     stores it: it belongs to the state of a stop), then the rule on row k - 1 = {mu_k1, nu_k1, rr_k1}, nu and rr read from
-//     a.dots_prev, where the launch before stored them.  On a verdict thread 0 of workgroup 0 records {k - 1, status} and every
-//     workgroup returns: no coefficient, no vector, no partial row of iteration k is written.  No verdict: the bits of launch_hs_update_xr.
-//   update_p (CSR-adaptive tiles and sliced rows): returns at once if the session stopped before k; else the bits of launch_hs_update_p.
-//   launch_reduce_hs_mu_stop (the reduction that ends a prcg_iterate call, and the session's start with k = 0): returns at once if the
-//     word is set (the partials are stale); else row[0] = mu_k summed as launch_reduce_final sums one slot, then the rule on
-//     {mu_k, row[3], row[4]} and the record {k, status}.
-int launch_hs_update_xr_stop(hipStream_t st, const HsArgs& a, const double* prev_mu, int nprev, double* dots_prev_w, const SmallStop& stop, int k);
-int launch_hs_update_p_stop(hipStream_t st, const HsArgs& a, const double* prev_nu, int nprev, double* dots_cur_w, const int* word, int k);
-void launch_reduce_hs_mu_stop(hipStream_t st, const double* partials, int nparts, double* row, const SmallStop& stop, int k);
+// stop: the launches of iteration k = stop.k of a Hestenes-Stiefel session that stops at a threshold (prcg_set_stop_hs), kernels of
+// their own.  stop.word: the session's stop word, SmallStop's layout and rule.
+//   update_xr (launch A of iteration k; k < 1: -1): returns at once if the session stopped before k - 1.  Otherwise mu_k1 as above
+//     (workgroup 0 stores it: it belongs to the state of a stop), then the rule on row k - 1 = {mu_k1, nu_k1, rr_k1}, nu and rr read
+//     from a.dots_prev, where the launch before stored them.  On a verdict thread 0 of workgroup 0 records {k - 1, status} and every
+//     workgroup returns: no coefficient, no vector, no partial row of iteration k is written.  No verdict: the bits without a stop.
+//   update_p (CSR-adaptive tiles and sliced rows): returns at once if the session stopped before k; else the bits without a stop.
+//   launch_reduce_hs_mu (the reduction that ends a prcg_iterate call, and the session's start with k = 0): row[PRCG_S_MU] = mu_k,
+//     one slot summed by launch_reduce_final.  With a stop it also DECIDES: it returns at once if the word is set (the partials
+//     are stale); else the same sum, then the rule on {mu_k, row[3], row[4]} and the record {k, status}.
+void launch_reduce_hs_mu(hipStream_t st, const double* partials, int nparts, double* row, const StopAt& stop = StopAt{});
 
 // ---- Hestenes-Stiefel, TWO right-hand sides in one session (prcg_rhs2.hip; prcg_solve_begin_multi) ----
 // x, r, rt, p, s: interleaved n x 2 arrays, row i = (column 0, column 1) -- p and s are directly the input and output of the
@@ -516,14 +518,13 @@ struct Pipe2Args {
     const double* dots_prev; double* coef_out; double* part0; double* part1;
     int meurant;
 };
-int launch_pipe2_update(hipStream_t st, const Pipe2Args& a);   // x, p, r, s, (r~, s~) of both columns; partials mu .. rr (slots 0..4) of part[c]
+// stop: the update of a session whose columns stop at their own thresholds (prcg_set_stop_rhs).  stop.word: four ints in device
+// memory, column c's stop word at word + 2 c ({iteration it stopped at or -1, status}: SmallStop's layout; written by
+// launch_reduce_final's stop form).  A column whose word names an iteration is FROZEN: the launch loads and stores nothing of it --
+// no vector, no coefficient row, no partial row (its reduction returns at once as well).  Both frozen: the launch returns in its
+// prologue.  The other column carries the bits of the launch without a stop: the same expressions, accumulation order and tree.
+int launch_pipe2_update(hipStream_t st, const Pipe2Args& a, const StopAt& stop = StopAt{});   // x, p, r, s, (r~, s~) of both columns; partials mu .. rr (slots 0..4) of part[c]
 int launch_pipe2_dots(hipStream_t st, const Pipe2Args& a);     // the five sums of the state as it stands: no update (initialisation)
-// The update of a session whose columns stop at their own thresholds (prcg_set_stop_rhs).  words: four ints in device memory, column
-// c's stop word at words + 2 c ({iteration it stopped at or -1, status}: SmallStop's layout; written by launch_reduce_final_stop).
-// A column whose word names an iteration is FROZEN: the launch loads and stores nothing of it -- no vector, no coefficient row,
-// no partial row (its reduction returns at once as well).  Both frozen: the launch returns in its prologue.  The other column
-// carries the bits of launch_pipe2_update: the same expressions, the same accumulation order, the same tree.
-int launch_pipe2_update_stop(hipStream_t st, const Pipe2Args& a, const int* words);
 
 struct PrArgs {   // non-pipelined predict-and-recompute (pr_pcg / m_pcg)
     int64_t n;
@@ -545,20 +546,19 @@ struct CgArgs {   // Chronopoulos-Gear / Ghysels-Vanroose vector kernels
 int launch_cg_update_ps(hipStream_t st, const CgArgs& a, const double* prev = nullptr, int nprev = 0);   // p,s,(s~),(u); mu by recurrence
 int launch_gv_update1(hipStream_t st, const CgArgs& a, bool dots_only);   // x,r,(r~),w,(w~); partials eta(1), nu(3), rr(4)
 
-// out[dst_first..+count) = fixed-order sum over blocks b of partials[b][src_first..+count)
-void launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
-                         int src_first, int dst_first, int count);
+// out[dst_first..+count) = fixed-order sum over blocks b of partials[b][src_first..+count).  0 / -1.
+// stop (sessions with a threshold; (src_first, dst_first, count) = (0, 0, 5) only, anything else: -1 and nothing launched): the same
+// kernel code, the same tree, the same bits in out[0..5) -- then the rule of SmallStop on {mu, nu, rr} = out[0], out[3], out[4], which
+// are the scalars of iteration stop.k: a stop is recorded as {stop.k, status} in stop.word.  If the word is already set the launch
+// returns at once and writes nothing: its partials belong to a launch that returned early.
+int launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
+                        int src_first, int dst_first, int count, const StopAt& stop = StopAt{});
 // up to kMaxReduceJobs such reductions in ONE launch, one workgroup each: job j's result carries the bits of launch_reduce_final
 // with its arguments (the same tree by the same code)
 constexpr int kMaxReduceJobs = 4;
 struct ReduceJob { const double* partials; int nparts; double* out; int src_first, dst_first, count; };
 struct ReduceJobs { ReduceJob job[kMaxReduceJobs]; };
 void launch_reduce_final_jobs(hipStream_t st, const ReduceJobs& jobs, int njobs);
-// The stop form (single sessions with a threshold: FusedPrev::word): out[0..5) = the five sums of slots 0..5 -- the same kernel
-// code, the same tree, the same bits -- then the rule of SmallStop on {mu, nu, rr} = out[0], out[3], out[4], which are the scalars
-// of iteration k: a stop is recorded as {k, status} in stop.word.  If the word is already set the launch returns at once and
-// writes nothing: its partials belong to a launch that returned early.
-void launch_reduce_final_stop(hipStream_t st, const double* partials, int nparts, double* out, const SmallStop& stop, int k);
 
 // ---- small utility kernels (strided so they can address one half of a pair array) ----
 void launch_copy(hipStream_t st, double* dst, int ds, const double* src, int ss, int64_t n);
@@ -579,21 +579,19 @@ int64_t block_jacobi_unlay(int64_t n, int bs, const double* laid, double* inv_bl
 int launch_block_jacobi_build(hipStream_t st, double* blocks, int64_t n, int bs, const int* indptr, const int* col, const double* val,
                               long long* first_bad);
 // both columns of the interleaved [w u] array in one launch: wt = M^-1 w (mask bit 0), ut = M^-1 u (mask bit 1)
-int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask);
+// (stop: the pair launch of iteration stop.k of a session that stops at a threshold (ProductStop; prcg_set_stop_block_jacobi), a kernel
+//  of its own: the pair launch belongs to the state of its iteration, so it runs unless the session stopped BEFORE stop.k
+//  (0 <= stop.word[0] < stop.k: returns at once, nothing loaded or stored); otherwise the bits of the launch without a stop)
+int launch_block_jacobi_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask,
+                             const StopAt& stop = StopAt{});
 // ---- the same with VARIABLE block sizes (prcg_set_block_jacobi_var / prcg_build_block_jacobi_var): the partition reaches the
 // kernels as prcg_bjvar.h's tables -- `tiles` ntiles x 4 int64 (first row, first line, first block, largest size), `code` and
 // `bidx` one byte per lane, 256 per tile -- and `blocks` is that header's layout (BjVarPlan::doubles()).  0 / -1.
 int launch_block_jacobi_var(hipStream_t st, double* dst, int dstride, const double* src, int sstride, int64_t ntiles, const long long* tiles,
                             const unsigned char* code, const double* blocks);
 int launch_block_jacobi_var_pair(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
-                                 const unsigned char* code, const double* blocks, int mask);
-// ... the pair launches of iteration stop.k of a session that stops at a threshold (ProductStop; prcg_set_stop_block_jacobi), kernels
-// of their own: the pair launch belongs to the state of its iteration, so it runs unless the session stopped BEFORE stop.k
-// (0 <= stop.word[0] < stop.k: returns at once, nothing loaded or stored); otherwise the bits of the launches above.  0 / -1.
-int launch_block_jacobi_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t n, int bs, const double* blocks, int mask,
-                                  const ProductStop& stop);
-int launch_block_jacobi_var_pair_stop(hipStream_t st, double* wt, double* ut, const double* wu, int64_t ntiles, const long long* tiles,
-                                      const unsigned char* code, const double* blocks, int mask, const ProductStop& stop);
+                                 const unsigned char* code, const double* blocks, int mask,
+                                 const StopAt& stop = StopAt{});      // (stop: as launch_block_jacobi_pair)
 // ---- M^-1 on an interleaved n x 2 array with the inner products that need the result, in ONE launch (block-Jacobi sessions with
 // two or four right-hand sides: prcg_solve_begin_multi_block_jacobi).  v: the source pairs (NU: r; PR: s), z: the result (r~ / s~);
 // p, r: read by PR only.  One partial row per TILE (a tile: 256 - 256 % bs rows, or a tile of the partition's table): part0 / part1

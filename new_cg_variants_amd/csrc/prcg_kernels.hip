@@ -413,7 +413,7 @@ __global__ __launch_bounds__(kBlock) void k_pipe_update(PipeUpdateArgs a, int tr
     block_reduce_store<5>(acc, a.partials, 0);
 }
 
-// The stop form of the STORED-TILDE flavour (launch_pipe_update_stop, prcg_kernels.h): update k of a block-Jacobi session begun with
+// The stop form of the STORED-TILDE flavour (launch_pipe_update with a stop, prcg_kernels.h): update k of a block-Jacobi session begun with
 // a threshold (prcg_set_stop_block_jacobi).  A kernel of its own: k_pipe_update above stays as it is, instruction for instruction.
 // The word is tested first: the reduction that closed an earlier iteration wrote it (k_reduce_final_stop), so it was complete before
 // this launch began, every wave reads the same value through readfirstlane, and a workgroup leaves as a whole on a scalar branch --
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(kBlock) void k_hs_update_p(HsArgs a, int trips, con
     }
 }
 
-// The stop forms (launch_hs_update_xr_stop / launch_hs_update_p_stop, prcg_kernels.h): iteration k of a Hestenes-Stiefel session begun with
+// The stop forms (launch_hs_update_xr / launch_hs_update_p with a stop, prcg_kernels.h): iteration k of a Hestenes-Stiefel session begun with
 // a threshold (prcg_set_stop_hs).  Kernels of their own: the two above stay as they are, instruction for instruction.  Behind their
 // heads they are the statements of k_hs_update_xr<PREC, false> and k_hs_update_p in their order -- the same expressions, the same
 // element order, the same accumulators and the same tree: the bits of those kernels in every vector and every partial row.
@@ -882,7 +882,7 @@ __global__ __launch_bounds__(kFinalThreads) void k_reduce_final_jobs(ReduceJobs 
     reduce_final_wave_sums(acc, red);
     if ((int)threadIdx.x < j.count) j.out[j.dst_first + threadIdx.x] = reduce_final_total(red, threadIdx.x);
 }
-// The stop form (launch_reduce_final_stop, prcg_kernels.h): the five sums of a pipelined iteration by the code above, then the
+// The stop form (launch_reduce_final with a stop, prcg_kernels.h): the five sums of a pipelined iteration by the code above, then the
 // rule on them.  The word is tested first: it was complete before this launch began (only a launch's end or this kernel's thread 0
 // writes it), so all four waves read the same value and leave together, before the barrier.  Thread 0 then adds the wave sums of
 // mu, nu, rr in the order threads 0, 3, 4 add them: the bits they store, and the bits the next launch's prologue would have had.
@@ -899,7 +899,7 @@ __global__ __launch_bounds__(kFinalThreads) void k_reduce_final_stop(
     }
 }
 
-// The stop form of the ONE-slot reduction that closes a Hestenes-Stiefel iteration (launch_reduce_hs_mu_stop, prcg_kernels.h): mu_k
+// The stop form of the ONE-slot reduction that closes a Hestenes-Stiefel iteration (launch_reduce_hs_mu with a stop, prcg_kernels.h): mu_k
 // from the product launch's partials by the code of k_reduce_final -- the same tree, the same bits --, stored to row[0]; nu_k and
 // rr_k are read from the row, where the launch before stored them (kernel boundary); then the rule.  The word is tested first, as in
 // k_reduce_final_stop: all four waves read the same value and leave together, before the barrier.
@@ -1196,9 +1196,13 @@ int launch_tiles_steps(int steps, hipStream_t st, const CsrDev& A, const Tile* t
 
 int launch_spmv(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
                 const double* x, double* y, SpmvEpilogue epi,
-                const double* ep_r, const double* ep_d, double* ep_st, double* partials, TileKnobs kn)
+                const double* ep_r, const double* ep_d, double* ep_st, double* partials, TileKnobs kn, const StopAt& stop)
 {
+    if (stop && epi != kEpiDotXY) return -1;
     if (ntiles <= 0) return 0;
+    if (stop)
+        return launch_tiles_steps<1, kEpiDotXYStop>(steps, st, A, tiles, ntiles, x, y, 3, nullptr, nullptr, nullptr, partials, kn, nullptr,
+                                                    product_prev(stop));
     switch (epi) {
     case kEpiNone: return launch_tiles_steps<1, kEpiNone>(steps, st, A, tiles, ntiles, x, y, 3, ep_r, ep_d, ep_st, partials, kn);
     case kEpiDotXY: return launch_tiles_steps<1, kEpiDotXY>(steps, st, A, tiles, ntiles, x, y, 3, ep_r, ep_d, ep_st, partials, kn);
@@ -1209,31 +1213,15 @@ int launch_spmv(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, 
     return -1;
 }
 
-int launch_spmv_dot_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps, const double* x, double* y,
-                         double* partials, const ProductStop& stop, TileKnobs kn)
-{
-    if (ntiles <= 0) return 0;
-    FusedPrev fz{};
-    fz.word = stop.word; fz.word_k = stop.k;
-    return launch_tiles_steps<1, kEpiDotXYStop>(steps, st, A, tiles, ntiles, x, y, 3, nullptr, nullptr, nullptr, partials, kn, nullptr, fz);
-}
-
 int launch_spmm2(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
-                 const double* rs, double* wu, int write_mask, TileKnobs kn)
+                 const double* rs, double* wu, int write_mask, TileKnobs kn, const StopAt& stop)
 {
     if (ntiles <= 0) return 0;
+    if (stop)
+        return launch_tiles_steps<2, kEpiNoneStop>(steps, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr,
+                                                   nullptr, kn, nullptr, product_prev(stop));
     return launch_tiles_steps<2, kEpiNone>(steps, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr,
                                            nullptr, kn);
-}
-
-int launch_spmm2_stop(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps,
-                      const double* rs, double* wu, int write_mask, const ProductStop& stop, TileKnobs kn)
-{
-    if (ntiles <= 0) return 0;
-    FusedPrev fz{};
-    fz.word = stop.word; fz.word_k = stop.k;
-    return launch_tiles_steps<2, kEpiNoneStop>(steps, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr,
-                                               nullptr, kn, nullptr, fz);
 }
 
 int launch_pipe_fused(hipStream_t st, const CsrDev& A, const Tile* tiles, int ntiles, int steps, const FusedState& f, TileKnobs kn)
@@ -1256,17 +1244,13 @@ int launch_pipe_fused(hipStream_t st, const CsrDev& A, const Tile* tiles, int nt
                                                  f.in_new, f.partials, kn, f.coef_out, fz);
 }
 
-int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a) {
+int launch_pipe_update(hipStream_t st, const PipeUpdateArgs& a, const StopAt& stop) {
+    if (stop && (!a.ut || a.d)) return -1;       // the stop form: the stored-tilde flavour only (u~ and w~ are vectors)
     const Chunking c = chunking(a.n);
     // preconditioned: the inverse diagonal, or u~ / w~ as vectors (host-callback preconditioner)
-    if (a.d || a.ut) hipLaunchKernelGGL((k_pipe_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
-    else             hipLaunchKernelGGL((k_pipe_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
-    return PRCG_LAUNCH_OK() ? c.grid : -1;
-}
-int launch_pipe_update_stop(hipStream_t st, const PipeUpdateArgs& a, const int* word, int k) {
-    if (!a.ut || a.d || !word) return -1;        // the stored-tilde flavour only: u~ and w~ are vectors
-    const Chunking c = chunking(a.n);
-    hipLaunchKernelGGL(k_pipe_update_stop, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, word, k);
+    if (stop)             hipLaunchKernelGGL(k_pipe_update_stop, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, stop.word, stop.k);
+    else if (a.d || a.ut) hipLaunchKernelGGL((k_pipe_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else                  hipLaunchKernelGGL((k_pipe_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 int launch_pipe_dots(hipStream_t st, const PipeUpdateArgs& a) {
@@ -1276,10 +1260,15 @@ int launch_pipe_dots(hipStream_t st, const PipeUpdateArgs& a) {
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 
-int launch_hs_update_xr(hipStream_t st, const HsArgs& a, const double* prev_mu, int nprev, double* dots_prev_w) {
+int launch_hs_update_xr(hipStream_t st, const HsArgs& a, const double* prev_mu, int nprev, double* dots_prev_w, const StopAt& stop) {
+    if (stop && stop.k < 1) return -1;
     const Chunking c = chunking(a.n);
-    if (a.d) hipLaunchKernelGGL((k_hs_update_xr<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w);
-    else     hipLaunchKernelGGL((k_hs_update_xr<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w);
+    if (stop) {
+        if (a.d) hipLaunchKernelGGL((k_hs_update_xr_stop<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w, stop.decides(), stop.k);
+        else     hipLaunchKernelGGL((k_hs_update_xr_stop<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w, stop.decides(), stop.k);
+    }
+    else if (a.d) hipLaunchKernelGGL((k_hs_update_xr<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w);
+    else          hipLaunchKernelGGL((k_hs_update_xr<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 int launch_hs_init_dots(hipStream_t st, const HsArgs& a) {
@@ -1290,27 +1279,15 @@ int launch_hs_init_dots(hipStream_t st, const HsArgs& a) {
     else     hipLaunchKernelGGL((k_hs_update_xr<false, true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, none, 0, nonew);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
-int launch_hs_update_p(hipStream_t st, const HsArgs& a, const double* prev_nu, int nprev, double* dots_cur_w) {
+int launch_hs_update_p(hipStream_t st, const HsArgs& a, const double* prev_nu, int nprev, double* dots_cur_w, const StopAt& stop) {
     const Chunking c = chunking(a.n);
-    hipLaunchKernelGGL(k_hs_update_p, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_nu, nprev, dots_cur_w);
+    if (stop) hipLaunchKernelGGL(k_hs_update_p_stop, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_nu, nprev, dots_cur_w, stop.word, stop.k);
+    else      hipLaunchKernelGGL(k_hs_update_p, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_nu, nprev, dots_cur_w);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
-
-int launch_hs_update_xr_stop(hipStream_t st, const HsArgs& a, const double* prev_mu, int nprev, double* dots_prev_w, const SmallStop& stop, int k) {
-    if (!stop.word || k < 1) return -1;
-    const Chunking c = chunking(a.n);
-    if (a.d) hipLaunchKernelGGL((k_hs_update_xr_stop<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w, stop, k);
-    else     hipLaunchKernelGGL((k_hs_update_xr_stop<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_mu, nprev, dots_prev_w, stop, k);
-    return PRCG_LAUNCH_OK() ? c.grid : -1;
-}
-int launch_hs_update_p_stop(hipStream_t st, const HsArgs& a, const double* prev_nu, int nprev, double* dots_cur_w, const int* word, int k) {
-    if (!word) return -1;
-    const Chunking c = chunking(a.n);
-    hipLaunchKernelGGL(k_hs_update_p_stop, dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, prev_nu, nprev, dots_cur_w, word, k);
-    return PRCG_LAUNCH_OK() ? c.grid : -1;
-}
-void launch_reduce_hs_mu_stop(hipStream_t st, const double* partials, int nparts, double* row, const SmallStop& stop, int k) {
-    hipLaunchKernelGGL(k_reduce_hs_mu_stop, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, row, stop, k);
+void launch_reduce_hs_mu(hipStream_t st, const double* partials, int nparts, double* row, const StopAt& stop) {
+    if (stop) hipLaunchKernelGGL(k_reduce_hs_mu_stop, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, row, stop.decides(), stop.k);
+    else      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, row, 0, 0 /* PRCG_S_MU */, 1);
 }
 
 int launch_pr_update(hipStream_t st, const PrArgs& a) {
@@ -1343,13 +1320,12 @@ int launch_gv_update1(hipStream_t st, const CgArgs& a, bool dots_only) {
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 
-void launch_reduce_final_stop(hipStream_t st, const double* partials, int nparts, double* out, const SmallStop& stop, int k) {
-    hipLaunchKernelGGL(k_reduce_final_stop, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, out, stop, k);
-}
-
-void launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
-                         int src_first, int dst_first, int count) {
-    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, out, src_first, dst_first, count);
+int launch_reduce_final(hipStream_t st, const double* partials, int nparts, double* out,
+                        int src_first, int dst_first, int count, const StopAt& stop) {
+    if (stop && (src_first != 0 || dst_first != 0 || count != 5)) return -1;      // the stop form sums and judges a whole pipelined row
+    if (stop) hipLaunchKernelGGL(k_reduce_final_stop, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, out, stop.decides(), stop.k);
+    else      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(kFinalThreads), 0, st, partials, nparts, out, src_first, dst_first, count);
+    return 0;      // (a launch error is left for the next checked launch to report, as ever)
 }
 
 void launch_reduce_final_jobs(hipStream_t st, const ReduceJobs& jobs, int njobs) {

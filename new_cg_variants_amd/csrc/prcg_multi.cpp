@@ -207,40 +207,34 @@ Pipe2Args pipe2_args(prcg_t* h, int k) {
     a.meurant = meurant(h->variant);
     return a;
 }
-// Each column stopped at its own threshold (prcg_set_stop_rhs; Session::stop_rhs).  Column c's stop word -- {iteration, status},
+// Each column stopped at its own threshold (prcg_set_stop_rhs; Session::stop_kind == kStopRhs).  Column c's stop word -- {iteration, status},
 // {-1, 0} while it runs -- is written by the reduction that sums its row k: the stop form of the final reduction applies the
 // rule of prcg_set_stop to {mu, nu, rr} of that row and, once the word is set, returns at once.  Every later launch reads the
 // words: the update skips a frozen column (no load, no store, no coefficient row, no partial row), the product of iteration k
 // skips a column that stopped BEFORE k (the product of iteration k_c belongs to the state of k_c and has run).  So a column
 // stopped at k_c holds the complete state of k_c, scalar rows 0 .. k_c and coefficient rows 1 .. k_c, and the other column
 // executes what it executes in a session without thresholds.  The host enqueues without knowing; prcg_sync reads the words.
-int* stop_word_rhs(prcg_t* h, int c) { return h->stop_words_rhs.i() + 2 * c; }
 // the five sums of each column from the block partials an update (or dots) launch of `grid` blocks left: rows 2 k, 2 k + 1
-void pipe2_reduce(prcg_t* h, int k, int grid) {
-    if (h->stop_rhs) {
-        launch_reduce_final_stop(h->sc, h->partA.d(), grid, dots_at(h, 2 * k), SmallStop{h->thr_rhs[0], stop_word_rhs(h, 0)}, k);
-        launch_reduce_final_stop(h->sc, h->partB.d(), grid, dots_at(h, 2 * k + 1), SmallStop{h->thr_rhs[1], stop_word_rhs(h, 1)}, k);
-        return;
-    }
-    launch_reduce_final(h->sc, h->partA.d(), grid, dots_at(h, 2 * k), 0, 0, 5);
-    launch_reduce_final(h->sc, h->partB.d(), grid, dots_at(h, 2 * k + 1), 0, 0, 5);
+int pipe2_reduce(prcg_t* h, int k, int grid) {
+    LAUNCHCHK(h, launch_reduce_final(h->sc, h->partA.d(), grid, dots_at(h, 2 * k), 0, 0, 5, h->stop_at(k, 0)));
+    LAUNCHCHK(h, launch_reduce_final(h->sc, h->partB.d(), grid, dots_at(h, 2 * k + 1), 0, 0, 5, h->stop_at(k, 1)));
+    return PRCG_OK;
 }
 // (w_c, u_c) = A (r_c, s_c) of both columns (Jacobi: A (r~_c, s~_c)): one launch on sliced rows, else two two-vector launches.
 // k > 0 in a session with thresholds: the product of iteration k in its stop form (the start-up products, k = 0, are plain)
 int pipe2_product(prcg_t* h, int k = 0) {
     DevBuf* src = h->prec ? h->crst : h->crs;
-    if (h->stop_rhs && k > 0) LAUNCHCHK(h, eng_spmm4_stop(h, h->sc, 0, src[0].d(), src[1].d(), h->cwu[0].d(), h->cwu[1].d(), stop_word_rhs(h, 0), k));
-    else LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, src[0].d(), src[1].d(), h->cwu[0].d(), h->cwu[1].d()));
+    LAUNCHCHK(h, eng_spmm4(h, h->sc, 0, src[0].d(), src[1].d(), h->cwu[0].d(), h->cwu[1].d(), k > 0 ? h->stop_at(k) : StopAt{}));
     return PRCG_OK;
 }
 int iterate_pipe2(prcg_t* h, int k) {
     const Pipe2Args a = pipe2_args(h, k);
     bool on = false;
     prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-    const int grid = h->stop_rhs ? launch_pipe2_update_stop(h->sc, a, stop_word_rhs(h, 0)) : launch_pipe2_update(h->sc, a);
+    const int grid = launch_pipe2_update(h->sc, a, h->stop_at(k));
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_upd, h->n_ev_upd, on);
-    pipe2_reduce(h, k, grid);
+    if (const int rc = pipe2_reduce(h, k, grid)) return rc;
     prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
     const int rc = pipe2_product(h, k);
     if (rc) return rc;
@@ -352,32 +346,7 @@ int start_pairs(prcg_t* h, const char* who, int groups, const double* const* b, 
 
 }  // namespace
 
-// A session with per-column thresholds, every stream idle (prcg_sync): which columns has the device stopped?  The words tell.  The
-// two-kernel schedule has no buffer flip to undo and nothing pending: a newly stopped column only records where and why; once
-// BOTH have stopped the iteration count goes back to the later stop (the launches behind it returned at once) and prcg_iterate
-// becomes a no-op.  Idempotent.
-int prcg::resolve_stops_rhs(prcg_t* h) {
-    if (!h->in_session || !h->stop_rhs || h->all_stopped_rhs()) return PRCG_OK;
-    int w[4] = {-1, 0, -1, 0};
-    HIPCHK(h, hipMemcpy(w, h->stop_words_rhs.p, sizeof w, hipMemcpyDeviceToHost));
-    for (int c = 0; c < 2; ++c)
-        if (h->stopped_k_rhs[c] < 0 && w[2 * c] >= 0) { h->stopped_k_rhs[c] = w[2 * c]; h->stop_status_rhs[c] = w[2 * c + 1]; }
-    if (h->all_stopped_rhs()) h->k = h->stopped_k_rhs[0] > h->stopped_k_rhs[1] ? h->stopped_k_rhs[0] : h->stopped_k_rhs[1];
-    return PRCG_OK;
-}
-
 int prcg::iterate_multi(prcg_t* h, int k) { return h->pipe2 ? iterate_pipe2(h, k) : pr2(h) ? iterate_pr2(h, k) : iterate_hs2(h, k); }
-
-// what the sessions that cannot stop say while per-column thresholds are set: nothing falls back to them
-#define STOP_RHS_SERVED "per-column stop thresholds are set (prcg_set_stop_rhs), which serve the pipelined two-RHS session only "  \
-                        "(prcg_solve_begin_multi_pipe: PRCG_PIPE_PR, PRCG_PIPE_PR_M, Jacobi or none); this session cannot stop -- "  \
-                        "prcg_set_stop_rhs(h, 0, NULL) clears the thresholds"
-// ... and so is the threshold of block-Jacobi single sessions: no multi-RHS session is begun while it is set
-#define STOP_BJ_SERVED "a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves pipelined SINGLE sessions with point-block "  \
-                       "Jacobi only (prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_block_jacobi(h, NULL) clears the threshold"
-// ... and the threshold of Hestenes-Stiefel single sessions (the Hestenes-Stiefel multi-RHS sessions do not stop: a follow-up)
-#define STOP_HS_SERVED "a Hestenes-Stiefel stop threshold is set (prcg_set_stop_hs), which serves SINGLE PRCG_HS sessions only "  \
-                       "(prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_hs(h, NULL) clears the threshold"
 
 extern "C" {
 
@@ -390,9 +359,7 @@ int prcg_solve_begin_multi(prcg_t* h, int variant, int nrhs, const double* const
     CHECK(h, variant == PRCG_HS || is_pr(variant), "prcg_solve_begin_multi: variant %d: the two-RHS session serves PRCG_HS (hs_cg / hs_pcg), "
                                                    "PRCG_PR (pr_cg / pr_pcg) and PRCG_M (m_cg / m_pcg) only", variant);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi", hist_mask)) return rc;
-    CHECK(h, !h->stop_rhs_set, "prcg_solve_begin_multi: " STOP_RHS_SERVED);
-    CHECK(h, !h->stop_bj_set, "prcg_solve_begin_multi: " STOP_BJ_SERVED);
-    CHECK(h, !h->stop_hs_set, "prcg_solve_begin_multi: " STOP_HS_SERVED);
+    if (int rc = refuse_unserved_stops(h, "prcg_solve_begin_multi", kBeginMulti)) return rc;
     CHECK(h, have_columns(b, x0, nrhs), "prcg_solve_begin_multi: null b or x0");
     if (int rc = open_pairs(h, "prcg_solve_begin_multi", variant, nrhs / 2, max_iter, hist_mask, inv_diag, 0)) return rc;
     return start_pairs(h, "prcg_solve_begin_multi", nrhs / 2, b, x0, 0);
@@ -409,8 +376,7 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     CHECK(h, nrhs == 2, "prcg_solve_begin_multi_pipe: nrhs = %d: the pipelined session serves exactly 2 right-hand sides (its product is the "
                         "four-vector one; an eight-vector product does not exist)", nrhs);
     if (int rc = refuse_unserved(h, "prcg_solve_begin_multi_pipe", hist_mask)) return rc;
-    CHECK(h, !h->stop_bj_set, "prcg_solve_begin_multi_pipe: " STOP_BJ_SERVED);
-    CHECK(h, !h->stop_hs_set, "prcg_solve_begin_multi_pipe: " STOP_HS_SERVED);
+    if (int rc = refuse_unserved_stops(h, "prcg_solve_begin_multi_pipe", kBeginMultiPipe)) return rc;
     CHECK(h, have_columns(b, x0, 2), "prcg_solve_begin_multi_pipe: null b or x0");
     const int64_t n = h->n, ne = h->n + kGatherPad;
     const size_t D = sizeof(double);
@@ -425,14 +391,8 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     h->groups = 1;
     h->pipe2 = true;
     h->spmm4 = spmm4_one_launch(h);
-    if (h->stop_rhs_set) {
-        // per-column thresholds (prcg_set_stop_rhs): copied now, the words armed to "running" before the first reduction is enqueued
-        static const int kRunning[4] = {-1, 0, -1, 0};
-        if (!h->stop_words_rhs.p) HIPCHK(h, h->stop_words_rhs.alloc(sizeof kRunning));
-        HIPCHK(h, hipMemcpyAsync(h->stop_words_rhs.p, kRunning, sizeof kRunning, hipMemcpyHostToDevice, h->sc));
-        h->stop_rhs = true;
-        h->thr_rhs[0] = h->stop_rhs_thr[0]; h->thr_rhs[1] = h->stop_rhs_thr[1];
-    }
+    // per-column thresholds (prcg_set_stop_rhs): copied now, the words armed to "running" before the first reduction is enqueued
+    if (h->stop_req[kStopRhs].set && (rc = arm_stop(h, kStopRhs))) return rc;
     if ((rc = upload_pairs(h, "prcg_solve_begin_multi_pipe", h->tmp_ext.d(), x0[0], x0[1]))) return rc;
     if ((rc = upload_pairs(h, "prcg_solve_begin_multi_pipe", h->b.d(), b[0], b[1]))) return rc;
     hipStream_t sc = h->sc;
@@ -455,7 +415,7 @@ int prcg_solve_begin_multi_pipe(prcg_t* h, int variant, int nrhs, const double* 
     if ((rc = pipe2_product(h))) return rc;
     const int grid = launch_pipe2_dots(sc, pipe2_args(h, 0));                               // mu, delta, gamma, nu, r.r   :25-36 / :126-140
     LAUNCHCHK(h, grid);
-    pipe2_reduce(h, 0, grid);
+    if ((rc = pipe2_reduce(h, 0, grid))) return rc;
     HIPCHK(h, hipStreamSynchronize(sc));
     h->in_session = true;
     return PRCG_OK;
@@ -475,9 +435,7 @@ int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const 
                                                    "and PRCG_M (m_pcg) only", who, variant);
     CHECK(h, nrhs == 2 || nrhs == 4, "%s: nrhs = %d: the session serves exactly 2 right-hand sides (or 4, as two pairs)", who, nrhs);
     if (int rc = refuse_hooks(h, who, "multi-RHS", hist_mask)) return rc;
-    CHECK(h, !h->stop_rhs_set, "%s: " STOP_RHS_SERVED, who);
-    CHECK(h, !h->stop_bj_set, "%s: " STOP_BJ_SERVED, who);
-    CHECK(h, !h->stop_hs_set, "%s: " STOP_HS_SERVED, who);
+    if (int rc = refuse_unserved_stops(h, who, kBeginMulti)) return rc;
     CHECK(h, have_columns(b, x0, nrhs), "%s: null b or x0", who);
     CHECK(h, max_iter >= 1, "%s: max_iter must be >= 1", who);
     const int64_t tiles = bj_tile_count(h);
@@ -498,13 +456,13 @@ int prcg_solve_begin_multi_block_jacobi(prcg_t* h, int variant, int nrhs, const 
 // ---- each column of a pipelined two-RHS session stopped at its own threshold ----
 int prcg_set_stop_rhs(prcg_t* h, int nrhs, const double* rr_stop) {
     if (!h) return PRCG_EINVAL;
-    if (!rr_stop) { h->stop_rhs_set = false; h->stop_rhs_thr[0] = h->stop_rhs_thr[1] = 0.0; return PRCG_OK; }
+    if (!rr_stop) { h->stop_req[kStopRhs] = Handle::StopRequest{}; return PRCG_OK; }
     CHECK(h, nrhs == 2, "prcg_set_stop_rhs: nrhs = %d: only the pipelined two-RHS session (prcg_solve_begin_multi_pipe) can stop its columns: "
                         "exactly 2 thresholds (NULL clears them)", nrhs);
     for (int c = 0; c < 2; ++c)
         CHECK(h, std::isfinite(rr_stop[c]) && rr_stop[c] >= 0.0, "prcg_set_stop_rhs: rr_stop[%d] = %g: the threshold of column %d must be finite "
               "and >= 0 (a bound on r.r; 0 stops on an exactly zero residual or on breakdown only)", c, rr_stop[c], c);
-    h->stop_rhs_set = true; h->stop_rhs_thr[0] = rr_stop[0]; h->stop_rhs_thr[1] = rr_stop[1];
+    h->stop_req[kStopRhs].set = true; h->stop_req[kStopRhs].thr[0] = rr_stop[0]; h->stop_req[kStopRhs].thr[1] = rr_stop[1];
     return PRCG_OK;
 }
 
@@ -515,9 +473,9 @@ int prcg_get_stops_rhs(prcg_t* h, int32_t* k_stop, int32_t* status) {
     int rc = prcg_sync(h);
     if (rc) return rc;
     for (int c = 0; c < 2 * h->groups; ++c) {
-        const bool stopped = h->stop_rhs && c < 2 && h->stopped_k_rhs[c] >= 0;
-        k_stop[c] = stopped ? h->stopped_k_rhs[c] : -1;
-        status[c] = stopped ? h->stop_status_rhs[c] : 0;
+        const bool stopped = h->column_stopped(c);
+        k_stop[c] = stopped ? h->stopped_k[c] : -1;
+        status[c] = stopped ? h->stop_status[c] : 0;
     }
     return PRCG_OK;
 }
@@ -559,7 +517,7 @@ int prcg_get_scalars_rhs(prcg_t* h, int k, int j, double* out) {
     if (rc) return rc;
     double row[kNS];
     const int first = row0(h, j / 2);
-    if (h->stop_rhs && h->stopped_k_rhs[j] >= 0 && k > h->stopped_k_rhs[j]) {      // beyond the column's stop: not part of its run
+    if (h->column_stopped(j) && k > h->stopped_k[j]) {      // beyond the column's stop: not part of its run
         for (int q = 0; q < kNS; ++q) out[q] = 0.0;
         return PRCG_OK;
     }
@@ -582,7 +540,7 @@ int prcg_get_coefficients_rhs(prcg_t* h, int k, int j, double* out) {
     if (rc) return rc;
     double row[kCoefStride];
     const int first = row0(h, j / 2);
-    if (h->stop_rhs && h->stopped_k_rhs[j] >= 0 && k > h->stopped_k_rhs[j]) { out[0] = out[1] = out[2] = 0.0; return PRCG_OK; }   // (as the scalars)
+    if (h->column_stopped(j) && k > h->stopped_k[j]) { out[0] = out[1] = out[2] = 0.0; return PRCG_OK; }   // (as the scalars)
     j %= 2;
     if ((rc = d2h(h, row, coef_at(h, first + (two_rows(h) ? 2 * k + j : k)), kCoefStride))) return rc;
     if (two_rows(h)) { out[0] = row[0]; out[1] = row[1]; out[2] = row[2]; return PRCG_OK; }     // a, b, the predicted nu
@@ -602,7 +560,7 @@ int prcg_get_history_rhs(prcg_t* h, int j, double* hist) {
     std::vector<double> all((size_t)(m + 1) * rows * kNS);
     if ((rc = d2h(h, all.data(), dots_at(h, row0(h, j / 2)), (int64_t)(m + 1) * rows * kNS))) return rc;
     // (a column stopped at its threshold: its history ends with the entry of its stop)
-    const int last = (h->stop_rhs && h->stopped_k_rhs[j] >= 0 && h->stopped_k_rhs[j] < h->k) ? h->stopped_k_rhs[j] : h->k;
+    const int last = (h->column_stopped(j) && h->stopped_k[j] < h->k) ? h->stopped_k[j] : h->k;
     j %= 2;
     for (int k = 0; k < m; ++k) {
         const double rr = two_rows(h) ? all[(size_t)(2 * k + j) * kNS + PRCG_S_RR] : all[(size_t)k * kNS + kHs2Rr + 2 * j];

@@ -446,16 +446,14 @@ int launch_pr2_dots(hipStream_t st, const Pr2Args& a) {
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 
-int launch_pipe2_update(hipStream_t st, const Pipe2Args& a) {
+int launch_pipe2_update(hipStream_t st, const Pipe2Args& a, const StopAt& stop) {
     const Chunking c = chunking(a.n);
-    if (a.d) hipLaunchKernelGGL((k_pipe2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
-    else     hipLaunchKernelGGL((k_pipe2_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
-    return PRCG_LAUNCH_OK() ? c.grid : -1;
-}
-int launch_pipe2_update_stop(hipStream_t st, const Pipe2Args& a, const int* words) {
-    const Chunking c = chunking(a.n);
-    if (a.d) hipLaunchKernelGGL((k_pipe2_update_stop<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, words);
-    else     hipLaunchKernelGGL((k_pipe2_update_stop<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, words);
+    if (stop) {
+        if (a.d) hipLaunchKernelGGL((k_pipe2_update_stop<true>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, stop.word);
+        else     hipLaunchKernelGGL((k_pipe2_update_stop<false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips, stop.word);
+    }
+    else if (a.d) hipLaunchKernelGGL((k_pipe2_update<true, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
+    else          hipLaunchKernelGGL((k_pipe2_update<false, false>), dim3(c.grid), dim3(kBlock), 0, st, a, c.trips);
     return PRCG_LAUNCH_OK() ? c.grid : -1;
 }
 int launch_pipe2_dots(hipStream_t st, const Pipe2Args& a) {

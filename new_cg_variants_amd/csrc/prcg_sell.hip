@@ -555,9 +555,11 @@ int launch_sell_set_values(hipStream_t st, const SellDev& A, const void* slices,
 }
 
 int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, SpmvEpilogue epi,
-                     const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu)
+                     const double* ep_r, const double* ep_d, double* ep_st, double* partials, int per_cu, const StopAt& stop)
 {
+    if (stop && epi != kEpiDotXY) return -1;
     if (nslices <= 0) return 0;
+    if (stop) return launch_sell<1, kEpiDotXYStop>(st, A, slices, nslices, x, y, 3, nullptr, nullptr, nullptr, partials, nullptr, product_prev(stop), per_cu);
     const FusedPrev none{};
     switch (epi) {
     case kEpiNone: return launch_sell<1, kEpiNone>(st, A, slices, nslices, x, y, 3, ep_r, ep_d, ep_st, partials, nullptr, none, per_cu);
@@ -569,45 +571,21 @@ int launch_sell_spmv(hipStream_t st, const SellDev& A, const void* slices, int n
     return -1;
 }
 
-int launch_sell_spmv_dot_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* x, double* y, double* partials,
-                              const ProductStop& stop, int per_cu)
-{
-    if (nslices <= 0) return 0;
-    FusedPrev fz{};
-    fz.word = stop.word; fz.word_k = stop.k;
-    return launch_sell<1, kEpiDotXYStop>(st, A, slices, nslices, x, y, 3, nullptr, nullptr, nullptr, partials, nullptr, fz, per_cu);
-}
-
 int launch_sell_spmm2(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
-                      int per_cu)
+                      int per_cu, const StopAt& stop)
 {
     if (nslices <= 0) return 0;
+    if (stop) return launch_sell<2, kEpiNoneStop>(st, A, slices, nslices, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, product_prev(stop), per_cu);
     return launch_sell<2, kEpiNone>(st, A, slices, nslices, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, FusedPrev{}, per_cu);
 }
 
 int launch_sell_spmm4(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
-                      double* dst0, double* dst1, int per_cu)
+                      double* dst0, double* dst1, int per_cu, const StopAt& stop)
 {
     if (nslices <= 0) return 0;
+    if (stop)      // (column 1's word follows column 0's: product_stopped<4>)
+        return launch_sell<4, kEpiNoneStop>(st, A, slices, nslices, src0, dst0, 3, src1, nullptr, dst1, nullptr, nullptr, product_prev(stop), per_cu);
     return launch_sell<4, kEpiNone>(st, A, slices, nslices, src0, dst0, 3, src1, nullptr, dst1, nullptr, nullptr, FusedPrev{}, per_cu);
-}
-
-int launch_sell_spmm2_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* rs, double* wu, int write_mask,
-                           const ProductStop& stop, int per_cu)
-{
-    if (nslices <= 0) return 0;
-    FusedPrev fz{};
-    fz.word = stop.word; fz.word_k = stop.k;
-    return launch_sell<2, kEpiNoneStop>(st, A, slices, nslices, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, fz, per_cu);
-}
-
-int launch_sell_spmm4_stop(hipStream_t st, const SellDev& A, const void* slices, int nslices, const double* src0, const double* src1,
-                           double* dst0, double* dst1, const ProductStop& stop, int per_cu)
-{
-    if (nslices <= 0) return 0;
-    FusedPrev fz{};
-    fz.word = stop.word; fz.word_k = stop.k;                 // (column 1's word follows column 0's: product_stopped<4>)
-    return launch_sell<4, kEpiNoneStop>(st, A, slices, nslices, src0, dst0, 3, src1, nullptr, dst1, nullptr, nullptr, fz, per_cu);
 }
 
 int launch_sell_pipe_fused(hipStream_t st, const SellDev& A, const void* slices, int nslices, const FusedState& f, int per_cu)

@@ -30,36 +30,24 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
     const int mask = pipe_recompute(h->variant) ? 3 : 2;
     bool on = false;
     int rc;
-    if (h->stop_bj) {
-        // a block-Jacobi session with a threshold (prcg_set_stop_block_jacobi): one stream, every launch in its stop form on the
-        // session's word, which is complete at each kernel boundary.  The reduction sums row k and decides on it (it returns at
-        // once if the session stopped earlier); the product and the pair launch of iteration k belong to the state of k, so they
-        // are skipped only if the session stopped BEFORE k -- stopped at k, it holds w, u, u~ (w~) of k as well.
-        const ProductStop ps{h->word, k};
-        launch_reduce_final_stop(h->sc, h->partA.d(), grid_upd, dots_at(h, k), SmallStop{h->thr, h->word}, k);
-        if (profile) prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
-        LAUNCHCHK(h, eng_spmm2_stop(h, h->sc, 0, in_ext, h->wu.d(), mask, ps));
-        if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
-        if (h->bj_var)
-            LAUNCHCHK(h, launch_block_jacobi_var_pair_stop(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->bjv_plan.ntiles, h->bjv_tiles_d(), h->bjv_code_d(),
-                                                           h->bj_blocks.d(), mask, ps));
-        else
-            LAUNCHCHK(h, launch_block_jacobi_pair_stop(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask, ps));
-        return PRCG_OK;
-    }
     if (!h->multi()) {
-        // everything in order on one stream
-        launch_reduce_final(h->sc, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5);
+        // everything in order on one stream.  A block-Jacobi session with a threshold (kStopBlockJacobi; no other kind comes here):
+        // every launch in its stop form on the session's word, which is complete at each kernel boundary.  The reduction sums row k
+        // and decides on it (it returns at once if the session stopped earlier); the product and the pair launch of iteration k
+        // belong to the state of k, so they are skipped only if the session stopped BEFORE k -- stopped at k, it holds w, u, u~
+        // (w~) of k as well.
+        const StopAt stop = h->stop_at(k);
+        LAUNCHCHK(h, launch_reduce_final(h->sc, h->partA.d(), grid_upd, dots_at(h, k), 0, 0, 5, stop));
         if (profile) prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
-        LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, in_ext, h->wu.d(), mask));
+        LAUNCHCHK(h, eng_spmm2(h, h->sc, 0, in_ext, h->wu.d(), mask, stop));
         if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         if (h->bj_session) {
             // block Jacobi: both columns of [w u] in one launch that reads every block once
             if (h->bj_var)
                 LAUNCHCHK(h, launch_block_jacobi_var_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->bjv_plan.ntiles, h->bjv_tiles_d(), h->bjv_code_d(),
-                                                          h->bj_blocks.d(), mask));
+                                                          h->bj_blocks.d(), mask, stop));
             else
-                LAUNCHCHK(h, launch_block_jacobi_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask));
+                LAUNCHCHK(h, launch_block_jacobi_pair(h->sc, h->wt.d(), h->ut.d(), h->wu.d(), h->n, h->bj_bs, h->bj_blocks.d(), mask, stop));
         } else if (h->stored_tilde) {
             // u~ = preconditioner(u); w~ = preconditioner(w) in the flavours that recompute w (pipe_pr_cg.py:178-182)
             if ((rc = apply_prec(h, h->wu.d() + 1, 2, h->ut.d(), 1))) return rc;
@@ -173,38 +161,41 @@ PipeUpdateArgs pipe_args(prcg_t* h, int k) {
 // make dots[pend_k] real if the last fused launch left it as block partials
 void fused_flush(prcg_t* h) {
     if (h->pend_parts > 0) {
-        // a session with a threshold: the reduction also DECIDES on the row it sums (the iteration has no later launch whose
-        // prologue would), and returns at once if the session has stopped -- its partials are then stale
-        if (h->stop && h->fused) launch_reduce_final_stop(h->sc, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k), SmallStop{h->thr, h->word}, h->pend_k);
-        else launch_reduce_final(h->sc, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k), 0, 0, 5);
+        // a one-launch session with a threshold: the reduction also DECIDES on the row it sums (the iteration has no later launch
+        // whose prologue would), and returns at once if the session has stopped -- its partials are then stale
+        launch_reduce_final(h->sc, h->pend_buf, h->pend_parts, dots_at(h, h->pend_k), 0, 0, 5, h->fused ? h->stop_at(h->pend_k) : StopAt{});
         h->pend_parts = 0;
     }
 }
 
-// A session with a threshold, every stream idle (prcg_sync): has the device stopped it?  The word tells.  prcg_iterate counted and
-// enqueued without knowing: launches k_stop + 1 .. h->k returned at once and wrote nothing, so the host's picture goes back to
-// iteration k_stop -- the iteration count; the input pairs, which every enqueued launch flipped once on the host only (the parity of
-// the difference says which buffer launch k_stop wrote; the one-workgroup solver works in place: no flip); and no partials are
-// pending (the reduction that would sum them returns at once as well).  A block-Jacobi session (Session::stop_bj) runs the
-// two-kernel schedule: nothing is flipped and nothing is ever pending, only the count goes back.  A Hestenes-Stiefel session
-// (Session::stop_hs) on a window operator flips its two direction buffers, once per enqueued iteration and on the host only like the
-// input pairs: the parity of the difference says which one launch B of k_stop wrote; on other operators and on the one-workgroup
-// solver p is updated in place; mu is not pending either.  Idempotent: once resolved, nothing more is enqueued.
+// A session with a threshold of any kind, every stream idle (prcg_sync): has the device stopped it?  The words tell, read once.
+// prcg_iterate counted and enqueued without knowing: launches k_stop + 1 .. h->k returned at once and wrote nothing.  A newly stopped
+// column records where and why; once EVERY column has stopped (a single session has one) the host's picture goes back to iteration
+// k_stop, with two columns the later stop -- the iteration count; the input pairs of a one-launch pipelined session, which every
+// enqueued launch flipped once on the host only (the parity of the difference says which buffer launch k_stop wrote; the
+// one-workgroup solver works in place: no flip); the two direction buffers of a Hestenes-Stiefel session on a window operator,
+// flipped in the same way (on other operators and in the one-workgroup solver p is updated in place); and nothing is pending, neither
+// partials nor mu (the reduction that would sum them returns at once as well).  The two-kernel schedules (block Jacobi, two
+// right-hand sides) flip nothing and leave nothing pending: only the count goes back.  Idempotent: once resolved, nothing more is
+// enqueued and prcg_iterate is a no-op.
 int resolve_stop(prcg_t* h) {
-    if (!h->in_session || !h->stop || h->stopped_k >= 0) return PRCG_OK;
-    int w[2] = {-1, 0};
+    if (!h->in_session || !h->stops() || h->stopped()) return PRCG_OK;
+    int w[4] = {-1, 0, -1, 0};
     HIPCHK(h, hipMemcpy(w, h->word, sizeof w, hipMemcpyDeviceToHost));
-    if (w[0] < 0) return PRCG_OK;
-    if (h->fused && !h->small && ((h->k - w[0]) & 1)) {       // (the two-kernel schedule of a block-Jacobi session flips nothing)
+    for (int c = 0; c < h->stop_cols(); ++c)
+        if (h->stopped_k[c] < 0 && w[2 * c] >= 0) { h->stopped_k[c] = w[2 * c]; h->stop_status[c] = w[2 * c + 1]; }
+    if (!h->stopped()) return PRCG_OK;
+    const int k_stop = h->stop_cols() == 2 && h->stopped_k[1] > h->stopped_k[0] ? h->stopped_k[1] : h->stopped_k[0];
+    const bool odd = (h->k - k_stop) & 1;
+    if (h->fused && !h->small && odd) {       // (the two-kernel schedules flip nothing)
         double* const bufA = h->prec ? h->rst.d() : h->rs.d();
         double* const bufB = h->prec ? h->rst2.d() : h->rs2.d();
         h->rs_cur = (h->rs_cur == bufA) ? bufB : bufA;
     }
-    if (h->stop_hs && h->win && !h->small_hs && ((h->k - w[0]) & 1)) h->p_cur = (h->p_cur == h->p.d()) ? h->p2.d() : h->p.d();
+    if (h->stop_kind == kStopHs && h->win && !h->small_hs && odd) h->p_cur = (h->p_cur == h->p.d()) ? h->p2.d() : h->p.d();
     h->pend_parts = 0;
     h->hs_pend_mu = 0;
-    h->k = w[0];
-    h->stopped_k = w[0]; h->stop_status = w[1];
+    h->k = k_stop;
     return PRCG_OK;
 }
 
@@ -214,7 +205,7 @@ int resolve_stop(prcg_t* h) {
 bool xp_deferred(const prcg_t* h) {
     const Session& s = *h;
     return h->opt.want_xp_defer && s.in_session && is_pipe(s.variant) && s.fused && !s.fused_comm && !s.small && h->win && !h->multi() &&
-           !records_state(s.hist_mask) && !s.stop;      // (with a threshold every launch closes itself: a stop leaves ONE iteration's state)
+           !records_state(s.hist_mask) && !s.stops();      // (with a threshold every launch closes itself: a stop leaves ONE iteration's state)
 }
 
 // what both one-launch pipelined schedules hand their kernel: the state of iteration k-1 and where iteration k goes
@@ -254,7 +245,7 @@ int iterate_pipe_fused(prcg_t* h, int k) {
     f.prev = prev;
     f.prev.xphase = h->xphase;
     f.prev.xcoef = h->xphase == 2 ? coef_at(h, k - 1) : nullptr;
-    if (h->stop) { f.prev.word = h->word; f.prev.thr = h->thr; f.prev.word_k = k - 1; }      // the prologue may stop the session at k - 1
+    if (const StopAt stop = h->stop_at(k - 1)) { f.prev.word = stop.word; f.prev.thr = stop.thr; f.prev.word_k = stop.k; }      // the prologue may stop the session at k - 1
     const int grid = eng_fused(h, h->sc, f);
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
@@ -356,7 +347,7 @@ int iterate_pipe(prcg_t* h, int k) {
     bool on = false;
     prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
     // (with a block-Jacobi threshold: update k is skipped if the session stopped at k - 1 or earlier)
-    const int grid = h->stop_bj ? launch_pipe_update_stop(h->sc, a, h->word, k) : launch_pipe_update(h->sc, a);
+    const int grid = launch_pipe_update(h->sc, a, h->stop_at(k));
     LAUNCHCHK(h, grid);
     prof_end(h, h->ev_upd, h->n_ev_upd, on);
     return pipe_spmm_and_reduce(h, k, grid, true);
@@ -405,8 +396,7 @@ int iterate_hs(prcg_t* h, int k) {
 //  whose prologue would -- and returns at once if the session has stopped: its partials are then stale)
 void hs_flush(prcg_t* h) {
     if (h->hs_pend_mu > 0) {
-        if (h->stop_hs) launch_reduce_hs_mu_stop(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), SmallStop{h->thr, h->word}, h->pend_k);
-        else launch_reduce_final(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), 0, PRCG_S_MU, 1);
+        launch_reduce_hs_mu(h->sc, h->partB.d(), h->hs_pend_mu, dots_at(h, h->pend_k), h->stop_at(h->pend_k));
         h->hs_pend_mu = 0;
     }
 }
@@ -429,9 +419,8 @@ int iterate_hs_fused(prcg_t* h, int k) {
     if (!have_mu) hs_flush(h);
     bool on = false;
     prof_begin(h, h->ev_upd, h->n_ev_upd, k, on);
-    const int g1 = h->stop_hs
-        ? launch_hs_update_xr_stop(h->sc, a, have_mu ? h->partB.d() : nullptr, have_mu ? h->hs_pend_mu : 0, dots_at(h, k - 1), SmallStop{h->thr, h->word}, k)
-        : launch_hs_update_xr(h->sc, a, have_mu ? h->partB.d() : nullptr, have_mu ? h->hs_pend_mu : 0, dots_at(h, k - 1));
+    const StopAt stop = h->stop_at(k);
+    const int g1 = launch_hs_update_xr(h->sc, a, have_mu ? h->partB.d() : nullptr, have_mu ? h->hs_pend_mu : 0, dots_at(h, k - 1), stop);
     LAUNCHCHK(h, g1);
     prof_end(h, h->ev_upd, h->n_ev_upd, on);
     h->hs_pend_mu = 0;
@@ -441,7 +430,7 @@ int iterate_hs_fused(prcg_t* h, int k) {
         FusedPrev hs{};
         hs.prev_partials = h->partA.d(); hs.nprev = g1;
         hs.dots_prev_out = dots_at(h, k); hs.dots_old = dots_at(h, k - 1);
-        if (h->stop_hs) { hs.word = h->word; hs.word_k = k; }
+        if (stop) { hs.word = stop.word; hs.word_k = stop.k; }      // (launch B skips, it never decides)
         double* p_new = (h->p_cur == h->p.d()) ? h->p2.d() : h->p.d();
         SRCCHK2(h, {h->prec ? h->rt.d() : h->r.d(), 1}, {h->p_cur, 1});
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
@@ -453,11 +442,9 @@ int iterate_hs_fused(prcg_t* h, int k) {
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->p_cur = p_new;
     } else {
-        LAUNCHCHK(h, h->stop_hs ? launch_hs_update_p_stop(h->sc, a, h->partA.d(), g1, dots_at(h, k), h->word, k)
-                                : launch_hs_update_p(h->sc, a, h->partA.d(), g1, dots_at(h, k)));
+        LAUNCHCHK(h, launch_hs_update_p(h->sc, a, h->partA.d(), g1, dots_at(h, k), stop));      // (launch B and the product skip, they never decide)
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, k, on);
-        grid = h->stop_hs ? eng_spmv_dot_stop(h, h->sc, 0, h->p_cur, h->s.d(), h->partB.d(), ProductStop{h->word, k})
-                          : eng_spmv(h, h->sc, 0, h->p_cur, h->s.d(), kEpiDotXY, nullptr, nullptr, nullptr, h->partB.d());
+        grid = eng_spmv(h, h->sc, 0, h->p_cur, h->s.d(), kEpiDotXY, nullptr, nullptr, nullptr, h->partB.d(), stop);
         LAUNCHCHK(h, grid);
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
     }
@@ -911,7 +898,7 @@ int begin_pipe(prcg_t* h) {
     // a session with a threshold runs the single-GPU one-launch schedule or the one-workgroup solver (what prcg_solve_begin let
     // through selects it); every launch closes itself (xp_deferred), so a stopped session holds one complete iteration
     // -- or, with blocks (prcg_set_stop_block_jacobi), the stored-tilde two-kernel schedule, whose launches have stop forms of their own
-    CHECK(h, !h->stop || (h->stop_bj ? (h->bj_session && !h->fused) : (h->fused && !h->fused_comm)),
+    CHECK(h, !h->stops() || (h->stop_kind == kStopBlockJacobi ? (h->bj_session && !h->fused) : (h->fused && !h->fused_comm)),
           "prcg_solve_begin: a stop threshold is set and the session did not get the one-launch schedule");
     HIPCHK(h, h->xp.ensure((size_t)2 * n * D, h->sc));
     HIPCHK(h, h->rs.ensure((size_t)2 * (h->prec ? n : ne) * D, h->sc));
@@ -969,8 +956,7 @@ int begin_pipe(prcg_t* h) {
     const int grid = launch_pipe_dots(sc, a);                           // nu, mu, delta, gamma
     LAUNCHCHK(h, grid);
     // (with a threshold: the rule on row 0 rides on its reduction -- b = A x0 stops the session before its first iteration)
-    if (h->stop) launch_reduce_final_stop(sc, h->partA.d(), grid, dots_at(h, 0), SmallStop{h->thr, h->word}, 0);
-    else launch_reduce_final(sc, h->partA.d(), grid, dots_at(h, 0), 0, 0, 5);
+    LAUNCHCHK(h, launch_reduce_final(sc, h->partA.d(), grid, dots_at(h, 0), 0, 0, 5, h->stop_at(0)));
     if ((rc = allreduce(h, dots_at(h, 0), 5, sc))) return rc;
     if (h->gather) {
         // COLLECTIVE part, the same on every rank of a merged-exchange session whatever schedule the rank itself
@@ -1096,7 +1082,7 @@ int begin_hs_pr(prcg_t* h) {
                   small_fits(h->n, h->nnz, h->max_row_len, &h->small_mode);
     // a session with a threshold (prcg_set_stop_hs) runs the schedule without reduction launches or the one-workgroup solver: what
     // prcg_solve_begin let through selects one of them
-    CHECK(h, !h->stop_hs || h->hs_fused, "prcg_solve_begin: a Hestenes-Stiefel stop threshold is set and the session did not get the schedule without reduction launches");
+    CHECK(h, h->stop_kind != kStopHs || h->hs_fused, "prcg_solve_begin: a Hestenes-Stiefel stop threshold is set and the session did not get the schedule without reduction launches");
     // r (r~) is the staged-window source of the Hestenes-Stiefel product launch: like every vector that feeds a
     // product it has the spare entries behind its end (a window page of the last tile may reach past row n)
     HIPCHK(h, h->r.ensure((size_t)(h->opt.debug_short_sources ? n : ne) * D, h->sc));
@@ -1138,8 +1124,7 @@ int begin_hs_pr(prcg_t* h) {
         if ((rc = dist_spmv(h, h->p.d(), h->s.d(), kEpiDotXY, nullptr, nullptr, nullptr, &grid))) return rc;
         // (with a threshold, prcg_set_stop_hs: the rule on row 0 rides on the reduction that completes it -- b = A x0 stops the session
         //  before its first iteration)
-        if (h->stop_hs) launch_reduce_hs_mu_stop(sc, h->partB.d(), grid, dots_at(h, 0), SmallStop{h->thr, h->word}, 0);
-        else launch_reduce_final(sc, h->partB.d(), grid, dots_at(h, 0), 0, PRCG_S_MU, 1);   // mu = p.s  :27
+        launch_reduce_hs_mu(sc, h->partB.d(), grid, dots_at(h, 0), h->stop_at(0));   // mu = p.s  :27
         if ((rc = allreduce(h, dots_at(h, 0) + PRCG_S_MU, 1, sc))) return rc;
     } else {
         PrArgs a = pr_args(h, 0);
@@ -1199,17 +1184,88 @@ int open_session(prcg_t* h, const char* who, int variant, int max_iter, uint32_t
     //  four right-hand sides: twice the rows again, one set per pair group)
     HIPCHK(h, h->dots.ensure((size_t)(max_iter + 1) * rows_per_iteration * kNS * D, h->sc));
     HIPCHK(h, h->coef.ensure((size_t)(max_iter + 1) * rows_per_iteration * kCoefStride * D, h->sc));
-    if (h->stop_set || h->stop_bj_set || h->stop_hs_set) {
-        // the stop word of a session with a threshold: {-1, 0} = running (prcg_solve_begin arms it; other session types leave it alone)
-        static const int kRunning[2] = {-1, 0};
-        if (!h->stop_word.p) HIPCHK(h, h->stop_word.alloc(16));
-        HIPCHK(h, hipMemcpyAsync(h->stop_word.p, kRunning, sizeof kRunning, hipMemcpyHostToDevice, h->sc));
-    }
     if (inv_diag) return h2d(h, h->dinv.d(), inv_diag, h->n);
     return PRCG_OK;
 }
 
+// ---- stop requests: what each begin path does not serve ------------------------------------------------------
+int refuse_unserved_stops(prcg_t* h, const char* who, BeginPath path, int variant, const double* inv_diag) {
+    const auto set = [h](StopKind kind) { return h->stop_req[kind].set; };
+    if (path != kBeginSingle) {
+        // the sessions with several right-hand sides: only the pipelined two-RHS one stops, by per-column thresholds; no such
+        // session is begun while a threshold it cannot stop by is set (the Hestenes-Stiefel multi-RHS sessions do not stop: a follow-up)
+        CHECK(h, !set(kStopRhs) || path == kBeginMultiPipe,
+              "%s: per-column stop thresholds are set (prcg_set_stop_rhs), which serve the pipelined two-RHS session only "
+              "(prcg_solve_begin_multi_pipe: PRCG_PIPE_PR, PRCG_PIPE_PR_M, Jacobi or none); this session cannot stop -- "
+              "prcg_set_stop_rhs(h, 0, NULL) clears the thresholds", who);
+        CHECK(h, !set(kStopBlockJacobi),
+              "%s: a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves pipelined SINGLE sessions with point-block "
+              "Jacobi only (prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_block_jacobi(h, NULL) clears the threshold", who);
+        CHECK(h, !set(kStopHs),
+              "%s: a Hestenes-Stiefel stop threshold is set (prcg_set_stop_hs), which serves SINGLE PRCG_HS sessions only "
+              "(prcg_solve_begin); this session cannot stop by it -- prcg_set_stop_hs(h, NULL) clears the threshold", who);
+        return PRCG_OK;
+    }
+    const bool one_gpu = !h->multi() && h->g == 0, stored = !inv_diag && (h->cb || h->have_block_jacobi());
+    if (set(kStopPipe)) {
+        const char* const served = "a stop threshold is set (prcg_set_stop), which serves the pipelined variants (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_PIPE_P, "
+                                   "PRCG_PIPE_P_M) on one GPU, unpreconditioned or with inv_diag, on the one-launch schedule or the one-workgroup solver";
+        CHECK(h, is_pipe(variant), "%s: %s; variant %d is not pipelined (prcg_set_stop(h, NULL) clears the threshold)", who, served, variant);
+        CHECK(h, one_gpu, "%s: %s; this handle has a communicator or ghost rows", who, served);
+        CHECK(h, !stored, "%s: %s; a host-callback or block-Jacobi preconditioner is in force (the stored-tilde schedule cannot stop)", who, served);
+        CHECK(h, h->opt.want_fused, "%s: %s; PRCG_FUSED=0 selects the two-kernel schedule, which cannot stop", who, served);
+        CHECK(h, !h->replace_fn, "%s: %s; a replace hook is set", who, served);
+    }
+    if (set(kStopBlockJacobi)) {
+        const char* const served = "a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves the pipelined variants (PRCG_PIPE_PR, "
+                                   "PRCG_PIPE_PR_M, PRCG_PIPE_P, PRCG_PIPE_P_M) on one GPU with point-block Jacobi in force";
+        const char* const clears = "(prcg_set_stop_block_jacobi(h, NULL) clears the threshold)";
+        CHECK(h, is_pipe(variant), "%s: %s; variant %d is not pipelined %s", who, served, variant, clears);
+        CHECK(h, one_gpu, "%s: %s; this handle has a communicator or ghost rows %s", who, served, clears);
+        CHECK(h, !inv_diag, "%s: %s; inv_diag overrides the blocks -- a session with a diagonal stops through prcg_set_stop %s", who, served, clears);
+        CHECK(h, !h->cb, "%s: %s; a host-callback preconditioner is in force %s", who, served, clears);
+        CHECK(h, h->have_block_jacobi(), "%s: %s; no blocks are in force -- a session without blocks stops through prcg_set_stop %s", who, served, clears);
+        CHECK(h, !h->replace_fn, "%s: %s; a replace hook is set %s", who, served, clears);
+    }
+    if (set(kStopHs)) {
+        const char* const served = "a Hestenes-Stiefel stop threshold is set (prcg_set_stop_hs), which serves PRCG_HS on one GPU, unpreconditioned or with inv_diag, "
+                                   "on the schedule without reduction launches or the one-workgroup solver";
+        const char* const clears = "(prcg_set_stop_hs(h, NULL) clears the threshold)";
+        CHECK(h, variant == PRCG_HS, "%s: %s; variant %d is not Hestenes-Stiefel %s", who, served, variant, clears);
+        CHECK(h, one_gpu, "%s: %s; this handle has a communicator or ghost rows %s", who, served, clears);
+        CHECK(h, !stored, "%s: %s; a host-callback or block-Jacobi preconditioner is in force (the stored-tilde schedule with reduction "
+                          "launches cannot stop) %s", who, served, clears);
+        CHECK(h, h->opt.want_fused, "%s: %s; PRCG_FUSED=0 selects the schedule with reduction launches, which cannot stop %s", who, served, clears);
+        CHECK(h, !h->replace_fn, "%s: %s; a replace hook is set %s", who, served, clears);
+    }
+    return PRCG_OK;
+}
+
+int arm_stop(prcg_t* h, StopKind kind) {
+    static const int kRunning[4] = {-1, 0, -1, 0};
+    if (!h->stop_words.p) HIPCHK(h, h->stop_words.alloc(sizeof kRunning));
+    HIPCHK(h, hipMemcpyAsync(h->stop_words.p, kRunning, sizeof kRunning, hipMemcpyHostToDevice, h->sc));
+    h->stop_kind = kind;
+    h->thr[0] = h->stop_req[kind].thr[0]; h->thr[1] = h->stop_req[kind].thr[1];
+    h->word = h->stop_words.i();
+    return PRCG_OK;
+}
+
 }  // namespace prcg
+
+namespace {
+
+// prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs (`name`): the request of `kind` set to *rr_stop or, with NULL, cleared
+int set_stop_request(prcg_t* h, StopKind kind, const char* name, const double* rr_stop) {
+    if (!h) return PRCG_EINVAL;
+    if (!rr_stop) { h->stop_req[kind] = Handle::StopRequest{}; return PRCG_OK; }
+    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "%s: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop stops "
+                                                         "the session; NULL clears it)", name, *rr_stop);
+    h->stop_req[kind].set = true; h->stop_req[kind].thr[0] = *rr_stop;
+    return PRCG_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1222,47 +1278,8 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     CHECK(h, !(hist_mask & (PRCG_HIST_ERROR_A_NORM | PRCG_HIST_ERROR_2_NORM)) || x_true,
           "prcg_solve_begin: error histories need x_true");
     CHECK(h, h->g == 0 || (h->multi() && h->have_halo), "ghost columns need a communicator and a halo plan");
-    if (h->stop_set) {
-        // a threshold is set (prcg_set_stop): only sessions that can stop on the device are begun -- nothing falls back
-#define STOP_SERVED "a stop threshold is set (prcg_set_stop), which serves the pipelined variants (PRCG_PIPE_PR, PRCG_PIPE_PR_M, PRCG_PIPE_P, " \
-                    "PRCG_PIPE_P_M) on one GPU, unpreconditioned or with inv_diag, on the one-launch schedule or the one-workgroup solver"
-        CHECK(h, is_pipe(variant), "prcg_solve_begin: " STOP_SERVED "; variant %d is not pipelined (prcg_set_stop(h, NULL) clears the threshold)", variant);
-        CHECK(h, !h->multi() && h->g == 0, "prcg_solve_begin: " STOP_SERVED "; this handle has a communicator or ghost rows");
-        CHECK(h, inv_diag || !(h->cb || h->have_block_jacobi()),
-              "prcg_solve_begin: " STOP_SERVED "; a host-callback or block-Jacobi preconditioner is in force (the stored-tilde schedule cannot stop)");
-        CHECK(h, h->opt.want_fused, "prcg_solve_begin: " STOP_SERVED "; PRCG_FUSED=0 selects the two-kernel schedule, which cannot stop");
-        CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set");
-#undef STOP_SERVED
-    }
-    if (h->stop_bj_set) {
-        // a threshold for block-Jacobi sessions is set (prcg_set_stop_block_jacobi): only what stops on the device is begun
-#define STOP_SERVED "a block-Jacobi stop threshold is set (prcg_set_stop_block_jacobi), which serves the pipelined variants (PRCG_PIPE_PR, " \
-                    "PRCG_PIPE_PR_M, PRCG_PIPE_P, PRCG_PIPE_P_M) on one GPU with point-block Jacobi in force"
-#define STOP_CLEARS "(prcg_set_stop_block_jacobi(h, NULL) clears the threshold)"
-        CHECK(h, is_pipe(variant), "prcg_solve_begin: " STOP_SERVED "; variant %d is not pipelined " STOP_CLEARS, variant);
-        CHECK(h, !h->multi() && h->g == 0, "prcg_solve_begin: " STOP_SERVED "; this handle has a communicator or ghost rows " STOP_CLEARS);
-        CHECK(h, !inv_diag, "prcg_solve_begin: " STOP_SERVED "; inv_diag overrides the blocks -- a session with a diagonal stops through prcg_set_stop " STOP_CLEARS);
-        CHECK(h, !h->cb, "prcg_solve_begin: " STOP_SERVED "; a host-callback preconditioner is in force " STOP_CLEARS);
-        CHECK(h, h->have_block_jacobi(), "prcg_solve_begin: " STOP_SERVED "; no blocks are in force -- a session without blocks stops through prcg_set_stop " STOP_CLEARS);
-        CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set " STOP_CLEARS);
-#undef STOP_CLEARS
-#undef STOP_SERVED
-    }
-    if (h->stop_hs_set) {
-        // a threshold for Hestenes-Stiefel sessions is set (prcg_set_stop_hs): only what stops on the device is begun
-#define STOP_SERVED "a Hestenes-Stiefel stop threshold is set (prcg_set_stop_hs), which serves PRCG_HS on one GPU, unpreconditioned or with inv_diag, " \
-                    "on the schedule without reduction launches or the one-workgroup solver"
-#define STOP_CLEARS "(prcg_set_stop_hs(h, NULL) clears the threshold)"
-        CHECK(h, variant == PRCG_HS, "prcg_solve_begin: " STOP_SERVED "; variant %d is not Hestenes-Stiefel " STOP_CLEARS, variant);
-        CHECK(h, !h->multi() && h->g == 0, "prcg_solve_begin: " STOP_SERVED "; this handle has a communicator or ghost rows " STOP_CLEARS);
-        CHECK(h, inv_diag || !(h->cb || h->have_block_jacobi()),
-              "prcg_solve_begin: " STOP_SERVED "; a host-callback or block-Jacobi preconditioner is in force (the stored-tilde schedule with reduction "
-              "launches cannot stop) " STOP_CLEARS);
-        CHECK(h, h->opt.want_fused, "prcg_solve_begin: " STOP_SERVED "; PRCG_FUSED=0 selects the schedule with reduction launches, which cannot stop " STOP_CLEARS);
-        CHECK(h, !h->replace_fn, "prcg_solve_begin: " STOP_SERVED "; a replace hook is set " STOP_CLEARS);
-#undef STOP_CLEARS
-#undef STOP_SERVED
-    }
+    // a threshold is set: only sessions that can stop on the device are begun -- nothing falls back
+    if (int rc = refuse_unserved_stops(h, "prcg_solve_begin", kBeginSingle, variant, inv_diag)) return rc;
     // every vector that feeds a matrix product has ghost room AND kGatherPad spare entries: the
     // narrow column encodings decode a few out-of-tile bytes per tile against the tile's own base
     // (products nobody reads); the pad keeps those gathers inside the allocation without a test
@@ -1271,9 +1288,9 @@ int prcg_solve_begin(prcg_t* h, int variant, const double* b, const double* x0, 
     int rc = open_session(h, "prcg_solve_begin", variant, max_iter, hist_mask, inv_diag, x_true != nullptr,
                           {{&h->x, (size_t)n * D}, {&h->b, (size_t)n * D}, {&h->xt, (size_t)n * D}, {&h->e_ext, (size_t)ne * D}});
     if (rc) return rc;
-    if (h->stop_set) { h->stop = true; h->thr = h->stop_thr; h->word = h->stop_word.i(); }
-    if (h->stop_bj_set) { h->stop = h->stop_bj = true; h->thr = h->stop_bj_thr; h->word = h->stop_word.i(); }
-    if (h->stop_hs_set) { h->stop = h->stop_hs = true; h->thr = h->stop_hs_thr; h->word = h->stop_word.i(); }
+    // (what refuse_unserved_stops let through is at most one request: each serves what the others refuse)
+    for (const StopKind kind : {kStopPipe, kStopBlockJacobi, kStopHs})
+        if (h->stop_req[kind].set && (rc = arm_stop(h, kind))) return rc;
     if ((rc = h2d(h, h->x.d(), x0, n))) return rc;
     if ((rc = h2d(h, h->b.d(), b, n))) return rc;
     if (x_true && (rc = h2d(h, h->xt.d(), x_true, n))) return rc;
@@ -1296,8 +1313,7 @@ int prcg_iterate(prcg_t* h, int iters) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_iterate: no open session");
     CHECK(h, iters >= 0, "prcg_iterate: negative count");
-    if (h->stopped_k >= 0) return PRCG_OK;       // stopped at its threshold (prcg_sync has seen the word): a no-op
-    if (h->all_stopped_rhs()) return PRCG_OK;    // ... both columns of a pipelined two-RHS session at theirs (prcg_set_stop_rhs)
+    if (h->stopped()) return PRCG_OK;            // stopped at its threshold, every column at its own (prcg_sync has seen the words): a no-op
     CHECK(h, h->k + iters <= h->max_iter, "prcg_iterate: %d more iterations exceed max_iter=%d (k=%d)", iters,
           h->max_iter, h->k);
     HIPCHK(h, hipSetDevice(h->dev));
@@ -1315,10 +1331,11 @@ int prcg_iterate(prcg_t* h, int iters) {
         // all `iters` iterations inside one launch of one workgroup (Hestenes-Stiefel or pipelined)
         if (h->small_hs) hs_flush(h);
         const SmallArgs sa = small_args(h, iters);
-        const SmallStop ss{h->thr, h->word};
+        const StopAt stop = h->stop_at(h->k);
+        const SmallStop ss = stop.decides();
         bool on = false;
         prof_begin(h, h->ev_spmv, h->n_ev_spmv, 0, on);
-        LAUNCHCHK(h, h->small_hs ? launch_small_hs(h->sc, sa, h->small_mode, h->stop ? &ss : nullptr) : launch_small_pipe_pr(h->sc, sa, h->small_mode, h->stop ? &ss : nullptr));
+        LAUNCHCHK(h, h->small_hs ? launch_small_hs(h->sc, sa, h->small_mode, stop ? &ss : nullptr) : launch_small_pipe_pr(h->sc, sa, h->small_mode, stop ? &ss : nullptr));
         prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         h->k += iters;
         return PRCG_OK;
@@ -1360,36 +1377,12 @@ int prcg_sync(prcg_t* h) {
                                             "(communication stream starved or a peer stalled); results are invalid. "
                                             "PRCG_FUSED_COMM=0 selects the two-kernel schedule");
     }
-    if (int rc = resolve_stop(h)) return rc;
-    return resolve_stops_rhs(h);
+    return resolve_stop(h);
 }
 
-int prcg_set_stop(prcg_t* h, const double* rr_stop) {
-    if (!h) return PRCG_EINVAL;
-    if (!rr_stop) { h->stop_set = false; h->stop_thr = 0.0; return PRCG_OK; }
-    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "prcg_set_stop: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop stops "
-                                                         "the session; NULL clears it)", *rr_stop);
-    h->stop_set = true; h->stop_thr = *rr_stop;
-    return PRCG_OK;
-}
-
-int prcg_set_stop_block_jacobi(prcg_t* h, const double* rr_stop) {
-    if (!h) return PRCG_EINVAL;
-    if (!rr_stop) { h->stop_bj_set = false; h->stop_bj_thr = 0.0; return PRCG_OK; }
-    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "prcg_set_stop_block_jacobi: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop "
-                                                         "stops the session; NULL clears it)", *rr_stop);
-    h->stop_bj_set = true; h->stop_bj_thr = *rr_stop;
-    return PRCG_OK;
-}
-
-int prcg_set_stop_hs(prcg_t* h, const double* rr_stop) {
-    if (!h) return PRCG_EINVAL;
-    if (!rr_stop) { h->stop_hs_set = false; h->stop_hs_thr = 0.0; return PRCG_OK; }
-    CHECK(h, std::isfinite(*rr_stop) && *rr_stop >= 0.0, "prcg_set_stop_hs: rr_stop = %g: the threshold must be finite and >= 0 (r.r <= rr_stop "
-                                                         "stops the session; NULL clears it)", *rr_stop);
-    h->stop_hs_set = true; h->stop_hs_thr = *rr_stop;
-    return PRCG_OK;
-}
+int prcg_set_stop(prcg_t* h, const double* rr_stop) { return set_stop_request(h, kStopPipe, "prcg_set_stop", rr_stop); }
+int prcg_set_stop_block_jacobi(prcg_t* h, const double* rr_stop) { return set_stop_request(h, kStopBlockJacobi, "prcg_set_stop_block_jacobi", rr_stop); }
+int prcg_set_stop_hs(prcg_t* h, const double* rr_stop) { return set_stop_request(h, kStopHs, "prcg_set_stop_hs", rr_stop); }
 
 int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status) {
     if (!h) return PRCG_EINVAL;
@@ -1398,7 +1391,7 @@ int prcg_get_stop(prcg_t* h, int32_t* k_stop, int32_t* status) {
     CHECK(h, k_stop && status, "prcg_get_stop: null buffer");
     int rc = prcg_sync(h);
     if (rc) return rc;
-    *k_stop = h->stopped_k; *status = h->stopped_k >= 0 ? h->stop_status : 0;
+    *k_stop = h->stopped_k[0]; *status = h->stopped_k[0] >= 0 ? h->stop_status[0] : 0;
     return PRCG_OK;
 }
 
@@ -1422,7 +1415,7 @@ int prcg_set_iteration(prcg_t* h, int k) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session, "prcg_set_iteration: no open session");
     NOT_RHS2(h, "prcg_set_iteration");
-    CHECK(h, !h->stop, "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
+    CHECK(h, !h->stops(), "prcg_set_iteration: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
     CHECK(h, k >= 0 && k < h->max_iter, "prcg_set_iteration: k out of range");
     h->k = k;
     if (h->peer && is_pipe(h->variant)) {
@@ -1483,7 +1476,7 @@ int prcg_set_vector(prcg_t* h, int which, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in, "prcg_set_vector: no session or null buffer");
     NOT_RHS2(h, "prcg_set_vector");
-    CHECK(h, !h->stop, "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
+    CHECK(h, !h->stops(), "prcg_set_vector: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     const int64_t n = h->n;
@@ -1506,7 +1499,7 @@ int prcg_get_scalars(prcg_t* h, int k, double* out) {
     NOT_RHS2(h, "prcg_get_scalars");
     int rc = prcg_sync(h);
     if (rc) return rc;
-    if (h->stopped_k >= 0 && k > h->stopped_k) { memset(out, 0, kNS * sizeof(double)); return PRCG_OK; }      // beyond the stop: not part of the run
+    if (h->stopped_k[0] >= 0 && k > h->stopped_k[0]) { memset(out, 0, kNS * sizeof(double)); return PRCG_OK; }      // beyond the stop: not part of the run
     return d2h(h, out, dots_at(h, k), kNS);
 }
 
@@ -1514,7 +1507,7 @@ int prcg_set_scalars(prcg_t* h, int k, const double* in) {
     if (!h) return PRCG_EINVAL;
     CHECK(h, h->in_session && in && k >= 0 && k <= h->max_iter, "prcg_set_scalars: bad argument");
     NOT_RHS2(h, "prcg_set_scalars");
-    CHECK(h, !h->stop, "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
+    CHECK(h, !h->stops(), "prcg_set_scalars: the open session was begun with a stop threshold (prcg_set_stop, prcg_set_stop_block_jacobi, prcg_set_stop_hs): its state is not set from outside");
     int rc = prcg_sync(h);
     if (rc) return rc;
     if ((rc = h2d(h, dots_at(h, k), in, kNS))) return rc;
@@ -1532,7 +1525,7 @@ int prcg_get_coefficients(prcg_t* h, int k, double* out) {
     NOT_RHS2(h, "prcg_get_coefficients");
     int rc = prcg_sync(h);
     if (rc) return rc;
-    if (h->stopped_k >= 0 && k > h->stopped_k) { memset(out, 0, 3 * sizeof(double)); return PRCG_OK; }
+    if (h->stopped_k[0] >= 0 && k > h->stopped_k[0]) { memset(out, 0, 3 * sizeof(double)); return PRCG_OK; }
     return d2h(h, out, coef_at(h, k), 3);
 }
 

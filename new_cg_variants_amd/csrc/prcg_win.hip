@@ -1592,20 +1592,14 @@ int launch_win_cg_one(hipStream_t st, const WinDev& A, const WTile* tiles, int n
 }
 
 int launch_win_spmm2(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
-                     int write_mask, int per_cu)
+                     int write_mask, int per_cu, const StopAt& stop)
 {
     if (ntiles <= 0) return 0;
+    if (stop)
+        return launch_win<2, kEpiNoneStop>(geom, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           product_prev(stop), per_cu);
     return launch_win<2, kEpiNone>(geom, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    FusedPrev{}, per_cu);
-}
-
-int launch_win_spmm2_stop(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const double* rs, double* wu,
-                          int write_mask, const ProductStop& stop, int per_cu)
-{
-    if (ntiles <= 0) return 0;
-    FusedPrev fz{};
-    fz.word = stop.word; fz.word_k = stop.k;
-    return launch_win<2, kEpiNoneStop>(geom, st, A, tiles, ntiles, rs, wu, write_mask, nullptr, nullptr, nullptr, nullptr, nullptr, fz, per_cu);
 }
 
 int launch_win_pipe_fused(hipStream_t st, const WinDev& A, const WTile* tiles, int ntiles, int geom, const FusedState& f,

@@ -369,21 +369,30 @@ class DeviceCSR:
         self._put_blocks(block_jacobi, block_jacobi_var)
         thr = None if rr_stop is None else np.array([rr_stop], dtype=np.float64)
         blocks = block_jacobi is not None or block_jacobi_var is not None
-        # Hestenes-Stiefel without blocks or a callback stops through a setter of its own (prcg.h: prcg_set_stop_hs)
+        # with blocks the block-Jacobi setter; Hestenes-Stiefel without blocks or a callback stops through a setter of its own
         hs = int(variant) == L.HS and not blocks and preconditioner is None
-        # each setter gets the threshold or None, which clears what an earlier session set: with blocks the block-Jacobi one
-        self._check(self._lib.prcg_set_stop(self._h, L.ptr(None if blocks or hs else thr)))
-        self._check(self._lib.prcg_set_stop_block_jacobi(self._h, L.ptr(thr if blocks else None)))
-        self._check(self._lib.prcg_set_stop_hs(self._h, L.ptr(thr if hs else None)))
-        try:
+        with self._stop_request('prcg_set_stop_block_jacobi' if blocks else 'prcg_set_stop_hs' if hs else 'prcg_set_stop', thr):
             self._check(self._lib.prcg_solve_begin(self._h, int(variant), L.ptr(b), L.ptr(x0), int(max_iter),
                                                    L.ptr(xt), L.ptr(dv), int(hist_mask)))
-        finally:
-            if blocks and thr is not None:     # the threshold is this session's: the multi-RHS begins, which it refuses, are served again
-                self._check(self._lib.prcg_set_stop_block_jacobi(self._h, None))
-            if hs and thr is not None:         # (the same for the Hestenes-Stiefel one)
-                self._check(self._lib.prcg_set_stop_hs(self._h, None))
         self.max_iter, self.hist_mask = int(max_iter), int(hist_mask)
+
+    _SINGLE_STOPS = ('prcg_set_stop', 'prcg_set_stop_block_jacobi', 'prcg_set_stop_hs')
+
+    @contextlib.contextmanager
+    def _stop_request(self, setter, thr):
+        """The handle's stop requests around ONE begin (prcg.h: prcg_set_stop, _block_jacobi, _hs, _rhs).  `setter`, the one the
+        session needs, gets thr -- None clears what an earlier session set -- and the other setters of single sessions get None
+        (prcg_set_stop_rhs has its begin to itself).  Afterwards the handle is restored: a threshold is this session's, so its
+        request is cleared and the begins that refuse it are served again; prcg_set_stop's stays, no other begin consults it."""
+        single = setter in self._SINGLE_STOPS
+        for name in self._SINGLE_STOPS if single else (setter,):
+            value = L.ptr(thr if name == setter else None)
+            self._check(getattr(self._lib, name)(self._h, *((value,) if single else (2, value))))
+        try:
+            yield
+        finally:
+            if thr is not None and setter != 'prcg_set_stop':
+                self._check(getattr(self._lib, setter)(self._h, *((None,) if single else (0, None))))
 
     def _put_blocks(self, block_jacobi, block_jacobi_var):
         """The blocks a session asks for, put in force on the handle (begin, begin_multi_block_jacobi): (bs, inv_blocks) or
@@ -470,12 +479,8 @@ class DeviceCSR:
         if X0.shape != (2, self.n):
             raise ValueError(f'begin_multi_pipe: X0 must have shape (2, {self.n}), the same as B, got {tuple(X0.shape)}')
         dv = _diagonal('begin_multi_pipe', inv_diag, self.n)
-        self._check(self._lib.prcg_set_stop_rhs(self._h, 2, L.ptr(thr)))        # (None clears what an earlier session set)
-        try:
+        with self._stop_request('prcg_set_stop_rhs', thr):
             self._begin_multi_pipe(variant, B, X0, max_iter, dv, hist_mask)
-        finally:
-            if thr is not None:                # the thresholds are this session's: the handle's other entries are served again
-                self._check(self._lib.prcg_set_stop_rhs(self._h, 0, None))
 
     def _begin_multi_pipe(self, variant, B, X0, max_iter, dv, hist_mask):
         self._check(self._lib.prcg_solve_begin_multi_pipe(self._h, int(variant), 2, _row_pointers(B), _row_pointers(X0), int(max_iter),
