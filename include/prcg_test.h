@@ -186,6 +186,11 @@ int64_t prcg_debug_layout(const prcg_t* h, int64_t* out, int64_t capacity);
  * prcg_debug_layout's out[4] follows the products with a dot epilogue (one launch over all tiles: sessions without a
  * communicator) as well as the one-launch pipelined iteration. */
 int64_t prcg_debug_slice_rows(const prcg_t* h, int32_t* out, int64_t capacity);
+/* Diagnostic (tests): the number of INTERIOR slices of a sliced-row operator -- slices [0, that) of prcg_debug_slice_rows' table
+ * hold no row with a ghost column, every later slice holds at least one -- which is where a product with a dot epilogue in two
+ * launches (prcg_debug_layout's out[8]) cuts the table: prcg_debug_layout's out[6] counts CSR-adaptive tiles whatever runs.
+ * 0 if the resident operator has no sliced rows, -1 on a bad argument. */
+int64_t prcg_debug_interior_slices(const prcg_t* h);
 /* Capacity rule of every vector a matrix-product launch reads (window pages are whole 64-column blocks, the narrow
  * column encodings decode a few out-of-tile bytes per tile): n_rows + n_ghost entries of `components` doubles plus
  * 65,536 spare entries must lie between the pointer and the end of its allocation.  The engine evaluates this at

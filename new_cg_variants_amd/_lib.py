@@ -136,6 +136,7 @@ _SIGNATURES = {
     'prcg_window_source_ok': (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int64]),
     'prcg_debug_layout': (C.c_int64, [_P, _P, C.c_int64]),
     'prcg_debug_slice_rows': (C.c_int64, [_P, _P, C.c_int64]),
+    'prcg_debug_interior_slices': (C.c_int64, [_P]),
 }
 
 REPLACE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)

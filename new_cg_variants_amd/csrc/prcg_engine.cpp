@@ -1560,6 +1560,11 @@ int64_t prcg_debug_slice_rows(const prcg_t* h, int32_t* out, int64_t capacity) {
     return need;
 }
 
+int64_t prcg_debug_interior_slices(const prcg_t* h) {
+    if (!h || !h->have_csr) return -1;
+    return h->sell ? h->nst_int : 0;
+}
+
 int prcg_window_source_ok(int64_t n_rows, int64_t n_ghost, int components, int64_t bytes_available) {
     if (n_rows < 0 || n_ghost < 0 || components < 1) return 0;
     return bytes_available >= (n_rows + n_ghost + (int64_t)kGatherPad) * components * (int64_t)sizeof(double) ? 1 : 0;

@@ -72,6 +72,8 @@ int pipe_spmm_and_reduce(prcg_t* h, int k, int grid_upd, bool profile) {
         LAUNCHCHK(h, eng_spmm2(h, h->sc, 1, in_ext, h->wu.d(), mask));
         if (profile) prof_end(h, h->ev_spmv, h->n_ev_spmv, on);
         HIPCHK(h, hipStreamWaitEvent(h->sc, h->e_red, 0));
+        // (nt_bnd counts CSR-adaptive tiles, whatever family runs: the row classes are shared by the three plans, so the sliced and the
+        //  window table have boundary units exactly when this one has; eng_spmm2 takes its own family's range from tile_range)
         if (h->nt_bnd > 0) LAUNCHCHK(h, eng_spmm2(h, h->sc, 2, in_ext, h->wu.d(), mask));
         return PRCG_OK;
     }

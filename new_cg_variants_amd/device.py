@@ -552,7 +552,9 @@ class DeviceCSR:
         boundary launch's (tiles[interior_tiles:]) and 'interior_grid' / 'interior_waves_per_block' the interior launch's
         (tiles[:interior_tiles], its partial rows first); both 0 when the last such launch ran over all the tiles.
         'sliced': the operator runs on sliced rows; 'slice_rows' (prcg_debug_slice_rows): then the row of every lane of
-        every slice in launch order, shape (slices, 64), -1 for an idle lane -- else shape (0, 64)."""
+        every slice in launch order (interior slices first), shape (slices, 64), -1 for an idle lane -- else shape (0, 64);
+        'interior_slices' (prcg_debug_interior_slices): slice_rows[:interior_slices] hold no row with a ghost column and are what
+        the interior launch of such a product runs on sliced rows ('interior_tiles' counts tiles, whatever runs); else 0."""
         need = -int(self._lib.prcg_debug_layout(self._h, L.ptr(np.zeros(1, dtype=np.int64)), 0))
         out = np.zeros(max(need, 10), dtype=np.int64)
         got = int(self._lib.prcg_debug_layout(self._h, L.ptr(out), out.size))
@@ -564,10 +566,13 @@ class DeviceCSR:
         rows = np.zeros(need, dtype=np.int32)
         if need and int(self._lib.prcg_debug_slice_rows(self._h, L.ptr(rows), rows.size)) != need:
             raise RuntimeError('prcg_debug_slice_rows failed')
+        nst_int = int(self._lib.prcg_debug_interior_slices(self._h))
+        if nst_int < 0 or 64 * nst_int > need:
+            raise RuntimeError('prcg_debug_interior_slices failed')
         return {'window': bool(out[0]), 'geometry': int(out[1]), 'rows_per_tile': int(out[2]), 'tiles': out[10:got].reshape(-1, 2).copy(),
                 'grid': int(out[4]), 'waves_per_block': int(out[5]), 'interior_tiles': int(out[6]), 'sweep_waves': int(out[7]) >> 8,
                 'interior_grid': int(out[8]), 'interior_waves_per_block': int(out[9]),
-                'sliced': need > 0, 'slice_rows': rows.reshape(-1, 64)}
+                'sliced': need > 0, 'slice_rows': rows.reshape(-1, 64), 'interior_slices': nst_int}
 
     def operator_bytes(self):
         """Bytes of the operator as the device streams it (prcg.h: prcg_operator_bytes)."""

@@ -43,7 +43,8 @@ SEVERAL RANKS (tests/test_trajectory_ranks.py): every rank sums ITS rows with it
 order, v = s[0]; v += s[r] -- ``RankSum``.  A rank's tree is one of the above built from that rank's layout(), or ``PeerLaunchTree``
 (the one-launch iteration over the direct peer exchange: one wave is the communication wave, the others' tiles shift by one slot, a
 few boundary tiles go to the communication wave) or ``TwoLaunchTree`` (a product with a dot epilogue run as an interior and a
-boundary launch whose partial rows lie end to end under one final tree).
+boundary launch whose partial rows lie end to end under one final tree).  On sliced rows and CSR-adaptive tiles
+(tests/test_trajectory_ranks_irregular.py) that product is ``TwoLaunchUnitTree``: UnitTree over each class of the unit table.
 
 ``Routed`` lets a schedule whose inner products come from different launches (Hestenes-Stiefel: nu from the update
 kernel, mu from the tile launch) plug into the oracle: the oracle calls ``dot`` in a fixed order per advance.
@@ -353,21 +354,53 @@ class RankSum:
         return self(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
 
 
+def tile_units(tiles):
+    """the units of CSR-adaptive tiles (process_tile) from layout()['tiles']: lane l of the tile's wave finishes rows rb + l,
+    rb + 64 + l, ... below re -- ceil(rows / 64) steps; a long-row tile is one row, finished by lane 0 after the wave has summed it"""
+    lane = np.arange(64)
+    units = []
+    for rb, re in np.asarray(tiles, dtype=np.int64):
+        rows = rb + 64 * np.arange(-(-(re - rb) // 64))[:, None] + lane[None, :]
+        units.append(np.where(rows < re, rows, -1))
+    return units
+
+
+def slice_units(slice_rows):
+    """the units of sliced rows (slice_row) from layout()['slice_rows']: lane l finishes ONE row per slice -- rb + l, or the row
+    the slice names for that lane; -1: an idle lane (a ragged, cut or padded slice)"""
+    return [r[None, :] for r in np.asarray(slice_rows, dtype=np.int64)]
+
+
+def _assert_rows_once(*launches):
+    """the launches together finish every row of one contiguous range exactly once; returns the range"""
+    covered = np.sort(np.concatenate([l.idx[l.idx >= 0] for l in launches]))
+    assert covered.size > 0 and np.array_equal(covered, np.arange(covered[0], covered[-1] + 1)), 'every row summed exactly once'
+    return int(covered[0]), int(covered[-1]) + 1
+
+
 class UnitTree:
     """The summation order of the inner products a launch of the sliced-row kernels (prcg_sell.hip: k_sell_win, k_sell_tiles)
     or of the CSR-adaptive tile kernel (prcg_kernels.hip: k_spmv_tiles) leaves, whatever its epilogue:
 
-      wave v of workgroup b takes UNITS (slices / tiles) xcd_remap(b, grid) * wpb + v, + grid * wpb, ... of the table, in
-      that order; one lane-private accumulator per inner product, starting at +0.0, adds the rows the lane finishes
+      wave v of workgroup b takes UNITS (slices / tiles) xcd_remap(b, grid) * wpb + v, + grid * wpb, ... of the launch's table,
+      in that order; one lane-private accumulator per inner product, starting at +0.0, adds the rows the lane finishes
       unit   : an ordered list of 64-lane row vectors, one per step, -1: the lane finishes no row in that step
-      wave   : xor butterfly       block : waves 0..wpb-1 in order (block_reduce_store)      final : the 256-thread tree
+      wave   : xor butterfly       block : waves 0..wpb-1 in order (block_reduce_store) -> ``partials``: one row per workgroup
+      final  : the 256-thread tree -> ``sum``
 
-    ``units``: a sequence of integer arrays of shape (steps, 64) -- steps may differ from unit to unit and may be 0."""
+    ``units``: a sequence of integer arrays of shape (steps, 64) -- steps may differ from unit to unit and may be 0.  A launch
+    over ONE CLASS of the table (an overlapped product's interior or boundary launch) is handed the table from its first unit on:
+    units [first, first + count), numbered from 0 within the launch.  Such a launch finishes only some of the rows (whole=False):
+    that every row is finished exactly once is then asserted by whoever combines the launches (TwoLaunchUnitTree)."""
 
-    def __init__(self, units, grid, wpb=4):
+    def __init__(self, units, grid, wpb=4, first=0, count=None, whole=True):
         grid, wpb = int(grid), int(wpb)
         assert grid > 0 and wpb > 0, (grid, wpb)
         units = [np.asarray(u, dtype=np.int64).reshape(-1, 64) for u in units]
+        first = int(first)
+        count = len(units) - first if count is None else int(count)
+        assert 0 <= first and 0 <= count and first + count <= len(units), (first, count, len(units))
+        units = units[first:first + count]
         W = grid * wpb
         waves = []
         for b in range(grid):
@@ -381,34 +414,26 @@ class UnitTree:
             idx[i, :w.shape[0]] = w
         self.idx = idx.reshape(grid, wpb, steps, 64)
         self.grid, self.wpb = grid, wpb
-        covered = np.sort(self.idx[self.idx >= 0])
-        assert covered.size > 0 and np.array_equal(covered, np.arange(covered[0], covered[-1] + 1)), 'every row summed exactly once'
-        self.rows = (int(covered[0]), int(covered[-1]) + 1)
+        self.rows = _assert_rows_once(self) if whole else None
 
     @classmethod
     def from_tiles(cls, layout):
-        """CSR-adaptive tiles (process_tile) from layout()['tiles']: lane l of the tile's wave finishes rows rb + l, rb + 64 + l,
-        ... below re -- ceil(rows / 64) steps; a long-row tile is one row, finished by lane 0 after the wave has summed it."""
+        """CSR-adaptive tiles (tile_units), one launch over the whole table"""
         assert not layout['window'] and not layout['sliced'] and layout['grid'] > 0, {k: v for k, v in layout.items() if np.ndim(v) == 0}
-        lane = np.arange(64)
-        units = []
-        for rb, re in np.asarray(layout['tiles'], dtype=np.int64):
-            rows = rb + 64 * np.arange(-(-(re - rb) // 64))[:, None] + lane[None, :]
-            units.append(np.where(rows < re, rows, -1))
-        return cls(units, layout['grid'], layout['waves_per_block'])
+        return cls(tile_units(layout['tiles']), layout['grid'], layout['waves_per_block'])
 
     @classmethod
     def from_slices(cls, layout):
-        """sliced rows (slice_row) from layout()['slice_rows']: lane l finishes ONE row per slice -- rb + l, or the row the
-        slice names for that lane; -1: an idle lane (a ragged, cut or padded slice)."""
+        """sliced rows (slice_units), one launch over the whole table"""
         assert layout['sliced'] and layout['grid'] > 0, {k: v for k, v in layout.items() if np.ndim(v) == 0}
-        return cls([r[None, :] for r in np.asarray(layout['slice_rows'], dtype=np.int64)], layout['grid'], layout['waves_per_block'])
+        return cls(slice_units(layout['slice_rows']), layout['grid'], layout['waves_per_block'])
 
     @classmethod
     def of(cls, layout):
         return cls.from_slices(layout) if layout['sliced'] else cls.from_tiles(layout)
 
-    def sum(self, prod):
+    def partials(self, prod):
+        """one value per workgroup, in workgroup order: the rows of the launch's partials buffer, before the final tree"""
         prod = np.asarray(prod, dtype=np.float64)
         ext = np.concatenate([prod, [0.0]])            # index -1 -> +0.0 (adding it changes nothing: acc starts at +0.0)
         acc = np.zeros(self.idx.shape[:2] + (64,))
@@ -418,7 +443,47 @@ class UnitTree:
         partial = waves[:, 0]
         for v in range(1, self.wpb):
             partial = partial + waves[:, v]
-        return _final_tree(partial)
+        return partial
+
+    def sum(self, prod):
+        return _final_tree(self.partials(prod))
+
+    def dot(self, a, b):
+        return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))
+
+
+class TwoLaunchUnitTree:
+    """TwoLaunchTree's sibling on sliced rows and CSR-adaptive tiles: a product with a dot epilogue as the two-kernel schedules
+    run it WITH A COMMUNICATOR (prcg_session.cpp: overlapped_spmv -> eng_spmv(which = 1), then (which = 2)).  The interior units
+    -- slices [0, 'interior_slices') of 'slice_rows' on sliced rows, tiles [0, 'interior_tiles') on CSR-adaptive tiles -- run on
+    'interior_grid' workgroups and leave partial rows [0, g1); the units with a ghost column, the rest of the table, run on 'grid'
+    workgroups and leave rows [g1, g1 + g2).  Each launch is handed ITS class's table: wave v of workgroup b takes units
+    xcd_remap(b, that launch's grid) * 4 + v, + 4 * that grid, ... counted from the class's first unit.  ONE 256-thread tree sums
+    the g1 + g2 rows, interior first.  A rank with one class empty ('interior_grid' == 0: no interior slice, or no unit that reads
+    a ghost row) launches the other class alone, on 'grid' workgroups: then this is UnitTree over that class."""
+
+    def __init__(self, layout):
+        assert not layout['window'] and layout['grid'] > 0, {k: v for k, v in layout.items() if np.ndim(v) == 0}
+        units = slice_units(layout['slice_rows']) if layout['sliced'] else tile_units(layout['tiles'])
+        n_int = int(layout['interior_slices'] if layout['sliced'] else layout['interior_tiles'])
+        g1, g2, wpb = int(layout['interior_grid']), int(layout['grid']), int(layout['waves_per_block'])
+        assert 0 <= n_int <= len(units) and len(units) > 0, (n_int, len(units))
+        if g1 == 0:
+            assert n_int in (0, len(units)), f'one launch, but {n_int} interior units of {len(units)}'
+            self.launches = [UnitTree(units, g2, wpb, whole=False)]
+        else:
+            assert 0 < n_int < len(units), f'two launches, but {n_int} interior units of {len(units)}'
+            self.launches = [UnitTree(units, g1, wpb, first=0, count=n_int, whole=False),
+                             UnitTree(units, g2, wpb, first=n_int, count=len(units) - n_int, whole=False)]
+        self.interior_units, self.units = n_int, len(units)
+        self.rows = _assert_rows_once(*self.launches)
+
+    def partials(self, prod):
+        """the g1 + g2 partial rows as they lie in the buffer: the interior launch's, then the boundary launch's"""
+        return np.concatenate([l.partials(prod) for l in self.launches])
+
+    def sum(self, prod):
+        return _final_tree(self.partials(prod))
 
     def dot(self, a, b):
         return self.sum(np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64))

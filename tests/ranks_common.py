@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE: N > 1 ranks on ONE GPU, the ranks threads of this process connected by tests/transport/libthreads_ccl.so
 (a stand-in for librccl.so that moves the collectives' bytes with device-to-device copies; RCCL itself refuses two ranks on one
 device).  Real inter-rank data: what rank r reads in its ghost rows was computed by the kernels of rank r +- 1.  Shared by
-tests/test_distributed.py (convergence-level assertions) and tests/test_trajectory_ranks.py (whole runs against the oracle)."""
+tests/test_distributed.py (convergence-level assertions) and, through tests/ranks_trajectory_common.py, tests/test_trajectory_ranks.py
+and tests/test_trajectory_ranks_irregular.py (whole runs against the oracle)."""
 import os
 import threading
 
@@ -11,7 +12,7 @@ from conftest import ROOT
 
 
 def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15, offsets=None, peer=False, chunks=None, x0=None,
-              vectors=(), scalars=False, read_start=False):
+              vectors=(), scalars=False, read_start=False, product=None):
     """Solve with `nranks` row blocks, one thread per rank, all on cuda:0: begin(max_iter = iters + 1), then prcg_iterate calls of
     `chunks` (default: one call of `iters`), sync (raises if a wave of a one-launch iteration timed out).
     knobs: one dict for all ranks or a list, one per rank.  peer: connect the ranks' exchange buffers (direct peer exchange; same
@@ -21,7 +22,8 @@ def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15
     after begin and after the run), 'hist', 'x', 'y' (the rank's rows of a probe product taken before the session), 'state'
     {k: the rank's rows of the state vectors named in `vectors`, read after each chunk}, and with scalars=True 'scalars'
     (get_scalars(k), k = 0..iters) and 'coef' (get_coefficients(k)[:2], k = 1..iters).  Asserts that the distributed product is
-    the global one bit for bit."""
+    the global one bit for bit -- SciPy's, or that of product(ranks): the operator as the ranks' kernels multiply it, built from what
+    they report (CSR-adaptive tiles sum a long row by a whole wave: device_order.LongRowOperator with the ranks' tile cap)."""
     from new_cg_variants_amd import _lib as L
     from new_cg_variants_amd import partition, problems
     from new_cg_variants_amd.device import DeviceCSR
@@ -87,7 +89,7 @@ def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15
     assert not errs, errs
     assert all(o is not None for o in out), 'a rank did not finish'
     y = np.concatenate([o['y'] for o in out])
-    assert np.array_equal(y, A @ (x_true * (1.0 + np.arange(n)))), 'distributed SpMV differs from the global product'
+    assert np.array_equal(y, (A if product is None else product(out)) @ (x_true * (1.0 + np.arange(n)))), 'distributed SpMV differs from the global product'
     return np.asarray(offsets, dtype=np.int64), out
 
 

@@ -11,15 +11,19 @@ tests/test_trajectory_stored_tilde.py is there to see.
 What tests/test_trajectory_ranks.py relies on (the last section): the trees of ONE RANK of a multi-rank session -- the one-launch
 iteration over the peer exchange (PeerLaunchTree: a communication wave, <= 8 boundary tiles relayed to it), a product in two
 launches (TwoLaunchTree) -- and the rank-order sum (RankSum); and that ranks added in another order, a slot added twice, a
-boundary tile's rows lost or a halo one iteration stale, at ONE iteration of a run, change the bits from there on."""
+boundary tile's rows lost or a halo one iteration stale, at ONE iteration of a run, change the bits from there on.
+
+What tests/test_trajectory_ranks_irregular.py relies on: the same product in two launches on sliced rows and CSR-adaptive tiles
+(TwoLaunchUnitTree: each launch numbers the units of ITS class from 0, the partial rows lie interior first) against a slow
+restatement, what it discriminates, and a ghost row of the PAIR array one iteration stale on one rank."""
 import math
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from device_order import (RELAY_TILES, LongRowOperator, OneLaunchTree, PeerLaunchTree, RankSum, Routed, TwoLaunchTree, UnitTree, device_sum,
-                          first_mismatch, long_row_sum, pair_dot, pair_sum, tile_cap_nnz, xcd_remap)
+from device_order import (RELAY_TILES, LongRowOperator, OneLaunchTree, PeerLaunchTree, RankSum, Routed, TwoLaunchTree, TwoLaunchUnitTree, UnitTree,
+                          device_sum, first_mismatch, long_row_sum, pair_dot, pair_sum, slice_units, tile_cap_nnz, tile_units, xcd_remap)
 from oracle import ne_oracle as orc
 
 
@@ -592,10 +596,13 @@ def test_rank_sum_starts_from_rank_zero():
 class StaleHaloOperator:
     """A as `nranks` row blocks multiply it, ONE product (call `at`, counted from 0) reading its GHOST columns -- the columns
     outside the rank's own rows -- from the vector of the call two before (the same product of the previous iteration: a halo one
-    iteration stale).  Every row is still SciPy's left-to-right sum: only the values of the ghost entries differ."""
+    iteration stale).  Every row is still SciPy's left-to-right sum: only the values of the ghost entries differ.  span=2: that
+    call and the next (both columns of a pair array: u = A s~ and w = A r~ of one pipelined iteration, each from ITS vector of the
+    iteration before); ranks: only these ranks read stale ghost rows (None: all)."""
 
-    def __init__(self, A, offsets, at):
+    def __init__(self, A, offsets, at, span=1, ranks=None):
         self.A, self.offsets, self.at, self.calls, self.seen, self.changed = A.tocsr(), [int(o) for o in offsets], at, 0, [], 0
+        self.span, self.ranks = span, ranks
         self.shape = A.shape
 
     def diagonal(self):
@@ -606,14 +613,16 @@ class StaleHaloOperator:
         self.seen = (self.seen + [v.copy()])[-3:]
         self.calls += 1
         y = self.A @ v
-        if self.calls - 1 != self.at:
+        if self.at < 0 or not self.at <= self.calls - 1 < self.at + self.span:
             return y
         stale = self.seen[0]
-        for lo, hi in zip(self.offsets, self.offsets[1:]):
+        for q, (lo, hi) in enumerate(zip(self.offsets, self.offsets[1:])):
+            if self.ranks is not None and q not in self.ranks:
+                continue
             mixed = stale.copy()
             mixed[lo:hi] = v[lo:hi]
             y[lo:hi] = self.A[lo:hi] @ mixed
-        self.changed = int(np.count_nonzero(y != self.A @ v))
+        self.changed += int(np.count_nonzero(y != self.A @ v))
         return y
 
 
@@ -645,7 +654,7 @@ class FaultyRankSum(RankSum):
         return np.float64(v + s[1]) if self.kind == 'twice' else np.float64(v)
 
 
-@pytest.mark.parametrize('kind,nranks', [('reversed', 4), ('twice', 2), ('tile_dropped', 2), ('stale_halo', 2)])
+@pytest.mark.parametrize('kind,nranks', [('reversed', 4), ('twice', 2), ('tile_dropped', 2), ('stale_halo', 2), ('stale_pair_halo', 2)])
 def test_one_wrong_exchange_at_one_iteration_of_a_multi_rank_run_shows_in_the_bits(kind, nranks):
     """What tests/test_trajectory_ranks.py is for, on the model's side: pipe_pr_pcg with Jacobi on a small band (the 5-point stencil
     on a 7 x 430 grid: n = 3010, 7-row halo, still converging at iteration 60 -- on the ex2b band Jacobi is the inverse to rounding,
@@ -656,7 +665,9 @@ def test_one_wrong_exchange_at_one_iteration_of_a_multi_rank_run_shows_in_the_bi
     stays in force from iteration 50 on: it must show by iteration 52 like the stale halo.  The
     trajectories agree bit for bit before iteration 50 and differ from 50 (a wrong sum: that iteration's inner products), or
     within the next two iterations (a stale halo reaches u of iteration 50, w and s of 51 and every inner product by 52), and
-    at every iteration after the first difference."""
+    at every iteration after the first difference.  'stale_pair_halo' (tests/test_trajectory_ranks_irregular.py: the two launches of
+    pipe_spmm_and_reduce read the ghost rows of the pair array (r~, s~) behind the rank's own pairs): BOTH products of iteration 50
+    read their ghost columns one iteration stale, on rank 1 only -- at most its 7 ghost rows' neighbours change, per product."""
     from new_cg_variants_amd import problems
     iters, k_bad = 90, 50
     A = problems.laplace_2d(7, 430)
@@ -685,9 +696,11 @@ def test_one_wrong_exchange_at_one_iteration_of_a_multi_rank_run_shows_in_the_bi
 
     clean = run(None)
     assert np.isfinite(clean).all() and clean.shape == (iters, 7) and (clean[:, [0, 1, 2, 3]] > 0).all()
-    if kind == 'stale_halo':
+    if kind in ('stale_halo', 'stale_pair_halo'):
+        pair = kind == 'stale_pair_halo'
         assert first_mismatch(run(None, StaleHaloOperator(A, offsets, -1)), clean) == -1       # the wrapper alone changes nothing
-        op = StaleHaloOperator(A, offsets, 3 + 2 * (k_bad - 1))          # three products at the start, then u = A s~, w = A r~ per iteration
+        # three products at the start, then u = A s~, w = A r~ per iteration
+        op = StaleHaloOperator(A, offsets, 3 + 2 * (k_bad - 1), span=2 if pair else 1, ranks=(1,) if pair else None)
         faulty = run(None, op)
         assert op.calls == 3 + 2 * (iters - 1) and 1 <= op.changed <= 14 * (nranks - 1), op.changed
         lo, hi = k_bad, k_bad + 2
@@ -698,3 +711,173 @@ def test_one_wrong_exchange_at_one_iteration_of_a_multi_rank_run_shows_in_the_bi
     assert lo <= first <= hi, (kind, first)
     differs = (faulty != clean).any(axis=1)
     assert differs[first:].all() and differs[-1] and not differs[:first].any()
+
+
+# ---- a product in two launches on sliced rows and CSR-adaptive tiles: TwoLaunchUnitTree (tests/test_trajectory_ranks_irregular.py) ----
+def rank_unit_layout(kind, n_int, n_bnd, g1, g2, rng):
+    """what DeviceCSR.layout() returns for one rank after an overlapped product on `kind` units (synthetic_units), n_int interior
+    ones on g1 workgroups in front of n_bnd boundary ones on g2; g1 == 0: one class is empty and the other ran alone on g2"""
+    lay = unit_layout(g2, **synthetic_units(kind, n_int + n_bnd, rng))
+    return dict(lay, interior_grid=g1, interior_waves_per_block=4 if g1 else 0, interior_tiles=0 if lay['sliced'] else n_int,
+                interior_slices=n_int if lay['sliced'] else 0)
+
+
+def slow_two_launch_sum(lay, prod):
+    """TwoLaunchUnitTree.sum restated with scalars and loops, nothing shared with tests/device_order.py: the XCD order as "the
+    workgroups of XCD 0 (b % 8 == 0) in launch order, then XCD 1's, ...", every lane's accumulator a Python float from +0.0"""
+    if lay['sliced']:
+        units = [[[int(r) for r in rows]] for rows in lay['slice_rows']]
+        n_int = lay['interior_slices']
+    else:
+        units = [[[rb + 64 * j + l if rb + 64 * j + l < re else -1 for l in range(64)] for j in range(-(-(re - rb) // 64))] for rb, re in lay['tiles'].tolist()]
+        n_int = lay['interior_tiles']
+    launches = [(0, len(units), lay['grid'])] if lay['interior_grid'] == 0 else [(0, n_int, lay['interior_grid']), (n_int, len(units), lay['grid'])]
+
+    def wave_sum(lanes):
+        for off in (32, 16, 8, 4, 2, 1):
+            lanes = [lanes[l] + lanes[l ^ off] for l in range(64)]
+        return lanes[0]
+    rows_of_partials = []
+    for first, end, grid in launches:
+        order = sorted(range(grid), key=lambda b: (b % 8, b // 8))
+        for b in range(grid):
+            waves = []
+            for v in range(4):
+                acc = [0.0] * 64
+                u = first + order.index(b) * 4 + v
+                while u < end:
+                    for step in units[u]:
+                        for l in range(64):
+                            if step[l] >= 0:
+                                acc[l] = acc[l] + float(prod[step[l]])
+                    u += grid * 4
+                waves.append(wave_sum(acc))
+            rows_of_partials.append(((waves[0] + waves[1]) + waves[2]) + waves[3])
+    threads = [0.0] * 256
+    for i, p in enumerate(rows_of_partials):
+        threads[i % 256] = threads[i % 256] + p                         # (thread t: partials t, t + 256, ... in that order)
+    w = [wave_sum(threads[64 * i:64 * i + 64]) for i in range(4)]
+    return ((w[0] + w[1]) + w[2]) + w[3]
+
+
+# (kind, interior units, boundary units, interior workgroups, boundary workgroups)
+TWO_LAUNCH_CASES = [
+    ('full', 34, 7, 9, 2),            # the shape of a 2-rank FEM block: a quarter of each class's units, the last slice ragged
+    ('cut', 35, 13, 9, 4),            # idle lanes; 35 units on 36 waves, 13 on 16: waves without a unit in both launches
+    ('named', 40, 24, 3, 2),          # named rows; 3 to 4 units per wave
+    ('tiles', 150, 33, 38, 9),        # ragged tiles, several rows per lane
+    ('tiles', 300, 290, 7, 70),       # more than 256 partial rows under the final tree: 77 + ... no -- 7 + 70; several rounds per wave
+    ('tiles', 1100, 70, 260, 18),     # 278 partial rows: thread t of the final tree adds rows t and t + 256, across the two launches
+    ('cut', 0, 14, 0, 4),             # no interior unit (g1 == 0): the boundary launch alone
+    ('tiles', 0, 361, 0, 91),
+    ('full', 41, 0, 0, 11),           # no boundary unit: the interior launch alone, reported as 'grid'
+]
+
+
+@pytest.mark.parametrize('kind,n_int,n_bnd,g1,g2', TWO_LAUNCH_CASES)
+def test_two_launch_unit_tree_against_a_slow_restatement(kind, n_int, n_bnd, g1, g2):
+    """Every row once over both launches (the constructor asserts it), the bits of the slow restatement on three vectors, a valid
+    summation (1e-13 * sum|terms| of the exactly rounded sum), exact on integers, np.float64 out; partials() are the g1 + g2 rows
+    and sum() their final tree; with one class empty the tree is UnitTree over the other class."""
+    rng = np.random.default_rng(1000 * n_int + 10 * n_bnd + g1)
+    lay = rank_unit_layout(kind, n_int, n_bnd, g1, g2, rng)
+    tree = TwoLaunchUnitTree(lay)
+    n = tree.rows[1]
+    assert tree.rows[0] == 0 and (tree.interior_units, tree.units) == (n_int, n_int + n_bnd)
+    assert len(tree.launches) == (2 if g1 else 1) and [l.grid for l in tree.launches] == ([g1, g2] if g1 else [g2])
+    for _ in range(3):
+        prod = rng.standard_normal(n) * np.exp(rng.uniform(-8, 8, n))
+        got = tree.sum(prod)
+        assert type(got) is np.float64 and got == slow_two_launch_sum(lay, prod)
+        assert abs(got - math.fsum(prod)) <= 1e-13 * math.fsum(np.abs(prod))
+        rows = tree.partials(prod)
+        assert rows.shape == (g1 + g2,) and np.array_equal(rows[:g1], tree.launches[0].partials(prod)[:g1 or None] if g1 else rows[:0])
+    a, b = rng.standard_normal(n), rng.standard_normal(n)
+    assert tree.dot(a, b) == tree.sum(a * b)
+    ints = rng.integers(-1000, 1000, n).astype(np.float64)
+    assert tree.sum(ints) == ints.sum()
+    if not g1:
+        one = UnitTree.of(lay)
+        assert np.array_equal(one.idx, tree.launches[0].idx) and one.sum(a) == tree.sum(a)
+
+
+def test_two_launch_unit_tree_refuses_layouts_that_are_no_two_launches():
+    rng = np.random.default_rng(8)
+    lay = rank_unit_layout('full', 20, 6, 5, 2, rng)
+    TwoLaunchUnitTree(lay)
+    with pytest.raises(AssertionError, match='two launches'):
+        TwoLaunchUnitTree(dict(lay, interior_slices=0))                # an interior launch ran, over no unit
+    with pytest.raises(AssertionError, match='one launch'):
+        TwoLaunchUnitTree(dict(lay, interior_grid=0))                  # one launch, yet both classes hold units
+    twice = lay['slice_rows'].copy()
+    twice[22] = twice[3]                                              # a boundary slice repeats an interior one's rows
+    with pytest.raises(AssertionError, match='exactly once'):
+        TwoLaunchUnitTree(dict(lay, slice_rows=twice))
+    with pytest.raises(AssertionError):
+        TwoLaunchUnitTree(dict(lay, window=True))
+    # a launch over one class does not finish every row, and says so only when asked to
+    units = [r[None, :] for r in lay['slice_rows']]
+    part = UnitTree(units, 2, 4, first=20, count=6, whole=False)
+    assert part.rows is None and int(part.idx[part.idx >= 0].min()) == 20 * 64
+    with pytest.raises(AssertionError, match='exactly once'):
+        UnitTree(units[:3] + units[4:], 2, 4)
+
+
+@pytest.mark.parametrize('kind', ['full', 'tiles'])
+def test_two_launch_unit_tree_discriminates(kind):
+    """What the device's order could differ in without losing a row -- each changes bits of the sum of a generic vector (three
+    vectors: at least one bit of any of the three sums): the boundary launch's partial rows laid BEFORE the interior launch's, one
+    launch over all the units, the classes cut one unit too early or too late, and both launches' workgroups remapped with the
+    summed grid instead of their own."""
+    rng = np.random.default_rng(77)
+    n_int, n_bnd, g1, g2 = 75, 22, 19, 6            # (neither grid a multiple of 8: the XCD order is no identity)
+    lay = rank_unit_layout(kind, n_int, n_bnd, g1, g2, rng)
+    tree = TwoLaunchUnitTree(lay)
+    n = tree.rows[1]
+    vecs = [rng.standard_normal(n) for _ in range(3)]
+    ref = [tree.sum(v) for v in vecs]
+    assert ref == [slow_two_launch_sum(lay, v) for v in vecs]
+    bound = [2e-13 * math.fsum(np.abs(v)) for v in vecs]
+
+    def differs(sums):
+        assert all(abs(s - r) <= b for s, r, b in zip(sums, ref, bound))          # (still a valid summation of the same rows)
+        return sums != ref
+    # boundary partials first
+    interior, boundary = tree.launches
+    assert differs([np.float64(first_tree(np.concatenate([boundary.partials(v), interior.partials(v)]))) for v in vecs])
+    # one launch over all the units, on a quarter of them as the start-up product runs
+    one = UnitTree.of(dict(lay, grid=-(-(n_int + n_bnd) // 4)))
+    assert differs([one.sum(v) for v in vecs])
+    # ... and on g1 + g2 workgroups
+    assert differs([UnitTree.of(dict(lay, grid=g1 + g2)).sum(v) for v in vecs])
+    # the cut one unit off, either way
+    key = 'interior_slices' if lay['sliced'] else 'interior_tiles'
+    for off in (-1, 1):
+        assert differs([TwoLaunchUnitTree(dict(lay, **{key: n_int + off})).sum(v) for v in vecs]), off
+    # xcd_remap with the summed grid: wave v of workgroup b of either launch starts at unit xcd_remap(b, g1 + g2) * 4 + v of its class
+    # (no permutation of the launch's own workgroups: rows are lost and taken twice -- the sum is no sum of these rows at all)
+    us = slice_units(lay['slice_rows']) if lay['sliced'] else tile_units(lay['tiles'])
+
+    def partials_remapped(first, count, grid, remap_grid, v_):
+        ext = np.concatenate([v_, [0.0]])
+        rows = []
+        for b in range(grid):
+            waves = []
+            for v in range(4):
+                acc = np.zeros(64)
+                for u in range(xcd_remap(b, remap_grid) * 4 + v, count, grid * 4):
+                    for step in us[first + u]:
+                        acc = acc + ext[step]
+                w = acc
+                for off in (32, 16, 8, 4, 2, 1):
+                    w = w + w[np.arange(64) ^ off]
+                waves.append(w[0])
+            rows.append(((waves[0] + waves[1]) + waves[2]) + waves[3])
+        return np.array(rows)
+    assert [first_tree(np.concatenate([partials_remapped(0, n_int, g1, g1, v), partials_remapped(n_int, n_bnd, g2, g2, v)])) for v in vecs] == ref
+    assert [first_tree(np.concatenate([partials_remapped(0, n_int, g1, g1 + g2, v), partials_remapped(n_int, n_bnd, g2, g1 + g2, v)])) for v in vecs] != ref
+
+
+def first_tree(partials):
+    from device_order import _final_tree
+    return _final_tree(np.asarray(partials, dtype=np.float64))
