@@ -11,6 +11,57 @@ import numpy as np
 from conftest import ROOT
 
 
+JOIN_TIMEOUT = 240           # seconds a caller waits for a rank thread
+GATHER_TIMEOUT = 120         # seconds a rank waits at a barrier of the object all-gather
+
+
+def transport_path():
+    path = os.path.join(ROOT, 'tests', 'transport', 'libthreads_ccl.so')
+    assert os.path.exists(path), 'build it with `make` (tests/transport/threads_ccl.hip)'
+    return path
+
+
+def new_unique_id(path):
+    """a communicator id of the transport at `path`: one per group of rank handles"""
+    from new_cg_variants_amd import _lib as L
+    uid = np.zeros(128, dtype=np.uint8)
+    L.check(None, L.lib().prcg_comm_unique_id(path.encode(), L.ptr(uid)))
+    return uid
+
+
+def object_gatherer(nranks, timeout=GATHER_TIMEOUT):
+    """all-gather of Python objects among the rank threads, which are named 'rank-<r>' (what torch.distributed.all_gather_object is
+    between processes)"""
+    box = {}
+    barrier = threading.Barrier(nranks)
+    seq = [0] * nranks
+
+    def gather_objects(obj):
+        r = int(threading.current_thread().name.split('-')[-1])
+        key = seq[r]
+        seq[r] += 1
+        box[(key, r)] = obj
+        barrier.wait(timeout=timeout)
+        res = [box[(key, q)] for q in range(nranks)]
+        barrier.wait(timeout=timeout)
+        return res
+    return gather_objects
+
+
+def open_rank(r, nranks, part, uid, path, knobs, peer, gather_objects):
+    """rank r's handle, on the thread 'rank-<r>': its row block `part` of partition.split_serial with a communicator over the
+    transport and its halo plan; knobs: one dict for all ranks or a list, one per rank; peer: the ranks' exchange buffers connected
+    (collective: every rank calls this)"""
+    from new_cg_variants_amd import partition
+    from new_cg_variants_amd.device import DeviceCSR
+    A_local, ghost_ids, halo = part
+    op = DeviceCSR(A_local, comm_init=(r, nranks, uid.tobytes(), path), halo=halo,
+                   knobs=knobs[r] if isinstance(knobs, list) else knobs)
+    if peer:
+        assert partition.connect_peer_exchange(op, r, gather_objects), 'peer exchange did not connect'
+    return op
+
+
 def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15, offsets=None, peer=False, chunks=None, x0=None,
               vectors=(), scalars=False, read_start=False, product=None):
     """Solve with `nranks` row blocks, one thread per rank, all on cuda:0: begin(max_iter = iters + 1), then prcg_iterate calls of
@@ -24,28 +75,21 @@ def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15
     (get_scalars(k), k = 0..iters) and 'coef' (get_coefficients(k)[:2], k = 1..iters).  Asserts that the distributed product is
     the global one bit for bit -- SciPy's, or that of product(ranks): the operator as the ranks' kernels multiply it, built from what
     they report (CSR-adaptive tiles sum a long row by a whole wave: device_order.LongRowOperator with the ranks' tile cap)."""
-    from new_cg_variants_amd import _lib as L
     from new_cg_variants_amd import partition, problems
-    from new_cg_variants_amd.device import DeviceCSR
-    path = os.path.join(ROOT, 'tests', 'transport', 'libthreads_ccl.so')
-    assert os.path.exists(path), 'build it with `make` (tests/transport/threads_ccl.hip)'
+    path = transport_path()
     n = A.shape[0]
     b, x0_ref, x_true = problems.reference_rhs(A, n)
     x0 = x0_ref if x0 is None else x0
     offsets, parts = partition.split_serial(A, nranks, offsets)
-    uid = np.zeros(128, dtype=np.uint8)
-    L.check(None, L.lib().prcg_comm_unique_id(path.encode(), L.ptr(uid)))
+    uid = new_unique_id(path)
+    gather_objects = object_gatherer(nranks)
     out = [None] * nranks
     errs = []
 
     def rank_main(r):
         try:
-            A_local, ghost_ids, halo = parts[r]
             lo, hi = int(offsets[r]), int(offsets[r + 1])
-            op = DeviceCSR(A_local, comm_init=(r, nranks, uid.tobytes(), path), halo=halo,
-                           knobs=knobs[r] if isinstance(knobs, list) else knobs)
-            if peer:
-                assert partition.connect_peer_exchange(op, r, gather_objects), 'peer exchange did not connect'
+            op = open_rank(r, nranks, parts[r], uid, path, knobs, peer, gather_objects)
             y = op.matvec(x_true[lo:hi] * (1.0 + np.arange(lo, hi)))[0]
             op.begin(variant, b[lo:hi], x0[lo:hi], iters + 1, x_true=x_true[lo:hi],
                      inv_diag=None if inv_diag is None else inv_diag[lo:hi], hist_mask=hist_mask)
@@ -66,26 +110,11 @@ def run_ranks(A, nranks, variant, iters, knobs=None, inv_diag=None, hist_mask=15
         except Exception as exc:           # noqa: BLE001 -- reported by the caller
             errs.append((r, repr(exc)))
 
-    # all-gather of Python objects among the rank threads (what torch.distributed.all_gather_object is between processes)
-    box = {}
-    barrier = threading.Barrier(nranks)
-    seq = [0] * nranks
-
-    def gather_objects(obj):
-        r = int(threading.current_thread().name.split('-')[-1])
-        key = seq[r]
-        seq[r] += 1
-        box[(key, r)] = obj
-        barrier.wait(timeout=120)
-        res = [box[(key, q)] for q in range(nranks)]
-        barrier.wait(timeout=120)
-        return res
-
     threads = [threading.Thread(target=rank_main, args=(r,), name=f'rank-{r}', daemon=True) for r in range(nranks)]
     for t in threads:
         t.start()
     for t in threads:
-        t.join(timeout=240)          # (daemon threads: a rank that never returns fails the test instead of hanging pytest)
+        t.join(timeout=JOIN_TIMEOUT)         # (daemon threads: a rank that never returns fails the test instead of hanging pytest)
     assert not errs, errs
     assert all(o is not None for o in out), 'a rank did not finish'
     y = np.concatenate([o['y'] for o in out])
